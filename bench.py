@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: x4 SR frames/s of the CVSR_V8 forward on synthetic JCT-VC ClassB-shape clips.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--height 270 --width 480] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--height 270 --width 480] [--dump-outputs DIR] [--full]
+                    [--no-cpu-baseline]
 
 A "step" is one forward of the hot path over one batch of clips already resident in HBM: 8 clips per GPU of
 7 x 1 x 272 x 480 luma (270 rows zero-padded to 272) + MV / residual / partition / unfiltered priors ->
@@ -11,10 +12,20 @@ a bare `python bench.py --gpus N` starts them itself, see `launch_ranks`); clips
 Rank 0 prints one JSON line.
 
 What is timed (`value`): K forwards of the DEFAULT path -- Gumbel noise drawn per call like the reference does
-(arch/SIDECVSR_our.py:2169), here inside the mask kernel -- with no per-launch instrumentation.  The per-kernel roofline
-numbers come from a second pass over the same K steps with one HIP-event pair per launch.  Parity (gated: the run fails
-above the 1e-3 bound) is checked on clip 0 of the timed batch against the CPU oracle, replaying the noise that forward
-drew; the same oracle run is the `cpu_baseline`.
+(arch/SIDECVSR_our.py:2169), here inside the mask kernel -- with no per-launch instrumentation.  The noise comes from torch's
+default generator, seeded once before the first forward, so a run's outputs are the same from run to run.
+
+A plain run does only what the headline needs: set-up, one first forward (weight packing, first allocations), W warm-up
+steps, the K timed steps, the outputs of the last timed step if --dump-outputs is given, and the JSON line.  Everything else
+runs with --full only: parity (gated: the run fails above the 1e-3 bound) on clip 0 of the timed batch against the CPU
+oracle, replaying the noise that forward drew -- the same oracle run is the `cpu_baseline` --, the per-kernel roofline
+numbers from a second pass over the same K steps with one HIP-event pair per launch (and --breakdown), the extra modes and
+the other configurations and operators (`other_configs`, `dcn_forward`, `cvsr_v7`, `streaming_b1`, `train_step`).
+
+--dump-outputs DIR writes what the last timed step returned (rank 0's), the HR frames and the L1 feature cache, as
+DIR/sr_frames.npy and DIR/l1_fea.npy in float32: whole if an array has at most DUMP_ELEMS elements, otherwise as a fixed
+sample of DUMP_ELEMS of its elements in row-major order (positions drawn once from a seeded generator, sorted, the same for
+every run of the same shape).
 """
 from __future__ import annotations
 
@@ -116,6 +127,25 @@ def flops_per_clip(H, W):
 
 
 PARITY_BOUND = 1e-3      # north_star: max-abs vs the fp32 reference path
+NOISE_SEED = 4100         # torch.manual_seed(NOISE_SEED + rank) before the first forward: the per-forward Philox keys of the run
+DUMP_ELEMS = 4 << 20      # --dump-outputs: arrays larger than this are written as a fixed sample of this many elements (16 MB each)
+DUMP_SEED = 20260         # the seed of the sample's positions
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy in float32: whole up to DUMP_ELEMS elements, else the elements at DUMP_ELEMS fixed
+    positions of the row-major order (numpy Generator(DUMP_SEED), drawn without replacement, sorted)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        n = t.numel()
+        if n > DUMP_ELEMS:
+            pos = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ELEMS, replace=False))
+            a = torch.take(t, torch.from_numpy(pos).to(t.device)).float().cpu().numpy()
+        else:
+            a = t.float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def launch_command(n: int, argv, port: int):
@@ -160,6 +190,12 @@ def parse_args(argv=None):
     ap.add_argument("--no-full-size-parity", action="store_true", help="N > 1: skip rank 0's clip-0 check at the timed size (every rank still checks c1)")
     ap.add_argument("--no-extra-modes", action="store_true", help="skip the extra measurements (bf16x3 mode, injected-noise path, DCN / V7 / streaming / training lines)")
     ap.add_argument("--process-group", action="store_true", help="N = 1: still initialise the process group (RCCL, world size 1) so that the barriers and the metric all_gather of the N > 1 path run over RCCL; automatic under torchrun")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the parity check against the CPU oracle and the "
+                                                         "cpu_baseline, the per-kernel roofline pass, the extra modes and the other configurations / "
+                                                         "operators (--no-parity, --no-cpu-baseline, --no-extra-modes, --no-full-size-parity and "
+                                                         "--breakdown act within it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned (rank 0's) as DIR/<name>.npy in float32 (fixed sample of large arrays)")
     return ap.parse_args(argv)
 
 
@@ -167,6 +203,10 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.breakdown and not args.full:
+        raise SystemExit("--breakdown needs --full (it is written from the per-launch event pass)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under torchrun: become the launcher.  Nothing above has initialised the GPU in this process.
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -226,6 +266,7 @@ def main():
     inp = make_inputs(B, Hp, Wp, 1002 + rank, pad_rows=Hp - args.height)
     d = {k: v.to(dev) for k, v in inp.items() if k != "gumbel_u"}
     injected = [u.to(dev) for u in inp["gumbel_u"]] if args.injected_noise else None
+    torch.manual_seed(NOISE_SEED + rank)                   # the Philox keys of every forward below: the same from run to run
 
     pre = None
     if args.streaming:
@@ -251,11 +292,11 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(nsteps):
-            o, _ = step(noise, eager)
+            res = step(noise, eager)
         if graph["cap"] is not None and not eager:
             graph["cap"].drain()              # the last step's range guard is settled inside the timed region
         barrier()
-        return time.perf_counter() - t0, o
+        return time.perf_counter() - t0, res
 
     # ---- parity against the CPU oracle, on the path that is timed.  N = 1: clip 0 of the timed batch at the timed size
     # (the oracle forward on one 272x480 clip is also the cpu_baseline measurement); N > 1: every rank checks the
@@ -265,7 +306,9 @@ def main():
     max_abs, psnr, cpu = float("nan"), float("nan"), None
     max_abs_full, ref_out_full, cap_full, pending_full = float("nan"), None, None, None
     parity_cfg = "skipped (--no-parity)"
-    if not args.no_parity:
+    if not args.full:
+        step()              # the first forward (weight packing, first allocations), untimed like the --full run's parity forward
+    elif not args.no_parity:
         full = not args.streaming and (world == 1 or (rank == 0 and not args.no_full_size_parity))
         if full:
             cap = []
@@ -301,28 +344,30 @@ def main():
             else:
                 parity_cfg = small + " -- small-config only (--no-full-size-parity)"
 
-    # ---- --launch graph: the forward of the timed configuration captured once (cdfo_amd/graph.py); a replay must BE the eager forward:
-    # both run once under the same generator seed and their images are compared bit for bit before anything is timed
+    # ---- --launch graph: the forward of the timed configuration captured once (cdfo_amd/graph.py); with --full a replay must BE the
+    # eager forward: both run once under the same generator seed and their images are compared bit for bit before anything is timed
     launch_info = {"mode": "eager"}
     if args.launch == "graph" and args.precision != "f32":
         try:
             with torch.no_grad():
                 cap_fwd = model.capture_pipelined(d["x"], d["mvs0"], d["mvs1"], d["pms"], d["rms"], d["ufs"], pre, gumbel_uniform=injected)
-            torch.manual_seed(4242 + rank)
-            e_out, _ = step(eager=True)
-            e_out = e_out.clone()
             graph["cap"] = cap_fwd
-            same = True
-            for _ in range(2):                                # both graphs of the pair
+            if args.full:
                 torch.manual_seed(4242 + rank)
-                g_out, _ = step()
-                cap_fwd.drain()
-                torch.cuda.synchronize()
-                same = same and bool(torch.equal(e_out, g_out))
-            del e_out, g_out
-            if not same:
-                raise SystemExit("bench.py: the replayed HIP graph and the eager forward differ under the same seed")
-            launch_info = {"mode": "hip_graph", "replay_equals_eager_bitwise": True, "range_guard_in_graph": bool(cap_fwd.guarded),
+                e_out, _ = step(eager=True)
+                e_out = e_out.clone()
+                same = True
+                for _ in range(2):                            # both graphs of the pair
+                    torch.manual_seed(4242 + rank)
+                    g_out, _ = step()
+                    cap_fwd.drain()
+                    torch.cuda.synchronize()
+                    same = same and bool(torch.equal(e_out, g_out))
+                del e_out, g_out
+                if not same:
+                    raise SystemExit("bench.py: the replayed HIP graph and the eager forward differ under the same seed")
+            launch_info = {"mode": "hip_graph", "replay_equals_eager_bitwise": True if args.full else None,
+                           "range_guard_in_graph": bool(cap_fwd.guarded),
                            "per_step": "operands copied into the buffers of one of two alternating graphs (cdfo_amd.graph.PipelinedForward), "
                                        "fresh Philox key, hipGraphLaunch, then the PREVIOUS step's fp16 range-guard probes are read back; "
                                        "the last step's inside the timed region"}
@@ -334,32 +379,37 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    elapsed, out = timed(args.steps)                      # the headline: no per-launch instrumentation
+    elapsed, (out, l1_fea) = timed(args.steps)            # the headline: no per-launch instrumentation
     range_info = (graph["cap"].last_range if graph["cap"] is not None and graph["cap"].guarded else getattr(model, "last_range", None))
-    if graph["cap"] is not None:                          # the same steps launched kernel by kernel, for the record
+    if args.dump_outputs and rank == 0:                  # the last timed step's results, final now that its range guard is settled
+        dump_outputs(args.dump_outputs, {"sr_frames": out, "l1_fea": l1_fea})
+    del l1_fea
+    elapsed_prof = float("nan")
+    if args.full and graph["cap"] is not None:            # the same steps launched kernel by kernel, for the record
         step(eager=True)
         elapsed_eager, _ = timed(args.steps, eager=True)
         launch_info["eager_ms_per_step"] = round(1e3 * elapsed_eager / args.steps, 3)
         launch_info["eager_frames_per_s"] = round(B * args.steps / elapsed_eager, 3)
 
-    # ---- second pass over the same steps with one HIP-event pair per launch: per-kernel durations for the roofline
-    nk = lib.cdfo_prof_kid_count()
-    cap_records = 4000 * max(1, args.steps)
-    _lib.check(lib.cdfo_prof_begin(cap_records), "cdfo_prof_begin")
-    elapsed_prof, _ = timed(args.steps, eager=True)       # (events are recorded around host launches: the eager path)
-    launches = (C.c_int * nk)()
-    ms = (C.c_double * nk)()
-    fl = (C.c_double * nk)()
-    by = (C.c_double * nk)()
-    nrec = lib.cdfo_prof_end(launches, ms, fl, by, nk)
-    if nrec < 0:
-        raise SystemExit(f"cdfo_prof_end failed: {nrec}")
-    if nrec >= cap_records:
-        raise SystemExit(f"the event profiler ran out of records ({nrec} >= {cap_records}): per-kernel numbers would be truncated")
+    if args.full:
+        # ---- second pass over the same steps with one HIP-event pair per launch: per-kernel durations for the roofline
+        nk = lib.cdfo_prof_kid_count()
+        cap_records = 4000 * max(1, args.steps)
+        _lib.check(lib.cdfo_prof_begin(cap_records), "cdfo_prof_begin")
+        elapsed_prof, _ = timed(args.steps, eager=True)   # (events are recorded around host launches: the eager path)
+        launches = (C.c_int * nk)()
+        ms = (C.c_double * nk)()
+        fl = (C.c_double * nk)()
+        by = (C.c_double * nk)()
+        nrec = lib.cdfo_prof_end(launches, ms, fl, by, nk)
+        if nrec < 0:
+            raise SystemExit(f"cdfo_prof_end failed: {nrec}")
+        if nrec >= cap_records:
+            raise SystemExit(f"the event profiler ran out of records ({nrec} >= {cap_records}): per-kernel numbers would be truncated")
 
-    # ---- extra measurements (N = 1 only, outside the headline): the fp32-grade mode and the injected-noise path
+    # ---- extra measurements (--full, N = 1 only, outside the headline): the fp32-grade mode and the injected-noise path
     extra = {}
-    if world == 1 and not args.no_extra_modes and not args.streaming:
+    if args.full and world == 1 and not args.no_extra_modes and not args.streaming:
         nst = max(2, min(args.steps, 5))
         if graph["cap"] is None and args.precision != "f32":
             # the same batch replayed from two alternating captured forwards (--launch graph's step), outside the headline
@@ -437,8 +487,8 @@ def main():
                            elapsed_prof, max_abs_full, float(local), *ident], dev if backend == "nccl" else None)
     t_max = allm[:, 0].max().item()
     # parity gate: a numerically broken build must not print a valid-looking line
-    parity_ok = args.no_parity or (all(math.isfinite(v) and v <= PARITY_BOUND for v in allm[:, 2].tolist())
-                                   and all(v != v or v <= PARITY_BOUND for v in allm[:, 5].tolist()))
+    parity_ok = not args.full or args.no_parity or (all(math.isfinite(v) and v <= PARITY_BOUND for v in allm[:, 2].tolist())
+                                                    and all(v != v or v <= PARITY_BOUND for v in allm[:, 5].tolist()))
     # one GPU per rank is what "n_gpus" claims: two ranks on one physical device (a wrong LOCAL_RANK / HIP_VISIBLE_DEVICES
     # mapping) would print a valid-looking scaling line.  Only the explicit gloo rehearsal may share devices.
     distinct = len({tuple(allm[r, 7:15].tolist()) for r in range(world)})
@@ -447,59 +497,60 @@ def main():
     if rank == 0:
         clips_total = B * world * args.steps
         value = clips_total / t_max
-        F = flops_per_clip(Hp, Wp)
-        dom = max(range(nk), key=lambda k: ms[k])
-        dom_avg_ms = ms[dom] / max(1, launches[dom])
-        achieved = (fl[dom] / max(1, launches[dom])) / (dom_avg_ms * 1e-3) / 1e12 if dom_avg_ms > 0 else 0.0
-        def fam(k):
-            name = KID_NAMES[k]
-            avg_ms = ms[k] / max(1, launches[k])
-            ach = (fl[k] / max(1, launches[k])) / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
-            if name in MFMA16:
-                symbol, passes = MFMA16[name]
-                peak = PEAK_TFLOPS[args.precision if passes is None else "fp16x2"]
-                passes = MFMA_PASSES[args.precision] if passes is None else passes
-            else:
-                symbol, passes, peak = name, 1, PEAK_TFLOPS["f32"]
-            return {"kernel": name, "kernel_symbol": symbol, "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s",
-                    "frac": round(ach / peak, 4), "mfma_passes_per_mac": passes,
-                    "algorithmic_flop_per_launch": round(fl[k] / max(1, launches[k]), 0),
-                    "launches_per_step": launches[k] // max(1, args.steps), "avg_launch_ms": round(avg_ms, 4),
-                    "share_of_gpu_time": round(ms[k] / max(1e-9, sum(ms)), 4)}
-        tr = load_traffic(args.precision)
-        tfam = tr.get("families", {})
-        traffic = (tfam.get(KID_NAMES[dom]) or {}).get("hbm_bytes_per_launch")
-        traffic_is_stale = traffic_stale(KID_NAMES[dom], (tfam.get(KID_NAMES[dom]) or {}).get("source_sha256")) if traffic else None
+        if args.full:
+            F = flops_per_clip(Hp, Wp)
+            dom = max(range(nk), key=lambda k: ms[k])
+            dom_avg_ms = ms[dom] / max(1, launches[dom])
+            achieved = (fl[dom] / max(1, launches[dom])) / (dom_avg_ms * 1e-3) / 1e12 if dom_avg_ms > 0 else 0.0
+            def fam(k):
+                name = KID_NAMES[k]
+                avg_ms = ms[k] / max(1, launches[k])
+                ach = (fl[k] / max(1, launches[k])) / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
+                if name in MFMA16:
+                    symbol, passes = MFMA16[name]
+                    peak = PEAK_TFLOPS[args.precision if passes is None else "fp16x2"]
+                    passes = MFMA_PASSES[args.precision] if passes is None else passes
+                else:
+                    symbol, passes, peak = name, 1, PEAK_TFLOPS["f32"]
+                return {"kernel": name, "kernel_symbol": symbol, "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s",
+                        "frac": round(ach / peak, 4), "mfma_passes_per_mac": passes,
+                        "algorithmic_flop_per_launch": round(fl[k] / max(1, launches[k]), 0),
+                        "launches_per_step": launches[k] // max(1, args.steps), "avg_launch_ms": round(avg_ms, 4),
+                        "share_of_gpu_time": round(ms[k] / max(1e-9, sum(ms)), 4)}
+            tr = load_traffic(args.precision)
+            tfam = tr.get("families", {})
+            traffic = (tfam.get(KID_NAMES[dom]) or {}).get("hbm_bytes_per_launch")
+            traffic_is_stale = traffic_stale(KID_NAMES[dom], (tfam.get(KID_NAMES[dom]) or {}).get("source_sha256")) if traffic else None
 
-        def hbm_fam(k):
-            name = KID_NAMES[k]
-            avg_ms = ms[k] / max(1, launches[k])
-            bpl = by[k] / max(1, launches[k])
-            gbs = bpl / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-            pmc = (tfam.get(name) or {}).get("hbm_bytes_per_launch")
-            return {"kernel": name, "kernel_symbols": HBM_FAMILIES.get(name, [name]), "bound": "hbm", "achieved": round(gbs, 1),
-                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
-                    "algorithmic_bytes_per_launch": round(bpl), "launches_per_step": launches[k] // max(1, args.steps),
-                    "avg_launch_ms": round(avg_ms, 4), "share_of_gpu_time": round(ms[k] / max(1e-9, sum(ms)), 4),
-                    "traffic": pmc, "traffic_ratio": (round(pmc / bpl, 3) if pmc and bpl else None),
-                    "traffic_stale": (traffic_stale(name, (tfam.get(name) or {}).get("source_sha256")) if pmc else None)}
-        hbm_rows = sorted((k for k in range(nk) if KID_NAMES[k] in HBM_FAMILIES and launches[k] and by[k] > 0), key=lambda k: -ms[k])[:6]
-        wf = F * B * args.steps / t_max / 1e12
-        roofline = {"bound": "mfma", **fam(dom), "traffic": traffic, "traffic_stale": traffic_is_stale,
-                    "whole_forward_tflops": round(wf, 2), "whole_forward_frac": round(wf / PEAK_TFLOPS[args.precision], 4),
-                    "measured_in": f"second pass over the same {args.steps} steps, launched eagerly, with one HIP-event pair per launch on the launch "
-                                   f"stream ({round(1e3 * allm[:, 4].max().item() / args.steps, 3)} ms per step with the events)",
-                    # the other matrix-core convolution kernels of the step, same definitions (not the headline entry)
-                    "other_mfma_kernels": [fam(k) for k in range(nk) if KID_NAMES[k] in MFMA16 and k != dom and launches[k]],
-                    # the step's largest HBM-bound kernel families, live HIP-event durations, in situ (the
-                    # neighbour phase runs two streams, so its families' durations overlap); `traffic` as for the headline entry
-                    "hbm_kernels": [hbm_fam(k) for k in hbm_rows],
-                    "traffic_source": ({"file": tr.get("file"), "profiles_commit": tr.get("commit"),
-                                        "note": "replayed from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this script "
-                                                "(tools/profile_run.sh) taken at profiles_commit, not measured in this run"}
-                                       if tr else None)}
-        if cpu is None and not args.no_cpu_baseline and world == 1:      # reported on rank 0 at N = 1 only
-            cpu = cpu_baseline_scaled(sd, Hp, Wp)       # (--no-parity / --streaming runs: bounded half-size sample)
+            def hbm_fam(k):
+                name = KID_NAMES[k]
+                avg_ms = ms[k] / max(1, launches[k])
+                bpl = by[k] / max(1, launches[k])
+                gbs = bpl / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+                pmc = (tfam.get(name) or {}).get("hbm_bytes_per_launch")
+                return {"kernel": name, "kernel_symbols": HBM_FAMILIES.get(name, [name]), "bound": "hbm", "achieved": round(gbs, 1),
+                        "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
+                        "algorithmic_bytes_per_launch": round(bpl), "launches_per_step": launches[k] // max(1, args.steps),
+                        "avg_launch_ms": round(avg_ms, 4), "share_of_gpu_time": round(ms[k] / max(1e-9, sum(ms)), 4),
+                        "traffic": pmc, "traffic_ratio": (round(pmc / bpl, 3) if pmc and bpl else None),
+                        "traffic_stale": (traffic_stale(name, (tfam.get(name) or {}).get("source_sha256")) if pmc else None)}
+            hbm_rows = sorted((k for k in range(nk) if KID_NAMES[k] in HBM_FAMILIES and launches[k] and by[k] > 0), key=lambda k: -ms[k])[:6]
+            wf = F * B * args.steps / t_max / 1e12
+            roofline = {"bound": "mfma", **fam(dom), "traffic": traffic, "traffic_stale": traffic_is_stale,
+                        "whole_forward_tflops": round(wf, 2), "whole_forward_frac": round(wf / PEAK_TFLOPS[args.precision], 4),
+                        "measured_in": f"second pass over the same {args.steps} steps, launched eagerly, with one HIP-event pair per launch on the launch "
+                                       f"stream ({round(1e3 * allm[:, 4].max().item() / args.steps, 3)} ms per step with the events)",
+                        # the other matrix-core convolution kernels of the step, same definitions (not the headline entry)
+                        "other_mfma_kernels": [fam(k) for k in range(nk) if KID_NAMES[k] in MFMA16 and k != dom and launches[k]],
+                        # the step's largest HBM-bound kernel families, live HIP-event durations, in situ (the
+                        # neighbour phase runs two streams, so its families' durations overlap); `traffic` as for the headline entry
+                        "hbm_kernels": [hbm_fam(k) for k in hbm_rows],
+                        "traffic_source": ({"file": tr.get("file"), "profiles_commit": tr.get("commit"),
+                                            "note": "replayed from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this script "
+                                                    "(tools/profile_run.sh) taken at profiles_commit, not measured in this run"}
+                                           if tr else None)}
+            if cpu is None and not args.no_cpu_baseline and world == 1:      # reported on rank 0 at N = 1 only
+                cpu = cpu_baseline_scaled(sd, Hp, Wp)       # (--no-parity / --streaming runs: bounded half-size sample)
         res = {
             "metric": "x4 SR frames/sec, 7-frame 270x480->1080p", "value": round(value, 4), "unit": "frames/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * t_max / args.steps, 3),
@@ -513,17 +564,18 @@ def main():
                        "clips_per_gpu": B, "lr_padded": [Hp, Wp], "parallelism": f"batch-shard x{world}",
                        "weights": "random init (seed 0)", "launch": launch_info["mode"]},
             "launch": launch_info,
-            "parity": {"config": parity_cfg, "max_abs": max_abs, "psnr_y_db": psnr, "bound": PARITY_BOUND,
-                       "verified": bool(parity_ok and not args.no_parity),
-                       "per_rank_max_abs": [float(v) for v in allm[:, 2]],
-                       "full_size_max_abs": (None if max_abs_full != max_abs_full else max_abs_full)},
             "world": world, "backend": (dist.get_backend() if use_pg else None),
             "ranks": [{"rank": r, "ms_per_step": round(1e3 * allm[r, 0].item() / args.steps, 3), "local_device": int(allm[r, 6].item()),
                        "device": format_identity(allm[r, 7:15].tolist())} for r in range(world)],
-            "distinct_devices": distinct,
-            "roofline": roofline, "cpu_baseline": cpu, "fp16_range_guard": range_info, **extra,
+            "distinct_devices": distinct, "fp16_range_guard": range_info,
         }
-        if world == 1 and not args.no_parity and not args.no_extra_modes:
+        if args.full:
+            res.update({"parity": {"config": parity_cfg, "max_abs": max_abs, "psnr_y_db": psnr, "bound": PARITY_BOUND,
+                                   "verified": bool(parity_ok and not args.no_parity),
+                                   "per_rank_max_abs": [float(v) for v in allm[:, 2]],
+                                   "full_size_max_abs": (None if max_abs_full != max_abs_full else max_abs_full)},
+                        "roofline": roofline, "cpu_baseline": cpu, **extra})
+        if args.full and world == 1 and not args.no_parity and not args.no_extra_modes:
             # the path's other operator row, outside the timed region: the fused DCNv2 forward at the
             # alignment module's shape against its HBM roofline (same definitions as tools/bench_dcn.py)
             # BASELINE configs 2 and 5 (the single-GPU share of c5), outside the timed region
@@ -539,7 +591,7 @@ def main():
             res["streaming_b1"] = streaming_b1_line(dev, args.height, args.width)
             res["train_step"] = train_step_line(dev)
         print(json.dumps(res))
-        if args.breakdown:
+        if args.full and args.breakdown:
             with open(args.breakdown, "w") as f:
                 tot = sum(ms)
                 f.write(f"# HIP-event timing per kernel family, {args.steps} steps, B={B}, {Hp}x{Wp}; wall {t_max*1e3:.1f} ms\n")

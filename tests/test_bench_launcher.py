@@ -30,6 +30,37 @@ def test_args_plumbing():
     # the driver reads these keys from the default line: they must be wired into main()
     src = open(bench.__file__).read()
     assert 'res["streaming_b1"] = streaming_b1_line(' in src and 'res["train_step"] = train_step_line(' in src
+    assert not d.full and d.dump_outputs == ""                                # a plain run: the headline only, nothing written
+    a = bench.parse_args(["--full", "--dump-outputs", "outs"])
+    assert a.full and a.dump_outputs == "outs"
+
+
+def test_breakdown_needs_the_full_run(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--breakdown", "b.txt"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert "--full" in str(e.value.code)
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files, an array whole up to DUMP_ELEMS elements, else the same seeded positions of its row-major
+    order every time (also for a non-contiguous view, like the channels-last L1 feature cache); the default shape's two arrays
+    stay within 64 MB."""
+    import numpy as np
+    import torch
+    assert 2 * bench.DUMP_ELEMS * 4 <= 64 << 20
+    monkeypatch.setattr(bench, "DUMP_ELEMS", 1000)
+    small = torch.arange(12, dtype=torch.float32).reshape(3, 4)
+    big = torch.randn(2, 30, 40, generator=torch.Generator().manual_seed(1), dtype=torch.float64).permute(0, 2, 1)
+    bench.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big})
+    bench.dump_outputs(str(tmp_path / "b"), {"big": big})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.numpy())
+    b = np.load(tmp_path / "a" / "big.npy")
+    pos = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(big.numel(), 1000, replace=False))
+    assert b.dtype == np.float32 and b.shape == (1000,) and len(np.unique(pos)) == 1000
+    assert np.array_equal(b, big.contiguous().numpy().reshape(-1)[pos].astype(np.float32))
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))
 
 
 def test_bare_multi_gpu_invocation_becomes_the_launcher(monkeypatch):
@@ -63,7 +94,7 @@ def test_four_rank_rehearsal_over_gloo():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--batch", "1", "--steps", "1", "--warmup", "1",
-           "--height", "64", "--width", "64", "--no-extra-modes", "--no-cpu-baseline", "--no-full-size-parity"]
+           "--height", "64", "--width", "64", "--full", "--no-extra-modes", "--no-cpu-baseline", "--no-full-size-parity"]
     rc, out, err = clean_process_run(cmd, env=env, cwd=ROOT, timeout=900)
     assert rc == 0, (rc, out[-2000:], err[-4000:])
     res = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
@@ -84,7 +115,7 @@ def test_two_rank_bench_line_reports_every_rank():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "2", "--steps", "2", "--warmup", "1",
-           "--height", "64", "--width", "96", "--no-extra-modes", "--no-cpu-baseline"]
+           "--height", "64", "--width", "96", "--full", "--no-extra-modes", "--no-cpu-baseline"]
     rc, out, err = clean_process_run(cmd, env=env, cwd=ROOT, timeout=900)
     assert rc == 0, (rc, out[-2000:], err[-4000:])
     line = [ln for ln in out.splitlines() if ln.startswith("{")][-1]
@@ -98,3 +129,32 @@ def test_two_rank_bench_line_reports_every_rank():
     par = res["parity"]
     assert par["verified"] and len(par["per_rank_max_abs"]) == 2 and all(v <= 1e-3 for v in par["per_rank_max_abs"])
     assert par["full_size_max_abs"] is not None and par["full_size_max_abs"] <= 1e-3
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_repeatable_outputs(tmp_path):
+    """A plain run (no --full): the headline keys, `steps` timed steps, none of the --full measurements; two runs with the same
+    arguments dump the same outputs of their last timed step (the HR frames whole, the L1 feature cache as a fixed sample)."""
+    import json
+    import numpy as np
+    from conftest import clean_process_run
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "CDFO_BENCH_BACKEND"):
+        env.pop(k, None)
+    dumps = []
+    for i in range(2):
+        out_dir = str(tmp_path / f"run{i}")
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "2", "--steps", "3", "--warmup", "1",
+               "--height", "64", "--width", "96", "--dump-outputs", out_dir]
+        rc, out, err = clean_process_run(cmd, env=env, cwd=ROOT, timeout=600)
+        assert rc == 0, (rc, out[-2000:], err[-4000:])
+        res = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
+        assert res["unit"] == "frames/s" and res["higher_is_better"] is True and res["metric"] and res["dtype"]
+        assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0
+        assert abs(res["value"] - 2 * 1e3 / res["ms_per_step"]) < 1e-2 * res["value"]
+        assert not {"parity", "roofline", "cpu_baseline", "other_configs", "train_step"} & set(res)
+        sr, l1 = np.load(os.path.join(out_dir, "sr_frames.npy")), np.load(os.path.join(out_dir, "l1_fea.npy"))
+        assert sr.dtype == np.float32 and sr.size == 2 * 256 * 384 and np.isfinite(sr).all()
+        assert l1.dtype == np.float32 and l1.shape == (4 << 20,) and np.isfinite(l1).all()      # 2*7 x 64 x 64 x 96 > 4 Mi: sampled
+        dumps.append((sr, l1))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])

@@ -49,7 +49,7 @@ def test_bench_under_torchrun_with_one_rank_runs_over_rccl():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "2", "--steps", "2",
-           "--warmup", "1", "--height", "64", "--width", "96", "--no-extra-modes", "--no-cpu-baseline"]
+           "--warmup", "1", "--height", "64", "--width", "96", "--full", "--no-extra-modes", "--no-cpu-baseline"]
     rc, out, err = clean_process_run(cmd, env=env, cwd=ROOT, timeout=600)
     assert rc == 0, (rc, out[-2000:], err[-4000:])
     res = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
