@@ -13,9 +13,10 @@ What makes a capture of THIS model correct (the pieces were built for ``Streamin
 * the fp16 range guard: ``capture`` runs ONE eager, guarded forward on the example inputs first and refuses to capture a workload
   whose activations leave the fp16 window (use ``precision="bf16x3"``).  Round 5: the two probes of the guard (trunk input, trunk
   output) are graph nodes too -- zeroed, filled by the probe kernels, copied to pinned host memory behind the last kernel -- and
-  ``replay()`` reads them back: a replay on operands that leave the window is repeated eagerly in bf16x3 INTO the graph's output
-  buffers, exactly what the eager forward does.  ``replay(sync=False)`` returns without waiting (pipelined callers); the check
-  then runs at the start of the next replay, in ``finish_range_guard()`` or when ``last_range`` is read;
+  ``replay()`` reads them back and decides as the eager forward does (``CVSR_V8._range_verdict``): a replay on operands that leave
+  the window is repeated eagerly in bf16x3 INTO the graph's output buffers.  ``replay(sync=False)`` returns without waiting
+  (pipelined callers); the check then runs at the start of the next replay, in ``finish_range_guard()`` or when ``last_range``
+  is read -- the one place where the guard is settled after the call returns (the eager forward always settles it first);
 * the caller sees graph-owned buffers: ``inputs`` (write the next batch there, or pass tensors to ``__call__`` and they are
   copied in) and the returned ``(out, L1_fea)``, which the NEXT replay overwrites -- ``clone()`` what must outlive it.
 """
@@ -129,16 +130,12 @@ class CapturedForward:
             return
         self._pending = False
         self._ev.synchronize()
-        h = self._probe_host
-        amax = h[0:1].view(torch.float32).item()
-        nonfinite = bool(h[1].item()) or bool(h[3].item())
         m = self.model
-        self.last_range_seen = {"trunk_input_amax": amax, "nonfinite": nonfinite, "fallback": False}
-        lo, hi = m.FP16_WINDOW
-        if not nonfinite and (amax == 0.0 or lo <= amax <= hi):
+        self.last_range_seen = m._range_verdict(self._probe_host)
+        if not self.last_range_seen["fallback"]:
             return
         ins = self.inputs
-        m._last_range = self.last_range_seen
+        m.last_range = self.last_range_seen
         args = (ins[0], ins[1], ins[2], ins[3], ins[4], ins[5], ins[6], None if self._nnoise == 0 else ins[7:],
                 self._seed if self._seed is not None else 0)
         with torch.cuda.device(self.dev):

@@ -111,7 +111,6 @@ def test_captured_forward_carries_the_fp16_range_guard():
         assert torch.equal(got0, want0)
         with pytest.warns(UserWarning, match="fp16 range"):
             want, want_l1 = m(xs, *rest, gumbel_uniform=n)
-            m.finish_range_guard()
         assert m.last_range["fallback"], f"scenario drifted: {m.last_range}"
         want, want_l1 = want.clone(), want_l1.clone()
         m._warned_range = False
@@ -151,7 +150,6 @@ def test_pipelined_forward_settles_the_previous_forward_after_launching_the_next
             warnings.simplefilter("ignore")
             for x, r, nn in seq:
                 o, l1 = m(x, *r, gumbel_uniform=nn)
-                m.finish_range_guard()
                 want.append((o.clone(), l1.clone(), bool(m.last_range["fallback"])))
         assert [w[2] for w in want] == [False, True, False, False, True], "scenario drifted"
         m._warned_range = False

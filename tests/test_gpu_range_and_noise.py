@@ -73,12 +73,13 @@ def test_fp16_range_guard(log2s):
         assert not (bad <= 1e-5)       # NaN / inf / visibly wrong: the scaling really leaves fp16's range
 
 
-def test_fp16_range_guard_deferred_result_check():
-    """Round 5: the result's non-finite probe is read at the start of the NEXT forward (or by finish_range_guard / last_range), not
-    behind a host sync at the end of this one.  Scenario the trunk-input window cannot see: ONE Block_ body re-parametrised by 2^24
-    (body.0 weight and bias x 2^24, body.2 weight x 2^-24: the same function, LeakyReLU is positively homogeneous) -- its fp16
-    weights and 256-channel fp16 intermediate overflow while max |trunk input| stays in the window.  The forward returns garbage (the trunk's output is non-finite; the up-sampler's tail turns that
-    into finite values, which is why the guard probes the trunk and not the image); settling the guard must warn, recompute in bf16x3 INTO the returned tensors and report the fallback; the next forwards are guarded the same way."""
+def test_fp16_range_guard_catches_a_nonfinite_trunk_result_before_returning():
+    """Scenario the trunk-input window cannot see: ONE Block_ body re-parametrised by 2^24 (body.0 weight and bias x 2^24, body.2
+    weight x 2^-24: the same function, LeakyReLU is positively homogeneous) -- its fp16 weights and 256-channel fp16 intermediate
+    overflow while max |trunk input| stays in the window.  Unguarded, the forward returns garbage (the trunk's output is
+    non-finite; the up-sampler's tail turns that into finite values, which is why the guard probes the trunk and not the image).
+    The forward itself must warn, recompute in bf16x3 and return the repaired result: no settle call; every later forward is
+    guarded the same way, and range_guard = "sync" (a truthy value) is the same guard."""
     from arch.SIDECVSR_our import CVSR_V8
     from oracle.cvsr_v8_ref import cvsr_v8_forward, make_inputs, make_state_dict
     sd = make_state_dict(3)
@@ -95,26 +96,17 @@ def test_fp16_range_guard_deferred_result_check():
     m = m.cuda().eval()
     d = {k: v.cuda() for k, v in inp.items() if k != "gumbel_u"}
     noise = [u.cuda() for u in inp["gumbel_u"]]
-    with torch.no_grad():
-        out, L1 = m(d["x"], d["mvs0"], d["mvs1"], d["pms"], d["rms"], d["ufs"], gumbel_uniform=noise)
-    assert m.__dict__.get("_pending_guard") is not None                     # the trunk-input window saw nothing: the result check is pending
-    with pytest.warns(UserWarning, match="fp16 range"):
-        m.finish_range_guard()
-    torch.cuda.synchronize()
-    assert m.last_range["fallback"] and m.last_range["nonfinite"]
-    err, err_l1 = (out.cpu() - ref).abs().max().item(), (L1.cpu() - L1_ref).abs().max().item()
-    print(f"deferred guard: repaired in place, out {err:.2e} L1_fea {err_l1:.2e}; {m.last_range}")
-    assert err <= TOL and err_l1 <= TOL
-    # the second forward settles nothing (no pending check) and is itself caught when ITS check is settled through last_range
-    with torch.no_grad():
-        out2, _ = m(d["x"], d["mvs0"], d["mvs1"], d["pms"], d["rms"], d["ufs"], gumbel_uniform=noise)
-    assert m.last_range["fallback"]
-    assert (out2.cpu() - ref).abs().max().item() <= TOL
-    # range_guard = "sync": the check-before-return behaviour of rounds 2-4
-    m.range_guard = "sync"
-    with torch.no_grad():
-        out3, _ = m(d["x"], d["mvs0"], d["mvs1"], d["pms"], d["rms"], d["ufs"], gumbel_uniform=noise)
-    assert m.__dict__.get("_pending_guard") is None and (out3.cpu() - ref).abs().max().item() <= TOL
+    lo, hi = CVSR_V8.FP16_WINDOW
+    for k, guard in enumerate((True, True, "sync")):
+        m.range_guard, m.last_range, m._warned_range = guard, None, False
+        with torch.no_grad(), pytest.warns(UserWarning, match="fp16 range"):
+            out, L1 = m(d["x"], d["mvs0"], d["mvs1"], d["pms"], d["rms"], d["ufs"], gumbel_uniform=noise)
+        lr = m.last_range
+        err, err_l1 = (out.cpu() - ref).abs().max().item(), (L1.cpu() - L1_ref).abs().max().item()
+        print(f"forward {k} (range_guard={guard!r}): out {err:.2e} L1_fea {err_l1:.2e}; {lr}")
+        assert lr["fallback"] and lr["nonfinite"]
+        assert lo <= lr["trunk_input_amax"] <= hi, f"scenario drifted: {lr}"      # the trunk-OUTPUT probe is what caught it
+        assert err <= TOL and err_l1 <= TOL
 
 
 class _nullcontext:
