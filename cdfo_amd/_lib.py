@@ -13,8 +13,10 @@ import os
 # process and every launch fails with hipErrorNoDevice.)
 import torch  # noqa: F401,E402
 
+from . import switches  # noqa: E402
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("CDFO_LIB_PATH") or os.path.join(_HERE, "lib", "libcdfo_hip.so")   # (env: developer A/B builds)
+LIB_PATH = switches.get("CDFO_LIB_PATH") or os.path.join(_HERE, "lib", "libcdfo_hip.so")   # (developer A/B builds)
 
 _lib = None
 
@@ -56,6 +58,7 @@ def lib() -> C.CDLL:
             raise CdfoError(
                 f"{LIB_PATH} is missing: the HIP extension has not been built "
                 "(run `python -m cdfo_amd.build`).  There is no CPU fallback for the product path.")
+        switches.check_hip_environment()      # a malformed switch of the library's own is an error here, not a silent default
         _lib = C.CDLL(LIB_PATH)
         for name, (restype, argtypes) in header_prototypes().items():
             fn = getattr(_lib, name)          # AttributeError here = header/library mismatch: fail loudly

@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence
 import torch
 from torch.autograd import Function
 
-from . import _lib
+from . import _lib, switches
 from . import kernels as K
 from ._lib import check
 from .kernels import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, PackedConv, _stream, _vp
@@ -39,8 +39,7 @@ F32 = K.PREC_F32
 #   PREC_F32 (CDFO_TRAIN_EXACT=1 in the environment, or `autograd.CONV_PREC = kernels.PREC_F32`): exact-fp32 MFMA everywhere
 #     (median 3e-7 - 1e-6, forward <= 1e-5), at 1/16 of the 16-bit matrix rate: 425 ms instead of 195 ms per step at 20 x 64 x 64.
 #   tests/test_gpu_train.py gates BOTH modes, each with its own tolerances.
-import os as _os
-CONV_PREC = K.PREC_F32 if _os.environ.get("CDFO_TRAIN_EXACT", "0") not in ("", "0") else K.PREC_BF16X3
+CONV_PREC = K.PREC_F32 if switches.get("CDFO_TRAIN_EXACT") else K.PREC_BF16X3
 
 
 def conv_precision_name() -> str:

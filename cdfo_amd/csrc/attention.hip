@@ -8,7 +8,6 @@
 //   seq_attn    : softmax(Q Q^T) V over a row, a column or an 8x8 window, one query per lane, keys streamed through
 //                 wave-uniform (scalar) loads, online softmax in registers.
 #include "common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -544,7 +543,7 @@ int seq_attn_launch(const float* q, int ldq, const float* v, int ldv, float* out
   const int ntq = cdiv(L, 32), nb = cdiv(ntq, NW), tpb = cdiv(ntq, nb);
   const long long nseq = MODE == 0 ? (long long)B * H : (MODE == 1 ? (long long)B * W : (long long)B * (H / 8) * (W / 8));
   if (nseq * nb >= (1ll << 31)) return CDFO_EINVAL;
-  static const int xcd_map = []() { const char* e = getenv("CDFO_ATTN_XCD"); return e ? atoi(e) : 1; }();   // developer A/B switch
+  static const int xcd_map = cdfo_switch("CDFO_ATTN_XCD", 1);   // developer A/B switch
   hipLaunchKernelGGL((seq_attn_mfma_kernel<MODE, NW, PV1>), dim3((unsigned)(nseq * nb)), dim3(NW * 64), LDSB, st, q, ldq, v, ldv,
                      out, ldo, B, H, W, nb, tpb, (nb > 1 && xcd_map) ? 1 : 0);
   return 0;
@@ -621,7 +620,7 @@ extern "C" int cdfo_seq_attn(const float* q, int ldq, const float* v, int ldv, f
     // it waits for: the same products over transposed tensors (contiguous rows of 272 keys) took 1.50 ms.
     const int L = mode == 0 ? W : H;
     const int ntq = cdiv(L, 32);
-    static const int force_nw = getenv("CDFO_ATTN_NW") ? atoi(getenv("CDFO_ATTN_NW")) : 0;     // developer switch (4 / 8)
+    static const int force_nw = cdfo_switch("CDFO_ATTN_NW", 0);     // developer switch (4 / 8)
     const bool wide = force_nw ? force_nw == 8
                                : L > 128 && (double)ntq / (cdiv(ntq, 8) * 8) >= (double)ntq / (cdiv(ntq, 4) * 4) - 0.1;
     int rc;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "../../include/cdfo_hip.h"
 #include "prof.h"
 
@@ -15,6 +16,13 @@ typedef short bf16x4 __attribute__((ext_vector_type(4)));
     hipError_t e__ = hipGetLastError();             \
     if (e__ != hipSuccess) return (int)e__;         \
   } while (0)
+
+// Developer switches: the one reader of the environment in this library.  Every name is a row of cdfo_amd/switches.py (layer
+// "hip"); unset -> dflt, else atoi ("0" off / "1" on).  Call sites keep the value in a `static const`: read once per process.
+static inline int cdfo_switch(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
 
 // Per-device host-side caches.  One process normally drives one GPU, but a caller may hold models on several devices:
 // everything cached on the host (CU count, "this kernel's LDS attribute is set") is keyed by the CURRENT device ordinal

@@ -12,7 +12,6 @@
 // pixel-shuffle store); every source must be a multiple of 64 channels wide.  Replaces the 1x1 convolutions of the
 // CVSR_V8 path (qkv, project_out folded, input_conv, fuse, fusion_out, down.0 / up.0, tsa_fusion, upconv1/2).
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -308,8 +307,8 @@ extern "C" int cdfo_conv1x1_bf16x3(const cdfo_conv_args* pa, void* stream) {
     return cdfo_layernorm64_cp16hl(a.out, a.ldo, a.ln_gamma, a.ln_beta, a.B, P, a.out2_cp16, stream);
   }
   {
-    static const bool use_stream = [] { const char* e = getenv("CDFO_CONV1X1_STREAM"); return !(e && e[0] == '0'); }();   // developer A/B switch
-    static const bool taps_stream = [] { const char* e = getenv("CDFO_TAPS_STREAM"); return !(e && e[0] == '0'); }();   // developer A/B switch
+    static const bool use_stream = cdfo_switch("CDFO_CONV1X1_STREAM", 1) != 0;   // developer A/B switch
+    static const bool taps_stream = cdfo_switch("CDFO_TAPS_STREAM", 1) != 0;   // developer A/B switch
     if (use_stream && (!taps || taps_stream)) {
       const int r = cdfo_conv1x1_stream_try(a, st);
       if (r == 1) return 0;

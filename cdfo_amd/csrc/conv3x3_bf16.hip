@@ -447,7 +447,8 @@ extern "C" int cdfo_conv3x3_bf16(const cdfo_conv_args* pa, void* stream) {
   CdfoProfScope prof(st, KID_CONV3_WIDE, 2.0 * px * a.Cout * a.Cin * 9,
                      4.0 * (px * a.Cout + px * a.Cin + 9.0 * a.Cin * a.Cout));
   const int dbg = a.prec >> 8, prec = a.prec & 255;
-  if (dbg) {   // developer ablations of the split-bf16 kernel (tools/bench_conv.py)
+  if (dbg) {   // developer ablations of the split-bf16 kernel: developer builds only
+#ifdef CDFO_DEV_ABLATIONS
     if (prec != CDFO_PREC_BF16X3) return CDFO_EINVAL;
 #define CDFO_DBG_CASE(D) case D: hipLaunchKernelGGL((conv3x3_mma16_kernel<M_BF16X3, 2, D>), grid, dim3(256), 0, st, a); break;
     switch (dbg) {
@@ -456,6 +457,9 @@ extern "C" int cdfo_conv3x3_bf16(const cdfo_conv_args* pa, void* stream) {
       default: return CDFO_EINVAL;
     }
 #undef CDFO_DBG_CASE
+#else
+    return CDFO_EINVAL;
+#endif
   } else if (prec == CDFO_PREC_BF16X3 && a.Cout <= 32 && a.CoutP == 64) {
     hipLaunchKernelGGL((conv3x3_mma16_kernel<M_BF16X3, 2, 0, 1>), grid, dim3(256), 0, st, a);
   } else if (prec == CDFO_PREC_FP16X2 && a.Cout <= 32 && a.CoutP == 64) {

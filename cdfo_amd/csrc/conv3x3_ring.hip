@@ -26,7 +26,6 @@
 //     while the tile's last chunk computes.
 // DMA completion is hand-counted (hipcc does not see inline-asm memory operations); the rules sit next to each wait.
 #include "common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -1214,7 +1213,7 @@ int rg_num_cus() { return cdfo_num_cus(); }
 
 // CDFO_RING_SPLIT=0 selects the round-2 form (eight identical waves); default: the wave-specialised form
 bool rg_split() {
-  static const bool v = [] { const char* s = getenv("CDFO_RING_SPLIT"); return !(s && s[0] == '0'); }();
+  static const bool v = cdfo_switch("CDFO_RING_SPLIT", 1) != 0;
   return v;
 }
 
@@ -1228,7 +1227,7 @@ int rg_launch(const cdfo_conv_args& a, const ring_extra& e, int grid, hipStream_
   // (with a half-resolution residual the producers spread its 48 tile pieces over a tile's first six chunks: nc >= 8)
   if constexpr (SPARSE) {
     if (rg_split() && !(a.res_up2 && e.nc < 8)) {
-      static const bool mf16 = [] { const char* v = getenv("CDFO_RING_MFMA16"); return !(v && v[0] == '0'); }();
+      static const bool mf16 = cdfo_switch("CDFO_RING_MFMA16", 1) != 0;
       if (mf16 && !(DBG & (4 | 16))) {
         static CdfoAttrOnce once16;
         const hipError_t err = cdfo_set_max_lds(once16, reinterpret_cast<const void*>(conv3x3_ring_split_kernel<SPARSE, DBG, true>), RingLds<SPARSE>::TOTAL);
@@ -1277,7 +1276,7 @@ extern "C" int cdfo_conv3x3_ring(const cdfo_conv_args* pa, void* stream) {
   e.halfsplit = a.src_halfsplit ? 1 : 0;
   // (off by default: the touched lines do not survive until the epilogue -- FETCH_SIZE of the launch rose by exactly the res1
   // tile bytes, 3.10 -> 3.44 GB, i.e. the epilogue fetched them again -- and the epilogue got 7 % shorter at best; CDFO_RING_TOUCH=1)
-  static const int touch = [] { const char* v = getenv("CDFO_RING_TOUCH"); return (v && v[0] == '1') ? 1 : 0; }();
+  static const int touch = cdfo_switch("CDFO_RING_TOUCH", 0);
   e.touch = (touch && a.res1 && (long long)a.H * a.W * a.ldr1 * 4 < (1ll << 31)) ? 1 : 0;
   e.src_planes = a.src_plane_wrap ? a.src_plane_wrap : nc;
   if (a.src_plane_wrap < 0 || a.src_plane_wrap > nc) return CDFO_EINVAL;
@@ -1288,6 +1287,7 @@ extern "C" int cdfo_conv3x3_ring(const cdfo_conv_args* pa, void* stream) {
   int rc;
   switch (a.prec >> 8) {
     case 0: rc = a.tap_mask ? rg_launch<true, 0>(a, e, grid, st) : rg_launch<false, 0>(a, e, grid, st); break;
+#ifdef CDFO_DEV_ABLATIONS      // developer ablations and probes (tools/bench_ring.py, ring_timeline.py): developer builds only
     case 1: rc = a.tap_mask ? rg_launch<true, 1>(a, e, grid, st) : rg_launch<false, 1>(a, e, grid, st); break;
     case 2: rc = a.tap_mask ? rg_launch<true, 2>(a, e, grid, st) : rg_launch<false, 2>(a, e, grid, st); break;
     case 4: rc = a.tap_mask ? rg_launch<true, 4>(a, e, grid, st) : rg_launch<false, 4>(a, e, grid, st); break;
@@ -1295,6 +1295,7 @@ extern "C" int cdfo_conv3x3_ring(const cdfo_conv_args* pa, void* stream) {
     case 9: rc = a.tap_mask ? rg_launch<true, 9>(a, e, grid, st) : rg_launch<false, 9>(a, e, grid, st); break;
     case 10: rc = a.tap_mask ? rg_launch<true, 10>(a, e, grid, st) : rg_launch<false, 10>(a, e, grid, st); break;
     case 16: rc = a.tap_mask ? rg_launch<true, 16>(a, e, grid, st) : rg_launch<false, 16>(a, e, grid, st); break;
+#endif
     default: return CDFO_EINVAL;
   }
   if (rc) return rc;

@@ -597,8 +597,8 @@ int wino_launch(const wino_args& a, int grid, hipStream_t st) {
 }
 }  // namespace
 
-// dbg: 0 (developer ablation bits otherwise, WRONG results: 1 no MFMAs, 2 no global loads, 4 no stores, 8 no epilogue arithmetic,
-// 16 no barrier)
+// dbg: 0 (developer ablation bits otherwise, -DCDFO_DEV_ABLATIONS builds only, WRONG results: 1 no MFMAs, 2 no global loads, 4 no stores,
+// 8 no epilogue arithmetic, 16 no barrier)
 extern "C" int cdfo_conv3x3_c64_wino_dbg(const void* src_cp16, int B, int H, int W, const void* w_wino, const float* bias, int Cout, int act,
                                          void* out_cp16, int store_mode, int dbg, void* clk_probe, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -631,6 +631,7 @@ extern "C" int cdfo_conv3x3_c64_wino_dbg(const void* src_cp16, int B, int H, int
   const double px = (double)B * H * W;
   CdfoProfScope prof(st, KID_CONV3_WINO, 2.0 * px * Cout * 64 * 9, 2.0 * (px * Cout + px * 64) + 2.0 * 12 * 64 * Cout);
   int rc = 0;
+#ifdef CDFO_DEV_ABLATIONS
   if (dbg == -2) {       // developer timeline of the UP form (tools/wino_timeline.py --up): dbg 512 | 2048
     static CdfoAttrOnce once_tl;
     const hipError_t e = cdfo_set_max_lds(once_tl, reinterpret_cast<const void*>(conv3x3_c64_wino_kernel<true, 2560, true>), WN_LDS_UP);
@@ -639,6 +640,7 @@ extern "C" int cdfo_conv3x3_c64_wino_dbg(const void* src_cp16, int B, int H, int
     CDFO_LAUNCH_CHECK();
     return 0;
   }
+#endif
   if (dbg == -1) {       // cdfo_conv3x3_c64_wino_up2
     rc = wino_launch_up(a, nslots * 8, st);
     if (rc) return rc;
@@ -647,6 +649,7 @@ extern "C" int cdfo_conv3x3_c64_wino_dbg(const void* src_cp16, int B, int H, int
   }
   switch (dbg) {
     case 0: rc = wino_launch<0>(a, nslots * 8, st); break;
+#ifdef CDFO_DEV_ABLATIONS      // developer ablations and probes (tools/bench_wino.py, wino_timeline.py): developer builds only
     case 1: rc = wino_launch<1>(a, nslots * 8, st); break;
     case 2: rc = wino_launch<2>(a, nslots * 8, st); break;
     case 4: rc = wino_launch<4>(a, nslots * 8, st); break;
@@ -668,6 +671,7 @@ extern "C" int cdfo_conv3x3_c64_wino_dbg(const void* src_cp16, int B, int H, int
     case 2048: rc = wino_launch<2048>(a, nslots * 8, st); break;
     case 4096: rc = wino_launch<4096>(a, nslots * 8, st); break;
     case 8192: rc = wino_launch<8192>(a, nslots * 8, st); break;
+#endif
     default: return CDFO_EINVAL;
   }
   if (rc) return rc;

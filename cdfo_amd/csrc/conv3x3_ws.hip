@@ -28,7 +28,6 @@
 // DMA completion is tracked by hand (hipcc does not count inline-asm memory operations) with counted s_waitcnt; the
 // rules are written next to each wait.
 #include "common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -1089,13 +1088,13 @@ int ws_num_cus() { return cdfo_num_cus(); }
 
 // CDFO_WS_RING=0 selects the private-halo form above for the non-residual calls; default: the ring-fed wave-specialised form
 bool ws_ring_form() {
-  static const bool v = [] { const char* s = getenv("CDFO_WS_RING"); return !(s && s[0] == '0'); }();
+  static const bool v = cdfo_switch("CDFO_WS_RING", 1) != 0;
   return v;
 }
 
 // CDFO_WS_MFMA16=0 keeps the 32x32x16 ring-fed form; default: the 16x16x32 one
 bool ws_mfma16() {
-  static const bool v = [] { const char* s = getenv("CDFO_WS_MFMA16"); return !(s && s[0] == '0'); }();
+  static const bool v = cdfo_switch("CDFO_WS_MFMA16", 1) != 0;
   return v;
 }
 
@@ -1127,7 +1126,7 @@ int ws_launch(const ws_args& a, int grid, hipStream_t st) {
   // three waves per SIMD by default (same-box A/B: 1.21 -> 1.18 ms at 64 -> 256 on 8 x 544 x 960, 0.295 -> 0.286 at 272 x 480):
   // with two, the matrix pipe idles whenever both are outside their MFMA runs at once (counters: pipe busy 67 %);
   // CDFO_WS_WAVES=8 selects the two-per-SIMD form with its 2-deep staging rings (developer A/B switch)
-  static const bool w12 = [] { const char* e = getenv("CDFO_WS_WAVES"); return !(e && atoi(e) == 8); }();
+  static const bool w12 = cdfo_switch("CDFO_WS_WAVES", 12) != 8;
   // (four per SIMD -- 16 waves at 128 VGPRs, 8 of them spilled -- was 5 % slower than three)
   if (DBG == 0 && !RES && w12) {     // (the residual form needs 221 VGPRs: two waves per SIMD only)
     static CdfoAttrOnce once12;
@@ -1194,6 +1193,7 @@ extern "C" int cdfo_conv3x3_c64_ws(const void* src_cp16, int B, int H, int W, co
   int rc;
   switch (dbg) {
     case 0: rc = ws_launch<0>(a, grid, st); break;
+#ifdef CDFO_DEV_ABLATIONS      // developer ablations and probes (tools/bench_ws.py, ws_timeline.py, probe/stress_ws.py): developer builds only
     case 1: rc = ws_launch<1>(a, grid, st); break;
     case 2: rc = ws_launch<2>(a, grid, st); break;
     case 3: rc = ws_launch<3>(a, grid, st); break;
@@ -1208,6 +1208,7 @@ extern "C" int cdfo_conv3x3_c64_ws(const void* src_cp16, int B, int H, int W, co
     case 72: rc = ws_launch<72>(a, grid, st); break;
     case 128: rc = ws_launch<128>(a, grid, st); break;
     case 136: rc = ws_launch<136>(a, grid, st); break;
+#endif
     default: return CDFO_EINVAL;
   }
   if (rc) return rc;

@@ -13,7 +13,6 @@
 // matching weight rows are staged transposed, and the contraction runs on the fp32 matrix cores
 // (v_mfma_f32_32x32x2_f32: M = output channel, N = pixel), so the output tile is written coalesced in NCHW.
 #include "common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -255,7 +254,7 @@ extern "C" int cdfo_dcn_forward(const float* in, const float* offset, const floa
                      4.0 * (px * (Co + 3.0 * deformable_groups * T) + (double)B * C * H * W + (double)Co * (C / groups) * T));
   const unsigned* rerun = nullptr;
   // (1) window-sampled kernel (dcn_win.hip): 3x3 / stride 1 / dilation 1 shapes of the alignment module's kind
-  static const int use_win = []() { const char* e = getenv("CDFO_DCN_WIN"); return e ? atoi(e) : 1; }();     // developer A/B switch
+  static const int use_win = cdfo_switch("CDFO_DCN_WIN", 1);     // developer A/B switch
   const int win = use_win ? cdfo_dcn_forward_win(in, offset, mask, weight, bias, out, B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw,
                                                  dh, dw, groups, deformable_groups, workspace, workspace_bytes, st, &rerun) : 0;
   if (win > 1) return win - 2;

@@ -519,7 +519,7 @@ int cdfo_dcn_forward_win(const float* in, const float* offset, const float* mask
 #ifdef CDFO_DEV_ABLATIONS
       // developer ablations of the alignment module's variant (tools/bench_dcn.py; results are wrong by construction): compiled only
       // into developer builds (-DCDFO_DEV_ABLATIONS) -- the shipped library reads no environment variable on this path
-      static const int dbg_sel = [] { const char* v = getenv("CDFO_DCN_DBG"); return v ? atoi(v) : 0; }();      // read once per process
+      static const int dbg_sel = cdfo_switch("CDFO_DCN_DBG", 0);
       switch (dbg_sel) {
         case 1: e = wn_launch<2, true, true, 1>(a, grid, st); break;
         case 2: e = wn_launch<2, true, true, 2>(a, grid, st); break;

@@ -19,8 +19,6 @@ fp16 hi+lo activations, two MFMA passes, in the 3x3 convolutions of the alignmen
 trunk's body convolutions on CVSR_V8's single-pass fp16 ``Block_`` kernels; the feature extractor stays split-bf16)."""
 from __future__ import annotations
 
-import os
-
 import contextlib
 import math
 from typing import Dict, List, Optional, Sequence
@@ -29,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
+from . import switches
 from .cvsr_v8 import CVSR_V8, NF, NFRAMES, _register
 from .mv_align import MVDualAttAlignment
 
@@ -99,6 +98,7 @@ class CVSR_V7(nn.Module):
         self.gumbel_uniform: Optional[Sequence[torch.Tensor]] = None
         self.precision = "bf16x3"
         self.neighbour_streams = 3       # HIP side streams for the twelve independent neighbour pipelines of a pyramid level
+        self.fea_r_single_pass = switches.get("CDFO_V7_FEAR_1PASS")      # fp16x2 mode, conv_expand_fea_r: see _forward (developer A/B)
         for key, shape, fan_in, init in _param_spec():
             if init == "module":
                 self.MV_deform_align = MVDualAttAlignment(64, 64, 3, padding=1, deformable_groups=16,
@@ -376,7 +376,7 @@ class CVSR_V7(nn.Module):
                 else:
                     u = noise[draw].to(device=dev, dtype=torch.float32).contiguous()
                 x_n = self._rdab(w, rms_prior, fea_com, u, du0)
-                if self.precision == "fp16x2" and os.environ.get("CDFO_V7_FEAR_1PASS", "1") != "0":
+                if self.precision == "fp16x2" and self.fea_r_single_pass:
                     # activations rounded once to fp16 (one MFMA pass): out_vs_golden unchanged at 7-10e-5 (developer A/B switch)
                     fea_i = K.conv([Lf[i], x_n], w["conv_expand_fea_r"], pad=1, prec=K.PREC_FP16X1)
                 else:

@@ -31,8 +31,6 @@ from __future__ import annotations
 import threading
 
 import contextlib
-import os
-
 import math
 from typing import Dict, List, Optional, Sequence
 
@@ -40,6 +38,7 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
+from . import switches
 
 NF, NFRAMES = 64, 7
 
@@ -147,19 +146,22 @@ class CVSR_V8(nn.Module):
         # HIP side streams for the two independent neighbour groups (frames 0-2 and 4-6): 1 = everything on the caller's
         # stream, 0 = auto = 2 (one side stream per group)
         self.neighbour_streams = 0
-        self.udsa_n16 = os.environ.get("CDFO_UDSA_N16", "1") not in ("", "0")       # developer A/B: the prior U-net's first layer, see _udsa
-        self.udsa_side_stream = os.environ.get("CDFO_UDSA_STREAM", "1") not in ("", "0")   # developer A/B, see _feature_extraction
-        self.attn_pv_single = os.environ.get("CDFO_ATTN_PV3", "0") in ("", "0")    # see _rdab (developer A/B: CDFO_ATTN_PV3=1 -> three passes)
+        self.udsa_n16 = switches.get("CDFO_UDSA_N16")       # developer A/B: the prior U-net's first layer, see _udsa
+        self.udsa_side_stream = switches.get("CDFO_UDSA_STREAM")   # developer A/B, see _feature_extraction
+        self.attn_pv_single = not switches.get("CDFO_ATTN_PV3")    # see _rdab (developer A/B: CDFO_ATTN_PV3=1 -> three passes)
         self.neighbour_group = 0        # frames per neighbour group: 0 = auto = 3
         # cached-feature call on one sequence (B = 1): the group of frames 0-2 (cached features only) starts beside the new
         # frame's feature extraction instead of behind it (see _forward)
-        self.overlap_new_frame = os.environ.get("CDFO_OVERLAP_NEW", "1") not in ("", "0")
+        self.overlap_new_frame = switches.get("CDFO_OVERLAP_NEW")
         # ... and the new frame's own neighbour pipeline follows the extraction as a group of one, frames 4-5 on the second side
         # stream (tools/bench_streaming.py, 24 frames 270x480, eager / HIP graph: 65.4 / 67.1 frames/s without the overlap,
         # 66.7 / 67.6 with it, 66.9 / 68.0 with the new frame alone)
-        self.new_frame_alone = os.environ.get("CDFO_NEW_ALONE", "1") not in ("", "0")
+        self.new_frame_alone = switches.get("CDFO_NEW_ALONE")
         # Block_: the half-resolution branch on a side stream beside the other two (see _block)
-        self.trunk_side_stream = os.environ.get("CDFO_TRUNK_SIDE", "1") not in ("", "0")
+        self.trunk_side_stream = switches.get("CDFO_TRUNK_SIDE")
+        # (the x2 branch's 256-channel intermediate in half-split rows: the Winograd kernel's lanes then store contiguous runs;
+        # measured: no gain in the forward (105.2 vs 105.3 ms), off by default)
+        self.wino_halfsplit = switches.get("CDFO_WINO_HS")
         # fp16x2 mode, the feature extractor's two 3x3 convolutions on the ring kernel: True = activations fp16 hi + lo x
         # weights fp16 hi + lo (three terms, fp32-grade: L1_fea 1.3e-5 max-abs); False = weights rounded once to fp16 (two
         # terms): measured 1.7e-3 on the RETURNED feature cache (|L1_fea| up to 7), outside the 1e-3 bound, for 1.3 ms per
@@ -167,7 +169,7 @@ class CVSR_V8(nn.Module):
         self.fe_weight_lo = True
         # fp16x2 mode, conv_expand_fea_r (arch.py:4454; 128 -> 64, 3x3, twice per forward on 3*B images): False = fp16 hi + lo
         # activations (two MFMA passes), True = activations rounded once to fp16 like the convolutions inside Block_ (one pass)
-        self.fea_r_single_pass = os.environ.get("CDFO_FEA_R_1PASS", "0") not in ("", "0")
+        self.fea_r_single_pass = switches.get("CDFO_FEA_R_1PASS")
         for key, shape, fan_in, init in _param_spec():
             t = torch.empty(shape)
             if init == "default":
@@ -480,8 +482,7 @@ class CVSR_V8(nn.Module):
                 u16, d16, x16 = K.block_prologue(x, w[p + "pro"], want_x16=True, lowres_up=up2)
             else:
                 u16, d16 = K.block_prologue(x, w[p + "pro"], lowres_up=up2)
-            # (the x2 branch's 256-channel intermediate in half-split rows: the Winograd kernel's lanes then store contiguous runs)
-            hs = up2 and os.environ.get("CDFO_WINO_HS", "0") != "0"      # measured: no gain in the forward (105.2 vs 105.3 ms), off by default
+            hs = up2 and self.wino_halfsplit
             c2 = (lambda src: K.conv3x3_wino_up2(src, b0, act=K.ACT_LRELU, halfsplit=hs)) if up2 else (lambda src: c1(src, s2d=True))
             # The x1/2 branch (two launches on a quarter of the pixels: 72 tiles per clip at 272x480, a fraction of the GPU for one
             # or two clips and a ragged last round for eight) runs on a side stream beside the x1 and x2 branches; the last

@@ -27,20 +27,19 @@ from __future__ import annotations
 import ctypes as C
 import threading
 import math
-import os
 from dataclasses import dataclass
 
 import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from . import _lib
+from . import _lib, switches
 from .kernels import _stream, on_device
 
 # Forward arithmetic of the float operator.  False (default): shapes the fused fast kernels cover run on split-fp16 MFMA
 # (fp32-grade: <= 2e-5 * max|out| against the C oracle; range-safe -- a sampled value outside fp16's range makes the
 # library re-run the exact kernel).  True (or CDFO_DCN_EXACT=1): always the exact-fp32 MFMA kernel.
-EXACT_FP32 = os.environ.get("CDFO_DCN_EXACT", "0") not in ("", "0")
+EXACT_FP32 = switches.get("CDFO_DCN_EXACT")
 
 _DTYPE_TAG = {torch.float32: 0, torch.float16: 1, torch.float64: 2}     # CDFO_DTYPE_* of include/cdfo_hip.h
 

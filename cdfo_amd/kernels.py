@@ -6,14 +6,13 @@ pitch ``ld = t.stride(2)`` may exceed C, so a channel slice ``t[..., a:b]`` of a
 from __future__ import annotations
 
 import contextlib
-import os
 import ctypes as C
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import torch
 
-from . import _lib
+from . import _lib, switches
 from ._lib import CdfoError, ConvArgs, check
 
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3
@@ -352,7 +351,7 @@ def conv3x3_ws(src: torch.Tensor, pc: PackedConv, *, act: int = ACT_NONE, s2d: b
 
 def wino_enabled() -> bool:
     """CDFO_WINO=0 keeps Block_.body[0] on the direct weights-stationary kernel (developer A/B switch)."""
-    return os.environ.get("CDFO_WINO", "1") != "0"
+    return switches.get("CDFO_WINO")
 
 
 def halfsplit_to_rows(t: torch.Tensor) -> torch.Tensor:
@@ -390,7 +389,7 @@ def conv3x3_wino(src: torch.Tensor, pc: PackedConv, *, act: int = ACT_NONE, s2d:
 
 def wino_up2_enabled() -> bool:
     """CDFO_WINO_UP2=0 keeps Block_'s x2 branch on a materialised double-resolution source (developer A/B switch)."""
-    return wino_enabled() and os.environ.get("CDFO_WINO_UP2", "1") != "0"
+    return wino_enabled() and switches.get("CDFO_WINO_UP2")
 
 
 def conv3x3_wino_up2(src_lr: torch.Tensor, pc: PackedConv, *, act: int = ACT_NONE, halfsplit: bool = False) -> torch.Tensor:
@@ -415,8 +414,7 @@ def conv3x3_body0(src: torch.Tensor, pc: PackedConv, *, act: int = ACT_NONE, s2d
     even width, one image of source / result below 2 GiB, CDFO_WINO != 0), the direct weights-stationary kernel otherwise."""
     _, _, H, W, _ = src.shape
     if pc.ww is not None and wino_enabled() and W % 2 == 0 and (not s2d or H % 2 == 0) and H * W * 2 * pc.Cout < (1 << 31):
-        plain_st = (not s2d) and os.environ.get("CDFO_WINO_NT", "1") == "0"    # developer A/B: the 1x launches WITHOUT non-temporal stores
-        return conv3x3_wino(src, pc, act=act, s2d=s2d, dbg=8192 if plain_st else 0)
+        return conv3x3_wino(src, pc, act=act, s2d=s2d)
     return conv3x3_ws(src, pc, act=act, s2d=s2d)
 
 

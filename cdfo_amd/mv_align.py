@@ -11,12 +11,11 @@ trains like the reference's; the folded inference schedule is used under ``torch
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import torch
 import torch.nn as nn
 
-from . import _lib, deform_conv_cuda
+from . import _lib, deform_conv_cuda, switches
 from . import kernels as K
 from ._lib import check
 from .dcn import ModulatedDeformConvPack
@@ -46,10 +45,10 @@ class MVDualAttAlignment(ModulatedDeformConvPack):
         # arithmetic of the 64->64->432 offset/mask head (the module's FLOPs): "bf16x3" = split-bf16 matrix cores,
         # fp32-grade (~1e-6 relative; the head's output is scaled by 10 px, so nothing coarser), or "f32" = exact
         self.precision = "bf16x3"
-        self.fuse_assembly = os.environ.get("CDFO_V7_FUSE_ASSEMBLY", "1") != "0"      # developer A/B switches
-        self.head_one_pass = os.environ.get("CDFO_V7_HEAD_1PASS", "1") != "0"
-        self.off0_one_pass = os.environ.get("CDFO_V7_OFF0_1PASS", "1") != "0"
-        self.ws_head = os.environ.get("CDFO_V7_WS_HEAD", "1") != "0"
+        self.fuse_assembly = switches.get("CDFO_V7_FUSE_ASSEMBLY")      # developer A/B switches
+        self.head_one_pass = switches.get("CDFO_V7_HEAD_1PASS")
+        self.off0_one_pass = switches.get("CDFO_V7_OFF0_1PASS")
+        self.ws_head = switches.get("CDFO_V7_WS_HEAD")
         self._packed = None
         self._sig = None
 

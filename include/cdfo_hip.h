@@ -53,7 +53,8 @@ typedef struct {
   const float* res1; int ldr1;
   const float* res2; int ldr2;
   float* out; int ldo; int store_mode;
-  int prec;
+  int prec;                   /* CDFO_PREC_*; bits 8 and up: developer ablation code of cdfo_conv3x3_ring / cdfo_conv3x3_bf16 (0 in the
+                                 shipped library, which answers CDFO_EINVAL otherwise; -DCDFO_DEV_ABLATIONS builds compile the rest) */
   const float* ln_gamma; const float* ln_beta;   /* optional fused per-pixel LayerNorm of a single 64-channel source (1x1 only) */
   const unsigned* tap_mask;   /* optional, cdfo_conv3x3_bf16 only: per 16-channel chunk, bit t set = tap t has non-zero weights */
   int src_f16;                /* cdfo_conv3x3_bf16 only: the single source is an fp16 tensor (ld in halves); implies CDFO_PREC_FP16 */
@@ -109,7 +110,8 @@ int cdfo_pack_conv3x3_f16(const float* w_oihw, void* packed, int Cout, int Cin, 
  * [B][4*Cout/16][H/2][W/2][16], chunk = ((y&1)*2+(x&1))*Cout/16 + channel/16 (CDFO_STORE_S2D).
  * H even, Cout % 64 == 0, the source smaller than 2 GiB.  Since round 3 the call runs the ring-fed, wave-specialised form
  * (four producer waves feed two groups of four consumer waves, v_mfma_f32_16x16x32_f16); same operands, same result layout.
- * dbg: 0 (developer ablation flags otherwise: 1 / 2 / 8 skip the MFMAs / the DMA / the epilogue, 4 = MFMA-shape clock
+ * dbg: 0 (developer ablation flags otherwise -- compiled only into developer builds, -DCDFO_DEV_ABLATIONS, `python -m cdfo_amd.build --dev`;
+ * the shipped library answers CDFO_EINVAL: 1 / 2 / 8 skip the MFMAs / the DMA / the epilogue, 4 = MFMA-shape clock
  * experiment with WRONG arithmetic; with dbg 32 clk_probe receives s_memtime stamps of the consumer waves, 256 x 12 x 4 x 8
  * 64-bit words; with dbg 128 -- private-halo form only -- per wave of the grid {shader-clock cycles, start, end in 100 MHz
  * real-time ticks}: 3 x 8 x 256 words; else pass NULL).  */
@@ -125,9 +127,9 @@ int cdfo_conv3x3_c64_ws(const void* src_cp16, int B, int H, int W, const void* w
 int cdfo_conv3x3_c64_wino(const void* src_cp16, int B, int H, int W, const void* w_wino, const float* bias, int Cout, int act,
                           void* out_cp16, int store_mode, void* stream);
 int cdfo_pack_conv3x3_wino(const float* w_oihw, void* packed, int Cout, void* stream);
-/* the same call with developer ablation bits (dbg != 0: WRONG results; 1 no MFMAs, 2 no global loads, 4 no stores, 8 no epilogue
- * arithmetic, 16 no barrier; 512 = timeline probe: clk_probe receives s_memtime stamps [workgroup][wave][8] of one steady-state
- * batch, 64-bit words, else NULL): tools/bench_wino.py, tools/wino_timeline.py */
+/* the same call with developer ablation bits (dbg != 0: developer builds only, -DCDFO_DEV_ABLATIONS, CDFO_EINVAL otherwise; WRONG
+ * results; 1 no MFMAs, 2 no global loads, 4 no stores, 8 no epilogue arithmetic, 16 no barrier; 512 = timeline probe: clk_probe
+ * receives s_memtime stamps [workgroup][wave][8] of one steady-state batch, 64-bit words, else NULL): tools/bench_wino.py, tools/wino_timeline.py */
 /* Block_'s double-resolution branch (arch.py:398-404: body(up(x))) without its double-resolution source: src_lr_cp16
  * [B][4][H/2][W/2][16] = up.0(x) at the block's resolution (cdfo_block_prologue2's t16); H x W (multiples of 4) = the size of the x2
  * image the convolution runs on.  The bilinear x2 (align_corners = False, clamped taps; the convolution pads the x2 image with zeros)

@@ -1,7 +1,8 @@
 """hipcc leaves one store-data hazard unpadded on gfx950: a vector instruction that overwrites a data register of a 128-bit buffer
 store WITH a scalar offset register within two wait states of it (it produced wrong lanes on the first store of a
 unit in the Winograd kernel).  This test compiles the kernels that use such stores to assembly and scans it with
-tools/check_store_hazard.py -- a source change that lets the compiler schedule such a write behind the store fails here, on the CPU."""
+tools/check_store_hazard.py, developer ablations included (-DCDFO_DEV_ABLATIONS: a superset of the shipped kernels) -- a source
+change that lets the compiler schedule such a write behind the store fails here, on the CPU."""
 import os, shutil, subprocess, sys, tempfile
 import pytest
 
@@ -21,8 +22,8 @@ def test_no_unpadded_store_data_hazard(src):
     from check_store_hazard import scan
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
-        r = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=fast", "-S", "--cuda-device-only",
-                            "-o", out, os.path.join(ROOT, "cdfo_amd", "csrc", src)], capture_output=True, text=True)
+        r = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=fast", "-DCDFO_DEV_ABLATIONS", "-S",
+                            "--cuda-device-only", "-o", out, os.path.join(ROOT, "cdfo_amd", "csrc", src)], capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-2000:]
         hits = scan(out)
     assert not hits, "\n".join(f"{k}: line {ln}: {st} <- {ins}" for k, ln, st, ins in hits[:10])

@@ -1,7 +1,24 @@
 """Synthetic weights / clips for the developer tools (shapes and statistics of SURVEY section 8d), generated with torch on
 the device.  The tools do not touch oracle/ (that is test infrastructure): a default-constructed model already carries a
 random init of the reference architecture."""
+import sys
+
 import torch
+
+
+def needs_dev_library():
+    """For the tools that pass a non-zero `dbg` (kernel ablations, timeline probes): those instantiations exist only in the developer
+    library, and the shipped one answers CDFO_EINVAL.  Call once at the top of the tool: that refusal then ends the tool with one
+    line saying how to build and select the developer library instead of a traceback."""
+    from cdfo_amd._lib import LIB_PATH, CdfoError
+    prev = sys.excepthook
+
+    def hook(tp, err, tb):
+        if not (issubclass(tp, CdfoError) and "invalid argument" in str(err)):
+            return prev(tp, err, tb)
+        print(f"{err} ({LIB_PATH}): a non-zero dbg needs the developer library -- `python -m cdfo_amd.build --dev`, then run with "
+              "CDFO_LIB_PATH=cdfo_amd/lib/dev/libcdfo_hip.so", file=sys.stderr)
+    sys.excepthook = hook
 
 
 def random_inputs(B, H, W, seed=0, device="cuda", levels=None):

@@ -3,7 +3,10 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from cdfo_amd import kernels as K
+from _inputs import needs_dev_library
 from bench_conv import timeit
+
+needs_dev_library()
 
 # Cin, Cout, H, W, B, sparse
 SHAPES = [(256, 64, 272, 480, 8, False), (256, 64, 136, 240, 8, False), (1024, 64, 272, 480, 8, True)]

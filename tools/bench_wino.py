@@ -1,9 +1,13 @@
-"""Developer micro-benchmark (GPU box only): the Winograd F(2,3) Block_.body[0] kernel vs the direct weights-stationary one."""
+"""Developer micro-benchmark (GPU box only): the Winograd F(2,3) Block_.body[0] kernel vs the direct weights-stationary one.
+    python tools/bench_wino.py [dbg,dbg,...]      (ablation codes of conv3x3_wino.hip; 8192 = the 1x launches WITHOUT non-temporal stores)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from cdfo_amd import kernels as K
+from _inputs import needs_dev_library
 from bench_conv import timeit
+
+needs_dev_library()
 
 SHAPES = [(256, 544, 960, 8, True), (256, 272, 480, 8, False), (256, 136, 240, 8, False), (256, 272, 480, 1, False), (256, 1088, 1920, 1, True)]
 

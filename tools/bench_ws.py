@@ -3,6 +3,9 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from cdfo_amd import kernels as K
+from _inputs import needs_dev_library
+
+needs_dev_library()
 from bench_conv import timeit
 
 SHAPES = [(256, 544, 960, 8, True), (256, 272, 480, 8, False), (256, 136, 240, 8, False)]

@@ -2,6 +2,9 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 from cdfo_amd import kernels as K
+from tools._inputs import needs_dev_library
+
+needs_dev_library()
 B, H, W, Cout = 8, 544, 960, 256
 g = torch.Generator(device="cuda").manual_seed(1)
 x = torch.randn(B, H, W, 64, device="cuda", generator=g)

@@ -6,6 +6,9 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from cdfo_amd import kernels as K
+from _inputs import needs_dev_library
+
+needs_dev_library()
 
 NAMES = ["entry", "waited", "barrier", "pre-tap", "tapA", "tapB", "tapC", "tapD", "end"]
 

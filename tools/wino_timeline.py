@@ -3,6 +3,9 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from cdfo_amd import kernels as K
+from _inputs import needs_dev_library
+
+needs_dev_library()
 
 B, H, W, s2d = 8, 544, 960, True
 UP = "--up" in sys.argv            # the UP form: the same launch from the low-resolution source (bilinear x2 inside the input transform)
