@@ -48,6 +48,7 @@ class ConvArgs(C.Structure):
         ("off_accumulate", C.c_int),
         ("res2_pixscale", C.c_void_p),
         ("src_halfsplit", C.c_int),
+        ("chan_sum_out", C.c_void_p), ("chan_sum_slots", C.c_int),
     ]
 
 

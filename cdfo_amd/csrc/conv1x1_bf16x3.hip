@@ -293,6 +293,21 @@ extern "C" int cdfo_conv1x1_bf16x3(const cdfo_conv_args* pa, void* stream) {
   if (!ln_out && a.ln_gamma && !(a.nsrc == 1 && a.cs[0] == 64 && a.ln_beta && aligned16(a.ln_gamma) && aligned16(a.ln_beta))) return CDFO_EINVAL;
   const long long P = (long long)a.H * a.W;
   if (a.res2_pixscale && (!a.res2 || taps)) return CDFO_EINVAL;
+  if (a.chan_sum_out) {
+    // channel sums of the result: from the streaming kernel's epilogue, else (outside its contract / switched off) a pass of their own
+    if (a.Cout != 64 || a.CoutP != 64 || a.store_mode != CDFO_STORE_PLAIN || a.chan_sum_slots <= 0 || !aligned16(a.chan_sum_out)) return CDFO_EINVAL;
+    static const bool use_stream = cdfo_switch("CDFO_CONV1X1_STREAM", 1) != 0;
+    if (use_stream && !ln_out) {
+      const int r = cdfo_conv1x1_stream_try(a, st);
+      if (r == 1) return 0;
+      if (r != 0) return r;
+    }
+    cdfo_conv_args plain = a;
+    plain.chan_sum_out = nullptr; plain.chan_sum_slots = 0;
+    const int rc = cdfo_conv1x1_bf16x3(&plain, stream);
+    if (rc) return rc;
+    return cdfo_chan_sum_partial(a.out, a.ldo, a.B, P, a.chan_sum_slots, a.chan_sum_out, stream);
+  }
   if (ln_out) {
     // the streaming kernel normalises in its epilogue; outside its contract: the convolution, then a LayerNorm pass
     const int r = cdfo_conv1x1_stream_try(a, st);

@@ -55,7 +55,26 @@ struct st_args {
   // out[HR pixel][ldo], HR pixel = (b, 2 y + (cb >> 1), 2 x + (cb & 1)) of the W-pixel-wide input row (y, x)
   const float* w_last;             // conv_last.weight as [64][9]
   int W;                           // input image width (pixels per row) for the pixel shuffle
+  // optional third output (CSUM form, Cout == 64): per-image channel sums of the RESULT as fixed-order partials [B][csum_slots][64]
+  // (cdfo_chan_sum_partial's layout; the buffer is zeroed by the caller).  The values are in the epilogue's registers: the global
+  // average pool that follows (CALayer, arch.py:3493) needs no pass of its own over the tensor
+  float* csum; int csum_slots;
 };
+
+// The persistent kernels here cut the stream of `tiles` 128-pixel tiles into `grid` contiguous ranges [tiles w / grid, tiles (w + 1) /
+// grid).  st_owner: the workgroup whose range holds tile t.  A workgroup's partial sums over its tiles of image b go to slot
+// (w - st_owner(first tile of b)) of that image: a static function of the shape and the grid, one writer per (image, slot).
+__host__ __device__ inline long long st_owner(long long t, long long tiles, int grid) { return ((t + 1) * grid + tiles - 1) / tiles - 1; }
+// slots per image that such a launch may write
+inline int st_slots(int B, int tiles_per_image, int grid) {
+  const long long tiles = (long long)B * tiles_per_image;
+  int n = 1;
+  for (int b = 0; b < B; ++b) {
+    const int m = (int)(st_owner((long long)(b + 1) * tiles_per_image - 1, tiles, grid) - st_owner((long long)b * tiles_per_image, tiles, grid)) + 1;
+    n = m > n ? m : n;
+  }
+  return n;
+}
 
 __device__ __forceinline__ unsigned st_pack_bf16(float a, float b) {
   const __bf16 ha = (__bf16)a, hb = (__bf16)b;
@@ -120,7 +139,8 @@ __device__ __forceinline__ void st_split_pair_f16(float x, float y, unsigned& hi
 }
 
 // NCB: 64-wide output-channel blocks (1, 2; 4 in the TAPS form)
-template <int NCB, bool TAPS = false>
+// CSUM (NCB == 1): also the channel sums of the result, see st_args.csum
+template <int NCB, bool TAPS = false, bool CSUM = false>
 __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r = lane & 31;
@@ -251,6 +271,9 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
     for (; issued < NS - 1 && issued < n_items; ++issued) issue(issued);
 
     f32x16 acc[NCB][2];
+    float cs[CSUM ? 32 : 1];       // CSUM: this lane's running sums of its 32 channels over its pixels of image b
+#pragma unroll
+    for (int e = 0; e < (CSUM ? 32 : 1); ++e) cs[e] = 0.f;
     for (long long it = 0; it < n_items; ++it) {
       const int k = (int)(it % items_per_tile);
       // item `it` has landed when at most the 8 * (younger items in flight) youngest DMA pieces are outstanding
@@ -433,6 +456,12 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
             }
           }
         } else if (pin < a.P) {
+          if (CSUM) {
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+              for (int e = 0; e < 16; ++e) cs[ni * 16 + e] += acc[0][ni][e];
+          }
           float* op = a.out + ((long long)b * a.P + pin) * a.ldo;
 #pragma unroll
           for (int cb = 0; cb < NCB; ++cb)
@@ -452,11 +481,328 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
         }
       }
     }
+    if (CSUM) {
+      // ---- leaving image b: the workgroup's channel sums -> its slot.  Every item of the segment has been consumed, so the wave's
+      // ring is idle: stage 0 takes the lanes' sums as [pixel lane r][64 channels]; summed in a fixed order (r ascending, then waves)
+      float* red = reinterpret_cast<float*>(ring);
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) {
+          const int n = ni * 32 + jj * 16 + h * 8;
+          const f32x4 v0 = {cs[ni * 16 + 8 * jj], cs[ni * 16 + 8 * jj + 1], cs[ni * 16 + 8 * jj + 2], cs[ni * 16 + 8 * jj + 3]};
+          const f32x4 v1 = {cs[ni * 16 + 8 * jj + 4], cs[ni * 16 + 8 * jj + 5], cs[ni * 16 + 8 * jj + 6], cs[ni * 16 + 8 * jj + 7]};
+          *reinterpret_cast<f32x4*>(red + r * 64 + n) = v0;
+          *reinterpret_cast<f32x4*>(red + r * 64 + n + 4) = v1;
+        }
+      __syncthreads();
+      const int slot = (int)(blockIdx.x - st_owner((long long)b * a.tiles_per_image, a.tiles, gridDim.x));
+      if (tid < 64 && slot >= 0 && slot < a.csum_slots) {
+        float sw[4];
+#pragma unroll
+        for (int wv = 0; wv < 4; ++wv) {
+          const float* rw = reinterpret_cast<const float*>(smem + ring_off + wv * NS * ST_STAGE);
+          float t = 0.f;
+          for (int rr = 0; rr < 32; ++rr) t += rw[rr * 64 + tid];
+          sw[wv] = t;
+        }
+        a.csum[((long long)b * a.csum_slots + slot) * 64 + tid] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+      }
+      // (the barriers at the top of the next image's trip keep its DMAs behind these reads)
+    }
+    img_t0 = seg_hi;
+  }
+}
+
+// ---- Statistics form: the alignment module's kf = act(W . [x0; x1]) (128 -> 64) is formed tile by tile like above and never
+// stored.  What leaves the kernel per (image, workgroup segment) is what the fold kernels of stats.hip read:
+//   gram[b][slot][c*(CH+2) + j]   j < CH: sum_p q[p][c] kf[p][head(c)*CH + j];  j == CH: sum q[p][c]^2;  j == CH+1: sum kf[p][c]^2
+//   sum0 / sum1[b][slot][c]       channel sums of x0 / x1
+// (cdfo_gram_partial's and cdfo_chan_sum_partial's layouts with "chunk" = slot, see st_owner; buffers zeroed by the caller).
+// Per tile a wave streams three items through its ring: x0, x1 (the two K blocks) and q.  When q is consumed, the stage of the item
+// before it (x1, already in the accumulators) is free until the next request is issued: the wave writes its 32 x 64 kf values there
+// in the ring's own swizzled layout, and lane c forms row c of the Gram from the two stages in fp32 (one dword of q and of kf,
+// CH/4 broadcast reads of the head's kf channels per pixel).  Sums are kept per tile and then added to the segment's running
+// values, so no chain is longer than 32 + tiles-per-segment terms; waves and slots are summed in index order: deterministic.
+struct sg_args {
+  st_item src[3];                  // x0, x1, q
+  const float* w; const float* bias; int act_fn;      // packed [128/4][64][4] weights, optional bias
+  long long P; int tiles_per_image; long long tiles;
+  float* gram; float* sum0; float* sum1; int slots;
+};
+
+constexpr int SG_NS = 3;
+
+template <int CH>
+__global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int NS = SG_NS, NKB = 2, IPT = 3, GS = CH + 2;
+  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // LDS map as conv1x1_stream_kernel<1>: weights hi | lo (16 KB each) | bias | 4 waves x NS stages
+  constexpr int w_half = NKB * 4 * 2 * 64 * 16;
+  unsigned char* sWh = smem;
+  unsigned char* sWl = smem + w_half;
+  float* sBias = reinterpret_cast<float*>(smem + 2 * w_half);
+  constexpr int ring_off = 2 * w_half + 64 * 4;
+  unsigned char* ring = smem + ring_off + wave * NS * ST_STAGE;
+  const unsigned ring_lds = (unsigned)(unsigned long long)(smem) + ring_off + wave * NS * ST_STAGE;
+  auto chan_of_row = [](int n) { const int m = n & 31; return (n & ~31) + ((m >> 4) & 1) * 16 + ((m >> 2) & 1) * 8 + ((m >> 3) & 1) * 4 + (m & 3); };
+
+  const long long t_lo = a.tiles * blockIdx.x / gridDim.x, t_hi = a.tiles * (blockIdx.x + 1) / gridDim.x;
+  if (t_lo >= t_hi) return;
+  const float slope = a.act_fn == CDFO_ACT_NONE ? 1.f : (a.act_fn == CDFO_ACT_LRELU ? 0.1f : 0.f);
+
+  int d_px[8], d_part[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int s = 64 * k + lane, p = s >> 4;
+    d_px[k] = p;
+    d_part[k] = (s & 15) ^ (p & 15);
+  }
+  auto part_off = [&](int q) { return r * 256 + ((q ^ (r & 15)) << 4); };
+
+  // ---- the weights (the same for every image) -> LDS, split bf16 hi | lo, rows permuted
+  for (int i = tid; i < (128 >> 2) * 64; i += ST_THREADS) {
+    const int rowpos = i % 64, kg = i / 64;
+    const int n = chan_of_row(rowpos);
+    const f32x4 wv = *reinterpret_cast<const f32x4*>(a.w + ((long long)kg * 64 + n) * 4);
+    const int c = kg >> 2, hh = (kg >> 1) & 1, j0 = (kg & 1) * 4;
+    u32x2 hi, lo;
+    hi[0] = st_pack_bf16(wv[0], wv[1]); hi[1] = st_pack_bf16(wv[2], wv[3]);
+    lo[0] = st_pack_bf16(wv[0] - st_bf16_round(wv[0]), wv[1] - st_bf16_round(wv[1]));
+    lo[1] = st_pack_bf16(wv[2] - st_bf16_round(wv[2]), wv[3] - st_bf16_round(wv[3]));
+    const int off = ((c * 2 + hh) * 64 + rowpos) * 16 + j0 * 2;
+    *reinterpret_cast<u32x2*>(sWh + off) = hi;
+    *reinterpret_cast<u32x2*>(sWl + off) = lo;
+  }
+  for (int i = tid; i < 64; i += ST_THREADS) sBias[i] = a.bias ? a.bias[i] : 0.f;
+
+  // lane c of the statistics phases: channel c of q / kf / x0 / x1 of pixel p sits at p*256 + (((c >> 2) ^ (p & 15)) << 4) + (c & 3)*4
+  const int c_part = lane >> 2, c_sub = (lane & 3) * 4, h_part = (lane / CH) * CH / 4;
+
+  for (long long img_t0 = t_lo; img_t0 < t_hi;) {
+    const int b = (int)(img_t0 / a.tiles_per_image);
+    const long long img_end = (long long)(b + 1) * a.tiles_per_image;
+    const long long seg_hi = img_end < t_hi ? img_end : t_hi;
+    __syncthreads();       // weights are in LDS / the previous segment's reduction has read the rings; no DMA is in flight here
+
+    const long long n_items = (seg_hi - img_t0) * IPT;
+    long long issued = 0;
+    auto issue = [&](long long it) {
+      const long long tile = img_t0 + it / IPT;
+      const st_item src = a.src[(int)(it % IPT)];
+      const long long p0 = (tile - (long long)b * a.tiles_per_image) * 128 + wave * 32;
+      const long long rows_left = a.P - p0;                               // may be <= 0: everything out of range
+      const float* base = src.base + ((long long)b * a.P + (rows_left > 0 ? p0 : 0)) * src.ld + src.ch0;
+      const unsigned long long pb = reinterpret_cast<unsigned long long>(base);
+      i32x4 rsrc;
+      rsrc[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)pb);
+      rsrc[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(pb >> 32));
+      const long long bytes = rows_left > 0 ? (rows_left < 32 ? rows_left : 32) * (long long)src.ld * 4 : 0;
+      rsrc[2] = __builtin_amdgcn_readfirstlane((int)bytes);               // lanes beyond the image read zeros
+      rsrc[3] = 0x00020000;
+      unsigned voff[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) voff[q] = (unsigned)(d_px[q] * src.ld * 4 + d_part[q] * 16);
+      st_dma8(voff, rsrc, __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(it % NS) * ST_STAGE));
+    };
+    for (; issued < NS - 1 && issued < n_items; ++issued) issue(issued);
+
+    f32x16 acc[2];
+    float g[CH], sq = 0.f, sk = 0.f, sx[2] = {0.f, 0.f};     // the segment's running sums of lane c
+#pragma unroll
+    for (int j = 0; j < CH; ++j) g[j] = 0.f;
+    for (long long it = 0; it < n_items; ++it) {
+      const int k = (int)(it % IPT);
+      const long long younger = issued - it - 1;
+      if (younger >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+      else if (younger == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const unsigned char* st = ring + (it % NS) * ST_STAGE;
+      if (k == 0) {
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc[ni][e] = 0.f;
+      }
+      if (k < NKB) {
+        // ---- one K block of the product, as conv1x1_stream_kernel
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const f32x4 v0 = *reinterpret_cast<const f32x4*>(st + part_off(c * 4 + h * 2));
+          const f32x4 v1 = *reinterpret_cast<const f32x4*>(st + part_off(c * 4 + h * 2 + 1));
+          union { unsigned u[4]; bf16x8_t v; } ph, pl;
+          ph.u[0] = st_pack_bf16(v0[0], v0[1]); ph.u[1] = st_pack_bf16(v0[2], v0[3]);
+          ph.u[2] = st_pack_bf16(v1[0], v1[1]); ph.u[3] = st_pack_bf16(v1[2], v1[3]);
+          pl.u[0] = st_pack_bf16(v0[0] - st_bf16_round(v0[0]), v0[1] - st_bf16_round(v0[1]));
+          pl.u[1] = st_pack_bf16(v0[2] - st_bf16_round(v0[2]), v0[3] - st_bf16_round(v0[3]));
+          pl.u[2] = st_pack_bf16(v1[0] - st_bf16_round(v1[0]), v1[1] - st_bf16_round(v1[1]));
+          pl.u[3] = st_pack_bf16(v1[2] - st_bf16_round(v1[2]), v1[3] - st_bf16_round(v1[3]));
+          const int wrow = ((k * 4 + c) * 2 + h) * 64 + r;
+#pragma unroll
+          for (int ni = 0; ni < 2; ++ni) {
+            const bf16x8_t wh = *reinterpret_cast<const bf16x8_t*>(sWh + (wrow + ni * 32) * 16);
+            const bf16x8_t wl = *reinterpret_cast<const bf16x8_t*>(sWl + (wrow + ni * 32) * 16);
+            acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, pl.v, acc[ni], 0, 0, 0);
+            acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, ph.v, acc[ni], 0, 0, 0);
+            acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, ph.v, acc[ni], 0, 0, 0);
+          }
+        }
+        // ---- channel sum of this operand over the wave's 32 pixels (rows beyond the image arrived as zeros)
+        float t4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int p = 0; p < 32; ++p)
+          t4[p & 3] += *reinterpret_cast<const float*>(st + p * 256 + ((c_part ^ (p & 15)) << 4) + c_sub);
+        sx[k] += (t4[0] + t4[1]) + (t4[2] + t4[3]);
+        if (k == NKB - 1) {      // bias + activation: acc[ni][8 jj + q] = kf channel ni*32 + jj*16 + h*8 + q of pixel r; zero beyond the image
+          const long long pin = (img_t0 + it / IPT - (long long)b * a.tiles_per_image) * 128 + wave * 32 + r;
+          const bool inside = pin < a.P;
+#pragma unroll
+          for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+              const float t = acc[ni][e] + sBias[ni * 32 + (e >> 3) * 16 + h * 8 + (e & 7)];
+              acc[ni][e] = inside ? fmaxf(t, 0.f) + slope * fminf(t, 0.f) : 0.f;
+            }
+        }
+      } else {
+        // ---- q has landed: kf -> the stage of the item before (free until the request below), then row c of the Gram
+        unsigned char* kst = ring + ((it - 1) % NS) * ST_STAGE;
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+          for (int jj = 0; jj < 2; ++jj) {
+            const int q0 = (ni * 32 + jj * 16 + h * 8) >> 2;
+            const f32x4 v0 = {acc[ni][8 * jj], acc[ni][8 * jj + 1], acc[ni][8 * jj + 2], acc[ni][8 * jj + 3]};
+            const f32x4 v1 = {acc[ni][8 * jj + 4], acc[ni][8 * jj + 5], acc[ni][8 * jj + 6], acc[ni][8 * jj + 7]};
+            *reinterpret_cast<f32x4*>(kst + part_off(q0)) = v0;
+            *reinterpret_cast<f32x4*>(kst + part_off(q0 + 1)) = v1;
+          }
+        float gt[CH], tq = 0.f, tk = 0.f;
+#pragma unroll
+        for (int j = 0; j < CH; ++j) gt[j] = 0.f;
+#pragma unroll
+        for (int p = 0; p < 32; ++p) {
+          const int own = p * 256 + ((c_part ^ (p & 15)) << 4) + c_sub;
+          const float qv = *reinterpret_cast<const float*>(st + own);
+          const float kc = *reinterpret_cast<const float*>(kst + own);
+          tq = fmaf(qv, qv, tq);
+          tk = fmaf(kc, kc, tk);
+#pragma unroll
+          for (int j4 = 0; j4 < CH / 4; ++j4) {
+            const f32x4 kv = *reinterpret_cast<const f32x4*>(kst + p * 256 + (((h_part + j4) ^ (p & 15)) << 4));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) gt[j4 * 4 + e] = fmaf(qv, kv[e], gt[j4 * 4 + e]);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < CH; ++j) g[j] += gt[j];
+        sq += tq;
+        sk += tk;
+      }
+      // this item's (and the kf stage's) LDS reads have returned before the next request overwrites the stage of item it - 1
+      if (issued < n_items) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); issue(issued); ++issued; }
+    }
+
+    // ---- leaving image b: the four waves' sums (each in stage 0 of its idle ring) -> this workgroup's slot, waves in index order
+    {
+      float* red = reinterpret_cast<float*>(ring);
+#pragma unroll
+      for (int j = 0; j < CH; ++j) red[lane * GS + j] = g[j];
+      red[lane * GS + CH] = sq;
+      red[lane * GS + CH + 1] = sk;
+      red[64 * GS + lane] = sx[0];
+      red[64 * GS + 64 + lane] = sx[1];
+      __syncthreads();
+      const int slot = (int)(blockIdx.x - st_owner((long long)b * a.tiles_per_image, a.tiles, gridDim.x));
+      if (slot >= 0 && slot < a.slots) {
+        const float* r0 = reinterpret_cast<const float*>(smem + ring_off);
+        const float* r1 = reinterpret_cast<const float*>(smem + ring_off + 1 * NS * ST_STAGE);
+        const float* r2 = reinterpret_cast<const float*>(smem + ring_off + 2 * NS * ST_STAGE);
+        const float* r3 = reinterpret_cast<const float*>(smem + ring_off + 3 * NS * ST_STAGE);
+        const long long bs = (long long)b * a.slots + slot;
+        for (int i = tid; i < 64 * GS + 128; i += ST_THREADS) {
+          const float v = (r0[i] + r1[i]) + (r2[i] + r3[i]);
+          if (i < 64 * GS) a.gram[bs * (64 * GS) + i] = v;
+          else if (i < 64 * GS + 64) a.sum0[bs * 64 + (i - 64 * GS)] = v;
+          else a.sum1[bs * 64 + (i - 64 * GS - 64)] = v;
+        }
+      }
+    }
     img_t0 = seg_hi;
   }
 }
 
 }  // namespace
+
+// Pure host arithmetic of the partial slots (no device needed): slots per image written by a launch of `grid` workgroups, and the
+// slot that workgroup `wg` writes for image b (-1: it holds no tile of b).
+extern "C" int cdfo_stream_slots_for_grid(int B, long long P, int grid) {
+  if (B <= 0 || P <= 0 || grid <= 0 || (P + 127) / 128 > 0x7fffffff / 2) return CDFO_EINVAL;
+  const int tpi = (int)((P + 127) / 128);
+  const long long tiles = (long long)B * tpi;
+  return st_slots(B, tpi, (int)(tiles < grid ? tiles : grid));
+}
+extern "C" int cdfo_stream_slot_of(int B, long long P, int grid, int wg, int b) {
+  if (B <= 0 || P <= 0 || grid <= 0 || wg < 0 || b < 0 || b >= B) return CDFO_EINVAL;
+  const int tpi = (int)((P + 127) / 128);
+  const long long tiles = (long long)B * tpi;
+  const int g = (int)(tiles < grid ? tiles : grid);
+  if (wg >= g) return -1;
+  const long long t_lo = tiles * wg / g, t_hi = tiles * (wg + 1) / g;
+  const long long lo = t_lo > (long long)b * tpi ? t_lo : (long long)b * tpi, hi = t_hi < (long long)(b + 1) * tpi ? t_hi : (long long)(b + 1) * tpi;
+  if (lo >= hi) return -1;
+  return (int)(wg - st_owner((long long)b * tpi, tiles, g));
+}
+// slots per image of the launches the CALLING THREAD would make now (its CU share): cdfo_align_stats and the channel-sum output of
+// cdfo_conv1x1_bf16x3 use the same cut of the tile stream
+extern "C" int cdfo_align_stats_slots(int B, long long P) {
+  const int cus = cdfo_num_cus();
+  if (cus <= 0) return CDFO_EINVAL;
+  return cdfo_stream_slots_for_grid(B, P, cus);
+}
+
+extern "C" int cdfo_align_stats(const float* x0, int ld0, const float* x1, int ld1, const float* q, int ldq, const float* w_packed,
+                                const float* bias, int act, int ch_per_head, int B, long long P, int nslots, float* gram_partial,
+                                float* sum0_partial, float* sum1_partial, void* stream) {
+  if (B <= 0 || P <= 0 || nslots <= 0 || !x0 || !x1 || !q || !w_packed || !gram_partial || !sum0_partial || !sum1_partial) return CDFO_EINVAL;
+  if (act != CDFO_ACT_NONE && act != CDFO_ACT_LRELU && act != CDFO_ACT_RELU) return CDFO_EINVAL;
+  if (ch_per_head != 8 && ch_per_head != 16) return CDFO_EINVAL;
+  const int lds_[3] = {ld0, ld1, ldq};
+  for (int i = 0; i < 3; ++i)
+    if (lds_[i] < 64 || lds_[i] % 4 || (long long)lds_[i] * 4 * 32 >= (1ll << 31)) return CDFO_EINVAL;
+  if (!aligned16(x0) || !aligned16(x1) || !aligned16(q) || !aligned16(w_packed) || !aligned16(gram_partial) || !aligned16(sum0_partial) ||
+      !aligned16(sum1_partial))
+    return CDFO_EALIGN;
+  if ((P + 127) / 128 > 0x7fffffff / 2) return CDFO_EINVAL;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  sg_args s{};
+  s.src[0] = {x0, ld0, 0}; s.src[1] = {x1, ld1, 0}; s.src[2] = {q, ldq, 0};
+  s.w = w_packed; s.bias = bias; s.act_fn = act;
+  s.P = P; s.tiles_per_image = (int)((P + 127) / 128); s.tiles = (long long)B * s.tiles_per_image;
+  s.gram = gram_partial; s.sum0 = sum0_partial; s.sum1 = sum1_partial; s.slots = nslots;
+  const int cus = cdfo_num_cus();
+  if (cus <= 0) return CDFO_EINVAL;
+  const int grid = (int)(s.tiles < cus ? s.tiles : cus);
+  if (nslots < st_slots(B, s.tiles_per_image, grid)) return CDFO_EINVAL;
+  const int lds = 2 * (2 * 4 * 2 * 64 * 16) + 64 * 4 + 4 * SG_NS * ST_STAGE;
+  const double px = (double)B * P;
+  CdfoProfScope prof(st, KID_GRAM, px * (2.0 * 128 * 64 + 2.0 * 64 * 18), 4.0 * 192 * px);
+  if (ch_per_head == 16) {
+    static CdfoAttrOnce once;
+    const hipError_t e = cdfo_set_max_lds(once, reinterpret_cast<const void*>(align_gram_partial_kernel<16>), 160 * 1024 - 256);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(align_gram_partial_kernel<16>, dim3(grid), dim3(ST_THREADS), lds, st, s);
+  } else {
+    static CdfoAttrOnce once;
+    const hipError_t e = cdfo_set_max_lds(once, reinterpret_cast<const void*>(align_gram_partial_kernel<8>), 160 * 1024 - 256);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(align_gram_partial_kernel<8>, dim3(grid), dim3(ST_THREADS), lds, st, s);
+  }
+  CDFO_LAUNCH_CHECK();
+  return 0;
+}
 
 // Returns 1 when the streaming kernel took the launch, 0 when the shapes are outside its contract (the caller falls back to
 // cdfo_conv1x1_bf16x3), < 0 / hipError_t on errors.  Same argument block as cdfo_conv1x1_bf16x3.
@@ -492,6 +838,7 @@ int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st) {
   }
   if (a.store_mode != CDFO_STORE_PLAIN || (a.ln_gamma && !ln_out) || a.CoutP % 64 || a.CoutP > 128 || a.Cout % 8) return 0;      // (ln_out without ln_gamma: plain fp16 copy)
   if (ln_out && (a.CoutP != 64 || a.Cout != 64)) return 0;
+  if (a.chan_sum_out && (a.CoutP != 64 || a.Cout != 64 || ln_out || a.chan_sum_slots <= 0)) return 0;   // the caller sums in a pass of its own
   const int ncb = a.CoutP / 64, nkb = a.Cin / 64;
   if (nkb < 1 || nkb > CDFO_MAXSRC * 4) return 0;
   const int w_bytes = 2 * nkb * 4 * 2 * ncb * 64 * 16 + ncb * 64 * 4;
@@ -533,7 +880,15 @@ int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st) {
   const int lds = w_bytes + 4 * ns * ST_STAGE + scale_bytes;
   const double px = (double)a.B * P;
   CdfoProfScope prof(st, KID_CONV1, 2.0 * px * a.Cout * a.Cin, 4.0 * (px * a.Cout * (1 + nr) + px * a.Cin + (double)a.Cin * a.Cout));
-  if (ncb == 1) {
+  if (a.chan_sum_out) {
+    // (checked above: ncb == 1, Cout == 64) the result's channel sums from the epilogue's registers, one slot per (image, workgroup segment)
+    if (a.chan_sum_slots < st_slots(a.B, s.tiles_per_image, grid)) return 0;
+    s.csum = a.chan_sum_out; s.csum_slots = a.chan_sum_slots;
+    static CdfoAttrOnce once;
+    const hipError_t e = cdfo_set_max_lds(once, reinterpret_cast<const void*>(conv1x1_stream_kernel<1, false, true>), 160 * 1024 - 256);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((conv1x1_stream_kernel<1, false, true>), dim3(grid), dim3(ST_THREADS), lds, st, s);
+  } else if (ncb == 1) {
     static CdfoAttrOnce once;
     const hipError_t e = cdfo_set_max_lds(once, reinterpret_cast<const void*>(conv1x1_stream_kernel<1>), 160 * 1024 - 256);
     if (e != hipSuccess) return (int)e;

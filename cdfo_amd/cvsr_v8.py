@@ -162,6 +162,9 @@ class CVSR_V8(nn.Module):
         # (the x2 branch's 256-channel intermediate in half-split rows: the Winograd kernel's lanes then store contiguous runs;
         # measured: no gain in the forward (105.2 vs 105.3 ms), off by default)
         self.wino_halfsplit = switches.get("CDFO_WINO_HS")
+        # DualAttAlignment's statistics in one pass that never writes kf, CALayer's pool from the producing epilogue (see _align;
+        # developer A/B: CDFO_ALIGN_STATS=0 -> the five launches of round 5)
+        self.align_stats = switches.get("CDFO_ALIGN_STATS")
         # fp16x2 mode, the feature extractor's two 3x3 convolutions on the ring kernel: True = activations fp16 hi + lo x
         # weights fp16 hi + lo (three terms, fp32-grade: L1_fea 1.3e-5 max-abs); False = weights rounded once to fp16 (two
         # terms): measured 1.7e-3 on the RETURNED feature cache (|L1_fea| up to 7), outside the 1e-3 bound, for 1.3 ms per
@@ -429,15 +432,25 @@ class CVSR_V8(nn.Module):
         warped = K.empty_act(GB, H, W, NF, xc.device)
         for g, mv in enumerate(mvs):
             K.flow_warp(extra[g * B:(g + 1) * B], mv, mv_bstride, out=warped[g * B:(g + 1) * B])
-        kf = self._conv([warped, pred], w[a + "fusion_out.0"], act=K.ACT_RELU)
-        gp, ng = K.gram_partial(xc, kf, 16)
-        sw, ns = K.chan_sum_partial(warped)
-        sp, _ = K.chan_sum_partial(pred)
+        fused = self.precision != "f32" and self.align_stats
+        if fused:
+            # kf = relu(fusion_out.0([warped, pred])) has one consumer, the Gram: one pass over warped, pred, xc forms it tile by tile
+            # and leaves the Gram and the two channel sums; kf never reaches memory
+            gp, sw, sp, ng = K.align_stats(warped, pred, xc, w[a + "fusion_out.0"], K.ACT_RELU, 16)
+            ns = ng
+        else:
+            kf = self._conv([warped, pred], w[a + "fusion_out.0"], act=K.ACT_RELU)
+            gp, ng = K.gram_partial(xc, kf, 16)
+            sw, ns = K.chan_sum_partial(warped)
+            sp, _ = K.chan_sum_partial(pred)
         fold = K.align_fold(gp, ng, sw, sp, ns, H * W, raw[a + "temperature"], raw[a + "conv_du.0.weight"],
                             raw[a + "conv_du.0.bias"], raw[a + "conv_du.2.weight"], raw[a + "conv_du.2.bias"],
                             raw[a + "project_out.weight"], raw[a + "fusion_out.0.weight"])
-        o = self._conv([warped, pred, xc], fold, act=K.ACT_RELU)
-        part, n = K.chan_sum_partial(o)
+        if fused:
+            o, part, n = self._conv([warped, pred, xc], fold, act=K.ACT_RELU, chan_sum_out=True)     # CALayer's pool from the epilogue
+        else:
+            o = self._conv([warped, pred, xc], fold, act=K.ACT_RELU)
+            part, n = K.chan_sum_partial(o)
         gate = K.vec_mlp(part, n, H * W, raw[a + "CALayer.conv_du.0.weight"], raw[a + "CALayer.conv_du.0.bias"], 64,
                          K.ACT_RELU, raw[a + "CALayer.conv_du.2.weight"], raw[a + "CALayer.conv_du.2.bias"], 64,
                          K.ACT_SIGMOID)

@@ -146,14 +146,24 @@ def conv(srcs: Sequence[torch.Tensor], pc: PackedConv, *, stride: int = 1, pad: 
          res1: Optional[torch.Tensor] = None, res2: Optional[torch.Tensor] = None,
          out: Optional[torch.Tensor] = None, prec: int = PREC_F32,
          ln: Optional[tuple] = None, s2d: bool = False, out_f16: bool = False, ln_out: Optional[tuple] = None,
-         res2_scale: Optional[torch.Tensor] = None, cp16_out: bool = False):
-    """cp16_out (1x1, Cout = 64, 16-bit modes): also the fp16 chunk-planar copy [B,4,H,W,16] of the result (to_cp16 of the returned
+         res2_scale: Optional[torch.Tensor] = None, cp16_out: bool = False, chan_sum_out: bool = False):
+    """chan_sum_out (64-channel result): also the per-image channel sums of the result as partials; the call returns (out, part, n)
+    as `chan_sum_partial(out)` would give them (the streaming 1x1 kernel sums in its epilogue, every other path runs that pass).
+    cp16_out (1x1, Cout = 64, 16-bit modes): also the fp16 chunk-planar copy [B,4,H,W,16] of the result (to_cp16 of the returned
     tensor) from the same kernel; the call then returns the pair (out, copy).
     res2_scale [B,H,W]: res2 enters the sum as res2 * res2_scale[pixel] (streaming 1x1 kernel only; raises elsewhere).
     ln_out = (gamma, beta) (1x1, Cout = 64, 16-bit modes): also LayerNorm64 of the RESULT as fp16 hi | lo planes
     [B,8,H,W,16] (layernorm64_hl of the returned tensor); the call then returns the pair (out, planes)."""
     if isinstance(srcs, torch.Tensor):
         srcs = [srcs]
+    if chan_sum_out:
+        if cp16_out or ln_out is not None or out_f16 or s2d or pc.shuffle2 or pc.Cout != 64:
+            raise ValueError("conv: chan_sum_out needs a plain fp32 64-channel result")
+        if (prec != PREC_F32 and pc.ks == 1 and stride == 1 and pad == 0 and pc.CoutP == 64 and ln is None
+                and all(s.dtype == torch.float32 and s.shape[3] % 64 == 0 for s in srcs)):
+            return _conv1x1_chan_sum(srcs, pc, act, res1, res2, out, res2_scale)
+        o = conv(srcs, pc, stride=stride, pad=pad, act=act, res1=res1, res2=res2, out=out, prec=prec, ln=ln, res2_scale=res2_scale)
+        return (o, *chan_sum_partial(o))
     a = ConvArgs()
     B = H = W = None
     cin = 0
@@ -250,6 +260,46 @@ def conv(srcs: Sequence[torch.Tensor], pc: PackedConv, *, stride: int = 1, pad: 
 
 def _vp(t):
     return C.c_void_p(None if t is None else t.data_ptr())
+
+
+def _conv1x1_chan_sum(srcs, pc: PackedConv, act, res1, res2, out, res2_scale):
+    """cdfo_conv1x1_bf16x3 with cdfo_conv_args.chan_sum_out (see conv(chan_sum_out=True)): -> (out, part [B, n, 64], n)."""
+    a = ConvArgs()
+    B, H, W, _, _ = _chk_act(srcs[0], "src0")
+    cin = 0
+    for i, s in enumerate(srcs):
+        b_, h_, w_, c_, ld_ = _chk_act(s, f"src{i}")
+        if (B, H, W) != (b_, h_, w_):
+            raise ValueError("conv sources disagree on B/H/W")
+        a.src[i], a.ld[i], a.cs[i] = s.data_ptr(), ld_, c_
+        cin += c_
+    if cin != pc.Cin:
+        raise ValueError(f"conv: sources have {cin} channels, weight expects {pc.Cin}")
+    a.nsrc = len(srcs)
+    a.B, a.H, a.W, a.Ho, a.Wo = B, H, W, H, W
+    a.ks, a.stride, a.pad = 1, 1, 0
+    a.Cin, a.Cout, a.CoutP = pc.Cin, pc.Cout, pc.CoutP
+    a.w, a.w_bstride, a.bias, a.act = pc.w.data_ptr(), pc.w_bstride, _p(pc.bias), act
+    if out is None:
+        out = empty_act(B, H, W, 64, srcs[0].device)
+    _, _, _, _, a.ldo = _chk_act(out, "out")
+    a.out = out.data_ptr()
+    for nm, r in (("res1", res1), ("res2", res2)):
+        if r is not None:
+            rb, rh, rw, rc, rld = _chk_act(r, nm)
+            if (rb, rh, rw) != (B, H, W) or rc < 64:
+                raise ValueError(f"{nm} shape {tuple(r.shape)} does not match the conv output")
+            setattr(a, nm, r.data_ptr())
+            setattr(a, "ldr" + nm[-1], rld)
+    if res2_scale is not None:
+        if res2 is None or tuple(res2_scale.shape) != (B, H, W) or not res2_scale.is_contiguous() or res2_scale.dtype != torch.float32:
+            raise ValueError("conv: res2_scale must be a contiguous fp32 [B,H,W] plane next to res2")
+        a.res2_pixscale = res2_scale.data_ptr()
+    n = align_stats_slots(B, H * W)
+    part = torch.zeros((B, n, 64), dtype=torch.float32, device=out.device)
+    a.chan_sum_out, a.chan_sum_slots = part.data_ptr(), n
+    check(_lib.lib().cdfo_conv1x1_bf16x3(C.byref(a), _stream()), "cdfo_conv1x1_bf16x3 (channel sums)")
+    return out, part, n
 
 
 @contextlib.contextmanager
@@ -947,6 +997,37 @@ def gram_partial(q: torch.Tensor, k: torch.Tensor, ch_per_head: int):
     check(_lib.lib().cdfo_gram_partial(_vp(q), ldq, _vp(k), ldk, B, C.c_longlong(H * W), ch_per_head, n, _vp(part),
                                        _stream()), "cdfo_gram_partial")
     return part, n
+
+
+def align_stats_slots(B: int, P: int) -> int:
+    """Partial slots per image of the persistent streaming kernels' statistics outputs (align_stats, conv(chan_sum_out=True)) for the
+    calling thread's CU share."""
+    n = _lib.lib().cdfo_align_stats_slots(B, C.c_longlong(P))
+    if n <= 0:
+        raise CdfoError(f"cdfo_align_stats_slots({B}, {P}) failed: {n}")
+    return n
+
+
+def align_stats(x0: torch.Tensor, x1: torch.Tensor, q: torch.Tensor, pc: PackedConv, act: int, ch_per_head: int):
+    """The statistics of DualAttAlignment in one pass over x0, x1, q ([B,H,W,64] each, any pixel pitch): with
+    kf = act(conv1x1([x0, x1], pc)) (128 -> 64, never written) returns (gram, sum0, sum1, n) = gram_partial(q, kf, ch_per_head)[0],
+    chan_sum_partial(x0)[0], chan_sum_partial(x1)[0] with n partial slots each (fixed-order sums: run-to-run identical)."""
+    B, H, W, c0, ld0 = _chk_act(x0, "x0")
+    b1, h1, w1, c1, ld1 = _chk_act(x1, "x1")
+    bq, hq, wq, cq, ldq = _chk_act(q, "q")
+    if (b1, h1, w1) != (B, H, W) or (bq, hq, wq) != (B, H, W) or (c0, c1, cq) != (64, 64, 64):
+        raise ValueError("align_stats: three [B,H,W,64] operands expected")
+    if pc.ks != 1 or pc.Cin != 128 or pc.Cout != 64 or pc.CoutP != 64 or pc.w_bstride != 0:
+        raise ValueError("align_stats: a packed 128 -> 64 1x1 convolution expected")
+    n = align_stats_slots(B, H * W)
+    gs = 64 * (ch_per_head + 2)
+    buf = torch.zeros((B * n * (gs + 128),), dtype=torch.float32, device=q.device)     # one fill for the three outputs
+    gram = buf[:B * n * gs].view(B, n, gs)
+    s0 = buf[B * n * gs:B * n * (gs + 64)].view(B, n, 64)
+    s1 = buf[B * n * (gs + 64):].view(B, n, 64)
+    check(_lib.lib().cdfo_align_stats(_vp(x0), ld0, _vp(x1), ld1, _vp(q), ldq, _vp(pc.w), _vp(pc.bias), act, ch_per_head, B,
+                                      C.c_longlong(H * W), n, _vp(gram), _vp(s0), _vp(s1), _stream()), "cdfo_align_stats")
+    return gram, s0, s1, n
 
 
 def mdta_fold(part: torch.Tensor, n: int, temperature: torch.Tensor, proj_w: torch.Tensor) -> PackedConv:

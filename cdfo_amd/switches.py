@@ -53,6 +53,7 @@ TABLE = (
     Switch("CDFO_V7_HEAD_1PASS", 1, ONOFF, "python", "0: MVDualAttAlignment's offset head on two-pass activations (head_one_pass)"),
     Switch("CDFO_V7_OFF0_1PASS", 1, ONOFF, "python", "0: MVDualAttAlignment's conv_offset[0] on two-pass activations (off0_one_pass)"),
     Switch("CDFO_V7_WS_HEAD", 1, ONOFF, "python", "0: MVDualAttAlignment's offset head off the weights-stationary kernel (ws_head)"),
+    Switch("CDFO_ALIGN_STATS", 1, ONOFF, "python", "0: DualAttAlignment's statistics on the five launches of round 5: kf written, Gram and channel sums in passes of their own (model.align_stats)"),
     # --- HIP layer (csrc/) --------------------------------------------------------------------------------------------------
     Switch("CDFO_WS_RING", 1, ONOFF, "hip", "0: Block_.body[0] on the private-halo kernel of rounds 1-2 instead of the ring-fed wave-specialised one"),
     Switch("CDFO_WS_MFMA16", 1, ONOFF, "hip", "0: the ring-fed weights-stationary kernel on v_mfma_f32_32x32x16_f16 instead of 16x16x32"),

@@ -79,6 +79,11 @@ typedef struct {
   int src_halfsplit;           /* cdfo_conv3x3_ring only: the fp16 chunk-planar source's rows are stored as [8-channel half][W][8]
                                  (a row's first halves, then its second halves: what cdfo_conv3x3_c64_wino writes with
                                  CDFO_STORE_S2D_HS, 16 contiguous bytes per lane and pixel) instead of [W][16] */
+  float* chan_sum_out;         /* optional, cdfo_conv1x1_bf16x3 only (plain store, Cout = CoutP = 64): per-image channel sums of the RESULT as
+                                 partials [B][chan_sum_slots][64] in cdfo_chan_sum_partial's layout.  Zeroed by the caller; chan_sum_slots =
+                                 cdfo_align_stats_slots(B, H*W).  The streaming kernel sums in its epilogue (one slot per image and
+                                 workgroup segment, fixed order); any other form runs cdfo_chan_sum_partial(out) with nchunk = chan_sum_slots */
+  int chan_sum_slots;
 } cdfo_conv_args;
 int cdfo_sizeof_conv_args(void);   /* sizeof(cdfo_conv_args) as the library was built: a binding checks its own mirror against it */
 int cdfo_conv_igemm(const cdfo_conv_args* a, void* stream);
@@ -245,6 +250,21 @@ int cdfo_spatial_gate16(const float* in, int ldi, const float* w, const float* b
 int cdfo_chan_sum_partial(const float* in, int ldi, int B, long long P, int nchunk, float* partial, void* stream);
 int cdfo_gram_partial(const float* q, int ldq, const float* k, int ldk, int B, long long P, int ch_per_head, int nchunk,
                       float* partial, void* stream);
+/* DualAttAlignment's statistics in one pass (arch/SIDECVSR_our.py:3455-3480): kf = act(W . [x0; x1] + bias) (1x1, 128 -> 64, split-bf16
+ * MFMA like cdfo_conv1x1_bf16x3) is formed on the fly and never stored; the pass leaves
+ *   gram_partial [B][nslots][64*(ch_per_head+2)]   cdfo_gram_partial(q, kf)'s layout
+ *   sum0_partial / sum1_partial [B][nslots][64]    cdfo_chan_sum_partial(x0) / (x1)'s layout
+ * for cdfo_align_fold (nchunk_g = nchunk_s = nslots).  x0, x1, q: pixel-major fp32 [B][P][ld >= 64] (64 channels each, 16-byte
+ * aligned); w_packed: cdfo_pack_conv_weight's layout of the [64][128] weight; bias optional; act: NONE / LRELU / RELU;
+ * ch_per_head: 8 | 16.  The three outputs are ZEROED BY THE CALLER, nslots >= cdfo_align_stats_slots(B, P): a persistent workgroup
+ * stores its sums over its tiles of an image into its own slot with plain stores (no atomics: run-to-run identical).
+ * cdfo_stream_slots_for_grid / cdfo_stream_slot_of: the slot arithmetic for a grid of `grid` workgroups, host only.  */
+int cdfo_align_stats_slots(int B, long long P);
+int cdfo_stream_slots_for_grid(int B, long long P, int grid);
+int cdfo_stream_slot_of(int B, long long P, int grid, int wg, int b);
+int cdfo_align_stats(const float* x0, int ld0, const float* x1, int ld1, const float* q, int ldq, const float* w_packed,
+                     const float* bias, int act, int ch_per_head, int B, long long P, int nslots, float* gram_partial,
+                     float* sum0_partial, float* sum1_partial, void* stream);
 /* MDTA (arch.py:1555-1575): wout[b] = packed 1x1 weights (64->64) = project_out x blockdiag(softmax(...)). */
 int cdfo_mdta_fold(const float* partial, int nchunk, const float* temperature, const float* proj_w, int B, float* wout,
                    void* stream);
