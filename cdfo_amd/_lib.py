@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 # torch first: its wheel bundles the HIP/HSA runtime (libamdhip64.so.7).  libcdfo_hip.so must bind to THAT copy --
 # the streams and device pointers handed across the C-ABI come from it -- so it has to be in the process before
@@ -25,31 +26,68 @@ class CdfoError(RuntimeError):
     pass
 
 
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cdfo_hip.h")
+
+
+def _header_text(path: str) -> str:
+    return re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+
+
+def _ctype(decl: str, where: str):
+    """A C declaration that starts with its type -> the ctypes type (every pointer crosses as void*)."""
+    if "*" in decl:
+        return C.c_void_p
+    for prefix, ct in (("long long", C.c_longlong), ("float", C.c_float), ("int", C.c_int)):
+        if decl.startswith(prefix):
+            return ct
+    raise CdfoError(f"cannot map C type in {where}: {decl!r}")
+
+
+def header_prototypes(path: str = HEADER_PATH):
+    """Parse include/cdfo_hip.h -> {symbol: (restype, [argtypes])}; the header is the single source of truth."""
+    protos = {}
+    for m in re.finditer(r"(const char\*|long long|int)\s+(cdfo_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _header_text(path)):
+        ret, name, args = m.group(1), m.group(2), m.group(3).strip()
+        at = []
+        if args and args != "void":
+            at = [_ctype(" ".join(a.split()), f"prototype of {name}") for a in args.split(",")]
+        protos[name] = (C.c_char_p if ret.startswith("const char") else C.c_longlong if ret == "long long" else C.c_int, at)
+    return protos
+
+
+def header_conv_args_fields(path: str = HEADER_PATH):
+    """Parse the body of `typedef struct { ... } cdfo_conv_args;` -> ctypes `_fields_`, in declaration order."""
+    text = _header_text(path)
+    m = re.search(r"typedef\s+struct\s*\{([^{}]*)\}\s*cdfo_conv_args\s*;", text)
+    if m is None:
+        raise CdfoError(f"{path} does not define cdfo_conv_args")
+    fields = []
+    for decl in m.group(1).split(";"):
+        decl = " ".join(decl.split())
+        if not decl:
+            continue
+        first, *more = (d.strip() for d in decl.split(","))      # `T a[N]` or `T a, b, c`
+        head = re.fullmatch(r"(.*[\s*])(\w+(?:\[\w+\])?)", first)
+        if head is None:
+            raise CdfoError(f"cannot parse field of cdfo_conv_args: {decl!r}")
+        ct = _ctype(head.group(1), "cdfo_conv_args")
+        for item in (head.group(2), *more):
+            f = re.fullmatch(r"(\w+)(?:\[(\w+)\])?", item)
+            if f is None:
+                raise CdfoError(f"cannot parse field of cdfo_conv_args: {decl!r}")
+            name, dim = f.groups()
+            if dim is not None and not dim.isdigit():
+                d = re.search(rf"#define\s+{dim}\s+(\d+)\s", text)
+                if d is None:
+                    raise CdfoError(f"array bound {dim} of cdfo_conv_args.{name} is not defined in {path}")
+                dim = d.group(1)
+            fields.append((name, ct if dim is None else ct * int(dim)))
+    return fields
+
+
 class ConvArgs(C.Structure):
-    _fields_ = [
-        ("src", C.c_void_p * 8), ("ld", C.c_int * 8), ("cs", C.c_int * 8), ("nsrc", C.c_int),
-        ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Ho", C.c_int), ("Wo", C.c_int),
-        ("ks", C.c_int), ("stride", C.c_int), ("pad", C.c_int),
-        ("Cin", C.c_int), ("Cout", C.c_int), ("CoutP", C.c_int),
-        ("w", C.c_void_p), ("w_bstride", C.c_longlong), ("bias", C.c_void_p),
-        ("act", C.c_int),
-        ("res1", C.c_void_p), ("ldr1", C.c_int),
-        ("res2", C.c_void_p), ("ldr2", C.c_int),
-        ("out", C.c_void_p), ("ldo", C.c_int), ("store_mode", C.c_int),
-        ("prec", C.c_int),
-        ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p),
-        ("tap_mask", C.c_void_p),
-        ("src_f16", C.c_int), ("out_f16", C.c_int),
-        ("out2_cp16", C.c_void_p),
-        ("src_plane_wrap", C.c_int),
-        ("res_up2", C.c_void_p), ("ldru", C.c_int),
-        ("out2_lo", C.c_int),
-        ("mask_out", C.c_void_p), ("flow", C.c_void_p), ("flow_bstride", C.c_longlong), ("off_mag", C.c_float),
-        ("off_accumulate", C.c_int),
-        ("res2_pixscale", C.c_void_p),
-        ("src_halfsplit", C.c_int),
-        ("chan_sum_out", C.c_void_p), ("chan_sum_slots", C.c_int),
-    ]
+    """ctypes mirror of cdfo_conv_args, derived from the header; lib() checks its size against the built library's."""
+    _fields_ = header_conv_args_fields()
 
 
 def lib() -> C.CDLL:
@@ -60,44 +98,24 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: the HIP extension has not been built "
                 "(run `python -m cdfo_amd.build`).  There is no CPU fallback for the product path.")
         switches.check_hip_environment()      # a malformed switch of the library's own is an error here, not a silent default
-        _lib = C.CDLL(LIB_PATH)
+        loaded = C.CDLL(LIB_PATH)
         for name, (restype, argtypes) in header_prototypes().items():
-            fn = getattr(_lib, name)          # AttributeError here = header/library mismatch: fail loudly
+            fn = getattr(loaded, name)        # AttributeError here = header/library mismatch: fail loudly
             fn.restype = restype
             fn.argtypes = argtypes
+        if loaded.cdfo_sizeof_conv_args() != C.sizeof(ConvArgs):
+            raise CdfoError(f"{LIB_PATH} was built with sizeof(cdfo_conv_args) = {loaded.cdfo_sizeof_conv_args()}, "
+                            f"{HEADER_PATH} gives {C.sizeof(ConvArgs)}: rebuild the library")
+        _lib = loaded
     return _lib
-
-
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cdfo_hip.h")
-
-
-def header_prototypes(path: str = HEADER_PATH):
-    """Parse include/cdfo_hip.h -> {symbol: (restype, [argtypes])}; the header is the single source of truth."""
-    import re
-    text = open(path).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    protos = {}
-    for m in re.finditer(r"(const char\*|long long|int)\s+(cdfo_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        ret, name, args = m.group(1), m.group(2), m.group(3).strip()
-        at = []
-        if args and args != "void":
-            for a in args.split(","):
-                a = " ".join(a.split())
-                if "*" in a:
-                    at.append(C.c_void_p)
-                elif a.startswith("long long"):
-                    at.append(C.c_longlong)
-                elif a.startswith("float"):
-                    at.append(C.c_float)
-                elif a.startswith("int"):
-                    at.append(C.c_int)
-                else:
-                    raise CdfoError(f"cannot map C type in prototype of {name}: {a!r}")
-        protos[name] = (C.c_char_p if ret.startswith("const char") else C.c_longlong if ret == "long long" else C.c_int, at)
-    return protos
 
 
 def check(status: int, what: str) -> None:
     if status != 0:
         kind = {-1: "invalid argument", -2: "misaligned pointer/pitch"}.get(status, f"hipError_t {status}")
         raise CdfoError(f"{what} failed: {kind}")
+
+
+def _vp(t) -> C.c_void_p:
+    """A tensor's device pointer, or NULL for None, as a C-ABI pointer argument."""
+    return C.c_void_p(None if t is None else t.data_ptr())

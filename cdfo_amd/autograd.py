@@ -20,8 +20,8 @@ from torch.autograd import Function
 
 from . import _lib, switches
 from . import kernels as K
-from ._lib import check
-from .kernels import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, PackedConv, _stream, _vp
+from ._lib import _vp, check
+from .kernels import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, PackedConv, _stream
 
 F32 = K.PREC_F32
 # Arithmetic of the training path's convolutions -- `CONV_PREC`, read at every call.

@@ -23,9 +23,9 @@ from . import _lib
 from . import autograd as A
 from . import kernels as K
 from . import nchw_autograd as G
-from ._lib import check
+from ._lib import _vp, check
 from .cvsr_v8_train import _pixel_shuffle_nhwc
-from .kernels import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, _stream, _vp
+from .kernels import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, _stream
 
 NF, NFRAMES = 64, 7
 

@@ -34,6 +34,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import _lib, switches
+from ._lib import _vp
 from .kernels import _stream, on_device
 
 # Forward arithmetic of the float operator.  False (default): shapes the fused fast kernels cover run on split-fp16 MFMA
@@ -123,10 +124,6 @@ def release_workspaces() -> None:
     _Scratch.release()
 
 
-def _ptr(t):
-    return C.c_void_p(None if t is None else t.data_ptr())
-
-
 def _operand_dtype(*tensors) -> int:
     """Device tensors of ONE of the reference's three element types (AT_DISPATCH_FLOATING_TYPES_AND_HALF,
     deform_conv_cuda_kernel.cu:258) -> the library's dtype tag."""
@@ -187,8 +184,8 @@ def launch_forward(x, offset, mask, weight, bias, out, geo: Geometry) -> None:
         if EXACT_FP32 and dt == 0:
             nbytes = x.numel() * 4      # room for the group-planar copy only: less than the fast kernels ask for
         ws = _Scratch.get(x.device, nbytes)
-        _lib.check(L.cdfo_dcn_forward_dt(dt, _ptr(x), _ptr(offset), _ptr(mask), _ptr(weight), _ptr(bias), _ptr(out), B, Cin,
-                                         H, W, Co, *geo.c_args(), _ptr(ws), C.c_longlong(nbytes), _stream()),
+        _lib.check(L.cdfo_dcn_forward_dt(dt, _vp(x), _vp(offset), _vp(mask), _vp(weight), _vp(bias), _vp(out), B, Cin,
+                                         H, W, Co, *geo.c_args(), _vp(ws), C.c_longlong(nbytes), _stream()),
                    "cdfo_dcn_forward_dt")
 
 
@@ -219,9 +216,9 @@ def launch_backward(x, offset, mask, weight, grad_out, geo: Geometry, *, grad_x=
         if nbytes < 0:
             raise RuntimeError("deformable convolution (HIP): unsupported shape")
         ws = _Scratch.get(x.device, nbytes)
-        _lib.check(L.cdfo_dcn_backward_dt(dt, _ptr(x), _ptr(offset), _ptr(mask), _ptr(weight), _ptr(grad_out), _ptr(grad_x),
-                                          _ptr(grad_offset), _ptr(grad_mask), _ptr(grad_weight), _ptr(grad_bias), B, Cin, H,
-                                          W, Co, *geo.c_args(), float(scale), _ptr(ws), C.c_longlong(nbytes), _stream()),
+        _lib.check(L.cdfo_dcn_backward_dt(dt, _vp(x), _vp(offset), _vp(mask), _vp(weight), _vp(grad_out), _vp(grad_x),
+                                          _vp(grad_offset), _vp(grad_mask), _vp(grad_weight), _vp(grad_bias), B, Cin, H,
+                                          W, Co, *geo.c_args(), float(scale), _vp(ws), C.c_longlong(nbytes), _stream()),
                    "cdfo_dcn_backward_dt")
 
 

@@ -13,7 +13,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib, switches
-from ._lib import CdfoError, ConvArgs, check
+from ._lib import CdfoError, ConvArgs, _vp, check
 
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3
 PREC_F32, PREC_BF16X3, PREC_BF16, PREC_FP16X2, PREC_FP16, PREC_FP16X1 = 0, 1, 2, 3, 4, 5
@@ -31,10 +31,6 @@ def on_device(t: torch.Tensor):
     if not t.is_cuda:
         raise NotImplementedError("the HIP path needs device tensors (there is no CPU fallback)")
     return torch.cuda.device(t.device)
-
-
-def _p(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
 
 
 def _chk_act(t: torch.Tensor, name: str = "tensor", dtype=torch.float32):
@@ -142,6 +138,111 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor], shuffle2: bool
     return pc
 
 
+def _chk_cp16(src: torch.Tensor, who: str, planes: Optional[int] = 4):
+    """src: fp16 chunk-planar [B, planes, H, W, 16] on the device (planes=None: any count) -> (B, planes, H, W)."""
+    if not src.is_cuda:
+        raise NotImplementedError(f"{who}: the HIP path needs device tensors (no CPU fallback)")
+    if (src.dtype != torch.float16 or src.dim() != 5 or src.shape[1] != (planes or src.shape[1]) or src.shape[4] != 16
+            or not src.is_contiguous()):
+        raise ValueError(f"{who}: expected a contiguous fp16 [B,{planes or 'C/16'},H,W,16] source, got {src.dtype} {tuple(src.shape)}")
+    return tuple(src.shape[:4])
+
+
+def _cp16_out(out: Optional[torch.Tensor], shape: tuple, device, who: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=torch.float16, device=device)
+    if out.shape != shape or out.dtype != torch.float16 or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous fp16 tensor of shape {shape}")
+    return out
+
+
+def _batch_slices(B: int, H: int, W: int, who: str):
+    """The weights-stationary kernels address their [nb,4,H,W,16] fp16 source with 32-bit buffer offsets (< 2 GiB per launch):
+    the batch in slices that fit."""
+    limit = (1 << 31)
+    per_img = 4 * H * W * 32
+    if per_img >= limit:
+        raise ValueError(f"{who}: one {H}x{W} image exceeds the 2 GiB source limit of a launch")
+    step = max(1, min(B, (limit - 1) // per_img))
+    for b0 in range(0, B, step):
+        yield slice(b0, min(B, b0 + step))
+
+
+def _offmask_ok(offset: torch.Tensor, mask: torch.Tensor, flow: torch.Tensor, B: int, third: int, H: int, W: int) -> bool:
+    """The DCN operator's inputs of conv_offset_mask[_ws]: contiguous fp32 offset [B,2 third,H,W], mask [B,third,H,W], flow [B,2,H,W]."""
+    return (tuple(offset.shape) == (B, 2 * third, H, W) and tuple(mask.shape) == (B, third, H, W) and tuple(flow.shape) == (B, 2, H, W)
+            and all(t.is_contiguous() and t.dtype == torch.float32 for t in (offset, mask, flow)))
+
+
+def _bind_res(res1: Optional[torch.Tensor], res2: Optional[torch.Tensor], B: int, Ho: int, Wo: int, Cout: int,
+              a: Optional[ConvArgs] = None):
+    """res1 / res2: fp32 pixel-major [B,Ho,Wo,>= Cout] or None -> their pitches (0 for None), also bound in `a` if given."""
+    lds = [0, 0]
+    for i, (nm, r) in enumerate((("res1", res1), ("res2", res2))):
+        if r is not None:
+            rb, rh, rw, rc, lds[i] = _chk_act(r, nm)
+            if (rb, rh, rw) != (B, Ho, Wo) or rc < Cout:
+                raise ValueError(f"{nm} shape {tuple(r.shape)} does not match the conv output")
+            if a is not None:
+                setattr(a, nm, r.data_ptr())
+                setattr(a, "ldr" + nm[-1], lds[i])
+    return lds
+
+
+def _bind_res2_scale(a: ConvArgs, res2: Optional[torch.Tensor], res2_scale: Optional[torch.Tensor]) -> None:
+    if res2_scale is not None:
+        if (res2 is None or tuple(res2_scale.shape) != (a.B, a.Ho, a.Wo) or not res2_scale.is_contiguous()
+                or res2_scale.dtype != torch.float32):
+            raise ValueError("conv: res2_scale must be a contiguous fp32 [B,H,W] plane next to res2")
+        a.res2_pixscale = res2_scale.data_ptr()
+
+
+def _conv_args(srcs, pc: PackedConv, *, stride: int = 1, pad: int = 0, act: int = ACT_NONE, src_dtype=torch.float32,
+               cp16: bool = False, store_mode: int = 0, out: Optional[torch.Tensor] = None, out_f16: bool = False,
+               ldo: Optional[int] = None):
+    """The one place that fills cdfo_conv_args: sources, geometry, weight / bias / activation, output -> (args, out).
+    srcs: pixel-major tensors of src_dtype (validated here), or with cp16 ONE fp16 chunk-planar tensor that passed _chk_cp16.
+    out=None allocates the tensor that store_mode writes; ldo: the pitch of an `out` that is no pixel-major activation (the caller
+    has checked it).  The weight is pc's fp32 packing; a caller on another packing overwrites w / CoutP, and sets every field
+    beyond these itself (a zero field = feature off)."""
+    a = ConvArgs()
+    if cp16:
+        B, _, H, W, _ = srcs.shape
+        device = srcs.device
+        a.src[0], a.ld[0], a.cs[0], a.nsrc = srcs.data_ptr(), 16, pc.Cin, 1
+    else:
+        B = H = W = None
+        cin = 0
+        for i, s in enumerate(srcs):
+            b_, h_, w_, c_, ld_ = _chk_act(s, f"src{i}", src_dtype)
+            if B is None:
+                B, H, W = b_, h_, w_
+            elif (B, H, W) != (b_, h_, w_):
+                raise ValueError("conv sources disagree on B/H/W")
+            a.src[i], a.ld[i], a.cs[i] = s.data_ptr(), ld_, c_
+            cin += c_
+        if cin != pc.Cin:
+            raise ValueError(f"conv: sources have {cin} channels, weight expects {pc.Cin}")
+        device = srcs[0].device
+        a.nsrc = len(srcs)
+    Ho = (H + 2 * pad - pc.ks) // stride + 1
+    Wo = (W + 2 * pad - pc.ks) // stride + 1
+    a.B, a.H, a.W, a.Ho, a.Wo = B, H, W, Ho, Wo
+    a.ks, a.stride, a.pad = pc.ks, stride, pad
+    a.Cin, a.Cout, a.CoutP = pc.Cin, pc.Cout, pc.CoutP
+    a.w, a.w_bstride, a.bias, a.act = pc.w.data_ptr(), pc.w_bstride, _vp(pc.bias), act
+    a.src_f16, a.out_f16, a.store_mode = int(cp16 or src_dtype == torch.float16), int(out_f16), store_mode
+    if ldo is None:
+        odt = torch.float16 if out_f16 else torch.float32
+        if out is None:    # CDFO_STORE_PLAIN, _SHUFFLE2, _S2D, _TAPS9
+            shape = ((B, Ho, Wo, pc.Cout), (B, 2 * Ho, 2 * Wo, pc.Cout // 4), (B, Ho // 2, Wo // 2, 4 * pc.Cout),
+                     (B, 2 * Ho, 2 * Wo, 12))[store_mode]
+            out = torch.empty(shape, dtype=odt, device=device)
+        _, _, _, _, ldo = _chk_act(out, "out", odt)
+    a.out, a.ldo = out.data_ptr(), ldo
+    return a, out
+
+
 def conv(srcs: Sequence[torch.Tensor], pc: PackedConv, *, stride: int = 1, pad: int = 0, act: int = ACT_NONE,
          res1: Optional[torch.Tensor] = None, res2: Optional[torch.Tensor] = None,
          out: Optional[torch.Tensor] = None, prec: int = PREC_F32,
@@ -159,78 +260,29 @@ def conv(srcs: Sequence[torch.Tensor], pc: PackedConv, *, stride: int = 1, pad: 
     if chan_sum_out:
         if cp16_out or ln_out is not None or out_f16 or s2d or pc.shuffle2 or pc.Cout != 64:
             raise ValueError("conv: chan_sum_out needs a plain fp32 64-channel result")
-        if (prec != PREC_F32 and pc.ks == 1 and stride == 1 and pad == 0 and pc.CoutP == 64 and ln is None
+        if not (prec != PREC_F32 and pc.ks == 1 and stride == 1 and pad == 0 and pc.CoutP == 64 and ln is None
                 and all(s.dtype == torch.float32 and s.shape[3] % 64 == 0 for s in srcs)):
-            return _conv1x1_chan_sum(srcs, pc, act, res1, res2, out, res2_scale)
-        o = conv(srcs, pc, stride=stride, pad=pad, act=act, res1=res1, res2=res2, out=out, prec=prec, ln=ln, res2_scale=res2_scale)
-        return (o, *chan_sum_partial(o))
-    a = ConvArgs()
-    B = H = W = None
-    cin = 0
+            o = conv(srcs, pc, stride=stride, pad=pad, act=act, res1=res1, res2=res2, out=out, prec=prec, ln=ln, res2_scale=res2_scale)
+            return (o, *chan_sum_partial(o))
     src_f16 = srcs[0].dtype == torch.float16       # Block_'s fp16 body intermediate (single source, 1-pass fp16 MFMA)
     if src_f16:
         prec = PREC_FP16
     elif prec == PREC_FP16:
         raise ValueError("PREC_FP16 needs an fp16 source tensor")
-    odt = torch.float16 if out_f16 else torch.float32
-    for i, s in enumerate(srcs):
-        b_, h_, w_, c_, ld_ = _chk_act(s, f"src{i}", torch.float16 if src_f16 else torch.float32)
-        if B is None:
-            B, H, W = b_, h_, w_
-        elif (B, H, W) != (b_, h_, w_):
-            raise ValueError("conv sources disagree on B/H/W")
-        a.src[i] = s.data_ptr()
-        a.ld[i] = ld_
-        a.cs[i] = c_
-        cin += c_
-    if cin != pc.Cin:
-        raise ValueError(f"conv: sources have {cin} channels, weight expects {pc.Cin}")
-    a.nsrc = len(srcs)
-    Ho = (H + 2 * pad - pc.ks) // stride + 1
-    Wo = (W + 2 * pad - pc.ks) // stride + 1
-    a.B, a.H, a.W, a.Ho, a.Wo = B, H, W, Ho, Wo
-    a.ks, a.stride, a.pad = pc.ks, stride, pad
-    a.Cin, a.Cout, a.CoutP = pc.Cin, pc.Cout, pc.CoutP
-    a.w = pc.w.data_ptr()
-    a.w_bstride = pc.w_bstride
-    a.bias = _p(pc.bias)
-    a.act = act
-    if pc.shuffle2:
-        if out is None:
-            out = empty_act(B, 2 * Ho, 2 * Wo, pc.Cout // 4, srcs[0].device)
-        a.store_mode = 1
-    elif s2d:
-        if out is None:
-            out = torch.empty((B, Ho // 2, Wo // 2, 4 * pc.Cout), dtype=odt, device=srcs[0].device)
-        a.store_mode = 2
-    else:
-        if out is None:
-            out = torch.empty((B, Ho, Wo, pc.Cout), dtype=odt, device=srcs[0].device)
-        a.store_mode = 0
-    _, _, _, _, a.ldo = _chk_act(out, "out", odt)
-    a.src_f16, a.out_f16 = int(src_f16), int(out_f16)
-    a.out = out.data_ptr()
-    for nm, r in (("res1", res1), ("res2", res2)):
-        if r is not None:
-            rb, rh, rw, rc, rld = _chk_act(r, nm)
-            if (rb, rh, rw) != (B, Ho, Wo) or rc < pc.Cout:
-                raise ValueError(f"{nm} shape {tuple(r.shape)} does not match the conv output")
-            setattr(a, nm, r.data_ptr())
-            setattr(a, "ldr" + nm[-1], rld)
-    if res2_scale is not None:
-        if res2 is None or tuple(res2_scale.shape) != (B, Ho, Wo) or not res2_scale.is_contiguous() or res2_scale.dtype != torch.float32:
-            raise ValueError("conv: res2_scale must be a contiguous fp32 [B,H,W] plane next to res2")
-        a.res2_pixscale = res2_scale.data_ptr()
+    a, out = _conv_args(srcs, pc, stride=stride, pad=pad, act=act, src_dtype=torch.float16 if src_f16 else torch.float32,
+                        store_mode=1 if pc.shuffle2 else 2 if s2d else 0, out=out, out_f16=out_f16)
+    B, Ho, Wo = a.B, a.Ho, a.Wo
+    _bind_res(res1, res2, B, Ho, Wo, pc.Cout, a)
+    _bind_res2_scale(a, res2, res2_scale)
     if (prec != PREC_F32 and pc.wq is not None and stride == 1 and pad == 1 and pc.w_bstride == 0):
         a.prec = prec
         a.CoutP = pc.CoutP16
         a.w = (pc.wh if prec in (PREC_FP16X2, PREC_FP16, PREC_FP16X1) else pc.wq).data_ptr()
-        a.tap_mask = _p(pc.tap_mask)
+        a.tap_mask = _vp(pc.tap_mask)
         check(_lib.lib().cdfo_conv3x3_bf16(C.byref(a), _stream()), "cdfo_conv3x3_bf16")
         return out
     if src_f16 or out_f16:
         raise ValueError("fp16 tensors are only supported by the 16-bit MFMA 3x3 kernel")
-    a.prec = 0
     if ln is not None:
         a.ln_gamma, a.ln_beta = ln[0].data_ptr(), ln[1].data_ptr()
     if (prec != PREC_F32 and pc.ks == 1 and stride == 1 and pad == 0 and pc.CoutP % 64 == 0 and pc.CoutP <= 256
@@ -242,6 +294,12 @@ def conv(srcs: Sequence[torch.Tensor], pc: PackedConv, *, stride: int = 1, pad: 
             a.out2_cp16 = copy.data_ptr()
             check(_lib.lib().cdfo_conv1x1_bf16x3(C.byref(a), _stream()), "cdfo_conv1x1_bf16x3")
             return out, copy
+        if chan_sum_out:
+            n = align_stats_slots(B, Ho * Wo)
+            part = torch.zeros((B, n, 64), dtype=torch.float32, device=out.device)
+            a.chan_sum_out, a.chan_sum_slots = part.data_ptr(), n
+            check(_lib.lib().cdfo_conv1x1_bf16x3(C.byref(a), _stream()), "cdfo_conv1x1_bf16x3")
+            return out, part, n
         planes = None
         if ln_out is not None and pc.Cout == 64 and pc.CoutP == 64 and ln is None:
             planes = torch.empty((B, 8, Ho, Wo, 16), dtype=torch.float16, device=out.device)
@@ -256,50 +314,6 @@ def conv(srcs: Sequence[torch.Tensor], pc: PackedConv, *, stride: int = 1, pad: 
     if cp16_out:
         return out, to_cp16(out)
     return out
-
-
-def _vp(t):
-    return C.c_void_p(None if t is None else t.data_ptr())
-
-
-def _conv1x1_chan_sum(srcs, pc: PackedConv, act, res1, res2, out, res2_scale):
-    """cdfo_conv1x1_bf16x3 with cdfo_conv_args.chan_sum_out (see conv(chan_sum_out=True)): -> (out, part [B, n, 64], n)."""
-    a = ConvArgs()
-    B, H, W, _, _ = _chk_act(srcs[0], "src0")
-    cin = 0
-    for i, s in enumerate(srcs):
-        b_, h_, w_, c_, ld_ = _chk_act(s, f"src{i}")
-        if (B, H, W) != (b_, h_, w_):
-            raise ValueError("conv sources disagree on B/H/W")
-        a.src[i], a.ld[i], a.cs[i] = s.data_ptr(), ld_, c_
-        cin += c_
-    if cin != pc.Cin:
-        raise ValueError(f"conv: sources have {cin} channels, weight expects {pc.Cin}")
-    a.nsrc = len(srcs)
-    a.B, a.H, a.W, a.Ho, a.Wo = B, H, W, H, W
-    a.ks, a.stride, a.pad = 1, 1, 0
-    a.Cin, a.Cout, a.CoutP = pc.Cin, pc.Cout, pc.CoutP
-    a.w, a.w_bstride, a.bias, a.act = pc.w.data_ptr(), pc.w_bstride, _p(pc.bias), act
-    if out is None:
-        out = empty_act(B, H, W, 64, srcs[0].device)
-    _, _, _, _, a.ldo = _chk_act(out, "out")
-    a.out = out.data_ptr()
-    for nm, r in (("res1", res1), ("res2", res2)):
-        if r is not None:
-            rb, rh, rw, rc, rld = _chk_act(r, nm)
-            if (rb, rh, rw) != (B, H, W) or rc < 64:
-                raise ValueError(f"{nm} shape {tuple(r.shape)} does not match the conv output")
-            setattr(a, nm, r.data_ptr())
-            setattr(a, "ldr" + nm[-1], rld)
-    if res2_scale is not None:
-        if res2 is None or tuple(res2_scale.shape) != (B, H, W) or not res2_scale.is_contiguous() or res2_scale.dtype != torch.float32:
-            raise ValueError("conv: res2_scale must be a contiguous fp32 [B,H,W] plane next to res2")
-        a.res2_pixscale = res2_scale.data_ptr()
-    n = align_stats_slots(B, H * W)
-    part = torch.zeros((B, n, 64), dtype=torch.float32, device=out.device)
-    a.chan_sum_out, a.chan_sum_slots = part.data_ptr(), n
-    check(_lib.lib().cdfo_conv1x1_bf16x3(C.byref(a), _stream()), "cdfo_conv1x1_bf16x3 (channel sums)")
-    return out, part, n
 
 
 @contextlib.contextmanager
@@ -318,22 +332,13 @@ def conv_offset_mask(src: torch.Tensor, pc: PackedConv, offset: torch.Tensor, ma
     epilogue (CDFO_STORE_OFFMASK): src pixel-major [B,H,W,64]; offset [B,18 dg,H,W] / mask [B,9 dg,H,W] NCHW = the DCN operator's
     inputs; flow [B,2,H,W] contiguous.  accumulate=False: the first head (offset = mag tanh + flipped flow, mask = raw sums);
     accumulate=True: the second head in place (offset += mag tanh, mask = sigmoid(mask + sums)).  W % 4 == 0, 16-bit modes only."""
-    B, H, W, Cc, ld = _chk_act(src)
-    third = pc.Cout // 3
-    if (pc.ks != 3 or Cc != pc.Cin or pc.Cout % 3 or pc.wq is None or W % 4 or prec not in (PREC_BF16X3, PREC_FP16X2, PREC_FP16X1)
-            or tuple(offset.shape) != (B, 2 * third, H, W) or tuple(mask.shape) != (B, third, H, W) or tuple(flow.shape) != (B, 2, H, W)
-            or not (offset.is_contiguous() and mask.is_contiguous() and flow.is_contiguous())
-            or any(t.dtype != torch.float32 for t in (offset, mask, flow))):
+    a, _ = _conv_args([src], pc, pad=1, store_mode=4, out=offset, ldo=4)
+    B, H, W = a.B, a.H, a.W
+    if (pc.ks != 3 or pc.Cout % 3 or pc.wq is None or W % 4 or prec not in (PREC_BF16X3, PREC_FP16X2, PREC_FP16X1)
+            or not _offmask_ok(offset, mask, flow, B, pc.Cout // 3, H, W)):
         raise ValueError("conv_offset_mask: unsupported configuration")
-    a = ConvArgs()
-    a.src[0], a.ld[0], a.cs[0], a.nsrc = src.data_ptr(), ld, Cc, 1
-    a.B, a.H, a.W, a.Ho, a.Wo = B, H, W, H, W
-    a.ks, a.stride, a.pad = 3, 1, 1
-    a.Cin, a.Cout, a.CoutP = pc.Cin, pc.Cout, pc.CoutP16
+    a.CoutP, a.prec = pc.CoutP16, prec
     a.w = (pc.wh if prec in (PREC_FP16X2, PREC_FP16X1) else pc.wq).data_ptr()
-    a.bias = _p(pc.bias)
-    a.act, a.prec, a.store_mode = ACT_NONE, prec, 4
-    a.out, a.ldo = offset.data_ptr(), 4
     a.mask_out, a.flow, a.flow_bstride = mask.data_ptr(), flow.data_ptr(), 2 * H * W
     a.off_mag, a.off_accumulate = float(mag), int(accumulate)
     check(_lib.lib().cdfo_conv3x3_bf16(C.byref(a), _stream()), "cdfo_conv3x3_bf16 (offset / mask epilogue)")
@@ -374,27 +379,14 @@ def conv3x3_ws(src: torch.Tensor, pc: PackedConv, *, act: int = ACT_NONE, s2d: b
     """Block_.body[0]-shaped convolution (3x3, 64 input channels, Cout % 64 == 0) on the weights-stationary kernel.
     src: fp16 chunk-planar [B,4,H,W,16]; result: fp16 chunk-planar [B,Cout/16,H,W,16], or with s2d its space-to-depth
     form [B,4*Cout/16,H/2,W/2,16] (chunk = phase*Cout/16 + channel/16, phase = (y&1)*2 + (x&1))."""
-    if not src.is_cuda:
-        raise NotImplementedError("conv3x3_ws: the HIP path needs device tensors (no CPU fallback)")
-    if src.dtype != torch.float16 or src.dim() != 5 or src.shape[1] != 4 or src.shape[4] != 16 or not src.is_contiguous():
-        raise ValueError(f"conv3x3_ws: expected a contiguous fp16 [B,4,H,W,16] source, got {src.dtype} {tuple(src.shape)}")
+    B, _, H, W = _chk_cp16(src, "conv3x3_ws")
     if pc.wh is None or pc.Cin != 64 or pc.ks != 3 or pc.Cout % 64:
         raise ValueError("conv3x3_ws: needs a 3x3 weight with 64 input channels and Cout % 64 == 0")
-    B, _, H, W, _ = src.shape
     shape = (B, pc.Cout // 4, H // 2, W // 2, 16) if s2d else (B, pc.Cout // 16, H, W, 16)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float16, device=src.device)
-    elif out.shape != shape or out.dtype != torch.float16 or not out.is_contiguous():
-        raise ValueError(f"conv3x3_ws: out must be a contiguous fp16 tensor of shape {shape}")
-    # the kernel addresses its source with 32-bit buffer offsets (< 2 GiB per launch): split the batch if needed
-    per_img = 4 * H * W * 32
-    step = max(1, min(B, ((1 << 31) - 1) // per_img))
-    if per_img >= (1 << 31):
-        raise ValueError(f"conv3x3_ws: one {H}x{W} image exceeds the 2 GiB source limit of a launch")
-    for b0 in range(0, B, step):
-        nb = min(step, B - b0)
-        check(_lib.lib().cdfo_conv3x3_c64_ws(_vp(src[b0:b0 + nb]), nb, H, W, _vp(pc.wh), pc.CoutP16, _vp(pc.bias), pc.Cout,
-                                             act, _vp(out[b0:b0 + nb]), 2 if s2d else 0, dbg, _vp(clk), _stream()),
+    out = _cp16_out(out, shape, src.device, "conv3x3_ws")
+    for sl in _batch_slices(B, H, W, "conv3x3_ws"):
+        check(_lib.lib().cdfo_conv3x3_c64_ws(_vp(src[sl]), sl.stop - sl.start, H, W, _vp(pc.wh), pc.CoutP16, _vp(pc.bias), pc.Cout,
+                                             act, _vp(out[sl]), 2 if s2d else 0, dbg, _vp(clk), _stream()),
               "cdfo_conv3x3_c64_ws")
     return out
 
@@ -413,18 +405,11 @@ def halfsplit_to_rows(t: torch.Tensor) -> torch.Tensor:
 def conv3x3_wino(src: torch.Tensor, pc: PackedConv, *, act: int = ACT_NONE, s2d: bool = False,
                  out: Optional[torch.Tensor] = None, dbg: int = 0, halfsplit: bool = False, clk: Optional[torch.Tensor] = None) -> torch.Tensor:
     """conv3x3_ws's operands and result on the row-streaming Winograd F(2,3) kernel (cdfo_conv3x3_c64_wino): Cout % 128 == 0, W even."""
-    if not src.is_cuda:
-        raise NotImplementedError("conv3x3_wino: the HIP path needs device tensors (no CPU fallback)")
-    if src.dtype != torch.float16 or src.dim() != 5 or src.shape[1] != 4 or src.shape[4] != 16 or not src.is_contiguous():
-        raise ValueError(f"conv3x3_wino: expected a contiguous fp16 [B,4,H,W,16] source, got {src.dtype} {tuple(src.shape)}")
+    B, _, H, W = _chk_cp16(src, "conv3x3_wino")
     if pc.ww is None:
         raise ValueError("conv3x3_wino: needs a 3x3 weight with 64 input channels and Cout % 128 == 0")
-    B, _, H, W, _ = src.shape
     shape = (B, pc.Cout // 4, H // 2, W // 2, 16) if s2d else (B, pc.Cout // 16, H, W, 16)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float16, device=src.device)
-    elif out.shape != shape or out.dtype != torch.float16 or not out.is_contiguous():
-        raise ValueError(f"conv3x3_wino: out must be a contiguous fp16 tensor of shape {shape}")
+    out = _cp16_out(out, shape, src.device, "conv3x3_wino")
     if halfsplit and not s2d:
         raise ValueError("conv3x3_wino: half-split rows exist for the space-to-depth store only")
     mode = (5 if halfsplit else 2) if s2d else 0
@@ -446,11 +431,7 @@ def conv3x3_wino_up2(src_lr: torch.Tensor, pc: PackedConv, *, act: int = ACT_NON
     """Block_.body[0] on the bilinear x2 of src_lr (fp16 chunk-planar [B,4,h,w,16], h and w even) without materialising it: the
     interpolation is folded into the Winograd kernel's input transform (cdfo_conv3x3_c64_wino_up2).  Result: the space-to-depth form
     [B, 4*Cout/16, h, w, 16] of the [B, Cout/16, 2h, 2w, 16] convolution output, as conv3x3_wino(..., s2d=True)."""
-    if not src_lr.is_cuda:
-        raise NotImplementedError("conv3x3_wino_up2: the HIP path needs device tensors (no CPU fallback)")
-    if src_lr.dtype != torch.float16 or src_lr.dim() != 5 or src_lr.shape[1] != 4 or src_lr.shape[4] != 16 or not src_lr.is_contiguous():
-        raise ValueError(f"conv3x3_wino_up2: expected a contiguous fp16 [B,4,h,w,16] source, got {src_lr.dtype} {tuple(src_lr.shape)}")
-    B, _, h, w, _ = src_lr.shape
+    B, _, h, w = _chk_cp16(src_lr, "conv3x3_wino_up2")
     if pc.ww is None or h % 2 or w % 2:
         raise ValueError("conv3x3_wino_up2: needs a Winograd weight image (Cout % 128 == 0) and even low-resolution sizes")
     out = torch.empty((B, pc.Cout // 4, h, w, 16), dtype=torch.float16, device=src_lr.device)
@@ -477,14 +458,10 @@ def conv_offset_mask_ws(src: torch.Tensor, pc: PackedConv, offset: torch.Tensor,
                         accumulate: bool) -> None:
     """conv_offset_mask on the weights-stationary kernel (single-pass fp16 operands): src fp16 chunk-planar [B,4,H,W,16]; the rest as
     conv_offset_mask.  H even, 18 dg a multiple of 32 (dg = 16: 288)."""
-    if src.dtype != torch.float16 or src.dim() != 5 or src.shape[1] != 4 or src.shape[4] != 16 or not src.is_contiguous():
-        raise ValueError(f"conv_offset_mask_ws: expected a contiguous fp16 [B,4,H,W,16] source, got {src.dtype} {tuple(src.shape)}")
-    B, _, H, W, _ = src.shape
+    B, _, H, W = _chk_cp16(src, "conv_offset_mask_ws")
     third = pc.Cout // 3
     if (pc.wh is None or pc.Cin != 64 or pc.ks != 3 or pc.Cout % 3 or H % 2 or (2 * third) % 32 or pc.Cout % 8
-            or tuple(offset.shape) != (B, 2 * third, H, W) or tuple(mask.shape) != (B, third, H, W) or tuple(flow.shape) != (B, 2, H, W)
-            or not (offset.is_contiguous() and mask.is_contiguous() and flow.is_contiguous())
-            or any(t.dtype != torch.float32 for t in (offset, mask, flow)) or not conv_offset_mask_ws_fits(B, H, W, third)):
+            or not _offmask_ok(offset, mask, flow, B, third, H, W) or not conv_offset_mask_ws_fits(B, H, W, third)):
         raise ValueError("conv_offset_mask_ws: unsupported configuration")
     check(_lib.lib().cdfo_conv3x3_c64_ws_offmask(_vp(src), B, H, W, _vp(pc.wh), pc.CoutP16, _vp(pc.bias), pc.Cout, _vp(offset), _vp(mask),
                                                  _vp(flow), C.c_longlong(2 * H * W), float(mag), int(accumulate), _stream()),
@@ -496,36 +473,19 @@ def conv3x3_ws_res(src: torch.Tensor, pc: PackedConv, *, res1: torch.Tensor, res
                    out2_cp16: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Residual form of conv3x3_ws: fp32 pixel-major act(conv + bias) + res1 (+ res2); optionally also the fp16
     chunk-planar copy of the result (out2_cp16 [B,Cout/16,H,W,16])."""
-    if not src.is_cuda:
-        raise NotImplementedError("conv3x3_ws_res: the HIP path needs device tensors (no CPU fallback)")
-    if src.dtype != torch.float16 or src.dim() != 5 or src.shape[1] != 4 or src.shape[4] != 16 or not src.is_contiguous():
-        raise ValueError(f"conv3x3_ws_res: expected a contiguous fp16 [B,4,H,W,16] source, got {src.dtype} {tuple(src.shape)}")
+    B, _, H, W = _chk_cp16(src, "conv3x3_ws_res")
     if pc.wh is None or pc.Cin != 64 or pc.ks != 3 or pc.Cout % 64:
         raise ValueError("conv3x3_ws_res: needs a 3x3 weight with 64 input channels and Cout % 64 == 0")
-    B, _, H, W, _ = src.shape
     if out is None:
         out = empty_act(B, H, W, pc.Cout, src.device)
     _, _, _, _, ldo = _chk_act(out, "out")
-    lds = []
-    for nm, t in (("res1", res1), ("res2", res2)):
-        if t is None:
-            lds.append(0)
-            continue
-        rb, rh, rw, rc, rld = _chk_act(t, nm)
-        if (rb, rh, rw) != (B, H, W) or rc < pc.Cout:
-            raise ValueError(f"{nm} shape {tuple(t.shape)} does not match the conv output")
-        lds.append(rld)
+    lds = _bind_res(res1, res2, B, H, W, pc.Cout)
     if out2_cp16 is not None and (out2_cp16.dtype != torch.float16 or not out2_cp16.is_contiguous()
                                   or tuple(out2_cp16.shape) != (B, pc.Cout // 16, H, W, 16)):
         raise ValueError("conv3x3_ws_res: out2_cp16 must be a contiguous fp16 [B,Cout/16,H,W,16] tensor")
-    per_img = 4 * H * W * 32
-    if per_img >= (1 << 31):
-        raise ValueError(f"conv3x3_ws_res: one {H}x{W} image exceeds the 2 GiB source limit of a launch")
-    step = max(1, min(B, ((1 << 31) - 1) // per_img))
-    for b0 in range(0, B, step):
-        sl = slice(b0, min(B, b0 + step))
+    for sl in _batch_slices(B, H, W, "conv3x3_ws_res"):
         check(_lib.lib().cdfo_conv3x3_c64_ws_res(
-            _vp(src[sl]), sl.stop - b0, H, W, _vp(pc.wh), pc.CoutP16, _vp(pc.bias), pc.Cout, act, _vp(out[sl]), ldo,
+            _vp(src[sl]), sl.stop - sl.start, H, W, _vp(pc.wh), pc.CoutP16, _vp(pc.bias), pc.Cout, act, _vp(out[sl]), ldo,
             _vp(res1[sl]), lds[0], _vp(None if res2 is None else res2[sl]), lds[1],
             _vp(None if out2_cp16 is None else out2_cp16[sl]), _stream()), "cdfo_conv3x3_c64_ws_res")
     return out
@@ -560,40 +520,20 @@ def conv_ring(src: torch.Tensor, pc: PackedConv, *, act: int = ACT_NONE, res1: O
               out2_hl: bool = False, src_halfsplit: bool = False) -> torch.Tensor:
     """3x3/s1/p1 convolution of an fp16 chunk-planar source [B,Cin/16,H,W,16] on the LDS-DMA ring kernel
     (Block_.body[2] and the composed stride-2 convolution).  Result: pixel-major fp32 (or fp16) [B,H,W,Cout]."""
-    if not src.is_cuda:
-        raise NotImplementedError("conv_ring: the HIP path needs device tensors (no CPU fallback)")
-    if src.dtype != torch.float16 or src.dim() != 5 or src.shape[4] != 16 or not src.is_contiguous():
-        raise ValueError(f"conv_ring: expected a contiguous fp16 [B,C/16,H,W,16] source, got {src.dtype} {tuple(src.shape)}")
-    B, nc, H, W, _ = src.shape
+    B, nc, H, W = _chk_cp16(src, "conv_ring", None)
     if pc.wh is None or pc.ks != 3 or (pc.Cin != nc * 16 and not (plane_wrap == nc and pc.Cin % 16 == 0 and pc.Cin > nc * 16)):
         raise ValueError("conv_ring: weight does not match the source")
-    a = ConvArgs()
-    a.src[0], a.ld[0], a.cs[0], a.nsrc = src.data_ptr(), 16, pc.Cin, 1
-    a.B, a.H, a.W, a.Ho, a.Wo = B, H, W, H, W
-    a.ks, a.stride, a.pad = 3, 1, 1
-    a.Cin, a.Cout, a.CoutP = pc.Cin, pc.Cout, pc.CoutP16
+    a, out = _conv_args(src, pc, pad=1, act=act, cp16=True, out=out, out_f16=out_f16)
+    a.CoutP, a.prec = pc.CoutP16, PREC_FP16 | (dbg << 8)
     if pc.tap_mask is not None:
         if pc.wh_sparse is None:
             pc.wh_sparse = sparse_taps_f16(pc)
         a.w, a.tap_mask = pc.wh_sparse.data_ptr(), pc.tap_mask.data_ptr()
     else:
         a.w = pc.wh.data_ptr()
-    a.bias, a.act = _p(pc.bias), act
-    odt = torch.float16 if out_f16 else torch.float32
-    if out is None:
-        out = torch.empty((B, H, W, pc.Cout), dtype=odt, device=src.device)
-    _, _, _, _, a.ldo = _chk_act(out, "out", odt)
-    a.out, a.store_mode, a.prec = out.data_ptr(), 0, PREC_FP16 | (dbg << 8)
-    a.src_f16, a.out_f16 = 1, int(out_f16)
     a.src_plane_wrap = plane_wrap
     a.src_halfsplit = int(src_halfsplit)
-    for nm, r in (("res1", res1), ("res2", None if dbg & 16 else res2)):
-        if r is not None:
-            rb, rh, rw, rc, rld = _chk_act(r, nm)
-            if (rb, rh, rw) != (B, H, W) or rc < pc.Cout:
-                raise ValueError(f"{nm} shape {tuple(r.shape)} does not match the conv output")
-            setattr(a, nm, r.data_ptr())
-            setattr(a, "ldr" + nm[-1], rld)
+    _bind_res(res1, None if dbg & 16 else res2, B, H, W, pc.Cout, a)
     if res_up2 is not None:         # half-resolution residual, added after bilinear x2
         rb, rh, rw, rc, rld = _chk_act(res_up2, "res_up2")
         if (rb, rh * 2, rw * 2) != (B, H, W) or rc < pc.Cout:
@@ -850,18 +790,11 @@ def upconv_last(x: torch.Tensor, pc: PackedConv, w_last: torch.Tensor, b_last: t
                 xc_bstride: int) -> torch.Tensor:
     """Upsampler tail (arch.py:4474-4480) without the HR feature map: lrelu(pixel_shuffle(upconv2(x))) -> conv_last ->
     + bilinear_x4(x_center).  x: [B,2H,2W,64]; pc: upconv2 packed with shuffle2=True; returns [B,1,4H,4W]."""
-    B, H2, W2, Cc, ld = _chk_act(x)
-    if not pc.shuffle2 or pc.Cout != 256 or pc.Cin != Cc or pc.ks != 1:
+    if not pc.shuffle2 or pc.Cout != 256 or pc.ks != 1:
         raise ValueError("upconv_last: needs the pixel-shuffle packing of a 1x1 conv with 256 outputs")
-    taps = torch.empty((B, 2 * H2, 2 * W2, 12), dtype=torch.float32, device=x.device)
-    a = ConvArgs()
-    a.src[0], a.ld[0], a.cs[0], a.nsrc = x.data_ptr(), ld, Cc, 1
-    a.B, a.H, a.W, a.Ho, a.Wo = B, H2, W2, H2, W2
-    a.ks, a.stride, a.pad = 1, 1, 0
-    a.Cin, a.Cout, a.CoutP = pc.Cin, pc.Cout, pc.CoutP
-    a.w, a.bias, a.act = pc.w.data_ptr(), _p(pc.bias), ACT_LRELU
+    a, taps = _conv_args([x], pc, act=ACT_LRELU, store_mode=3)       # CDFO_STORE_TAPS9: taps [B,4H,4W,12]
+    B, H2, W2 = a.B, a.H, a.W
     a.res2 = w_last.detach().contiguous().float().data_ptr()
-    a.out, a.ldo, a.store_mode = taps.data_ptr(), 12, 3
     check(_lib.lib().cdfo_conv1x1_bf16x3(C.byref(a), _stream()), "cdfo_conv1x1_bf16x3 (tap sums)")
     out = torch.empty((B, 1, 2 * H2, 2 * W2), dtype=torch.float32, device=x.device)
     check(_lib.lib().cdfo_conv_last_taps(_vp(taps), 12, _vp(b_last), _vp(xc), C.c_longlong(xc_bstride), B, 2 * H2, 2 * W2,

@@ -15,12 +15,8 @@ from torch.autograd import Function
 from . import _lib
 from . import kernels as K
 from . import nchw as N
-from ._lib import check
+from ._lib import _vp, check
 from .kernels import ACT_NONE, ACT_RELU, ACT_SIGMOID, _stream
-
-
-def _p(t):
-    return C.c_void_p(None if t is None else t.data_ptr())
 
 
 def _c(t):
@@ -29,7 +25,7 @@ def _c(t):
 
 def _ew_bwd(mode, g, y=None, a=None, x=None, yv=None, P=1, shape=None):
     out = torch.empty(shape if shape is not None else g.shape, dtype=torch.float32, device=g.device)
-    check(_lib.lib().cdfo_ew_nchw_bwd(_p(g), _p(y), _p(a), _p(x), _p(yv), C.c_longlong(out.numel()), C.c_longlong(P), mode, _p(out),
+    check(_lib.lib().cdfo_ew_nchw_bwd(_vp(g), _vp(y), _vp(a), _vp(x), _vp(yv), C.c_longlong(out.numel()), C.c_longlong(P), mode, _vp(out),
                                       _stream()), "cdfo_ew_nchw_bwd")
     return out
 
@@ -60,7 +56,7 @@ class _Conv2d(Function):
         gx = torch.empty_like(x) if need_x else None
         gw = torch.empty_like(w) if (need_w or need_b) else None
         gb = torch.empty(Co, dtype=torch.float32, device=x.device) if need_b else None
-        check(_lib.lib().cdfo_conv2d_nchw_bwd(_p(x), _p(w), _p(g), B, Cc, H, W, Co, kh, kw, stride, pad, _p(gx), _p(gw), _p(gb),
+        check(_lib.lib().cdfo_conv2d_nchw_bwd(_vp(x), _vp(w), _vp(g), B, Cc, H, W, Co, kh, kw, stride, pad, _vp(gx), _vp(gw), _vp(gb),
                                               _stream()), "cdfo_conv2d_nchw_bwd")
         return gx, (gw if need_w else None), gb, None, None, None
 
@@ -81,7 +77,7 @@ class _MaxPool(Function):
         B, Cc, H, W = x.shape
         idx = torch.empty(g.numel(), dtype=torch.int32, device=x.device)
         gx = torch.empty_like(x)
-        check(_lib.lib().cdfo_maxpool_nchw_bwd(_p(x), _p(g), B * Cc, H, W, k, stride, _p(idx), _p(gx), _stream()),
+        check(_lib.lib().cdfo_maxpool_nchw_bwd(_vp(x), _vp(g), B * Cc, H, W, k, stride, _vp(idx), _vp(gx), _stream()),
               "cdfo_maxpool_nchw_bwd")
         return gx, None, None
 
@@ -100,7 +96,7 @@ class _Resize(Function):
         (B, Cc, H, W), Ho, Wo = ctx.meta
         g = _c(g)
         gx = torch.empty((B, Cc, H, W), dtype=torch.float32, device=g.device)
-        check(_lib.lib().cdfo_resize_bilinear_nchw_bwd(_p(g), B * Cc, H, W, Ho, Wo, _p(gx), _stream()), "cdfo_resize_bilinear_nchw_bwd")
+        check(_lib.lib().cdfo_resize_bilinear_nchw_bwd(_vp(g), B * Cc, H, W, Ho, Wo, _vp(gx), _stream()), "cdfo_resize_bilinear_nchw_bwd")
         return gx, None, None
 
 
@@ -163,7 +159,7 @@ class _Gate(Function):
         ga = _ew_bwd(5, g, a=a, x=x, yv=yv, P=P)
         gx = _ew_bwd(6, g, a=a, yv=yv, P=P)
         gy = torch.empty((B, Cc, 1, 1), dtype=torch.float32, device=x.device)
-        check(_lib.lib().cdfo_gate_nchw_bwd_y(_p(g), _p(a), _p(x), B * Cc, C.c_longlong(P), _p(gy), _stream()), "cdfo_gate_nchw_bwd_y")
+        check(_lib.lib().cdfo_gate_nchw_bwd_y(_vp(g), _vp(a), _vp(x), B * Cc, C.c_longlong(P), _vp(gy), _stream()), "cdfo_gate_nchw_bwd_y")
         return ga, gx, gy
 
 
@@ -200,8 +196,8 @@ class _OffsetMask(Function):
         P = H * W
         offset = torch.empty((B, 2 * third, H, W), dtype=torch.float32, device=h1.device)
         mask = torch.empty((B, third, H, W), dtype=torch.float32, device=h1.device)
-        check(_lib.lib().cdfo_mv_offset_mask(_p(h1), _p(h2), h1.stride(2), _p(flow), C.c_longlong(2 * P), B, C.c_longlong(P), third,
-                                             float(mag), _p(offset), _p(mask), _stream()), "cdfo_mv_offset_mask")
+        check(_lib.lib().cdfo_mv_offset_mask(_vp(h1), _vp(h2), h1.stride(2), _vp(flow), C.c_longlong(2 * P), B, C.c_longlong(P), third,
+                                             float(mag), _vp(offset), _vp(mask), _stream()), "cdfo_mv_offset_mask")
         ctx.meta = (third, float(mag))
         ctx.save_for_backward(h1, h2)
         return offset, mask
@@ -212,8 +208,8 @@ class _OffsetMask(Function):
         third, mag = ctx.meta
         B, H, W, _ = h1.shape
         g1, g2 = torch.empty_like(h1), torch.empty_like(h2)
-        check(_lib.lib().cdfo_mv_offset_mask_bwd(_p(h1), _p(h2), h1.stride(2), _p(_c(goff)), _p(_c(gmask)), B, C.c_longlong(H * W),
-                                                 third, mag, _p(g1), _p(g2), _stream()), "cdfo_mv_offset_mask_bwd")
+        check(_lib.lib().cdfo_mv_offset_mask_bwd(_vp(h1), _vp(h2), h1.stride(2), _vp(_c(goff)), _vp(_c(gmask)), B, C.c_longlong(H * W),
+                                                 third, mag, _vp(g1), _vp(g2), _stream()), "cdfo_mv_offset_mask_bwd")
         return g1, g2, None, None, None
 
 

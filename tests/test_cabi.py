@@ -18,8 +18,36 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(raw, name), f"{name} declared in include/cdfo_hip.h but not exported"
     lib = _lib.lib()
     assert lib.cdfo_abi_version() == 1
-    assert lib.cdfo_sizeof_conv_args() == C.sizeof(_lib.ConvArgs)          # the ctypes mirror and the header agree field by field
+    assert lib.cdfo_sizeof_conv_args() == C.sizeof(_lib.ConvArgs)          # the mirror derived from the header has the built struct's size
     assert b"gfx950" in lib.cdfo_build_info()
+
+
+def test_conv_args_mirror_is_derived_from_the_header():
+    """_lib.ConvArgs is parsed out of include/cdfo_hip.h: the names, in order, and the types the parser has to tell apart."""
+    from cdfo_amd import _lib
+    fields = _lib.header_conv_args_fields()
+    assert _lib.ConvArgs._fields_ == fields
+    assert [n for n, _ in fields] == [
+        "src", "ld", "cs", "nsrc", "B", "H", "W", "Ho", "Wo", "ks", "stride", "pad", "Cin", "Cout", "CoutP",
+        "w", "w_bstride", "bias", "act", "res1", "ldr1", "res2", "ldr2", "out", "ldo", "store_mode", "prec",
+        "ln_gamma", "ln_beta", "tap_mask", "src_f16", "out_f16", "out2_cp16", "src_plane_wrap", "res_up2", "ldru", "out2_lo",
+        "mask_out", "flow", "flow_bstride", "off_mag", "off_accumulate", "res2_pixscale", "src_halfsplit",
+        "chan_sum_out", "chan_sum_slots"]
+    types = dict(fields)
+    assert types["src"] is C.c_void_p * 8 and types["ld"] is C.c_int * 8 and types["cs"] is C.c_int * 8     # CDFO_MAXSRC
+    assert types["w_bstride"] is C.c_longlong and types["flow_bstride"] is C.c_longlong and types["off_mag"] is C.c_float
+    assert types["tap_mask"] is C.c_void_p and types["out2_cp16"] is C.c_void_p and types["Wo"] is C.c_int
+
+
+def test_conv_args_parser_refuses_what_it_cannot_map(tmp_path):
+    from cdfo_amd import _lib
+    h = tmp_path / "h.h"
+    h.write_text("#define N 2\ntypedef struct { int a[N], b; double c; } cdfo_conv_args;\n")
+    with pytest.raises(_lib.CdfoError):
+        _lib.header_conv_args_fields(str(h))
+    h.write_text("typedef struct { int a[M]; } cdfo_conv_args;\n")
+    with pytest.raises(_lib.CdfoError):
+        _lib.header_conv_args_fields(str(h))
 
 
 def test_argument_validation_needs_no_gpu():
