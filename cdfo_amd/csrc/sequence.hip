@@ -1,0 +1,187 @@
+// Sequence-level input building for chunked inference (cdfo_amd/streaming.py::StreamingSR.run_chunked): K consecutive centre
+// frames of ONE sequence per forward, against a per-frame feature bank.
+//
+//   cdfo_seq_flows      the decoder's motion field [T,H,W,3] -> the seven per-slot flows of K centre frames [K,7,2,Hp,Wp] in one
+//                       launch: test_LD_22_FPS.py's mv2mvs (:100-122) and modify_mv_for_end_frames (:200-225) per pixel, bit for bit.
+//   cdfo_gather_frames  dst[j] = src[idx[j]] over whole frames, index table on the device: the frame-major window stack out of
+//                       the feature bank (clipped / repeated indices at the sequence's ends included) and the [K,7] windows of
+//                       the one-channel planes, one pass each.
+//
+// Both are streaming kernels: 16-byte stores, 16-byte reads through a buffer descriptor whose range check returns zero for
+// everything outside the frame (a bad index), no atomics, no LDS.  cdfo_seq_flows reads 12 bytes per pixel for the 56 it writes;
+// only the fp32 field (what the evaluation loop holds) is read in 16-byte loads, every other element type in guarded element loads.
+#include "common.h"
+
+namespace {
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t frame_rsrc(const unsigned char* base, int bytes) {
+  // wave-uniform by construction (kernel arguments and blockIdx only); readfirstlane makes that provable, so the loads are not
+  // wrapped in waterfall loops
+  const unsigned long long p = reinterpret_cast<unsigned long long>(base);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)p), hi = __builtin_amdgcn_readfirstlane((unsigned)(p >> 32));
+  void* q = reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
+  return __builtin_amdgcn_make_buffer_rsrc(q, 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+
+// ---------------------------------------------------------------------------------------------------- cdfo_gather_frames
+// grid (x: 16-byte vectors of a frame, four per thread and trip; y: destination frame)
+__global__ __launch_bounds__(256) void gather_frames_kernel(const unsigned char* __restrict__ src, u32x4* __restrict__ dst,
+                                                            const int* __restrict__ idx, int n_src, int frame_bytes) {
+  const int j = blockIdx.y;
+  const int s = idx[j];
+  // an index outside [0, n_src) gets a descriptor of zero bytes: every load through it returns zero
+  const bool ok = s >= 0 && s < n_src;
+  const __amdgpu_buffer_rsrc_t r = frame_rsrc(src + (long long)(ok ? s : 0) * frame_bytes, ok ? frame_bytes : 0);
+  const int n16 = frame_bytes >> 4;
+  u32x4* d = dst + (long long)j * n16;
+  const int stride = gridDim.x * 256;
+  int i = blockIdx.x * 256 + threadIdx.x;
+  for (; i + 3 * stride < n16; i += 4 * stride) {
+    u32x4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (i + u * stride) << 4, 0, 0));
+#pragma unroll
+    for (int u = 0; u < 4; ++u) d[i + u * stride] = v[u];
+  }
+  for (; i < n16; i += stride) d[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, i << 4, 0, 0));
+}
+
+// -------------------------------------------------------------------------------------------------------- cdfo_seq_flows
+template <typename T> __device__ __forceinline__ float mv_to_float(T v) { return (float)v; }
+
+struct bf16_t { unsigned short bits; };
+template <> __device__ __forceinline__ float mv_to_float<bf16_t>(bf16_t v) { return __uint_as_float((unsigned)v.bits << 16); }
+
+// the twelve values (four pixels x three components) at element offset e0 of a field of n elements; outside -> 0
+template <typename T>
+__device__ __forceinline__ void load_mv12(const T* __restrict__ f, int e0, int n, float (&m)[12]) {
+#pragma unroll
+  for (int k = 0; k < 12; ++k) m[k] = (e0 + k < n) ? mv_to_float<T>(f[e0 + k]) : 0.f;
+}
+// fp32: three 16-byte buffer loads (dword-aligned: a row of W pixels is 12 W bytes).  The last pixels of a field, whose twelve
+// values would run past its end, and the padding rows take the guarded element loads; the descriptor's range check stays
+// behind them as the net under a wrong offset
+template <>
+__device__ __forceinline__ void load_mv12<float>(const float* __restrict__ f, int e0, int n, float (&m)[12]) {
+  if (e0 + 12 > n) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) m[k] = (e0 + k < n) ? f[e0 + k] : 0.f;
+    return;
+  }
+  const __amdgpu_buffer_rsrc_t r = frame_rsrc(reinterpret_cast<const unsigned char*>(f), n * 4);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (e0 + 4 * q) * 4, 0, 0));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) m[4 * q + k] = v[k];
+  }
+}
+
+// One thread: four consecutive pixels of one row of one centre frame, all seven slots and both components: 14 16-byte stores.
+// grid (x: Hp * Wp / 4 threads; y: centre frame)
+template <typename T>
+__global__ __launch_bounds__(256) void seq_flows_kernel(const T* __restrict__ mv, int Tn, int H, int W, int i0, int Hp, int Wp,
+                                                        float* __restrict__ out) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const int w4 = Wp >> 2;
+  if (t >= Hp * w4) return;
+  const int y = t / w4, x = (t - y * w4) << 2;
+  const int i = i0 + (int)blockIdx.y;
+  const int entry = Tn > 1 ? (i > 1 ? i : 1) : 0;            // the field of frame 0 is read from entry 1 (test_LD_22_FPS.py:168)
+  const int n = H * W * 3;
+  float m[12];
+  // padding rows start beyond the field: every element is out of range
+  load_mv12<T>(mv + (long long)entry * n, y < H ? (y * W + x) * 3 : n, n, m);
+  float v[7][2][4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const bool inside = y < H && x + p < W;
+    // mv2mvs: components swapped, divided by -mv[2], NaN -> 0 (x / 0 stays inf), x 3, 2, 1, 0, -1, -2, -3, slot 3 forced to 0, / 128.
+    // Each step is one correctly rounded fp32 operation, in the order of the host function.
+    const float d = m[3 * p + 2] * -1.0f;
+    float f[2] = {__fdiv_rn(m[3 * p + 1], d), __fdiv_rn(m[3 * p + 0], d)};
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      if (f[c] != f[c]) f[c] = 0.f;
+#pragma unroll
+      for (int s = 0; s < 7; ++s) {
+        const float sc = (float)(3 - s);
+        const float r = s == 3 ? 0.f : __fdiv_rn(f[c] * sc, 128.0f);
+        v[s][c][p] = inside ? r : 0.f;                       // zero padding to Hp x Wp
+      }
+    }
+  }
+  // modify_mv_for_end_frames, the six rules in the reference's order (they overlap in sequences shorter than six frames)
+#pragma unroll
+  for (int c = 0; c < 2; ++c)
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      auto& a = v;
+      if (i == 0) a[0][c][p] = a[1][c][p] = a[2][c][p] = 0.f;
+      if (i == 1) { a[0][c][p] = a[2][c][p]; a[1][c][p] = a[2][c][p]; }
+      if (i == 2) a[0][c][p] = a[1][c][p];
+      if (i == Tn - 1) a[4][c][p] = a[5][c][p] = a[6][c][p] = 0.f;
+      if (i == Tn - 2) { a[5][c][p] = a[4][c][p]; a[6][c][p] = a[4][c][p]; }
+      if (i == Tn - 3) a[6][c][p] = a[5][c][p];
+    }
+  const long long plane = (long long)Hp * Wp;
+  float* o = out + (long long)blockIdx.y * 14 * plane + (long long)y * Wp + x;
+#pragma unroll
+  for (int s = 0; s < 7; ++s)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      f32x4 q = {v[s][c][0], v[s][c][1], v[s][c][2], v[s][c][3]};
+      *reinterpret_cast<f32x4*>(o + (s * 2 + c) * plane) = q;
+    }
+}
+
+template <typename T>
+void launch_seq_flows(const void* mv, int Tn, int H, int W, int i0, int K, int Hp, int Wp, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(seq_flows_kernel<T>, dim3(cdiv(Hp * (Wp / 4), 256), K), dim3(256), 0, st, static_cast<const T*>(mv), Tn, H, W,
+                     i0, Hp, Wp, out);
+}
+
+}  // namespace
+
+extern "C" int cdfo_seq_flows(const void* mv, int dtype, int T, int H, int W, int i0, int K, int Hp, int Wp, float* out, void* stream) {
+  if (!mv || !out || T <= 0 || H <= 0 || W <= 0 || K <= 0 || i0 < 0 || i0 + K > T || Hp < H || Wp < W || Wp % 4) return CDFO_EINVAL;
+  if ((long long)H * W * 3 * 8 > 0x7fffffffLL || (long long)Hp * Wp > 0x7fffffffLL) return CDFO_EINVAL;   // 32-bit offsets inside a field
+  if (!aligned16(out) || (dtype == CDFO_MV_F32 && (reinterpret_cast<uintptr_t>(mv) & 3u) != 0)) return CDFO_EALIGN;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  CdfoProfScope prof(st, KID_LAYOUT, 0, (double)K * (56.0 * Hp * Wp + 12.0 * H * W));
+  switch (dtype) {
+    case CDFO_MV_F32: launch_seq_flows<float>(mv, T, H, W, i0, K, Hp, Wp, out, st); break;
+    case CDFO_MV_F64: launch_seq_flows<double>(mv, T, H, W, i0, K, Hp, Wp, out, st); break;
+    case CDFO_MV_F16: launch_seq_flows<_Float16>(mv, T, H, W, i0, K, Hp, Wp, out, st); break;
+    case CDFO_MV_BF16: launch_seq_flows<bf16_t>(mv, T, H, W, i0, K, Hp, Wp, out, st); break;
+    case CDFO_MV_I8: launch_seq_flows<signed char>(mv, T, H, W, i0, K, Hp, Wp, out, st); break;
+    case CDFO_MV_U8: launch_seq_flows<unsigned char>(mv, T, H, W, i0, K, Hp, Wp, out, st); break;
+    case CDFO_MV_I16: launch_seq_flows<short>(mv, T, H, W, i0, K, Hp, Wp, out, st); break;
+    case CDFO_MV_I32: launch_seq_flows<int>(mv, T, H, W, i0, K, Hp, Wp, out, st); break;
+    case CDFO_MV_I64: launch_seq_flows<long long>(mv, T, H, W, i0, K, Hp, Wp, out, st); break;
+    default: return CDFO_EINVAL;
+  }
+  CDFO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cdfo_gather_frames(const void* src, int n_src, const int* idx, int n_dst, long long frame_bytes, void* dst, void* stream) {
+  if (!src || !dst || !idx || n_src <= 0 || n_dst <= 0 || n_dst > 65535 || frame_bytes <= 0 || frame_bytes % 16 ||
+      frame_bytes > 0x7ffffff0LL)
+    return CDFO_EINVAL;
+  if (!aligned16(src) || !aligned16(dst) || (reinterpret_cast<uintptr_t>(idx) & 3u)) return CDFO_EALIGN;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long n16 = frame_bytes / 16;
+  // enough workgroups over all frames to fill the chip a few times, at most one thread per 16-byte vector
+  long long bx = (n16 + 1023) / 1024;
+  const long long want = cdiv(8 * (cdfo_num_cus() > 0 ? cdfo_num_cus() : 256), n_dst);
+  if (bx > want) bx = want;
+  if (bx < 1) bx = 1;
+  CdfoProfScope prof(st, KID_LAYOUT, 0, 2.0 * (double)n_dst * (double)frame_bytes);
+  hipLaunchKernelGGL(gather_frames_kernel, dim3((unsigned)bx, (unsigned)n_dst), dim3(256), 0, st,
+                     static_cast<const unsigned char*>(src), static_cast<u32x4*>(dst), idx, n_src, (int)frame_bytes);
+  CDFO_LAUNCH_CHECK();
+  return 0;
+}

@@ -199,6 +199,8 @@ class CVSR_V8(nn.Module):
         self.last_range: Optional[dict] = None
         self._probe = None
         self._warned_range = False
+        # frames sent through feature extraction since construction (every inference route counts here; StreamingSR reports it)
+        self.frames_extracted = 0
         self._packed: Optional[dict] = None
         self._packed_sig = None
 
@@ -636,18 +638,23 @@ class CVSR_V8(nn.Module):
                 self._probe = None
             if capturing:
                 return res
-            pinned = self.__dict__.setdefault("_guard_pinned", {})
-            if x.device not in pinned:
-                pinned[x.device] = torch.zeros(4, dtype=torch.int32).pin_memory()
-            host = pinned[x.device]
-            host.copy_(probe, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            ev.synchronize()
-            self.last_range = self._range_verdict(host)
-            if not self.last_range["fallback"]:
+            if not self._settle_range(probe):
                 return res
             return self._range_fallback((x, mvs0, mvs1, pms, rms, ufs, pre_L1_fea, noise, self._noise_seed), None, None)
+
+    def _settle_range(self, probe) -> bool:
+        """Read a guarded forward's probe words back behind its last kernel (one host sync), set ``last_range``; True = the
+        forward has to be repeated in bf16x3."""
+        pinned = self.__dict__.setdefault("_guard_pinned", {})
+        if probe.device not in pinned:
+            pinned[probe.device] = torch.zeros(4, dtype=torch.int32).pin_memory()
+        host = pinned[probe.device]
+        host.copy_(probe, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        ev.synchronize()
+        self.last_range = self._range_verdict(host)
+        return self.last_range["fallback"]
 
     FP16_WINDOW = (2.0 ** -6, 2.0 ** 11)
 
@@ -664,6 +671,15 @@ class CVSR_V8(nn.Module):
         """Recompute a forward whose activations left fp16's range in the split-bf16 mode; with out_ref / l1_ref (a captured
         forward's output buffers) the results are written into those tensors."""
         x, mvs0, mvs1, pms, rms, ufs, pre, noise, seed = args
+        res = self._recompute_bf16x3(lambda: self._forward(x, mvs0, mvs1, pms, rms, ufs, pre, noise), seed)
+        if out_ref is not None:
+            out_ref.copy_(res[0])
+        if l1_ref is not None:
+            l1_ref.copy_(res[1])
+        return res
+
+    def _recompute_bf16x3(self, run, seed):
+        """``run()`` once more in the split-bf16 mode with the Philox key `seed` of the rejected forward; warns once per model."""
         lr = self.last_range
         if not self._warned_range:
             import warnings
@@ -677,15 +693,10 @@ class CVSR_V8(nn.Module):
         keep_seed, self._noise_seed = self._noise_seed, seed
         try:
             with torch.no_grad():
-                res = self._forward(x, mvs0, mvs1, pms, rms, ufs, pre, noise)
+                return run()
         finally:
             CVSR_V8._tls.override = None
             self._noise_seed = keep_seed
-        if out_ref is not None:
-            out_ref.copy_(res[0])
-        if l1_ref is not None:
-            l1_ref.copy_(res[1])
-        return res
 
     # -- the forward in two halves (inference only, no range guard: the caller owns the schedule) -------------------
     def forward_front(self, x, mvs0, mvs1, pms, rms, ufs, pre_L1_fea=None, gumbel_uniform=None):
@@ -707,6 +718,69 @@ class CVSR_V8(nn.Module):
         fused, xf = state
         with K.on_device(fused):
             return self._back(fused, xf)
+
+    # -- one sequence, K centre frames per call, features supplied by the caller (inference only) ----------------------
+    def _inference_only(self, what: str, t: torch.Tensor):
+        if not t.is_cuda:
+            raise NotImplementedError("CVSR_V8 (HIP): CPU tensors are not supported; there is no CPU fallback")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError(f"CVSR_V8 (HIP): {what} is an inference call -- wrap it in torch.no_grad()")
+        if torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError(f"CVSR_V8 (HIP): {what} is not captured into HIP graphs")
+
+    def extract_features(self, frames, pms):
+        """Step 1 of the forward per frame (arch.py:4416-4427 is per image): frames, pms [F,1,H,W] -> features [F,H,W,64],
+        pixel-major.  What any window of a sequence uses for frame t is extract_features(lr[t], pms[max(1, t)])."""
+        self._inference_only("extract_features", frames)
+        F, C, H, W = frames.shape
+        if C != 1 or tuple(pms.shape) != (F, 1, H, W):
+            raise ValueError(f"expected frames and pms of shape [F,1,H,W], got {tuple(frames.shape)} and {tuple(pms.shape)}")
+        if H % 8 or W % 8:
+            raise ValueError(f"H and W must be multiples of 8 (window attention, arch.py:2147,2235); got {H}x{W}")
+        with K.on_device(frames):
+            w = self._weights()
+            raw = w["raw"]
+            self.H, self.W = H, W
+            self.frames_extracted += F
+            f = K.stem_conv(frames.contiguous().float(), H * W, F, H, W, raw["conv_first.weight"], raw["conv_first.bias"], K.ACT_LRELU)
+            return self._feature_extraction(w, f, pms.contiguous().float(), H * W, F)
+
+    def forward_windows(self, Lf, x, mvs0, mvs1, rms, ufs, gumbel_uniform=None):
+        """K windows of one sequence from extracted features: Lf [7,K,H,W,64] the frame-major window stack (slot n of window k
+        = the features of the frame that window has there), x [K,7,1,H,W] (only the centre frames are read: the skip
+        connection), mvs0 / mvs1 / rms / ufs / gumbel_uniform as for ``forward`` at B = K (mvs0 is unused there too).  Returns
+        out [K,1,4H,4W].  Steps 2-5 of ``forward`` on the same kernels; the clip-major feature tensor, its shift copy and its
+        transpose never exist.  The fp16 range guard is that of ``forward``: settled before the call returns, a rejected call
+        is repeated in bf16x3 from the same Lf."""
+        self._inference_only("forward_windows", x)
+        Kw, N, C, H, W = x.shape
+        if N != NFRAMES or C != 1 or tuple(Lf.shape) != (N, Kw, H, W, NF):
+            raise ValueError(f"expected x [K,7,1,H,W] and Lf [7,K,H,W,64], got {tuple(x.shape)} and {tuple(Lf.shape)}")
+        if H % 8 or W % 8:
+            raise ValueError(f"H and W must be multiples of 8 (window attention, arch.py:2147,2235); got {H}x{W}")
+        if Lf.dtype != torch.float32 or not Lf.is_contiguous():
+            raise ValueError("Lf must be a dense fp32 tensor")
+        with K.on_device(x):
+            noise = self._resolve_noise(x, gumbel_uniform)
+            x = x.contiguous().float()
+            mvs1 = mvs1.contiguous().float()
+            self.H, self.W = H, W
+
+            def run():
+                fused = self._fuse_windows(self._weights(), Lf, x, mvs1, rms, ufs, noise)
+                return self._back(fused, x)
+
+            if not (self.precision == "fp16x2" and self.range_guard):
+                return run()
+            self._probe = torch.zeros(4, dtype=torch.int32, device=x.device)
+            try:
+                out = run()
+                probe = self._probe
+            finally:
+                self._probe = None
+            if not self._settle_range(probe):
+                return out
+            return self._recompute_bf16x3(run, self._noise_seed)
 
     def capture(self, x, mvs0, mvs1, pms, rms, ufs, pre_L1_fea=None, gumbel_uniform=None, check_range: bool = True):
         """Capture one inference forward at these operands' shapes into a HIP graph (opt-in; fixed shapes).  Returns a
@@ -766,6 +840,7 @@ class CVSR_V8(nn.Module):
         deferred_new = None
 
         # 1. feature extraction (arch.py:4416-4427)
+        self.frames_extracted += B * N if pre_L1_fea is None else B
         if pre_L1_fea is None:
             f = K.stem_conv(x, P, B * N, H, W, raw["conv_first.weight"], raw["conv_first.bias"], K.ACT_LRELU)
             L1 = self._feature_extraction(w, f, pms, P, B * N)           # [B*7,H,W,64], clip-major
@@ -789,7 +864,17 @@ class CVSR_V8(nn.Module):
             else:
                 new_frame_features()
         Lf = (K.swap_outer(L1, B, N) if B > 1 else L1).view(N, B, H, W, NF)   # frame-major views for the loop
+        return self._fuse_windows(w, Lf, x, mvs1, rms, ufs, gumbel_uniform, deferred_new), L1, x
 
+    def _fuse_windows(self, w, Lf, x, mvs1, rms, ufs, gumbel_uniform, deferred_new=None):
+        """Steps 2-3 of the forward from the frame-major feature stack Lf [7,B,H,W,64]: the six neighbour pipelines and the
+        temporal fusion.  x: only its device and shape are read here.  deferred_new: `_front`'s cached path at B = 1 -- the new
+        frame's feature extraction, enqueued behind the fork of the side streams.  Returns fused [B,H,W,64]."""
+        B, N, _, H, W = x.shape
+        raw = w["raw"]
+        ctr, P = self.center, H * W
+        nstr = int(getattr(self, "neighbour_streams", 0)) or 2
+        gsz = int(getattr(self, "neighbour_group", 0)) or ctr
         # 2. per-neighbour compensation + alignment (arch.py:4443-4460)
         if ufs.shape[1] != 1:
             ufs, rms = ufs.transpose(1, 2), rms.transpose(1, 2)
@@ -843,7 +928,7 @@ class CVSR_V8(nn.Module):
         fused = self._conv(aligned, w["tsa_fusion"], act=K.ACT_LRELU)
         if self._probe is not None:
             K.range_probe(fused, self._probe[0:2])
-        return fused, L1, x
+        return fused
 
     def _back(self, fused, x, L1=None):
         """Steps 4-5: reconstruction trunk, upsampling + skip (arch.py:4464-4481).  x: the fp32 input clip of `_front`."""

@@ -565,6 +565,38 @@ def swap_outer(x: torch.Tensor, B: int, N: int) -> torch.Tensor:
     return out
 
 
+_MV_DTYPES = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3, torch.int8: 4, torch.uint8: 5,
+              torch.int16: 6, torch.int32: 7, torch.int64: 8}        # CDFO_MV_* of include/cdfo_hip.h
+
+
+def seq_flows(mv: torch.Tensor, i0: int, K: int, Hp: int, Wp: int) -> torch.Tensor:
+    """mv: the decoder's motion field [T,H,W,3] of one sequence (device) -> the flows of centre frames i0 .. i0+K-1,
+    [K,7,2,Hp,Wp] fp32: streaming.mv2mvs + modify_mv_for_end_frames of each centre, bit for bit, in one launch."""
+    if not mv.is_cuda or mv.dim() != 4 or mv.shape[3] != 3 or mv.dtype not in _MV_DTYPES:
+        raise ValueError(f"seq_flows: a device tensor [T,H,W,3] of a real dtype expected, got {mv.dtype} {tuple(mv.shape)}")
+    mv = mv if mv.is_contiguous() else mv.contiguous()
+    T, H, W, _ = mv.shape
+    out = torch.empty((K, 7, 2, Hp, Wp), dtype=torch.float32, device=mv.device)
+    check(_lib.lib().cdfo_seq_flows(_vp(mv), _MV_DTYPES[mv.dtype], T, H, W, i0, K, Hp, Wp, _vp(out), _stream()), "cdfo_seq_flows")
+    return out
+
+
+def gather_frames(src: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[j] = src[idx[j]] over the frames src[i] of a dense tensor; idx: int32 on the device.  Returns [len(idx), *src.shape[1:]]."""
+    if not src.is_cuda or not src.is_contiguous() or idx.dtype != torch.int32 or idx.device != src.device or idx.dim() != 1 \
+            or not idx.is_contiguous():
+        raise ValueError("gather_frames: a dense device tensor and a dense int32 index vector on the same device expected")
+    n = int(idx.shape[0])
+    frame_bytes = src[0].numel() * src.element_size()
+    if out is None:
+        out = torch.empty((n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    elif out.dtype != src.dtype or out.numel() != n * src[0].numel() or not out.is_contiguous() or out.device != src.device:
+        raise ValueError("gather_frames: out must be a dense tensor of len(idx) frames of src's dtype")
+    check(_lib.lib().cdfo_gather_frames(_vp(src), int(src.shape[0]), _vp(idx), n, C.c_longlong(frame_bytes), _vp(out), _stream()),
+          "cdfo_gather_frames")
+    return out
+
+
 def stem_conv(img: torch.Tensor, img_bstride: int, B: int, H: int, W: int, w: torch.Tensor, bias: torch.Tensor,
               act: int = ACT_NONE, add: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
               out2: Optional[torch.Tensor] = None):

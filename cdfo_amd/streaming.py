@@ -9,11 +9,14 @@ goes through feature extraction (``arch/SIDECVSR_our.py:4420-4427``).  Quirks of
 window indices are clipped to the sequence (``generate_input_index``, ``:14-17``); the priors and motion fields of
 frame 0 are read from entry 1 (``ii = max(1, i)``, ``:36,53,66,168``); ``x / 0`` in ``mv2mvs`` stays ``inf`` (only NaN
 becomes 0).
+
+``run_chunked`` processes the same sequence several centre frames per forward against a per-frame feature bank (each frame
+extracted once; `plan_chunks` is its schedule), with the windows, planes and flows built by the library's own kernels.
 """
 from __future__ import annotations
 
 import time
-from typing import List, Optional, Sequence
+from typing import Iterator, List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -58,6 +61,58 @@ def modify_mv_for_end_frames(i: int, mvs: torch.Tensor, max_idx: int) -> torch.T
     return mvs
 
 
+class ChunkPlan(NamedTuple):
+    """One chunk of `plan_chunks`: plain Python integers, no device work."""
+    centres: List[int]            # the centre frames of the chunk, consecutive
+    windows: List[List[int]]      # per centre: the seven frame indices of its window (= generate_input_index)
+    priors: List[List[int]]       # per centre: the entries its pms / rms / ufs planes are read from (max(1, .); 0 if T == 1)
+    mv_entry: List[int]           # per centre: the entry its motion fields are read from (max(1, i); 0 if T == 1)
+    extract: List[int]            # frames that go through feature extraction before this chunk's forward, consecutive
+    extract_priors: List[int]     # per extracted frame: the entry its pms plane is read from
+    oldest: int                   # the bank may drop every frame below this one before the chunk's forward
+
+
+def plan_chunks(T: int, chunk: int) -> Iterator[ChunkPlan]:
+    """The schedule of `StreamingSR.run_chunked` for a sequence of T frames, `chunk` centre frames per forward (the last chunk
+    may be shorter).  The features a window uses for frame t are always those of (lr[t], pms[max(1, t)]), whichever step or
+    slot asks, so every frame is extracted once, by the first chunk whose windows reach it, and is kept until the last window
+    that contains it has run: at most chunk + 6 frames are resident."""
+    if T < 1 or chunk < 1:
+        raise ValueError(f"plan_chunks: T >= 1 and chunk >= 1 expected, got T = {T}, chunk = {chunk}")
+    prior = (lambda t: max(1, t)) if T > 1 else (lambda t: 0)
+    half = NFRAMES // 2
+    extracted = 0                                                  # frames 0 .. extracted-1 have been scheduled
+    for c0 in range(0, T, chunk):
+        centres = list(range(c0, min(c0 + chunk, T)))
+        windows = [[min(max(i + n - half, 0), T - 1) for n in range(NFRAMES)] for i in centres]
+        reach = windows[-1][-1] + 1
+        extract = list(range(extracted, reach))
+        extracted = max(extracted, reach)
+        yield ChunkPlan(centres, windows, [[prior(t) for t in w] for w in windows], [prior(i) for i in centres], extract,
+                        [prior(t) for t in extract], windows[0][0])
+
+
+def bank_capacity(T: int, chunk: int) -> int:
+    """Frames of features the bank of `run_chunked` holds: the chunk's centres and three neighbours on either side."""
+    return min(chunk, T) + NFRAMES - 1
+
+
+def bank_slot(t: int, capacity: int) -> int:
+    """The bank is a ring: frame t lives in slot t mod capacity, and is overwritten by frame t + capacity."""
+    return t % capacity
+
+
+def bank_runs(first: int, count: int, capacity: int) -> List[tuple]:
+    """Frames first .. first+count-1 as contiguous runs of ring slots: [(slot, offset into the run of frames, length)], at most two."""
+    runs, done = [], 0
+    while done < count:
+        slot = bank_slot(first + done, capacity)
+        n = min(count - done, capacity - slot)
+        runs.append((slot, done, n))
+        done += n
+    return runs
+
+
 class StreamingSR:
     """One sequence, device resident.
 
@@ -88,6 +143,7 @@ class StreamingSR:
         self.noise = gumbel_uniform
         self.fea = None
         self.seconds = 0.0
+        self._extracted0 = int(getattr(model, "frames_extracted", 0))
         # use_graph: the cached-path forward (frames >= 1: identical shapes every step, ~700 kernel launches of a few
         # microseconds each at one clip) is captured once into a HIP graph and replayed from static buffers
         self.use_graph = use_graph
@@ -181,6 +237,71 @@ class StreamingSR:
         """All frames in order; ``self.fps`` afterwards = frames / summed forward time (test_LD_22_FPS.py:192)."""
         self.fea, self.seconds = None, 0.0
         return [self.step(i) for i in range(self.T)]
+
+    # -- chunked inference: `chunk` consecutive centre frames per forward against a per-frame feature bank ------------------------
+    def run_chunked(self, chunk: int = 8) -> List[torch.Tensor]:
+        """All frames in order, `chunk` centre frames per forward (the last chunk may be shorter).  Each frame goes through
+        feature extraction ONCE, into a bank of at most chunk + 6 frames of features; the windows of a chunk are gathered from the
+        bank in one pass and the neighbour pipelines, the fusion, the trunk and the up-sampler run at batch `chunk`
+        (CVSR_V8.forward_windows).  Per output frame the arithmetic is that of `run()`.  The windows, the flows and the planes are
+        built by libcdfo_hip.so (cdfo_gather_frames, cdfo_seq_flows).  ``self.seconds`` / ``fps`` cover everything a chunk does
+        on the device: extraction, input building, forward."""
+        if not hasattr(self.model, "forward_windows"):
+            raise NotImplementedError("run_chunked needs a model with extract_features / forward_windows (CVSR_V8)")
+        plans = list(plan_chunks(self.T, int(chunk)))
+        self.fea, self.seconds = None, 0.0
+        self._extracted0 = self.model.frames_extracted
+        cap = bank_capacity(self.T, int(chunk))
+        bank = torch.empty((cap, self.Hp, self.Wp, 64), dtype=torch.float32, device=self.dev)
+        # every index table of the sequence in one upload: per chunk the bank slots of its window stack (slot-major), the
+        # frames and the prior entries of its windows (centre-major) and the prior entries of the frames it extracts
+        flat = []
+        for p in plans:
+            flat += [bank_slot(p.windows[k][n], cap) for n in range(NFRAMES) for k in range(len(p.centres))]
+            flat += [t for w in p.windows for t in w] + [t for w in p.priors for t in w] + p.extract_priors
+        tables = torch.tensor(flat, dtype=torch.int32).to(self.dev)
+        outs, at = [], 0
+        for p in plans:
+            n7 = NFRAMES * len(p.centres)
+            idx = tables[at:at + 3 * n7 + len(p.extract)]
+            at += 3 * n7 + len(p.extract)
+            outs.extend(self._chunk_step(p, bank, idx[:n7], idx[n7:2 * n7], idx[2 * n7:3 * n7], idx[3 * n7:]))
+        return outs
+
+    def _chunk_step(self, plan: ChunkPlan, bank, lf_idx, frame_idx, prior_idx, extract_prior_idx) -> List[torch.Tensor]:
+        """One chunk: extract the frames it is the first to reach into the bank (frame t lives in slot t mod capacity; what it
+        overwrites is below `plan.oldest`), gather the inputs of its windows, one forward at batch len(plan.centres)."""
+        from . import kernels as K
+        k, cap = len(plan.centres), int(bank.shape[0])
+        noise = None
+        if self.noise is not None:      # per-step format: noise[i] = the six [1,64,H,W] draws of centre i
+            noise = [torch.cat([self.noise[i][d] for i in plan.centres], 0) for d in range(NFRAMES - 1)]
+        torch.cuda.synchronize(self.dev)
+        t0 = time.perf_counter()
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            if plan.extract:
+                a, b = plan.extract[0], plan.extract[-1] + 1
+                fea = self.model.extract_features(self.lr[a:b].unsqueeze(1), K.gather_frames(self.pms, extract_prior_idx).unsqueeze(1))
+                for slot, off, n in bank_runs(a, b - a, cap):
+                    bank[slot:slot + n].copy_(fea[off:off + n])
+            shape = (k, NFRAMES, 1, self.Hp, self.Wp)
+            Lf = K.gather_frames(bank, lf_idx).view(NFRAMES, k, self.Hp, self.Wp, 64)
+            x = K.gather_frames(self.lr, frame_idx).view(shape)
+            r, u = K.gather_frames(self.rms, prior_idx).view(shape), K.gather_frames(self.ufs, prior_idx).view(shape)
+            # (the model reads mvs1 only, like the reference's forward: mvl0's flows are not built)
+            m1 = K.seq_flows(self.mvl1, plan.centres[0], k, self.Hp, self.Wp)
+            out = self.model.forward_windows(Lf, x, None, m1, r, u, gumbel_uniform=noise)
+        torch.cuda.synchronize(self.dev)
+        self.seconds += time.perf_counter() - t0
+        return [out[j:j + 1, :, :4 * self.H, :4 * self.W] for j in range(k)]
+
+    @property
+    def frames_extracted(self) -> int:
+        """Frames the model has sent through feature extraction since this object was made or its last `run_chunked()` began
+        (one `run()`: 7 + (T - 1); `run_chunked()`: T).  It is the model's counter of eager extraction calls: exact for `run()`,
+        `run_pipelined()` and `run_chunked()`; a forward that the fp16 range guard of `forward` repeats is counted twice (a repeated
+        chunk is not: it reuses the bank), and replays of a HIP graph (`use_graph=True`) are not counted, only the capture is."""
+        return self.model.frames_extracted - self._extracted0
 
     @property
     def fps(self) -> float:

@@ -526,6 +526,28 @@ int cdfo_dot_plane(const float* a, int lda, const float* b, int ldb, long long n
 int cdfo_gumbel_softmax(const float* v, const float* u, int B, long long P, float* out, int ldo, void* stream);
 int cdfo_softmax64_bwd(const float* r, int ldr, const float* dm, int ldm, long long npix, float* dz, int ldo, void* stream);
 
+/* ---- sequence-level input building of chunked inference (sequence.hip; cdfo_amd/streaming.py::StreamingSR.run_chunked) ----
+ * cdfo_seq_flows:     the decoder's motion field mv [T][H][W][3] (element type `dtype`, one of CDFO_MV_*) -> the per-slot flows of
+ *                     the K centre frames i0 .. i0+K-1, out [K][7][2][Hp][Wp] fp32, zero padded from H x W to Hp x Wp (Wp % 4 == 0).
+ *                     Per pixel test_LD_22_FPS.py's mv2mvs (:100-122: components swapped, / -mv[2] with NaN -> 0 and inf kept,
+ *                     x 3, 2, 1, 0, -1, -2, -3 with slot 3 forced to 0, / 128) on entry max(1, i) of the field (entry 0 if T == 1),
+ *                     then modify_mv_for_end_frames (:200-225) for centre i in a sequence of T frames.  Every step is one correctly
+ *                     rounded fp32 operation in the host function's order: bit-identical to cdfo_amd.streaming.mv2mvs +
+ *                     modify_mv_for_end_frames.
+ * cdfo_gather_frames: dst[j] = src[idx[j]], j < n_dst, over frames of frame_bytes bytes (a multiple of 16; src, dst 16-byte
+ *                     aligned); idx: n_dst ints in DEVICE memory; an index outside [0, n_src) gives a frame of zeros. */
+#define CDFO_MV_F32 0
+#define CDFO_MV_F64 1
+#define CDFO_MV_F16 2
+#define CDFO_MV_BF16 3
+#define CDFO_MV_I8 4
+#define CDFO_MV_U8 5
+#define CDFO_MV_I16 6
+#define CDFO_MV_I32 7
+#define CDFO_MV_I64 8
+int cdfo_seq_flows(const void* mv, int dtype, int T, int H, int W, int i0, int K, int Hp, int Wp, float* out, void* stream);
+int cdfo_gather_frames(const void* src, int n_src, const int* idx, int n_dst, long long frame_bytes, void* dst, void* stream);
+
 /* ---- optional per-launch HIP-event timing on the launch stream (bench.py's live roofline figures) ----------- */
 int cdfo_prof_begin(int max_records);
 int cdfo_prof_end(int* launches, double* ms, double* flops, double* bytes, int nkid);

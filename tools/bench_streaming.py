@@ -8,8 +8,8 @@ from arch.SIDECVSR_our import CVSR_V8
 from cdfo_amd.streaming import StreamingSR
 
 
-def main():
-    T, H, W = int(sys.argv[1]) if len(sys.argv) > 1 else 24, 270, 480
+def _synthetic(T, H, W):
+    """One synthetic sequence: 8-bit planes, a residual map, two decoder motion fields that are constant on 8x8 blocks."""
     rs = np.random.RandomState(0)
     u8 = lambda: rs.randint(0, 256, size=(T, H, W)).astype(np.uint8)
     lr, pms, ufs = u8(), u8(), u8()
@@ -17,6 +17,12 @@ def main():
     mv = rs.randint(-64, 64, size=(2, T, (H + 7) // 8, (W + 7) // 8, 3)).astype(np.float32)
     mv[..., 2] = rs.choice([-2.0, -1.0, 1.0], size=mv.shape[:-1])
     mv = np.repeat(np.repeat(mv, 8, axis=2), 8, axis=3)[:, :, :H, :W]
+    return lr, pms, rms, ufs, mv
+
+
+def main():
+    T, H, W = int(sys.argv[1]) if len(sys.argv) > 1 else 24, 270, 480
+    lr, pms, rms, ufs, mv = _synthetic(T, H, W)
     model = CVSR_V8()
     model = model.cuda().eval()
     # (HIP graph, neighbour streams, frames per group, group of frames 0-2 beside the new frame's feature extraction, new frame alone)
@@ -36,13 +42,7 @@ def pipelined():
     if "--size" in sys.argv:
         k = sys.argv.index("--size")
         T, H, W = int(sys.argv[k + 1]), int(sys.argv[k + 2]), int(sys.argv[k + 3])
-    rs = np.random.RandomState(0)
-    u8 = lambda: rs.randint(0, 256, size=(T, H, W)).astype(np.uint8)
-    lr, pms, ufs = u8(), u8(), u8()
-    rms = np.clip(np.round(rs.randn(T, H, W) * 6), -128, 127).astype(np.float32)
-    mv = rs.randint(-64, 64, size=(2, T, (H + 7) // 8, (W + 7) // 8, 3)).astype(np.float32)
-    mv[..., 2] = rs.choice([-2.0, -1.0, 1.0], size=mv.shape[:-1])
-    mv = np.repeat(np.repeat(mv, 8, axis=2), 8, axis=3)[:, :, :H, :W]
+    lr, pms, rms, ufs, mv = _synthetic(T, H, W)
     model = CVSR_V8().cuda().eval()
     s = StreamingSR(model, lr, pms, rms, ufs, mv[0], mv[1])
     s.run()
@@ -54,7 +54,80 @@ def pipelined():
               f"({1e3 * s.seconds / T:.2f} ms per frame)", flush=True)
 
 
+def chunked():
+    """--chunk K [K ...] [--size T H W] [--repeats R]: run(), HIP-graph replay, run_pipelined() and run_chunked(K) on one synthetic
+    sequence in one process; after a warm-up pass each mode runs R times and every repeat's frames/s is printed (the spread,
+    not one number).  --only-chunk skips the three one-frame modes (for a kernel trace of the chunked path alone); --phases adds an event breakdown of
+    one pass per chunk size."""
+    T, H, W = 64, 270, 480
+    if "--size" in sys.argv:
+        k = sys.argv.index("--size")
+        T, H, W = int(sys.argv[k + 1]), int(sys.argv[k + 2]), int(sys.argv[k + 3])
+    reps = int(sys.argv[sys.argv.index("--repeats") + 1]) if "--repeats" in sys.argv else 3
+    k = sys.argv.index("--chunk") + 1
+    chunks = []
+    while k < len(sys.argv) and sys.argv[k].isdigit():
+        chunks.append(int(sys.argv[k]))
+        k += 1
+    lr, pms, rms, ufs, mv = _synthetic(T, H, W)
+    model = CVSR_V8().cuda().eval()
+
+    def report(name, make, loop):
+        s = make()
+        loop(s)                                # warm-up (weight packing, first-touch allocations, graph capture)
+        fps = []
+        for _ in range(reps):
+            loop(s)
+            fps.append(s.fps)
+        print(f"{name}, {T} frames {H}x{W}: frames/s per repeat {' '.join('%.2f' % f for f in fps)}; median {np.median(fps):.2f}, "
+              f"min {min(fps):.2f}, max {max(fps):.2f}" + (f"; frames extracted per pass {s.frames_extracted}" if "chunk" in name else ""), flush=True)
+
+    seq = lambda **kw: StreamingSR(model, lr, pms, rms, ufs, mv[0], mv[1], **kw)
+    if "--only-chunk" not in sys.argv:
+        report("run() (per-frame timing, B=1)", seq, lambda s: s.run())
+        report("run() under HIP-graph replay", lambda: seq(use_graph=True), lambda s: s.run())
+        report("run_pipelined() (whole-loop wall time)", seq, lambda s: s.run_pipelined())
+    for c in chunks:
+        report(f"run_chunked(chunk={c}) (extraction + input building + forward)", seq, lambda s: s.run_chunked(c))
+    if "--phases" in sys.argv:
+        for c in chunks:
+            _phases(model, seq(), c)
+
+
+def _phases(model, s, chunk):
+    """Where a chunk's time goes: events around feature extraction, the neighbour pipelines + fusion, the trunk, and the whole
+    chunk step (the rest = input building, the copy into the bank, the up-sampler), summed over one pass of the sequence."""
+    marks = {}
+
+    def wrap(name, fn):
+        def f(*a, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = fn(*a, **kw)
+            e1.record()
+            marks.setdefault(name, []).append((e0, e1))
+            return r
+        return f
+
+    s.run_chunked(chunk)
+    keep = model.extract_features, model._fuse_windows, model._trunk, s._chunk_step
+    model.extract_features, model._fuse_windows = wrap("feature extraction", keep[0]), wrap("neighbour pipelines + fusion", keep[1])
+    model._trunk, s._chunk_step = wrap("trunk", keep[2]), wrap("whole chunk step", keep[3])
+    try:
+        s.run_chunked(chunk)
+    finally:
+        del model.extract_features, model._fuse_windows, model._trunk, s._chunk_step
+    torch.cuda.synchronize()
+    ms = {k: sum(a.elapsed_time(b) for a, b in v) for k, v in marks.items()}
+    rest = ms["whole chunk step"] - sum(v for k, v in ms.items() if k != "whole chunk step")
+    print(f"phases of run_chunked(chunk={chunk}), ms per frame over {s.T} frames: "
+          + ", ".join(f"{k} {v / s.T:.2f}" for k, v in ms.items()) + f", rest {rest / s.T:.2f}", flush=True)
+
+
 if __name__ == "__main__":
+    if "--chunk" in sys.argv:
+        chunked()
+        sys.exit(0)
     if "--pipelined" in sys.argv:
         pipelined()
         sys.exit(0)
