@@ -7,25 +7,12 @@
 //   colconv9    : directH1_conv, the 9-tap conv along H on sparse_q (arch.py:2225).
 //   seq_attn    : softmax(Q Q^T) V over a row, a column or an 8x8 window, one query per lane, keys streamed through
 //                 wave-uniform (scalar) loads, online softmax in registers.
-#include "common.h"
+#include "numeric.h"
 
 namespace {
 
 constexpr int ZS = 65;  // LDS pitch for the [pixel][channel] logits (conflict-free both ways)
 constexpr int QS = 72;  // 4 zero floats on both sides of the 64 channels for the 9-tap channel conv
-
-// Philox4x32-10 (Salmon et al., SC'11): counter-based generator, 4 x 32 random bits per (counter, key).
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&o)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
 
 // RNG: the uniform draws of gumbel_softmax (arch.py:2169, torch.rand_like + "redraw while any == 0") are generated here
 // instead of being read: u = (24 random bits + 0.5) * 2^-24 lies strictly inside (0, 1), element (image b, channel c,
@@ -280,24 +267,6 @@ typedef _Float16 attn_f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 attn_f16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned attn_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned attn_u32x4 __attribute__((ext_vector_type(4)));
-
-// Two fp32 values -> packed fp16 hi (round to nearest) and packed fp16 lo = fp16(v - hi), four instructions per pair:
-// v_cvt_pk_f16_f32, two v_fma_mix_f32 (f32 * 1.0 - f16 -> f32: the exact remainder, the fp16 operand read straight from its
-// half of the packed register), v_cvt_pk_f16_f32.  hipcc emits cvt_f32_f16 + sub per element for the plain C expression (six
-// per pair) and folds a source-level fma back into it; the kernel is bound by its vector instructions, so
-// the form is spelled out.  Full-register results only: the three-instruction form through v_fma_mixlo_f16 / v_fma_mixhi_f16
-// writes half registers, and gfx950 needs a wait state between such a write and the next vector read of the register, which
-// hipcc cannot insert around inline assembly (measured: wrong window-attention results where the consumer followed directly).
-__device__ __forceinline__ void split_pair_f16(float a, float b, unsigned& hi, unsigned& lo) {
-  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-  const h2 hv = {(_Float16)a, (_Float16)b};
-  hi = __builtin_bit_cast(unsigned, hv);
-  float ra, rb;
-  asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(ra) : "v"(a), "v"(hi));
-  asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(rb) : "v"(b), "v"(hi));
-  const h2 lv = {(_Float16)ra, (_Float16)rb};
-  lo = __builtin_bit_cast(unsigned, lv);
-}
 
 // NW waves per workgroup = 32*NW queries of one sequence at most; a stage is 8*NW keys (NW/4 sub-tiles of 32), staged by
 // all NW*64 threads with one 4-key x 4-channel unit each -- the larger the workgroup, the less staging work (loads,

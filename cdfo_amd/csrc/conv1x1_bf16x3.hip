@@ -11,7 +11,7 @@
 // Same argument block / epilogue contract as cdfo_conv_igemm (bias, LeakyReLU/ReLU, two residuals, plain or 2x
 // pixel-shuffle store); every source must be a multiple of 64 channels wide.  Replaces the 1x1 convolutions of the
 // CVSR_V8 path (qkv, project_out folded, input_conv, fuse, fusion_out, down.0 / up.0, tsa_fusion, upconv1/2).
-#include "common.h"
+#include "numeric.h"
 
 namespace {
 
@@ -26,29 +26,12 @@ constexpr int EPI_BYTES = 4 * 32 * EPI_RS * 4;  // 34,816
 constexpr int MAXCB = 4;                        // up to 256 output channels
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-  const __bf16 ha = (__bf16)a, hb = (__bf16)b;
-  return (unsigned)__builtin_bit_cast(unsigned short, ha) | ((unsigned)__builtin_bit_cast(unsigned short, hb) << 16);
-}
-__device__ __forceinline__ float bf16_round(float a) { return (float)(__bf16)a; }
 __device__ __forceinline__ void split_store(unsigned char* dst_hi, int lo_delta, const f32x4 v) {
   u32x2 hi, lo;
-  hi[0] = pack_bf16(v[0], v[1]);
-  hi[1] = pack_bf16(v[2], v[3]);
-  lo[0] = pack_bf16(v[0] - bf16_round(v[0]), v[1] - bf16_round(v[1]));
-  lo[1] = pack_bf16(v[2] - bf16_round(v[2]), v[3] - bf16_round(v[3]));
+  split4_bf16(v, hi, lo);
   *reinterpret_cast<u32x2*>(dst_hi) = hi;
   *reinterpret_cast<u32x2*>(dst_hi + lo_delta) = lo;
-}
-
-__device__ __forceinline__ float c1_row16_sum(float v) {  // sum over the 16 lanes of a DPP row, result in every lane
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, true));
-  return v;
 }
 
 // NCB: number of 64-wide output-channel blocks (1..4).

@@ -21,17 +21,17 @@
 //     straight from registers.
 // Contract: cdfo_conv_args as cdfo_conv1x1_bf16x3 with plain store, Cin % 64 == 0 per source, Cout % 8 == 0,
 // CoutP in {64, 128}, weights + ring within the CU's LDS (Cin * CoutP <= 192 * 64); everything else stays on that kernel.
-#include "common.h"
+#include "numeric.h"
 
 namespace {
 
 constexpr int ST_THREADS = 256;
 constexpr int ST_STAGE = 8192;                 // 32 pixels x 64 channels x 4 B
 constexpr int ST_MAXNS = 4;
+constexpr int ST_MAX_LDS = 160 * 1024 - 256;   // dynamic LDS a workgroup of these kernels may ask for
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 struct st_item { const float* base; int ld; int ch0; };     // one 64-channel slice of a pixel-major operand
 
@@ -76,12 +76,6 @@ inline int st_slots(int B, int tiles_per_image, int grid) {
   return n;
 }
 
-__device__ __forceinline__ unsigned st_pack_bf16(float a, float b) {
-  const __bf16 ha = (__bf16)a, hb = (__bf16)b;
-  return (unsigned)__builtin_bit_cast(unsigned short, ha) | ((unsigned)__builtin_bit_cast(unsigned short, hb) << 16);
-}
-__device__ __forceinline__ float st_bf16_round(float a) { return (float)(__bf16)a; }
-
 // eight 1 KiB pieces of one stage: lane l of piece k writes LDS bytes lds + 1024 k + 16 l from (buffer base + voff[k])
 __device__ __forceinline__ void st_dma8(const unsigned (&voff)[8], i32x4 rsrc, unsigned lds) {
   unsigned keep;
@@ -125,19 +119,13 @@ __device__ __forceinline__ void st_dma1(unsigned voff, i32x4 rsrc, unsigned lds)
       : "memory", "scc");
 }
 
-// two fp32 -> packed fp16 hi and packed fp16 lo = fp16(v - hi): v_cvt_pk_f16_f32, two v_fma_mix_f32 (exact remainders, the fp16
-// operand read from its half of the packed register), v_cvt_pk_f16_f32 (see attention.hip: full-register results only)
-__device__ __forceinline__ void st_split_pair_f16(float x, float y, unsigned& hi, unsigned& lo) {
-  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-  const h2 hv = {(_Float16)x, (_Float16)y};
-  hi = __builtin_bit_cast(unsigned, hv);
-  float rx, ry;
-  asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(rx) : "v"(x), "v"(hi));
-  asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(ry) : "v"(y), "v"(hi));
-  const h2 lv = {(_Float16)rx, (_Float16)ry};
-  lo = __builtin_bit_cast(unsigned, lv);
+// An item has landed when at most the 8 * (younger items in flight) youngest DMA pieces are outstanding (pieces retire in order
+// among themselves; stores and older requests in flight only make the wait more conservative)
+__device__ __forceinline__ void st_wait_landed(long long younger) {
+  if (younger >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+  else if (younger == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
-
 // NCB: 64-wide output-channel blocks (1, 2; 4 in the TAPS form)
 // CSUM (NCB == 1): also the channel sums of the result, see st_args.csum
 template <int NCB, bool TAPS = false, bool CSUM = false>
@@ -147,12 +135,12 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nkb = a.nkb, NS = a.ns;
   // LDS map: weights hi [nkb*4 chunks][2 k-halves][NCB*64 rows][8 bf16] | weights lo (same) | bias [NCB*64 floats] |
-  //          4 waves x NS stages
+  //          4 waves x NS stages (st_weight_bytes on the host)
   const int w_half = nkb * 4 * 2 * NCB * 64 * 16;
+  const int ring_off = 2 * w_half + NCB * 64 * 4;
   unsigned char* sWh = smem;
   unsigned char* sWl = smem + w_half;
   float* sBias = reinterpret_cast<float*>(smem + 2 * w_half);
-  const int ring_off = 2 * w_half + NCB * 64 * 4;
   unsigned char* ring = smem + ring_off + wave * NS * ST_STAGE;
   const unsigned ring_lds = (unsigned)(unsigned long long)(smem) + ring_off + wave * NS * ST_STAGE;
   // res_scale: two 256-byte slots per wave (tile parity) behind the rings
@@ -213,9 +201,9 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
         if (n < a.CoutP) wv = *reinterpret_cast<const f32x4*>(wb + ((long long)kg * a.CoutP + n) * 4);
         const int c = kg >> 2, hh = (kg >> 1) & 1, j0 = (kg & 1) * 4;
         u32x2 hi, lo;
-        hi[0] = st_pack_bf16(wv[0], wv[1]); hi[1] = st_pack_bf16(wv[2], wv[3]);
-        lo[0] = st_pack_bf16(wv[0] - st_bf16_round(wv[0]), wv[1] - st_bf16_round(wv[1]));
-        lo[1] = st_pack_bf16(wv[2] - st_bf16_round(wv[2]), wv[3] - st_bf16_round(wv[3]));
+        hi[0] = pack_bf16(wv[0], wv[1]); hi[1] = pack_bf16(wv[2], wv[3]);
+        lo[0] = pack_bf16(wv[0] - bf16_round(wv[0]), wv[1] - bf16_round(wv[1]));
+        lo[1] = pack_bf16(wv[2] - bf16_round(wv[2]), wv[3] - bf16_round(wv[3]));
         const int off = ((c * 2 + hh) * (NCB * 64) + rowpos) * 16 + j0 * 2;
         *reinterpret_cast<u32x2*>(sWh + off) = hi;
         *reinterpret_cast<u32x2*>(sWl + off) = lo;
@@ -278,10 +266,7 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
       const int k = (int)(it % items_per_tile);
       // item `it` has landed when at most the 8 * (younger items in flight) youngest DMA pieces are outstanding
       // (pieces retire in order among themselves; stores in flight only make the wait more conservative)
-      const long long younger = TAPS ? 0 : issued - it - 1;
-      if (younger >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else if (younger == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      st_wait_landed(TAPS ? 0 : issued - it - 1);      // TAPS: nothing younger is in flight, its next request goes out just below
       const unsigned char* st = ring + (it % NS) * ST_STAGE;
       if (TAPS) {
         // two-stage ring (the 64 KB weight image leaves room for no more): the stage of item it - 1 was consumed in the previous
@@ -303,12 +288,12 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
           const f32x4 v0 = *reinterpret_cast<const f32x4*>(st + part_off(c * 4 + h * 2));
           const f32x4 v1 = *reinterpret_cast<const f32x4*>(st + part_off(c * 4 + h * 2 + 1));
           union { unsigned u[4]; bf16x8_t v; } ph, pl;
-          ph.u[0] = st_pack_bf16(v0[0], v0[1]); ph.u[1] = st_pack_bf16(v0[2], v0[3]);
-          ph.u[2] = st_pack_bf16(v1[0], v1[1]); ph.u[3] = st_pack_bf16(v1[2], v1[3]);
-          pl.u[0] = st_pack_bf16(v0[0] - st_bf16_round(v0[0]), v0[1] - st_bf16_round(v0[1]));
-          pl.u[1] = st_pack_bf16(v0[2] - st_bf16_round(v0[2]), v0[3] - st_bf16_round(v0[3]));
-          pl.u[2] = st_pack_bf16(v1[0] - st_bf16_round(v1[0]), v1[1] - st_bf16_round(v1[1]));
-          pl.u[3] = st_pack_bf16(v1[2] - st_bf16_round(v1[2]), v1[3] - st_bf16_round(v1[3]));
+          ph.u[0] = pack_bf16(v0[0], v0[1]); ph.u[1] = pack_bf16(v0[2], v0[3]);
+          ph.u[2] = pack_bf16(v1[0], v1[1]); ph.u[3] = pack_bf16(v1[2], v1[3]);
+          pl.u[0] = pack_bf16(v0[0] - bf16_round(v0[0]), v0[1] - bf16_round(v0[1]));
+          pl.u[1] = pack_bf16(v0[2] - bf16_round(v0[2]), v0[3] - bf16_round(v0[3]));
+          pl.u[2] = pack_bf16(v1[0] - bf16_round(v1[0]), v1[1] - bf16_round(v1[1]));
+          pl.u[3] = pack_bf16(v1[2] - bf16_round(v1[2]), v1[3] - bf16_round(v1[3]));
           const int wrow = ((k * 4 + c) * 2 + h) * (NCB * 64) + r;
 #pragma unroll
           for (int cb = 0; cb < NCB; ++cb)
@@ -439,7 +424,7 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
               unsigned hh[4], ll[4];
 #pragma unroll
               for (int j = 0; j < 4; ++j)
-                st_split_pair_f16(acc[cb][s4 >> 1][8 * (s4 & 1) + 2 * j] * sc, acc[cb][s4 >> 1][8 * (s4 & 1) + 2 * j + 1] * sc, hh[j], ll[j]);
+                split_pair_f16(acc[cb][s4 >> 1][8 * (s4 & 1) + 2 * j] * sc, acc[cb][s4 >> 1][8 * (s4 & 1) + 2 * j + 1] * sc, hh[j], ll[j]);
               const st_u4 hu = {hh[0], hh[1], hh[2], hh[3]}, lu = {ll[0], ll[1], ll[2], ll[3]};
               const st_h8 yh = __builtin_bit_cast(st_h8, hu), yl = __builtin_bit_cast(st_h8, lu);
               tacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(twl[s4], yh, tacc, 0, 0, 0);
@@ -541,10 +526,10 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // LDS map as conv1x1_stream_kernel<1>: weights hi | lo (16 KB each) | bias | 4 waves x NS stages
   constexpr int w_half = NKB * 4 * 2 * 64 * 16;
+  constexpr int ring_off = 2 * w_half + 64 * 4;
   unsigned char* sWh = smem;
   unsigned char* sWl = smem + w_half;
   float* sBias = reinterpret_cast<float*>(smem + 2 * w_half);
-  constexpr int ring_off = 2 * w_half + 64 * 4;
   unsigned char* ring = smem + ring_off + wave * NS * ST_STAGE;
   const unsigned ring_lds = (unsigned)(unsigned long long)(smem) + ring_off + wave * NS * ST_STAGE;
   auto chan_of_row = [](int n) { const int m = n & 31; return (n & ~31) + ((m >> 4) & 1) * 16 + ((m >> 2) & 1) * 8 + ((m >> 3) & 1) * 4 + (m & 3); };
@@ -569,9 +554,9 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
     const f32x4 wv = *reinterpret_cast<const f32x4*>(a.w + ((long long)kg * 64 + n) * 4);
     const int c = kg >> 2, hh = (kg >> 1) & 1, j0 = (kg & 1) * 4;
     u32x2 hi, lo;
-    hi[0] = st_pack_bf16(wv[0], wv[1]); hi[1] = st_pack_bf16(wv[2], wv[3]);
-    lo[0] = st_pack_bf16(wv[0] - st_bf16_round(wv[0]), wv[1] - st_bf16_round(wv[1]));
-    lo[1] = st_pack_bf16(wv[2] - st_bf16_round(wv[2]), wv[3] - st_bf16_round(wv[3]));
+    hi[0] = pack_bf16(wv[0], wv[1]); hi[1] = pack_bf16(wv[2], wv[3]);
+    lo[0] = pack_bf16(wv[0] - bf16_round(wv[0]), wv[1] - bf16_round(wv[1]));
+    lo[1] = pack_bf16(wv[2] - bf16_round(wv[2]), wv[3] - bf16_round(wv[3]));
     const int off = ((c * 2 + hh) * 64 + rowpos) * 16 + j0 * 2;
     *reinterpret_cast<u32x2*>(sWh + off) = hi;
     *reinterpret_cast<u32x2*>(sWl + off) = lo;
@@ -615,10 +600,7 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
     for (int j = 0; j < CH; ++j) g[j] = 0.f;
     for (long long it = 0; it < n_items; ++it) {
       const int k = (int)(it % IPT);
-      const long long younger = issued - it - 1;
-      if (younger >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else if (younger == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      st_wait_landed(issued - it - 1);
       const unsigned char* st = ring + (it % NS) * ST_STAGE;
       if (k == 0) {
 #pragma unroll
@@ -633,12 +615,12 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
           const f32x4 v0 = *reinterpret_cast<const f32x4*>(st + part_off(c * 4 + h * 2));
           const f32x4 v1 = *reinterpret_cast<const f32x4*>(st + part_off(c * 4 + h * 2 + 1));
           union { unsigned u[4]; bf16x8_t v; } ph, pl;
-          ph.u[0] = st_pack_bf16(v0[0], v0[1]); ph.u[1] = st_pack_bf16(v0[2], v0[3]);
-          ph.u[2] = st_pack_bf16(v1[0], v1[1]); ph.u[3] = st_pack_bf16(v1[2], v1[3]);
-          pl.u[0] = st_pack_bf16(v0[0] - st_bf16_round(v0[0]), v0[1] - st_bf16_round(v0[1]));
-          pl.u[1] = st_pack_bf16(v0[2] - st_bf16_round(v0[2]), v0[3] - st_bf16_round(v0[3]));
-          pl.u[2] = st_pack_bf16(v1[0] - st_bf16_round(v1[0]), v1[1] - st_bf16_round(v1[1]));
-          pl.u[3] = st_pack_bf16(v1[2] - st_bf16_round(v1[2]), v1[3] - st_bf16_round(v1[3]));
+          ph.u[0] = pack_bf16(v0[0], v0[1]); ph.u[1] = pack_bf16(v0[2], v0[3]);
+          ph.u[2] = pack_bf16(v1[0], v1[1]); ph.u[3] = pack_bf16(v1[2], v1[3]);
+          pl.u[0] = pack_bf16(v0[0] - bf16_round(v0[0]), v0[1] - bf16_round(v0[1]));
+          pl.u[1] = pack_bf16(v0[2] - bf16_round(v0[2]), v0[3] - bf16_round(v0[3]));
+          pl.u[2] = pack_bf16(v1[0] - bf16_round(v1[0]), v1[1] - bf16_round(v1[1]));
+          pl.u[3] = pack_bf16(v1[2] - bf16_round(v1[2]), v1[3] - bf16_round(v1[3]));
           const int wrow = ((k * 4 + c) * 2 + h) * 64 + r;
 #pragma unroll
           for (int ni = 0; ni < 2; ++ni) {
@@ -734,6 +716,28 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
   }
 }
 
+// ---- host side of both kernels
+// the stream of B images of P pixels as 128-pixel tiles, and the persistent grid over the calling thread's CUs; false: no device
+inline bool st_tiling(int B, long long P, int& tiles_per_image, long long& tiles, int& grid) {
+  tiles_per_image = (int)((P + 127) / 128);
+  tiles = (long long)B * tiles_per_image;
+  const int cus = cdfo_num_cus();
+  grid = (int)(tiles < cus ? tiles : cus);
+  return cus > 0;
+}
+// the kernels' LDS map: split weights hi | lo and the bias in front of the rings
+inline int st_weight_bytes(int nkb, int ncb) { return 2 * (nkb * 4 * 2 * ncb * 64 * 16) + ncb * 64 * 4; }
+inline int st_lds_bytes(int nkb, int ncb, int ns) { return st_weight_bytes(nkb, ncb) + 4 * ns * ST_STAGE; }
+
+// `once`: the call site's static table, one per kernel instantiation.  Returns 0 or the hipError_t.
+template <class KernelPtr, class Args>
+int st_launch(KernelPtr kernel, CdfoAttrOnce& once, int grid, int lds, hipStream_t st, const Args& s) {
+  const hipError_t e = cdfo_set_max_lds(once, reinterpret_cast<const void*>(kernel), ST_MAX_LDS);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(ST_THREADS), lds, st, s);
+  return (int)hipGetLastError();
+}
+
 }  // namespace
 
 // Pure host arithmetic of the partial slots (no device needed): slots per image written by a launch of `grid` workgroups, and the
@@ -780,28 +784,17 @@ extern "C" int cdfo_align_stats(const float* x0, int ld0, const float* x1, int l
   sg_args s{};
   s.src[0] = {x0, ld0, 0}; s.src[1] = {x1, ld1, 0}; s.src[2] = {q, ldq, 0};
   s.w = w_packed; s.bias = bias; s.act_fn = act;
-  s.P = P; s.tiles_per_image = (int)((P + 127) / 128); s.tiles = (long long)B * s.tiles_per_image;
+  s.P = P;
   s.gram = gram_partial; s.sum0 = sum0_partial; s.sum1 = sum1_partial; s.slots = nslots;
-  const int cus = cdfo_num_cus();
-  if (cus <= 0) return CDFO_EINVAL;
-  const int grid = (int)(s.tiles < cus ? s.tiles : cus);
+  int grid;
+  if (!st_tiling(B, P, s.tiles_per_image, s.tiles, grid)) return CDFO_EINVAL;
   if (nslots < st_slots(B, s.tiles_per_image, grid)) return CDFO_EINVAL;
-  const int lds = 2 * (2 * 4 * 2 * 64 * 16) + 64 * 4 + 4 * SG_NS * ST_STAGE;
+  const int lds = st_lds_bytes(2, 1, SG_NS);
   const double px = (double)B * P;
   CdfoProfScope prof(st, KID_GRAM, px * (2.0 * 128 * 64 + 2.0 * 64 * 18), 4.0 * 192 * px);
-  if (ch_per_head == 16) {
-    static CdfoAttrOnce once;
-    const hipError_t e = cdfo_set_max_lds(once, reinterpret_cast<const void*>(align_gram_partial_kernel<16>), 160 * 1024 - 256);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(align_gram_partial_kernel<16>, dim3(grid), dim3(ST_THREADS), lds, st, s);
-  } else {
-    static CdfoAttrOnce once;
-    const hipError_t e = cdfo_set_max_lds(once, reinterpret_cast<const void*>(align_gram_partial_kernel<8>), 160 * 1024 - 256);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(align_gram_partial_kernel<8>, dim3(grid), dim3(ST_THREADS), lds, st, s);
-  }
-  CDFO_LAUNCH_CHECK();
-  return 0;
+  static CdfoAttrOnce once8, once16;
+  return ch_per_head == 16 ? st_launch(align_gram_partial_kernel<16>, once16, grid, lds, st, s)
+                           : st_launch(align_gram_partial_kernel<8>, once8, grid, lds, st, s);
 }
 
 // Returns 1 when the streaming kernel took the launch, 0 when the shapes are outside its contract (the caller falls back to
@@ -819,31 +812,23 @@ int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st) {
     s.Cin = 64; s.Cout = 256; s.CoutP = 256; s.act_fn = a.act;
     s.out = a.out; s.ldo = a.ldo; s.B = a.B; s.P = (long long)a.H * a.W;
     s.w_last = a.res2; s.W = a.W;
-    s.tiles_per_image = (int)((s.P + 127) / 128);
-    s.tiles = (long long)a.B * s.tiles_per_image;
     s.ns = 2;
-    const int w_bytes = 2 * 1 * 4 * 2 * 4 * 64 * 16 + 4 * 64 * 4;
-    const int lds = w_bytes + 4 * s.ns * ST_STAGE;
-    const int cus = cdfo_num_cus();
-    if (cus <= 0) return CDFO_EINVAL;
-    const int grid = (int)(s.tiles < cus ? s.tiles : cus);
+    int grid;
+    if (!st_tiling(a.B, s.P, s.tiles_per_image, s.tiles, grid)) return CDFO_EINVAL;
     const double px = (double)a.B * s.P;
     CdfoProfScope prof(st, KID_CONV1, 2.0 * px * 256 * 64 + 2.0 * px * 4 * 9 * 64, 4.0 * (px * 64 + px * 4 * a.ldo + 64.0 * 256));
     static CdfoAttrOnce once;
-    const hipError_t e = cdfo_set_max_lds(once, reinterpret_cast<const void*>(conv1x1_stream_kernel<4, true>), 160 * 1024 - 256);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((conv1x1_stream_kernel<4, true>), dim3(grid), dim3(ST_THREADS), lds, st, s);
-    const hipError_t e2 = hipGetLastError();
-    return e2 == hipSuccess ? 1 : (int)e2;
+    const int e = st_launch(conv1x1_stream_kernel<4, true>, once, grid, st_lds_bytes(1, 4, s.ns), st, s);
+    return e == 0 ? 1 : e;
   }
   if (a.store_mode != CDFO_STORE_PLAIN || (a.ln_gamma && !ln_out) || a.CoutP % 64 || a.CoutP > 128 || a.Cout % 8) return 0;      // (ln_out without ln_gamma: plain fp16 copy)
   if (ln_out && (a.CoutP != 64 || a.Cout != 64)) return 0;
   if (a.chan_sum_out && (a.CoutP != 64 || a.Cout != 64 || ln_out || a.chan_sum_slots <= 0)) return 0;   // the caller sums in a pass of its own
   const int ncb = a.CoutP / 64, nkb = a.Cin / 64;
   if (nkb < 1 || nkb > CDFO_MAXSRC * 4) return 0;
-  const int w_bytes = 2 * nkb * 4 * 2 * ncb * 64 * 16 + ncb * 64 * 4;
+  const int w_bytes = st_weight_bytes(nkb, ncb);
   const int scale_bytes = (a.res2 && a.res2_pixscale) ? 4 * 512 : 0;      // two tile-parity slots per wave
-  int ns = (160 * 1024 - 256 - scale_bytes - w_bytes) / (4 * ST_STAGE);
+  int ns = (ST_MAX_LDS - scale_bytes - w_bytes) / (4 * ST_STAGE);
   if (ns > ST_MAXNS) ns = ST_MAXNS;
   if (scale_bytes) {
     // the per-pixel factors of tile t + 2 are requested with item (t + 2, 0), NS - 1 items ahead of consumption, into the slot tile t
@@ -871,34 +856,20 @@ int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st) {
   s.Cin = a.Cin; s.Cout = a.Cout; s.CoutP = a.CoutP; s.act_fn = a.act;
   s.out = a.out; s.ldo = a.ldo; s.B = a.B; s.P = P;
   s.ln_hl = ln_out ? static_cast<_Float16*>(a.out2_cp16) : nullptr; s.ln_g = a.ln_gamma; s.ln_b = a.ln_beta;
-  s.tiles_per_image = (int)((P + 127) / 128);
-  s.tiles = (long long)a.B * s.tiles_per_image;
   s.ns = ns;
-  const int cus = cdfo_num_cus();
-  if (cus <= 0) return CDFO_EINVAL;
-  const int grid = (int)(s.tiles < cus ? s.tiles : cus);
-  const int lds = w_bytes + 4 * ns * ST_STAGE + scale_bytes;
+  int grid;
+  if (!st_tiling(a.B, P, s.tiles_per_image, s.tiles, grid)) return CDFO_EINVAL;
+  const int lds = st_lds_bytes(nkb, ncb, ns) + scale_bytes;
   const double px = (double)a.B * P;
   CdfoProfScope prof(st, KID_CONV1, 2.0 * px * a.Cout * a.Cin, 4.0 * (px * a.Cout * (1 + nr) + px * a.Cin + (double)a.Cin * a.Cout));
   if (a.chan_sum_out) {
     // (checked above: ncb == 1, Cout == 64) the result's channel sums from the epilogue's registers, one slot per (image, workgroup segment)
     if (a.chan_sum_slots < st_slots(a.B, s.tiles_per_image, grid)) return 0;
     s.csum = a.chan_sum_out; s.csum_slots = a.chan_sum_slots;
-    static CdfoAttrOnce once;
-    const hipError_t e = cdfo_set_max_lds(once, reinterpret_cast<const void*>(conv1x1_stream_kernel<1, false, true>), 160 * 1024 - 256);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((conv1x1_stream_kernel<1, false, true>), dim3(grid), dim3(ST_THREADS), lds, st, s);
-  } else if (ncb == 1) {
-    static CdfoAttrOnce once;
-    const hipError_t e = cdfo_set_max_lds(once, reinterpret_cast<const void*>(conv1x1_stream_kernel<1>), 160 * 1024 - 256);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(conv1x1_stream_kernel<1>, dim3(grid), dim3(ST_THREADS), lds, st, s);
-  } else {
-    static CdfoAttrOnce once;
-    const hipError_t e = cdfo_set_max_lds(once, reinterpret_cast<const void*>(conv1x1_stream_kernel<2>), 160 * 1024 - 256);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(conv1x1_stream_kernel<2>, dim3(grid), dim3(ST_THREADS), lds, st, s);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 1 : (int)e;
+  static CdfoAttrOnce once_csum, once1, once2;
+  const int e = a.chan_sum_out ? st_launch(conv1x1_stream_kernel<1, false, true>, once_csum, grid, lds, st, s)
+                : ncb == 1     ? st_launch(conv1x1_stream_kernel<1>, once1, grid, lds, st, s)
+                               : st_launch(conv1x1_stream_kernel<2>, once2, grid, lds, st, s);
+  return e == 0 ? 1 : e;
 }

@@ -24,7 +24,7 @@
 // (|in * mask| > 3750 max |in|, i.e. a mask far outside [0, 1]) or is not finite raises a device flag, and
 // cdfo_dcn_forward then re-runs the exact-fp32 kernel of dcn.hip over the whole result (its workgroups return at once
 // while the flag is clear).  Callers who want the exact kernel unconditionally pass workspace = NULL.
-#include "common.h"
+#include "numeric.h"
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -51,11 +51,6 @@ __global__ __launch_bounds__(256) void dcn_wmax_kernel(const float* __restrict__
   if ((threadIdx.x & 63) == 0 && m < 3.0e38f) atomicMax(wmax, __float_as_uint(m));
 }
 
-__device__ __forceinline__ float pow2_scale(unsigned max_bits) {
-  const float m = __uint_as_float(max_bits);
-  // a power of two: m * s in (8, 16]; the exponent is clamped so that neither s nor 1 / s leaves the fp32 range
-  return m > 0.f ? exp2f(fminf(fmaxf(4.f - ceilf(log2f(m)), -100.f), 100.f)) : 1.f;
-}
 __device__ __forceinline__ float weight_scale(const unsigned* wmax) { return pow2_scale(wmax[0]); }
 
 // one thread per fp16 element of the packed A operand: index = (((chunk*S + s)*MT + mtile)*64 + lane)*8 + j

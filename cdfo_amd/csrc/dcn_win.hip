@@ -25,7 +25,7 @@
 //     cdfo_dcn_forward re-runs the exact-fp32 kernel, as for dcn_fast.
 // HBM roofline: (C + 3*dg*9 + Co) * 4 bytes per output pixel; offsets + mask are 77 % of it and are read
 // exactly once, coalesced (each half-wave reads 128-byte rows of one tap plane).
-#include "common.h"
+#include "numeric.h"
 
 typedef _Float16 wn_h8 __attribute__((ext_vector_type(8)));
 
@@ -59,11 +59,6 @@ struct WinArgs {
   int tiles_x, ntiles;
 };
 
-__device__ __forceinline__ float wn_pow2_scale(unsigned max_bits) {      // as dcn_fast.hip: m * s in (8, 16]
-  const float m = __uint_as_float(max_bits);
-  return m > 0.f ? exp2f(fminf(fmaxf(4.f - ceilf(log2f(m)), -100.f), 100.f)) : 1.f;
-}
-
 __global__ __launch_bounds__(256) void dcn_win_wmax_kernel(const float* __restrict__ w, long long n, unsigned* __restrict__ wmax) {
   float m = 0.f;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
@@ -83,7 +78,7 @@ __global__ __launch_bounds__(256) void dcn_win_pack_kernel(const float* __restri
   const int blk = lane >> 5, t = 2 * s + (e >> 2);
   const int c = 8 * chunk + 4 * blk + (e & 3), m = mj * 32 + (lane & 31);
   float v = 0.f;
-  if (t < WN_T && c < C && m < Co) v = w[((long long)m * C + c) * WN_T + t] * wn_pow2_scale(wmax[0]);
+  if (t < WN_T && c < C && m < Co) v = w[((long long)m * C + c) * WN_T + t] * pow2_scale(wmax[0]);
   const _Float16 h = (_Float16)v;
   wp[gid] = hl ? (_Float16)(v - (float)h) : h;
 }
@@ -447,7 +442,7 @@ __global__ __launch_bounds__(WN_THREADS) void dcn_win_kernel(WinArgs a) {
   if (ovfbits) atomicOr(a.flags + 2, 1u);      // out of the fp16 hi + lo range somewhere: the exact kernel re-runs (dcn.hip)
   // ---- store D[row = cout][col = pixel] (+ bias), NCHW: 32 lanes = 128 contiguous bytes of one output row
   if (pvalid) {
-    const float inv = ldexpf(1.f / wn_pow2_scale(a.flags[0]), e_run > -1000 ? e_run - 3 : 0);
+    const float inv = ldexpf(1.f / pow2_scale(a.flags[0]), e_run > -1000 ? e_run - 3 : 0);
 #pragma unroll
     for (int j = 0; j < MJ; ++j)
 #pragma unroll

@@ -2,7 +2,7 @@
 // warp, 2x2 mean / bilinear x2 resampling, channel gating, the final 64->1 conv fused with the bilinear x4 skip.
 // One pixel's 64 channels are a contiguous 256-B run, so 16 consecutive lanes (a float4 each) cover a pixel and
 // every wave-instruction moves 4 whole pixels = 1 KiB, fully coalesced.
-#include "common.h"
+#include "numeric.h"
 
 namespace {
 
@@ -407,14 +407,6 @@ __global__ __launch_bounds__(256) void scale_channels_kernel(const float* __rest
 // then the sum of nine parked values at its shifted positions.  (First cut: every output pixel gathered its 3x3
 // neighbourhood itself, 9 x 256 B per pixel through the caches: 1.3 TB/s.)
 constexpr int CL_TY = 16, CL_TX = 64, CL_HX = CL_TX + 2, CL_NP = (CL_TY + 2) * CL_HX;    // 1188 halo pixels
-
-__device__ __forceinline__ float row16_sum(float v) {     // sum over the 16 lanes of a DPP row, result in every lane
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xF, 0xF, true));  // row_ror:4
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, true));  // row_ror:8
-  return v;
-}
 
 __global__ __launch_bounds__(256) void conv_last_kernel(const float* __restrict__ in, int ldi,
                                                         const float* __restrict__ w, const float* __restrict__ bias,

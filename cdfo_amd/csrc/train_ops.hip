@@ -12,7 +12,7 @@
 //     stored), flow_warp's scatter, the bilinear resamples' adjoints.
 // All tensors fp32 pixel-major [B][H][W][C] with a pixel pitch ld >= C (floats), like the rest of the library.
 // Correctness-first: plain VALU kernels except the weight gradient; training runs on 64x64 crops (train_LD_37.py:316-325).
-#include "common.h"
+#include "numeric.h"
 
 namespace {
 
@@ -461,18 +461,8 @@ __global__ __launch_bounds__(256) void sg16_wgrad_kernel(const float* __restrict
 // ------------------------------------------------------------------------------------------------ Gumbel hard mask as a tensor
 // mask[p][c] = softmax_c(vmax[b][c] - log(-log u[b][c][p])) >= 0.5   (arch.py:2168-2195); 4 lanes per pixel.
 // RNG: the uniforms are drawn here exactly as cdfo_rdab_prep_rng draws them (attention.hip: Philox4x32-10, counter =
-// (pixel, image, channel group, draw), key = seed), so the training and the inference path see the same noise for one seed.
-__device__ __forceinline__ void tr_philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                                 unsigned (&o)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
+// (pixel, image, channel group, draw), key = seed; one philox4x32_10, numeric.h), so the training and the inference path see the
+// same noise for one seed.
 template <bool RNG>
 __global__ __launch_bounds__(256) void gumbel_mask_kernel(const float* __restrict__ vmax, const float* __restrict__ noise, long long P,
                                                           long long npix, float* __restrict__ mask, int ldm, unsigned long long seed,
@@ -485,7 +475,7 @@ __global__ __launch_bounds__(256) void gumbel_mask_kernel(const float* __restric
 #pragma unroll
   for (int jj = 0; jj < 4; ++jj) {
     unsigned o[4] = {0u, 0u, 0u, 0u};
-    if (RNG) tr_philox4x32_10((unsigned)pin, (unsigned)b, (unsigned)(part * 4 + jj), draw, (unsigned)seed, (unsigned)(seed >> 32), o);
+    if (RNG) philox4x32_10((unsigned)pin, (unsigned)b, (unsigned)(part * 4 + jj), draw, (unsigned)seed, (unsigned)(seed >> 32), o);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int c = jj * 4 + k, ch = part * 16 + c;
