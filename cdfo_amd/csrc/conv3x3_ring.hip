@@ -527,8 +527,8 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_kernel(cdfo_conv_args
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Wave-specialised form of the same kernel (round 3; same LDS map, stage layout, DMA pieces, unit order and epilogue
-// arithmetic as conv3x3_ring_kernel above -- the results are bit-identical).
+// Wave-specialised form of the four-tap kernel on v_mfma_f32_16x16x32_f16 (round 3; same LDS map, DMA pieces, unit order and
+// epilogue arithmetic as conv3x3_ring_kernel<true> above).  The dense convolutions keep conv3x3_ring_kernel (see rg_launch).
 //
 // Why.  s_memtime stamps inside the kernel above (dbg 16, tools/ring_timeline.py) show where a chunk's cycles go: with eight
 // identical waves -- two per SIMD, each owning 2 tile rows and issuing its share of the DMA pieces between its taps -- a wave
@@ -537,32 +537,34 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_kernel(cdfo_conv_args
 // after the older one, which then sits at the barrier; 290-400 cycles pass between the barrier and a chunk's first MFMA.  The
 // matrix pipe is busy 36 % (four-tap form) / 47 % (dense) of the launch (SQ counters, profiles/r03_pmc_counters_conv3x3_ring.txt).
 // Here the two jobs are separated:
-//   * waves 0-3 (one per SIMD) are CONSUMERS: 4 tile rows x 32 pixels x 64 channels each (8 accumulators), nothing in their
-//     instruction stream but fragment reads and MFMAs (0.75 ds_read_b128 per MFMA instead of 1);
-//   * waves 4-7 (the other wave of each SIMD) are PRODUCERS: all DMA pieces of a chunk (dense: 10 per wave; four-tap form: 8),
-//     the ring cursor, the half-resolution residual tile -- scalar work and DMA issue that now overlap the consumer's MFMAs
-//     instead of interrupting them.
+//   * waves 0-3 (one per SIMD) are CONSUMERS: 4 tile rows x 32 pixels x 64 channels each, nothing in their instruction stream
+//     but fragment reads and MFMAs;
+//   * waves 4-7 (the other wave of each SIMD) are PRODUCERS: all DMA pieces of a chunk (8 per wave), the ring cursor, the
+//     half-resolution residual tile -- scalar work and DMA issue that now overlap the consumer's MFMAs instead of
+//     interrupting them.
 // One workgroup barrier per chunk, as before: producers arrive once THEIR pieces of batch g have landed (counted vmcnt),
 // consumers once their fragment reads of batch g-1 have returned; behind it the producers refill the stage of batch g-1.
 // Both role loops execute exactly my_units * nc barriers.
-// MF16 (four-tap form only): the consumers run v_mfma_f32_16x16x32_f16 instead of 32x32x16 -- the loop is power-limited and the
+// The consumers run v_mfma_f32_16x16x32_f16, not the 32x32x16 of conv3x3_ring_kernel -- the loop is power-limited and the
 // chip holds a higher clock under that shape (see conv3x3_ws.hip, conv3x3_c64_wsq_kernel): K = 32 = the two taps of a window row
 // x 16 channels; a lane holds k-group l >> 4 = (tap of the pair, 8-channel half) of pixel / output channel l & 15; natural
 // [pixel][16 ch] records (no half swizzle: this read pattern is conflict-free without it) and a weight-row order in which a
 // lane's accumulators of channel blocks 2e, 2e+1 are 8 consecutive channels (the epilogue keeps its 32-byte granularity).
-template <bool SPARSE, int DBG, bool MF16 = false>
+// Its 32x32x16 consumer (8 accumulators of 32 x 32 per wave, 0.75 ds_read_b128 per MFMA, swizzled records; results bit-identical
+// to conv3x3_ring_kernel) and with it the dense instantiation's text were retired at this commit; git history keeps them.
+template <bool SPARSE, int DBG>
 __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_conv_args a, ring_extra e) {
-  static_assert(!MF16 || SPARSE, "the 16x16x32 consumer exists for the four-tap form");
+  static_assert(SPARSE, "the wave-specialised form exists for the four-tap convolutions only");
+  static_assert(!(DBG & (4 | 16)), "the clock experiment and the timeline probe live in conv3x3_ring_kernel");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int TAPS = SPARSE ? 4 : 9;
+  constexpr int TAPS = 4;
   using L = RingLds<SPARSE>;
   constexpr int STAGE = L::STAGE, RG_NS = L::NS;
   constexpr int CR = 4;                               // tile rows per consumer wave
-  // producer pieces per chunk: dense 10 + 10 activation pieces, 9 + 9 weight pieces (+1 pad each); four-tap form 7 + 7 + 6
-  // activation pieces (+1, +1, +2 pads into the dump kilobyte) and 8 weight pieces: every producer issues exactly PPW
-  // instructions per batch, which is what the counted waits count
-  constexpr int PPW = SPARSE ? 8 : 10, ACT_PW = SPARSE ? 3 : 2, ACT_PER = SPARSE ? 7 : 10, WGT_PER = SPARSE ? 8 : 9;
-  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r = lane & 31;
+  // producer pieces per chunk: 7 + 7 + 6 activation pieces (+1, +1, +2 pads into the dump kilobyte) and 8 weight pieces:
+  // every producer issues exactly PPW instructions per batch, which is what the counted waits count
+  constexpr int PPW = 8, ACT_PW = 3, ACT_PER = 7, WGT_PER = 8;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool consumer = wave < 4;
   const int H = a.H, W = a.W, nc = e.nc;
@@ -578,8 +580,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
   for (int i = tid; i < a.CoutP; i += RG_THREADS)
     reinterpret_cast<float*>(smem + L::BIAS)[i] = (a.bias && i < a.Cout) ? a.bias[i] : 0.f;
   auto win_of = [](unsigned tm) { return ((tm & 0x7u) ? 0 : 2) + ((tm & 0x49u) ? 0 : 1); };
-  if (SPARSE)
-    for (int i = tid; i < nc; i += RG_THREADS) smem[L::WINTAB + i] = (unsigned char)win_of(e.tap_mask[i]);
+  for (int i = tid; i < nc; i += RG_THREADS) smem[L::WINTAB + i] = (unsigned char)win_of(e.tap_mask[i]);
   // (bias and window table become visible to the consumers through the chunk barriers: the first read of either comes after
   // the first barrier)
   const int total = my_units * nc;                    // chunk batches = barriers of this workgroup
@@ -602,7 +603,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
       if (!loader_w) {
         const int q = pw * ACT_PER + j;
         const bool real = j < ACT_PER && q < 20;
-        const int s = q * 64 + lane, p = s >> 1, half = MF16 ? (s & 1) : (s & 1) ^ ((p >> 3) & 1);
+        const int s = q * 64 + lane, p = s >> 1, half = s & 1;      // natural [pixel][16 ch] records
         const int iy = p / RG_IW, ix = p - iy * RG_IW;
         d_iy[j] = (real && p < RG_NPIX) ? iy : 1 << 20;
         d_ix[j] = ix;
@@ -613,9 +614,9 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
         const bool real = j < WGT_PER && q < TAPS * 2;
         d_iy[j] = real ? 0 : 1 << 20;
         d_ix[j] = 0;
-        const int m = lane & 31;      // slab row position `lane` = MFMA row m of block (lane >> 5), see the kernel above
-        const int chan = MF16 ? (lane >> 5) * 32 + ((lane & 15) >> 2) * 8 + ((lane >> 4) & 1) * 4 + (lane & 3)
-                              : (lane & 32) + ((m >> 4) & 1) * 16 + ((m >> 2) & 1) * 8 + ((m >> 3) & 1) * 4 + (m & 3);
+        // slab row position `lane` = MFMA row lane & 15 of 16-row block lane >> 4: a lane's accumulators of blocks 2e, 2e+1 are 8
+        // consecutive channels
+        const int chan = (lane >> 5) * 32 + ((lane & 15) >> 2) * 8 + ((lane >> 4) & 1) * 4 + (lane & 3);
         d_rel[j] = (q * e.CoutP + chan) * 16;
         dst_off[j] = real ? RG_ACT + q * 1024 : -1;
       }
@@ -678,9 +679,9 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
       //     are then in L2 / the Infinity Cache when the epilogue asks for them, and their HBM reads fall into the MFMA phase.
       constexpr int EPP = RG_ET_PIECES / 4, EPC = 2;       // residual-tile pieces per producer, per chunk
       constexpr int TCH = 8, TPC = 4;                      // touch chunks per tile, touch pieces per producer and chunk (4 x 8 x 4 = 128)
-      unsigned evoff[SPARSE ? EPP : 1];
+      unsigned evoff[EPP];
       i32x4 ersrc = rsrc_w, trsrc = rsrc_w;
-      const bool etile = SPARSE && a.res_up2 && !(DBG & 2);
+      const bool etile = a.res_up2 && !(DBG & 2);
       const bool touch = a.res1 != nullptr && !(DBG & (2 | 8)) && rg_touch_on(e);
       int ub, uoy0, uox0, un0;
       unit_coords(ord, ub, uoy0, uox0, un0);
@@ -709,8 +710,6 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
       const unsigned dump = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)L::DUMP);
       const int t0 = nc - TCH;                        // first touch chunk (tiles of fewer chunks are touched in part)
       for (int c = 0; c < nc; ++c, ++g) {
-        unsigned long long ts[4] = {0, 0, 0, 0};     // dbg 16: entry, pieces landed, barrier passed, batch issued
-        if (DBG & 16) asm volatile("s_memtime %0" : "=s"(ts[0]) : : "memory");
         // my pieces of batch g have landed: everything but the newest (NS - 2) batches and the extras issued behind them in
         // the last NS - 2 iterations may be pending (DMA pieces retire in issue order among themselves; a producer issues
         // nothing else)
@@ -725,14 +724,12 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
           else rg_wait_vm<(RG_NS - 2) * PPW>();      // (any other mix: the plain bound is always safe)
           static_assert((RG_NS - 2) * PPW + 2 * TPC < 64, "vmcnt is a 6-bit counter");
         }
-        if (DBG & 16) asm volatile("s_memtime %0" : "=s"(ts[1]) : : "memory");
         __builtin_amdgcn_s_barrier();
-        if (DBG & 16) asm volatile("s_memtime %0" : "=s"(ts[2]) : : "memory");
         // behind the barrier nobody reads the stage of batch g-1 any more (and, at c == 0, the previous tile's epilogue is
         // through with the residual tile)
         if (g + RG_NS - 1 < total) issue_batch();
         int extras = 0;
-        if (SPARSE && etile && c < EPP / EPC) {
+        if (etile && c < EPP / EPC) {
           // (c is a loop variable: the two pieces are selected by a uniform switch so that evoff[] stays in registers)
 #pragma unroll
           for (int k = 0; k < EPP / EPC; ++k)
@@ -755,17 +752,6 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
         }
         ex_prev2 = ex_prev1;
         ex_prev1 = extras;
-        if (DBG & 16) {
-          asm volatile("s_memtime %0" : "=s"(ts[3]) : : "memory");
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          if (ord == RG_PROBE_UNIT && c >= 8 && c < 12 && lane == 0) {
-            unsigned long long* cb = reinterpret_cast<unsigned long long*>(const_cast<float*>(a.res2)) +
-                                     (((long long)blockIdx.x * 8 + wave) * 4 + (c - 8)) * 10;
-            cb[0] = ts[0]; cb[1] = ts[1]; cb[2] = ts[2]; cb[3] = ts[3];
-#pragma unroll
-            for (int i = 4; i < 9; ++i) cb[i] = ts[3];
-          }
-        }
       }
     }
     return;
@@ -773,397 +759,141 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
 
   // ================================================================================================== consumers
   const float slope = a.act == CDFO_ACT_NONE ? 1.f : (a.act == CDFO_ACT_LRELU ? 0.1f : 0.f);
-  if constexpr (MF16) {
-    const int l16 = lane & 15, kg = lane >> 4, ktap = kg >> 1, khalf = kg & 1;
-    // weight fragment of (tap pair, channel block mb): slab row (pair*2 + ktap)*2 + khalf, position mb*16 + l16
-    const int w16 = RG_ACT + (ktap * 2 + khalf) * 1024 + l16 * 16;
-    // pixel fragments of the chunk about to be consumed (stage base included): halo rows 4w + rr + y0 (rr = row + pair = 0..4),
-    // column x0 + ktap + l16 (+16: immediate); computed one chunk ahead
-    int f16a[5] = {0, 0, 0, 0, 0};
-    auto frag16 = [&](int win, int stage_base) {
-      const int y0 = win >> 1, x0 = win & 1;
-#pragma unroll
-      for (int rr = 0; rr < 5; ++rr)
-        f16a[rr] = stage_base + ((wave * CR + rr + y0) * RG_IW + x0 + ktap + l16) * 32 + khalf * 16;
-    };
-    frag16(__builtin_amdgcn_readfirstlane(win_of(e.tap_mask[0])), 0);
-    int g = 0;
-    for (int ord = 0; ord < my_units; ++ord) {
-      // acc[mb][nbk][k]: block mb row 4 kg + k = channel (mb>>1)*32 + 8 kg + (mb&1)*4 + k; nbk = row*2 + pixel half
-      f32x4 acc[4][2 * CR];
-#pragma unroll
-      for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-        for (int nbk = 0; nbk < 2 * CR; ++nbk) acc[mb][nbk] = f32x4{0.f, 0.f, 0.f, 0.f};
-      int b, oy0, ox0, n0;
-      unit_coords(ord, b, oy0, ox0, n0);
-      const int oyw = oy0 + wave * CR;
-      auto chunk = [&](int c) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // my fragment reads of batch g-1 have returned
-        __builtin_amdgcn_s_barrier();
-        const unsigned char* sW = smem + (g % RG_NS) * STAGE + w16;
-        // four sub-steps: (tap pair, rows 0-1), (pair, rows 2-3); the weight fragments of a pair serve both
-        f16x8_t fw[2][4], fp[2][4];                 // [pair parity / sub-step parity][channel block / (row, pixel half)]
-        auto load_w = [&](int pair) {
-#pragma unroll
-          for (int mb = 0; mb < 4; ++mb) fw[pair & 1][mb] = *reinterpret_cast<const f16x8_t*>(sW + pair * 4096 + mb * 256);
-        };
-        auto load_p = [&](int ss) {
-          const int pair = ss >> 1, hr = ss & 1;
-#pragma unroll
-          for (int q = 0; q < 4; ++q)              // q = (row within the half)*2 + pixel half
-            fp[ss & 1][q] = *reinterpret_cast<const f16x8_t*>(smem + f16a[2 * hr + (q >> 1) + pair] + (q & 1) * 512);
-        };
-        load_w(0);
-        load_p(0);
-        const int win_n = smem[L::WINTAB + (c + 1 == nc ? 0 : c + 1)];
-#pragma unroll
-        for (int ss = 0; ss < 4; ++ss) {
-          if (ss < 3) load_p(ss + 1);
-          if (ss == 1) load_w(1);
-          __builtin_amdgcn_sched_barrier(0);
-          const int pair = ss >> 1, hr = ss & 1;
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb) {
-              if (DBG & 1) acc[mb][hr * 4 + q][0] += (float)fw[pair & 1][mb][0] * (float)fp[ss & 1][q][0];
-              else acc[mb][hr * 4 + q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[pair & 1][mb], fp[ss & 1][q], acc[mb][hr * 4 + q], 0, 0, 0);
-            }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        frag16(__builtin_amdgcn_readfirstlane(win_n), ((g + 1) % RG_NS) * STAGE);
-      };
-      // residual values of one tile row: [pixel half][e][4-channel half] -- 32 contiguous bytes per (pixel, e)
-      const bool has_res = a.res1 != nullptr && !(DBG & 8);
-      auto px_ok = [&](int mi, int nh) { return oyw + mi < H && ox0 + nh * 16 + l16 < W; };
-      auto load_res_row = [&](int mi, f32x4 (&rv)[2][2][2]) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) (&rv[0][0][0])[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (!has_res) return;
-#pragma unroll
-        for (int nh = 0; nh < 2; ++nh) {
-          if (!px_ok(mi, nh)) continue;
-          const float* rp = a.res1 + ((long long)(b * H + oyw + mi) * W + ox0 + nh * 16 + l16) * a.ldr1 + n0 + kg * 8;
-#pragma unroll
-          for (int ee = 0; ee < 2; ++ee)
-            if (n0 + ee * 32 + kg * 8 < a.Cout) {
-              rv[nh][ee][0] = *reinterpret_cast<const f32x4*>(rp + ee * 32);
-              rv[nh][ee][1] = *reinterpret_cast<const f32x4*>(rp + ee * 32 + 4);
-            }
-        }
-      };
-      for (int c = 0; c < nc - 1; ++c, ++g) chunk(c);
-      f32x4 rva[2][2][2], rvb[2][2][2];
-      load_res_row(0, rva);
-      chunk(nc - 1);
-      ++g;
-      if (DBG & 8) {
-        float t = 0.f;
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-          for (int nbk = 0; nbk < 2 * CR; ++nbk)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) t += acc[mb][nbk][k] + rva[nbk & 1][mb & 1][0][k];
-        if (t == 123.456f) a.out[0] = t;
-        continue;
-      }
-      auto epilogue_row = [&](int mi, const f32x4 (&rv)[2][2][2]) {
-        const int oy = oyw + mi;
-#pragma unroll
-        for (int nh = 0; nh < 2; ++nh) {
-          const int X = ox0 + nh * 16 + l16;
-          const bool ok = px_ok(mi, nh);
-          const long long pix = (long long)(b * H + oy) * W + X;
-#pragma unroll
-          for (int ee = 0; ee < 2; ++ee) {
-            const int n = n0 + ee * 32 + kg * 8;
-            const f32x4 b0 = *reinterpret_cast<const f32x4*>(smem + L::BIAS + n * 4);
-            const f32x4 b1 = *reinterpret_cast<const f32x4*>(smem + L::BIAS + n * 4 + 16);
-            f32x4 v0, v1;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              const float t0 = acc[2 * ee][mi * 2 + nh][k] + b0[k], t1 = acc[2 * ee + 1][mi * 2 + nh][k] + b1[k];
-              v0[k] = fmaxf(t0, slope * t0);
-              v1[k] = fmaxf(t1, slope * t1);
-            }
-            v0 += rv[nh][ee][0];
-            v1 += rv[nh][ee][1];
-            if (!ok || n >= a.Cout) continue;
-            if (a.res2) {
-              const float* p2 = a.res2 + pix * a.ldr2 + n;
-              v0 += *reinterpret_cast<const f32x4*>(p2);
-              v1 += *reinterpret_cast<const f32x4*>(p2 + 4);
-            }
-            if (a.res_up2) {      // + bilinear x2 of the half-resolution tensor, from the staged tile (see the form above)
-              const float ly = (oy & 1) ? 0.25f : 0.75f, lx = (X & 1) ? 0.25f : 0.75f;
-              const int li = ((oy + 1) >> 1) - (oy0 >> 1), lj = ((X + 1) >> 1) - (ox0 >> 1);
-              const unsigned char* et = smem + L::ETILE;
-              const int cq = (ee * 32 + kg * 8) >> 2;
-#pragma unroll
-              for (int hf = 0; hf < 2; ++hf) {
-                auto tap = [&](int i, int j) {
-                  const int px = i * RG_ET_COLS + j;
-                  return *reinterpret_cast<const f32x4*>(et + px * 256 + (((cq + hf) ^ (px & 15)) << 4));
-                };
-                (hf ? v1 : v0) += (1.f - ly) * ((1.f - lx) * tap(li, lj) + lx * tap(li, lj + 1)) +
-                                  ly * ((1.f - lx) * tap(li + 1, lj) + lx * tap(li + 1, lj + 1));
-              }
-            }
-            f16x8_t hv;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { hv[k] = (_Float16)v0[k]; hv[4 + k] = (_Float16)v1[k]; }
-            if (a.out_f16) {
-              *reinterpret_cast<f16x8_t*>(reinterpret_cast<_Float16*>(a.out) + pix * a.ldo + n) = hv;
-            } else {
-              *reinterpret_cast<f32x4*>(a.out + pix * a.ldo + n) = v0;
-              *reinterpret_cast<f32x4*>(a.out + pix * a.ldo + n + 4) = v1;
-            }
-            if (a.out2_cp16) {
-              const int npl = a.out2_lo ? (a.Cout >> 3) : (a.Cout >> 4);
-              _Float16* o2 = static_cast<_Float16*>(a.out2_cp16) + (((long long)b * npl + (n >> 4)) * H * W + (long long)oy * W + X) * 16 + (n & 15);
-              *reinterpret_cast<f16x8_t*>(o2) = hv;
-              if (a.out2_lo) {
-                f16x8_t lv;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { lv[k] = (_Float16)(v0[k] - (float)hv[k]); lv[4 + k] = (_Float16)(v1[k] - (float)hv[4 + k]); }
-                *reinterpret_cast<f16x8_t*>(o2 + (long long)(a.Cout >> 4) * H * W * 16) = lv;
-              }
-            }
-          }
-        }
-      };
-      load_res_row(1, rvb);
-      epilogue_row(0, rva);
-      load_res_row(2, rva);
-      epilogue_row(1, rvb);
-      load_res_row(3, rvb);
-      epilogue_row(2, rva);
-      epilogue_row(3, rvb);
-    }
-    return;
-  }
-  const int w_off = RG_ACT + (h * 64 + r) * 16;
-  // dense: fragment offsets of halo rows 4w + rr (rr = 0..5), column offset dx, this lane's pixel r
-  int p_off[SPARSE ? 1 : 18];
-  if (!SPARSE) {
-#pragma unroll
-    for (int rr = 0; rr < 6; ++rr)
-#pragma unroll
-      for (int dx = 0; dx < 3; ++dx) {
-        const int p = (wave * CR + rr) * RG_IW + dx + r;
-        p_off[SPARSE ? 0 : rr * 3 + dx] = (2 * p + (h ^ ((p >> 3) & 1))) * 16;
-      }
-  }
-  // four-tap form: LDS byte addresses (stage base included) of the chunk about to be consumed: halo rows 4w + rr + y0
-  // (rr = 0..4), columns x0 + dx + r -- computed one chunk ahead
-  int f_cur[5][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}};
-  auto frag_addresses = [&](int win, int stage_base) {
+  const int l16 = lane & 15, kg = lane >> 4, ktap = kg >> 1, khalf = kg & 1;
+  // weight fragment of (tap pair, channel block mb): slab row (pair*2 + ktap)*2 + khalf, position mb*16 + l16
+  const int w16 = RG_ACT + (ktap * 2 + khalf) * 1024 + l16 * 16;
+  // pixel fragments of the chunk about to be consumed (stage base included): halo rows 4w + rr + y0 (rr = row + pair = 0..4),
+  // column x0 + ktap + l16 (+16: immediate); computed one chunk ahead
+  int f16a[5] = {0, 0, 0, 0, 0};
+  auto frag16 = [&](int win, int stage_base) {
     const int y0 = win >> 1, x0 = win & 1;
 #pragma unroll
     for (int rr = 0; rr < 5; ++rr)
-#pragma unroll
-      for (int dx = 0; dx < 2; ++dx) {
-        const int p = (wave * CR + rr + y0) * RG_IW + x0 + dx + r;
-        f_cur[rr][dx] = stage_base + (2 * p + (h ^ ((p >> 3) & 1))) * 16;
-      }
+      f16a[rr] = stage_base + ((wave * CR + rr + y0) * RG_IW + x0 + ktap + l16) * 32 + khalf * 16;
   };
-  if (SPARSE) frag_addresses(__builtin_amdgcn_readfirstlane(win_of(e.tap_mask[0])), 0);
-
+  frag16(__builtin_amdgcn_readfirstlane(win_of(e.tap_mask[0])), 0);
   int g = 0;
   for (int ord = 0; ord < my_units; ++ord) {
-    // acc[ni][mi][8jj + q] = channel ni*32 + jj*16 + h*8 + q of pixel r in tile row 4w + mi
-    f32x16 acc[2][CR];
+    // acc[mb][nbk][k]: block mb row 4 kg + k = channel (mb>>1)*32 + 8 kg + (mb&1)*4 + k; nbk = row*2 + pixel half
+    f32x4 acc[4][2 * CR];
 #pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
+    for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
-      for (int mi = 0; mi < CR; ++mi)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[ni][mi][q] = 0.f;
+      for (int nbk = 0; nbk < 2 * CR; ++nbk) acc[mb][nbk] = f32x4{0.f, 0.f, 0.f, 0.f};
     int b, oy0, ox0, n0;
     unit_coords(ord, b, oy0, ox0, n0);
     const int oyw = oy0 + wave * CR;
-
-    unsigned long long ts[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    auto stamp = [&](int i) {
-      if (DBG & 16) asm volatile("s_memtime %0" : "=s"(ts[i]) : : "memory");
-    };
     auto chunk = [&](int c) {
-      stamp(0);
-      if ((DBG & 16) && ord == RG_PROBE_UNIT + 1 && (c == 2 || c == nc - 1)) {     // undisturbed chunk period: two entry stamps
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (lane == 0)
-          (reinterpret_cast<unsigned long long*>(const_cast<float*>(a.res2)) +
-           (((long long)blockIdx.x * 8 + wave) * 4 + (c == 2 ? 0 : 1)) * 10)[9] = ts[0];
-      }
-      // my fragment reads of batch g-1 have returned (its stage is refilled behind the barrier)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      stamp(1);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // my fragment reads of batch g-1 have returned
       __builtin_amdgcn_s_barrier();
-      stamp(2);
-      const unsigned char* st = smem + (g % RG_NS) * STAGE;
-      const unsigned char* sW = st + w_off;
-      f16x8_t fa[2][CR], fb[2][2];                     // [parity][row / channel block]: fragments are read one tap ahead
-      auto mma_tap = [&](int par) {
+      const unsigned char* sW = smem + (g % RG_NS) * STAGE + w16;
+      // four sub-steps: (tap pair, rows 0-1), (pair, rows 2-3); the weight fragments of a pair serve both
+      f16x8_t fw[2][4], fp[2][4];                 // [pair parity / sub-step parity][channel block / (row, pixel half)]
+      auto load_w = [&](int pair) {
 #pragma unroll
-        for (int mi = 0; mi < CR; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni) {
-            if (DBG & 1) acc[ni][mi][0] += (float)fa[par][mi][0] * (float)fb[par][ni][0];
-            else if (DBG & 4) {      // clock experiment: the 16x16x32 shape at equal FLOPs and fragment reads (NOT the convolution)
-              f32x4 lo = {acc[ni][mi][0], acc[ni][mi][1], acc[ni][mi][2], acc[ni][mi][3]};
-              f32x4 hi = {acc[ni][mi][4], acc[ni][mi][5], acc[ni][mi][6], acc[ni][mi][7]};
-              lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[par][ni], fa[par][mi], lo, 0, 0, 0);
-              hi = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[par][ni], fa[par][mi], hi, 0, 0, 0);
-#pragma unroll
-              for (int q = 0; q < 4; ++q) { acc[ni][mi][q] = lo[q]; acc[ni][mi][4 + q] = hi[q]; }
-            } else acc[ni][mi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb[par][ni], fa[par][mi], acc[ni][mi], 0, 0, 0);
-          }
+        for (int mb = 0; mb < 4; ++mb) fw[pair & 1][mb] = *reinterpret_cast<const f16x8_t*>(sW + pair * 4096 + mb * 256);
       };
-      if (SPARSE) {
-        auto load_frags = [&](int j, int par) {      // j = dy*2 + dx inside the window = slab slot
+      auto load_p = [&](int ss) {
+        const int pair = ss >> 1, hr = ss & 1;
 #pragma unroll
-          for (int ni = 0; ni < 2; ++ni) fb[par][ni] = *reinterpret_cast<const f16x8_t*>(sW + (j * 2 * 64 + ni * 32) * 16);
+        for (int q = 0; q < 4; ++q)              // q = (row within the half)*2 + pixel half
+          fp[ss & 1][q] = *reinterpret_cast<const f16x8_t*>(smem + f16a[2 * hr + (q >> 1) + pair] + (q & 1) * 512);
+      };
+      load_w(0);
+      load_p(0);
+      const int win_n = smem[L::WINTAB + (c + 1 == nc ? 0 : c + 1)];
 #pragma unroll
-          for (int mi = 0; mi < CR; ++mi) fa[par][mi] = *reinterpret_cast<const f16x8_t*>(smem + f_cur[mi + (j >> 1)][j & 1]);
-        };
-        load_frags(0, 0);
-        const int win_n = smem[L::WINTAB + (c + 1 == nc ? 0 : c + 1)];
-        stamp(3);
+      for (int ss = 0; ss < 4; ++ss) {
+        if (ss < 3) load_p(ss + 1);
+        if (ss == 1) load_w(1);
+        __builtin_amdgcn_sched_barrier(0);
+        const int pair = ss >> 1, hr = ss & 1;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (j < 3) load_frags(j + 1, (j & 1) ^ 1);
-          __builtin_amdgcn_sched_barrier(0);
-          mma_tap(j & 1);
-          __builtin_amdgcn_sched_barrier(0);
-          stamp(4 + j);
-        }
-        frag_addresses(__builtin_amdgcn_readfirstlane(win_n), ((g + 1) % RG_NS) * STAGE);
-      } else {
-        auto load_frags = [&](int t, int par) {
-          const int dy = t / 3, dx = t - dy * 3;
+        for (int q = 0; q < 4; ++q)
 #pragma unroll
-          for (int ni = 0; ni < 2; ++ni) fb[par][ni] = *reinterpret_cast<const f16x8_t*>(sW + (t * 2 * 64 + ni * 32) * 16);
-#pragma unroll
-          for (int mi = 0; mi < CR; ++mi) fa[par][mi] = *reinterpret_cast<const f16x8_t*>(st + p_off[SPARSE ? 0 : (mi + dy) * 3 + dx]);
-        };
-        load_frags(0, 0);
-        stamp(3);
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-          if (t < 8) load_frags(t + 1, (t & 1) ^ 1);
-          __builtin_amdgcn_sched_barrier(0);
-          mma_tap(t & 1);
-          __builtin_amdgcn_sched_barrier(0);
-          if (t == 1 || t == 3 || t == 5 || t == 8) stamp(t == 8 ? 7 : 4 + (t >> 1));
-        }
+          for (int mb = 0; mb < 4; ++mb) {
+            if (DBG & 1) acc[mb][hr * 4 + q][0] += (float)fw[pair & 1][mb][0] * (float)fp[ss & 1][q][0];
+            else acc[mb][hr * 4 + q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[pair & 1][mb], fp[ss & 1][q], acc[mb][hr * 4 + q], 0, 0, 0);
+          }
+        __builtin_amdgcn_sched_barrier(0);
       }
-      if (DBG & 16) {
-        stamp(8);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (ord == RG_PROBE_UNIT && c >= 8 && c < 12 && lane == 0) {
-          unsigned long long* cb = reinterpret_cast<unsigned long long*>(const_cast<float*>(a.res2)) +
-                                   (((long long)blockIdx.x * 8 + wave) * 4 + (c - 8)) * 10;
-#pragma unroll
-          for (int i = 0; i < 9; ++i) cb[i] = ts[i];
-        }
-      }
+      frag16(__builtin_amdgcn_readfirstlane(win_n), ((g + 1) % RG_NS) * STAGE);
     };
-
-    // residual values of one tile row: [ni][jj][half] x 4 channels = 32 contiguous bytes per (ni, jj)
+    // residual values of one tile row: [pixel half][e][4-channel half] -- 32 contiguous bytes per (pixel, e)
     const bool has_res = a.res1 != nullptr && !(DBG & 8);
-    auto row_ok = [&](int mi) { return oyw + mi < H && ox0 + r < W; };
+    auto px_ok = [&](int mi, int nh) { return oyw + mi < H && ox0 + nh * 16 + l16 < W; };
     auto load_res_row = [&](int mi, f32x4 (&rv)[2][2][2]) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) (&rv[0][0][0])[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (!has_res || !row_ok(mi)) return;
-      const float* rp = a.res1 + ((long long)(b * H + oyw + mi) * W + ox0 + r) * a.ldr1 + n0 + h * 8;
+      if (!has_res) return;
 #pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
+      for (int nh = 0; nh < 2; ++nh) {
+        if (!px_ok(mi, nh)) continue;
+        const float* rp = a.res1 + ((long long)(b * H + oyw + mi) * W + ox0 + nh * 16 + l16) * a.ldr1 + n0 + kg * 8;
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj)
-          if (n0 + ni * 32 + jj * 16 + h * 8 < a.Cout) {
-            rv[ni][jj][0] = *reinterpret_cast<const f32x4*>(rp + ni * 32 + jj * 16);
-            rv[ni][jj][1] = *reinterpret_cast<const f32x4*>(rp + ni * 32 + jj * 16 + 4);
+        for (int ee = 0; ee < 2; ++ee)
+          if (n0 + ee * 32 + kg * 8 < a.Cout) {
+            rv[nh][ee][0] = *reinterpret_cast<const f32x4*>(rp + ee * 32);
+            rv[nh][ee][1] = *reinterpret_cast<const f32x4*>(rp + ee * 32 + 4);
           }
+      }
     };
-
     for (int c = 0; c < nc - 1; ++c, ++g) chunk(c);
-    // last chunk of the tile (peeled): the first row's residual values are requested in front of its MFMAs
     f32x4 rva[2][2][2], rvb[2][2][2];
     load_res_row(0, rva);
     chunk(nc - 1);
     ++g;
-
     if (DBG & 8) {
       float t = 0.f;
 #pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
+      for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
-        for (int mi = 0; mi < CR; ++mi)
+        for (int nbk = 0; nbk < 2 * CR; ++nbk)
 #pragma unroll
-          for (int q = 0; q < 16; ++q) t += acc[ni][mi][q] + rva[ni & 1][mi & 1][0][q & 3];
+          for (int k = 0; k < 4; ++k) t += acc[mb][nbk][k] + rva[nbk & 1][mb & 1][0][k];
       if (t == 123.456f) a.out[0] = t;
       continue;
     }
-    // ---- epilogue, one tile row at a time; row mi + 1's residual values are requested before row mi is processed
     auto epilogue_row = [&](int mi, const f32x4 (&rv)[2][2][2]) {
-      const int oy = oyw + mi, X = ox0 + r;
-      const bool ok = row_ok(mi);
-      const long long pix = (long long)(b * H + oy) * W + X;
+      const int oy = oyw + mi;
 #pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
+      for (int nh = 0; nh < 2; ++nh) {
+        const int X = ox0 + nh * 16 + l16;
+        const bool ok = px_ok(mi, nh);
+        const long long pix = (long long)(b * H + oy) * W + X;
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-          const int n = n0 + ni * 32 + jj * 16 + h * 8;
+        for (int ee = 0; ee < 2; ++ee) {
+          const int n = n0 + ee * 32 + kg * 8;
           const f32x4 b0 = *reinterpret_cast<const f32x4*>(smem + L::BIAS + n * 4);
           const f32x4 b1 = *reinterpret_cast<const f32x4*>(smem + L::BIAS + n * 4 + 16);
           f32x4 v0, v1;
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            const float t0 = acc[ni][mi][8 * jj + k] + b0[k], t1 = acc[ni][mi][8 * jj + 4 + k] + b1[k];
+            const float t0 = acc[2 * ee][mi * 2 + nh][k] + b0[k], t1 = acc[2 * ee + 1][mi * 2 + nh][k] + b1[k];
             v0[k] = fmaxf(t0, slope * t0);
             v1[k] = fmaxf(t1, slope * t1);
           }
-          v0 += rv[ni][jj][0];
-          v1 += rv[ni][jj][1];
+          v0 += rv[nh][ee][0];
+          v1 += rv[nh][ee][1];
           if (!ok || n >= a.Cout) continue;
-          if (a.res2 && !(DBG & 16)) {
+          if (a.res2) {
             const float* p2 = a.res2 + pix * a.ldr2 + n;
             v0 += *reinterpret_cast<const f32x4*>(p2);
             v1 += *reinterpret_cast<const f32x4*>(p2 + 4);
           }
-          if (a.res_up2) {      // + bilinear x2 of a half-resolution tensor: taps (Q-1, Q) x (P-1, P), clamped
+          if (a.res_up2) {      // + bilinear x2 of the half-resolution tensor, from the staged tile (see conv3x3_ring_kernel)
             const float ly = (oy & 1) ? 0.25f : 0.75f, lx = (X & 1) ? 0.25f : 0.75f;
-            if (SPARSE) {       // from the staged tile: local tap rows Q - oy0/2 (+1), columns P - ox0/2 (+1)
-              const int li = ((oy + 1) >> 1) - (oy0 >> 1), lj = ((X + 1) >> 1) - (ox0 >> 1);
-              const unsigned char* et = smem + L::ETILE;
-              const int cq = (ni * 32 + jj * 16 + h * 8) >> 2;
+            const int li = ((oy + 1) >> 1) - (oy0 >> 1), lj = ((X + 1) >> 1) - (ox0 >> 1);
+            const unsigned char* et = smem + L::ETILE;
+            const int cq = (ee * 32 + kg * 8) >> 2;
 #pragma unroll
-              for (int hf = 0; hf < 2; ++hf) {
-                auto tap = [&](int i, int j) {
-                  const int px = i * RG_ET_COLS + j;
-                  return *reinterpret_cast<const f32x4*>(et + px * 256 + (((cq + hf) ^ (px & 15)) << 4));
-                };
-                (hf ? v1 : v0) += (1.f - ly) * ((1.f - lx) * tap(li, lj) + lx * tap(li, lj + 1)) +
-                                  ly * ((1.f - lx) * tap(li + 1, lj) + lx * tap(li + 1, lj + 1));
-              }
-            } else {
-              const int Hd = H >> 1, Wd = W >> 1;
-              const int Q = (oy + 1) >> 1, P = (X + 1) >> 1;
-              const int ya = Q > 0 ? Q - 1 : 0, yb = Q < Hd ? Q : Hd - 1, xa = P > 0 ? P - 1 : 0, xb = P < Wd ? P : Wd - 1;
-              const float* eb = a.res_up2 + (long long)b * Hd * Wd * a.ldru + n;
-              const float* paa = eb + ((long long)ya * Wd + xa) * a.ldru;
-              const float* pab = eb + ((long long)ya * Wd + xb) * a.ldru;
-              const float* pba = eb + ((long long)yb * Wd + xa) * a.ldru;
-              const float* pbb = eb + ((long long)yb * Wd + xb) * a.ldru;
-#pragma unroll
-              for (int hf = 0; hf < 2; ++hf) {
-                const f32x4 eaa = *reinterpret_cast<const f32x4*>(paa + 4 * hf), eab = *reinterpret_cast<const f32x4*>(pab + 4 * hf);
-                const f32x4 eba = *reinterpret_cast<const f32x4*>(pba + 4 * hf), ebb = *reinterpret_cast<const f32x4*>(pbb + 4 * hf);
-                (hf ? v1 : v0) += (1.f - ly) * ((1.f - lx) * eaa + lx * eab) + ly * ((1.f - lx) * eba + lx * ebb);
-              }
+            for (int hf = 0; hf < 2; ++hf) {
+              auto tap = [&](int i, int j) {
+                const int px = i * RG_ET_COLS + j;
+                return *reinterpret_cast<const f32x4*>(et + px * 256 + (((cq + hf) ^ (px & 15)) << 4));
+              };
+              (hf ? v1 : v0) += (1.f - ly) * ((1.f - lx) * tap(li, lj) + lx * tap(li, lj + 1)) +
+                                ly * ((1.f - lx) * tap(li + 1, lj) + lx * tap(li + 1, lj + 1));
             }
           }
           f16x8_t hv;
@@ -1177,7 +907,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
           }
           if (a.out2_cp16) {
             const int npl = a.out2_lo ? (a.Cout >> 3) : (a.Cout >> 4);
-            _Float16* o2 = static_cast<_Float16*>(a.out2_cp16) + (((long long)b * npl + (n >> 4)) * H * W + (long long)oy * W + X) * 16 + h * 8;
+            _Float16* o2 = static_cast<_Float16*>(a.out2_cp16) + (((long long)b * npl + (n >> 4)) * H * W + (long long)oy * W + X) * 16 + (n & 15);
             *reinterpret_cast<f16x8_t*>(o2) = hv;
             if (a.out2_lo) {
               f16x8_t lv;
@@ -1187,9 +917,8 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
             }
           }
         }
+      }
     };
-    unsigned long long te0 = 0, te1 = 0;
-    if (DBG & 16) asm volatile("s_memtime %0" : "=s"(te0) : : "memory");
     load_res_row(1, rvb);
     epilogue_row(0, rva);
     load_res_row(2, rva);
@@ -1197,15 +926,6 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
     load_res_row(3, rvb);
     epilogue_row(2, rva);
     epilogue_row(3, rvb);
-    if (DBG & 16) {      // epilogue length of the undisturbed tile: slots [chunk 2][9], [chunk 3][9]
-      asm volatile("s_memtime %0" : "=s"(te1) : : "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (ord == RG_PROBE_UNIT + 1 && lane == 0) {
-        unsigned long long* cb = reinterpret_cast<unsigned long long*>(const_cast<float*>(a.res2)) + ((long long)blockIdx.x * 8 + wave) * 40;
-        cb[29] = te0;
-        cb[39] = te1;
-      }
-    }
   }
 }
 
@@ -1219,22 +939,16 @@ bool rg_split() {
 
 template <bool SPARSE, int DBG>
 int rg_launch(const cdfo_conv_args& a, const ring_extra& e, int grid, hipStream_t st) {
-  static CdfoAttrOnce once, once_split;
+  static CdfoAttrOnce once;
   // The wave-specialised form runs the four-tap convolutions only (same-box op table, 8 x 272x480: 0.801 -> 0.711 ms per call,
   // 1.8 ms per forward).  The dense form is NOT faster with it (256 -> 64: 0.354 -> 0.366 ms; the short-K split-fp16
   // convolutions 192 -> 64 and 48 -> 64 on 56 frames +12 % / +17 %: a tile of 3-16 chunks ends in an epilogue that four
   // consumer waves take through 4 rows each, one wave per SIMD), so it keeps the eight-identical-waves kernel.
   // (with a half-resolution residual the producers spread its 48 tile pieces over a tile's first six chunks: nc >= 8)
-  if constexpr (SPARSE) {
+  // (ablation bit 4 = the 16x16x32 clock experiment and bit 16 = the timeline probe exist in conv3x3_ring_kernel only)
+  if constexpr (SPARSE && !(DBG & (4 | 16))) {
     if (rg_split() && !(a.res_up2 && e.nc < 8)) {
-      static const bool mf16 = cdfo_switch("CDFO_RING_MFMA16", 1) != 0;
-      if (mf16 && !(DBG & (4 | 16))) {
-        static CdfoAttrOnce once16;
-        const hipError_t err = cdfo_set_max_lds(once16, reinterpret_cast<const void*>(conv3x3_ring_split_kernel<SPARSE, DBG, true>), RingLds<SPARSE>::TOTAL);
-        if (err != hipSuccess) return (int)err;
-        hipLaunchKernelGGL((conv3x3_ring_split_kernel<SPARSE, DBG, true>), dim3(grid), dim3(RG_THREADS), RingLds<SPARSE>::TOTAL, st, a, e);
-        return 0;
-      }
+      static CdfoAttrOnce once_split;
       const hipError_t err = cdfo_set_max_lds(once_split, reinterpret_cast<const void*>(conv3x3_ring_split_kernel<SPARSE, DBG>), RingLds<SPARSE>::TOTAL);
       if (err != hipSuccess) return (int)err;
       hipLaunchKernelGGL((conv3x3_ring_split_kernel<SPARSE, DBG>), dim3(grid), dim3(RG_THREADS), RingLds<SPARSE>::TOTAL, st, a, e);

@@ -56,10 +56,8 @@ TABLE = (
     Switch("CDFO_ALIGN_STATS", 1, ONOFF, "python", "0: DualAttAlignment's statistics on the five launches of round 5: kf written, Gram and channel sums in passes of their own (model.align_stats)"),
     # --- HIP layer (csrc/) --------------------------------------------------------------------------------------------------
     Switch("CDFO_WS_RING", 1, ONOFF, "hip", "0: Block_.body[0] on the private-halo kernel of rounds 1-2 instead of the ring-fed wave-specialised one"),
-    Switch("CDFO_WS_MFMA16", 1, ONOFF, "hip", "0: the ring-fed weights-stationary kernel on v_mfma_f32_32x32x16_f16 instead of 16x16x32"),
     Switch("CDFO_WS_WAVES", 12, INT, "hip", "8: two instead of three waves per SIMD in the private-halo weights-stationary kernel", (8, 12)),
     Switch("CDFO_RING_SPLIT", 1, ONOFF, "hip", "0: the four-tap ring convolution on the eight-identical-waves kernel"),
-    Switch("CDFO_RING_MFMA16", 1, ONOFF, "hip", "0: the wave-specialised ring kernel's consumers on 32x32x16"),
     Switch("CDFO_RING_TOUCH", 0, ONOFF, "hip", "1: producer-side touches of the tile's residual lines ahead of the epilogue (measured useless, off)"),
     Switch("CDFO_CONV1X1_STREAM", 1, ONOFF, "hip", "0: 1x1 convolutions on the one-tile-per-workgroup kernel instead of the persistent streaming one"),
     Switch("CDFO_TAPS_STREAM", 1, ONOFF, "hip", "0: the CDFO_STORE_TAPS9 1x1 convolution off the persistent streaming kernel"),

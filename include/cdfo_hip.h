@@ -116,8 +116,7 @@ int cdfo_pack_conv3x3_f16(const float* w_oihw, void* packed, int Cout, int Cin, 
  * H even, Cout % 64 == 0, the source smaller than 2 GiB.  Since round 3 the call runs the ring-fed, wave-specialised form
  * (four producer waves feed two groups of four consumer waves, v_mfma_f32_16x16x32_f16); same operands, same result layout.
  * dbg: 0 (developer ablation flags otherwise -- compiled only into developer builds, -DCDFO_DEV_ABLATIONS, `python -m cdfo_amd.build --dev`;
- * the shipped library answers CDFO_EINVAL: 1 / 2 / 8 skip the MFMAs / the DMA / the epilogue, 4 = MFMA-shape clock
- * experiment with WRONG arithmetic; with dbg 32 clk_probe receives s_memtime stamps of the consumer waves, 256 x 12 x 4 x 8
+ * the shipped library answers CDFO_EINVAL: 1 / 2 / 8 skip the MFMAs / the DMA / the epilogue; with dbg 32 clk_probe receives s_memtime stamps of the consumer waves, 256 x 12 x 4 x 8
  * 64-bit words; with dbg 128 -- private-halo form only -- per wave of the grid {shader-clock cycles, start, end in 100 MHz
  * real-time ticks}: 3 x 8 x 256 words; else pass NULL).  */
 int cdfo_conv3x3_c64_ws(const void* src_cp16, int B, int H, int W, const void* w_f16, int CoutP, const float* bias,

@@ -10,9 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 VARIANTS = [
     ({"CDFO_WS_RING": "0"}, "ws"),            # Block_.body[0] on the private-halo kernel of rounds 1-2
-    ({"CDFO_WS_MFMA16": "0"}, "ws"),          # ring-fed form on v_mfma_f32_32x32x16_f16
     ({"CDFO_RING_SPLIT": "0"}, "ring"),       # four-tap ring convolution on the eight-identical-waves kernel
-    ({"CDFO_RING_MFMA16": "0"}, "ring"),      # wave-specialised four-tap form with 32x32x16 consumers
     ({"CDFO_RING_TOUCH": "1"}, "ring"),       # producer-side touches of the tile's residual lines
 ]
 

@@ -128,7 +128,7 @@ def _ring_kernel_dbg_arguments(*defines):
         assert r.returncode == 0, r.stderr[-2000:]
         mangled = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", open(out).read(), re.M)
     dbg = [int(m.group(1)) for n in mangled for m in [re.search(r"conv3x3_ring(?:_split)?_kernelILb[01]ELi(\d+)E", n)] if m]
-    assert len(dbg) == len(mangled) >= 4, mangled
+    assert len(dbg) == len(mangled) >= 3, mangled      # dense, four-tap, wave-specialised four-tap
     return dbg
 
 

@@ -1,9 +1,11 @@
-# Developer script (GPU box): SQ counter passes over the three forms of the Block_.body[0] kernel (tools/bench_ws.py 0), one rocprofv3
-# run per counter group and form:   gpurun -- 'bash tools/pmc_ws.sh'   -> gpurun_out/pmcws/counters_{old,ring32,mfma16}.txt
+# Developer script (GPU box): SQ counter passes over the two forms of the Block_.body[0] kernel (tools/bench_ws.py 0), one rocprofv3
+# run per counter group and form:   bash tools/pmc_ws.sh   -> $O/counters_{old,mfma16}.txt
+# (old = the private-halo kernel, mfma16 = the ring-fed 16x16x32 kernel; the ring-fed 32x32x16 form, "ring32" in
+# profiles/r03_pmc_counters_conv3x3_ws.txt, no longer exists)
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && O=gpurun_out/pmcws && mkdir -p $O
-for form in old ring32 mfma16; do
-  case $form in old) export CDFO_WS_RING=0; unset CDFO_WS_MFMA16;; ring32) unset CDFO_WS_RING; export CDFO_WS_MFMA16=0;; mfma16) unset CDFO_WS_RING; unset CDFO_WS_MFMA16;; esac
+for form in old mfma16; do
+  case $form in old) export CDFO_WS_RING=0;; mfma16) unset CDFO_WS_RING;; esac
   i=0
   for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" \
              "SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_SALU SQ_INSTS_VALU SQ_INSTS_LDS" \

@@ -1,6 +1,8 @@
 """Developer tool (GPU box only): s_memtime stamps inside the LDS-DMA ring kernel (dbg 16, conv3x3_ring.hip) -- where a chunk's
 cycles go, per wave.  Prints, for one workgroup, each wave's stamps of chunks 8..11 relative to the workgroup's earliest stamp of
 chunk 8, and the mean length of every phase over all workgroups (100 MHz real-time ticks -> ns).
+Both modes probe conv3x3_ring_kernel, eight identical waves: `sparse` is its four-tap instantiation (the wave-specialised
+four-tap kernel that runs by default carries no probe), `dense` the nine-tap one.
     python tools/ring_timeline.py [sparse|dense]"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -42,23 +44,14 @@ def main():
         K.conv_ring(src, pc, res1=res, out=out, res2=clk, dbg=16)
     torch.cuda.synchronize()
     raw = clk.cpu().double()
-    nck = Cin // 16
-    span = raw[:, :4, 1, 9] - raw[:, :4, 0, 9]           # consumers: entry of the next tile's last chunk - entry of its chunk 2
-    if (span > 0).any():
-        print(f"# undisturbed chunk period (next tile: entry of chunk 2 -> entry of chunk {nck - 1}, consumer waves): "
-              f"{(span[span > 0] / (nck - 1 - 2)).mean():.1f} ticks")
-    ep = raw[:, :4, 3, 9] - raw[:, :4, 2, 9]
-    if (ep > 0).any():
-        print(f"# epilogue of that tile (consumer waves): {ep[ep > 0].mean():.0f} ticks; last-chunk entry -> epilogue start "
-              f"{(raw[:, :4, 2, 9] - raw[:, :4, 1, 9])[ep > 0].mean():.0f} ticks")
     t = raw[..., :9]                                     # [wg, wave, chunk, stamp]
     ok = (t[..., 0] > 0).all(dim=-1).all(dim=-1)
-    print(f"# {'four-tap' if sparse else 'dense'} form, {int(ok.sum())} workgroups with stamps; s_memtime ticks (constant 100 MHz clock): 1 tick = 10 ns")
+    print(f"# {'four-tap' if sparse else 'dense'} form on the eight-identical-waves kernel, {int(ok.sum())} workgroups with stamps; s_memtime ticks (constant 100 MHz clock): 1 tick = 10 ns")
     t = t[ok]
     d = t[..., 1:] - t[..., :-1]                         # phase lengths
     print("# mean phase length over workgroups x waves x chunks (ticks):")
     for i in range(8):
-        print(f"   {NAMES[i]:8s} -> {NAMES[i + 1]:8s} {d[..., i].mean():7.2f}   (waves 0-3 {d[:, :4, :, i].mean():6.2f}, waves 4-7 {d[:, 4:, :, i].mean():6.2f})")
+        print(f"   {NAMES[i]:8s} -> {NAMES[i + 1]:8s} {d[..., i].mean():7.2f}")
     per_chunk = (t[:, :, 1:, 0] - t[:, :, :-1, 0]).mean()
     print(f"# chunk period (entry to entry): {per_chunk:.2f} ticks")
     g = t[0]

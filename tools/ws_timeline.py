@@ -24,7 +24,7 @@ def main():
         K.conv3x3_ws(src, pc, act=1, s2d=s2d, out=out, dbg=32, clk=clk)
     torch.cuda.synchronize()
     t = clk.cpu().double()[:, :8]                  # consumers
-    nst = 4 if (t[:, :, 3, 0] > 0).any() else 2    # steps per tile: 4 chunks (32x32x16 form) or 2 superchunks (16x16x32 form)
+    nst = 2                                        # steps per tile: two 32-channel superchunks
     ok = (t[:, :, :nst, 0] > 0).all(dim=-1).all(dim=-1)
     t = t[ok]
     print(f"# 64->256 {H}x{W} B{B}: {int(ok.sum())} workgroups; ticks = shader cycles")
