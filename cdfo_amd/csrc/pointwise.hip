@@ -3,6 +3,7 @@
 // One pixel's 64 channels are a contiguous 256-B run, so 16 consecutive lanes (a float4 each) cover a pixel and
 // every wave-instruction moves 4 whole pixels = 1 KiB, fully coalesced.
 #include "numeric.h"
+#include "flow_sample.h"
 
 namespace {
 
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const float* __restrict_
 
 // ------------------------------------------------------------------------------------------------------------
 // flow_warp (arch.py:3068-3099): bilinear sample at (x + mv_x, y + mv_y), zeros outside, align_corners=True
-// with the same normalise / un-normalise arithmetic as F.grid_sample.  mv: [B][2][H][W] planes.
+// with the same normalise / un-normalise arithmetic as F.grid_sample (flow_sample.h).  mv: [B][2][H][W] planes.
 __global__ __launch_bounds__(256) void flow_warp_kernel(const float* __restrict__ in, int ldi,
                                                         const float* __restrict__ mv, long long mv_bstride, int B,
                                                         int H, int W, int C, float* __restrict__ out, int ldo) {
@@ -234,35 +235,8 @@ __global__ __launch_bounds__(256) void flow_warp_kernel(const float* __restrict_
     const int x = p % W;
     const int y = (p / W) % H;
     const long long b = p / ((long long)W * H);
-    const float* m = mv + b * mv_bstride;
-    const float fx = m[(long long)y * W + x], fy = m[(long long)(H + y) * W + x];
-    const float nx = 2.0f * ((float)x + fx) / wm - 1.0f;
-    const float ny = 2.0f * ((float)y + fy) / hm - 1.0f;
-    const float sx = ((nx + 1.f) / 2.f) * (float)(W - 1);
-    const float sy = ((ny + 1.f) / 2.f) * (float)(H - 1);
-    // a sample at or beyond one pixel outside the image has no corner inside it: the result is 0 (grid_sample, zeros
-    // padding).  Decided in floating point BEFORE any conversion to int -- the reference's mv2mvs leaves x / 0 = inf in the
-    // motion field (test_LD_22_FPS.py:106-110) and float -> int of inf / NaN is undefined
-    if (!(sx > -1.f && sx < (float)W && sy > -1.f && sy < (float)H)) {
-      *reinterpret_cast<f32x4*>(out + p * ldo + cg * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
-      continue;
-    }
-    const float x0f = floorf(sx), y0f = floorf(sy);
-    const int x0 = (int)x0f, y0 = (int)y0f;
-    const float tx = sx - x0f, ty = sy - y0f;
-    const float w00 = (1.f - tx) * (1.f - ty), w01 = tx * (1.f - ty), w10 = (1.f - tx) * ty, w11 = tx * ty;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const float* base = in + b * H * W * ldi + cg * 4;
-    const bool xa = x0 >= 0 && x0 < W, xb = x0 + 1 >= 0 && x0 + 1 < W;
-    if (y0 >= 0 && y0 < H) {
-      if (xa) acc += *reinterpret_cast<const f32x4*>(base + ((long long)y0 * W + x0) * ldi) * w00;
-      if (xb) acc += *reinterpret_cast<const f32x4*>(base + ((long long)y0 * W + x0 + 1) * ldi) * w01;
-    }
-    if (y0 + 1 >= 0 && y0 + 1 < H) {
-      if (xa) acc += *reinterpret_cast<const f32x4*>(base + ((long long)(y0 + 1) * W + x0) * ldi) * w10;
-      if (xb) acc += *reinterpret_cast<const f32x4*>(base + ((long long)(y0 + 1) * W + x0 + 1) * ldi) * w11;
-    }
-    *reinterpret_cast<f32x4*>(out + p * ldo + cg * 4) = acc;
+    *reinterpret_cast<f32x4*>(out + p * ldo + cg * 4) =
+        flow_warp_sample(in + b * H * W * ldi + cg * 4, ldi, mv + b * mv_bstride, x, y, H, W, wm, hm);
   }
 }
 

@@ -6,11 +6,15 @@
 //   cdfo_gather_frames  dst[j] = src[idx[j]] over whole frames, index table on the device: the frame-major window stack out of
 //                       the feature bank (clipped / repeated indices at the sequence's ends included) and the [K,7] windows of
 //                       the one-channel planes, one pass each.
+//   cdfo_flow_warp_frames  flow_warp with an indexed source: each output image samples the bank frame its index names, in place,
+//                       with the flow of its (window, neighbour slot): one launch per neighbour group of the shared-compensation
+//                       mode, no gathered copy of the bank.  Per pixel it is flow_warp_kernel's arithmetic (flow_sample.h).
 //
-// Both are streaming kernels: 16-byte stores, 16-byte reads through a buffer descriptor whose range check returns zero for
+// The first two are streaming kernels: 16-byte stores, 16-byte reads through a buffer descriptor whose range check returns zero for
 // everything outside the frame (a bad index), no atomics, no LDS.  cdfo_seq_flows reads 12 bytes per pixel for the 56 it writes;
 // only the fp32 field (what the evaluation loop holds) is read in 16-byte loads, every other element type in guarded element loads.
 #include "common.h"
+#include "flow_sample.h"
 
 namespace {
 
@@ -46,6 +50,37 @@ __global__ __launch_bounds__(256) void gather_frames_kernel(const unsigned char*
     for (int u = 0; u < 4; ++u) d[i + u * stride] = v[u];
   }
   for (; i < n16; i += stride) d[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, i << 4, 0, 0));
+}
+
+// ------------------------------------------------------------------------------------------------- cdfo_flow_warp_frames
+// thread = (pixel, 4-channel group) of ONE output image, 16-byte loads and stores as in flow_warp_kernel.
+// grid (x: workgroups striding over the image's H * W * C / 4 threads; y: output image j = g * K + k): the image's bank index and
+// the base of its motion field depend on blockIdx.y alone, so they are wave-uniform (one scalar load of idx[j] per wave)
+__global__ __launch_bounds__(256) void flow_warp_frames_kernel(const float* __restrict__ bank, int ldi, int n_bank,
+                                                               const int* __restrict__ idx, const float* __restrict__ mv,
+                                                               long long mv_kstride, int slot0, int K, int H, int W, int C,
+                                                               float* __restrict__ out, int ldo) {
+  const int j = blockIdx.y;
+  const int s = idx[j];
+  const int g = j / K, k = j - g * K;
+  const int cgs = C >> 2;
+  const int total = H * W * cgs;
+  float* o = out + (long long)j * H * W * ldo;
+  if (s < 0 || s >= n_bank) {     // cdfo_gather_frames' contract: an index outside the bank names a frame of zeros
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+      const int cg = i % cgs, p = i / cgs;
+      *reinterpret_cast<f32x4*>(o + (long long)p * ldo + cg * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    return;
+  }
+  const float* img = bank + (long long)s * H * W * ldi;
+  const float* m = mv + (long long)k * mv_kstride + (long long)(slot0 + g) * 2 * H * W;
+  const float wm = (float)(W - 1 > 1 ? W - 1 : 1), hm = (float)(H - 1 > 1 ? H - 1 : 1);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int cg = i % cgs, p = i / cgs;
+    const int x = p % W, y = p / W;
+    *reinterpret_cast<f32x4*>(o + (long long)p * ldo + cg * 4) = flow_warp_sample(img + cg * 4, ldi, m, x, y, H, W, wm, hm);
+  }
 }
 
 // -------------------------------------------------------------------------------------------------------- cdfo_seq_flows
@@ -182,6 +217,27 @@ extern "C" int cdfo_gather_frames(const void* src, int n_src, const int* idx, in
   CdfoProfScope prof(st, KID_LAYOUT, 0, 2.0 * (double)n_dst * (double)frame_bytes);
   hipLaunchKernelGGL(gather_frames_kernel, dim3((unsigned)bx, (unsigned)n_dst), dim3(256), 0, st,
                      static_cast<const unsigned char*>(src), static_cast<u32x4*>(dst), idx, n_src, (int)frame_bytes);
+  CDFO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cdfo_flow_warp_frames(const float* bank, int ldi, int n_bank, const int* idx, const float* mv, long long mv_kstride,
+                                     int slot0, int G, int K, int H, int W, int C, float* out, int ldo, void* stream) {
+  if (!bank || !idx || !mv || !out || n_bank <= 0 || G <= 0 || K <= 0 || (long long)G * K > 65535 || slot0 < 0 || mv_kstride < 0 ||
+      H <= 0 || W <= 0 || C <= 0 || C % 4 || ldi % 4 || ldo % 4 || ldi < C || ldo < C)
+    return CDFO_EINVAL;
+  if ((long long)H * W * (C / 4) + 8192LL * 256 > 0x7fffffffLL) return CDFO_EINVAL;          // 32-bit thread index inside an image
+  if (!aligned16(bank) || !aligned16(out) || (reinterpret_cast<uintptr_t>(idx) & 3u) || (reinterpret_cast<uintptr_t>(mv) & 3u))
+    return CDFO_EALIGN;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int n = G * K;
+  // flow_warp's grid: at most 8192 workgroups in all, at most one thread per 16-byte vector of an image
+  int bx = cdiv(8192, n);
+  const int need = cdiv(H * W * (C / 4), 256);
+  if (bx > need) bx = need;
+  CdfoProfScope prof(st, KID_FLOW_WARP, 0, 4.0 * (2 * C + 2) * (double)n * H * W);
+  hipLaunchKernelGGL(flow_warp_frames_kernel, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, st, bank, ldi, n_bank, idx, mv, mv_kstride,
+                     slot0, K, H, W, C, out, ldo);
   CDFO_LAUNCH_CHECK();
   return 0;
 }

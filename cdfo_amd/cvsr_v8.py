@@ -25,6 +25,11 @@ Differences, all deliberate:
   * the debug side effects of the reference forward (``featuremap_visual`` PNG dumps, arch.py:4450-4475) are absent.
   * ``L1_fea`` is returned as a ``[B*7,64,H,W]`` tensor in channels-last memory format (a view of the kernels'
     pixel-major buffer); feeding it back as ``pre_L1_fea`` needs no conversion.  Plain NCHW tensors are accepted too.
+  * ``extract_features`` / ``forward_windows`` serve one sequence K centre frames per call (StreamingSR.run_chunked): same
+    arithmetic per output frame.  ``compensate_features`` / ``forward_windows_shared`` (opt-in,
+    ``run_chunked(share_compensation=True)``) also run the per-frame half of the neighbour pipelines once per FRAME, with one
+    Gumbel draw per frame where the reference draws per (forward, slot): every window still sees six draws (independent when its
+    neighbour frames are distinct), but windows that hold the same frame share its draw.
 """
 from __future__ import annotations
 
@@ -201,6 +206,8 @@ class CVSR_V8(nn.Module):
         self._warned_range = False
         # frames sent through feature extraction since construction (every inference route counts here; StreamingSR reports it)
         self.frames_extracted = 0
+        # frames sent through compensate_features (the per-frame half of the neighbour pipeline, shared-compensation mode)
+        self.frames_compensated = 0
         self._packed: Optional[dict] = None
         self._packed_sig = None
 
@@ -424,15 +431,20 @@ class CVSR_V8(nn.Module):
         K.seq_attn(qwin, xq[..., 64:128], am + 2, out=cat[..., 64:128])
         return self._conv(cat, w["RDAB.fuse"], res1=x)
 
-    def _align(self, w, xc, extra, pred, mvs, mv_bstride, out):
+    def _align(self, w, xc, extra, pred, mvs, mv_bstride, out, frames=None):
         """DualAttAlignment (arch.py:3455-3496) on a group of neighbours: xc / extra / pred / out are [G*B,H,W,64] (xc = the
-        centre frame's features repeated per neighbour), mvs one motion field view per neighbour."""
+        centre frame's features repeated per neighbour), mvs one motion field view per neighbour.  frames (shared compensation):
+        (bank, idx, mvs1, slot0) -- `extra` is None and image g*B + b is bank[idx[g*B + b]], warped in place by one launch with
+        the flow of window b at slot slot0 + g of mvs1 [B,7,2,H,W]."""
         raw = w["raw"]
         a = "MV_deform_align."
         GB, H, W, _ = xc.shape
         B = GB // len(mvs)
         warped = K.empty_act(GB, H, W, NF, xc.device)
-        for g, mv in enumerate(mvs):
+        if frames is not None:
+            bank, idx, mvs1, slot0 = frames
+            K.flow_warp_frames(bank, idx, mvs1, mv_bstride, slot0, len(mvs), B, out=warped)
+        for g, mv in enumerate(mvs if frames is None else ()):
             K.flow_warp(extra[g * B:(g + 1) * B], mv, mv_bstride, out=warped[g * B:(g + 1) * B])
         fused = self.precision != "f32" and self.align_stats
         if fused:
@@ -782,6 +794,115 @@ class CVSR_V8(nn.Module):
                 return out
             return self._recompute_bf16x3(run, self._noise_seed)
 
+    def resolve_noise_key(self, device, key: Optional[int] = None) -> int:
+        """The Philox key that compensate_features draws with: `key`, or a fresh one taken from torch's default generator of
+        `device` as a forward does (``torch.manual_seed`` reproduces it).  A caller that shares one key over several calls (one
+        sequence) passes the returned value back in before each of them."""
+        self._noise_seed = K.next_noise_seed(torch.device(device)) if key is None else int(key)
+        return self._noise_seed
+
+    def compensate_features(self, fea, rms, gumbel_uniform=None, draws=None):
+        """The per-frame half of a neighbour pipeline (arch.py:4443-4454), once per FRAME instead of once per (window, slot):
+        fea [F,H,W,64] pixel-major fp32 (extract_features), rms [F,1,H,W] in [0,1] -> comp [F,H,W,64] =
+        conv_expand_fea_r([fea, RDAB(fea + conv_expand_rms(rms))]), the `fea_i` that `_neighbour_group` hands to the alignment,
+        on the same kernels.  What any window of a sequence uses for frame t is compensate_features(fea[t], rms[max(1, t)]).
+        Noise: gumbel_uniform = F tensors [1,64,H,W] (one draw per FRAME), else the in-kernel Philox generator, one mask launch
+        per frame with image index 0, draw = draws[f] (default f) and the key of resolve_noise_key(): a frame's uniforms depend on
+        (key, draws[f]) only, not on which other frames share the call.  Deviation from the reference, which draws per (forward,
+        slot): see StreamingSR.run_chunked(share_compensation=True)."""
+        self._inference_only("compensate_features", fea)
+        if fea.dim() != 4 or fea.shape[3] != NF or fea.dtype != torch.float32 or not fea.is_contiguous():
+            raise ValueError(f"compensate_features: fea must be a dense fp32 [F,H,W,64] tensor, got {fea.dtype} {tuple(fea.shape)}")
+        F, H, W, _ = fea.shape
+        if tuple(rms.shape) != (F, 1, H, W):
+            raise ValueError(f"compensate_features: rms must be [F,1,H,W] = {(F, 1, H, W)}, got {tuple(rms.shape)}")
+        if H % 8 or W % 8:
+            raise ValueError(f"H and W must be multiples of 8 (window attention, arch.py:2147,2235); got {H}x{W}")
+        noise = gumbel_uniform if gumbel_uniform is not None else self.gumbel_uniform
+        draws = list(range(F)) if draws is None else [int(d) for d in draws]
+        if len(draws) != F or (noise is not None and len(noise) != F):
+            raise ValueError(f"compensate_features: one noise tensor / one draw index per frame expected (F = {F})")
+        with K.on_device(fea):
+            w = self._weights()
+            raw = w["raw"]
+            self.H, self.W = H, W
+            self.frames_compensated += F
+            dev = fea.device
+            fea_com = K.empty_act(F, H, W, NF, dev)
+            du0 = K.empty_act(F, H // 2 + 1, W // 2 + 1, 4 * NF, dev)       # space-to-depth, + one zero row / column
+            du0[:, H // 2].zero_()
+            du0[:, :, W // 2].zero_()
+            K.stem_conv2(rms.contiguous().float(), H * W, F, H, W, raw["conv_expand_rms.weight"], raw["conv_expand_rms.bias"], fea,
+                         fea_com, w["rms_du0"][0], w["rms_du0"][1], K.ACT_RELU, du0, s2dB=True)
+            noises = []
+            for f in range(F):
+                if noise is None:
+                    cap = None
+                    if self.capture_noise is not None:
+                        cap = torch.empty((1, NF, H, W), device=dev, dtype=torch.float32)
+                        self.capture_noise.append(cap)
+                    noises.append(("rng", self._noise_seed, draws[f], cap))
+                else:
+                    u = noise[f].to(device=dev, dtype=torch.float32).contiguous()
+                    if tuple(u.shape) != (1, NF, H, W):
+                        raise ValueError(f"compensate_features: noise of frame {f} must be [1,64,{H},{W}], got {tuple(u.shape)}")
+                    noises.append(u)
+            x_n = self._rdab(w, du0, fea_com, noises)          # one image per "neighbour": the mask kernel runs per frame
+            return self._conv([fea, x_n], w["conv_expand_fea_r"], pad=1, inner=self.fea_r_single_pass)
+
+    def forward_windows_shared(self, Lc, comp_bank, comp_idx, x, mvs1, ufs, recompensate=None):
+        """K windows of one sequence whose neighbours' compensation is banked per frame: Lc [K,H,W,64] the centres' features,
+        comp_bank [cap,H,W,64] the output of compensate_features per bank slot, comp_idx a device int32 [6,K] (slot-major over
+        the neighbour slots 0, 1, 2, 4, 5, 6): the bank slot of each window's neighbour; x [K,7,1,H,W] (centre frames: the skip
+        connection), mvs1 [K,7,2,H,W], ufs [K,7,1,H,W].  Returns out [K,1,4H,4W].  Steps 2b-5 of ``forward``: the partition-map
+        stem per slot, the alignment of two groups of three slots on the two side streams (each reads the bank in place through
+        cdfo_flow_warp_frames), temporal fusion, trunk, up-sampler.  The fp16 range guard is that of ``forward_windows``, settled
+        before the call returns; a rejected call is repeated in bf16x3 -- from `recompensate()` -> (comp_bank, comp_idx) if given
+        (called in the bf16x3 mode: the caller recomputes the compensation its windows use), else from the same bank."""
+        self._inference_only("forward_windows_shared", x)
+        Kw, N, C, H, W = x.shape
+        if N != NFRAMES or C != 1 or tuple(Lc.shape) != (Kw, H, W, NF) or comp_bank.dim() != 4 or tuple(comp_bank.shape[1:]) != (H, W, NF):
+            raise ValueError(f"expected x [K,7,1,H,W], Lc [K,H,W,64] and comp_bank [cap,H,W,64], got {tuple(x.shape)}, {tuple(Lc.shape)} "
+                             f"and {tuple(comp_bank.shape)}")
+        if H % 8 or W % 8:
+            raise ValueError(f"H and W must be multiples of 8 (window attention, arch.py:2147,2235); got {H}x{W}")
+        for name, t in (("Lc", Lc), ("comp_bank", comp_bank)):
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{name} must be a dense fp32 tensor")
+        if comp_idx.dtype != torch.int32 or comp_idx.device != x.device or comp_idx.numel() != (N - 1) * Kw or not comp_idx.is_contiguous():
+            raise ValueError("comp_idx must be a dense int32 [6,K] tensor on the operands' device")
+        if tuple(mvs1.shape) != (Kw, N, 2, H, W) or ufs.numel() != Kw * N * H * W:
+            raise ValueError(f"expected mvs1 [K,7,2,H,W] and ufs [K,7,1,H,W], got {tuple(mvs1.shape)} and {tuple(ufs.shape)}")
+        with K.on_device(x):
+            x = x.contiguous().float()
+            mvs1 = mvs1.contiguous().float()
+            ufs = ufs.contiguous().float().view(Kw, 1, N, H, W)
+            self.H, self.W = H, W
+            state = [comp_bank, comp_idx.view(-1)]
+
+            def run():
+                fused = self._fuse_windows_shared(self._weights(), Lc, state[0], state[1], x, mvs1, ufs)
+                return self._back(fused, x)
+
+            if not (self.precision == "fp16x2" and self.range_guard):
+                return run()
+            self._probe = torch.zeros(4, dtype=torch.int32, device=x.device)
+            try:
+                out = run()
+                probe = self._probe
+            finally:
+                self._probe = None
+            if not self._settle_range(probe):
+                return out
+
+            def rerun():
+                if recompensate is not None:
+                    bank2, idx2 = recompensate()
+                    state[0], state[1] = bank2, idx2.view(-1)
+                return run()
+
+            return self._recompute_bf16x3(rerun, self._noise_seed)
+
     def capture(self, x, mvs0, mvs1, pms, rms, ufs, pre_L1_fea=None, gumbel_uniform=None, check_range: bool = True):
         """Capture one inference forward at these operands' shapes into a HIP graph (opt-in; fixed shapes).  Returns a
         ``cdfo_amd.graph.CapturedForward``: ``cap(x, mvs0, ...)`` copies the operands into the graph's input buffers, refreshes
@@ -930,6 +1051,38 @@ class CVSR_V8(nn.Module):
             K.range_probe(fused, self._probe[0:2])
         return fused
 
+    def _fuse_windows_shared(self, w, Lc, comp_bank, comp_idx, x, mvs1, ufs):
+        """Steps 2b-3 of the forward with banked compensations: the two neighbour groups (slots 0-2 and 4-6) on the two side
+        streams as in `_fuse_windows`, each aligning comp_bank[comp_idx[...]] to the centres; then the temporal fusion.  ufs:
+        [K,1,7,H,W] dense.  Returns fused [K,H,W,64]."""
+        B, N, _, H, W = x.shape
+        raw = w["raw"]
+        ctr, P = self.center, H * W
+        main = torch.cuda.current_stream(x.device)
+        cache = self.__dict__.setdefault("_side_streams", {})
+        side = cache.get((x.device, 2))
+        if side is None:
+            side = cache[(x.device, 2)] = [torch.cuda.Stream(x.device) for _ in range(2)]
+        keep = []
+        groups = [list(range(0, ctr)), list(range(ctr + 1, N))]
+        xcG = Lc.repeat(ctr, 1, 1, 1)        # on the caller's stream, before the side streams fork from it (see _fuse_windows)
+        for st in side:
+            st.wait_stream(main)
+        aligned_by_frame = {}
+        for gi, idxs in enumerate(groups):
+            with torch.cuda.stream(side[gi]):
+                al = self._neighbour_group(w, raw, None, idxs, xcG, ufs, None, mvs1, None, 0, B, H, W, P, N, keep,
+                                           shared=(comp_bank, comp_idx[gi * ctr * B:(gi + 1) * ctr * B]))
+            al.record_stream(main)
+            for n, i in enumerate(idxs):
+                aligned_by_frame[i] = al[n * B:(n + 1) * B]
+        for st in side:
+            main.wait_stream(st)
+        fused = self._conv([Lc if i == ctr else aligned_by_frame[i] for i in range(N)], w["tsa_fusion"], act=K.ACT_LRELU)
+        if self._probe is not None:
+            K.range_probe(fused, self._probe[0:2])
+        return fused
+
     def _back(self, fused, x, L1=None):
         """Steps 4-5: reconstruction trunk, upsampling + skip (arch.py:4464-4481).  x: the fp32 input clip of `_front`."""
         B, N, C, H, W = x.shape
@@ -952,12 +1105,28 @@ class CVSR_V8(nn.Module):
             out = K.upconv_last(t, w["upconv2"], raw["conv_last.weight"], raw["conv_last.bias"], x[:, ctr], N * P)
         return out
 
-    def _neighbour_group(self, w, raw, Lf, idxs, xcG, ufs, rms, mvs1, noise, draw0, B, H, W, P, N, keep):
+    def _neighbour_group(self, w, raw, Lf, idxs, xcG, ufs, rms, mvs1, noise, draw0, B, H, W, P, N, keep, shared=None):
         """Neighbour frames `idxs` (consecutive) together: prior stems, RDAB compensation, conv_expand_fea_r, MV alignment
-        (arch.py:4443-4460) on [len(idxs)*B, H, W, 64] tensors, neighbour major."""
-        x_dev = Lf.device
+        (arch.py:4443-4460) on [len(idxs)*B, H, W, 64] tensors, neighbour major.  shared = (comp_bank, idx): the compensation
+        of every frame exists already (compensate_features); only the partition-map stem and the alignment run, the latter
+        reading comp_bank[idx[n*B + b]] in place (Lf, rms, noise, draw0 are unused)."""
         G = len(idxs)
         GB = G * B
+        if shared is not None:
+            x_dev = xcG.device
+            ufs_prior = K.empty_act(GB, H, W, NF, x_dev)
+            for n, i in enumerate(idxs):
+                K.stem_conv(ufs[:, 0, i], N * P, B, H, W, raw["conv_expand_ufs.weight"], raw["conv_expand_ufs.bias"],
+                            out=ufs_prior[n * B:(n + 1) * B])
+            al = K.empty_act(GB, H, W, NF, x_dev)
+            xc = xcG if xcG.shape[0] == GB else xcG[:GB]
+            self._align(w, xc, None, ufs_prior, [mvs1[:, i] for i in idxs], N * 2 * P, al, frames=(*shared, mvs1, idxs[0]))
+            if self.debug_taps is not None:
+                for n, i in enumerate(idxs):
+                    self.debug_taps[f"align_{i}"] = al[n * B:(n + 1) * B]
+            keep.extend([ufs_prior, xc])
+            return al
+        x_dev = Lf.device
         feaG = Lf[idxs[0]:idxs[0] + G].view(GB, H, W, NF)
         ufs_prior, fea_com = (K.empty_act(GB, H, W, NF, x_dev) for _ in range(2))
         du0 = K.empty_act(GB, H // 2 + 1, W // 2 + 1, 4 * NF, x_dev)       # space-to-depth, + one zero row / column

@@ -787,6 +787,25 @@ def flow_warp(x: torch.Tensor, mv: torch.Tensor, mv_bstride: int, out: Optional[
     return out
 
 
+def flow_warp_frames(bank: torch.Tensor, idx: torch.Tensor, mv: torch.Tensor, mv_kstride: int, slot0: int, G: int, K: int,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """flow_warp with an indexed source: out[g*K + k] = flow_warp(bank[idx[g*K + k]], mv + k*mv_kstride + (slot0 + g)*2*H*W) for
+    g < G, k < K.  bank [n,H,W,C] is read in place; idx: int32 [G*K] on the device, an index outside the bank gives zeros."""
+    n_bank, H, W, Cc, ld = _chk_act(bank, "bank")
+    if idx.dtype != torch.int32 or idx.device != bank.device or idx.dim() != 1 or not idx.is_contiguous() or idx.numel() != G * K:
+        raise ValueError("flow_warp_frames: idx must be a dense int32 vector of G*K entries on the bank's device")
+    if mv.dtype != torch.float32 or mv.device != bank.device:
+        raise ValueError("flow_warp_frames: mv must be an fp32 tensor on the bank's device")
+    if out is None:
+        out = empty_act(G * K, H, W, Cc, bank.device)
+    _, _, _, _, ldo = _chk_act(out, "out")
+    if tuple(out.shape) != (G * K, H, W, Cc):
+        raise ValueError("flow_warp_frames: out must hold G*K frames of the bank's shape")
+    check(_lib.lib().cdfo_flow_warp_frames(_vp(bank), ld, n_bank, _vp(idx), _vp(mv), C.c_longlong(mv_kstride), slot0, G, K, H, W, Cc,
+                                           _vp(out), ldo, _stream()), "cdfo_flow_warp_frames")
+    return out
+
+
 def resample2(x: torch.Tensor, up: bool, out: Optional[torch.Tensor] = None, accumulate: bool = False,
               out_f16: bool = False, cp16: bool = False) -> torch.Tensor:
     """cp16 (up only): the result is the fp16 chunk-planar tensor [B, C/16, 2H, 2W, 16] that conv3x3_ws reads."""

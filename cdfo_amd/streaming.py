@@ -12,6 +12,9 @@ becomes 0).
 
 ``run_chunked`` processes the same sequence several centre frames per forward against a per-frame feature bank (each frame
 extracted once; `plan_chunks` is its schedule), with the windows, planes and flows built by the library's own kernels.
+With ``share_compensation=True`` (opt-in) the per-frame half of the six neighbour pipelines (residual-map stem, RDAB compensation,
+conv_expand_fea_r) is also computed once per frame, into a second ring beside the feature bank, with ONE Gumbel draw per frame;
+the reference draws per (step, slot), so the windows of different output frames then see correlated noise -- see `run_chunked`.
 """
 from __future__ import annotations
 
@@ -70,6 +73,9 @@ class ChunkPlan(NamedTuple):
     extract: List[int]            # frames that go through feature extraction before this chunk's forward, consecutive
     extract_priors: List[int]     # per extracted frame: the entry its pms plane is read from
     oldest: int                   # the bank may drop every frame below this one before the chunk's forward
+    # shared-compensation mode: a frame is compensated by the chunk that extracts it, into the same slot of a second ring
+    compensate: List[int]                 # frames that go through compensate_features before this chunk's forward (= extract)
+    compensate_priors: List[int]          # per compensated frame: the entry its rms plane is read from (max(1, .); 0 if T == 1)
 
 
 def plan_chunks(T: int, chunk: int) -> Iterator[ChunkPlan]:
@@ -89,7 +95,7 @@ def plan_chunks(T: int, chunk: int) -> Iterator[ChunkPlan]:
         extract = list(range(extracted, reach))
         extracted = max(extracted, reach)
         yield ChunkPlan(centres, windows, [[prior(t) for t in w] for w in windows], [prior(i) for i in centres], extract,
-                        [prior(t) for t in extract], windows[0][0])
+                        [prior(t) for t in extract], windows[0][0], list(extract), [prior(t) for t in extract])
 
 
 def bank_capacity(T: int, chunk: int) -> int:
@@ -113,6 +119,26 @@ def bank_runs(first: int, count: int, capacity: int) -> List[tuple]:
     return runs
 
 
+NEIGHBOUR_SLOTS = (0, 1, 2, 4, 5, 6)
+
+
+def comp_slot_table(plan: ChunkPlan, capacity: int) -> List[int]:
+    """The [6,K] table of `CVSR_V8.forward_windows_shared` for one chunk, flat and slot-major over the neighbour slots 0, 1, 2, 4,
+    5, 6: entry [n][k] = the ring slot of the frame that window k has at neighbour slot n."""
+    return [bank_slot(w[n], capacity) for n in NEIGHBOUR_SLOTS for w in plan.windows]
+
+
+def check_noise_format(share_compensation: bool, gumbel_uniform, frame_noise, T: int) -> None:
+    """Injected noise comes per step (`gumbel_uniform`: T entries of six [1,64,H,W] draws, one per neighbour slot of that step's
+    window) or per frame (`frame_noise`: T tensors [1,64,H,W]).  The shared mode draws once per FRAME and the unshared modes once
+    per (step, slot): neither format converts into the other.  (The unshared modes never read `frame_noise`.)"""
+    if share_compensation and frame_noise is None and gumbel_uniform is not None:
+        raise ValueError("run_chunked(share_compensation=True) draws one noise tensor per frame: pass frame_noise= (T tensors "
+                         "[1,64,H,W]); the per-step gumbel_uniform= format does not convert")
+    if share_compensation and frame_noise is not None and len(frame_noise) != T:
+        raise ValueError(f"frame_noise must hold one tensor per frame (T = {T}), got {len(frame_noise)}")
+
+
 class StreamingSR:
     """One sequence, device resident.
 
@@ -120,10 +146,17 @@ class StreamingSR:
     (``*_res.npy[:,:,0]``), mvl0 / mvl1 : [T,H,W,3] decoder motion fields (``*_mvl0.npy``); index t = file index t.
     H, W are padded with zero rows / columns to multiples of 8 (``test_LD_37.py:24-26`` pads 270 -> 272) and the
     output is cropped back to 4H x 4W.
+
+    gumbel_uniform: injected noise per step (T entries of six draws); frame_noise: injected noise per frame (T tensors
+    [1,64,Hp,Wp]), read by ``run_chunked(share_compensation=True)`` only.
+
+    Deliberate deviations from the reference loop: the sequence is device resident and windows are gathered by index;
+    `run_chunked` extracts each frame once (same arithmetic per output frame); ``run_chunked(share_compensation=True)`` -- opt-in
+    -- also compensates each neighbour frame once, with one Gumbel draw per frame where the reference draws per (step, slot).
     """
 
     def __init__(self, model, lr, pms, rms, ufs, mvl0, mvl1, device: Optional[torch.device] = None,
-                 gumbel_uniform: Optional[Sequence] = None, use_graph: bool = False):
+                 gumbel_uniform: Optional[Sequence] = None, use_graph: bool = False, frame_noise: Optional[Sequence] = None):
         dev = torch.device(device) if device is not None else next(model.parameters()).device
         if dev.type != "cuda":
             raise NotImplementedError("StreamingSR needs the model on a GPU (HIP path, no CPU fallback)")
@@ -141,9 +174,11 @@ class StreamingSR:
         self.lr, self.pms, self.rms, self.ufs = plane(lr), plane(pms), plane(rms), plane(ufs)
         self.mvl0, self.mvl1 = as_dev(mvl0), as_dev(mvl1)
         self.noise = gumbel_uniform
+        self.frame_noise = frame_noise
         self.fea = None
         self.seconds = 0.0
         self._extracted0 = int(getattr(model, "frames_extracted", 0))
+        self._compensated0 = int(getattr(model, "frames_compensated", 0))
         # use_graph: the cached-path forward (frames >= 1: identical shapes every step, ~700 kernel launches of a few
         # microseconds each at one clip) is captured once into a HIP graph and replayed from static buffers
         self.use_graph = use_graph
@@ -239,13 +274,29 @@ class StreamingSR:
         return [self.step(i) for i in range(self.T)]
 
     # -- chunked inference: `chunk` consecutive centre frames per forward against a per-frame feature bank ------------------------
-    def run_chunked(self, chunk: int = 8) -> List[torch.Tensor]:
+    def run_chunked(self, chunk: int = 8, share_compensation: bool = False) -> List[torch.Tensor]:
         """All frames in order, `chunk` centre frames per forward (the last chunk may be shorter).  Each frame goes through
         feature extraction ONCE, into a bank of at most chunk + 6 frames of features; the windows of a chunk are gathered from the
         bank in one pass and the neighbour pipelines, the fusion, the trunk and the up-sampler run at batch `chunk`
         (CVSR_V8.forward_windows).  Per output frame the arithmetic is that of `run()`.  The windows, the flows and the planes are
         built by libcdfo_hip.so (cdfo_gather_frames, cdfo_seq_flows).  ``self.seconds`` / ``fps`` cover everything a chunk does
-        on the device: extraction, input building, forward."""
+        on the device: extraction, input building, forward.
+
+        share_compensation=True (opt-in; False is the path above, unchanged): everything a neighbour pipeline does before the
+        alignment depends on the neighbour FRAME only (fea + conv_expand_rms(rms), RDAB, conv_expand_fea_r on frame t and
+        rms[max(1, t)]), so it is computed once per frame, by the chunk that extracts the frame, into a second ring of the same
+        capacity and slot rule as the feature bank (CVSR_V8.compensate_features); the alignment of all six slots reads that ring
+        through a [6,K] slot table (CVSR_V8.forward_windows_shared, cdfo_flow_warp_frames).  6 K pipelines per chunk become at
+        most K + 6.  NOISE: one Gumbel draw per frame -- `frame_noise[t]`, or the in-kernel Philox generator with one key per
+        run_chunked call and draw = t, so the result does not depend on the chunk size.  Each window still sees six draws,
+        independent whenever its six neighbour frames are distinct, so away from the ends of the sequence every output frame has
+        the reference's distribution; but the reference draws afresh per step and per slot, while here a frame carries ONE draw
+        into every window that holds it (and into every slot of a clipped window that repeats frame 0 or T - 1): across output
+        frames the draws are correlated.  That is why the mode is opt-in.  A chunk that the fp16 range guard rejects is repeated
+        in bf16x3 with the compensation of its frames recomputed (same noise) into a scratch stack; the ring is not rewritten."""
+        check_noise_format(bool(share_compensation), self.noise, self.frame_noise, getattr(self, "T", 0))
+        if share_compensation:
+            return self._run_chunked_shared(int(chunk))
         if not hasattr(self.model, "forward_windows"):
             raise NotImplementedError("run_chunked needs a model with extract_features / forward_windows (CVSR_V8)")
         plans = list(plan_chunks(self.T, int(chunk)))
@@ -294,6 +345,88 @@ class StreamingSR:
         torch.cuda.synchronize(self.dev)
         self.seconds += time.perf_counter() - t0
         return [out[j:j + 1, :, :4 * self.H, :4 * self.W] for j in range(k)]
+
+    # -- the same with each neighbour frame's compensation computed once (share_compensation=True) --------------------------------
+    def _run_chunked_shared(self, chunk: int) -> List[torch.Tensor]:
+        if not hasattr(self.model, "forward_windows_shared"):
+            raise NotImplementedError("run_chunked(share_compensation=True) needs a model with compensate_features / "
+                                      "forward_windows_shared (CVSR_V8)")
+        plans = list(plan_chunks(self.T, chunk))
+        self.fea, self.seconds = None, 0.0
+        self._extracted0, self._compensated0 = self.model.frames_extracted, self.model.frames_compensated
+        cap = bank_capacity(self.T, chunk)
+        bank = torch.empty((cap, self.Hp, self.Wp, 64), dtype=torch.float32, device=self.dev)
+        comp_bank = torch.empty_like(bank)
+        # one Philox key per sequence; frame t draws with (key, t) whichever chunk compensates it
+        key = None if self.frame_noise is not None else self.model.resolve_noise_key(self.dev)
+        # every index table of the sequence in one upload: per chunk the [6,K] ring slots of its neighbours, the ring slots of its
+        # centres, the frames and the prior entries of its windows (centre-major) and the prior entries of the frames it extracts
+        flat = []
+        for p in plans:
+            flat += comp_slot_table(p, cap) + [bank_slot(i, cap) for i in p.centres]
+            flat += [t for w in p.windows for t in w] + [t for w in p.priors for t in w] + p.compensate_priors
+        tables = torch.tensor(flat, dtype=torch.int32).to(self.dev)
+        outs, at = [], 0
+        for p in plans:
+            k = len(p.centres)
+            n = 21 * k + len(p.compensate)
+            idx = tables[at:at + n]
+            at += n
+            outs.extend(self._chunk_step_shared(p, bank, comp_bank, key, idx[:6 * k], idx[6 * k:7 * k], idx[7 * k:14 * k],
+                                                idx[14 * k:21 * k], idx[21 * k:]))
+        return outs
+
+    def _compensate(self, fea, frames: List[int], rms_planes, key):
+        """compensate_features of `frames` (their features `fea`, their rms planes [F,Hp,Wp]) with each frame's own noise: its
+        injected tensor, or draw = frame index under the sequence's key."""
+        noise = None if self.frame_noise is None else [self.frame_noise[t] for t in frames]
+        if noise is None:
+            self.model.resolve_noise_key(self.dev, key)
+        return self.model.compensate_features(fea, rms_planes.unsqueeze(1), gumbel_uniform=noise, draws=frames)
+
+    def _chunk_step_shared(self, plan: ChunkPlan, bank, comp_bank, key, comp_idx, centre_idx, frame_idx, prior_idx,
+                           new_prior_idx) -> List[torch.Tensor]:
+        """One chunk of the shared mode: the frames it is the first to reach are extracted AND compensated into the two rings (same
+        slot in both), then one forward at batch len(plan.centres) whose alignment reads the compensation ring in place."""
+        from . import kernels as K
+        k, cap = len(plan.centres), int(bank.shape[0])
+        torch.cuda.synchronize(self.dev)
+        t0 = time.perf_counter()
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            if plan.extract:
+                a, b = plan.extract[0], plan.extract[-1] + 1
+                fea = self.model.extract_features(self.lr[a:b].unsqueeze(1), K.gather_frames(self.pms, new_prior_idx).unsqueeze(1))
+                comp = self._compensate(fea, plan.compensate, K.gather_frames(self.rms, new_prior_idx), key)
+                for slot, off, n in bank_runs(a, b - a, cap):
+                    bank[slot:slot + n].copy_(fea[off:off + n])
+                    comp_bank[slot:slot + n].copy_(comp[off:off + n])
+            shape = (k, NFRAMES, 1, self.Hp, self.Wp)
+            Lc = K.gather_frames(bank, centre_idx)
+            x = K.gather_frames(self.lr, frame_idx).view(shape)
+            u = K.gather_frames(self.ufs, prior_idx).view(shape)
+            m1 = K.seq_flows(self.mvl1, plan.centres[0], k, self.Hp, self.Wp)
+
+            def recompensate():
+                # a rejected chunk (rare; called in the bf16x3 mode): the frames its windows hold, from the feature ring, into a
+                # scratch stack -- the compensation ring keeps what later chunks will read in the sequence's own arithmetic
+                need = sorted({t for w in plan.windows for t in w})
+                at = lambda v: torch.tensor(v, dtype=torch.int32).to(self.dev)
+                prior = (lambda t: max(1, t)) if self.T > 1 else (lambda t: 0)
+                fea2 = K.gather_frames(bank, at([bank_slot(t, cap) for t in need]))
+                comp2 = self._compensate(fea2, need, K.gather_frames(self.rms, at([prior(t) for t in need])), key)
+                return comp2, at([need.index(w[n]) for n in NEIGHBOUR_SLOTS for w in plan.windows])
+
+            out = self.model.forward_windows_shared(Lc, comp_bank, comp_idx, x, m1, u, recompensate=recompensate)
+        torch.cuda.synchronize(self.dev)
+        self.seconds += time.perf_counter() - t0
+        return [out[j:j + 1, :, :4 * self.H, :4 * self.W] for j in range(k)]
+
+    @property
+    def frames_compensated(self) -> int:
+        """Frames the model has sent through `compensate_features` since this object was made or its last shared `run_chunked()`
+        began: T for ``run_chunked(share_compensation=True)`` (a chunk that the range guard repeats adds the frames of its windows
+        once more), 0 for every other mode."""
+        return self.model.frames_compensated - self._compensated0
 
     @property
     def frames_extracted(self) -> int:

@@ -534,7 +534,13 @@ int cdfo_softmax64_bwd(const float* r, int ldr, const float* dm, int ldm, long l
  *                     rounded fp32 operation in the host function's order: bit-identical to cdfo_amd.streaming.mv2mvs +
  *                     modify_mv_for_end_frames.
  * cdfo_gather_frames: dst[j] = src[idx[j]], j < n_dst, over frames of frame_bytes bytes (a multiple of 16; src, dst 16-byte
- *                     aligned); idx: n_dst ints in DEVICE memory; an index outside [0, n_src) gives a frame of zeros. */
+ *                     aligned); idx: n_dst ints in DEVICE memory; an index outside [0, n_src) gives a frame of zeros.
+ * cdfo_flow_warp_frames: cdfo_flow_warp with an indexed source, G neighbour slots of K windows in one launch: for g < G, k < K
+ *                     out[g*K + k] = flow_warp(bank[idx[g*K + k]], mv + k*mv_kstride + (slot0 + g)*2*H*W), i.e. mv is the
+ *                     [K][7][2][H][W] output of cdfo_seq_flows with mv_kstride = 14*H*W and slot0 the group's first slot.
+ *                     bank: n_bank frames [H][W] of C channels at pixel pitch ldi, read in place; out: G*K dense frames at pitch
+ *                     ldo; idx: G*K ints in DEVICE memory, an index outside [0, n_bank) gives a frame of zeros (the contract of
+ *                     cdfo_gather_frames).  Per pixel the arithmetic of cdfo_flow_warp, bit for bit.  G*K <= 65535. */
 #define CDFO_MV_F32 0
 #define CDFO_MV_F64 1
 #define CDFO_MV_F16 2
@@ -546,6 +552,8 @@ int cdfo_softmax64_bwd(const float* r, int ldr, const float* dm, int ldm, long l
 #define CDFO_MV_I64 8
 int cdfo_seq_flows(const void* mv, int dtype, int T, int H, int W, int i0, int K, int Hp, int Wp, float* out, void* stream);
 int cdfo_gather_frames(const void* src, int n_src, const int* idx, int n_dst, long long frame_bytes, void* dst, void* stream);
+int cdfo_flow_warp_frames(const float* bank, int ldi, int n_bank, const int* idx, const float* mv, long long mv_kstride, int slot0,
+                          int G, int K, int H, int W, int C, float* out, int ldo, void* stream);
 
 /* ---- optional per-launch HIP-event timing on the launch stream (bench.py's live roofline figures) ----------- */
 int cdfo_prof_begin(int max_records);

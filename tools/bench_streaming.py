@@ -58,7 +58,8 @@ def chunked():
     """--chunk K [K ...] [--size T H W] [--repeats R]: run(), HIP-graph replay, run_pipelined() and run_chunked(K) on one synthetic
     sequence in one process; after a warm-up pass each mode runs R times and every repeat's frames/s is printed (the spread,
     not one number).  --only-chunk skips the three one-frame modes (for a kernel trace of the chunked path alone); --phases adds an event breakdown of
-    one pass per chunk size."""
+    one pass per chunk size; --share adds run_chunked(K, share_compensation=True) rows (and their --phases breakdown, with the
+    per-frame compensation and the indexed warp as rows of their own)."""
     T, H, W = 64, 270, 480
     if "--size" in sys.argv:
         k = sys.argv.index("--size")
@@ -80,7 +81,8 @@ def chunked():
             loop(s)
             fps.append(s.fps)
         print(f"{name}, {T} frames {H}x{W}: frames/s per repeat {' '.join('%.2f' % f for f in fps)}; median {np.median(fps):.2f}, "
-              f"min {min(fps):.2f}, max {max(fps):.2f}" + (f"; frames extracted per pass {s.frames_extracted}" if "chunk" in name else ""), flush=True)
+              f"min {min(fps):.2f}, max {max(fps):.2f}" + (f"; frames extracted per pass {s.frames_extracted}" if "chunk" in name else "")
+              + (f", compensated {s.frames_compensated}" if "share" in name else ""), flush=True)
 
     seq = lambda **kw: StreamingSR(model, lr, pms, rms, ufs, mv[0], mv[1], **kw)
     if "--only-chunk" not in sys.argv:
@@ -89,14 +91,21 @@ def chunked():
         report("run_pipelined() (whole-loop wall time)", seq, lambda s: s.run_pipelined())
     for c in chunks:
         report(f"run_chunked(chunk={c}) (extraction + input building + forward)", seq, lambda s: s.run_chunked(c))
+        if "--share" in sys.argv:
+            report(f"run_chunked(chunk={c}, share_compensation=True) (extraction + compensation + input building + forward)", seq,
+                   lambda s: s.run_chunked(c, share_compensation=True))
     if "--phases" in sys.argv:
         for c in chunks:
             _phases(model, seq(), c)
+            if "--share" in sys.argv:
+                _phases(model, seq(), c, share=True)
 
 
-def _phases(model, s, chunk):
+def _phases(model, s, chunk, share=False):
     """Where a chunk's time goes: events around feature extraction, the neighbour pipelines + fusion, the trunk, and the whole
-    chunk step (the rest = input building, the copy into the bank, the up-sampler), summed over one pass of the sequence."""
+    chunk step (the rest = input building, the copy into the bank, the up-sampler), summed over one pass of the sequence.
+    share: the shared-compensation mode -- compensation is a row of its own, "alignment + fusion" is what is left of the
+    neighbour phase, and the indexed warp (one launch per neighbour group, timed on its side stream) is reported per chunk."""
     marks = {}
 
     def wrap(name, fn):
@@ -109,6 +118,27 @@ def _phases(model, s, chunk):
             return r
         return f
 
+    if share:
+        from cdfo_amd import kernels as K
+        s.run_chunked(chunk, share_compensation=True)
+        keep_warp = K.flow_warp_frames
+        model.extract_features, model.compensate_features = wrap("feature extraction", model.extract_features), wrap("compensation", model.compensate_features)
+        model._fuse_windows_shared, model._trunk = wrap("alignment + fusion", model._fuse_windows_shared), wrap("trunk", model._trunk)
+        s._chunk_step_shared, K.flow_warp_frames = wrap("whole chunk step", s._chunk_step_shared), wrap("flow_warp_frames", keep_warp)
+        try:
+            s.run_chunked(chunk, share_compensation=True)
+        finally:
+            del model.extract_features, model.compensate_features, model._fuse_windows_shared, model._trunk, s._chunk_step_shared
+            K.flow_warp_frames = keep_warp
+        torch.cuda.synchronize()
+        warp = marks.pop("flow_warp_frames")
+        ms = {k: sum(a.elapsed_time(b) for a, b in v) for k, v in marks.items()}
+        rest = ms["whole chunk step"] - sum(v for k, v in ms.items() if k != "whole chunk step")
+        nchunks = len(marks["whole chunk step"])
+        print(f"phases of run_chunked(chunk={chunk}, share_compensation=True), ms per frame over {s.T} frames: "
+              + ", ".join(f"{k} {v / s.T:.2f}" for k, v in ms.items()) + f", rest {rest / s.T:.2f}; flow_warp_frames "
+              f"{sum(a.elapsed_time(b) for a, b in warp) / nchunks:.3f} ms per chunk ({len(warp) // nchunks} launches)", flush=True)
+        return
     s.run_chunked(chunk)
     keep = model.extract_features, model._fuse_windows, model._trunk, s._chunk_step
     model.extract_features, model._fuse_windows = wrap("feature extraction", keep[0]), wrap("neighbour pipelines + fusion", keep[1])
