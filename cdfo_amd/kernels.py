@@ -597,6 +597,59 @@ def gather_frames(src: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tens
     return out
 
 
+QUANT_MODES = {"trunc": 0, "nearest": 1}        # CDFO_QUANT_* of include/cdfo_hip.h
+
+
+def u8_frames(t: torch.Tensor, name: str):
+    """An 8-bit frame stack [N,H,W] (or [H,W]) with contiguous rows -> (tensor [N,H,W], N, H, W, pitch, frame stride), in bytes;
+    pitch and stride may exceed W and H * pitch (a view of larger frames is read in place)."""
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 3 or t.stride(2) != 1 or t.stride(1) < t.shape[2] or t.stride(0) < 0:
+        raise ValueError(f"{name}: a device uint8 tensor [N,H,W] with contiguous rows expected, got {t.dtype} {tuple(t.shape)} "
+                         f"strides {t.stride()}")
+    return t, int(t.shape[0]), int(t.shape[1]), int(t.shape[2]), int(t.stride(1)), int(t.stride(0))
+
+
+def finish_frames(out: torch.Tensor, H: int, W: int, gt: Optional[torch.Tensor] = None, crop: int = 4, mode: str = "trunc",
+                  dst: Optional[torch.Tensor] = None):
+    """out: the fp32 output of a chunk, [K,1,>=4H,>=4W] or [K,>=4H,>=4W] with contiguous rows (the padded tensor, read in place)
+    -> (u8 [K,4H,4W], sse): clamp to [0,1] (NaN -> 0), fp32 * 255, truncation (``mode="trunc"``, the reference's writer) or
+    round-to-nearest-even (``"nearest"``).  With ``gt`` (uint8 [K,Hgt,Wgt], device) sse is the int64 [K] sum of (u8 - gt)^2 over the
+    common min(4H, Hgt) x min(4W, Wgt) less ``crop`` border pixels, exact; else None.  ``dst``: an optional dense uint8 [K,4H,4W]
+    destination."""
+    if mode not in QUANT_MODES:
+        raise ValueError(f"finish_frames: mode must be one of {sorted(QUANT_MODES)}, got {mode!r}")
+    if out.dim() == 4 and out.shape[1] == 1:
+        out = out[:, 0]
+    Ho, Wo = 4 * int(H), 4 * int(W)
+    if not out.is_cuda or out.dtype != torch.float32 or out.dim() != 3 or out.stride(2) != 1 or out.shape[1] < Ho or out.shape[2] < Wo \
+            or Ho <= 0 or Wo <= 0 or out.stride(1) < out.shape[2] or out.stride(0) < 0:
+        raise ValueError(f"finish_frames: a device fp32 tensor [K,1,>={Ho},>={Wo}] with contiguous rows expected, got {out.dtype} "
+                         f"{tuple(out.shape)} strides {out.stride()}")
+    K = int(out.shape[0])
+    if dst is None:
+        dst = torch.empty((K, Ho, Wo), dtype=torch.uint8, device=out.device)
+    elif dst.dtype != torch.uint8 or tuple(dst.shape) != (K, Ho, Wo) or not dst.is_contiguous() or dst.device != out.device:
+        raise ValueError(f"finish_frames: dst must be a dense uint8 [{K},{Ho},{Wo}] tensor on out's device")
+    part, nb = None, C.c_int(0)
+    g = gp = gs = gh = gw = None
+    if gt is not None:
+        g, n, gh, gw, gp, gs = u8_frames(gt, "finish_frames: gt")
+        if n != K or g.device != out.device:
+            raise ValueError(f"finish_frames: gt must hold one frame per output frame (K = {K}) on out's device, got {n}")
+        part = torch.empty((K, 1024), dtype=torch.int64, device=out.device)
+    with on_device(out):
+        check(_lib.lib().cdfo_finish_frames(_vp(out), int(out.stride(1)), C.c_longlong(out.stride(0)), K, Ho, Wo, _vp(dst),
+                                            QUANT_MODES[mode], _vp(g), gp or 0, C.c_longlong(gs or 0), gh or 0, gw or 0, int(crop),
+                                            _vp(part), 0 if part is None else part.numel(), C.byref(nb), _stream()),
+              "cdfo_finish_frames")
+    if part is None:
+        return dst, None
+    # the kernel packs its partial sums as [K][nblocks]; integers, so the sum is exact in any order
+    return dst, part.view(-1)[:K * nb.value].view(K, nb.value).sum(dim=1)
+
+
 def stem_conv(img: torch.Tensor, img_bstride: int, B: int, H: int, W: int, w: torch.Tensor, bias: torch.Tensor,
               act: int = ACT_NONE, add: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
               out2: Optional[torch.Tensor] = None):

@@ -3,17 +3,24 @@
 
 The reference saves the network output as an 8-bit PNG, reads it back and compares with the ground-truth PNG; here the
 tensors stay in HBM.  ``from_unit_range=True`` multiplies by 255 and clamps (the network emits [0,1] values);
-``round8=True`` additionally rounds to integers, which is what the PNG round trip does.
+``round8=True`` additionally rounds to the nearest integer.  (The reference's PNG round trip does NOT round: its writer is
+``(clamp(out,0,1).numpy() * 255.0).astype(np.uint8)``, test_LD_37.py:179-180, a truncation.  The 8-bit path -- ``kernels.finish_frames``
+with ``mode="trunc"``, then ``psnr_u8`` / ``ssim_u8`` below -- has the writer's semantics.)
+
+``psnr_u8`` / ``ssim_u8`` compare two stacks of 8-bit frames over their common size (``cal_psnr_ssim``'s min_height / min_width,
+psnr_ssim.py:462-468).  PSNR is formed on the host in fp64 from the exact integer sum of squared differences, which makes it
+bit-identical to the fp64 restatement of the reference's calculate_psnr on the same integers.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
-from .kernels import _stream, _vp, on_device
+from .kernels import _stream, _vp, on_device, u8_frames
 
 
 def _partials(a: torch.Tensor, b: torch.Tensor, crop: int, metric: int, from_unit_range: bool, round8: bool):
@@ -48,4 +55,51 @@ def calculate_ssim(img1: torch.Tensor, img2: torch.Tensor, crop_border: int = 4,
                    round8: bool = False) -> torch.Tensor:
     """Per-frame SSIM (fp64 tensor [N]): mean of the 11x11-Gaussian SSIM map over its valid positions."""
     s, Hc, Wc = _partials(img1, img2, crop_border, 1, from_unit_range, round8)
+    return s / float((Hc - 10) * (Wc - 10))
+
+
+def common_size(h1: int, w1: int, h2: int, w2: int):
+    """The size two frames are compared over: psnr_ssim.py:462-468 crops both to (min_height, min_width)."""
+    return min(h1, h2), min(w1, w2)
+
+
+def psnr_from_sse(sse, n: int) -> np.ndarray:
+    """fp64 [N] PSNR from integer sums of squared differences over n pixels each: calculate_psnr's arithmetic on the host
+    (mse = sum / n in fp64; inf where it is 0, else 20 log10(255 / sqrt(mse)))."""
+    mse = np.asarray(sse, dtype=np.int64).astype(np.float64).reshape(-1) / n
+    # frame by frame on numpy scalars: the very expression of calculate_psnr
+    return np.array([np.inf if m == 0 else 20.0 * np.log10(255.0 / np.sqrt(m)) for m in mse], dtype=np.float64)
+
+
+def _partials_u8(a: torch.Tensor, b: torch.Tensor, crop: int, metric: int):
+    a, N, Ha, Wa, pa, sa = u8_frames(a, "img1")
+    b, Nb, Hb, Wb, pb, sb = u8_frames(b, "img2")
+    if N != Nb or a.device != b.device:
+        raise ValueError(f"the two stacks must hold the same number of frames on one device, got {N} and {Nb}")
+    part = torch.empty((N, 1024), dtype=torch.float64, device=a.device)
+    nb = C.c_int(0)
+    with on_device(a):
+        _lib.check(_lib.lib().cdfo_metric_partials_u8(_vp(a), pa, C.c_longlong(sa), Ha, Wa, _vp(b), pb, C.c_longlong(sb), Hb, Wb, N,
+                                                      int(crop), metric, _vp(part), part.numel(), C.byref(nb), _stream()),
+                   "cdfo_metric_partials_u8")
+    Hm, Wm = common_size(Ha, Wa, Hb, Wb)
+    return part.view(-1)[:N * nb.value].view(N, nb.value).sum(dim=1), Hm - 2 * crop, Wm - 2 * crop
+
+
+def sse_u8(img1: torch.Tensor, img2: torch.Tensor, crop_border: int = 4):
+    """(int64 device tensor [N] of the sums of squared differences, pixels per frame): the exact numerator of `psnr_u8`."""
+    s, Hc, Wc = _partials_u8(img1, img2, crop_border, 0)
+    return s.to(torch.int64), Hc * Wc          # sums of integers below 2^53: the fp64 partials are exact
+
+
+def psnr_u8(img1: torch.Tensor, img2: torch.Tensor, crop_border: int = 4) -> np.ndarray:
+    """Per-frame PSNR of uint8 [N,H,W] device stacks (sizes may differ: compared over the common size), fp64 numpy [N] on the
+    host; ``inf`` where the frames are identical."""
+    s, n = sse_u8(img1, img2, crop_border)
+    return psnr_from_sse(s.cpu().numpy(), n)
+
+
+def ssim_u8(img1: torch.Tensor, img2: torch.Tensor, crop_border: int = 4) -> torch.Tensor:
+    """Per-frame SSIM of uint8 [N,H,W] device stacks over their common size (fp64 device tensor [N])."""
+    s, Hc, Wc = _partials_u8(img1, img2, crop_border, 1)
     return s / float((Hc - 10) * (Wc - 10))

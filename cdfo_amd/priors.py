@@ -88,9 +88,28 @@ def read_gray_png(path: str) -> np.ndarray:
     return out[:, ::bpp].copy() if bpp == 2 else out
 
 
-def write_gray_png(path: str, img: np.ndarray, filter_type: int = 0) -> None:
-    """uint8 [H,W] -> 8-bit greyscale PNG with every row filtered by ``filter_type`` (0-4).  For tests and tools."""
+def write_gray_png(path: str, img: np.ndarray, filter_type: int = 0, level: int = 6) -> None:
+    """uint8 [H,W] -> 8-bit greyscale PNG with every row filtered by ``filter_type`` (0-4), deflated at zlib ``level``.  Filter 0
+    (the default, what the evaluation loop writes) is one array operation; the other filters, for tests and tools, go row by row."""
     img = np.ascontiguousarray(img, dtype=np.uint8)
+    H, W = img.shape
+    if filter_type == 0:
+        packed = np.zeros((H, W + 1), dtype=np.uint8)           # each row: its filter byte (0), then the pixels
+        packed[:, 1:] = img
+        raw = packed.tobytes()
+    else:
+        raw = _filtered_rows(img, filter_type)
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+
+    with open(path, "wb") as f:
+        f.write(_SIG + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 0, 0, 0, 0)) +
+                chunk(b"IDAT", zlib.compress(raw, level)) + chunk(b"IEND", b""))
+
+
+def _filtered_rows(img: np.ndarray, filter_type: int) -> bytes:
+    """The rows of `img` under PNG filter 1-4 (Sub, Up, Average, Paeth), each behind its filter byte."""
     H, W = img.shape
     rows = bytearray()
     prev = np.zeros(W, dtype=np.int32)
@@ -98,9 +117,7 @@ def write_gray_png(path: str, img: np.ndarray, filter_type: int = 0) -> None:
         cur = img[y].astype(np.int32)
         left = np.concatenate([[0], cur[:-1]])
         ul = np.concatenate([[0], prev[:-1]])
-        if filter_type == 0:
-            enc = cur
-        elif filter_type == 1:
+        if filter_type == 1:
             enc = cur - left
         elif filter_type == 2:
             enc = cur - prev
@@ -114,13 +131,7 @@ def write_gray_png(path: str, img: np.ndarray, filter_type: int = 0) -> None:
         rows.append(filter_type)
         rows += (enc & 255).astype(np.uint8).tobytes()
         prev = cur
-
-    def chunk(kind, body):
-        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
-
-    with open(path, "wb") as f:
-        f.write(_SIG + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 0, 0, 0, 0)) +
-                chunk(b"IDAT", zlib.compress(bytes(rows), 6)) + chunk(b"IEND", b""))
+    return bytes(rows)
 
 
 def load_sequence(lr_dir: str, side_dir: str) -> Dict[str, np.ndarray]:

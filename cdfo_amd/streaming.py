@@ -19,7 +19,7 @@ the reference draws per (step, slot), so the windows of different output frames 
 from __future__ import annotations
 
 import time
-from typing import Iterator, List, NamedTuple, Optional, Sequence
+from typing import Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -294,9 +294,20 @@ class StreamingSR:
         into every window that holds it (and into every slot of a clipped window that repeats frame 0 or T - 1): across output
         frames the draws are correlated.  That is why the mode is opt-in.  A chunk that the fp16 range guard rejects is repeated
         in bf16x3 with the compensation of its frames recomputed (same noise) into a scratch stack; the ring is not rewritten."""
+        outs = []
+        for centres, out in self.iter_chunked(chunk, share_compensation):
+            outs.extend(out[j:j + 1, :, :4 * self.H, :4 * self.W] for j in range(len(centres)))
+        return outs
+
+    def iter_chunked(self, chunk: int = 8, share_compensation: bool = False) -> Iterator[Tuple[List[int], torch.Tensor]]:
+        """`run_chunked` one chunk at a time: yields ``(centres, out)`` with `centres` the chunk's frame indices and `out` its padded
+        fp32 output [len(centres),1,4Hp,4Wp] (frame j's picture is ``out[j, :, :4H, :4W]``).  A consumer that is done with a chunk
+        before it asks for the next one (cdfo_amd.evaluate) never holds more than one chunk of fp32 frames.  The schedule, the
+        counters and ``self.seconds`` are those of `run_chunked`, which is a list-builder over this generator."""
         check_noise_format(bool(share_compensation), self.noise, self.frame_noise, getattr(self, "T", 0))
         if share_compensation:
-            return self._run_chunked_shared(int(chunk))
+            yield from self._iter_chunked_shared(int(chunk))
+            return
         if not hasattr(self.model, "forward_windows"):
             raise NotImplementedError("run_chunked needs a model with extract_features / forward_windows (CVSR_V8)")
         plans = list(plan_chunks(self.T, int(chunk)))
@@ -311,17 +322,17 @@ class StreamingSR:
             flat += [bank_slot(p.windows[k][n], cap) for n in range(NFRAMES) for k in range(len(p.centres))]
             flat += [t for w in p.windows for t in w] + [t for w in p.priors for t in w] + p.extract_priors
         tables = torch.tensor(flat, dtype=torch.int32).to(self.dev)
-        outs, at = [], 0
+        at = 0
         for p in plans:
             n7 = NFRAMES * len(p.centres)
             idx = tables[at:at + 3 * n7 + len(p.extract)]
             at += 3 * n7 + len(p.extract)
-            outs.extend(self._chunk_step(p, bank, idx[:n7], idx[n7:2 * n7], idx[2 * n7:3 * n7], idx[3 * n7:]))
-        return outs
+            yield p.centres, self._chunk_step(p, bank, idx[:n7], idx[n7:2 * n7], idx[2 * n7:3 * n7], idx[3 * n7:])
 
-    def _chunk_step(self, plan: ChunkPlan, bank, lf_idx, frame_idx, prior_idx, extract_prior_idx) -> List[torch.Tensor]:
+    def _chunk_step(self, plan: ChunkPlan, bank, lf_idx, frame_idx, prior_idx, extract_prior_idx) -> torch.Tensor:
         """One chunk: extract the frames it is the first to reach into the bank (frame t lives in slot t mod capacity; what it
-        overwrites is below `plan.oldest`), gather the inputs of its windows, one forward at batch len(plan.centres)."""
+        overwrites is below `plan.oldest`), gather the inputs of its windows, one forward at batch len(plan.centres).  Returns the
+        padded output [len(plan.centres),1,4Hp,4Wp]."""
         from . import kernels as K
         k, cap = len(plan.centres), int(bank.shape[0])
         noise = None
@@ -344,10 +355,10 @@ class StreamingSR:
             out = self.model.forward_windows(Lf, x, None, m1, r, u, gumbel_uniform=noise)
         torch.cuda.synchronize(self.dev)
         self.seconds += time.perf_counter() - t0
-        return [out[j:j + 1, :, :4 * self.H, :4 * self.W] for j in range(k)]
+        return out
 
     # -- the same with each neighbour frame's compensation computed once (share_compensation=True) --------------------------------
-    def _run_chunked_shared(self, chunk: int) -> List[torch.Tensor]:
+    def _iter_chunked_shared(self, chunk: int) -> Iterator[Tuple[List[int], torch.Tensor]]:
         if not hasattr(self.model, "forward_windows_shared"):
             raise NotImplementedError("run_chunked(share_compensation=True) needs a model with compensate_features / "
                                       "forward_windows_shared (CVSR_V8)")
@@ -366,15 +377,14 @@ class StreamingSR:
             flat += comp_slot_table(p, cap) + [bank_slot(i, cap) for i in p.centres]
             flat += [t for w in p.windows for t in w] + [t for w in p.priors for t in w] + p.compensate_priors
         tables = torch.tensor(flat, dtype=torch.int32).to(self.dev)
-        outs, at = [], 0
+        at = 0
         for p in plans:
             k = len(p.centres)
             n = 21 * k + len(p.compensate)
             idx = tables[at:at + n]
             at += n
-            outs.extend(self._chunk_step_shared(p, bank, comp_bank, key, idx[:6 * k], idx[6 * k:7 * k], idx[7 * k:14 * k],
-                                                idx[14 * k:21 * k], idx[21 * k:]))
-        return outs
+            yield p.centres, self._chunk_step_shared(p, bank, comp_bank, key, idx[:6 * k], idx[6 * k:7 * k], idx[7 * k:14 * k],
+                                                     idx[14 * k:21 * k], idx[21 * k:])
 
     def _compensate(self, fea, frames: List[int], rms_planes, key):
         """compensate_features of `frames` (their features `fea`, their rms planes [F,Hp,Wp]) with each frame's own noise: its
@@ -385,7 +395,7 @@ class StreamingSR:
         return self.model.compensate_features(fea, rms_planes.unsqueeze(1), gumbel_uniform=noise, draws=frames)
 
     def _chunk_step_shared(self, plan: ChunkPlan, bank, comp_bank, key, comp_idx, centre_idx, frame_idx, prior_idx,
-                           new_prior_idx) -> List[torch.Tensor]:
+                           new_prior_idx) -> torch.Tensor:
         """One chunk of the shared mode: the frames it is the first to reach are extracted AND compensated into the two rings (same
         slot in both), then one forward at batch len(plan.centres) whose alignment reads the compensation ring in place."""
         from . import kernels as K
@@ -419,7 +429,7 @@ class StreamingSR:
             out = self.model.forward_windows_shared(Lc, comp_bank, comp_idx, x, m1, u, recompensate=recompensate)
         torch.cuda.synchronize(self.dev)
         self.seconds += time.perf_counter() - t0
-        return [out[j:j + 1, :, :4 * self.H, :4 * self.W] for j in range(k)]
+        return out
 
     @property
     def frames_compensated(self) -> int:

@@ -555,6 +555,29 @@ int cdfo_gather_frames(const void* src, int n_src, const int* idx, int n_dst, lo
 int cdfo_flow_warp_frames(const float* bank, int ldi, int n_bank, const int* idx, const float* mv, long long mv_kstride, int slot0,
                           int G, int K, int H, int W, int C, float* out, int ldo, void* stream);
 
+/* ---- the output side of sequence evaluation (finish.hip; cdfo_amd/evaluate.py) ----
+ * cdfo_finish_frames: K fp32 frames, read in place (frame k, row y at src + k*src_fstride + y*src_pitch, in elements; src 16-byte
+ *                     aligned, pitch and stride multiples of 4), -> K 8-bit frames dst [K][Ho][Wo], packed (Wo % 4 == 0, dst 16-byte
+ *                     aligned).  Per pixel, each step one correctly rounded fp32 operation: clamp to [0,1] (NaN -> 0), x 255, then
+ *                     CDFO_QUANT_TRUNC: truncation, the reference's `.astype(np.uint8)` (test_LD_37.py:179-180), or
+ *                     CDFO_QUANT_NEAREST: round to nearest even.  gt != NULL: in the same pass the PSNR numerator against 8-bit
+ *                     ground truth (frame k, row y at gt + k*gt_fstride + y*gt_pitch bytes, Hgt x Wgt): the sum of (u8 - gt)^2 over
+ *                     [crop, Hm-crop) x [crop, Wm-crop), Hm = min(Ho, Hgt), Wm = min(Wo, Wgt) (psnr_ssim.py:462-468), as exact
+ *                     64-bit integers: partial receives [K][*nblocks_out] sums (partial_cap = its capacity; K * 1024 always
+ *                     suffices), which the caller adds up.  gt == NULL: partial and nblocks_out are not touched.
+ * cdfo_metric_partials_u8: cdfo_metric_partials (metric 0: sum (a-b)^2; 1: sum of the SSIM map; fp64 partials [N][*nblocks_out],
+ *                     `crop`) on two stacks of N 8-bit frames with their own sizes, pitches and frame strides (bytes), compared
+ *                     over their common Hm x Wm = min(Ha, Hb) x min(Wa, Wb).
+ * Offsets inside a frame are 32-bit: rows * pitch beyond 2^31 - 1 is CDFO_EINVAL. */
+#define CDFO_QUANT_TRUNC 0
+#define CDFO_QUANT_NEAREST 1
+int cdfo_finish_frames(const float* src, int src_pitch, long long src_fstride, int K, int Ho, int Wo, unsigned char* dst, int mode,
+                       const unsigned char* gt, int gt_pitch, long long gt_fstride, int Hgt, int Wgt, int crop, long long* partial,
+                       int partial_cap, int* nblocks_out, void* stream);
+int cdfo_metric_partials_u8(const unsigned char* a, int a_pitch, long long a_fstride, int Ha, int Wa, const unsigned char* b,
+                            int b_pitch, long long b_fstride, int Hb, int Wb, int N, int crop, int metric, double* partial,
+                            int partial_cap, int* nblocks_out, void* stream);
+
 /* ---- optional per-launch HIP-event timing on the launch stream (bench.py's live roofline figures) ----------- */
 int cdfo_prof_begin(int max_records);
 int cdfo_prof_end(int* launches, double* ms, double* flops, double* bytes, int nkid);
