@@ -327,11 +327,18 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void seq_attn_mfma_kernel
   for (int s = 0; s < 4; ++s) {
     const f32x4 t0 = *reinterpret_cast<const f32x4*>(q + qpix * ldq + 16 * s + 8 * h) * LOG2E;
     const f32x4 t1 = *reinterpret_cast<const f32x4*>(q + qpix * ldq + 16 * s + 8 * h + 4) * LOG2E;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      qh[s][e] = (_Float16)t0[e];      ql[s][e] = (_Float16)(t0[e] - (float)qh[s][e]);
-      qh[s][4 + e] = (_Float16)t1[e];  ql[s][4 + e] = (_Float16)(t1[e] - (float)qh[s][4 + e]);
-    }
+    // split_pair_f16, not "lo = fp16(x - (float)hi)" written out: under -ffp-contract=fast the compiler fused the multiplication
+    // into ONE of hi's two uses (v_fma_mixlo_f16 rounds the exact product q * log2 e, v_cvt_pk_f16_f32 the fp32 product).  Where
+    // the fp32 product is an exact fp16 tie (1 element in 8192) the two can round apart, and hi + lo was then off by a whole fp16
+    // ulp of that element, 2^-10 relative, in every score of its query.  The helper's remainder reads the hi register it returns.
+    unsigned hu[4], lu[4];
+    split_pair_f16(t0[0], t0[1], hu[0], lu[0]);
+    split_pair_f16(t0[2], t0[3], hu[1], lu[1]);
+    split_pair_f16(t1[0], t1[1], hu[2], lu[2]);
+    split_pair_f16(t1[2], t1[3], hu[3], lu[3]);
+    const attn_u32x4 qhu = {hu[0], hu[1], hu[2], hu[3]}, qlu = {lu[0], lu[1], lu[2], lu[3]};
+    qh[s] = __builtin_bit_cast(attn_f16x8, qhu);
+    ql[s] = __builtin_bit_cast(attn_f16x8, qlu);
   }
   f32x16 o0, o1;
 #pragma unroll
