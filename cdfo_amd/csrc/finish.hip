@@ -12,6 +12,7 @@
 // writes the five moments (a, b, a^2, b^2, ab) in fp64 to LDS, a vertical pass forms the SSIM term.  22 taps per output instead of
 // the 121 of ssim_kernel (metrics.hip); fp64 throughout, as there.  No atomics: per-block partials, summed by the caller in order.
 #include "common.h"
+#include "numeric.h"
 
 namespace {
 
@@ -24,21 +25,6 @@ __device__ __forceinline__ unsigned quantise(float x, int mode) {
   v = __fmul_rn(v, 255.f);
   if (mode == CDFO_QUANT_NEAREST) v = rintf(v);
   return (unsigned)(int)v;
-}
-
-__device__ __forceinline__ long long block_sum_i64(long long v, long long* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)((unsigned long long)v >> 32), o, 64);
-    v += (long long)(((unsigned long long)hi << 32) | lo);
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  long long t = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
-  return t;   // valid in thread 0
 }
 
 template <int P> struct store_t;

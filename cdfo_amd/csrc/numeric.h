@@ -1,6 +1,7 @@
 // Device numerics that more than one translation unit needs: the split-precision conversions, the Philox generator, the
-// DPP row sum and the DCN power-of-two scale.  Two of them are contracts BETWEEN kernels (philox4x32_10: inference and
-// training draw the same noise for one seed; pow2_scale: both DCN paths scale alike), so each has exactly one definition here.
+// DPP row sum, the DCN power-of-two scale and the workgroup's 64-bit integer sum.  Two of them are contracts BETWEEN kernels
+// (philox4x32_10: inference and training draw the same noise for one seed; pow2_scale: both DCN paths scale alike), so each
+// has exactly one definition here.
 #pragma once
 #include "common.h"
 
@@ -65,4 +66,20 @@ __device__ __forceinline__ float row16_sum(float v) {     // sum over the 16 lan
 __device__ __forceinline__ float pow2_scale(unsigned max_bits) {
   const float m = __uint_as_float(max_bits);
   return m > 0.f ? exp2f(fminf(fmaxf(4.f - ceilf(log2f(m)), -100.f), 100.f)) : 1.f;
+}
+
+// exact 64-bit integer sum over a workgroup of whole waves (sh: one slot per wave); the total is valid in thread 0
+__device__ __forceinline__ long long block_sum_i64(long long v, long long* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)((unsigned long long)v >> 32), o, 64);
+    v += (long long)(((unsigned long long)hi << 32) | lo);
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  long long t = 0;
+  if (threadIdx.x == 0)
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
+  return t;   // valid in thread 0
 }

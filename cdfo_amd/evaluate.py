@@ -13,6 +13,9 @@ has completed and its PNGs are written), so nothing relies on the allocator's st
 chunk and the output side's memory does not depend on the sequence's length.  Ground truth comes up the same way: the pool decodes
 the next chunk's files during the current forward into one of two pinned buffers, uploaded as 8-bit without blocking.
 
+``evaluate_yuv`` is the same loop on raw 8-bit YUV 4:2:0 files (cdfo_amd/yuv.py): the luma as above, the two chroma planes upsampled x4
+on the device by ``cdfo_chroma_up4`` without passing through the model, PSNR for Y, U and V, the result appended to an I420 file.
+
 Deliberate deviation: ``cal_psnr_ssim`` sends single-channel frames through ``to_y_channel``, an fp32 ``/255*255`` round
 trip, and takes fp32 means.  The metric semantics here are the project's established ones, ``oracle/metrics_ref.py``: fp64 on the
 integers."""
@@ -21,7 +24,7 @@ from __future__ import annotations
 import concurrent.futures as cf
 import os
 import time
-from typing import List, NamedTuple, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -30,6 +33,7 @@ from . import kernels as K
 from . import metrics as M
 from .priors import load_sequence, read_gray_png, write_gray_png
 from .streaming import StreamingSR
+from .yuv import YuvReader, YuvWriter, load_sequence_yuv
 
 MAX_WORKERS = 16
 
@@ -185,20 +189,207 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
     return SequenceResult(psnr, ssim_t, mean(psnr), mean(ssim_t), T, s.seconds, time.perf_counter() - t_start)
 
 
-def write_synthetic_sequence(root: str, T: int, H: int, W: int, seed: int = 0, gt: bool = True):
-    """A random sequence of T frames of H x W in the reference's layout under ``root`` (lr/, side/..., and gt/ with 4H x 4W frames):
-    (lr_dir, side_dir, gt_dir or None).  For tools and benchmarks that have no data set at hand."""
+class YuvResult(NamedTuple):
+    psnr_y: np.ndarray          # fp64 [T] each (empty without ground truth)
+    psnr_u: np.ndarray
+    psnr_v: np.ndarray
+    ssim_y: np.ndarray
+    psnr_yuv: np.ndarray        # (6 Y + U + V) / 8 per frame
+    mean_psnr_y: float          # nan without ground truth
+    mean_psnr_u: float
+    mean_psnr_v: float
+    mean_ssim_y: float
+    mean_psnr_yuv: float
+    frames: int
+    seconds_forward: float      # StreamingSR.seconds
+    seconds_total: float        # the whole call
+
+
+def format_log_yuv(result: YuvResult, name: str) -> str:
+    """`format_log` for a 4:2:0 result: the luma figures in the reference's places, then the chroma and the combined PSNR."""
+    return '%s Average PSNR/SSIM: %.3f/%.5f PSNR-U/V/YUV: %.3f/%.3f/%.3f' % (
+        name, result.mean_psnr_y, result.mean_ssim_y, result.mean_psnr_u, result.mean_psnr_v, result.mean_psnr_yuv)
+
+
+def chroma_crop(crop_border: int) -> int:
+    """The border dropped from a 4:2:0 chroma plane when ``crop_border`` is dropped from the luma: half of it, rounded down."""
+    return int(crop_border) // 2
+
+
+def psnr_yuv(psnr_y, psnr_u, psnr_v) -> np.ndarray:
+    """The JCT-VC combined PSNR of 4:2:0 material, per frame: (6 Y + U + V) / 8."""
+    y, u, v = (np.asarray(a, dtype=np.float64) for a in (psnr_y, psnr_u, psnr_v))
+    return (6.0 * y + u + v) / 8.0
+
+
+def _stage_frame(reader: YuvReader, t: int, y: np.ndarray, u: np.ndarray, v: np.ndarray) -> None:
+    """Frame t of a mapped file into its places in a pinned buffer (the page faults of the map happen here, in the pool)."""
+    np.copyto(y, reader.y(t))
+    np.copyto(u, reader.u(t))
+    np.copyto(v, reader.v(t))
+
+
+def _append_when_copied(before: Optional[cf.Future], done: torch.cuda.Event, writer: YuvWriter, y: np.ndarray, c: np.ndarray) -> None:
+    """Append a chunk (y [k,Ho,Wo]; c [2k,Ho/2,Wo/2], its U planes then its V planes) once the chunk before it is in the file and
+    its own download into the pinned buffers `y` and `c` are views of has completed."""
+    if before is not None:
+        before.result()
+    done.synchronize()
+    k = len(y)
+    for j in range(k):
+        writer.append(y[j], c[j], c[k + j])
+
+
+def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_yuv: Optional[str] = None,
+                 save_yuv: Optional[str] = None, chunk: int = 8, share_compensation: bool = False, crop_border: int = 4,
+                 quantise: str = "trunc", workers: int = 8, gumbel_uniform: Optional[Sequence] = None,
+                 frame_noise: Optional[Sequence] = None, gt_size: Optional[Tuple[int, int]] = None) -> YuvResult:
+    """`evaluate_sequence` on raw 8-bit I420 files (cdfo_amd/yuv.py).  ``lr_yuv``: the LR sequence, ``width`` x ``height`` (even);
+    the coding priors stay in ``side_dir``.  The luma goes the way it goes there (`StreamingSR.iter_chunked`, ``finish_frames`` with the
+    PSNR numerator, ``ssim_u8``).  The chroma never passes through the model: per chunk the U and V planes of its centre frames are
+    uploaded as 8 bits and upsampled x4 by ``kernels.chroma_up4`` (from the unpadded planes), against the ground truth's chroma with
+    the border ``crop_border // 2``.  ``gt_yuv``: ground truth, an I420 file of ``gt_size`` = (width, height), by default 4 x the
+    LR size; the pool copies the next chunk out of the memory map into one of two pinned buffers during the current forward.
+    ``save_yuv``: the result as an I420 file of 4 width x 4 height, appended in frame order by the pool from one of two sets of
+    pinned buffers.  The other arguments are `evaluate_sequence`'s."""
+    workers = _check_workers(workers)
+    if quantise not in K.QUANT_MODES:
+        raise ValueError(f"quantise must be one of {sorted(K.QUANT_MODES)}, got {quantise!r}")
+    if int(chunk) < 1:
+        raise ValueError(f"chunk >= 1 expected, got {chunk}")
+    t_start = time.perf_counter()
+    chunk, ccrop = int(chunk), chroma_crop(crop_border)
+    with YuvReader(lr_yuv, width, height) as head:
+        T = head.frames
+    kmax, Ho, Wo, hc, wc = min(chunk, T), 4 * height, 4 * width, height // 2, width // 2
+    Hoc, Woc = 4 * hc, 4 * wc
+    gt = writer = Hgt = Wgt = None
+    try:
+        if gt_yuv is not None:
+            Wgt, Hgt = gt_size if gt_size is not None else (Wo, Ho)
+            gt = YuvReader(gt_yuv, Wgt, Hgt)
+            if gt.frames != T:
+                raise ValueError(f"{gt_yuv} holds {gt.frames} frames of {Wgt}x{Hgt}, {lr_yuv} holds {T}")
+            if min(metric_region(Ho, Wo, Hgt, Wgt, crop_border)[2:]) <= 10:
+                raise ValueError(f"crop_border {crop_border} leaves no SSIM window in the common {min(Ho, Hgt)} x {min(Wo, Wgt)} of "
+                                 f"result and ground truth")
+            if min(metric_region(Hoc, Woc, Hgt // 2, Wgt // 2, ccrop)[2:]) <= 0:
+                raise ValueError(f"crop_border {crop_border} leaves nothing of the chroma planes")
+        pinned = lambda n, h, w: torch.empty((n, h, w), dtype=torch.uint8).pin_memory()
+        writer = YuvWriter(save_yuv, Wo, Ho) if save_yuv is not None else None
+        with cf.ThreadPoolExecutor(max_workers=workers) as pool:
+            # ground truth comes up through two sets of pinned buffers: chunk c's frames are copied out of the map by the pool
+            # while chunk c - 1's forward runs
+            gt_y = [pinned(kmax, Hgt, Wgt) for _ in range(2)] if gt is not None else None
+            gt_c = [pinned(2 * kmax, Hgt // 2, Wgt // 2) for _ in range(2)] if gt is not None else None
+
+            def read_gt(c):
+                if gt is None or c * chunk >= T:
+                    return []
+                k, y, uv = min(chunk, T - c * chunk), gt_y[c % 2].numpy(), gt_c[c % 2].numpy()
+                return [pool.submit(_stage_frame, gt, c * chunk + j, y[j], uv[j], uv[k + j]) for j in range(k)]
+
+            gt_reads = read_gt(0)
+            seq = load_sequence_yuv(lr_yuv, width, height, side_dir)
+            lr_u, lr_v = seq.pop("u"), seq.pop("v")
+            s = StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"],
+                            gumbel_uniform=gumbel_uniform, frame_noise=frame_noise)
+            del seq
+            dev = s.dev
+            with torch.cuda.device(dev):
+                main, copy = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+                on_dev = lambda n, h, w: torch.empty((n, h, w), dtype=torch.uint8, device=dev)
+                dev_y, dev_c = [on_dev(kmax, Ho, Wo) for _ in range(2)], [on_dev(2 * kmax, Hoc, Woc) for _ in range(2)]
+                host_y = [pinned(kmax, Ho, Wo) for _ in range(2)] if writer is not None else None
+                host_c = [pinned(2 * kmax, Hoc, Woc) for _ in range(2)] if writer is not None else None
+                copied = [torch.cuda.Event() for _ in range(2)]
+                lrc_host, lrc_dev = [pinned(2 * kmax, hc, wc) for _ in range(2)], [on_dev(2 * kmax, hc, wc) for _ in range(2)]
+                gty_dev = [on_dev(kmax, Hgt, Wgt) for _ in range(2)] if gt is not None else None
+                gtc_dev = [on_dev(2 * kmax, Hgt // 2, Wgt // 2) for _ in range(2)] if gt is not None else None
+                uploaded = [torch.cuda.Event() for _ in range(2)]
+                pending: List[Optional[cf.Future]] = [None, None]
+                last_write: Optional[cf.Future] = None
+                sse_y, sse_c, ssim = [], [], []
+                chunks = s.iter_chunked(chunk, share_compensation)
+                for c in range((T + chunk - 1) // chunk):
+                    b = c % 2
+                    uploaded[1 - b].synchronize()       # chunk c - 1 has left the pinned buffers chunk c + 1 is staged in
+                    mine, gt_reads = gt_reads, read_gt(c + 1)   # the next chunk's frames: copied during this chunk's forward
+                    centres, out = next(chunks)
+                    k = len(centres)
+                    if pending[b] is not None:          # chunk c - 2 is out of the pinned result buffers b (raises what it raised)
+                        pending[b].result()
+                        pending[b] = None
+                    if c >= 2 and writer is not None:
+                        main.wait_event(copied[b])      # ... and out of the device buffers b
+                    uploaded[b].synchronize()           # chunk c - 2 has left the pinned LR chroma buffer b
+                    planes = lrc_host[b].numpy()
+                    planes[:k], planes[k:2 * k] = lr_u[centres[0]:centres[0] + k], lr_v[centres[0]:centres[0] + k]
+                    src_c = lrc_dev[b][:2 * k]
+                    src_c.copy_(lrc_host[b][:2 * k], non_blocking=True)
+                    gy = gc = None
+                    if gt is not None:
+                        for f in mine:
+                            f.result()
+                        gy, gc = gty_dev[b][:k], gtc_dev[b][:2 * k]
+                        gy.copy_(gt_y[b][:k], non_blocking=True)
+                        gc.copy_(gt_c[b][:2 * k], non_blocking=True)
+                    uploaded[b].record(main)
+                    y8, e = K.finish_frames(out, s.H, s.W, gt=gy, crop=crop_border, mode=quantise, dst=dev_y[b][:k])
+                    del out                              # the chunk's fp32 frames end here
+                    c8, ec = K.chroma_up4(src_c, gt=gc, crop=ccrop, dst=dev_c[b][:2 * k])
+                    if gt is not None:
+                        sse_y.append(e)
+                        sse_c.append(ec.view(2, k))
+                        ssim.append(M.ssim_u8(y8, gy, crop_border))
+                    if writer is not None:
+                        ready = torch.cuda.Event()
+                        ready.record(main)
+                        copy.wait_event(ready)
+                        with torch.cuda.stream(copy):
+                            host_y[b][:k].copy_(y8, non_blocking=True)
+                            host_c[b][:2 * k].copy_(c8, non_blocking=True)
+                            copied[b].record(copy)
+                        last_write = pending[b] = pool.submit(_append_when_copied, last_write, copied[b], writer,
+                                                              host_y[b].numpy()[:k], host_c[b].numpy()[:2 * k])
+                for f in pending:
+                    if f is not None:
+                        f.result()
+                main.wait_stream(copy)
+                empty = np.zeros(0, np.float64)
+                py, pu, pv, ssim_t = empty, empty, empty, empty
+                if gt is not None:
+                    n_y = int(np.prod(metric_region(Ho, Wo, Hgt, Wgt, crop_border)[2:]))
+                    n_c = int(np.prod(metric_region(Hoc, Woc, Hgt // 2, Wgt // 2, ccrop)[2:]))
+                    py = M.psnr_from_sse(torch.cat(sse_y).cpu().numpy(), n_y)
+                    ec = torch.cat(sse_c, dim=1).cpu().numpy()
+                    pu, pv = M.psnr_from_sse(ec[0], n_c), M.psnr_from_sse(ec[1], n_c)
+                    ssim_t = torch.cat(ssim).cpu().numpy().astype(np.float64)
+                torch.cuda.synchronize(dev)
+    finally:
+        if writer is not None:
+            writer.close()
+        if gt is not None:
+            gt.close()
+    pyuv = psnr_yuv(py, pu, pv)
+    mean = lambda a: float(a.sum() / len(a)) if len(a) else float("nan")
+    return YuvResult(py, pu, pv, ssim_t, pyuv, mean(py), mean(pu), mean(pv), mean(ssim_t), mean(pyuv), T, s.seconds,
+                     time.perf_counter() - t_start)
+
+
+def _write_synthetic(root: str, T: int, H: int, W: int, seed: int, put_lr, put_gt) -> str:
+    """The random content of the synthetic writers, drawn in one fixed order: per frame the LR luma to ``put_lr(t, frame)``, the
+    4H x 4W ground-truth luma to ``put_gt(t, frame)`` (None: not drawn), then the frame's coding priors into ``<root>/side``, which
+    is returned."""
     rs = np.random.RandomState(seed)
-    lr_dir, side, gt_dir = os.path.join(root, "lr"), os.path.join(root, "side"), os.path.join(root, "gt")
-    for d in (lr_dir, *(os.path.join(side, n) for n in ("part_m", "res", "unfiltered", "mvl0", "mvl1"))):
+    side = os.path.join(root, "side")
+    for d in (os.path.join(side, n) for n in ("part_m", "res", "unfiltered", "mvl0", "mvl1")):
         os.makedirs(d, exist_ok=True)
-    if gt:
-        os.makedirs(gt_dir, exist_ok=True)
     hb, wb = (H + 7) // 8, (W + 7) // 8
     for t in range(T):
-        write_gray_png(os.path.join(lr_dir, "%05d.png" % t), rs.randint(0, 256, (H, W)).astype(np.uint8))
-        if gt:
-            write_gray_png(os.path.join(gt_dir, "%05d.png" % t), rs.randint(0, 256, (4 * H, 4 * W)).astype(np.uint8), level=1)
+        put_lr(t, rs.randint(0, 256, (H, W)).astype(np.uint8))
+        if put_gt is not None:
+            put_gt(t, rs.randint(0, 256, (4 * H, 4 * W)).astype(np.uint8))
         if t >= 1 or T == 1:                         # the reference's side-info files start at 00001
             i = "%05d" % max(1, t)
             write_gray_png(os.path.join(side, "part_m", i + "_M_mask.png"), rs.randint(0, 256, (H, W)).astype(np.uint8))
@@ -210,4 +401,35 @@ def write_synthetic_sequence(root: str, T: int, H: int, W: int, seed: int = 0, g
                 mv[..., 2] = rs.choice([-2, -1, 1], size=(hb, wb))
                 mv = np.repeat(np.repeat(mv, 8, axis=0), 8, axis=1)[:H, :W]
                 np.save(os.path.join(side, name, i + "_" + name + ".npy"), mv)
+    return side
+
+
+def write_synthetic_sequence(root: str, T: int, H: int, W: int, seed: int = 0, gt: bool = True):
+    """A random sequence of T frames of H x W in the reference's layout under ``root`` (lr/, side/..., and gt/ with 4H x 4W frames):
+    (lr_dir, side_dir, gt_dir or None).  For tools and benchmarks that have no data set at hand."""
+    lr_dir, gt_dir = os.path.join(root, "lr"), os.path.join(root, "gt")
+    os.makedirs(lr_dir, exist_ok=True)
+    if gt:
+        os.makedirs(gt_dir, exist_ok=True)
+    side = _write_synthetic(root, T, H, W, seed, lambda t, f: write_gray_png(os.path.join(lr_dir, "%05d.png" % t), f),
+                            (lambda t, f: write_gray_png(os.path.join(gt_dir, "%05d.png" % t), f, level=1)) if gt else None)
     return lr_dir, side, (gt_dir if gt else None)
+
+
+def write_synthetic_sequence_yuv(root: str, T: int, H: int, W: int, seed: int = 0, gt: bool = True):
+    """`write_synthetic_sequence` with the frames in raw I420 files: the same luma and the same coding priors for the same ``seed``,
+    plus random chroma (a generator of its own, so the luma's draws are those of the PNG layout).  H and W even.
+    (lr_yuv, side_dir, gt_yuv or None); the files are ``<root>/lr_WxH.yuv`` and ``<root>/gt_4Wx4H.yuv``."""
+    rc = np.random.RandomState((seed + 0x9E3779B9) % (1 << 32))
+    lr_yuv, gt_yuv = os.path.join(root, "lr_%dx%d.yuv" % (W, H)), os.path.join(root, "gt_%dx%d.yuv" % (4 * W, 4 * H))
+    os.makedirs(root, exist_ok=True)
+    chroma = lambda h, w: rc.randint(0, 256, (h, w)).astype(np.uint8)
+    with YuvWriter(lr_yuv, W, H) as lw:
+        gw = YuvWriter(gt_yuv, 4 * W, 4 * H) if gt else None
+        try:
+            side = _write_synthetic(root, T, H, W, seed, lambda t, f: lw.append(f, chroma(H // 2, W // 2), chroma(H // 2, W // 2)),
+                                    (lambda t, f: gw.append(f, chroma(2 * H, 2 * W), chroma(2 * H, 2 * W))) if gt else None)
+        finally:
+            if gw is not None:
+                gw.close()
+    return lr_yuv, side, (gt_yuv if gt else None)

@@ -650,6 +650,35 @@ def finish_frames(out: torch.Tensor, H: int, W: int, gt: Optional[torch.Tensor] 
     return dst, part.view(-1)[:K * nb.value].view(K, nb.value).sum(dim=1)
 
 
+def chroma_up4(src: torch.Tensor, gt: Optional[torch.Tensor] = None, crop: int = 2, dst: Optional[torch.Tensor] = None):
+    """src: 8-bit planes [N,h,w] (or [h,w]) on the device with contiguous rows, read in place (pitch and plane stride may exceed the
+    plane) -> (u8 [N,4h,4w], sse): the centre-aligned x4 cubic of include/cdfo_hip.h, in integers, bit-exact against its numpy
+    statement.  With ``gt`` (uint8 [N,Hgt,Wgt], device) sse is the int64 [N] sum of (u8 - gt)^2 over the common min(4h, Hgt) x
+    min(4w, Wgt) less ``crop`` border pixels, exact; else None.  ``dst``: an optional dense uint8 [N,4h,4w] destination."""
+    s, N, h, w, sp, ss = u8_frames(src, "chroma_up4: src")
+    if h <= 0 or w <= 0 or N <= 0:
+        raise ValueError(f"chroma_up4: src holds no pixels: {tuple(s.shape)}")
+    if dst is None:
+        dst = torch.empty((N, 4 * h, 4 * w), dtype=torch.uint8, device=s.device)
+    elif dst.dtype != torch.uint8 or tuple(dst.shape) != (N, 4 * h, 4 * w) or not dst.is_contiguous() or dst.device != s.device:
+        raise ValueError(f"chroma_up4: dst must be a dense uint8 [{N},{4 * h},{4 * w}] tensor on src's device")
+    part, nb = None, C.c_int(0)
+    g = gp = gs = gh = gw = None
+    if gt is not None:
+        g, n, gh, gw, gp, gs = u8_frames(gt, "chroma_up4: gt")
+        if n != N or g.device != s.device:
+            raise ValueError(f"chroma_up4: gt must hold one plane per source plane (N = {N}) on src's device, got {n}")
+        part = torch.empty((N, 1024), dtype=torch.int64, device=s.device)
+    with on_device(s):
+        check(_lib.lib().cdfo_chroma_up4(_vp(s), sp, C.c_longlong(ss), N, h, w, _vp(dst), _vp(g), gp or 0, C.c_longlong(gs or 0),
+                                         gh or 0, gw or 0, int(crop), _vp(part), 0 if part is None else part.numel(), C.byref(nb),
+                                         _stream()), "cdfo_chroma_up4")
+    if part is None:
+        return dst, None
+    # the kernel packs its partial sums as [N][nblocks]; integers, so the sum is exact in any order
+    return dst, part.view(-1)[:N * nb.value].view(N, nb.value).sum(dim=1)
+
+
 def stem_conv(img: torch.Tensor, img_bstride: int, B: int, H: int, W: int, w: torch.Tensor, bias: torch.Tensor,
               act: int = ACT_NONE, add: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
               out2: Optional[torch.Tensor] = None):

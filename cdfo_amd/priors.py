@@ -134,15 +134,10 @@ def _filtered_rows(img: np.ndarray, filter_type: int) -> bytes:
     return bytes(rows)
 
 
-def load_sequence(lr_dir: str, side_dir: str) -> Dict[str, np.ndarray]:
-    """One sequence of the reference's test layout -> the arrays ``StreamingSR`` takes:
-    lr, pms, ufs uint8 [T,H,W]; rms [T,H,W] (dtype of the ``*_res.npy`` files); mvl0, mvl1 [T,H,W,3].
-    Index t = file index t; entry 0 of the priors (which the reference never reads: ``ii = max(1, i)``) repeats entry 1."""
-    names = sorted(n for n in os.listdir(lr_dir) if n.lower().endswith(".png"))
-    if not names:
-        raise FileNotFoundError(f"no PNG frames in {lr_dir}")
-    T = len(names)
-    lr = np.stack([read_gray_png(os.path.join(lr_dir, n)) for n in names])
+def load_priors(side_dir: str, T: int, shape=None) -> Dict[str, np.ndarray]:
+    """The coding priors of a sequence of T frames: pms, ufs uint8 [T,H,W]; rms [T,H,W] (dtype of the ``*_res.npy`` files); mvl0,
+    mvl1 [T,H,W,3].  Entry 0 (which the reference never reads: ``ii = max(1, i)``) repeats entry 1.  ``shape``: the (T,H,W) of the
+    LR frames the planes must have, else ValueError."""
 
     def per_frame(fn):
         items = [fn("%05d" % max(1, t)) for t in range(T)] if T > 1 else [fn("%05d" % 1)]
@@ -153,7 +148,19 @@ def load_sequence(lr_dir: str, side_dir: str) -> Dict[str, np.ndarray]:
     rms = per_frame(lambda i: np.load(os.path.join(side_dir, "res", i + "_res.npy"))[:, :, 0])
     mvl0 = per_frame(lambda i: np.load(os.path.join(side_dir, "mvl0", i + "_mvl0.npy")))
     mvl1 = per_frame(lambda i: np.load(os.path.join(side_dir, "mvl1", i + "_mvl1.npy")))
-    for name, arr in (("pms", pms), ("ufs", ufs), ("rms", rms)):
-        if arr.shape != lr.shape:
-            raise ValueError(f"{name} planes are {arr.shape[1:]} but the LR frames are {lr.shape[1:]}")
-    return dict(lr=lr, pms=pms, rms=rms, ufs=ufs, mvl0=mvl0, mvl1=mvl1)
+    if shape is not None:
+        for name, arr in (("pms", pms), ("ufs", ufs), ("rms", rms)):
+            if arr.shape != tuple(shape):
+                raise ValueError(f"{name} planes are {arr.shape[1:]} but the LR frames are {tuple(shape)[1:]}")
+    return dict(pms=pms, rms=rms, ufs=ufs, mvl0=mvl0, mvl1=mvl1)
+
+
+def load_sequence(lr_dir: str, side_dir: str) -> Dict[str, np.ndarray]:
+    """One sequence of the reference's test layout -> the arrays ``StreamingSR`` takes:
+    lr, pms, ufs uint8 [T,H,W]; rms [T,H,W] (dtype of the ``*_res.npy`` files); mvl0, mvl1 [T,H,W,3].
+    Index t = file index t; entry 0 of the priors (which the reference never reads: ``ii = max(1, i)``) repeats entry 1."""
+    names = sorted(n for n in os.listdir(lr_dir) if n.lower().endswith(".png"))
+    if not names:
+        raise FileNotFoundError(f"no PNG frames in {lr_dir}")
+    lr = np.stack([read_gray_png(os.path.join(lr_dir, n)) for n in names])
+    return dict(lr=lr, **load_priors(side_dir, len(names), lr.shape))

@@ -578,6 +578,20 @@ int cdfo_metric_partials_u8(const unsigned char* a, int a_pitch, long long a_fst
                             int b_pitch, long long b_fstride, int Hb, int Wb, int N, int crop, int metric, double* partial,
                             int partial_cap, int* nblocks_out, void* stream);
 
+/* ---- chroma of YUV 4:2:0 evaluation (chroma.hip; cdfo_amd/evaluate.py: evaluate_yuv) ----
+ * cdfo_chroma_up4: N 8-bit planes h x w, read in place (plane n, row y at src + n*src_pstride + y*src_pitch bytes), -> N 8-bit planes
+ *                     dst [N][4h][4w], packed (dst 4-byte aligned).  Centre-aligned x4 Catmull-Rom in integers: output index 4q + r
+ *                     takes four taps from q-2 (r = 0, 1) or q-1 (r = 2, 3), indices clamped to the plane, coefficients / 128
+ *                     (-6,50,93,-9), (-1,12,123,-6), (-6,123,12,-1), (-9,93,50,-6) for r = 0..3; along x and y in 32-bit integers
+ *                     without intermediate rounding, then clamp((v + 8192) >> 14, 0, 255), the shift arithmetic.  gt != NULL: in the
+ *                     same pass the sum of (out - gt)^2 over [crop, Hm-crop) x [crop, Wm-crop), Hm = min(4h, Hgt), Wm = min(4w, Wgt),
+ *                     as exact 64-bit integers: partial receives [N][*nblocks_out] sums (partial_cap = its capacity; N * 1024 always
+ *                     suffices), which the caller adds up.  gt == NULL: partial and nblocks_out are not touched.
+ * Offsets inside a plane are 32-bit: rows * pitch (and 16 h w) beyond 2^31 - 1 is CDFO_EINVAL. */
+int cdfo_chroma_up4(const unsigned char* src, int src_pitch, long long src_pstride, int N, int h, int w, unsigned char* dst,
+                    const unsigned char* gt, int gt_pitch, long long gt_pstride, int Hgt, int Wgt, int crop, long long* partial,
+                    int partial_cap, int* nblocks_out, void* stream);
+
 /* ---- optional per-launch HIP-event timing on the launch stream (bench.py's live roofline figures) ----------- */
 int cdfo_prof_begin(int max_records);
 int cdfo_prof_end(int* launches, double* ms, double* flops, double* bytes, int nkid);

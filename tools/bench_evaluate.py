@@ -2,11 +2,15 @@
 
     python tools/bench_evaluate.py [--size T H W] [--chunk K] [--repeats R]     sequence benchmark
     python tools/bench_evaluate.py --ssim [--frames N]                          the two SSIM kernels at 1080 x 1920
+    python tools/bench_evaluate.py --yuv [--size T H W] [--chunk K] [--repeats R]    the PNG path against the raw 4:2:0 path
 
 Sequence benchmark, one process, one warm-up pass then R passes each, medians: run_chunked alone; evaluate_sequence with metrics
 only; with metrics and PNG writing at 8 and 16 workers; and the per-chunk times of the finish kernel and the two 8-bit metric
 kernels from events.  --ssim: the separable 8-bit SSIM kernel (cdfo_metric_partials_u8) against ssim_kernel (cdfo_metric_partials)
-on fp32 copies of the same frames, median of five."""
+on fp32 copies of the same frames, median of five.  --yuv: the same synthetic content once in the PNG layout and once as I420
+files; run_chunked alone, then evaluate_sequence and evaluate_yuv end to end, metrics only and with the result written (the baseline
+is the PNG path of this very run); the time the priors' PNGs and NPYs take to read, which both paths pay before their first chunk;
+and chroma_up4 per chunk from events."""
 import os
 import sys
 import tempfile
@@ -96,5 +100,65 @@ def sequence():
               f"8-bit squared-difference kernel {sq:.3f} ms, 8-bit SSIM kernel {ss:.3f} ms", flush=True)
 
 
+def yuv():
+    import time
+    from arch.SIDECVSR_our import CVSR_V8
+    from cdfo_amd import kernels as K
+    from cdfo_amd.evaluate import evaluate_sequence, evaluate_yuv, write_synthetic_sequence, write_synthetic_sequence_yuv
+    from cdfo_amd.priors import load_priors, load_sequence
+    from cdfo_amd.streaming import StreamingSR
+    T, H, W = _arg("--size", 3, [64, 270, 480])
+    chunk, reps = _arg("--chunk", 1, 8), _arg("--repeats", 1, 5)
+    model = CVSR_V8().cuda().eval()
+    with tempfile.TemporaryDirectory() as tmp:
+        lr, side, gt = write_synthetic_sequence(os.path.join(tmp, "png"), T, H, W)
+        lr_yuv, side_yuv, gt_yuv = write_synthetic_sequence_yuv(os.path.join(tmp, "raw"), T, H, W)
+        seq = load_sequence(lr, side)
+        s = StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"])
+        s.run_chunked(chunk)
+        fps = []
+        for _ in range(reps):
+            s.run_chunked(chunk)
+            fps.append(s.fps)
+        base = float(np.median(fps))
+        print(f"run_chunked(chunk={chunk}) alone, {T} frames {H}x{W}: frames/s per pass {' '.join('%.2f' % f for f in fps)}; median "
+              f"{base:.2f}", flush=True)
+        del s, seq
+        secs = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            load_priors(side, T)
+            secs.append(time.perf_counter() - t0)
+        priors = float(np.median(secs))
+        print(f"load_priors ({2 * (T - 1)} LR-sized PNGs, {3 * (T - 1)} NPYs), before the first chunk of either path: median "
+              f"{priors * 1e3:.1f} ms", flush=True)
+        png_out, yuv_out = os.path.join(tmp, "out"), os.path.join(tmp, "out.yuv")
+        runs = (("evaluate_sequence, metrics only", lambda: evaluate_sequence(model, lr, side, gt_dir=gt, chunk=chunk)),
+                ("evaluate_yuv, metrics only", lambda: evaluate_yuv(model, lr_yuv, W, H, side_yuv, gt_yuv=gt_yuv, chunk=chunk)),
+                ("evaluate_sequence, metrics + PNGs, 8 workers",
+                 lambda: evaluate_sequence(model, lr, side, gt_dir=gt, save_dir=png_out, chunk=chunk)),
+                ("evaluate_yuv, metrics + I420 file",
+                 lambda: evaluate_yuv(model, lr_yuv, W, H, side_yuv, gt_yuv=gt_yuv, save_yuv=yuv_out, chunk=chunk)))
+        for label, run in runs:
+            run()
+            rs = [run() for _ in range(reps)]
+            fwd, tot = [r.frames / r.seconds_forward for r in rs], [r.frames / r.seconds_total for r in rs]
+            sec = float(np.median([r.seconds_total for r in rs]))
+            print(f"{label}: forward-only frames/s median {np.median(fwd):.2f}; end to end (files read included) per pass "
+                  f"{' '.join('%.2f' % f for f in tot)}; median {np.median(tot):.2f} ({np.median(tot) / base:.3f} of run_chunked alone); "
+                  f"{sec:.3f} s per pass, of which load_priors {100 * priors / sec:.1f} %", flush=True)
+        # chroma_up4 on one chunk's worth of planes (2 per frame), with and without ground truth, from events
+        hc, wc = H // 2, W // 2
+        src = torch.randint(0, 256, (2 * chunk, hc, wc), dtype=torch.uint8).cuda()
+        gt8 = torch.randint(0, 256, (2 * chunk, 4 * hc, 4 * wc), dtype=torch.uint8).cuda()
+        dst, _ = K.chroma_up4(src, gt=gt8)
+        with_gt, _ = _median_ms(lambda: K.chroma_up4(src, gt=gt8, dst=dst))
+        plain, _ = _median_ms(lambda: K.chroma_up4(src, dst=dst))
+        mb = 2 * chunk * hc * wc / 1e6
+        print(f"chroma_up4 per chunk of {chunk} frames ({2 * chunk} planes {hc}x{wc} -> {4 * hc}x{4 * wc}; wrapper included), median of "
+              f"5: {plain:.3f} ms ({17 * mb / plain:.1f} GB/s), with the squared-difference sum {with_gt:.3f} ms "
+              f"({33 * mb / with_gt:.1f} GB/s)", flush=True)
+
+
 if __name__ == "__main__":
-    ssim_ab() if "--ssim" in sys.argv else sequence()
+    ssim_ab() if "--ssim" in sys.argv else yuv() if "--yuv" in sys.argv else sequence()

@@ -3,6 +3,11 @@
     python tools/eval_sequence.py --lr LR_DIR --side SIDE_DIR [--gt GT_DIR] [--out SAVE_DIR] [--chunk 8] [--share] [--workers 8]
                                   [--weights FILE.pth] [--name SEQUENCE]
     python tools/eval_sequence.py --synthetic T H W [--out SAVE_DIR] ...
+    python tools/eval_sequence.py --lr-yuv FILE --size W H --side SIDE_DIR [--gt-yuv FILE [--gt-size W H]] [--out-yuv FILE] ...
+    python tools/eval_sequence.py --synthetic T H W --yuv [--out-yuv FILE] ...
+
+The last two forms read and write raw 8-bit YUV 4:2:0 (I420) files (cdfo_amd.evaluate.evaluate_yuv): the luma goes through the model,
+the chroma is upsampled x4 on the device, PSNR is reported for Y, U and V.  The ground truth is 4W x 4H unless --gt-size says otherwise.
 
 Prints the reference's log line and frames/s, forward only and end to end.  --synthetic writes a random sequence of T frames of
 H x W with 4H x 4W ground truth into a temporary directory and evaluates that (with --weights absent the model is randomly
@@ -27,27 +32,49 @@ def main():
     ap.add_argument("--weights")
     ap.add_argument("--name")
     ap.add_argument("--synthetic", type=int, nargs=3, metavar=("T", "H", "W"))
+    ap.add_argument("--lr-yuv")
+    ap.add_argument("--size", type=int, nargs=2, metavar=("W", "H"))
+    ap.add_argument("--gt-yuv")
+    ap.add_argument("--gt-size", type=int, nargs=2, metavar=("W", "H"))
+    ap.add_argument("--out-yuv")
+    ap.add_argument("--yuv", action="store_true", help="with --synthetic: write the sequence as I420 files and run evaluate_yuv")
     a = ap.parse_args()
-    if a.synthetic is None and not (a.lr and a.side):
-        ap.error("--lr and --side, or --synthetic T H W")
+    yuv = a.lr_yuv is not None or a.yuv
+    if a.lr_yuv is not None and not (a.size and a.side):
+        ap.error("--lr-yuv needs --size W H and --side")
+    if a.yuv and a.synthetic is None:
+        ap.error("--yuv goes with --synthetic T H W")
+    if a.synthetic is None and not yuv and not (a.lr and a.side):
+        ap.error("--lr and --side, or --lr-yuv, --size and --side, or --synthetic T H W")
     import torch
     from arch.SIDECVSR_our import CVSR_V8
-    from cdfo_amd.evaluate import evaluate_sequence, format_log, write_synthetic_sequence
+    from cdfo_amd.evaluate import (evaluate_sequence, evaluate_yuv, format_log, format_log_yuv, write_synthetic_sequence,
+                                   write_synthetic_sequence_yuv)
     model = CVSR_V8()
     if a.weights:
         model.load_state_dict(torch.load(a.weights, map_location="cpu"))
     model = model.cuda().eval()
     with tempfile.TemporaryDirectory() as tmp:
-        lr, side, gt = a.lr, a.side, a.gt
-        if a.synthetic is not None:
-            lr, side, gt = write_synthetic_sequence(tmp, *a.synthetic)
-        r = evaluate_sequence(model, lr, side, gt_dir=gt, save_dir=a.out, chunk=a.chunk, share_compensation=a.share, workers=a.workers)
+        if yuv:
+            lr, side, gt, size = a.lr_yuv, a.side, a.gt_yuv, a.size
+            if a.synthetic is not None:
+                T, H, W = a.synthetic
+                (lr, side, gt), size = write_synthetic_sequence_yuv(tmp, T, H, W), (W, H)
+            r = evaluate_yuv(model, lr, size[0], size[1], side, gt_yuv=gt, save_yuv=a.out_yuv, chunk=a.chunk,
+                             share_compensation=a.share, workers=a.workers, gt_size=tuple(a.gt_size) if a.gt_size else None)
+        else:
+            lr, side, gt = a.lr, a.side, a.gt
+            if a.synthetic is not None:
+                lr, side, gt = write_synthetic_sequence(tmp, *a.synthetic)
+            r = evaluate_sequence(model, lr, side, gt_dir=gt, save_dir=a.out, chunk=a.chunk, share_compensation=a.share,
+                                  workers=a.workers)
     name = a.name or os.path.basename(os.path.normpath(lr if a.synthetic is None else "synthetic"))
     if gt is not None:
-        print(format_log(r, name))
+        print(format_log_yuv(r, name) if yuv else format_log(r, name))
+    written = ", I420 file written" if yuv and a.out_yuv else ", PNGs written with " + str(a.workers) + " workers" if a.out and not yuv else ""
     print(f"{name}: {r.frames} frames, chunk {a.chunk}{', shared compensation' if a.share else ''}: "
           f"{r.frames / r.seconds_forward:.2f} frames/s forward only, {r.frames / r.seconds_total:.2f} frames/s end to end "
-          f"(files read, metrics{', PNGs written with ' + str(a.workers) + ' workers' if a.out else ''})")
+          f"(files read, metrics{written})")
 
 
 if __name__ == "__main__":
