@@ -83,3 +83,33 @@ __device__ __forceinline__ long long block_sum_i64(long long v, long long* sh) {
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
   return t;   // valid in thread 0
 }
+
+// Ground truth of the evaluation kernels (finish.hip, chroma.hip): the samples x0 .. x0+3 of a row (x0 a multiple of 4) as one word,
+// sample e in bits [8 sizeof(T) e, 8 sizeof(T) (e + 1)).  words = 0: nothing is read here (the caller reads per element); 1: aligned
+// 32-bit words (for 16-bit samples two of them, the second, samples x0+2 and x0+3, only where the caller wants it: it may lie beyond
+// the row's pitch); 2, 16-bit samples only: one aligned 64-bit word.
+template <typename T> struct gt_word;
+template <> struct gt_word<unsigned char> { typedef unsigned type; };
+template <> struct gt_word<unsigned short> { typedef unsigned long long type; };
+
+__device__ __forceinline__ unsigned load_gt_word(const unsigned char* p, int words, bool) {
+  return words ? *reinterpret_cast<const unsigned*>(p) : 0u;
+}
+__device__ __forceinline__ unsigned long long load_gt_word(const unsigned short* p, int words, bool second) {
+  if (words == 2) return *reinterpret_cast<const unsigned long long*>(p);
+  if (words == 0) return 0ull;
+  const unsigned* q = reinterpret_cast<const unsigned*>(p);
+  return (unsigned long long)q[0] | (second ? (unsigned long long)q[1] << 32 : 0ull);
+}
+
+// (q - r)^2 of two samples as a 64-bit addend.  8-bit: the signed 32-bit product.  16-bit: 65535^2 = 4294836225 does not fit a signed
+// 32-bit product; the unsigned one holds it (the square of a wrapped negative difference is the same number modulo 2^32).
+template <typename T> __device__ __forceinline__ long long sqdiff(unsigned q, unsigned r) {
+  if constexpr (sizeof(T) == 1) {
+    const int df = (int)q - (int)r;
+    return df * df;
+  } else {
+    const unsigned df = q - r;
+    return (long long)(unsigned long long)(df * df);
+  }
+}

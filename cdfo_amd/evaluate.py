@@ -18,7 +18,11 @@ on the device by ``cdfo_chroma_up4`` without passing through the model, PSNR for
 
 Deliberate deviation: ``cal_psnr_ssim`` sends single-channel frames through ``to_y_channel``, an fp32 ``/255*255`` round
 trip, and takes fp32 means.  The metric semantics here are the project's established ones, ``oracle/metrics_ref.py``: fp64 on the
-integers."""
+integers.
+
+``evaluate_yuv(..., pix_fmt=)`` takes the other planar formats of cdfo_amd/yuv.py: 4:0:0, 4:2:0 and 4:4:4 at 8, 10, 12 or 16 bits, one
+format for the LR file, the ground truth and the result.  Above 8 bits the sample buffers are uint16, `StreamingSR` divides by the
+format's peak 2**depth - 1, and the three kernels are their 16-bit forms with that peak."""
 from __future__ import annotations
 
 import concurrent.futures as cf
@@ -33,7 +37,7 @@ from . import kernels as K
 from . import metrics as M
 from .priors import load_sequence, read_gray_png, write_gray_png
 from .streaming import StreamingSR
-from .yuv import YuvReader, YuvWriter, load_sequence_yuv
+from .yuv import YuvReader, YuvWriter, load_sequence_yuv, parse_pix_fmt
 
 MAX_WORKERS = 16
 
@@ -53,17 +57,20 @@ def format_log(result: SequenceResult, name: str) -> str:
     return '%s Average PSNR/SSIM: %.3f/%.5f' % (name, result.mean_psnr, result.mean_ssim)
 
 
-def quantise_numpy(x: np.ndarray, mode: str = "trunc") -> np.ndarray:
+def quantise_numpy(x: np.ndarray, mode: str = "trunc", peak: int = 255) -> np.ndarray:
     """The numpy statement of ``kernels.finish_frames``: clip to [0,1] (NaN -> 0), fp32 * 255, truncation or round-to-nearest-even.
-    On finite values ``mode="trunc"`` is ``(np.clip(x, 0, 1) * 255.0).astype(np.uint8)``, the reference's writer."""
+    On finite values ``mode="trunc"`` is ``(np.clip(x, 0, 1) * 255.0).astype(np.uint8)``, the reference's writer.  ``peak``: the
+    multiplier in place of 255 (1 .. 65535); uint16 comes back above 255."""
+    if isinstance(peak, bool) or not isinstance(peak, (int, np.integer)) or not 1 <= peak <= 65535:
+        raise ValueError(f"peak must be an integer in 1 .. 65535, got {peak!r}")
     v = np.asarray(x, dtype=np.float32)
     v = np.where(np.isnan(v), np.float32(0), v)
-    v = np.clip(v, np.float32(0), np.float32(1)) * np.float32(255.0)
+    v = np.clip(v, np.float32(0), np.float32(1)) * np.float32(peak)
     if mode == "nearest":
         v = np.rint(v)
     elif mode != "trunc":
         raise ValueError(f"quantise must be 'trunc' or 'nearest', got {mode!r}")
-    return v.astype(np.uint8)
+    return v.astype(np.uint8 if peak <= 255 else np.uint16)
 
 
 def metric_region(h_out: int, w_out: int, h_gt: int, w_gt: int, crop: int):
@@ -194,7 +201,7 @@ class YuvResult(NamedTuple):
     psnr_u: np.ndarray
     psnr_v: np.ndarray
     ssim_y: np.ndarray
-    psnr_yuv: np.ndarray        # (6 Y + U + V) / 8 per frame
+    psnr_yuv: np.ndarray        # (6 Y + U + V) / 8 per frame (4:0:0: Y)
     mean_psnr_y: float          # nan without ground truth
     mean_psnr_u: float
     mean_psnr_v: float
@@ -211,39 +218,48 @@ def format_log_yuv(result: YuvResult, name: str) -> str:
         name, result.mean_psnr_y, result.mean_ssim_y, result.mean_psnr_u, result.mean_psnr_v, result.mean_psnr_yuv)
 
 
-def chroma_crop(crop_border: int) -> int:
-    """The border dropped from a 4:2:0 chroma plane when ``crop_border`` is dropped from the luma: half of it, rounded down."""
-    return int(crop_border) // 2
+def chroma_crop(crop_border: int, chroma: str = "420") -> int:
+    """The border dropped from a 4:2:0 chroma plane when ``crop_border`` is dropped from the luma: half of it, rounded down.
+    ``chroma="444"``: the planes are the luma's size and so is the border."""
+    return int(crop_border) // 2 if chroma == "420" else int(crop_border)
 
 
 def psnr_yuv(psnr_y, psnr_u, psnr_v) -> np.ndarray:
-    """The JCT-VC combined PSNR of 4:2:0 material, per frame: (6 Y + U + V) / 8."""
+    """The JCT-VC combined PSNR of 4:2:0 material, per frame: (6 Y + U + V) / 8.  The project's definition for 4:4:4 as well (the
+    weights are the convention's, not the planes' share of the samples); a 4:0:0 sequence reports its luma PSNR in this place."""
     y, u, v = (np.asarray(a, dtype=np.float64) for a in (psnr_y, psnr_u, psnr_v))
     return (6.0 * y + u + v) / 8.0
 
 
-def _stage_frame(reader: YuvReader, t: int, y: np.ndarray, u: np.ndarray, v: np.ndarray) -> None:
-    """Frame t of a mapped file into its places in a pinned buffer (the page faults of the map happen here, in the pool)."""
+def _stage_frame(reader: YuvReader, t: int, y: np.ndarray, u: Optional[np.ndarray], v: Optional[np.ndarray]) -> None:
+    """Frame t of a mapped file into its places in a pinned buffer (the page faults of the map happen here, in the pool); u and v
+    None: a 4:0:0 file."""
     np.copyto(y, reader.y(t))
-    np.copyto(u, reader.u(t))
-    np.copyto(v, reader.v(t))
+    if u is not None:
+        np.copyto(u, reader.u(t))
+        np.copyto(v, reader.v(t))
 
 
-def _append_when_copied(before: Optional[cf.Future], done: torch.cuda.Event, writer: YuvWriter, y: np.ndarray, c: np.ndarray) -> None:
-    """Append a chunk (y [k,Ho,Wo]; c [2k,Ho/2,Wo/2], its U planes then its V planes) once the chunk before it is in the file and
-    its own download into the pinned buffers `y` and `c` are views of has completed."""
+def _append_when_copied(before: Optional[cf.Future], done: torch.cuda.Event, writer: YuvWriter, y: np.ndarray,
+                        c: Optional[np.ndarray]) -> None:
+    """Append a chunk (y [k,Ho,Wo]; c [2k,Ho/2,Wo/2], its U planes then its V planes; None: 4:0:0) once the chunk before it is in the
+    file and its own download into the pinned buffers `y` and `c` are views of has completed."""
     if before is not None:
         before.result()
     done.synchronize()
     k = len(y)
     for j in range(k):
-        writer.append(y[j], c[j], c[k + j])
+        if c is None:
+            writer.append(y[j])
+        else:
+            writer.append(y[j], c[j], c[k + j])
 
 
 def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_yuv: Optional[str] = None,
                  save_yuv: Optional[str] = None, chunk: int = 8, share_compensation: bool = False, crop_border: int = 4,
                  quantise: str = "trunc", workers: int = 8, gumbel_uniform: Optional[Sequence] = None,
-                 frame_noise: Optional[Sequence] = None, gt_size: Optional[Tuple[int, int]] = None) -> YuvResult:
+                 frame_noise: Optional[Sequence] = None, gt_size: Optional[Tuple[int, int]] = None,
+                 pix_fmt: str = "yuv420p") -> YuvResult:
     """`evaluate_sequence` on raw 8-bit I420 files (cdfo_amd/yuv.py).  ``lr_yuv``: the LR sequence, ``width`` x ``height`` (even);
     the coding priors stay in ``side_dir``.  The luma goes the way it goes there (`StreamingSR.iter_chunked`, ``finish_frames`` with the
     PSNR numerator, ``ssim_u8``).  The chroma never passes through the model: per chunk the U and V planes of its centre frames are
@@ -251,61 +267,76 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     the border ``crop_border // 2``.  ``gt_yuv``: ground truth, an I420 file of ``gt_size`` = (width, height), by default 4 x the
     LR size; the pool copies the next chunk out of the memory map into one of two pinned buffers during the current forward.
     ``save_yuv``: the result as an I420 file of 4 width x 4 height, appended in frame order by the pool from one of two sets of
-    pinned buffers.  The other arguments are `evaluate_sequence`'s."""
+    pinned buffers.  The other arguments are `evaluate_sequence`'s.
+
+    ``pix_fmt`` (`yuv.parse_pix_fmt`): the one format of ``lr_yuv``, ``gt_yuv`` and ``save_yuv``.  Above 8 bits the buffers hold
+    uint16 samples and every figure is on the 0 .. 2**depth - 1 scale; the unfiltered planes and residuals in ``side_dir`` are at that
+    depth too (16-bit PNGs, wider NPYs), the partition maps stay 8-bit masks.  ``gray*``: no chroma work, ``psnr_u`` / ``psnr_v`` are
+    empty and ``psnr_yuv`` is ``psnr_y``.  ``yuv444p*``: chroma planes of the luma's size, their border ``crop_border``."""
+    fmt = parse_pix_fmt(pix_fmt)
+    peak, has_c = fmt.peak, fmt.chroma != "400"
+    kind = torch.uint8 if fmt.sample_bytes == 1 else torch.uint16
     workers = _check_workers(workers)
     if quantise not in K.QUANT_MODES:
         raise ValueError(f"quantise must be one of {sorted(K.QUANT_MODES)}, got {quantise!r}")
     if int(chunk) < 1:
         raise ValueError(f"chunk >= 1 expected, got {chunk}")
     t_start = time.perf_counter()
-    chunk, ccrop = int(chunk), chroma_crop(crop_border)
-    with YuvReader(lr_yuv, width, height) as head:
+    chunk, ccrop = int(chunk), chroma_crop(crop_border, fmt.chroma)
+    with YuvReader(lr_yuv, width, height, fmt) as head:
         T = head.frames
-    kmax, Ho, Wo, hc, wc = min(chunk, T), 4 * height, 4 * width, height // 2, width // 2
+    kmax, Ho, Wo = min(chunk, T), 4 * height, 4 * width
+    hc, wc = fmt.chroma_shape(height, width) or (0, 0)
     Hoc, Woc = 4 * hc, 4 * wc
     gt = writer = Hgt = Wgt = None
+    Hgc = Wgc = 0                                        # the ground truth's chroma planes
     try:
         if gt_yuv is not None:
             Wgt, Hgt = gt_size if gt_size is not None else (Wo, Ho)
-            gt = YuvReader(gt_yuv, Wgt, Hgt)
+            gt = YuvReader(gt_yuv, Wgt, Hgt, fmt)
+            Hgc, Wgc = fmt.chroma_shape(Hgt, Wgt) or (0, 0)
             if gt.frames != T:
                 raise ValueError(f"{gt_yuv} holds {gt.frames} frames of {Wgt}x{Hgt}, {lr_yuv} holds {T}")
             if min(metric_region(Ho, Wo, Hgt, Wgt, crop_border)[2:]) <= 10:
                 raise ValueError(f"crop_border {crop_border} leaves no SSIM window in the common {min(Ho, Hgt)} x {min(Wo, Wgt)} of "
                                  f"result and ground truth")
-            if min(metric_region(Hoc, Woc, Hgt // 2, Wgt // 2, ccrop)[2:]) <= 0:
+            if has_c and min(metric_region(Hoc, Woc, Hgc, Wgc, ccrop)[2:]) <= 0:
                 raise ValueError(f"crop_border {crop_border} leaves nothing of the chroma planes")
-        pinned = lambda n, h, w: torch.empty((n, h, w), dtype=torch.uint8).pin_memory()
-        writer = YuvWriter(save_yuv, Wo, Ho) if save_yuv is not None else None
+        pinned = lambda n, h, w: torch.empty((n, h, w), dtype=kind).pin_memory()
+        writer = YuvWriter(save_yuv, Wo, Ho, fmt) if save_yuv is not None else None
         with cf.ThreadPoolExecutor(max_workers=workers) as pool:
             # ground truth comes up through two sets of pinned buffers: chunk c's frames are copied out of the map by the pool
             # while chunk c - 1's forward runs
             gt_y = [pinned(kmax, Hgt, Wgt) for _ in range(2)] if gt is not None else None
-            gt_c = [pinned(2 * kmax, Hgt // 2, Wgt // 2) for _ in range(2)] if gt is not None else None
+            gt_c = [pinned(2 * kmax, Hgc, Wgc) for _ in range(2)] if gt is not None and has_c else None
 
             def read_gt(c):
                 if gt is None or c * chunk >= T:
                     return []
-                k, y, uv = min(chunk, T - c * chunk), gt_y[c % 2].numpy(), gt_c[c % 2].numpy()
+                k, y = min(chunk, T - c * chunk), gt_y[c % 2].numpy()
+                if not has_c:
+                    return [pool.submit(_stage_frame, gt, c * chunk + j, y[j], None, None) for j in range(k)]
+                uv = gt_c[c % 2].numpy()
                 return [pool.submit(_stage_frame, gt, c * chunk + j, y[j], uv[j], uv[k + j]) for j in range(k)]
 
             gt_reads = read_gt(0)
-            seq = load_sequence_yuv(lr_yuv, width, height, side_dir)
-            lr_u, lr_v = seq.pop("u"), seq.pop("v")
+            seq = load_sequence_yuv(lr_yuv, width, height, side_dir, fmt)
+            lr_u, lr_v = seq.pop("u", None), seq.pop("v", None)
             s = StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"],
-                            gumbel_uniform=gumbel_uniform, frame_noise=frame_noise)
+                            gumbel_uniform=gumbel_uniform, frame_noise=frame_noise, peak=peak)
             del seq
             dev = s.dev
             with torch.cuda.device(dev):
                 main, copy = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
-                on_dev = lambda n, h, w: torch.empty((n, h, w), dtype=torch.uint8, device=dev)
-                dev_y, dev_c = [on_dev(kmax, Ho, Wo) for _ in range(2)], [on_dev(2 * kmax, Hoc, Woc) for _ in range(2)]
-                host_y = [pinned(kmax, Ho, Wo) for _ in range(2)] if writer is not None else None
-                host_c = [pinned(2 * kmax, Hoc, Woc) for _ in range(2)] if writer is not None else None
+                on_dev = lambda n, h, w: torch.empty((n, h, w), dtype=kind, device=dev)
+                pair = lambda make, *shape: [make(*shape) for _ in range(2)]
+                dev_y, dev_c = pair(on_dev, kmax, Ho, Wo), pair(on_dev, 2 * kmax, Hoc, Woc) if has_c else None
+                host_y = pair(pinned, kmax, Ho, Wo) if writer is not None else None
+                host_c = pair(pinned, 2 * kmax, Hoc, Woc) if writer is not None and has_c else None
                 copied = [torch.cuda.Event() for _ in range(2)]
-                lrc_host, lrc_dev = [pinned(2 * kmax, hc, wc) for _ in range(2)], [on_dev(2 * kmax, hc, wc) for _ in range(2)]
-                gty_dev = [on_dev(kmax, Hgt, Wgt) for _ in range(2)] if gt is not None else None
-                gtc_dev = [on_dev(2 * kmax, Hgt // 2, Wgt // 2) for _ in range(2)] if gt is not None else None
+                lrc_host, lrc_dev = (pair(pinned, 2 * kmax, hc, wc), pair(on_dev, 2 * kmax, hc, wc)) if has_c else (None, None)
+                gty_dev = pair(on_dev, kmax, Hgt, Wgt) if gt is not None else None
+                gtc_dev = pair(on_dev, 2 * kmax, Hgc, Wgc) if gt is not None and has_c else None
                 uploaded = [torch.cuda.Event() for _ in range(2)]
                 pending: List[Optional[cf.Future]] = [None, None]
                 last_write: Optional[cf.Future] = None
@@ -323,35 +354,43 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
                     if c >= 2 and writer is not None:
                         main.wait_event(copied[b])      # ... and out of the device buffers b
                     uploaded[b].synchronize()           # chunk c - 2 has left the pinned LR chroma buffer b
-                    planes = lrc_host[b].numpy()
-                    planes[:k], planes[k:2 * k] = lr_u[centres[0]:centres[0] + k], lr_v[centres[0]:centres[0] + k]
-                    src_c = lrc_dev[b][:2 * k]
-                    src_c.copy_(lrc_host[b][:2 * k], non_blocking=True)
+                    src_c = None
+                    if has_c:
+                        planes = lrc_host[b].numpy()
+                        planes[:k], planes[k:2 * k] = lr_u[centres[0]:centres[0] + k], lr_v[centres[0]:centres[0] + k]
+                        src_c = lrc_dev[b][:2 * k]
+                        src_c.copy_(lrc_host[b][:2 * k], non_blocking=True)
                     gy = gc = None
                     if gt is not None:
                         for f in mine:
                             f.result()
-                        gy, gc = gty_dev[b][:k], gtc_dev[b][:2 * k]
+                        gy = gty_dev[b][:k]
                         gy.copy_(gt_y[b][:k], non_blocking=True)
-                        gc.copy_(gt_c[b][:2 * k], non_blocking=True)
+                        if has_c:
+                            gc = gtc_dev[b][:2 * k]
+                            gc.copy_(gt_c[b][:2 * k], non_blocking=True)
                     uploaded[b].record(main)
-                    y8, e = K.finish_frames(out, s.H, s.W, gt=gy, crop=crop_border, mode=quantise, dst=dev_y[b][:k])
+                    y8, e = K.finish_frames(out, s.H, s.W, gt=gy, crop=crop_border, mode=quantise, dst=dev_y[b][:k], peak=peak)
                     del out                              # the chunk's fp32 frames end here
-                    c8, ec = K.chroma_up4(src_c, gt=gc, crop=ccrop, dst=dev_c[b][:2 * k])
+                    c8 = ec = None
+                    if has_c:
+                        c8, ec = K.chroma_up4(src_c, gt=gc, crop=ccrop, dst=dev_c[b][:2 * k], peak=peak)
                     if gt is not None:
                         sse_y.append(e)
-                        sse_c.append(ec.view(2, k))
-                        ssim.append(M.ssim_u8(y8, gy, crop_border))
+                        if has_c:
+                            sse_c.append(ec.view(2, k))
+                        ssim.append(M.ssim_u8(y8, gy, crop_border) if kind == torch.uint8 else M.ssim_u16(y8, gy, crop_border, peak))
                     if writer is not None:
                         ready = torch.cuda.Event()
                         ready.record(main)
                         copy.wait_event(ready)
                         with torch.cuda.stream(copy):
                             host_y[b][:k].copy_(y8, non_blocking=True)
-                            host_c[b][:2 * k].copy_(c8, non_blocking=True)
+                            if has_c:
+                                host_c[b][:2 * k].copy_(c8, non_blocking=True)
                             copied[b].record(copy)
                         last_write = pending[b] = pool.submit(_append_when_copied, last_write, copied[b], writer,
-                                                              host_y[b].numpy()[:k], host_c[b].numpy()[:2 * k])
+                                                              host_y[b].numpy()[:k], host_c[b].numpy()[:2 * k] if has_c else None)
                 for f in pending:
                     if f is not None:
                         f.result()
@@ -360,10 +399,11 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
                 py, pu, pv, ssim_t = empty, empty, empty, empty
                 if gt is not None:
                     n_y = int(np.prod(metric_region(Ho, Wo, Hgt, Wgt, crop_border)[2:]))
-                    n_c = int(np.prod(metric_region(Hoc, Woc, Hgt // 2, Wgt // 2, ccrop)[2:]))
-                    py = M.psnr_from_sse(torch.cat(sse_y).cpu().numpy(), n_y)
-                    ec = torch.cat(sse_c, dim=1).cpu().numpy()
-                    pu, pv = M.psnr_from_sse(ec[0], n_c), M.psnr_from_sse(ec[1], n_c)
+                    py = M.psnr_from_sse(torch.cat(sse_y).cpu().numpy(), n_y, peak)
+                    if has_c:
+                        n_c = int(np.prod(metric_region(Hoc, Woc, Hgc, Wgc, ccrop)[2:]))
+                        ec = torch.cat(sse_c, dim=1).cpu().numpy()
+                        pu, pv = M.psnr_from_sse(ec[0], n_c, peak), M.psnr_from_sse(ec[1], n_c, peak)
                     ssim_t = torch.cat(ssim).cpu().numpy().astype(np.float64)
                 torch.cuda.synchronize(dev)
     finally:
@@ -371,30 +411,32 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
             writer.close()
         if gt is not None:
             gt.close()
-    pyuv = psnr_yuv(py, pu, pv)
+    pyuv = psnr_yuv(py, pu, pv) if has_c else py
     mean = lambda a: float(a.sum() / len(a)) if len(a) else float("nan")
     return YuvResult(py, pu, pv, ssim_t, pyuv, mean(py), mean(pu), mean(pv), mean(ssim_t), mean(pyuv), T, s.seconds,
                      time.perf_counter() - t_start)
 
 
-def _write_synthetic(root: str, T: int, H: int, W: int, seed: int, put_lr, put_gt) -> str:
+def _write_synthetic(root: str, T: int, H: int, W: int, seed: int, put_lr, put_gt, peak: int = 255) -> str:
     """The random content of the synthetic writers, drawn in one fixed order: per frame the LR luma to ``put_lr(t, frame)``, the
     4H x 4W ground-truth luma to ``put_gt(t, frame)`` (None: not drawn), then the frame's coding priors into ``<root>/side``, which
-    is returned."""
+    is returned.  ``peak`` above 255: samples over 0 .. peak as uint16, the unfiltered planes as 16-bit PNGs, the residuals scaled to
+    the depth as int16; the partition maps stay 8-bit."""
     rs = np.random.RandomState(seed)
+    kind, gain = (np.uint8, 1) if peak == 255 else (np.uint16, (peak + 1) // 256)
     side = os.path.join(root, "side")
     for d in (os.path.join(side, n) for n in ("part_m", "res", "unfiltered", "mvl0", "mvl1")):
         os.makedirs(d, exist_ok=True)
     hb, wb = (H + 7) // 8, (W + 7) // 8
     for t in range(T):
-        put_lr(t, rs.randint(0, 256, (H, W)).astype(np.uint8))
+        put_lr(t, rs.randint(0, peak + 1, (H, W)).astype(kind))
         if put_gt is not None:
-            put_gt(t, rs.randint(0, 256, (4 * H, 4 * W)).astype(np.uint8))
+            put_gt(t, rs.randint(0, peak + 1, (4 * H, 4 * W)).astype(kind))
         if t >= 1 or T == 1:                         # the reference's side-info files start at 00001
             i = "%05d" % max(1, t)
             write_gray_png(os.path.join(side, "part_m", i + "_M_mask.png"), rs.randint(0, 256, (H, W)).astype(np.uint8))
-            write_gray_png(os.path.join(side, "unfiltered", i + "_unflt.png"), rs.randint(0, 256, (H, W)).astype(np.uint8))
-            res = np.clip(np.round(rs.randn(H, W, 3) * 6), -128, 127).astype(np.int8)
+            write_gray_png(os.path.join(side, "unfiltered", i + "_unflt.png"), rs.randint(0, peak + 1, (H, W)).astype(kind))
+            res = np.clip(np.round(rs.randn(H, W, 3) * (6 * gain)), -128 * gain, 128 * gain - 1).astype(np.int8 if gain == 1 else np.int16)
             np.save(os.path.join(side, "res", i + "_res.npy"), res)
             for name in ("mvl0", "mvl1"):            # block-constant motion, a reference distance of -2, -1 or 1
                 mv = rs.randint(-64, 64, (hb, wb, 3)).astype(np.int16)
@@ -416,19 +458,33 @@ def write_synthetic_sequence(root: str, T: int, H: int, W: int, seed: int = 0, g
     return lr_dir, side, (gt_dir if gt else None)
 
 
-def write_synthetic_sequence_yuv(root: str, T: int, H: int, W: int, seed: int = 0, gt: bool = True):
+def write_synthetic_sequence_yuv(root: str, T: int, H: int, W: int, seed: int = 0, gt: bool = True, pix_fmt: str = "yuv420p"):
     """`write_synthetic_sequence` with the frames in raw I420 files: the same luma and the same coding priors for the same ``seed``,
     plus random chroma (a generator of its own, so the luma's draws are those of the PNG layout).  H and W even.
-    (lr_yuv, side_dir, gt_yuv or None); the files are ``<root>/lr_WxH.yuv`` and ``<root>/gt_4Wx4H.yuv``."""
+    (lr_yuv, side_dir, gt_yuv or None); the files are ``<root>/lr_WxH.yuv`` and ``<root>/gt_4Wx4H.yuv``.
+    ``pix_fmt``: another format of cdfo_amd/yuv.py (H and W even for 4:2:0 only).  Above 8 bits every plane draws from the whole
+    0 .. 2**depth - 1, the priors are at that depth, and each chroma plane holds both ends of the range."""
+    fmt = parse_pix_fmt(pix_fmt)
     rc = np.random.RandomState((seed + 0x9E3779B9) % (1 << 32))
     lr_yuv, gt_yuv = os.path.join(root, "lr_%dx%d.yuv" % (W, H)), os.path.join(root, "gt_%dx%d.yuv" % (4 * W, 4 * H))
     os.makedirs(root, exist_ok=True)
-    chroma = lambda h, w: rc.randint(0, 256, (h, w)).astype(np.uint8)
-    with YuvWriter(lr_yuv, W, H) as lw:
-        gw = YuvWriter(gt_yuv, 4 * W, 4 * H) if gt else None
+
+    def planes(h, w):                                    # the two chroma planes of an h x w frame, drawn U then V
+        shape = fmt.chroma_shape(h, w)
+        if shape is None:
+            return ()
+        if fmt.depth == 8:
+            return tuple(rc.randint(0, 256, shape).astype(np.uint8) for _ in range(2))
+        both = tuple(rc.randint(0, fmt.peak + 1, shape).astype(np.uint16) for _ in range(2))
+        for p in both:
+            p.flat[0], p.flat[-1] = 0, fmt.peak
+        return both
+
+    with YuvWriter(lr_yuv, W, H, fmt) as lw:
+        gw = YuvWriter(gt_yuv, 4 * W, 4 * H, fmt) if gt else None
         try:
-            side = _write_synthetic(root, T, H, W, seed, lambda t, f: lw.append(f, chroma(H // 2, W // 2), chroma(H // 2, W // 2)),
-                                    (lambda t, f: gw.append(f, chroma(2 * H, 2 * W), chroma(2 * H, 2 * W))) if gt else None)
+            side = _write_synthetic(root, T, H, W, seed, lambda t, f: lw.append(f, *planes(H, W)),
+                                    (lambda t, f: gw.append(f, *planes(4 * H, 4 * W))) if gt else None, fmt.peak)
         finally:
             if gw is not None:
                 gw.close()

@@ -600,24 +600,57 @@ def gather_frames(src: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tens
 QUANT_MODES = {"trunc": 0, "nearest": 1}        # CDFO_QUANT_* of include/cdfo_hip.h
 
 
-def u8_frames(t: torch.Tensor, name: str):
-    """An 8-bit frame stack [N,H,W] (or [H,W]) with contiguous rows -> (tensor [N,H,W], N, H, W, pitch, frame stride), in bytes;
-    pitch and stride may exceed W and H * pitch (a view of larger frames is read in place)."""
+def _sample_frames(t: torch.Tensor, name: str, dtype: torch.dtype):
     if t.dim() == 2:
         t = t.unsqueeze(0)
-    if not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 3 or t.stride(2) != 1 or t.stride(1) < t.shape[2] or t.stride(0) < 0:
-        raise ValueError(f"{name}: a device uint8 tensor [N,H,W] with contiguous rows expected, got {t.dtype} {tuple(t.shape)} "
+    if not t.is_cuda or t.dtype != dtype or t.dim() != 3 or t.stride(2) != 1 or t.stride(1) < t.shape[2] or t.stride(0) < 0:
+        kind = str(dtype).split(".")[-1]
+        raise ValueError(f"{name}: a device {kind} tensor [N,H,W] with contiguous rows expected, got {t.dtype} {tuple(t.shape)} "
                          f"strides {t.stride()}")
     return t, int(t.shape[0]), int(t.shape[1]), int(t.shape[2]), int(t.stride(1)), int(t.stride(0))
 
 
+def u8_frames(t: torch.Tensor, name: str):
+    """An 8-bit frame stack [N,H,W] (or [H,W]) with contiguous rows -> (tensor [N,H,W], N, H, W, pitch, frame stride), in bytes;
+    pitch and stride may exceed W and H * pitch (a view of larger frames is read in place)."""
+    return _sample_frames(t, name, torch.uint8)
+
+
+def u16_frames(t: torch.Tensor, name: str):
+    """`u8_frames` for 16-bit samples (torch.uint16): pitch and frame stride in samples."""
+    return _sample_frames(t, name, torch.uint16)
+
+
+def sample_dtype(peak: Optional[int], given: Optional[torch.dtype], name: str):
+    """(dtype, peak) of the samples of a kernel call: ``peak`` None or 255 with 8-bit tensors is the 8-bit kernel; a peak in
+    1 .. 65535 beyond that (or any peak with uint16 tensors, which need one) is the 16-bit kernel."""
+    if peak is not None and (isinstance(peak, bool) or not isinstance(peak, int) or not 1 <= peak <= 65535):
+        raise ValueError(f"{name}: peak must be an integer in 1 .. 65535, got {peak!r}")
+    if given is None:
+        given = torch.uint8 if peak in (None, 255) else torch.uint16
+    if given == torch.uint8:
+        if peak not in (None, 255):
+            raise ValueError(f"{name}: 8-bit samples have the peak 255, got {peak}")
+        return torch.uint8, 255
+    if given == torch.uint16:
+        if peak is None:
+            raise ValueError(f"{name}: uint16 samples need their peak (2**depth - 1)")
+        return torch.uint16, peak
+    raise ValueError(f"{name}: uint8 or uint16 samples expected, got {given}")
+
+
 def finish_frames(out: torch.Tensor, H: int, W: int, gt: Optional[torch.Tensor] = None, crop: int = 4, mode: str = "trunc",
-                  dst: Optional[torch.Tensor] = None):
+                  dst: Optional[torch.Tensor] = None, peak: int = 255):
     """out: the fp32 output of a chunk, [K,1,>=4H,>=4W] or [K,>=4H,>=4W] with contiguous rows (the padded tensor, read in place)
     -> (u8 [K,4H,4W], sse): clamp to [0,1] (NaN -> 0), fp32 * 255, truncation (``mode="trunc"``, the reference's writer) or
     round-to-nearest-even (``"nearest"``).  With ``gt`` (uint8 [K,Hgt,Wgt], device) sse is the int64 [K] sum of (u8 - gt)^2 over the
     common min(4H, Hgt) x min(4W, Wgt) less ``crop`` border pixels, exact; else None.  ``dst``: an optional dense uint8 [K,4H,4W]
-    destination."""
+    destination.  ``peak``: 255 with uint8 ``dst`` / ``gt`` (or neither) is the call above; any other peak in 1 .. 65535, or uint16
+    ``dst`` / ``gt``, multiplies by the peak and gives uint16 frames (cdfo_finish_frames_u16)."""
+    given = dst.dtype if dst is not None else gt.dtype if gt is not None else None
+    kind, peak = sample_dtype(peak, given, "finish_frames")
+    wide = kind == torch.uint16
+    frames_of = u16_frames if wide else u8_frames
     if mode not in QUANT_MODES:
         raise ValueError(f"finish_frames: mode must be one of {sorted(QUANT_MODES)}, got {mode!r}")
     if out.dim() == 4 and out.shape[1] == 1:
@@ -629,50 +662,63 @@ def finish_frames(out: torch.Tensor, H: int, W: int, gt: Optional[torch.Tensor] 
                          f"{tuple(out.shape)} strides {out.stride()}")
     K = int(out.shape[0])
     if dst is None:
-        dst = torch.empty((K, Ho, Wo), dtype=torch.uint8, device=out.device)
-    elif dst.dtype != torch.uint8 or tuple(dst.shape) != (K, Ho, Wo) or not dst.is_contiguous() or dst.device != out.device:
-        raise ValueError(f"finish_frames: dst must be a dense uint8 [{K},{Ho},{Wo}] tensor on out's device")
+        dst = torch.empty((K, Ho, Wo), dtype=kind, device=out.device)
+    elif dst.dtype != kind or tuple(dst.shape) != (K, Ho, Wo) or not dst.is_contiguous() or dst.device != out.device:
+        raise ValueError(f"finish_frames: dst must be a dense {kind} [{K},{Ho},{Wo}] tensor on out's device")
     part, nb = None, C.c_int(0)
     g = gp = gs = gh = gw = None
     if gt is not None:
-        g, n, gh, gw, gp, gs = u8_frames(gt, "finish_frames: gt")
+        g, n, gh, gw, gp, gs = frames_of(gt, "finish_frames: gt")
         if n != K or g.device != out.device:
             raise ValueError(f"finish_frames: gt must hold one frame per output frame (K = {K}) on out's device, got {n}")
         part = torch.empty((K, 1024), dtype=torch.int64, device=out.device)
     with on_device(out):
-        check(_lib.lib().cdfo_finish_frames(_vp(out), int(out.stride(1)), C.c_longlong(out.stride(0)), K, Ho, Wo, _vp(dst),
-                                            QUANT_MODES[mode], _vp(g), gp or 0, C.c_longlong(gs or 0), gh or 0, gw or 0, int(crop),
-                                            _vp(part), 0 if part is None else part.numel(), C.byref(nb), _stream()),
-              "cdfo_finish_frames")
+        src = (_vp(out), int(out.stride(1)), C.c_longlong(out.stride(0)), K, Ho, Wo, _vp(dst))
+        rest = (QUANT_MODES[mode], _vp(g), gp or 0, C.c_longlong(gs or 0), gh or 0, gw or 0, int(crop), _vp(part),
+                0 if part is None else part.numel(), C.byref(nb), _stream())
+        if wide:
+            check(_lib.lib().cdfo_finish_frames_u16(*src, peak, *rest), "cdfo_finish_frames_u16")
+        else:
+            check(_lib.lib().cdfo_finish_frames(*src, *rest), "cdfo_finish_frames")
     if part is None:
         return dst, None
     # the kernel packs its partial sums as [K][nblocks]; integers, so the sum is exact in any order
     return dst, part.view(-1)[:K * nb.value].view(K, nb.value).sum(dim=1)
 
 
-def chroma_up4(src: torch.Tensor, gt: Optional[torch.Tensor] = None, crop: int = 2, dst: Optional[torch.Tensor] = None):
+def chroma_up4(src: torch.Tensor, gt: Optional[torch.Tensor] = None, crop: int = 2, dst: Optional[torch.Tensor] = None,
+               peak: Optional[int] = None):
     """src: 8-bit planes [N,h,w] (or [h,w]) on the device with contiguous rows, read in place (pitch and plane stride may exceed the
     plane) -> (u8 [N,4h,4w], sse): the centre-aligned x4 cubic of include/cdfo_hip.h, in integers, bit-exact against its numpy
     statement.  With ``gt`` (uint8 [N,Hgt,Wgt], device) sse is the int64 [N] sum of (u8 - gt)^2 over the common min(4h, Hgt) x
-    min(4w, Wgt) less ``crop`` border pixels, exact; else None.  ``dst``: an optional dense uint8 [N,4h,4w] destination."""
-    s, N, h, w, sp, ss = u8_frames(src, "chroma_up4: src")
+    min(4w, Wgt) less ``crop`` border pixels, exact; else None.  ``dst``: an optional dense uint8 [N,4h,4w] destination.
+    uint16 planes (``src``, ``gt``, ``dst`` alike) need ``peak``, 2**depth - 1: the same filter clamped to [0, peak]
+    (cdfo_chroma_up4_u16)."""
+    kind, peak = sample_dtype(peak, src.dtype, "chroma_up4")
+    wide = kind == torch.uint16
+    frames_of = u16_frames if wide else u8_frames
+    s, N, h, w, sp, ss = frames_of(src, "chroma_up4: src")
     if h <= 0 or w <= 0 or N <= 0:
         raise ValueError(f"chroma_up4: src holds no pixels: {tuple(s.shape)}")
     if dst is None:
-        dst = torch.empty((N, 4 * h, 4 * w), dtype=torch.uint8, device=s.device)
-    elif dst.dtype != torch.uint8 or tuple(dst.shape) != (N, 4 * h, 4 * w) or not dst.is_contiguous() or dst.device != s.device:
-        raise ValueError(f"chroma_up4: dst must be a dense uint8 [{N},{4 * h},{4 * w}] tensor on src's device")
+        dst = torch.empty((N, 4 * h, 4 * w), dtype=kind, device=s.device)
+    elif dst.dtype != kind or tuple(dst.shape) != (N, 4 * h, 4 * w) or not dst.is_contiguous() or dst.device != s.device:
+        raise ValueError(f"chroma_up4: dst must be a dense {kind} [{N},{4 * h},{4 * w}] tensor on src's device")
     part, nb = None, C.c_int(0)
     g = gp = gs = gh = gw = None
     if gt is not None:
-        g, n, gh, gw, gp, gs = u8_frames(gt, "chroma_up4: gt")
+        g, n, gh, gw, gp, gs = frames_of(gt, "chroma_up4: gt")
         if n != N or g.device != s.device:
             raise ValueError(f"chroma_up4: gt must hold one plane per source plane (N = {N}) on src's device, got {n}")
         part = torch.empty((N, 1024), dtype=torch.int64, device=s.device)
     with on_device(s):
-        check(_lib.lib().cdfo_chroma_up4(_vp(s), sp, C.c_longlong(ss), N, h, w, _vp(dst), _vp(g), gp or 0, C.c_longlong(gs or 0),
-                                         gh or 0, gw or 0, int(crop), _vp(part), 0 if part is None else part.numel(), C.byref(nb),
-                                         _stream()), "cdfo_chroma_up4")
+        planes = (_vp(s), sp, C.c_longlong(ss), N, h, w, _vp(dst))
+        rest = (_vp(g), gp or 0, C.c_longlong(gs or 0), gh or 0, gw or 0, int(crop), _vp(part), 0 if part is None else part.numel(),
+                C.byref(nb), _stream())
+        if wide:
+            check(_lib.lib().cdfo_chroma_up4_u16(*planes, peak, *rest), "cdfo_chroma_up4_u16")
+        else:
+            check(_lib.lib().cdfo_chroma_up4(*planes, *rest), "cdfo_chroma_up4")
     if part is None:
         return dst, None
     # the kernel packs its partial sums as [N][nblocks]; integers, so the sum is exact in any order

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .kernels import _stream, _vp, on_device, u8_frames
+from .kernels import _stream, _vp, on_device, u8_frames, u16_frames
 
 
 def _partials(a: torch.Tensor, b: torch.Tensor, crop: int, metric: int, from_unit_range: bool, round8: bool):
@@ -63,12 +63,14 @@ def common_size(h1: int, w1: int, h2: int, w2: int):
     return min(h1, h2), min(w1, w2)
 
 
-def psnr_from_sse(sse, n: int) -> np.ndarray:
+def psnr_from_sse(sse, n: int, peak: int = 255) -> np.ndarray:
     """fp64 [N] PSNR from integer sums of squared differences over n pixels each: calculate_psnr's arithmetic on the host
-    (mse = sum / n in fp64; inf where it is 0, else 20 log10(255 / sqrt(mse)))."""
+    (mse = sum / n in fp64; inf where it is 0, else 20 log10(255 / sqrt(mse))).  ``peak``: the samples' largest value, 2**depth - 1,
+    in place of 255."""
     mse = np.asarray(sse, dtype=np.int64).astype(np.float64).reshape(-1) / n
+    peak = float(peak)
     # frame by frame on numpy scalars: the very expression of calculate_psnr
-    return np.array([np.inf if m == 0 else 20.0 * np.log10(255.0 / np.sqrt(m)) for m in mse], dtype=np.float64)
+    return np.array([np.inf if m == 0 else 20.0 * np.log10(peak / np.sqrt(m)) for m in mse], dtype=np.float64)
 
 
 def _partials_u8(a: torch.Tensor, b: torch.Tensor, crop: int, metric: int):
@@ -103,3 +105,23 @@ def ssim_u8(img1: torch.Tensor, img2: torch.Tensor, crop_border: int = 4) -> tor
     """Per-frame SSIM of uint8 [N,H,W] device stacks over their common size (fp64 device tensor [N])."""
     s, Hc, Wc = _partials_u8(img1, img2, crop_border, 1)
     return s / float((Hc - 10) * (Wc - 10))
+
+
+def ssim_u16(img1: torch.Tensor, img2: torch.Tensor, crop_border: int, peak: int) -> torch.Tensor:
+    """`ssim_u8` for uint16 [N,H,W] device stacks of samples in 0 .. ``peak`` (2**depth - 1): C1 = (0.01 peak)^2, C2 = (0.03 peak)^2.
+    There is no ``sse_u16``: the sums of squares come, as integers, from ``kernels.finish_frames`` and ``kernels.chroma_up4``."""
+    if isinstance(peak, bool) or not isinstance(peak, int) or not 1 <= peak <= 65535:
+        raise ValueError(f"ssim_u16: peak must be an integer in 1 .. 65535, got {peak!r}")
+    a, N, Ha, Wa, pa, sa = u16_frames(img1, "img1")
+    b, Nb, Hb, Wb, pb, sb = u16_frames(img2, "img2")
+    if N != Nb or a.device != b.device:
+        raise ValueError(f"the two stacks must hold the same number of frames on one device, got {N} and {Nb}")
+    part = torch.empty((N, 1024), dtype=torch.float64, device=a.device)
+    nb = C.c_int(0)
+    with on_device(a):
+        _lib.check(_lib.lib().cdfo_ssim_partials_u16(_vp(a), pa, C.c_longlong(sa), Ha, Wa, _vp(b), pb, C.c_longlong(sb), Hb, Wb, N,
+                                                     int(crop_border), peak, _vp(part), part.numel(), C.byref(nb), _stream()),
+                   "cdfo_ssim_partials_u16")
+    Hm, Wm = common_size(Ha, Wa, Hb, Wb)
+    s = part.view(-1)[:N * nb.value].view(N, nb.value).sum(dim=1)
+    return s / float((Hm - 2 * crop_border - 10) * (Wm - 2 * crop_border - 10))

@@ -5,7 +5,8 @@ by frame with ``cv2.imread(path, 0)`` and ``np.load``.  Here a sequence is read 
 (``:24-26``) and the seven-frame window gathering happen on the device.
 
 ``cv2`` is not available in this image, so the PNG decoder is a small stdlib one (zlib + the five PNG row filters) for
-the formats the data set uses: 8-bit greyscale (colour type 0; an alpha channel is dropped), non-interlaced.
+the formats the data set uses: 8-bit greyscale (colour type 0; an alpha channel is dropped), non-interlaced; and 16-bit greyscale
+of the same kinds (samples big-endian in the file, uint16 here), which a decoder at 10 or more bits writes its unfiltered planes as.
 
 Directory layout and the reference's naming (``test_LD_22_FPS.py:143-170``):
     <lr_dir>/<any sorted file names>.png                      LR luma frames, index i = position in the sorted list
@@ -26,7 +27,7 @@ _SIG = b"\x89PNG\r\n\x1a\n"
 
 
 def read_gray_png(path: str) -> np.ndarray:
-    """8-bit greyscale PNG -> uint8 [H,W] (what ``cv2.imread(path, 0)`` returns for such a file)."""
+    """8-bit greyscale PNG -> uint8 [H,W] (what ``cv2.imread(path, 0)`` returns for such a file); 16-bit greyscale -> uint16 [H,W]."""
     data = open(path, "rb").read()
     if data[:8] != _SIG:
         raise ValueError(f"{path}: not a PNG file")
@@ -44,10 +45,10 @@ def read_gray_png(path: str) -> np.ndarray:
     if hdr is None:
         raise ValueError(f"{path}: no IHDR chunk")
     W, H, depth, ctype, _, _, interlace = hdr
-    if depth != 8 or ctype not in (0, 4) or interlace:
-        raise NotImplementedError(f"{path}: only 8-bit non-interlaced greyscale PNGs are supported "
+    if depth not in (8, 16) or ctype not in (0, 4) or interlace:
+        raise NotImplementedError(f"{path}: only 8- and 16-bit non-interlaced greyscale PNGs are supported "
                                   f"(bit depth {depth}, colour type {ctype}, interlace {interlace})")
-    bpp = 1 if ctype == 0 else 2
+    bpp = (1 if ctype == 0 else 2) * (depth // 8)          # the filters run over bytes, a pixel apart
     raw = np.frombuffer(zlib.decompress(b"".join(idat)), dtype=np.uint8)
     stride = W * bpp
     if raw.size != H * (stride + 1):
@@ -85,38 +86,47 @@ def read_gray_png(path: str) -> np.ndarray:
             raise ValueError(f"{path}: bad filter type {f} in row {y}")
         out[y] = cur
         prev = cur
+    if depth == 16:                                        # big-endian samples; with alpha, every second one
+        return out.view(">u2")[:, ::bpp // 2].astype(np.uint16)
     return out[:, ::bpp].copy() if bpp == 2 else out
 
 
 def write_gray_png(path: str, img: np.ndarray, filter_type: int = 0, level: int = 6) -> None:
     """uint8 [H,W] -> 8-bit greyscale PNG with every row filtered by ``filter_type`` (0-4), deflated at zlib ``level``.  Filter 0
-    (the default, what the evaluation loop writes) is one array operation; the other filters, for tests and tools, go row by row."""
-    img = np.ascontiguousarray(img, dtype=np.uint8)
-    H, W = img.shape
+    (the default, what the evaluation loop writes) is one array operation; the other filters, for tests and tools, go row by row.
+    uint16 [H,W] -> a 16-bit greyscale PNG: the same over the rows' big-endian bytes, a pixel two bytes apart."""
+    depth = 16 if np.asarray(img).dtype == np.uint16 else 8
+    if depth == 16:
+        H, W = img.shape
+        img = np.ascontiguousarray(img, dtype=">u2").view(np.uint8)      # [H, 2W] bytes
+    else:
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        H, W = img.shape
     if filter_type == 0:
-        packed = np.zeros((H, W + 1), dtype=np.uint8)           # each row: its filter byte (0), then the pixels
+        packed = np.zeros((H, img.shape[1] + 1), dtype=np.uint8)    # each row: its filter byte (0), then the pixels
         packed[:, 1:] = img
         raw = packed.tobytes()
     else:
-        raw = _filtered_rows(img, filter_type)
+        raw = _filtered_rows(img, filter_type, depth // 8)
 
     def chunk(kind, body):
         return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
 
     with open(path, "wb") as f:
-        f.write(_SIG + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 0, 0, 0, 0)) +
+        f.write(_SIG + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, depth, 0, 0, 0, 0)) +
                 chunk(b"IDAT", zlib.compress(raw, level)) + chunk(b"IEND", b""))
 
 
-def _filtered_rows(img: np.ndarray, filter_type: int) -> bytes:
-    """The rows of `img` under PNG filter 1-4 (Sub, Up, Average, Paeth), each behind its filter byte."""
+def _filtered_rows(img: np.ndarray, filter_type: int, bpp: int = 1) -> bytes:
+    """The rows of `img` (bytes, a pixel ``bpp`` of them apart) under PNG filter 1-4 (Sub, Up, Average, Paeth), each behind its
+    filter byte."""
     H, W = img.shape
     rows = bytearray()
     prev = np.zeros(W, dtype=np.int32)
     for y in range(H):
         cur = img[y].astype(np.int32)
-        left = np.concatenate([[0], cur[:-1]])
-        ul = np.concatenate([[0], prev[:-1]])
+        left = np.concatenate([[0] * bpp, cur[:-bpp]])
+        ul = np.concatenate([[0] * bpp, prev[:-bpp]])
         if filter_type == 1:
             enc = cur - left
         elif filter_type == 2:
@@ -134,17 +144,28 @@ def _filtered_rows(img: np.ndarray, filter_type: int) -> bytes:
     return bytes(rows)
 
 
-def load_priors(side_dir: str, T: int, shape=None) -> Dict[str, np.ndarray]:
-    """The coding priors of a sequence of T frames: pms, ufs uint8 [T,H,W]; rms [T,H,W] (dtype of the ``*_res.npy`` files); mvl0,
-    mvl1 [T,H,W,3].  Entry 0 (which the reference never reads: ``ii = max(1, i)``) repeats entry 1.  ``shape``: the (T,H,W) of the
-    LR frames the planes must have, else ValueError."""
+def load_priors(side_dir: str, T: int, shape=None, depth: int = 8) -> Dict[str, np.ndarray]:
+    """The coding priors of a sequence of T frames: pms uint8, ufs uint8 or (16-bit PNGs) uint16 [T,H,W]; rms [T,H,W] (dtype of the
+    ``*_res.npy`` files); mvl0, mvl1 [T,H,W,3].  Entry 0 (which the reference never reads: ``ii = max(1, i)``) repeats entry 1.  ``shape``: the (T,H,W) of the
+    LR frames the planes must have, else ValueError.  ``depth``: the bit depth of the sequence's samples; the unfiltered planes must
+    be 8-bit PNGs at depth 8 and 16-bit PNGs above it, and the partition maps 8-bit at every depth, else ValueError (a plane of the
+    wrong depth would be divided by the wrong peak without a sound)."""
 
     def per_frame(fn):
         items = [fn("%05d" % max(1, t)) for t in range(T)] if T > 1 else [fn("%05d" % 1)]
         return np.stack(items)
 
-    pms = per_frame(lambda i: read_gray_png(os.path.join(side_dir, "part_m", i + "_M_mask.png")))
-    ufs = per_frame(lambda i: read_gray_png(os.path.join(side_dir, "unfiltered", i + "_unflt.png")))
+    def png(part, suffix, want, what):                   # every file on its own: stacking would widen a stray 8-bit plane
+        def read(i):
+            img = read_gray_png(os.path.join(side_dir, part, i + suffix))
+            if img.dtype != want:
+                raise ValueError(f"{os.path.join(side_dir, part, i + suffix)}: a {8 * img.dtype.itemsize}-bit PNG; {what}")
+            return img
+        return per_frame(read)
+
+    pms = png("part_m", "_M_mask.png", np.uint8, "partition maps are 8-bit masks at every depth")
+    ufs = png("unfiltered", "_unflt.png", np.uint8 if depth == 8 else np.uint16,
+              f"the unfiltered planes of a sequence of {depth}-bit samples are {'8' if depth == 8 else '16'}-bit PNGs")
     rms = per_frame(lambda i: np.load(os.path.join(side_dir, "res", i + "_res.npy"))[:, :, 0])
     mvl0 = per_frame(lambda i: np.load(os.path.join(side_dir, "mvl0", i + "_mvl0.npy")))
     mvl1 = per_frame(lambda i: np.load(os.path.join(side_dir, "mvl1", i + "_mvl1.npy")))
@@ -163,4 +184,7 @@ def load_sequence(lr_dir: str, side_dir: str) -> Dict[str, np.ndarray]:
     if not names:
         raise FileNotFoundError(f"no PNG frames in {lr_dir}")
     lr = np.stack([read_gray_png(os.path.join(lr_dir, n)) for n in names])
+    if lr.dtype != np.uint8:
+        raise NotImplementedError(f"{lr_dir}: only 8-bit LR frames are supported in the PNG layout, these are {lr.dtype} "
+                                  f"(high bit depth goes through raw files: cdfo_amd/yuv.py)")
     return dict(lr=lr, **load_priors(side_dir, len(names), lr.shape))

@@ -150,13 +150,17 @@ class StreamingSR:
     gumbel_uniform: injected noise per step (T entries of six draws); frame_noise: injected noise per frame (T tensors
     [1,64,Hp,Wp]), read by ``run_chunked(share_compensation=True)`` only.
 
+    peak: the largest sample of lr, rms and ufs, 2**depth - 1 (255: 8-bit files).  The three are divided by it, and pms, a mask that is
+    8-bit at every depth, by 255: true fp32 divisions, so a sequence and its samples times 257 at peak 65535 give the same planes.
+
     Deliberate deviations from the reference loop: the sequence is device resident and windows are gathered by index;
     `run_chunked` extracts each frame once (same arithmetic per output frame); ``run_chunked(share_compensation=True)`` -- opt-in
     -- also compensates each neighbour frame once, with one Gumbel draw per frame where the reference draws per (step, slot).
     """
 
     def __init__(self, model, lr, pms, rms, ufs, mvl0, mvl1, device: Optional[torch.device] = None,
-                 gumbel_uniform: Optional[Sequence] = None, use_graph: bool = False, frame_noise: Optional[Sequence] = None):
+                 gumbel_uniform: Optional[Sequence] = None, use_graph: bool = False, frame_noise: Optional[Sequence] = None,
+                 peak: int = 255):
         dev = torch.device(device) if device is not None else next(model.parameters()).device
         if dev.type != "cuda":
             raise NotImplementedError("StreamingSR needs the model on a GPU (HIP path, no CPU fallback)")
@@ -166,12 +170,20 @@ class StreamingSR:
         self.T, self.H, self.W = int(lr.shape[0]), int(lr.shape[1]), int(lr.shape[2])
         self.Hp, self.Wp = (self.H + 7) // 8 * 8, (self.W + 7) // 8 * 8
 
-        def plane(t):                        # [T,H,W] file units -> float32 / 255, zero padded
+        if isinstance(peak, bool) or not isinstance(peak, int) or not 1 <= peak <= 65535:
+            raise ValueError(f"peak must be an integer in 1 .. 65535, got {peak!r}")
+        self.peak = peak
+        # the divisors are device tensors: with a host scalar torch's device kernel multiplies by the rounded reciprocal, which is
+        # not the correctly rounded quotient the reference's CPU `/ 255.0` (test_LD_37.py:27) and the oracle loop give
+        mask_peak, sample_peak = (torch.tensor(p, dtype=torch.float32, device=dev) for p in (255.0, float(peak)))
+
+        def plane(t, divisor):               # [T,H,W] file units -> float32 / divisor, zero padded
             out = torch.zeros((self.T, self.Hp, self.Wp), dtype=torch.float32, device=dev)
-            out[:, :self.H, :self.W] = as_dev(t).to(torch.float32) / 255.0
+            out[:, :self.H, :self.W] = as_dev(t).to(torch.float32) / divisor
             return out
 
-        self.lr, self.pms, self.rms, self.ufs = plane(lr), plane(pms), plane(rms), plane(ufs)
+        self.lr, self.pms = plane(lr, sample_peak), plane(pms, mask_peak)
+        self.rms, self.ufs = plane(rms, sample_peak), plane(ufs, sample_peak)
         self.mvl0, self.mvl1 = as_dev(mvl0), as_dev(mvl1)
         self.noise = gumbel_uniform
         self.frame_noise = frame_noise

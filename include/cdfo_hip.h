@@ -592,6 +592,28 @@ int cdfo_chroma_up4(const unsigned char* src, int src_pitch, long long src_pstri
                     const unsigned char* gt, int gt_pitch, long long gt_pstride, int Hgt, int Wgt, int crop, long long* partial,
                     int partial_cap, int* nblocks_out, void* stream);
 
+/* ---- high-bit-depth samples (finish.hip, chroma.hip; evaluate_yuv at 10, 12 and 16 bits) ----
+ * The three kernels above on 16-bit samples (unsigned short, the value in the low bits) of a peak of 1 .. 65535 (2^depth - 1; else
+ * CDFO_EINVAL).  Pitches and strides are in SAMPLES, sample pointers 2-byte aligned, destinations 16-byte aligned (else CDFO_EALIGN);
+ * the 32-bit-offset guards and the partial / nblocks_out contracts are their 8-bit twins'.
+ * cdfo_finish_frames_u16: cdfo_finish_frames with `x peak` for `x 255`: clamp to [0,1] (NaN -> 0), one correctly rounded fp32 multiply
+ *                     by (float)peak, truncation or round to nearest even; Wo % 4 == 0, so a row is at least 8 bytes.  gt != NULL: the
+ *                     sum of (u16 - gt)^2 as exact 64-bit integers (one square reaches 65535^2 > 2^31: squared unsigned).
+ * cdfo_ssim_partials_u16: metric 1 of cdfo_metric_partials_u8 (the sum of the SSIM map, fp64 partials [N][*nblocks_out]) with
+ *                     C1 = (0.01 peak)^2, C2 = (0.03 peak)^2 in fp64.  There is no metric 0: fp64 partial sums of squares are not
+ *                     exact at 16 bits, the two kernels beside it give that sum in integers.
+ * cdfo_chroma_up4_u16: cdfo_chroma_up4 with clamp((v + 8192) >> 14, 0, peak); the 32-bit sums hold up to 16 bits
+ *                     (|v| <= 65535 * 158^2 = 1 636 015 740 < 2^31 - 8192). */
+int cdfo_finish_frames_u16(const float* src, int src_pitch, long long src_fstride, int K, int Ho, int Wo, unsigned short* dst, int peak,
+                           int mode, const unsigned short* gt, int gt_pitch, long long gt_fstride, int Hgt, int Wgt, int crop,
+                           long long* partial, int partial_cap, int* nblocks_out, void* stream);
+int cdfo_ssim_partials_u16(const unsigned short* a, int a_pitch, long long a_fstride, int Ha, int Wa, const unsigned short* b,
+                           int b_pitch, long long b_fstride, int Hb, int Wb, int N, int crop, int peak, double* partial,
+                           int partial_cap, int* nblocks_out, void* stream);
+int cdfo_chroma_up4_u16(const unsigned short* src, int src_pitch, long long src_pstride, int N, int h, int w, unsigned short* dst,
+                        int peak, const unsigned short* gt, int gt_pitch, long long gt_pstride, int Hgt, int Wgt, int crop,
+                        long long* partial, int partial_cap, int* nblocks_out, void* stream);
+
 /* ---- optional per-launch HIP-event timing on the launch stream (bench.py's live roofline figures) ----------- */
 int cdfo_prof_begin(int max_records);
 int cdfo_prof_end(int* launches, double* ms, double* flops, double* bytes, int nkid);

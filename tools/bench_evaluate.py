@@ -3,6 +3,7 @@
     python tools/bench_evaluate.py [--size T H W] [--chunk K] [--repeats R]     sequence benchmark
     python tools/bench_evaluate.py --ssim [--frames N]                          the two SSIM kernels at 1080 x 1920
     python tools/bench_evaluate.py --yuv [--size T H W] [--chunk K] [--repeats R]    the PNG path against the raw 4:2:0 path
+    python tools/bench_evaluate.py --yuv --pix-fmt NAME [--size T H W] ...           evaluate_yuv at NAME against 8-bit yuv420p
 
 Sequence benchmark, one process, one warm-up pass then R passes each, medians: run_chunked alone; evaluate_sequence with metrics
 only; with metrics and PNG writing at 8 and 16 workers; and the per-chunk times of the finish kernel and the two 8-bit metric
@@ -10,7 +11,9 @@ kernels from events.  --ssim: the separable 8-bit SSIM kernel (cdfo_metric_parti
 on fp32 copies of the same frames, median of five.  --yuv: the same synthetic content once in the PNG layout and once as I420
 files; run_chunked alone, then evaluate_sequence and evaluate_yuv end to end, metrics only and with the result written (the baseline
 is the PNG path of this very run); the time the priors' PNGs and NPYs take to read, which both paths pay before their first chunk;
-and chroma_up4 per chunk from events."""
+and chroma_up4 per chunk from events.  --yuv --pix-fmt NAME (a format of cdfo_amd/yuv.py): evaluate_yuv with metrics and the result
+file, on 8-bit yuv420p and on NAME in the same process (the 8-bit run is the baseline), then the three 16-bit kernels against their
+8-bit twins on one chunk of 1080 x 1920 frames, from events."""
 import os
 import sys
 import tempfile
@@ -160,5 +163,60 @@ def yuv():
               f"({33 * mb / with_gt:.1f} GB/s)", flush=True)
 
 
+def pix_fmt():
+    from arch.SIDECVSR_our import CVSR_V8
+    from cdfo_amd import kernels as K
+    from cdfo_amd import metrics as M
+    from cdfo_amd.evaluate import evaluate_yuv, write_synthetic_sequence_yuv
+    from cdfo_amd.yuv import parse_pix_fmt
+    fmt = parse_pix_fmt(sys.argv[sys.argv.index("--pix-fmt") + 1])
+    T, H, W = _arg("--size", 3, [64, 270, 480])
+    chunk, reps = _arg("--chunk", 1, 8), _arg("--repeats", 1, 5)
+    model = CVSR_V8().cuda().eval()
+    with tempfile.TemporaryDirectory() as tmp:
+        base = None
+        for name in ("yuv420p", fmt.name):
+            lr, side, gt = write_synthetic_sequence_yuv(os.path.join(tmp, name), T, H, W, pix_fmt=name)
+            out = os.path.join(tmp, name + ".yuv")
+            run = lambda: evaluate_yuv(model, lr, W, H, side, gt_yuv=gt, save_yuv=out, chunk=chunk, pix_fmt=name)
+            run()
+            rs = [run() for _ in range(reps)]
+            tot, fwd = [r.frames / r.seconds_total for r in rs], [r.frames / r.seconds_forward for r in rs]
+            med = float(np.median(tot))
+            base = med if base is None else base
+            print(f"evaluate_yuv, {name}, metrics + file, {T} frames {H}x{W}, chunk {chunk}: forward-only frames/s median "
+                  f"{np.median(fwd):.2f}; end to end per pass {' '.join('%.2f' % f for f in tot)}; median {med:.2f} (spread "
+                  f"{100 * (max(tot) - min(tot)) / med:.2f} %; {med / base:.4f} of the 8-bit run)", flush=True)
+    if fmt.sample_bytes == 1:
+        return
+    # the three kernels and their 8-bit twins on one chunk of 1080 x 1920 frames (270 x 480 LR), from events
+    h, w, peak = 270, 480, fmt.peak
+    src = torch.rand((chunk, 1, 4 * ((h + 7) // 8 * 8), 4 * w), device="cuda") * 1.2 - 0.1
+    frames = lambda n, hh, ww, top, kind: torch.from_numpy(
+        np.random.RandomState(n + hh).randint(0, top + 1, (n, hh, ww)).astype(kind)).cuda()
+    gt8, gt16 = frames(chunk, 4 * h, 4 * w, 255, np.uint8), frames(chunk, 4 * h, 4 * w, peak, np.uint16)
+    c8, c16 = frames(2 * chunk, h // 2, w // 2, 255, np.uint8), frames(2 * chunk, h // 2, w // 2, peak, np.uint16)
+    gc8, gc16 = frames(2 * chunk, 2 * h, 2 * w, 255, np.uint8), frames(2 * chunk, 2 * h, 2 * w, peak, np.uint16)
+    y8, _ = K.finish_frames(src, h, w, gt=gt8)
+    y16, _ = K.finish_frames(src, h, w, gt=gt16, peak=peak)
+    d8, _ = K.chroma_up4(c8, gt=gc8)
+    d16, _ = K.chroma_up4(c16, gt=gc16, peak=peak)
+    pairs = (("finish_frames with the squared-difference sum", "8/6", lambda: K.finish_frames(src, h, w, gt=gt8, dst=y8),
+              lambda: K.finish_frames(src, h, w, gt=gt16, dst=y16, peak=peak)),
+             ("chroma_up4 with the squared-difference sum", "2", lambda: K.chroma_up4(c8, gt=gc8, dst=d8),
+              lambda: K.chroma_up4(c16, gt=gc16, dst=d16, peak=peak)),
+             ("SSIM", "about 1 (fp64 compute)", lambda: M.ssim_u8(y8, gt8, 4), lambda: M.ssim_u16(y16, gt16, 4, peak)))
+    for label, ratio, f8, f16 in pairs:
+        (m8, a8), (m16, a16) = _median_ms(f8), _median_ms(f16)
+        print(f"{label}, chunk of {chunk} frames 1080x1920 (wrapper included), median of 5: 8-bit {m8:.3f} ms (passes "
+              f"{' '.join('%.3f' % x for x in a8)}), 16-bit at peak {peak} {m16:.3f} ms (passes {' '.join('%.3f' % x for x in a16)}): "
+              f"x{m16 / m8:.3f}, byte ratio {ratio}", flush=True)
+
+
 if __name__ == "__main__":
-    ssim_ab() if "--ssim" in sys.argv else yuv() if "--yuv" in sys.argv else sequence()
+    if "--ssim" in sys.argv:
+        ssim_ab()
+    elif "--yuv" in sys.argv:
+        pix_fmt() if "--pix-fmt" in sys.argv else yuv()
+    else:
+        sequence()

@@ -8,6 +8,7 @@
 
 The last two forms read and write raw 8-bit YUV 4:2:0 (I420) files (cdfo_amd.evaluate.evaluate_yuv): the luma goes through the model,
 the chroma is upsampled x4 on the device, PSNR is reported for Y, U and V.  The ground truth is 4W x 4H unless --gt-size says otherwise.
+--pix-fmt NAME (ffmpeg's names: gray, yuv420p, yuv444p and their 10le / 12le / 16le forms) gives the one format of the three files.
 
 Prints the reference's log line and frames/s, forward only and end to end.  --synthetic writes a random sequence of T frames of
 H x W with 4H x 4W ground truth into a temporary directory and evaluates that (with --weights absent the model is randomly
@@ -38,12 +39,15 @@ def main():
     ap.add_argument("--gt-size", type=int, nargs=2, metavar=("W", "H"))
     ap.add_argument("--out-yuv")
     ap.add_argument("--yuv", action="store_true", help="with --synthetic: write the sequence as I420 files and run evaluate_yuv")
+    ap.add_argument("--pix-fmt", default="yuv420p", help="the format of the raw files (cdfo_amd.yuv.parse_pix_fmt); default yuv420p")
     a = ap.parse_args()
     yuv = a.lr_yuv is not None or a.yuv
     if a.lr_yuv is not None and not (a.size and a.side):
         ap.error("--lr-yuv needs --size W H and --side")
     if a.yuv and a.synthetic is None:
         ap.error("--yuv goes with --synthetic T H W")
+    if a.pix_fmt != "yuv420p" and not yuv:
+        ap.error("--pix-fmt goes with --lr-yuv or --synthetic T H W --yuv")
     if a.synthetic is None and not yuv and not (a.lr and a.side):
         ap.error("--lr and --side, or --lr-yuv, --size and --side, or --synthetic T H W")
     import torch
@@ -59,9 +63,10 @@ def main():
             lr, side, gt, size = a.lr_yuv, a.side, a.gt_yuv, a.size
             if a.synthetic is not None:
                 T, H, W = a.synthetic
-                (lr, side, gt), size = write_synthetic_sequence_yuv(tmp, T, H, W), (W, H)
+                (lr, side, gt), size = write_synthetic_sequence_yuv(tmp, T, H, W, pix_fmt=a.pix_fmt), (W, H)
             r = evaluate_yuv(model, lr, size[0], size[1], side, gt_yuv=gt, save_yuv=a.out_yuv, chunk=a.chunk,
-                             share_compensation=a.share, workers=a.workers, gt_size=tuple(a.gt_size) if a.gt_size else None)
+                             share_compensation=a.share, workers=a.workers, gt_size=tuple(a.gt_size) if a.gt_size else None,
+                             pix_fmt=a.pix_fmt)
         else:
             lr, side, gt = a.lr, a.side, a.gt
             if a.synthetic is not None:
@@ -71,7 +76,11 @@ def main():
     name = a.name or os.path.basename(os.path.normpath(lr if a.synthetic is None else "synthetic"))
     if gt is not None:
         print(format_log_yuv(r, name) if yuv else format_log(r, name))
-    written = ", I420 file written" if yuv and a.out_yuv else ", PNGs written with " + str(a.workers) + " workers" if a.out and not yuv else ""
+    written = ""
+    if yuv and a.out_yuv:
+        written = ", I420 file written" if a.pix_fmt == "yuv420p" else f", {a.pix_fmt} file written"
+    elif a.out and not yuv:
+        written = f", PNGs written with {a.workers} workers"
     print(f"{name}: {r.frames} frames, chunk {a.chunk}{', shared compensation' if a.share else ''}: "
           f"{r.frames / r.seconds_forward:.2f} frames/s forward only, {r.frames / r.seconds_total:.2f} frames/s end to end "
           f"(files read, metrics{written})")
