@@ -4,30 +4,35 @@ The reference, per frame: forward, ``torch.clamp(out,0,1).numpy() * 255.0`` with
 then TRUNCATION), ``cv2.imwrite`` under the LR frame's file name; afterwards ``cal_psnr_ssim`` (psnr_ssim.py:446-484) reads the PNGs back
 and logs the sequence's mean PSNR / SSIM against ``<gt>/%05d.png``, both cropped to (min_height, min_width), border 4.
 
-Here: ``priors.load_sequence`` -> ``StreamingSR.iter_chunked``; per chunk, on the device, ``cdfo_finish_frames`` turns the padded fp32
-chunk output into cropped 8-bit frames and sums the squared differences against the ground truth in the same pass (exact integers),
-``cdfo_metric_partials_u8`` sums the SSIM map of the 8-bit frames; the 8-bit frames then go to the host on a copy stream, ordered by
-events, into one of TWO pinned buffers, and a thread pool encodes the PNGs while the next chunk's forward runs.  The two device 8-bit
-buffers and the two pinned buffers belong to the evaluator and are reused in turn (a buffer is handed out again only after its copy
-has completed and its PNGs are written), so nothing relies on the allocator's stream bookkeeping, no fp32 output frame outlives its
-chunk and the output side's memory does not depend on the sequence's length.  Ground truth comes up the same way: the pool decodes
-the next chunk's files during the current forward into one of two pinned buffers, uploaded as 8-bit without blocking.
+Here one chunk loop, `_run_chunks`, serves ``evaluate_sequence`` (8-bit gray PNG directories, the reference's layout) and
+``evaluate_yuv`` (raw planar files of cdfo_amd/yuv.py: 4:0:0, 4:2:0 and 4:4:4 at 8, 10, 12 or 16 bits, one format for the LR file, the
+ground truth and the result).  The two are adapters: they check their arguments, build a frame SOURCE for the ground truth (frame
+count, plane shapes, sample dtype and peak, and "stage frame t into these numpy views", which runs in the pool: `_PngSource` decodes a
+file, `_YuvSource` copies out of a memory map) and a frame SINK for the result (`_PngSink`: one PNG per frame under the LR file's name,
+in any order; `_YuvSink`: chunks appended to one file in frame order), call the loop and turn its integer sums into PSNR.
 
-``evaluate_yuv`` is the same loop on raw 8-bit YUV 4:2:0 files (cdfo_amd/yuv.py): the luma as above, the two chroma planes upsampled x4
-on the device by ``cdfo_chroma_up4`` without passing through the model, PSNR for Y, U and V, the result appended to an I420 file.
+The loop, per chunk of ``StreamingSR.iter_chunked``, on the device: ``cdfo_finish_frames`` turns the padded fp32 output into cropped
+8- or 16-bit frames and sums the squared differences against the ground truth in the same pass (exact integers), the SSIM kernel sums
+the map of those frames, and the chroma planes, which never pass through the model, are upsampled x4 from the LR file's by
+``cdfo_chroma_up4``, with their sums.  Above 8 bits the buffers are uint16, `StreamingSR` divides by the format's peak 2**depth - 1 and
+the three kernels are their 16-bit forms with that peak.  Every buffer the loop owns exists TWICE
+(`_Slots`) and chunk c works in slot c % 2.  Up: the pool stages chunk c + 1's ground truth into pinned buffers during chunk c's forward,
+from where it is uploaded without blocking; a slot's pinned buffers are staged again only after the event behind that upload.  Down:
+the frames go to the host on a copy stream into pinned buffers and the sink's pool tasks write them while the next forward runs; a
+slot's device buffers are written again only after the event behind that copy, its pinned buffers only after the sink's tasks.  So
+nothing relies on the allocator's stream bookkeeping, no fp32 output frame outlives its chunk, and the memory held does not depend
+on the sequence's length.
 
 Deliberate deviation: ``cal_psnr_ssim`` sends single-channel frames through ``to_y_channel``, an fp32 ``/255*255`` round
 trip, and takes fp32 means.  The metric semantics here are the project's established ones, ``oracle/metrics_ref.py``: fp64 on the
-integers.
-
-``evaluate_yuv(..., pix_fmt=)`` takes the other planar formats of cdfo_amd/yuv.py: 4:0:0, 4:2:0 and 4:4:4 at 8, 10, 12 or 16 bits, one
-format for the LR file, the ground truth and the result.  Above 8 bits the sample buffers are uint16, `StreamingSR` divides by the
-format's peak 2**depth - 1, and the three kernels are their 16-bit forms with that peak."""
+integers."""
 from __future__ import annotations
 
 import concurrent.futures as cf
 import os
+import struct
 import time
+from types import SimpleNamespace
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -80,20 +85,226 @@ def metric_region(h_out: int, w_out: int, h_gt: int, w_gt: int, crop: int):
     return hm, wm, hm - 2 * crop, wm - 2 * crop
 
 
-def _check_workers(workers: int) -> int:
+def _check_args(workers, quantise, chunk) -> Tuple[int, int]:
     if not isinstance(workers, int) or not 1 <= workers <= MAX_WORKERS:
         raise ValueError(f"workers must be an integer between 1 and {MAX_WORKERS}, got {workers!r}")
-    return workers
+    if quantise not in K.QUANT_MODES:
+        raise ValueError(f"quantise must be one of {sorted(K.QUANT_MODES)}, got {quantise!r}")
+    if int(chunk) < 1:
+        raise ValueError(f"chunk >= 1 expected, got {chunk}")
+    return workers, int(chunk)
 
 
-def _frame_names(lr_dir: str) -> List[str]:
-    """The LR frames in `load_sequence`'s order: the result PNGs take these names (test_LD_37.py:180)."""
-    return sorted(n for n in os.listdir(lr_dir) if n.lower().endswith(".png"))
+def _inside(shape, gt_shape, crop: int) -> Tuple[int, int]:
+    """(rows, columns) PSNR runs over: the x4 result of LR planes of ``shape`` against ground truth of ``gt_shape``, less the border."""
+    return metric_region(4 * shape[0], 4 * shape[1], *gt_shape, crop)[2:]
 
 
-def _write_when_copied(done: torch.cuda.Event, path: str, frame: np.ndarray, level: int) -> None:
-    done.synchronize()                      # the chunk's download into the pinned buffer `frame` is a view of
-    write_gray_png(path, frame, 0, level)
+def _check_regions(lr, gt, crop_border: int, ccrop: int) -> None:
+    if min(_inside(lr.shape, gt.shape, crop_border)) <= 10:
+        raise ValueError(f"crop_border {crop_border} leaves no SSIM window in the common {min(4 * lr.shape[0], gt.shape[0])} x "
+                         f"{min(4 * lr.shape[1], gt.shape[1])} of result and ground truth")
+    if lr.chroma_shape is not None and min(_inside(lr.chroma_shape, gt.chroma_shape, ccrop)) <= 0:
+        raise ValueError(f"crop_border {crop_border} leaves nothing of the chroma planes")
+
+
+def _psnr(sse: np.ndarray, shape, gt_shape, crop: int, peak: int) -> np.ndarray:
+    """Per-frame PSNR from the loop's integer sums; empty where it has none (no ground truth, no chroma)."""
+    return M.psnr_from_sse(sse, int(np.prod(_inside(shape, gt_shape, crop))), peak) if len(sse) else np.zeros(0, np.float64)
+
+
+def _mean(a: np.ndarray) -> float:
+    return float(a.sum() / len(a)) if len(a) else float("nan")      # psnr / frames, as the reference accumulates
+
+
+class _PngSource:
+    """A frame source: a directory of 8-bit gray PNGs, frame t in the file ``names[t]`` (by default the directory's PNGs in
+    `load_sequence`'s order).  The plane shape is that of frame 0, read from its header."""
+    chroma_shape, dtype, peak = None, torch.uint8, 255
+
+    def __init__(self, directory: str, names: Optional[List[str]] = None):
+        self.directory = directory
+        self.names = sorted(n for n in os.listdir(directory) if n.lower().endswith(".png")) if names is None else names
+        if not self.names:
+            raise FileNotFoundError(f"no PNG frames in {directory}")
+        self.frames = len(self.names)
+        with open(os.path.join(directory, self.names[0]), "rb") as f:
+            header = f.read(24)
+        if len(header) < 24 or header[12:16] != b"IHDR":
+            raise ValueError(f"{os.path.join(directory, self.names[0])}: not a PNG file")
+        W, H = struct.unpack(">II", header[16:24])
+        self.shape = (H, W)
+
+    def stage(self, t: int, y: np.ndarray) -> None:
+        g = read_gray_png(os.path.join(self.directory, self.names[t]))
+        if g.shape != self.shape:
+            raise ValueError(f"ground-truth frame {t} is {g.shape}, frame 0 is {self.shape}")
+        y[...] = g
+
+
+class _YuvSource:
+    """A frame source: the planes of an open `YuvReader`."""
+
+    def __init__(self, reader: YuvReader):
+        fmt = reader.pix_fmt
+        self.reader, self.frames, self.shape = reader, reader.frames, (reader.height, reader.width)
+        self.chroma_shape = fmt.chroma_shape(reader.height, reader.width)
+        self.dtype, self.peak = torch.uint8 if fmt.sample_bytes == 1 else torch.uint16, fmt.peak
+
+    def stage(self, t: int, y: np.ndarray, u: Optional[np.ndarray] = None, v: Optional[np.ndarray] = None) -> None:
+        """Frame t of the mapped file into its places in a pinned buffer (the page faults of the map happen here, in the pool); u and
+        v None: a 4:0:0 file."""
+        np.copyto(y, self.reader.y(t))
+        if u is not None:
+            np.copyto(u, self.reader.u(t))
+            np.copyto(v, self.reader.v(t))
+
+
+class _PngSink:
+    """A frame sink: frame t as an 8-bit PNG ``<save_dir>/<names[t]>``, one pool task per frame, in any order."""
+
+    def __init__(self, save_dir: str, names: List[str], level: int):
+        os.makedirs(save_dir, exist_ok=True)
+        self.save_dir, self.names, self.level = save_dir, names, level
+
+    def _write(self, copied, path: str, frame: np.ndarray) -> None:
+        copied.synchronize()                    # the chunk's download into the pinned buffer `frame` is a view of
+        write_gray_png(path, frame, 0, self.level)
+
+    def __call__(self, pool, copied, centres, y: np.ndarray, c: Optional[np.ndarray]) -> List[cf.Future]:
+        return [pool.submit(self._write, copied, os.path.join(self.save_dir, self.names[t]), y[j]) for j, t in enumerate(centres)]
+
+
+class _YuvSink:
+    """A frame sink: the chunks appended to a `YuvWriter` in the order they are handed in, one pool task per chunk."""
+
+    def __init__(self, writer: YuvWriter):
+        self.writer, self.last = writer, None
+
+    def _append(self, before: Optional[cf.Future], copied, y: np.ndarray, c: Optional[np.ndarray]) -> None:
+        """Append a chunk (y [k,Ho,Wo]; c [2k,Hc,Wc], its U planes then its V planes; None: 4:0:0) once the chunk before it is in the
+        file and its own download into the pinned buffers `y` and `c` are views of has completed."""
+        if before is not None:
+            before.result()
+        copied.synchronize()
+        k = len(y)
+        for j in range(k):
+            if c is None:
+                self.writer.append(y[j])
+            else:
+                self.writer.append(y[j], c[j], c[k + j])
+
+    def __call__(self, pool, copied, centres, y: np.ndarray, c: Optional[np.ndarray]) -> List[cf.Future]:
+        self.last = pool.submit(self._append, self.last, copied, y, c)
+        return [self.last]
+
+
+class _Slots:
+    """Two alternating sets of buffers with an event each.  Chunk c works in slot c % 2 and records the slot's event behind the
+    asynchronous copy that reads (uploads) or fills (downloads) the slot's buffers; chunk c + 2 may touch them once that event, and
+    whatever the pool still does with them (`futures`), has completed."""
+
+    def __init__(self):
+        self._two = [SimpleNamespace(event=torch.cuda.Event(), futures=[]) for _ in range(2)]
+
+    def __getitem__(self, c: int) -> SimpleNamespace:
+        return self._two[c % 2]
+
+    def add(self, make, **shapes) -> None:
+        """name=(n, plane shape): a buffer ``make((n, *shape))`` of that name in each slot; None where the shape is None (planes this
+        run does not have)."""
+        for slot in self._two:
+            for name, (n, shape) in shapes.items():
+                setattr(slot, name, None if shape is None else make((n, *shape)))
+
+
+def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: int, ccrop: int, quantise: str, workers: int):
+    """The chunk loop of both evaluators.  ``lr``: the LR sequence as a frame source (its counts, shapes, dtype and peak; its frames
+    come from ``load``).  ``load()`` -> (`StreamingSR`, (u, v) LR chroma planes [T,h,w] or None); it runs after the first
+    ground-truth reads have been handed to the pool.  ``gt``: a frame source or None.  ``sink``: a frame sink or None.
+    -> (the `StreamingSR`, sse_y int64 [T], sse_uv int64 [2,T], ssim fp64 [T]); the arrays are empty without ground truth (sse_uv
+    without chroma).  The module's docstring has the order of events."""
+    T, kmax, kind, peak = lr.frames, min(chunk, lr.frames), lr.dtype, lr.peak
+    has_c = lr.chroma_shape is not None
+    out_y, out_c = (shape and (4 * shape[0], 4 * shape[1]) for shape in (lr.shape, lr.chroma_shape))      # None stays None
+    gt_y, gt_c = (gt.shape, gt.chroma_shape) if gt is not None else (None, None)
+    pinned = lambda shape: torch.empty(shape, dtype=kind).pin_memory()
+    with cf.ThreadPoolExecutor(max_workers=workers) as pool:
+        up, down = _Slots(), _Slots()
+        up.add(pinned, gt_y=(kmax, gt_y), gt_c=(2 * kmax, gt_c))
+
+        def stage(c: int) -> List[cf.Future]:
+            """Hand chunk c's ground-truth reads to the pool: they fill the pinned buffers of slot c."""
+            up[c].event.synchronize()                   # chunk c - 2 has left the pinned upload buffers of slot c
+            t0, k = c * chunk, max(0, min(chunk, T - c * chunk))
+            if gt is None or k == 0:
+                return []
+            y, uv = up[c].gt_y.numpy(), up[c].gt_c.numpy() if has_c else None
+            return [pool.submit(gt.stage, t0 + j, y[j], *((uv[j], uv[k + j]) if has_c else ())) for j in range(k)]
+
+        reads = stage(0)
+        s, lr_c = load()
+        dev = s.dev
+        with torch.cuda.device(dev):
+            main, copy = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+            on_dev = lambda shape: torch.empty(shape, dtype=kind, device=dev)
+            up.add(pinned, lr_c=(2 * kmax, lr.chroma_shape))
+            up.add(on_dev, lr_c_dev=(2 * kmax, lr.chroma_shape), gt_y_dev=(kmax, gt_y), gt_c_dev=(2 * kmax, gt_c))
+            down.add(on_dev, y=(kmax, out_y), c=(2 * kmax, out_c))
+            if sink is not None:
+                down.add(pinned, host_y=(kmax, out_y), host_c=(2 * kmax, out_c))
+            sse_y, sse_c, ssim = [], [], []
+            chunks = s.iter_chunked(chunk, share_compensation)
+            for c in range((T + chunk - 1) // chunk):
+                u, d = up[c], down[c]
+                mine, reads = reads, stage(c + 1)       # the next chunk's frames: decoded or copied during this chunk's forward
+                centres, out = next(chunks)
+                k = len(centres)
+                for f in d.futures:                     # chunk c - 2 is out of the pinned result buffers (raises what a writer raised)
+                    f.result()
+                main.wait_event(d.event)                # ... and out of the device result buffers
+                src_c = gy = gc = None
+                if has_c:                               # (stage(c) has seen chunk c - 2 leave this pinned buffer too)
+                    planes = u.lr_c.numpy()
+                    planes[:k], planes[k:2 * k] = (p[centres[0]:centres[0] + k] for p in lr_c)
+                    src_c = u.lr_c_dev[:2 * k]
+                    src_c.copy_(u.lr_c[:2 * k], non_blocking=True)
+                if gt is not None:
+                    for f in mine:
+                        f.result()
+                    gy = u.gt_y_dev[:k]
+                    gy.copy_(u.gt_y[:k], non_blocking=True)
+                    if has_c:
+                        gc = u.gt_c_dev[:2 * k]
+                        gc.copy_(u.gt_c[:2 * k], non_blocking=True)
+                u.event.record(main)                    # the launch stream orders the reuse of the device upload buffers
+                y8, e = K.finish_frames(out, s.H, s.W, gt=gy, crop=crop, mode=quantise, dst=d.y[:k], peak=peak)
+                del out                                 # the chunk's fp32 frames end here
+                c8 = ec = None
+                if has_c:
+                    c8, ec = K.chroma_up4(src_c, gt=gc, crop=ccrop, dst=d.c[:2 * k], peak=peak)
+                if gt is not None:
+                    sse_y.append(e)
+                    if has_c:
+                        sse_c.append(ec.view(2, k))
+                    ssim.append(M.ssim_u8(y8, gy, crop) if kind == torch.uint8 else M.ssim_u16(y8, gy, crop, peak))
+                if sink is not None:
+                    ready = torch.cuda.Event()
+                    ready.record(main)
+                    copy.wait_event(ready)
+                    with torch.cuda.stream(copy):
+                        d.host_y[:k].copy_(y8, non_blocking=True)
+                        if has_c:
+                            d.host_c[:2 * k].copy_(c8, non_blocking=True)
+                        d.event.record(copy)
+                    d.futures = sink(pool, d.event, centres, d.host_y.numpy()[:k], d.host_c.numpy()[:2 * k] if has_c else None)
+            for f in down[0].futures + down[1].futures:
+                f.result()
+            main.wait_stream(copy)
+            host = lambda parts, dim, empty: torch.cat(parts, dim=dim).cpu().numpy() if parts else np.zeros(empty, np.int64)
+            result = (s, host(sse_y, 0, 0), host(sse_c, 1, (2, 0)), host(ssim, 0, 0).astype(np.float64))
+            torch.cuda.synchronize(dev)
+    return result
 
 
 def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] = None, save_dir: Optional[str] = None, chunk: int = 8,
@@ -106,94 +317,24 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
     ``quantise``: "trunc" (the reference's writer) or "nearest".  ``workers``: threads that read ground truth and encode PNGs, at
     most 16.  ``gumbel_uniform`` / ``frame_noise``: injected noise, per step or per frame, as `StreamingSR` takes it; without it the
     default mode draws per forward call, so its frames depend on the chunk size (the shared mode's never do)."""
-    workers = _check_workers(workers)
-    if quantise not in K.QUANT_MODES:
-        raise ValueError(f"quantise must be one of {sorted(K.QUANT_MODES)}, got {quantise!r}")
-    if int(chunk) < 1:
-        raise ValueError(f"chunk >= 1 expected, got {chunk}")
+    workers, chunk = _check_args(workers, quantise, chunk)
     t_start = time.perf_counter()
-    names = _frame_names(lr_dir)
-    T, chunk = len(names), int(chunk)
-    with cf.ThreadPoolExecutor(max_workers=workers) as pool:
-        # ground truth is read a chunk ahead by the pool: chunk c's files are decoded while chunk c - 1's forward runs
-        read_gt = lambda c: [pool.submit(read_gray_png, os.path.join(gt_dir, "%05d.png" % t))
-                             for t in range(c * chunk, min((c + 1) * chunk, T))] if gt_dir is not None else []
-        gt_reads = read_gt(0)
+    lr = _PngSource(lr_dir)
+    gt = sink = None
+    if gt_dir is not None:
+        gt = _PngSource(gt_dir, ["%05d.png" % t for t in range(lr.frames)])
+        _check_regions(lr, gt, crop_border, 0)
+    if save_dir is not None:
+        sink = _PngSink(save_dir, lr.names, png_level)   # the result PNGs take the LR frames' names (test_LD_37.py:180)
+
+    def load():
         seq = load_sequence(lr_dir, side_dir)
-        if save_dir is not None:
-            os.makedirs(save_dir, exist_ok=True)
-        s = StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"], gumbel_uniform=gumbel_uniform,
-                        frame_noise=frame_noise)
-        del seq
-        dev, Ho, Wo, kmax = s.dev, 4 * s.H, 4 * s.W, min(chunk, T)
-        Hgt = Wgt = 0
-        if gt_dir is not None:
-            Hgt, Wgt = gt_reads[0].result().shape
-            if min(metric_region(Ho, Wo, Hgt, Wgt, crop_border)[2:]) <= 10:
-                raise ValueError(f"crop_border {crop_border} leaves no SSIM window in the common {min(Ho, Hgt)} x {min(Wo, Wgt)} of "
-                                 f"result and ground truth")
-        with torch.cuda.device(dev):
-            main, copy = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
-            pinned = lambda h, w: torch.empty((kmax, h, w), dtype=torch.uint8).pin_memory()
-            dev8 = [torch.empty((kmax, Ho, Wo), dtype=torch.uint8, device=dev) for _ in range(2)]
-            host8 = [pinned(Ho, Wo) for _ in range(2)] if save_dir is not None else None
-            copied = [torch.cuda.Event() for _ in range(2)]
-            # the ground truth's way up: two pinned buffers and two device buffers, alternating like the frames' way down
-            gt_host = [pinned(Hgt, Wgt) for _ in range(2)] if gt_dir is not None else None
-            gt_dev = [torch.empty((kmax, Hgt, Wgt), dtype=torch.uint8, device=dev) for _ in range(2)] if gt_dir is not None else None
-            uploaded = [torch.cuda.Event() for _ in range(2)]
-            pending: List[List[cf.Future]] = [[], []]
-            sse, ssim = [], []
-            chunks = s.iter_chunked(chunk, share_compensation)
-            for c in range((T + chunk - 1) // chunk):
-                b = c % 2
-                mine, gt_reads = gt_reads, read_gt(c + 1)    # the next chunk's files: decoded during this chunk's forward
-                centres, out = next(chunks)
-                k = len(centres)
-                for f in pending[b]:                # chunk c - 2 is out of pinned buffer b (raises here what a writer raised)
-                    f.result()
-                pending[b] = []
-                if c >= 2 and save_dir is not None:
-                    main.wait_event(copied[b])      # ... and out of device buffer b
-                gt8 = None
-                if gt_dir is not None:
-                    uploaded[b].synchronize()       # chunk c - 2 has left pinned buffer b (the launch stream orders gt_dev[b]'s reuse)
-                    frames = gt_host[b].numpy()
-                    for j, f in enumerate(mine):
-                        g = f.result()
-                        if g.shape != (Hgt, Wgt):
-                            raise ValueError(f"ground-truth frame {centres[j]} is {g.shape}, frame 0 is {(Hgt, Wgt)}")
-                        frames[j] = g
-                    gt8 = gt_dev[b][:k]
-                    gt8.copy_(gt_host[b][:k], non_blocking=True)
-                    uploaded[b].record(main)
-                u8, e = K.finish_frames(out, s.H, s.W, gt=gt8, crop=crop_border, mode=quantise, dst=dev8[b][:k])
-                del out                              # the chunk's fp32 frames end here
-                if gt8 is not None:
-                    sse.append(e)
-                    ssim.append(M.ssim_u8(u8, gt8, crop_border))
-                if save_dir is not None:
-                    ready = torch.cuda.Event()
-                    ready.record(main)
-                    copy.wait_event(ready)
-                    with torch.cuda.stream(copy):
-                        host8[b][:k].copy_(u8, non_blocking=True)
-                        copied[b].record(copy)
-                    frames = host8[b].numpy()
-                    pending[b] = [pool.submit(_write_when_copied, copied[b], os.path.join(save_dir, names[t]), frames[j], png_level)
-                                  for j, t in enumerate(centres)]
-            for f in pending[0] + pending[1]:
-                f.result()
-            main.wait_stream(copy)
-            if gt_dir is not None:
-                n = int(np.prod(metric_region(Ho, Wo, Hgt, Wgt, crop_border)[2:]))
-                psnr = M.psnr_from_sse(torch.cat(sse).cpu().numpy(), n)
-                ssim_t = torch.cat(ssim).cpu().numpy().astype(np.float64)
-            else:
-                psnr, ssim_t = np.zeros(0, np.float64), np.zeros(0, np.float64)
-            torch.cuda.synchronize(dev)
-    mean = lambda a: float(a.sum() / len(a)) if len(a) else float("nan")      # psnr / frames, as the reference accumulates
-    return SequenceResult(psnr, ssim_t, mean(psnr), mean(ssim_t), T, s.seconds, time.perf_counter() - t_start)
+        return StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"], gumbel_uniform=gumbel_uniform,
+                           frame_noise=frame_noise), None
+
+    s, sse, _, ssim = _run_chunks(lr, load, gt, sink, chunk, share_compensation, crop_border, 0, quantise, workers)
+    psnr = _psnr(sse, lr.shape, gt and gt.shape, crop_border, 255)
+    return SequenceResult(psnr, ssim, _mean(psnr), _mean(ssim), lr.frames, s.seconds, time.perf_counter() - t_start)
 
 
 class YuvResult(NamedTuple):
@@ -231,30 +372,6 @@ def psnr_yuv(psnr_y, psnr_u, psnr_v) -> np.ndarray:
     return (6.0 * y + u + v) / 8.0
 
 
-def _stage_frame(reader: YuvReader, t: int, y: np.ndarray, u: Optional[np.ndarray], v: Optional[np.ndarray]) -> None:
-    """Frame t of a mapped file into its places in a pinned buffer (the page faults of the map happen here, in the pool); u and v
-    None: a 4:0:0 file."""
-    np.copyto(y, reader.y(t))
-    if u is not None:
-        np.copyto(u, reader.u(t))
-        np.copyto(v, reader.v(t))
-
-
-def _append_when_copied(before: Optional[cf.Future], done: torch.cuda.Event, writer: YuvWriter, y: np.ndarray,
-                        c: Optional[np.ndarray]) -> None:
-    """Append a chunk (y [k,Ho,Wo]; c [2k,Ho/2,Wo/2], its U planes then its V planes; None: 4:0:0) once the chunk before it is in the
-    file and its own download into the pinned buffers `y` and `c` are views of has completed."""
-    if before is not None:
-        before.result()
-    done.synchronize()
-    k = len(y)
-    for j in range(k):
-        if c is None:
-            writer.append(y[j])
-        else:
-            writer.append(y[j], c[j], c[k + j])
-
-
 def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_yuv: Optional[str] = None,
                  save_yuv: Optional[str] = None, chunk: int = 8, share_compensation: bool = False, crop_border: int = 4,
                  quantise: str = "trunc", workers: int = 8, gumbel_uniform: Optional[Sequence] = None,
@@ -274,146 +391,39 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     depth too (16-bit PNGs, wider NPYs), the partition maps stay 8-bit masks.  ``gray*``: no chroma work, ``psnr_u`` / ``psnr_v`` are
     empty and ``psnr_yuv`` is ``psnr_y``.  ``yuv444p*``: chroma planes of the luma's size, their border ``crop_border``."""
     fmt = parse_pix_fmt(pix_fmt)
-    peak, has_c = fmt.peak, fmt.chroma != "400"
-    kind = torch.uint8 if fmt.sample_bytes == 1 else torch.uint16
-    workers = _check_workers(workers)
-    if quantise not in K.QUANT_MODES:
-        raise ValueError(f"quantise must be one of {sorted(K.QUANT_MODES)}, got {quantise!r}")
-    if int(chunk) < 1:
-        raise ValueError(f"chunk >= 1 expected, got {chunk}")
+    workers, chunk = _check_args(workers, quantise, chunk)
     t_start = time.perf_counter()
-    chunk, ccrop = int(chunk), chroma_crop(crop_border, fmt.chroma)
+    ccrop = chroma_crop(crop_border, fmt.chroma)
     with YuvReader(lr_yuv, width, height, fmt) as head:
-        T = head.frames
-    kmax, Ho, Wo = min(chunk, T), 4 * height, 4 * width
-    hc, wc = fmt.chroma_shape(height, width) or (0, 0)
-    Hoc, Woc = 4 * hc, 4 * wc
-    gt = writer = Hgt = Wgt = None
-    Hgc = Wgc = 0                                        # the ground truth's chroma planes
+        lr = _YuvSource(head)
+    gt = reader = writer = None
     try:
         if gt_yuv is not None:
-            Wgt, Hgt = gt_size if gt_size is not None else (Wo, Ho)
-            gt = YuvReader(gt_yuv, Wgt, Hgt, fmt)
-            Hgc, Wgc = fmt.chroma_shape(Hgt, Wgt) or (0, 0)
-            if gt.frames != T:
-                raise ValueError(f"{gt_yuv} holds {gt.frames} frames of {Wgt}x{Hgt}, {lr_yuv} holds {T}")
-            if min(metric_region(Ho, Wo, Hgt, Wgt, crop_border)[2:]) <= 10:
-                raise ValueError(f"crop_border {crop_border} leaves no SSIM window in the common {min(Ho, Hgt)} x {min(Wo, Wgt)} of "
-                                 f"result and ground truth")
-            if has_c and min(metric_region(Hoc, Woc, Hgc, Wgc, ccrop)[2:]) <= 0:
-                raise ValueError(f"crop_border {crop_border} leaves nothing of the chroma planes")
-        pinned = lambda n, h, w: torch.empty((n, h, w), dtype=kind).pin_memory()
-        writer = YuvWriter(save_yuv, Wo, Ho, fmt) if save_yuv is not None else None
-        with cf.ThreadPoolExecutor(max_workers=workers) as pool:
-            # ground truth comes up through two sets of pinned buffers: chunk c's frames are copied out of the map by the pool
-            # while chunk c - 1's forward runs
-            gt_y = [pinned(kmax, Hgt, Wgt) for _ in range(2)] if gt is not None else None
-            gt_c = [pinned(2 * kmax, Hgc, Wgc) for _ in range(2)] if gt is not None and has_c else None
+            Wgt, Hgt = gt_size if gt_size is not None else (4 * width, 4 * height)
+            reader = YuvReader(gt_yuv, Wgt, Hgt, fmt)
+            gt = _YuvSource(reader)
+            if gt.frames != lr.frames:
+                raise ValueError(f"{gt_yuv} holds {gt.frames} frames of {Wgt}x{Hgt}, {lr_yuv} holds {lr.frames}")
+            _check_regions(lr, gt, crop_border, ccrop)
+        writer = YuvWriter(save_yuv, 4 * width, 4 * height, fmt) if save_yuv is not None else None
 
-            def read_gt(c):
-                if gt is None or c * chunk >= T:
-                    return []
-                k, y = min(chunk, T - c * chunk), gt_y[c % 2].numpy()
-                if not has_c:
-                    return [pool.submit(_stage_frame, gt, c * chunk + j, y[j], None, None) for j in range(k)]
-                uv = gt_c[c % 2].numpy()
-                return [pool.submit(_stage_frame, gt, c * chunk + j, y[j], uv[j], uv[k + j]) for j in range(k)]
-
-            gt_reads = read_gt(0)
+        def load():
             seq = load_sequence_yuv(lr_yuv, width, height, side_dir, fmt)
-            lr_u, lr_v = seq.pop("u", None), seq.pop("v", None)
-            s = StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"],
-                            gumbel_uniform=gumbel_uniform, frame_noise=frame_noise, peak=peak)
-            del seq
-            dev = s.dev
-            with torch.cuda.device(dev):
-                main, copy = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
-                on_dev = lambda n, h, w: torch.empty((n, h, w), dtype=kind, device=dev)
-                pair = lambda make, *shape: [make(*shape) for _ in range(2)]
-                dev_y, dev_c = pair(on_dev, kmax, Ho, Wo), pair(on_dev, 2 * kmax, Hoc, Woc) if has_c else None
-                host_y = pair(pinned, kmax, Ho, Wo) if writer is not None else None
-                host_c = pair(pinned, 2 * kmax, Hoc, Woc) if writer is not None and has_c else None
-                copied = [torch.cuda.Event() for _ in range(2)]
-                lrc_host, lrc_dev = (pair(pinned, 2 * kmax, hc, wc), pair(on_dev, 2 * kmax, hc, wc)) if has_c else (None, None)
-                gty_dev = pair(on_dev, kmax, Hgt, Wgt) if gt is not None else None
-                gtc_dev = pair(on_dev, 2 * kmax, Hgc, Wgc) if gt is not None and has_c else None
-                uploaded = [torch.cuda.Event() for _ in range(2)]
-                pending: List[Optional[cf.Future]] = [None, None]
-                last_write: Optional[cf.Future] = None
-                sse_y, sse_c, ssim = [], [], []
-                chunks = s.iter_chunked(chunk, share_compensation)
-                for c in range((T + chunk - 1) // chunk):
-                    b = c % 2
-                    uploaded[1 - b].synchronize()       # chunk c - 1 has left the pinned buffers chunk c + 1 is staged in
-                    mine, gt_reads = gt_reads, read_gt(c + 1)   # the next chunk's frames: copied during this chunk's forward
-                    centres, out = next(chunks)
-                    k = len(centres)
-                    if pending[b] is not None:          # chunk c - 2 is out of the pinned result buffers b (raises what it raised)
-                        pending[b].result()
-                        pending[b] = None
-                    if c >= 2 and writer is not None:
-                        main.wait_event(copied[b])      # ... and out of the device buffers b
-                    uploaded[b].synchronize()           # chunk c - 2 has left the pinned LR chroma buffer b
-                    src_c = None
-                    if has_c:
-                        planes = lrc_host[b].numpy()
-                        planes[:k], planes[k:2 * k] = lr_u[centres[0]:centres[0] + k], lr_v[centres[0]:centres[0] + k]
-                        src_c = lrc_dev[b][:2 * k]
-                        src_c.copy_(lrc_host[b][:2 * k], non_blocking=True)
-                    gy = gc = None
-                    if gt is not None:
-                        for f in mine:
-                            f.result()
-                        gy = gty_dev[b][:k]
-                        gy.copy_(gt_y[b][:k], non_blocking=True)
-                        if has_c:
-                            gc = gtc_dev[b][:2 * k]
-                            gc.copy_(gt_c[b][:2 * k], non_blocking=True)
-                    uploaded[b].record(main)
-                    y8, e = K.finish_frames(out, s.H, s.W, gt=gy, crop=crop_border, mode=quantise, dst=dev_y[b][:k], peak=peak)
-                    del out                              # the chunk's fp32 frames end here
-                    c8 = ec = None
-                    if has_c:
-                        c8, ec = K.chroma_up4(src_c, gt=gc, crop=ccrop, dst=dev_c[b][:2 * k], peak=peak)
-                    if gt is not None:
-                        sse_y.append(e)
-                        if has_c:
-                            sse_c.append(ec.view(2, k))
-                        ssim.append(M.ssim_u8(y8, gy, crop_border) if kind == torch.uint8 else M.ssim_u16(y8, gy, crop_border, peak))
-                    if writer is not None:
-                        ready = torch.cuda.Event()
-                        ready.record(main)
-                        copy.wait_event(ready)
-                        with torch.cuda.stream(copy):
-                            host_y[b][:k].copy_(y8, non_blocking=True)
-                            if has_c:
-                                host_c[b][:2 * k].copy_(c8, non_blocking=True)
-                            copied[b].record(copy)
-                        last_write = pending[b] = pool.submit(_append_when_copied, last_write, copied[b], writer,
-                                                              host_y[b].numpy()[:k], host_c[b].numpy()[:2 * k] if has_c else None)
-                for f in pending:
-                    if f is not None:
-                        f.result()
-                main.wait_stream(copy)
-                empty = np.zeros(0, np.float64)
-                py, pu, pv, ssim_t = empty, empty, empty, empty
-                if gt is not None:
-                    n_y = int(np.prod(metric_region(Ho, Wo, Hgt, Wgt, crop_border)[2:]))
-                    py = M.psnr_from_sse(torch.cat(sse_y).cpu().numpy(), n_y, peak)
-                    if has_c:
-                        n_c = int(np.prod(metric_region(Hoc, Woc, Hgc, Wgc, ccrop)[2:]))
-                        ec = torch.cat(sse_c, dim=1).cpu().numpy()
-                        pu, pv = M.psnr_from_sse(ec[0], n_c, peak), M.psnr_from_sse(ec[1], n_c, peak)
-                    ssim_t = torch.cat(ssim).cpu().numpy().astype(np.float64)
-                torch.cuda.synchronize(dev)
+            lr_c = (seq["u"], seq["v"]) if "u" in seq else None
+            return StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"],
+                               gumbel_uniform=gumbel_uniform, frame_noise=frame_noise, peak=fmt.peak), lr_c
+
+        s, sse_y, sse_c, ssim = _run_chunks(lr, load, gt, writer and _YuvSink(writer), chunk, share_compensation, crop_border, ccrop,
+                                            quantise, workers)
     finally:
         if writer is not None:
             writer.close()
-        if gt is not None:
-            gt.close()
-    pyuv = psnr_yuv(py, pu, pv) if has_c else py
-    mean = lambda a: float(a.sum() / len(a)) if len(a) else float("nan")
-    return YuvResult(py, pu, pv, ssim_t, pyuv, mean(py), mean(pu), mean(pv), mean(ssim_t), mean(pyuv), T, s.seconds,
+        if reader is not None:
+            reader.close()
+    py = _psnr(sse_y, lr.shape, gt and gt.shape, crop_border, fmt.peak)
+    pu, pv = (_psnr(e, lr.chroma_shape, gt and gt.chroma_shape, ccrop, fmt.peak) for e in sse_c)
+    pyuv = psnr_yuv(py, pu, pv) if lr.chroma_shape is not None else py
+    return YuvResult(py, pu, pv, ssim, pyuv, _mean(py), _mean(pu), _mean(pv), _mean(ssim), _mean(pyuv), lr.frames, s.seconds,
                      time.perf_counter() - t_start)
 
 

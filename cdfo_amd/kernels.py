@@ -601,6 +601,8 @@ QUANT_MODES = {"trunc": 0, "nearest": 1}        # CDFO_QUANT_* of include/cdfo_h
 
 
 def _sample_frames(t: torch.Tensor, name: str, dtype: torch.dtype):
+    """A stack of uint8 or uint16 frames [N,H,W] (or [H,W]) with contiguous rows -> (tensor [N,H,W], N, H, W, pitch, frame stride),
+    in samples; pitch and stride may exceed W and H * pitch (a view of larger frames is read in place)."""
     if t.dim() == 2:
         t = t.unsqueeze(0)
     if not t.is_cuda or t.dtype != dtype or t.dim() != 3 or t.stride(2) != 1 or t.stride(1) < t.shape[2] or t.stride(0) < 0:
@@ -608,17 +610,6 @@ def _sample_frames(t: torch.Tensor, name: str, dtype: torch.dtype):
         raise ValueError(f"{name}: a device {kind} tensor [N,H,W] with contiguous rows expected, got {t.dtype} {tuple(t.shape)} "
                          f"strides {t.stride()}")
     return t, int(t.shape[0]), int(t.shape[1]), int(t.shape[2]), int(t.stride(1)), int(t.stride(0))
-
-
-def u8_frames(t: torch.Tensor, name: str):
-    """An 8-bit frame stack [N,H,W] (or [H,W]) with contiguous rows -> (tensor [N,H,W], N, H, W, pitch, frame stride), in bytes;
-    pitch and stride may exceed W and H * pitch (a view of larger frames is read in place)."""
-    return _sample_frames(t, name, torch.uint8)
-
-
-def u16_frames(t: torch.Tensor, name: str):
-    """`u8_frames` for 16-bit samples (torch.uint16): pitch and frame stride in samples."""
-    return _sample_frames(t, name, torch.uint16)
 
 
 def sample_dtype(peak: Optional[int], given: Optional[torch.dtype], name: str):
@@ -639,6 +630,33 @@ def sample_dtype(peak: Optional[int], given: Optional[torch.dtype], name: str):
     raise ValueError(f"{name}: uint8 or uint16 samples expected, got {given}")
 
 
+def _write_samples(name: str, src: torch.Tensor, planes: tuple, N: int, Ho: int, Wo: int, kind: torch.dtype, peak: int, mode: tuple,
+                   gt: Optional[torch.Tensor], crop: int, dst: Optional[torch.Tensor], on: str, one_per: str):
+    """The common end of `finish_frames` and `chroma_up4`, cdfo_<name> or its _u16 form by ``kind``: ``planes``, the entry point's
+    arguments up to the source's sizes; a dense ``dst`` [N,Ho,Wo] of ``kind`` on ``src``'s device, validated or allocated; ``gt``
+    bound as a stack of N frames; the [N,1024] int64 partial sums, added up per frame.  -> (dst, sse or None)."""
+    if dst is None:
+        dst = torch.empty((N, Ho, Wo), dtype=kind, device=src.device)
+    elif dst.dtype != kind or tuple(dst.shape) != (N, Ho, Wo) or not dst.is_contiguous() or dst.device != src.device:
+        raise ValueError(f"{name}: dst must be a dense {kind} [{N},{Ho},{Wo}] tensor on {on}'s device")
+    part, nb = None, C.c_int(0)
+    g = gp = gs = gh = gw = None
+    if gt is not None:
+        g, n, gh, gw, gp, gs = _sample_frames(gt, f"{name}: gt", kind)
+        if n != N or g.device != src.device:
+            raise ValueError(f"{name}: gt must hold {one_per} = {N}) on {on}'s device, got {n}")
+        part = torch.empty((N, 1024), dtype=torch.int64, device=src.device)
+    entry = f"cdfo_{name}_u16" if kind == torch.uint16 else f"cdfo_{name}"
+    with on_device(src):
+        check(getattr(_lib.lib(), entry)(*planes, _vp(dst), *((peak,) if kind == torch.uint16 else ()), *mode, _vp(g), gp or 0,
+                                         C.c_longlong(gs or 0), gh or 0, gw or 0, int(crop), _vp(part),
+                                         0 if part is None else part.numel(), C.byref(nb), _stream()), entry)
+    if part is None:
+        return dst, None
+    # the kernel packs its partial sums as [N][nblocks]; integers, so the sum is exact in any order
+    return dst, part.view(-1)[:N * nb.value].view(N, nb.value).sum(dim=1)
+
+
 def finish_frames(out: torch.Tensor, H: int, W: int, gt: Optional[torch.Tensor] = None, crop: int = 4, mode: str = "trunc",
                   dst: Optional[torch.Tensor] = None, peak: int = 255):
     """out: the fp32 output of a chunk, [K,1,>=4H,>=4W] or [K,>=4H,>=4W] with contiguous rows (the padded tensor, read in place)
@@ -649,8 +667,6 @@ def finish_frames(out: torch.Tensor, H: int, W: int, gt: Optional[torch.Tensor] 
     ``dst`` / ``gt``, multiplies by the peak and gives uint16 frames (cdfo_finish_frames_u16)."""
     given = dst.dtype if dst is not None else gt.dtype if gt is not None else None
     kind, peak = sample_dtype(peak, given, "finish_frames")
-    wide = kind == torch.uint16
-    frames_of = u16_frames if wide else u8_frames
     if mode not in QUANT_MODES:
         raise ValueError(f"finish_frames: mode must be one of {sorted(QUANT_MODES)}, got {mode!r}")
     if out.dim() == 4 and out.shape[1] == 1:
@@ -661,29 +677,9 @@ def finish_frames(out: torch.Tensor, H: int, W: int, gt: Optional[torch.Tensor] 
         raise ValueError(f"finish_frames: a device fp32 tensor [K,1,>={Ho},>={Wo}] with contiguous rows expected, got {out.dtype} "
                          f"{tuple(out.shape)} strides {out.stride()}")
     K = int(out.shape[0])
-    if dst is None:
-        dst = torch.empty((K, Ho, Wo), dtype=kind, device=out.device)
-    elif dst.dtype != kind or tuple(dst.shape) != (K, Ho, Wo) or not dst.is_contiguous() or dst.device != out.device:
-        raise ValueError(f"finish_frames: dst must be a dense {kind} [{K},{Ho},{Wo}] tensor on out's device")
-    part, nb = None, C.c_int(0)
-    g = gp = gs = gh = gw = None
-    if gt is not None:
-        g, n, gh, gw, gp, gs = frames_of(gt, "finish_frames: gt")
-        if n != K or g.device != out.device:
-            raise ValueError(f"finish_frames: gt must hold one frame per output frame (K = {K}) on out's device, got {n}")
-        part = torch.empty((K, 1024), dtype=torch.int64, device=out.device)
-    with on_device(out):
-        src = (_vp(out), int(out.stride(1)), C.c_longlong(out.stride(0)), K, Ho, Wo, _vp(dst))
-        rest = (QUANT_MODES[mode], _vp(g), gp or 0, C.c_longlong(gs or 0), gh or 0, gw or 0, int(crop), _vp(part),
-                0 if part is None else part.numel(), C.byref(nb), _stream())
-        if wide:
-            check(_lib.lib().cdfo_finish_frames_u16(*src, peak, *rest), "cdfo_finish_frames_u16")
-        else:
-            check(_lib.lib().cdfo_finish_frames(*src, *rest), "cdfo_finish_frames")
-    if part is None:
-        return dst, None
-    # the kernel packs its partial sums as [K][nblocks]; integers, so the sum is exact in any order
-    return dst, part.view(-1)[:K * nb.value].view(K, nb.value).sum(dim=1)
+    planes = (_vp(out), int(out.stride(1)), C.c_longlong(out.stride(0)), K, Ho, Wo)
+    return _write_samples("finish_frames", out, planes, K, Ho, Wo, kind, peak, (QUANT_MODES[mode],), gt, crop, dst, "out",
+                          "one frame per output frame (K")
 
 
 def chroma_up4(src: torch.Tensor, gt: Optional[torch.Tensor] = None, crop: int = 2, dst: Optional[torch.Tensor] = None,
@@ -695,34 +691,11 @@ def chroma_up4(src: torch.Tensor, gt: Optional[torch.Tensor] = None, crop: int =
     uint16 planes (``src``, ``gt``, ``dst`` alike) need ``peak``, 2**depth - 1: the same filter clamped to [0, peak]
     (cdfo_chroma_up4_u16)."""
     kind, peak = sample_dtype(peak, src.dtype, "chroma_up4")
-    wide = kind == torch.uint16
-    frames_of = u16_frames if wide else u8_frames
-    s, N, h, w, sp, ss = frames_of(src, "chroma_up4: src")
+    s, N, h, w, sp, ss = _sample_frames(src, "chroma_up4: src", kind)
     if h <= 0 or w <= 0 or N <= 0:
         raise ValueError(f"chroma_up4: src holds no pixels: {tuple(s.shape)}")
-    if dst is None:
-        dst = torch.empty((N, 4 * h, 4 * w), dtype=kind, device=s.device)
-    elif dst.dtype != kind or tuple(dst.shape) != (N, 4 * h, 4 * w) or not dst.is_contiguous() or dst.device != s.device:
-        raise ValueError(f"chroma_up4: dst must be a dense {kind} [{N},{4 * h},{4 * w}] tensor on src's device")
-    part, nb = None, C.c_int(0)
-    g = gp = gs = gh = gw = None
-    if gt is not None:
-        g, n, gh, gw, gp, gs = frames_of(gt, "chroma_up4: gt")
-        if n != N or g.device != s.device:
-            raise ValueError(f"chroma_up4: gt must hold one plane per source plane (N = {N}) on src's device, got {n}")
-        part = torch.empty((N, 1024), dtype=torch.int64, device=s.device)
-    with on_device(s):
-        planes = (_vp(s), sp, C.c_longlong(ss), N, h, w, _vp(dst))
-        rest = (_vp(g), gp or 0, C.c_longlong(gs or 0), gh or 0, gw or 0, int(crop), _vp(part), 0 if part is None else part.numel(),
-                C.byref(nb), _stream())
-        if wide:
-            check(_lib.lib().cdfo_chroma_up4_u16(*planes, peak, *rest), "cdfo_chroma_up4_u16")
-        else:
-            check(_lib.lib().cdfo_chroma_up4(*planes, *rest), "cdfo_chroma_up4")
-    if part is None:
-        return dst, None
-    # the kernel packs its partial sums as [N][nblocks]; integers, so the sum is exact in any order
-    return dst, part.view(-1)[:N * nb.value].view(N, nb.value).sum(dim=1)
+    return _write_samples("chroma_up4", s, (_vp(s), sp, C.c_longlong(ss), N, h, w), N, 4 * h, 4 * w, kind, peak, (), gt, crop, dst,
+                          "src", "one plane per source plane (N")
 
 
 def stem_conv(img: torch.Tensor, img_bstride: int, B: int, H: int, W: int, w: torch.Tensor, bias: torch.Tensor,

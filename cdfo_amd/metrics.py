@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .kernels import _stream, _vp, on_device, u8_frames, u16_frames
+from .kernels import _sample_frames, _stream, _vp, on_device
 
 
 def _partials(a: torch.Tensor, b: torch.Tensor, crop: int, metric: int, from_unit_range: bool, round8: bool):
@@ -73,24 +73,27 @@ def psnr_from_sse(sse, n: int, peak: int = 255) -> np.ndarray:
     return np.array([np.inf if m == 0 else 20.0 * np.log10(peak / np.sqrt(m)) for m in mse], dtype=np.float64)
 
 
-def _partials_u8(a: torch.Tensor, b: torch.Tensor, crop: int, metric: int):
-    a, N, Ha, Wa, pa, sa = u8_frames(a, "img1")
-    b, Nb, Hb, Wb, pb, sb = u8_frames(b, "img2")
+def _partials_samples(a: torch.Tensor, b: torch.Tensor, crop: int, kind: torch.dtype, which: int):
+    """Per-frame sums over the common size of two stacks of ``kind`` samples, and what is left of it inside the border.  uint8:
+    cdfo_metric_partials_u8, ``which`` its metric (0: squared differences, 1: the SSIM map); uint16: cdfo_ssim_partials_u16, ``which``
+    the peak."""
+    a, N, Ha, Wa, pa, sa = _sample_frames(a, "img1", kind)
+    b, Nb, Hb, Wb, pb, sb = _sample_frames(b, "img2", kind)
     if N != Nb or a.device != b.device:
         raise ValueError(f"the two stacks must hold the same number of frames on one device, got {N} and {Nb}")
     part = torch.empty((N, 1024), dtype=torch.float64, device=a.device)
     nb = C.c_int(0)
+    entry = "cdfo_metric_partials_u8" if kind == torch.uint8 else "cdfo_ssim_partials_u16"
     with on_device(a):
-        _lib.check(_lib.lib().cdfo_metric_partials_u8(_vp(a), pa, C.c_longlong(sa), Ha, Wa, _vp(b), pb, C.c_longlong(sb), Hb, Wb, N,
-                                                      int(crop), metric, _vp(part), part.numel(), C.byref(nb), _stream()),
-                   "cdfo_metric_partials_u8")
+        _lib.check(getattr(_lib.lib(), entry)(_vp(a), pa, C.c_longlong(sa), Ha, Wa, _vp(b), pb, C.c_longlong(sb), Hb, Wb, N, int(crop),
+                                              which, _vp(part), part.numel(), C.byref(nb), _stream()), entry)
     Hm, Wm = common_size(Ha, Wa, Hb, Wb)
     return part.view(-1)[:N * nb.value].view(N, nb.value).sum(dim=1), Hm - 2 * crop, Wm - 2 * crop
 
 
 def sse_u8(img1: torch.Tensor, img2: torch.Tensor, crop_border: int = 4):
     """(int64 device tensor [N] of the sums of squared differences, pixels per frame): the exact numerator of `psnr_u8`."""
-    s, Hc, Wc = _partials_u8(img1, img2, crop_border, 0)
+    s, Hc, Wc = _partials_samples(img1, img2, crop_border, torch.uint8, 0)
     return s.to(torch.int64), Hc * Wc          # sums of integers below 2^53: the fp64 partials are exact
 
 
@@ -103,7 +106,7 @@ def psnr_u8(img1: torch.Tensor, img2: torch.Tensor, crop_border: int = 4) -> np.
 
 def ssim_u8(img1: torch.Tensor, img2: torch.Tensor, crop_border: int = 4) -> torch.Tensor:
     """Per-frame SSIM of uint8 [N,H,W] device stacks over their common size (fp64 device tensor [N])."""
-    s, Hc, Wc = _partials_u8(img1, img2, crop_border, 1)
+    s, Hc, Wc = _partials_samples(img1, img2, crop_border, torch.uint8, 1)
     return s / float((Hc - 10) * (Wc - 10))
 
 
@@ -112,16 +115,5 @@ def ssim_u16(img1: torch.Tensor, img2: torch.Tensor, crop_border: int, peak: int
     There is no ``sse_u16``: the sums of squares come, as integers, from ``kernels.finish_frames`` and ``kernels.chroma_up4``."""
     if isinstance(peak, bool) or not isinstance(peak, int) or not 1 <= peak <= 65535:
         raise ValueError(f"ssim_u16: peak must be an integer in 1 .. 65535, got {peak!r}")
-    a, N, Ha, Wa, pa, sa = u16_frames(img1, "img1")
-    b, Nb, Hb, Wb, pb, sb = u16_frames(img2, "img2")
-    if N != Nb or a.device != b.device:
-        raise ValueError(f"the two stacks must hold the same number of frames on one device, got {N} and {Nb}")
-    part = torch.empty((N, 1024), dtype=torch.float64, device=a.device)
-    nb = C.c_int(0)
-    with on_device(a):
-        _lib.check(_lib.lib().cdfo_ssim_partials_u16(_vp(a), pa, C.c_longlong(sa), Ha, Wa, _vp(b), pb, C.c_longlong(sb), Hb, Wb, N,
-                                                     int(crop_border), peak, _vp(part), part.numel(), C.byref(nb), _stream()),
-                   "cdfo_ssim_partials_u16")
-    Hm, Wm = common_size(Ha, Wa, Hb, Wb)
-    s = part.view(-1)[:N * nb.value].view(N, nb.value).sum(dim=1)
-    return s / float((Hm - 2 * crop_border - 10) * (Wm - 2 * crop_border - 10))
+    s, Hc, Wc = _partials_samples(img1, img2, crop_border, torch.uint16, peak)
+    return s / float((Hc - 10) * (Wc - 10))

@@ -1,5 +1,5 @@
 """Host side of sequence evaluation (cdfo_amd/evaluate.py): the log line, the min-crop rule, the PNG writer's level / vectorised
-filter-0 path, the numpy statement of the quantiser and the worker cap.  No GPU."""
+filter-0 path, the numpy statement of the quantiser, the worker cap, and the chunk loop's frame sources and sinks.  No GPU."""
 import struct
 import zlib
 
@@ -109,3 +109,66 @@ def test_psnr_from_integer_sums_is_the_oracle_bit_for_bit():
         sse = int(((a[c].astype(np.int64) - b[c].astype(np.int64)) ** 2).sum())
         assert psnr_from_sse([sse], a[c].size)[0] == calculate_psnr(a, b, crop)
     assert np.isinf(psnr_from_sse([0], 100)[0])
+
+
+class _NoEvent:
+    """Stands in for the copy's event: the download it guards is not what these tests are about."""
+
+    def synchronize(self):
+        pass
+
+
+def test_sources_and_sinks_without_a_gpu(tmp_path):
+    """The two kinds of frame source on the same content (T = 3, 6 x 8, one seed, once as PNGs and once as a gray raw file), and the
+    two kinds of frame sink behind an event that does nothing."""
+    import concurrent.futures as cf
+    import os
+    import threading
+    from cdfo_amd.yuv import YuvReader, YuvWriter
+    T, H, W = 3, 6, 8
+    lr_dir, _, gt_dir = E.write_synthetic_sequence(str(tmp_path / "png"), T, H, W, seed=7)
+    _, _, gt_yuv = E.write_synthetic_sequence_yuv(str(tmp_path / "raw"), T, H, W, seed=7, pix_fmt="gray")
+    png = E._PngSource(gt_dir)
+    with YuvReader(gt_yuv, 4 * W, 4 * H, "gray") as reader:
+        raw = E._YuvSource(reader)
+        assert png.frames == raw.frames == T and png.shape == raw.shape == (4 * H, 4 * W)
+        assert png.chroma_shape is None and raw.chroma_shape is None
+        assert (png.dtype, png.peak) == (raw.dtype, raw.peak)
+        for t in range(T):
+            a, b = np.full((4 * H, 4 * W), 7, np.uint8), np.full((4 * H, 4 * W), 9, np.uint8)
+            png.stage(t, a)
+            raw.stage(t, b)
+            assert np.array_equal(a, b) and a.tobytes() == b.tobytes()
+            # exactly the arrays the two readers hand out
+            assert np.array_equal(a, read_gray_png(os.path.join(gt_dir, "%05d.png" % t))) and np.array_equal(b, reader.y(t))
+    # a ground-truth directory whose frame 1 has another shape: refused when that frame is staged, by its number
+    write_gray_png(os.path.join(gt_dir, "00001.png"), np.zeros((4 * H, 4 * W - 1), np.uint8))
+    odd, view = E._PngSource(gt_dir), np.zeros((4 * H, 4 * W), np.uint8)
+    odd.stage(0, view)
+    with pytest.raises(ValueError, match="frame 1 "):
+        odd.stage(1, view)
+    frames = np.random.RandomState(1).randint(0, 256, (4, 4 * H, 4 * W)).astype(np.uint8)
+    with cf.ThreadPoolExecutor(max_workers=2) as pool:
+        # PNGs under the LR names, whichever slot of the chunk a frame sits in
+        names = E._PngSource(lr_dir).names
+        assert names == ["%05d.png" % t for t in range(T)]
+        save = str(tmp_path / "out")
+        for f in E._PngSink(save, names, 1)(pool, _NoEvent(), [1, 2], frames[:2], None):
+            f.result()
+        assert sorted(os.listdir(save)) == names[1:]
+        assert all(np.array_equal(read_gray_png(os.path.join(save, names[1 + j])), frames[j]) for j in range(2))
+        # the raw file in submission order: chunk 1 is handed in, and runs on the second worker, while chunk 0 still waits for its copy
+        gate = threading.Event()
+        held = _NoEvent()
+        held.synchronize = gate.wait
+        out = str(tmp_path / "out.yuv")
+        with YuvWriter(out, 4 * W, 4 * H, "gray") as writer:
+            sink = E._YuvSink(writer)
+            first, = sink(pool, held, [0, 1], frames[:2], None)
+            second, = sink(pool, _NoEvent(), [2, 3], frames[2:], None)
+            assert not first.done() and not second.done()
+            gate.set()
+            second.result()
+            assert first.done()
+        with YuvReader(out, 4 * W, 4 * H, "gray") as r:
+            assert r.frames == 4 and np.array_equal(r.y(0, 4), frames)

@@ -143,3 +143,20 @@ def test_ground_truth_of_another_size_and_bad_files(case, tmp_path):
         _evaluate(case, 2, False, gt_yuv=other, gt_size=(46, 74))            # read as 10 frames of 46x74
     with pytest.raises(ValueError, match="SSIM window"):
         _evaluate(case, 2, False, gt_yuv=case["raw"][2], crop_border=32)
+
+
+def test_gray_raw_file_is_the_png_path(case, tmp_path):
+    """One loop, two front ends: the same luma as a `gray` raw file through evaluate_yuv and as PNGs through evaluate_sequence
+    (chunk 2: every staging buffer is reused) give the same bytes and the same figures."""
+    from cdfo_amd.evaluate import evaluate_yuv, write_synthetic_sequence_yuv
+    from cdfo_amd.yuv import YuvReader
+    ref, ref_frames = _png_reference(case, 2, False)
+    lr_yuv, side, gt_yuv = write_synthetic_sequence_yuv(str(tmp_path / "gray"), T, H, W, seed=11, pix_fmt="gray")
+    out = str(tmp_path / "out.yuv")
+    torch.manual_seed(SEED)
+    r = evaluate_yuv(case["model"], lr_yuv, W, H, side, gt_yuv=gt_yuv, save_yuv=out, chunk=2, pix_fmt="gray", **_noise(case, False))
+    with YuvReader(out, 4 * W, 4 * H, "gray") as saved:
+        assert saved.frames == T and np.array_equal(saved.y(0, T), ref_frames)
+    assert np.array_equal(r.psnr_y, ref.psnr) and np.array_equal(r.ssim_y, ref.ssim) and r.psnr_y.shape == (T,)
+    assert r.psnr_u.shape == r.psnr_v.shape == (0,)
+    assert r.psnr_yuv is r.psnr_y
