@@ -21,7 +21,8 @@ from where it is uploaded without blocking; a slot's pinned buffers are staged a
 the frames go to the host on a copy stream into pinned buffers and the sink's pool tasks write them while the next forward runs; a
 slot's device buffers are written again only after the event behind that copy, its pinned buffers only after the sink's tasks.  So
 nothing relies on the allocator's stream bookkeeping, no fp32 output frame outlives its chunk, and the memory held does not depend
-on the sequence's length.
+on the sequence's length.  ``msssim=True`` adds the luma's five-scale MS-SSIM (`metrics.msssim_components`)
+on the frames SSIM runs on; its pyramid scratch exists once, the launch stream orders its use.
 
 Deliberate deviation: ``cal_psnr_ssim`` sends single-channel frames through ``to_y_channel``, an fp32 ``/255*255`` round
 trip, and takes fp32 means.  The metric semantics here are the project's established ones, ``oracle/metrics_ref.py``: fp64 on the
@@ -47,6 +48,10 @@ from .yuv import YuvReader, YuvWriter, load_sequence_yuv, parse_pix_fmt
 MAX_WORKERS = 16
 
 
+_NO_FRAMES = np.zeros(0, np.float64)               # the default of the result tuples' trailing arrays: one object, so read-only
+_NO_FRAMES.setflags(write=False)
+
+
 class SequenceResult(NamedTuple):
     psnr: np.ndarray            # fp64 [T] (empty without ground truth)
     ssim: np.ndarray            # fp64 [T] (empty without ground truth)
@@ -55,11 +60,17 @@ class SequenceResult(NamedTuple):
     frames: int
     seconds_forward: float      # StreamingSR.seconds: everything the chunks do on the device up to their fp32 output
     seconds_total: float        # the whole call: reading the files, the forwards, metrics, downloads, PNG encoding
+    msssim: np.ndarray = _NO_FRAMES                 # fp64 [T] with ``msssim=True`` and ground truth, else empty
+    mean_msssim: float = float("nan")
 
 
 def format_log(result: SequenceResult, name: str) -> str:
-    """The reference's log line (psnr_ssim.py:481)."""
-    return '%s Average PSNR/SSIM: %.3f/%.5f' % (name, result.mean_psnr, result.mean_ssim)
+    """The reference's log line (psnr_ssim.py:481); with MS-SSIM figures, `` MS-SSIM: %.5f`` behind it."""
+    return '%s Average PSNR/SSIM: %.3f/%.5f' % (name, result.mean_psnr, result.mean_ssim) + _msssim_suffix(result)
+
+
+def _msssim_suffix(result) -> str:
+    return ' MS-SSIM: %.5f' % result.mean_msssim if len(result.msssim) else ''
 
 
 def quantise_numpy(x: np.ndarray, mode: str = "trunc", peak: int = 255) -> np.ndarray:
@@ -106,6 +117,11 @@ def _check_regions(lr, gt, crop_border: int, ccrop: int) -> None:
                          f"{min(4 * lr.shape[1], gt.shape[1])} of result and ground truth")
     if lr.chroma_shape is not None and min(_inside(lr.chroma_shape, gt.chroma_shape, ccrop)) <= 0:
         raise ValueError(f"crop_border {crop_border} leaves nothing of the chroma planes")
+
+
+def _check_msssim(lr, gt, crop_border: int) -> None:
+    """MS-SSIM's five scales need `metrics.msssim_min_size` samples each way inside the border (ValueError, naming the size)."""
+    M.msssim_region(4 * lr.shape[0], 4 * lr.shape[1], *gt.shape, crop_border)
 
 
 def _psnr(sse: np.ndarray, shape, gt_shape, crop: int, peak: int) -> np.ndarray:
@@ -218,12 +234,15 @@ class _Slots:
                 setattr(slot, name, None if shape is None else make((n, *shape)))
 
 
-def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: int, ccrop: int, quantise: str, workers: int):
+def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: int, ccrop: int, quantise: str, workers: int,
+                msssim: bool = False):
     """The chunk loop of both evaluators.  ``lr``: the LR sequence as a frame source (its counts, shapes, dtype and peak; its frames
     come from ``load``).  ``load()`` -> (`StreamingSR`, (u, v) LR chroma planes [T,h,w] or None); it runs after the first
     ground-truth reads have been handed to the pool.  ``gt``: a frame source or None.  ``sink``: a frame sink or None.
-    -> (the `StreamingSR`, sse_y int64 [T], sse_uv int64 [2,T], ssim fp64 [T]); the arrays are empty without ground truth (sse_uv
-    without chroma).  The module's docstring has the order of events."""
+    ``msssim``: with ground truth, `metrics.msssim_components` on the frames SSIM runs on, on the main stream; its pyramid scratch
+    exists once (every call that writes or reads it is on that stream, which orders them).
+    -> (the `StreamingSR`, sse_y int64 [T], sse_uv int64 [2,T], ssim fp64 [T], MS-SSIM components fp64 [T,5,2]); the arrays are empty
+    without ground truth (sse_uv without chroma, the components without ``msssim``).  The module's docstring has the order of events."""
     T, kmax, kind, peak = lr.frames, min(chunk, lr.frames), lr.dtype, lr.peak
     has_c = lr.chroma_shape is not None
     out_y, out_c = (shape and (4 * shape[0], 4 * shape[1]) for shape in (lr.shape, lr.chroma_shape))      # None stays None
@@ -253,7 +272,10 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
             down.add(on_dev, y=(kmax, out_y), c=(2 * kmax, out_c))
             if sink is not None:
                 down.add(pinned, host_y=(kmax, out_y), host_c=(2 * kmax, out_c))
-            sse_y, sse_c, ssim = [], [], []
+            sse_y, sse_c, ssim, ms = [], [], [], []
+            ms_scratch = None
+            if msssim and gt is not None:
+                ms_scratch = M.msssim_scratch(kmax, *M.msssim_region(*out_y, *gt_y, crop), dev)
             chunks = s.iter_chunked(chunk, share_compensation)
             for c in range((T + chunk - 1) // chunk):
                 u, d = up[c], down[c]
@@ -288,6 +310,8 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
                     if has_c:
                         sse_c.append(ec.view(2, k))
                     ssim.append(M.ssim_u8(y8, gy, crop) if kind == torch.uint8 else M.ssim_u16(y8, gy, crop, peak))
+                    if ms_scratch is not None:
+                        ms.append(M.msssim_components(y8, gy, crop, None if kind == torch.uint8 else peak, ms_scratch))
                 if sink is not None:
                     ready = torch.cuda.Event()
                     ready.record(main)
@@ -302,7 +326,8 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
                 f.result()
             main.wait_stream(copy)
             host = lambda parts, dim, empty: torch.cat(parts, dim=dim).cpu().numpy() if parts else np.zeros(empty, np.int64)
-            result = (s, host(sse_y, 0, 0), host(sse_c, 1, (2, 0)), host(ssim, 0, 0).astype(np.float64))
+            result = (s, host(sse_y, 0, 0), host(sse_c, 1, (2, 0)), host(ssim, 0, 0).astype(np.float64),
+                      host(ms, 0, (0, 5, 2)).astype(np.float64))
             torch.cuda.synchronize(dev)
     return result
 
@@ -310,13 +335,15 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
 def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] = None, save_dir: Optional[str] = None, chunk: int = 8,
                       share_compensation: bool = False, crop_border: int = 4, quantise: str = "trunc", workers: int = 8,
                       png_level: int = 6, gumbel_uniform: Optional[Sequence] = None,
-                      frame_noise: Optional[Sequence] = None) -> SequenceResult:
+                      frame_noise: Optional[Sequence] = None, msssim: bool = False) -> SequenceResult:
     """Super-resolve the sequence in ``lr_dir`` / ``side_dir`` (the reference's test layout, see cdfo_amd/priors.py) with ``model`` (on a
     GPU), ``chunk`` centre frames per forward.  ``save_dir``: write every frame as an 8-bit PNG under its LR file name.  ``gt_dir``:
     per-frame PSNR / SSIM of the 8-bit frames against ``<gt_dir>/%05d.png`` over the common size less ``crop_border``.
     ``quantise``: "trunc" (the reference's writer) or "nearest".  ``workers``: threads that read ground truth and encode PNGs, at
     most 16.  ``gumbel_uniform`` / ``frame_noise``: injected noise, per step or per frame, as `StreamingSR` takes it; without it the
-    default mode draws per forward call, so its frames depend on the chunk size (the shared mode's never do)."""
+    default mode draws per forward call, so its frames depend on the chunk size (the shared mode's never do).  ``msssim``: with
+    ground truth, per-frame five-scale MS-SSIM (`metrics.msssim_u8`) as well; the region inside the border must then be at least
+    `metrics.msssim_min_size` each way."""
     workers, chunk = _check_args(workers, quantise, chunk)
     t_start = time.perf_counter()
     lr = _PngSource(lr_dir)
@@ -324,6 +351,8 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
     if gt_dir is not None:
         gt = _PngSource(gt_dir, ["%05d.png" % t for t in range(lr.frames)])
         _check_regions(lr, gt, crop_border, 0)
+        if msssim:
+            _check_msssim(lr, gt, crop_border)
     if save_dir is not None:
         sink = _PngSink(save_dir, lr.names, png_level)   # the result PNGs take the LR frames' names (test_LD_37.py:180)
 
@@ -332,9 +361,9 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
         return StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"], gumbel_uniform=gumbel_uniform,
                            frame_noise=frame_noise), None
 
-    s, sse, _, ssim = _run_chunks(lr, load, gt, sink, chunk, share_compensation, crop_border, 0, quantise, workers)
-    psnr = _psnr(sse, lr.shape, gt and gt.shape, crop_border, 255)
-    return SequenceResult(psnr, ssim, _mean(psnr), _mean(ssim), lr.frames, s.seconds, time.perf_counter() - t_start)
+    s, sse, _, ssim, ms = _run_chunks(lr, load, gt, sink, chunk, share_compensation, crop_border, 0, quantise, workers, msssim)
+    psnr, ms = _psnr(sse, lr.shape, gt and gt.shape, crop_border, 255), M.msssim_from_components(ms)
+    return SequenceResult(psnr, ssim, _mean(psnr), _mean(ssim), lr.frames, s.seconds, time.perf_counter() - t_start, ms, _mean(ms))
 
 
 class YuvResult(NamedTuple):
@@ -351,12 +380,14 @@ class YuvResult(NamedTuple):
     frames: int
     seconds_forward: float      # StreamingSR.seconds
     seconds_total: float        # the whole call
+    msssim: np.ndarray = _NO_FRAMES                 # of the luma; fp64 [T] with ``msssim=True`` and ground truth, else empty
+    mean_msssim: float = float("nan")
 
 
 def format_log_yuv(result: YuvResult, name: str) -> str:
     """`format_log` for a 4:2:0 result: the luma figures in the reference's places, then the chroma and the combined PSNR."""
     return '%s Average PSNR/SSIM: %.3f/%.5f PSNR-U/V/YUV: %.3f/%.3f/%.3f' % (
-        name, result.mean_psnr_y, result.mean_ssim_y, result.mean_psnr_u, result.mean_psnr_v, result.mean_psnr_yuv)
+        name, result.mean_psnr_y, result.mean_ssim_y, result.mean_psnr_u, result.mean_psnr_v, result.mean_psnr_yuv) + _msssim_suffix(result)
 
 
 def chroma_crop(crop_border: int, chroma: str = "420") -> int:
@@ -376,7 +407,7 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
                  save_yuv: Optional[str] = None, chunk: int = 8, share_compensation: bool = False, crop_border: int = 4,
                  quantise: str = "trunc", workers: int = 8, gumbel_uniform: Optional[Sequence] = None,
                  frame_noise: Optional[Sequence] = None, gt_size: Optional[Tuple[int, int]] = None,
-                 pix_fmt: str = "yuv420p") -> YuvResult:
+                 pix_fmt: str = "yuv420p", msssim: bool = False) -> YuvResult:
     """`evaluate_sequence` on raw 8-bit I420 files (cdfo_amd/yuv.py).  ``lr_yuv``: the LR sequence, ``width`` x ``height`` (even);
     the coding priors stay in ``side_dir``.  The luma goes the way it goes there (`StreamingSR.iter_chunked`, ``finish_frames`` with the
     PSNR numerator, ``ssim_u8``).  The chroma never passes through the model: per chunk the U and V planes of its centre frames are
@@ -389,7 +420,8 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     ``pix_fmt`` (`yuv.parse_pix_fmt`): the one format of ``lr_yuv``, ``gt_yuv`` and ``save_yuv``.  Above 8 bits the buffers hold
     uint16 samples and every figure is on the 0 .. 2**depth - 1 scale; the unfiltered planes and residuals in ``side_dir`` are at that
     depth too (16-bit PNGs, wider NPYs), the partition maps stay 8-bit masks.  ``gray*``: no chroma work, ``psnr_u`` / ``psnr_v`` are
-    empty and ``psnr_yuv`` is ``psnr_y``.  ``yuv444p*``: chroma planes of the luma's size, their border ``crop_border``."""
+    empty and ``psnr_yuv`` is ``psnr_y``.  ``yuv444p*``: chroma planes of the luma's size, their border ``crop_border``.
+    ``msssim``: as `evaluate_sequence`'s, on the luma (`metrics.msssim_u8` / `msssim_u16` with the format's peak)."""
     fmt = parse_pix_fmt(pix_fmt)
     workers, chunk = _check_args(workers, quantise, chunk)
     t_start = time.perf_counter()
@@ -405,6 +437,8 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
             if gt.frames != lr.frames:
                 raise ValueError(f"{gt_yuv} holds {gt.frames} frames of {Wgt}x{Hgt}, {lr_yuv} holds {lr.frames}")
             _check_regions(lr, gt, crop_border, ccrop)
+            if msssim:
+                _check_msssim(lr, gt, crop_border)
         writer = YuvWriter(save_yuv, 4 * width, 4 * height, fmt) if save_yuv is not None else None
 
         def load():
@@ -413,8 +447,8 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
             return StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"],
                                gumbel_uniform=gumbel_uniform, frame_noise=frame_noise, peak=fmt.peak), lr_c
 
-        s, sse_y, sse_c, ssim = _run_chunks(lr, load, gt, writer and _YuvSink(writer), chunk, share_compensation, crop_border, ccrop,
-                                            quantise, workers)
+        s, sse_y, sse_c, ssim, ms = _run_chunks(lr, load, gt, writer and _YuvSink(writer), chunk, share_compensation, crop_border, ccrop,
+                                                quantise, workers, msssim)
     finally:
         if writer is not None:
             writer.close()
@@ -423,8 +457,9 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     py = _psnr(sse_y, lr.shape, gt and gt.shape, crop_border, fmt.peak)
     pu, pv = (_psnr(e, lr.chroma_shape, gt and gt.chroma_shape, ccrop, fmt.peak) for e in sse_c)
     pyuv = psnr_yuv(py, pu, pv) if lr.chroma_shape is not None else py
+    ms = M.msssim_from_components(ms)
     return YuvResult(py, pu, pv, ssim, pyuv, _mean(py), _mean(pu), _mean(pv), _mean(ssim), _mean(pyuv), lr.frames, s.seconds,
-                     time.perf_counter() - t_start)
+                     time.perf_counter() - t_start, ms, _mean(ms))
 
 
 def _write_synthetic(root: str, T: int, H: int, W: int, seed: int, put_lr, put_gt, peak: int = 255) -> str:

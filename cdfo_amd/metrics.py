@@ -10,6 +10,9 @@ with ``mode="trunc"``, then ``psnr_u8`` / ``ssim_u8`` below -- has the writer's 
 ``psnr_u8`` / ``ssim_u8`` compare two stacks of 8-bit frames over their common size (``cal_psnr_ssim``'s min_height / min_width,
 psnr_ssim.py:462-468).  PSNR is formed on the host in fp64 from the exact integer sum of squared differences, which makes it
 bit-identical to the fp64 restatement of the reference's calculate_psnr on the same integers.
+
+``msssim_u8`` / ``msssim_u16``: five-scale MS-SSIM of such stacks, the project's own definition (DESIGN.md section 5.000000000;
+tests/msssim_ref.py is its numpy statement).  The device leaves ten means per frame, the host combines them in fp64.
 """
 from __future__ import annotations
 
@@ -117,3 +120,110 @@ def ssim_u16(img1: torch.Tensor, img2: torch.Tensor, crop_border: int, peak: int
         raise ValueError(f"ssim_u16: peak must be an integer in 1 .. 65535, got {peak!r}")
     s, Hc, Wc = _partials_samples(img1, img2, crop_border, torch.uint16, peak)
     return s / float((Hc - 10) * (Wc - 10))
+
+
+# ---- MS-SSIM: five scales of the luma (DESIGN.md has the definition; the kernels are in csrc/finish.hip) ----
+msssim_min_size = 176                                   # level 4 still holds one 11 x 11 window: 176 >> 4 = 11
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)     # Wang, Simoncelli, Bovik 2003
+
+
+def msssim_from_components(c) -> np.ndarray:
+    """The combined value from the ten means, on the host in fp64: ``c`` [...,5,2] (numpy or a tensor) holds (M_cs, M_ssim) per
+    level; -> [...] prod_{j<4} max(M_cs[j], 0)^w[j] * max(M_ssim[4], 0)^w[4]."""
+    c = c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
+    c = c.astype(np.float64)
+    if c.shape[-2:] != (5, 2):
+        raise ValueError(f"components [...,5,2] expected, got {c.shape}")
+    m = np.maximum(np.concatenate([c[..., :4, 0], c[..., 4:, 1]], axis=-1), 0.0)
+    return np.prod(m ** np.array(MSSSIM_WEIGHTS, dtype=np.float64), axis=-1)
+
+
+def msssim_region(h1: int, w1: int, h2: int, w2: int, crop: int):
+    """(rows, columns) of level 0: the common size less the border.  ValueError below `msssim_min_size`."""
+    Hm, Wm = common_size(h1, w1, h2, w2)
+    Hc, Wc = Hm - 2 * crop, Wm - 2 * crop
+    if min(Hc, Wc) < msssim_min_size:
+        raise ValueError(f"MS-SSIM needs at least {msssim_min_size} x {msssim_min_size} samples inside the border for its five "
+                         f"scales, crop_border {crop} leaves {Hc} x {Wc} of the common {Hm} x {Wm}")
+    return Hc, Wc
+
+
+class MsssimScratch:
+    """What a call of `msssim_components` needs beside its operands, for up to ``frames`` pairs with a level 0 of ``rows`` x ``cols``
+    (`msssim_region`): the pyramid scratch, the buffer of partial sums and the five map sizes as a device tensor.  Calls that share
+    one must be ordered, which one stream does."""
+
+    def __init__(self, frames: int, rows: int, cols: int, device):
+        frames, rows, cols = int(frames), int(rows), int(cols)
+        size = int(_lib.lib().cdfo_msssim_pyramid_bytes(rows, cols, frames))
+        if size <= 0:
+            raise ValueError(f"no MS-SSIM pyramid for {frames} frames of {rows} x {cols}")
+        self.pyramid = torch.empty(size // 4, dtype=torch.float32, device=device)
+        self.frames, self.rows, self.cols, self.device = frames, rows, cols, self.pyramid.device
+        self.partial = torch.empty(frames * 10240, dtype=torch.float64, device=device)     # the library's "always suffices"
+        # the divisors are a device tensor: with a host scalar torch multiplies by the rounded reciprocal, and n ones would not average to 1
+        self.sizes = torch.tensor([[((rows >> j) - 10) * ((cols >> j) - 10)] for j in range(5)], dtype=torch.float64, device=device)
+
+
+def msssim_scratch(n: int, rows: int, cols: int, device) -> MsssimScratch:
+    """A `MsssimScratch` for ``n`` frame pairs: what `msssim_components` makes per call unless it is handed one."""
+    return MsssimScratch(n, rows, cols, device)
+
+
+def msssim_components(img1: torch.Tensor, img2: torch.Tensor, crop_border: int, peak: int = None,
+                      scratch: MsssimScratch = None) -> torch.Tensor:
+    """fp64 device tensor [N,5,2]: per frame and level (M_cs, M_ssim), the means of cs and of l * cs over the level's valid map.
+    ``peak`` None: uint8 stacks; else uint16 stacks of that peak.  With a ``scratch`` (`msssim_scratch`, for at least N frames of
+    this region on this device) nothing here allocates beyond the result or waits for the device."""
+    if peak is not None and (isinstance(peak, bool) or not isinstance(peak, int) or not 1 <= peak <= 65535):
+        raise ValueError(f"msssim_u16: peak must be an integer in 1 .. 65535, got {peak!r}")
+    kind = torch.uint8 if peak is None else torch.uint16
+    a, N, Ha, Wa, pa, sa = _sample_frames(img1, "img1", kind)
+    b, Nb, Hb, Wb, pb, sb = _sample_frames(img2, "img2", kind)
+    if N != Nb or a.device != b.device:
+        raise ValueError(f"the two stacks must hold the same number of frames on one device, got {N} and {Nb}")
+    crop = int(crop_border)
+    Hm, Wm = common_size(Ha, Wa, Hb, Wb)
+    Hc, Wc = Hm - 2 * crop, Wm - 2 * crop
+    nb = (C.c_int * 5)()
+    with on_device(a):
+        if scratch is None and min(Hc, Wc) >= msssim_min_size:
+            scratch = MsssimScratch(N, Hc, Wc, a.device)
+        if scratch is None:                             # a region below the minimum: the library says so
+            tail = (None, C.c_longlong(0), _vp(torch.empty(1, dtype=torch.float64, device=a.device)), 1, nb, _stream())
+        elif not isinstance(scratch, MsssimScratch) or scratch.device != a.device or scratch.frames < N or \
+                (scratch.rows, scratch.cols) != (Hc, Wc):
+            raise ValueError(f"scratch: a msssim_scratch for at least {N} frames of {Hc} x {Wc} on {a.device} expected")
+        else:
+            tail = (_vp(scratch.pyramid), C.c_longlong(4 * scratch.pyramid.numel()), _vp(scratch.partial), scratch.partial.numel(), nb,
+                    _stream())
+        entry = "cdfo_msssim_partials_u8" if peak is None else "cdfo_msssim_partials_u16"
+        _lib.check(getattr(_lib.lib(), entry)(_vp(a), pa, C.c_longlong(sa), Ha, Wa, _vp(b), pb, C.c_longlong(sb), Hb, Wb, N, crop,
+                                              *(() if peak is None else (peak,)), *tail), entry)
+    # the kernels pack the rows as [N][row]; frame n's holds level 0's (cs, l cs) pairs, then level 1's, ...: fixed-order fp64 sums
+    row = 2 * sum(nb)
+    rows, at, sums = scratch.partial[:N * row].view(N, row), 0, []
+    for j in range(5):
+        sums.append(rows[:, 2 * at:2 * (at + nb[j])].reshape(N, nb[j], 2).sum(dim=1))
+        at += nb[j]
+    return torch.stack(sums, dim=1) / scratch.sizes
+
+
+def _msssim(img1, img2, crop_border, peak, components):
+    c = msssim_components(img1, img2, crop_border, peak)
+    x = torch.from_numpy(np.atleast_1d(msssim_from_components(c))).to(c.device)
+    return (x, c) if components else x
+
+
+def msssim_u8(img1: torch.Tensor, img2: torch.Tensor, crop_border: int = 4, components: bool = False):
+    """Per-frame MS-SSIM of uint8 [N,H,W] device stacks over their common size less ``crop_border`` (fp64 device tensor [N]; the
+    combine runs on the host).  ``components=True``: (that, the fp64 device tensor [N,5,2] of (M_cs, M_ssim) per level);
+    ``[:,0,1]`` is `ssim_u8`'s value.  A region below `msssim_min_size` is an error of the library's (invalid argument)."""
+    return _msssim(img1, img2, crop_border, None, components)
+
+
+def msssim_u16(img1: torch.Tensor, img2: torch.Tensor, crop_border: int, peak: int, components: bool = False):
+    """`msssim_u8` for uint16 [N,H,W] device stacks of samples in 0 .. ``peak`` (2**depth - 1)."""
+    if peak is None:
+        raise ValueError("msssim_u16: uint16 samples need their peak (2**depth - 1)")
+    return _msssim(img1, img2, crop_border, peak, components)

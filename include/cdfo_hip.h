@@ -614,6 +614,29 @@ int cdfo_chroma_up4_u16(const unsigned short* src, int src_pitch, long long src_
                         int peak, const unsigned short* gt, int gt_pitch, long long gt_pstride, int Hgt, int Wgt, int crop,
                         long long* partial, int partial_cap, int* nblocks_out, void* stream);
 
+/* ---- five-scale MS-SSIM of the luma (finish.hip; cdfo_amd/metrics.py: msssim_u8, msssim_u16; DESIGN.md has the definition) ----
+ * cdfo_msssim_partials_u8 / _u16: two stacks of N frames as cdfo_metric_partials_u8 / cdfo_ssim_partials_u16 take them, compared over
+ *                     Hc x Wc = their common size less `crop` on every side; Hc, Wc >= CDFO_MSSSIM_MIN_SIZE, else CDFO_EINVAL (there is
+ *                     no metric with fewer scales).  Level 0 is that region, level j + 1 the 2x2 mean of level j (from the top-left
+ *                     sample, a trailing odd row or column dropped), exact.  Per level j = 0..4 and frame the call leaves two sums
+ *                     over the level's valid 11x11-Gaussian map of (Hc >> j) - 10 by (Wc >> j) - 10 positions: of
+ *                     cs = (2 s12 + C2) / (s1^2 + s2^2 + C2) and of l * cs, l = (2 m1 m2 + C1) / (m1^2 + m2^2 + C1), in fp64.
+ *                     partial: frame n's row is partial[n * row .. (n + 1) * row), row = 2 * (nblocks_out[0] + .. + nblocks_out[4]);
+ *                     in it level 0's nblocks_out[0] pairs (cs sum, l cs sum) come first, then level 1's, ...; the caller adds each
+ *                     level's pairs up in order and divides by the map's size.  nblocks_out: 5 ints.  partial_cap: capacity in
+ *                     doubles, N * 10240 always suffices (less is CDFO_EINVAL when it does not).  partial 8-byte aligned.
+ *                     pyramid: scratch of pyramid_bytes >= cdfo_msssim_pyramid_bytes(Hc, Wc, N), 4-byte aligned, overwritten by every
+ *                     call (calls that share it must be ordered, e.g. by one stream).  Three launches whatever N.
+ * cdfo_msssim_pyramid_bytes: 2 N * 4 * sum_{j=1..4} (Hc >> j)(Wc >> j); 0 for a region below the minimum or N <= 0. */
+#define CDFO_MSSSIM_MIN_SIZE 176
+long long cdfo_msssim_pyramid_bytes(int Hc, int Wc, int N);
+int cdfo_msssim_partials_u8(const unsigned char* a, int a_pitch, long long a_fstride, int Ha, int Wa, const unsigned char* b,
+                            int b_pitch, long long b_fstride, int Hb, int Wb, int N, int crop, float* pyramid, long long pyramid_bytes,
+                            double* partial, int partial_cap, int* nblocks_out, void* stream);
+int cdfo_msssim_partials_u16(const unsigned short* a, int a_pitch, long long a_fstride, int Ha, int Wa, const unsigned short* b,
+                             int b_pitch, long long b_fstride, int Hb, int Wb, int N, int crop, int peak, float* pyramid,
+                             long long pyramid_bytes, double* partial, int partial_cap, int* nblocks_out, void* stream);
+
 /* ---- optional per-launch HIP-event timing on the launch stream (bench.py's live roofline figures) ----------- */
 int cdfo_prof_begin(int max_records);
 int cdfo_prof_end(int* launches, double* ms, double* flops, double* bytes, int nkid);

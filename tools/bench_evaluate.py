@@ -4,6 +4,7 @@
     python tools/bench_evaluate.py --ssim [--frames N]                          the two SSIM kernels at 1080 x 1920
     python tools/bench_evaluate.py --yuv [--size T H W] [--chunk K] [--repeats R]    the PNG path against the raw 4:2:0 path
     python tools/bench_evaluate.py --yuv --pix-fmt NAME [--size T H W] ...           evaluate_yuv at NAME against 8-bit yuv420p
+    python tools/bench_evaluate.py --msssim [--yuv] [--size T H W] [--chunk K] [--repeats R]    MS-SSIM: the kernels, and the option on / off
 
 Sequence benchmark, one process, one warm-up pass then R passes each, medians: run_chunked alone; evaluate_sequence with metrics
 only; with metrics and PNG writing at 8 and 16 workers; and the per-chunk times of the finish kernel and the two 8-bit metric
@@ -13,7 +14,11 @@ files; run_chunked alone, then evaluate_sequence and evaluate_yuv end to end, me
 is the PNG path of this very run); the time the priors' PNGs and NPYs take to read, which both paths pay before their first chunk;
 and chroma_up4 per chunk from events.  --yuv --pix-fmt NAME (a format of cdfo_amd/yuv.py): evaluate_yuv with metrics and the result
 file, on 8-bit yuv420p and on NAME in the same process (the 8-bit run is the baseline), then the three 16-bit kernels against their
-8-bit twins on one chunk of 1080 x 1920 frames, from events."""
+8-bit twins on one chunk of 1080 x 1920 frames, from events.  --msssim: msssim_u8 / msssim_u16 beside ssim_u8 / ssim_u16 on one chunk
+of correlated 1080 x 1920 pairs, from events; then evaluate_sequence (with --yuv: evaluate_yuv) with metrics only, ``msssim`` off and
+on in alternating passes of one process.  (Against another commit there is no switch: export that commit into a directory of its own,
+build it there, and run this tool, or a pass set of evaluate_yuv, from each tree in fresh processes in alternation on one box; DESIGN.md
+section 5.000000000 has the figures taken that way.)"""
 import os
 import sys
 import tempfile
@@ -213,8 +218,49 @@ def pix_fmt():
               f"x{m16 / m8:.3f}, byte ratio {ratio}", flush=True)
 
 
+def msssim():
+    from arch.SIDECVSR_our import CVSR_V8
+    from cdfo_amd import metrics as M
+    from cdfo_amd.evaluate import evaluate_sequence, evaluate_yuv, write_synthetic_sequence, write_synthetic_sequence_yuv
+    T, H, W = _arg("--size", 3, [64, 270, 480])
+    chunk, reps = _arg("--chunk", 1, 8), _arg("--repeats", 1, 5)
+    rs = np.random.RandomState(0)
+    for peak, kind, sigma in ((255, np.uint8, 20), (1023, np.uint16, 80)):
+        a = rs.randint(0, peak + 1, (chunk, 4 * H, 4 * W))
+        b = np.clip(a + np.rint(sigma * rs.randn(*a.shape)).astype(np.int64), 0, peak)
+        a, b = torch.from_numpy(a.astype(kind)).cuda(), torch.from_numpy(b.astype(kind)).cuda()
+        one, many = (M.ssim_u8, M.msssim_u8) if peak == 255 else (lambda *x: M.ssim_u16(*x, peak), lambda *x: M.msssim_u16(*x, peak))
+        scratch = M.msssim_scratch(chunk, *M.msssim_region(4 * H, 4 * W, 4 * H, 4 * W, 4), a.device)
+        (ss, ps), (ms, pm) = _median_ms(lambda: one(a, b, 4)), _median_ms(lambda: many(a, b, 4))
+        mc, pc = _median_ms(lambda: M.msssim_components(a, b, 4, None if peak == 255 else peak, scratch))
+        print(f"chunk of {chunk} pairs {4 * H}x{4 * W}, peak {peak}, crop 4 (wrapper included), median of 5: SSIM {ss:.3f} ms (passes "
+              f"{' '.join('%.3f' % x for x in ps)}); MS-SSIM {ms:.3f} ms (passes {' '.join('%.3f' % x for x in pm)}): x{ms / ss:.3f}; "
+              f"its ten means alone, as the evaluators call it (scratch held, no host combine) {mc:.3f} ms (passes "
+              f"{' '.join('%.3f' % x for x in pc)}): x{mc / ss:.3f}", flush=True)
+    model = CVSR_V8().cuda().eval()
+    with tempfile.TemporaryDirectory() as tmp:
+        if "--yuv" in sys.argv:
+            lr, side, gt = write_synthetic_sequence_yuv(tmp, T, H, W)
+            run = lambda on: evaluate_yuv(model, lr, W, H, side, gt_yuv=gt, chunk=chunk, msssim=on)
+        else:
+            lr, side, gt = write_synthetic_sequence(tmp, T, H, W)
+            run = lambda on: evaluate_sequence(model, lr, side, gt_dir=gt, chunk=chunk, msssim=on)
+        run(False), run(True)
+        fps = {False: [], True: []}
+        for _ in range(reps):                                # alternating passes: drift of the box falls on both alike
+            for on in (False, True):
+                r = run(on)
+                fps[on].append(r.frames / r.seconds_total)
+        off, on = float(np.median(fps[False])), float(np.median(fps[True]))
+        print(f"{'evaluate_yuv' if '--yuv' in sys.argv else 'evaluate_sequence'}, metrics only, {T} frames {H}x{W}, chunk {chunk}, end to "
+              f"end frames/s: msssim off per pass {' '.join('%.2f' % f for f in fps[False])}; median {off:.2f}; msssim on per pass "
+              f"{' '.join('%.2f' % f for f in fps[True])}; median {on:.2f} ({on / off:.4f} of off)", flush=True)
+
+
 if __name__ == "__main__":
-    if "--ssim" in sys.argv:
+    if "--msssim" in sys.argv:
+        msssim()
+    elif "--ssim" in sys.argv:
         ssim_ab()
     elif "--yuv" in sys.argv:
         pix_fmt() if "--pix-fmt" in sys.argv else yuv()
