@@ -7,9 +7,12 @@
 //   colconv9    : directH1_conv, the 9-tap conv along H on sparse_q (arch.py:2225).
 //   seq_attn    : softmax(Q Q^T) V over a row, a column or an 8x8 window, one query per lane, keys streamed through
 //                 wave-uniform (scalar) loads, online softmax in registers.
-#include "numeric.h"
+#include "stream_ring.h"
 
 namespace {
+
+typedef _Float16 attn_f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 attn_f16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int ZS = 65;  // LDS pitch for the [pixel][channel] logits (conflict-free both ways)
 constexpr int QS = 72;  // 4 zero floats on both sides of the 64 channels for the 9-tap channel conv
@@ -122,6 +125,282 @@ __global__ __launch_bounds__(256) void rdab_prep_kernel(const float* __restrict_
       *reinterpret_cast<f32x4*>(ps + c4 * 4) = a;
       *reinterpret_cast<f32x4*>(pv + c4 * 4) = bq;
     }
+  }
+}
+
+// ---- RDAB.input_conv (1x1, 64 -> 128: q | v) and rdab_prep in ONE pass: the 128-channel product never reaches HBM.
+// The persistent LDS-DMA stream of conv1x1_stream.hip (NCB = 2, one K block): a wave's 32 pixels x 128 channels are in its
+// accumulators after the split-bf16 product -- the same instructions in the same order as conv1x1_stream_kernel<2>, so q and v carry
+// the bits that kernel would have stored.  Lane (pixel r, half h) holds channels 16 s + 8 h .. + 7 (s = 0..3) of q and of v, and
+// everything rdab_prep does is local to the pixel:
+//   * the weights E_c / (-log u_c) of the lane's 32 channels (noise read or drawn for exactly those channels);
+//   * their sum in rdab_prep's order: 16 sequential terms per quarter -- lane h = 0 adds its 8, hands the partial sum to lane h = 1,
+//     which adds its 8 and hands the total back --, then (q0 + q1) + (q2 + q3), which is what the xor-shuffles 1 and 2 form in every lane;
+//   * qwin = (1 - mask) q and the window V straight from registers;
+//   * the 9-tap channel convolutions need 4 channels on either side of a lane's 8: mask * q, then v, go through the stage the K
+//     block has just been read from (free until the request after next), in the ring's own swizzled layout, wave-privately.
+// V outputs (vrow: VT, window V: WT) as fp32 or, _Float16, rounded once -- the rounding the single-pass attentions apply while staging.
+struct rf_args {
+  const float* x; int ldx;                       // [B][P][>= 64]
+  const float* w; const float* bias;             // input_conv: packed [64/4][128][4], bias [128] or null
+  const float* vmax; const float* noise; const float* wW; const float* bW;
+  long long P; int tiles_per_image; long long tiles; int ns;
+  float* sq; int lds_; float* qwin; int ldw;
+  void* vrow; int ldv; void* vwin; int ldvw;     // fp32 or fp16, pitches in elements
+  unsigned long long seed; unsigned draw; float* noise_out; const unsigned long long* seed_dev;
+};
+
+template <bool RNG, typename VT, typename WT>      // VT: vrow, WT: window V
+__global__ __launch_bounds__(ST_THREADS) void rdab_prep_kernel_fused(rf_args a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char rf_smem[];
+  constexpr int NCB = 2;
+  constexpr bool VH = sizeof(VT) == 2, WH = sizeof(WT) == 2;
+  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int NS = a.ns;
+  // LDS map: weights hi [4 chunks][2 k-halves][128 rows][8 bf16] | lo (same) | bias [128] | E [64] | 4 waves x NS stages
+  constexpr int w_half = 4 * 2 * NCB * 64 * 16;
+  constexpr int ring_off = 2 * w_half + NCB * 64 * 4 + 64 * 4;
+  unsigned char* sWh = rf_smem;
+  unsigned char* sWl = rf_smem + w_half;
+  float* sBias = reinterpret_cast<float*>(rf_smem + 2 * w_half);
+  float* ev = sBias + NCB * 64;
+  unsigned char* ring = rf_smem + ring_off + wave * NS * ST_STAGE;
+  const unsigned ring_lds = (unsigned)(unsigned long long)(rf_smem) + ring_off + wave * NS * ST_STAGE;
+
+  const long long t_lo = a.tiles * blockIdx.x / gridDim.x, t_hi = a.tiles * (blockIdx.x + 1) / gridDim.x;
+  if (t_lo >= t_hi) return;
+
+  int d_px[8], d_part[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int s = 64 * k + lane, p = s >> 4;
+    d_px[k] = p;
+    d_part[k] = (s & 15) ^ (p & 15);
+  }
+  auto part_off = [&](int q) { return r * 256 + ((q ^ (r & 15)) << 4); };
+
+  // ---- the weights (the same for every image) -> LDS, split bf16 hi | lo, rows permuted (as conv1x1_stream_kernel)
+  for (int i = tid; i < 16 * NCB * 64; i += ST_THREADS) {
+    const int rowpos = i % (NCB * 64), kg = i / (NCB * 64);
+    const int n = st_chan_of_row(rowpos);
+    const f32x4 wv = *reinterpret_cast<const f32x4*>(a.w + ((long long)kg * (NCB * 64) + n) * 4);
+    const int c = kg >> 2, hh = (kg >> 1) & 1, j0 = (kg & 1) * 4;
+    u32x2 hi, lo;
+    hi[0] = pack_bf16(wv[0], wv[1]); hi[1] = pack_bf16(wv[2], wv[3]);
+    lo[0] = pack_bf16(wv[0] - bf16_round(wv[0]), wv[1] - bf16_round(wv[1]));
+    lo[1] = pack_bf16(wv[2] - bf16_round(wv[2]), wv[3] - bf16_round(wv[3]));
+    const int off = ((c * 2 + hh) * (NCB * 64) + rowpos) * 16 + j0 * 2;
+    *reinterpret_cast<u32x2*>(sWh + off) = hi;
+    *reinterpret_cast<u32x2*>(sWl + off) = lo;
+  }
+  for (int i = tid; i < NCB * 64; i += ST_THREADS) sBias[i] = a.bias ? a.bias[i] : 0.f;
+
+  float w9[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) w9[t] = a.wW[t];
+  const float bb = a.bW[0];
+  unsigned long long seed = a.seed;
+  if (RNG && a.seed_dev) seed = *a.seed_dev;       // key in device memory (graph replays: rewritten between replays)
+
+  for (long long img_t0 = t_lo; img_t0 < t_hi;) {
+    const int b = (int)(img_t0 / a.tiles_per_image);
+    const long long img_end = (long long)(b + 1) * a.tiles_per_image;
+    const long long seg_hi = img_end < t_hi ? img_end : t_hi;           // tiles [img_t0, seg_hi) belong to image b
+    __syncthreads();                                                     // the previous image's E has been read; no DMA is in flight here
+    if (tid < 64) {                                                      // E_c = exp(v_c - max v), as rdab_prep_kernel
+      float vm = a.vmax[(long long)b * 64];
+      for (int c = 1; c < 64; ++c) vm = fmaxf(vm, a.vmax[(long long)b * 64 + c]);
+      ev[tid] = expf(a.vmax[(long long)b * 64 + tid] - vm);
+    }
+    __syncthreads();
+
+    const long long n_items = seg_hi - img_t0;                           // one item = one tile (a single K block)
+    long long issued = 0;
+    auto issue = [&](long long it) {
+      const long long p0 = (img_t0 + it - (long long)b * a.tiles_per_image) * 128 + wave * 32;      // first pixel (inside image b)
+      const long long rows_left = a.P - p0;                              // may be <= 0: everything out of range
+      const float* base = a.x + ((long long)b * a.P + (rows_left > 0 ? p0 : 0)) * a.ldx;
+      const unsigned long long pb = reinterpret_cast<unsigned long long>(base);
+      i32x4 rsrc;
+      rsrc[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)pb);
+      rsrc[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(pb >> 32));
+      const long long bytes = rows_left > 0 ? (rows_left < 32 ? rows_left : 32) * (long long)a.ldx * 4 : 0;
+      rsrc[2] = __builtin_amdgcn_readfirstlane((int)bytes);              // lanes beyond the image read zeros
+      rsrc[3] = 0x00020000;
+      unsigned voff[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) voff[q] = (unsigned)(d_px[q] * a.ldx * 4 + d_part[q] * 16);
+      st_dma8(voff, rsrc, __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(it % NS) * ST_STAGE));
+    };
+    for (; issued < NS - 1 && issued < n_items; ++issued) issue(issued);
+
+    for (long long it = 0; it < n_items; ++it) {
+      st_wait_landed(issued - it - 1);
+      unsigned char* st = ring + (it % NS) * ST_STAGE;
+      f32x16 acc[NCB][2];
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc[cb][ni][e] = 0.f;
+      // ---- the K block, as conv1x1_stream_kernel: this lane's operand = channels c*16 + h*8 .. +7 of pixel r
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(st + part_off(c * 4 + h * 2));
+        const f32x4 v1 = *reinterpret_cast<const f32x4*>(st + part_off(c * 4 + h * 2 + 1));
+        union { unsigned u[4]; bf16x8_t v; } ph, pl;
+        ph.u[0] = pack_bf16(v0[0], v0[1]); ph.u[1] = pack_bf16(v0[2], v0[3]);
+        ph.u[2] = pack_bf16(v1[0], v1[1]); ph.u[3] = pack_bf16(v1[2], v1[3]);
+        pl.u[0] = pack_bf16(v0[0] - bf16_round(v0[0]), v0[1] - bf16_round(v0[1]));
+        pl.u[1] = pack_bf16(v0[2] - bf16_round(v0[2]), v0[3] - bf16_round(v0[3]));
+        pl.u[2] = pack_bf16(v1[0] - bf16_round(v1[0]), v1[1] - bf16_round(v1[1]));
+        pl.u[3] = pack_bf16(v1[2] - bf16_round(v1[2]), v1[3] - bf16_round(v1[3]));
+        const int wrow = (c * 2 + h) * (NCB * 64) + r;
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+          for (int ni = 0; ni < 2; ++ni) {
+            const bf16x8_t wh = *reinterpret_cast<const bf16x8_t*>(sWh + (wrow + cb * 64 + ni * 32) * 16);
+            const bf16x8_t wl = *reinterpret_cast<const bf16x8_t*>(sWl + (wrow + cb * 64 + ni * 32) * 16);
+            acc[cb][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, pl.v, acc[cb][ni], 0, 0, 0);
+            acc[cb][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, ph.v, acc[cb][ni], 0, 0, 0);
+            acc[cb][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, ph.v, acc[cb][ni], 0, 0, 0);
+          }
+      }
+      // the next request overwrites the stage of item it - 1; this item's fragment reads have returned (the MFMAs consumed them)
+      if (issued < n_items) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); issue(issued); ++issued; }
+
+      const long long pin = (img_t0 + it - (long long)b * a.tiles_per_image) * 128 + wave * 32 + r;
+      if (pin - r >= a.P) continue;                  // P % 32 == 0: a wave's 32 pixels lie inside the image or all beyond it
+      const long long gp = (long long)b * a.P + pin;
+      // acc[cb][s >> 1][8 (s & 1) + k] = channel 16 s + 8 h + k of q (cb = 0) / v (cb = 1), + bias
+      float ez[4][8];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int c0 = 16 * s + 8 * h;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          acc[0][s >> 1][8 * (s & 1) + k] += sBias[c0 + k];
+          acc[1][s >> 1][8 * (s & 1) + k] += sBias[64 + c0 + k];
+        }
+        // ---- weights E_c / (-log u_c)
+        if (RNG) {
+#pragma unroll
+          for (int j2 = 0; j2 < 2; ++j2) {
+            unsigned o[4];
+            philox4x32_10((unsigned)pin, (unsigned)b, (unsigned)((c0 >> 2) + j2), a.draw, (unsigned)seed, (unsigned)(seed >> 32), o);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const int c = c0 + 4 * j2 + k;
+              const float u = ((float)(o[k] >> 8) + 0.5f) * (1.f / 16777216.f);
+              if (a.noise_out) a.noise_out[((long long)b * 64 + c) * a.P + pin] = u;
+              ez[s][4 * j2 + k] = ev[c] / (-logf(u));
+            }
+          }
+        } else {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            const float u = a.noise[((long long)b * 64 + c0 + k) * a.P + pin];
+            ez[s][k] = ev[c0 + k] / (-logf(u));
+          }
+        }
+      }
+      // ---- the pixel's sum in rdab_prep's order
+      float qs[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        float p = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) p += ez[s][k];                     // h = 0: terms 0..7 of the quarter
+        float f = __shfl_xor(p, 32, 64);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) f += ez[s][k];                     // h = 1: ... + terms 8..15
+        const float fo = __shfl_xor(f, 32, 64);
+        qs[s] = h ? f : fo;
+      }
+      const float half_s = 0.5f * ((qs[0] + qs[1]) + (qs[2] + qs[3]));
+      // ---- mask; qwin and the window V from registers; mask * q replaces q in the accumulators
+      {
+        float* pw = a.qwin + gp * a.ldw;
+        WT* pvw = static_cast<WT*>(a.vwin) + gp * a.ldvw;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int c0 = 16 * s + 8 * h;
+          float wq[8];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            const float mk = (ez[s][k] >= half_s) ? 1.f : 0.f;
+            const float qv = acc[0][s >> 1][8 * (s & 1) + k];
+            acc[0][s >> 1][8 * (s & 1) + k] = mk * qv;
+            wq[k] = (1.f - mk) * qv;
+          }
+          const f32x4 w0 = {wq[0], wq[1], wq[2], wq[3]}, w1 = {wq[4], wq[5], wq[6], wq[7]};
+          *reinterpret_cast<f32x4*>(pw + c0) = w0;
+          *reinterpret_cast<f32x4*>(pw + c0 + 4) = w1;
+          if (WH) {
+            attn_f16x8 hv;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) hv[k] = (_Float16)acc[1][s >> 1][8 * (s & 1) + k];
+            *reinterpret_cast<attn_f16x8*>(pvw + c0) = hv;
+          } else {
+            const f32x4 x0 = {acc[1][s >> 1][8 * (s & 1)], acc[1][s >> 1][8 * (s & 1) + 1], acc[1][s >> 1][8 * (s & 1) + 2], acc[1][s >> 1][8 * (s & 1) + 3]};
+            const f32x4 x1 = {acc[1][s >> 1][8 * (s & 1) + 4], acc[1][s >> 1][8 * (s & 1) + 5], acc[1][s >> 1][8 * (s & 1) + 6], acc[1][s >> 1][8 * (s & 1) + 7]};
+            *reinterpret_cast<f32x4*>(pvw + c0) = x0;
+            *reinterpret_cast<f32x4*>(pvw + c0 + 4) = x1;
+          }
+        }
+      }
+      // ---- 9-tap cross-correlation along the channel axis (zero padded) + bias: mask * q -> sq, then v -> vrow
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");           // the other lanes' reads of the previous contents come first
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int q0 = 4 * s + 2 * h;
+          const f32x4 x0 = {acc[cb][s >> 1][8 * (s & 1)], acc[cb][s >> 1][8 * (s & 1) + 1], acc[cb][s >> 1][8 * (s & 1) + 2], acc[cb][s >> 1][8 * (s & 1) + 3]};
+          const f32x4 x1 = {acc[cb][s >> 1][8 * (s & 1) + 4], acc[cb][s >> 1][8 * (s & 1) + 5], acc[cb][s >> 1][8 * (s & 1) + 6], acc[cb][s >> 1][8 * (s & 1) + 7]};
+          *reinterpret_cast<f32x4*>(st + part_off(q0)) = x0;
+          *reinterpret_cast<f32x4*>(st + part_off(q0 + 1)) = x1;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");           // a wave's LDS operations execute in order: lane ^ 32's values are there
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int c0 = 16 * s + 8 * h, q0 = 4 * s + 2 * h;
+          const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+          f32x4 lf = *reinterpret_cast<const f32x4*>(st + part_off(q0 > 0 ? q0 - 1 : 0));
+          f32x4 rt = *reinterpret_cast<const f32x4*>(st + part_off(q0 + 2 < 16 ? q0 + 2 : 15));
+          lf = q0 > 0 ? lf : z4;
+          rt = q0 + 2 < 16 ? rt : z4;
+          float win[16];                                                  // channels c0 - 4 .. c0 + 11
+#pragma unroll
+          for (int k = 0; k < 4; ++k) { win[k] = lf[k]; win[12 + k] = rt[k]; }
+#pragma unroll
+          for (int k = 0; k < 8; ++k) win[4 + k] = acc[cb][s >> 1][8 * (s & 1) + k];
+          float o8[8];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            float s1 = bb;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) s1 = fmaf(w9[t], win[k + t], s1);
+            o8[k] = s1;
+          }
+          if (cb == 1 && VH) {
+            attn_f16x8 hv;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) hv[k] = (_Float16)o8[k];
+            *reinterpret_cast<attn_f16x8*>(static_cast<VT*>(a.vrow) + gp * a.ldv + c0) = hv;
+          } else {
+            float* po = cb == 0 ? a.sq + gp * a.lds_ : static_cast<float*>(a.vrow) + gp * a.ldv;
+            const f32x4 y0 = {o8[0], o8[1], o8[2], o8[3]}, y1 = {o8[4], o8[5], o8[6], o8[7]};
+            *reinterpret_cast<f32x4*>(po + c0) = y0;
+            *reinterpret_cast<f32x4*>(po + c0 + 4) = y1;
+          }
+        }
+      }
+    }
+    img_t0 = seg_hi;
   }
 }
 
@@ -263,8 +542,6 @@ __global__ __launch_bounds__(64) void seq_attn_kernel(const float* __restrict__ 
 //                     product is free, so V is staged TRANSPOSED ([channel][key slot], slot = 16u + 8h + j) in that
 //                     same order: a staging thread loads 4 keys x 4 channels, transposes 4x4 in registers and writes
 //                     8-byte runs of 4 keys; no data movement between the two products.
-typedef _Float16 attn_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 attn_f16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned attn_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned attn_u32x4 __attribute__((ext_vector_type(4)));
 
@@ -278,11 +555,16 @@ typedef unsigned attn_u32x4 __attribute__((ext_vector_type(4)));
 // (sum 1) and values rounded once to fp16: |error of an output| <= 2^-11 * sum_j p_j |v_j| <= 4.9e-4 * max|v| in the worst case,
 // ~1e-5 * |v| measured (random signs average); the scores, whose error the exponential amplifies, keep all three passes.  8 of the
 // 24 MFMAs per 32 x 32 tile, the lo halves of V's staging and of P's conversion, and half of V's fragment reads go away.
-template <int MODE, int NW, bool PV1 = false>   // MODE 0: sequence = image row, 1: image column, 2: 8x8 window (row-major inside the window)
+// VT = _Float16 (PV1 only): V arrives already rounded -- its producer stored (_Float16)v, the same single rounding the staging
+// thread applies to an fp32 V -- and goes to sV unconverted, ldv counted in halves.  OT = _Float16: the output leaves as
+// (_Float16)(o / l), the form in which the next attention's staging would round it (row attention -> V of the column attention).
+template <int MODE, int NW, bool PV1 = false, typename VT = float, typename OT = float>   // MODE 0: sequence = image row, 1: image column, 2: 8x8 window (row-major inside the window)
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void seq_attn_mfma_kernel(const float* __restrict__ q, int ldq,
-                                                                const float* __restrict__ v, int ldv,
-                                                                float* __restrict__ out, int ldo, int B, int H, int W,
+                                                                const VT* __restrict__ v, int ldv,
+                                                                OT* __restrict__ out, int ldo, int B, int H, int W,
                                                                 int nb, int tpb, int xcd_map) {
+  constexpr bool VH = sizeof(VT) == 2, OH = sizeof(OT) == 2;
+  static_assert(PV1 || !VH, "an fp16 V is the single-pass second product's operand");
   constexpr int KROW = 272;                                 // bytes per staged key row: 128 B hi | 128 B lo | 16 B pad
   constexpr int NT = NW * 64, SUB = NW / 4, KT = 32 * SUB, KQ = KT / 4;
   constexpr int K_BYTES = KT * KROW, V_BYTES = SUB * 64 * 128;
@@ -346,11 +628,16 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void seq_attn_mfma_kernel
   float m = -INFINITY, l = 0.f;                             // running maximum (log2 domain) and sum of this half-wave's keys
 
   // staging (4 float4 loads per thread and stage): the first NT/2 threads take V -- keys 4sm..4sm+3 x channels 4c..4c+3
-  // each --, the others K -- keys sm + KQ*s (s = 0..3) x channels 4c..4c+3
-  const bool st_v = tid < NT / 2;
-  const int sj = st_v ? tid : tid - NT / 2, sm = sj >> 4, sc4 = sj & 15;
-  const float* const sbase = (st_v ? v : q) + sc4 * 4;
-  const int sld = st_v ? ldv : ldq;
+  // each --, the others K -- keys sm + KQ*s (s = 0..3) x channels 4c..4c+3.
+  // fp16 V: a 16-byte load is 8 channels of a key, so the first NT/4 threads cover the stage's V (keys 4sm..4sm+3 x channels
+  // 8c..8c+7); the next NT/4 repeat their loads and write nothing -- one instruction stream for every thread, no branch around the
+  // loads (a branch there made hipcc wait for them where the paths meet instead of behind the stage's products; sharing the writes
+  // between the two quarters, four channels each, measured no better)
+  const bool st_v = tid < NT / 2, vh_t = VH && st_v;
+  const int sj = st_v ? tid : tid - NT / 2, sjv = sj & (NT / 4 - 1);
+  const int sm = vh_t ? sjv >> 3 : sj >> 4, sc4 = vh_t ? 2 * (sjv & 7) : sj & 15;        // sc4: the first 4-channel group
+  const float* const sbase = (st_v ? reinterpret_cast<const float*>(v) : q) + (vh_t ? sc4 * 2 : sc4 * 4);
+  const int sld = vh_t ? ldv >> 1 : (st_v ? ldv : ldq);                                  // in floats
   f32x4 rs[4];
   auto load_tile = [&](int t0) {
 #pragma unroll
@@ -365,6 +652,20 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void seq_attn_mfma_kernel
       // keys 4m..4m+3 of sub-tile sm>>3 = slots 16u + 8hh + 4g + (0..3) with m = sm&7, u = m>>2, hh = m&1, g = (m&3)>>1
       const int mm = sm & 7, c = 2 * (mm >> 2) + (mm & 1), g = (mm & 3) >> 1;
       unsigned char* const vb = sV + buf * V_BYTES + (sm >> 3) * 8192 + g * 8;
+      if (VH) {                                             // rounded by the producer: 8 channels x keys 4m .. 4m+3, as they are
+        if (sj < NT / 4) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const int ch = 4 * sc4 + e, swz = (ch >> 1) & 7;
+            unsigned k[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) k[s] = __float_as_uint(rs[s][e >> 1]);
+            const attn_u32x2 vh = {(e & 1) ? (k[0] >> 16) | (k[1] & 0xffff0000u) : (k[0] & 0xffffu) | (k[1] << 16),
+                                   (e & 1) ? (k[2] >> 16) | (k[3] & 0xffff0000u) : (k[2] & 0xffffu) | (k[3] << 16)};
+            *reinterpret_cast<attn_u32x2*>(vb + ch * 128 + ((c ^ swz) * 16)) = vh;
+          }
+        }
+      } else
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int ch = 4 * sc4 + e, swz = (ch >> 1) & 7;
@@ -496,33 +797,64 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void seq_attn_mfma_kernel
     l += __shfl_xor(l, 32, 64);
     const float inv = 1.f / l;
     if (q_ok) {
-      float* po = out + qpix * ldo;
+      OT* po = out + qpix * ldo;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {                          // rows 8g+4h .. +3 of each 32-channel tile
         f32x4 a0, a1;
 #pragma unroll
         for (int e = 0; e < 4; ++e) { a0[e] = o0[4 * g + e] * inv; a1[e] = o1[4 * g + e] * inv; }
-        *reinterpret_cast<f32x4*>(po + 8 * g + 4 * h) = a0;
-        *reinterpret_cast<f32x4*>(po + 32 + 8 * g + 4 * h) = a1;
+        if (OH) {
+          // The fp32 products are pinned in their registers first: hipcc otherwise merges product and conversion into ONE
+          // v_fma_mixlo_f16, which rounds the exact product -- not the fp32 value that the fp32 form stores and the next
+          // attention's staging rounds (an empty statement, no instruction)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { asm("" : "+v"(a0[e])); asm("" : "+v"(a1[e])); }
+          const attn_f16x4 h0 = {(_Float16)a0[0], (_Float16)a0[1], (_Float16)a0[2], (_Float16)a0[3]};
+          const attn_f16x4 h1 = {(_Float16)a1[0], (_Float16)a1[1], (_Float16)a1[2], (_Float16)a1[3]};
+          *reinterpret_cast<attn_f16x4*>(po + 8 * g + 4 * h) = h0;
+          *reinterpret_cast<attn_f16x4*>(po + 32 + 8 * g + 4 * h) = h1;
+        } else {
+          *reinterpret_cast<f32x4*>(po + 8 * g + 4 * h) = a0;
+          *reinterpret_cast<f32x4*>(po + 32 + 8 * g + 4 * h) = a1;
+        }
       }
     }
   }
 }
 
-template <int MODE, int NW, bool PV1 = false>
-int seq_attn_launch(const float* q, int ldq, const float* v, int ldv, float* out, int ldo, int B, int H, int W, hipStream_t st) {
+template <int MODE, int NW, bool PV1 = false, typename VT = float, typename OT = float>
+int seq_attn_launch(const float* q, int ldq, const VT* v, int ldv, OT* out, int ldo, int B, int H, int W, hipStream_t st) {
   static CdfoAttrOnce once;
   constexpr int SUB = NW / 4, LDSB = 2 * (32 * SUB * 272 + SUB * 64 * 128);
-  const hipError_t e = cdfo_set_max_lds(once, reinterpret_cast<const void*>(&seq_attn_mfma_kernel<MODE, NW, PV1>), LDSB);
+  const hipError_t e = cdfo_set_max_lds(once, reinterpret_cast<const void*>(&seq_attn_mfma_kernel<MODE, NW, PV1, VT, OT>), LDSB);
   if (e != hipSuccess) return (int)e;
   const int L = MODE == 0 ? W : (MODE == 1 ? H : 64);
   const int ntq = cdiv(L, 32), nb = cdiv(ntq, NW), tpb = cdiv(ntq, nb);
   const long long nseq = MODE == 0 ? (long long)B * H : (MODE == 1 ? (long long)B * W : (long long)B * (H / 8) * (W / 8));
   if (nseq * nb >= (1ll << 31)) return CDFO_EINVAL;
   static const int xcd_map = cdfo_switch("CDFO_ATTN_XCD", 1);   // developer A/B switch
-  hipLaunchKernelGGL((seq_attn_mfma_kernel<MODE, NW, PV1>), dim3((unsigned)(nseq * nb)), dim3(NW * 64), LDSB, st, q, ldq, v, ldv,
+  hipLaunchKernelGGL((seq_attn_mfma_kernel<MODE, NW, PV1, VT, OT>), dim3((unsigned)(nseq * nb)), dim3(NW * 64), LDSB, st, q, ldq, v, ldv,
                      out, ldo, B, H, W, nb, tpb, (nb > 1 && xcd_map) ? 1 : 0);
   return 0;
+}
+
+// 8-wave workgroups amortise the staging over twice the queries, but only if the sequence's 32-query tiles fill them:
+// 272 keys = 9 tiles = 2 x 8 waves at 56 % or 3 x 4 waves at 75 % (column attention at 24 x 272 x 480: 1.61 vs 1.35 ms;
+// row attention, 480 keys: 1.67 ms with 8 waves, 1.86 with 4).  The strided key rows of the column form are NOT what
+// it waits for: the same products over transposed tensors (contiguous rows of 272 keys) took 1.50 ms.
+bool seq_attn_wide(int L) {
+  const int ntq = cdiv(L, 32);
+  static const int force_nw = cdfo_switch("CDFO_ATTN_NW", 0);     // developer switch (4 / 8)
+  return force_nw ? force_nw == 8 : L > 128 && (double)ntq / (cdiv(ntq, 8) * 8) >= (double)ntq / (cdiv(ntq, 4) * 4) - 0.1;
+}
+
+// the single-pass forms (modes 20 / 21 / 22) over the operand types
+template <int MODE, typename VT, typename OT>
+int seq_attn_pv1(const float* q, int ldq, const VT* v, int ldv, OT* out, int ldo, int B, int H, int W, hipStream_t st) {
+  if constexpr (MODE != 2) {
+    if (seq_attn_wide(MODE == 0 ? W : H)) return seq_attn_launch<MODE, 8, true, VT, OT>(q, ldq, v, ldv, out, ldo, B, H, W, st);
+  }
+  return seq_attn_launch<MODE, 4, true, VT, OT>(q, ldq, v, ldv, out, ldo, B, H, W, st);
 }
 
 }  // namespace
@@ -567,6 +899,50 @@ extern "C" int cdfo_rdab_prep_rng_dev(const float* xq, int ldx, const float* vma
   return 0;
 }
 
+// RDAB.input_conv + rdab_prep in one launch (rdab_prep_kernel_fused): x [B][P][ldx >= 64] fp32, w_packed / bias the convolution's
+// packed [16][128][4] weights and [128] bias (null: none).  noise != null: the injected [B][64][P] draws (cdfo_rdab_prep); else Philox
+// with (seed_dev ? *seed_dev : seed, draw) and the optional noise_out (cdfo_rdab_prep_rng / _rng_dev).  v_f16 bit 0: vrow, bit 1: vwin
+// (the v half of the product, which the two-kernel path reads from xq) is fp16 with its pitch in halves.  Results equal those of
+// cdfo_conv1x1_bf16x3's streaming kernel followed by cdfo_rdab_prep* bit for bit (fp16: rounded once).
+extern "C" int cdfo_rdab_prep_fused(const float* x, int ldx, const float* w_packed, const float* bias, const float* vmax,
+                                    const float* noise, long long seed, const void* seed_dev, int draw, float* noise_out,
+                                    const float* wW, const float* bW, int B, long long P, float* sq, int lds_, void* vrow, int ldv,
+                                    float* qwin, int ldw, void* vwin, int ldvw, int v_f16, void* stream) {
+  if (B <= 0 || P <= 0 || P % 64 || P >= (1ll << 32) || ldx < 64 || ldx % 4 || (long long)ldx * 4 * 32 >= (1ll << 31) || lds_ % 4 ||
+      ldw % 4 || ldv % 8 || ldvw % 8 || !x || !w_packed || !vmax || !wW || !bW)
+    return CDFO_EINVAL;
+  if ((P + 127) / 128 > 0x7fffffff / 2) return CDFO_EINVAL;
+  if (!aligned16(x) || !aligned16(w_packed) || !aligned16(sq) || !aligned16(vrow) || !aligned16(qwin) || !aligned16(vwin) ||
+      (reinterpret_cast<uintptr_t>(seed_dev) & 7u))
+    return CDFO_EALIGN;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  rf_args s{};
+  s.x = x; s.ldx = ldx; s.w = w_packed; s.bias = bias; s.vmax = vmax; s.noise = noise; s.wW = wW; s.bW = bW;
+  s.P = P; s.ns = 3;
+  s.sq = sq; s.lds_ = lds_; s.qwin = qwin; s.ldw = ldw; s.vrow = vrow; s.ldv = ldv; s.vwin = vwin; s.ldvw = ldvw;
+  s.seed = (unsigned long long)seed; s.draw = (unsigned)draw; s.noise_out = noise ? nullptr : noise_out;
+  s.seed_dev = static_cast<const unsigned long long*>(seed_dev);
+  int grid;
+  if (!st_tiling(B, P, s.tiles_per_image, s.tiles, grid)) return CDFO_EINVAL;
+  const int lds = st_lds_bytes(1, 2, s.ns) + 64 * 4;
+  const double px = (double)B * P;
+  if (v_f16 < 0 || v_f16 > 3) return CDFO_EINVAL;
+  CdfoProfScope prof(st, KID_RDAB_PREP, 2.0 * px * 128 * 64,
+                     px * (4.0 * (64 + 128 + (noise ? 64 : 0)) + ((v_f16 & 1) ? 2.0 : 4.0) * 64 + ((v_f16 & 2) ? 2.0 : 4.0) * 64));
+  static CdfoAttrOnce once[8];
+  typedef _Float16 h;
+  switch ((noise ? 0 : 4) + v_f16) {
+    case 0: return st_launch(rdab_prep_kernel_fused<false, float, float>, once[0], grid, lds, st, s);
+    case 1: return st_launch(rdab_prep_kernel_fused<false, h, float>, once[1], grid, lds, st, s);
+    case 2: return st_launch(rdab_prep_kernel_fused<false, float, h>, once[2], grid, lds, st, s);
+    case 3: return st_launch(rdab_prep_kernel_fused<false, h, h>, once[3], grid, lds, st, s);
+    case 4: return st_launch(rdab_prep_kernel_fused<true, float, float>, once[4], grid, lds, st, s);
+    case 5: return st_launch(rdab_prep_kernel_fused<true, h, float>, once[5], grid, lds, st, s);
+    case 6: return st_launch(rdab_prep_kernel_fused<true, float, h>, once[6], grid, lds, st, s);
+    default: return st_launch(rdab_prep_kernel_fused<true, h, h>, once[7], grid, lds, st, s);
+  }
+}
+
 extern "C" int cdfo_colconv9(const float* in, int ldi, const float* wH, const float* bH, int B, int H, int W, float* out,
                              int ldo, void* stream) {
   if (B <= 0 || ldi % 4 || ldo % 4) return CDFO_EINVAL;
@@ -590,22 +966,10 @@ extern "C" int cdfo_seq_attn(const float* q, int ldq, const float* v, int ldv, f
   const bool pv1 = mode >= 20 && mode <= 22;           // modes 20 / 21 / 22: modes 0 / 1 / 2 with the single-fp16 second product (PV1)
   if (pv1) mode -= 20;
   if (mode == 0 || mode == 1) {
-    // 8-wave workgroups amortise the staging over twice the queries, but only if the sequence's 32-query tiles fill them:
-    // 272 keys = 9 tiles = 2 x 8 waves at 56 % or 3 x 4 waves at 75 % (column attention at 24 x 272 x 480: 1.61 vs 1.35 ms;
-    // row attention, 480 keys: 1.67 ms with 8 waves, 1.86 with 4).  The strided key rows of the column form are NOT what
-    // it waits for: the same products over transposed tensors (contiguous rows of 272 keys) took 1.50 ms.
-    const int L = mode == 0 ? W : H;
-    const int ntq = cdiv(L, 32);
-    static const int force_nw = cdfo_switch("CDFO_ATTN_NW", 0);     // developer switch (4 / 8)
-    const bool wide = force_nw ? force_nw == 8
-                               : L > 128 && (double)ntq / (cdiv(ntq, 8) * 8) >= (double)ntq / (cdiv(ntq, 4) * 4) - 0.1;
+    const bool wide = seq_attn_wide(mode == 0 ? W : H);
     int rc;
-    if (pv1) {
-      if (mode == 0) rc = !wide ? seq_attn_launch<0, 4, true>(q, ldq, v, ldv, out, ldo, B, H, W, st)
-                                : seq_attn_launch<0, 8, true>(q, ldq, v, ldv, out, ldo, B, H, W, st);
-      else rc = !wide ? seq_attn_launch<1, 4, true>(q, ldq, v, ldv, out, ldo, B, H, W, st)
-                      : seq_attn_launch<1, 8, true>(q, ldq, v, ldv, out, ldo, B, H, W, st);
-    } else if (mode == 0) rc = !wide ? seq_attn_launch<0, 4>(q, ldq, v, ldv, out, ldo, B, H, W, st)
+    if (pv1) rc = mode == 0 ? seq_attn_pv1<0>(q, ldq, v, ldv, out, ldo, B, H, W, st) : seq_attn_pv1<1>(q, ldq, v, ldv, out, ldo, B, H, W, st);
+    else if (mode == 0) rc = !wide ? seq_attn_launch<0, 4>(q, ldq, v, ldv, out, ldo, B, H, W, st)
                                      : seq_attn_launch<0, 8>(q, ldq, v, ldv, out, ldo, B, H, W, st);
     else rc = !wide ? seq_attn_launch<1, 4>(q, ldq, v, ldv, out, ldo, B, H, W, st)
                     : seq_attn_launch<1, 8>(q, ldq, v, ldv, out, ldo, B, H, W, st);
@@ -618,7 +982,7 @@ extern "C" int cdfo_seq_attn(const float* q, int ldq, const float* v, int ldv, f
                        ldv, out, ldo, B, H, W);
   } else if (mode == 2) {
     if ((H & 7) || (W & 7)) return CDFO_EINVAL;
-    const int rc = pv1 ? seq_attn_launch<2, 4, true>(q, ldq, v, ldv, out, ldo, B, H, W, st)
+    const int rc = pv1 ? seq_attn_pv1<2>(q, ldq, v, ldv, out, ldo, B, H, W, st)
                        : seq_attn_launch<2, 4>(q, ldq, v, ldv, out, ldo, B, H, W, st);
     if (rc) return rc;
   } else if (mode == 12) {   // VALU reference form of mode 2
@@ -628,6 +992,36 @@ extern "C" int cdfo_seq_attn(const float* q, int ldq, const float* v, int ldv, f
   } else {
     return CDFO_EINVAL;
   }
+  CDFO_LAUNCH_CHECK();
+  return 0;
+}
+
+// Modes 20 / 21 / 22 with 16-bit operands: v_f16: V is fp16 [.,ldv] (ldv in halves) holding (_Float16)v -- the rounding the fp32
+// form applies while staging, so the result is the same bit for bit; out_f16 (mode 20 only): the output as (_Float16)result, the V
+// operand of the column attention that follows.  With neither flag this is cdfo_seq_attn.
+extern "C" int cdfo_seq_attn_f16(const float* q, int ldq, const void* v, int ldv, void* out, int ldo, int B, int H, int W, int mode,
+                                 int v_f16, int out_f16, void* stream) {
+  if (!v_f16 && !out_f16)
+    return cdfo_seq_attn(q, ldq, static_cast<const float*>(v), ldv, static_cast<float*>(out), ldo, B, H, W, mode, stream);
+  if (mode < 20 || mode > 22 || (out_f16 && mode != 20)) return CDFO_EINVAL;
+  if (B <= 0 || H <= 0 || W <= 0 || ldq % 4 || ldv % (v_f16 ? 8 : 4) || ldo % 4) return CDFO_EINVAL;
+  if (mode == 22 && ((H & 7) || (W & 7))) return CDFO_EINVAL;
+  if (!aligned16(q) || !aligned16(v) || (reinterpret_cast<uintptr_t>(out) & (out_f16 ? 7u : 15u)))
+    return CDFO_EALIGN;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int L = mode == 20 ? W : (mode == 21 ? H : 64);
+  CdfoProfScope prof(st, mode == 20 ? KID_ATTN_ROW : (mode == 21 ? KID_ATTN_COL : KID_ATTN_WIN), 4.0 * 64 * (double)B * H * W * L,
+                     (4.0 * 64 + (v_f16 ? 2.0 : 4.0) * 64 + (out_f16 ? 2.0 : 4.0) * 64) * (double)B * H * W);
+  const _Float16* vh = static_cast<const _Float16*>(v);
+  const float* vf = static_cast<const float*>(v);
+  int rc;
+  if (mode == 20) {
+    if (v_f16) rc = out_f16 ? seq_attn_pv1<0>(q, ldq, vh, ldv, static_cast<_Float16*>(out), ldo, B, H, W, st)
+                            : seq_attn_pv1<0>(q, ldq, vh, ldv, static_cast<float*>(out), ldo, B, H, W, st);
+    else rc = seq_attn_pv1<0>(q, ldq, vf, ldv, static_cast<_Float16*>(out), ldo, B, H, W, st);
+  } else if (mode == 21) rc = seq_attn_pv1<1>(q, ldq, vh, ldv, static_cast<float*>(out), ldo, B, H, W, st);
+  else rc = seq_attn_pv1<2>(q, ldq, vh, ldv, static_cast<float*>(out), ldo, B, H, W, st);
+  if (rc) return rc;
   CDFO_LAUNCH_CHECK();
   return 0;
 }

@@ -21,17 +21,9 @@
 //     straight from registers.
 // Contract: cdfo_conv_args as cdfo_conv1x1_bf16x3 with plain store, Cin % 64 == 0 per source, Cout % 8 == 0,
 // CoutP in {64, 128}, weights + ring within the CU's LDS (Cin * CoutP <= 192 * 64); everything else stays on that kernel.
-#include "numeric.h"
+#include "stream_ring.h"
 
 namespace {
-
-constexpr int ST_THREADS = 256;
-constexpr int ST_STAGE = 8192;                 // 32 pixels x 64 channels x 4 B
-constexpr int ST_MAXNS = 4;
-constexpr int ST_MAX_LDS = 160 * 1024 - 256;   // dynamic LDS a workgroup of these kernels may ask for
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct st_item { const float* base; int ld; int ch0; };     // one 64-channel slice of a pixel-major operand
 
@@ -76,56 +68,6 @@ inline int st_slots(int B, int tiles_per_image, int grid) {
   return n;
 }
 
-// eight 1 KiB pieces of one stage: lane l of piece k writes LDS bytes lds + 1024 k + 16 l from (buffer base + voff[k])
-__device__ __forceinline__ void st_dma8(const unsigned (&voff)[8], i32x4 rsrc, unsigned lds) {
-  unsigned keep;
-  asm volatile(
-      "s_nop 4\n\t"
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %10\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %1, %9, 0 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %2, %9, 0 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %3, %9, 0 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %4, %9, 0 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %5, %9, 0 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %6, %9, 0 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %7, %9, 0 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %8, %9, 0 offen lds\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "v"(voff[5]), "v"(voff[6]), "v"(voff[7]),
-        "s"(rsrc), "s"(lds)
-      : "memory", "scc");
-}
-
-// one dword per lane: lane l writes LDS bytes lds + 4 l from (buffer base + voff)
-__device__ __forceinline__ void st_dma1(unsigned voff, i32x4 rsrc, unsigned lds) {
-  unsigned keep;
-  asm volatile(
-      "s_nop 4\n\t"
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\ts_nop 0\n\t"
-      "buffer_load_dword %1, %2, 0 offen lds\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(rsrc), "s"(lds)
-      : "memory", "scc");
-}
-
-// An item has landed when at most the 8 * (younger items in flight) youngest DMA pieces are outstanding (pieces retire in order
-// among themselves; stores and older requests in flight only make the wait more conservative)
-__device__ __forceinline__ void st_wait_landed(long long younger) {
-  if (younger >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  else if (younger == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
 // NCB: 64-wide output-channel blocks (1, 2; 4 in the TAPS form)
 // CSUM (NCB == 1): also the channel sums of the result, see st_args.csum
 template <int NCB, bool TAPS = false, bool CSUM = false>
@@ -714,28 +656,6 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
     }
     img_t0 = seg_hi;
   }
-}
-
-// ---- host side of both kernels
-// the stream of B images of P pixels as 128-pixel tiles, and the persistent grid over the calling thread's CUs; false: no device
-inline bool st_tiling(int B, long long P, int& tiles_per_image, long long& tiles, int& grid) {
-  tiles_per_image = (int)((P + 127) / 128);
-  tiles = (long long)B * tiles_per_image;
-  const int cus = cdfo_num_cus();
-  grid = (int)(tiles < cus ? tiles : cus);
-  return cus > 0;
-}
-// the kernels' LDS map: split weights hi | lo and the bias in front of the rings
-inline int st_weight_bytes(int nkb, int ncb) { return 2 * (nkb * 4 * 2 * ncb * 64 * 16) + ncb * 64 * 4; }
-inline int st_lds_bytes(int nkb, int ncb, int ns) { return st_weight_bytes(nkb, ncb) + 4 * ns * ST_STAGE; }
-
-// `once`: the call site's static table, one per kernel instantiation.  Returns 0 or the hipError_t.
-template <class KernelPtr, class Args>
-int st_launch(KernelPtr kernel, CdfoAttrOnce& once, int grid, int lds, hipStream_t st, const Args& s) {
-  const hipError_t e = cdfo_set_max_lds(once, reinterpret_cast<const void*>(kernel), ST_MAX_LDS);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(ST_THREADS), lds, st, s);
-  return (int)hipGetLastError();
 }
 
 }  // namespace

@@ -154,6 +154,8 @@ class CVSR_V8(nn.Module):
         self.udsa_n16 = switches.get("CDFO_UDSA_N16")       # developer A/B: the prior U-net's first layer, see _udsa
         self.udsa_side_stream = switches.get("CDFO_UDSA_STREAM")   # developer A/B, see _feature_extraction
         self.attn_pv_single = not switches.get("CDFO_ATTN_PV3")    # see _rdab (developer A/B: CDFO_ATTN_PV3=1 -> three passes)
+        # see _rdab (developer A/B: CDFO_RDAB_FUSED=0 -> input_conv and the mask kernel as two launches, every V operand fp32)
+        self.rdab_fused = switches.get("CDFO_RDAB_FUSED")
         self.neighbour_group = 0        # frames per neighbour group: 0 = auto = 3
         # cached-feature call on one sequence (B = 1): the group of frames 0-2 (cached features only) starts beside the new
         # frame's feature extraction instead of behind it (see _forward)
@@ -410,25 +412,39 @@ class CVSR_V8(nn.Module):
         part, n = K.chan_sum_partial(t)
         vmax = K.vec_mlp(part, n, t.shape[1] * t.shape[2], raw["RDAB.conv_du_re2.0.weight"],
                          raw["RDAB.conv_du_re2.0.bias"], 64, K.ACT_RELU)
-        xq = self._conv(x, w["RDAB.input_conv"])
-        sq, vrow, qwin = (K.empty_act(GB, H, W, 64, x.device) for _ in range(3))
-        for g, noise in enumerate(noises):
-            sl = slice(g * B, (g + 1) * B)
-            outs = (sq[sl], vrow[sl], qwin[sl])
-            if isinstance(noise, tuple):  # ("rng", seed, draw, capture): draw the uniforms inside the kernel (default path)
-                _, seed, draw, capture = noise
-                K.rdab_prep_rng(xq[sl], vmax[sl], seed, draw, raw["RDAB.directW1_conv.weight"], raw["RDAB.directW1_conv.bias"],
-                                noise_out=capture, outs=outs)
-            else:
-                K.rdab_prep(xq[sl], vmax[sl], noise, raw["RDAB.directW1_conv.weight"], raw["RDAB.directW1_conv.bias"], outs=outs)
-        cat = K.empty_act(GB, H, W, 128, x.device)
         # fp16x2 (default): the probabilities-times-values product of the three attentions on single-fp16 operands (modes 20-22:
         # error <= 2^-11 max|v|, measured ~1e-5 |v|; the scores keep their three split-fp16 passes); fp32-grade modes: all three passes
         am = 20 if self.precision == "fp16x2" and self.attn_pv_single else 0
-        rowo = K.seq_attn(sq, vrow, am)
+        wW, bW = raw["RDAB.directW1_conv.weight"], raw["RDAB.directW1_conv.bias"]
+        if self.rdab_fused and self.precision != "f32" and K.rdab_prep_fused_ok(x, w["RDAB.input_conv"]):
+            # input_conv inside the mask kernel: its 128-channel result is never written.  Modes 20-22 round every V once to fp16
+            # while staging, so the V operands of the column and window attentions (the row attention's output, the window V) are
+            # stored that way: same bits.  vrow stays fp32: the row form measured slower on an fp16 V
+            vdt = torch.float16 if am == 20 else torch.float32
+            sq, vrow, qwin = (K.empty_act(GB, H, W, 64, x.device) for _ in range(3))
+            vwin = torch.empty((GB, H, W, 64), dtype=vdt, device=x.device)
+            for g, noise in enumerate(noises):
+                sl = slice(g * B, (g + 1) * B)
+                K.rdab_prep_fused(x[sl], w["RDAB.input_conv"], vmax[sl], noise, wW, bW, v_f16=(False, am == 20),
+                                  outs=(sq[sl], vrow[sl], qwin[sl], vwin[sl]))
+        else:
+            vdt = torch.float32
+            xq = self._conv(x, w["RDAB.input_conv"])
+            vwin = xq[..., 64:128]
+            sq, vrow, qwin = (K.empty_act(GB, H, W, 64, x.device) for _ in range(3))
+            for g, noise in enumerate(noises):
+                sl = slice(g * B, (g + 1) * B)
+                outs = (sq[sl], vrow[sl], qwin[sl])
+                if isinstance(noise, tuple):  # ("rng", seed, draw, capture): draw the uniforms inside the kernel (default path)
+                    _, seed, draw, capture = noise
+                    K.rdab_prep_rng(xq[sl], vmax[sl], seed, draw, wW, bW, noise_out=capture, outs=outs)
+                else:
+                    K.rdab_prep(xq[sl], vmax[sl], noise, wW, bW, outs=outs)
+        cat = K.empty_act(GB, H, W, 128, x.device)
+        rowo = K.seq_attn(sq, vrow, am, out_dtype=vdt)
         qc = K.colconv9(sq, raw["RDAB.directH1_conv.weight"], raw["RDAB.directH1_conv.bias"])
         K.seq_attn(qc, rowo, am + 1, out=cat[..., 0:64])
-        K.seq_attn(qwin, xq[..., 64:128], am + 2, out=cat[..., 64:128])
+        K.seq_attn(qwin, vwin, am + 2, out=cat[..., 64:128])
         return self._conv(cat, w["RDAB.fuse"], res1=x)
 
     def _align(self, w, xc, extra, pred, mvs, mv_bstride, out, frames=None):

@@ -1202,6 +1202,53 @@ def rdab_prep_rng(xq: torch.Tensor, vmax: torch.Tensor, seed: int, draw: int, wW
     return sq, vrow, qwin
 
 
+def rdab_prep_fused_ok(x: torch.Tensor, pc: PackedConv) -> bool:
+    """Inside the contract of rdab_prep_fused: a 64 -> 128 1x1 convolution with shared weights over whole 64-pixel blocks."""
+    return (x.dim() == 4 and x.shape[3] == 64 and (x.shape[1] * x.shape[2]) % 64 == 0 and pc.ks == 1 and pc.Cin == 64
+            and pc.Cout == 128 and pc.CoutP == 128 and pc.w_bstride == 0 and not pc.shuffle2)
+
+
+def rdab_prep_fused(x: torch.Tensor, pc: PackedConv, vmax: torch.Tensor, noise, wW: torch.Tensor, bW: torch.Tensor,
+                    v_f16: bool = False, outs=None):
+    """conv(x, pc) (RDAB.input_conv, 64 -> 128 = q | v) followed by rdab_prep / rdab_prep_rng in ONE launch: the 128-channel product
+    is never written.  noise: the injected fp32 [B,64,H,W] draws, or ("rng", seed, draw, noise_out) as rdab_prep_rng takes them.
+    Returns (sq, vrow, qwin, vwin) -- vwin = the v half of the product, which the two-kernel path reads from xq[..., 64:].
+    v_f16 (a bool for both, or a pair (vrow, vwin)): that output as fp16, each value rounded once (what seq_attn's modes 20-22 do
+    to an fp32 V while staging).  outs: the four [B,H,W,64] result tensors, dense, of those dtypes."""
+    B, H, W, Cc, ld = _chk_act(x, "x")
+    if not rdab_prep_fused_ok(x, pc):
+        raise ValueError("rdab_prep_fused: a 64 -> 128 1x1 convolution over H*W % 64 == 0 pixels expected (use conv + rdab_prep)")
+    row16, win16 = (v_f16, v_f16) if isinstance(v_f16, bool) else v_f16
+    dts = (torch.float32, torch.float16 if row16 else torch.float32, torch.float32, torch.float16 if win16 else torch.float32)
+    if outs is None:
+        outs = tuple(torch.empty((B, H, W, 64), dtype=dt, device=x.device) for dt in dts)
+    sq, vrow, qwin, vwin = outs
+    for t, dt in zip(outs, dts):
+        if tuple(t.shape) != (B, H, W, 64) or not t.is_contiguous() or t.dtype != dt:
+            raise ValueError("rdab_prep_fused: outs must be dense [B,H,W,64] tensors: sq, qwin fp32; vrow, vwin fp32 or, as v_f16 says, fp16")
+    seed, seed_dev, draw, noise_in, noise_out = 0, None, 0, None, None
+    if isinstance(noise, tuple):
+        _, seed, draw, noise_out = noise
+        if noise_out is not None and (tuple(noise_out.shape) != (B, 64, H, W) or not noise_out.is_contiguous()
+                                      or noise_out.dtype != torch.float32):
+            raise ValueError("rdab_prep_fused: noise_out must be a contiguous fp32 [B,64,H,W] tensor")
+        if isinstance(seed, torch.Tensor):      # the key lives in device memory (int64[1]): graph replays re-read it
+            if seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != x.device:
+                raise ValueError("rdab_prep_fused: a device-side key must be an int64[1] tensor on the operands' device")
+            seed, seed_dev = 0, seed
+        else:
+            seed &= 0x7FFFFFFFFFFFFFFF
+    else:
+        noise_in = noise
+        if tuple(noise.shape) != (B, 64, H, W) or not noise.is_contiguous() or noise.dtype != torch.float32:
+            raise ValueError("rdab_prep_fused: noise must be a contiguous fp32 [B,64,H,W] tensor")
+    check(_lib.lib().cdfo_rdab_prep_fused(_vp(x), ld, _vp(pc.w), _vp(pc.bias), _vp(vmax), _vp(noise_in), C.c_longlong(seed),
+                                          _vp(seed_dev), draw, _vp(noise_out), _vp(wW), _vp(bW), B, C.c_longlong(H * W),
+                                          _vp(sq), 64, _vp(vrow), 64, _vp(qwin), 64, _vp(vwin), 64, int(row16) + 2 * int(win16), _stream()),
+          "cdfo_rdab_prep_fused")
+    return sq, vrow, qwin, vwin
+
+
 _seed_counter = 0
 
 
@@ -1228,11 +1275,24 @@ def colconv9(x: torch.Tensor, wH: torch.Tensor, bH: torch.Tensor) -> torch.Tenso
     return out
 
 
-def seq_attn(q: torch.Tensor, v: torch.Tensor, mode: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def seq_attn(q: torch.Tensor, v: torch.Tensor, mode: int, out: Optional[torch.Tensor] = None,
+             out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Modes 20-22 (single-fp16 second product) also take v as fp16 -- (fp16)v, the rounding they apply to an fp32 v while staging:
+    the same result at half the bytes --, and mode 20 can leave its result as fp16 (`out` of that dtype, or out_dtype), the form in
+    which mode 21 would round it as ITS v.  16-bit operands with any other mode raise."""
+    if out is not None:
+        out_dtype = out.dtype
+    v_f16, out_f16 = v.dtype == torch.float16, out_dtype == torch.float16
+    if (v_f16 and mode not in (20, 21, 22)) or (out_f16 and mode != 20):
+        raise ValueError(f"seq_attn: an fp16 v needs mode 20, 21 or 22 and an fp16 out mode 20, got mode {mode}")
     B, H, W, Cc, ldq = _chk_act(q, "q")
-    _, _, _, _, ldv = _chk_act(v, "v")
+    _, _, _, _, ldv = _chk_act(v, "v", v.dtype if v_f16 else torch.float32)
     if out is None:
-        out = empty_act(B, H, W, 64, q.device)
-    _, _, _, _, ldo = _chk_act(out, "out")
+        out = torch.empty((B, H, W, 64), dtype=out_dtype, device=q.device)
+    _, _, _, _, ldo = _chk_act(out, "out", out_dtype if out_f16 else torch.float32)
+    if v_f16 or out_f16:
+        check(_lib.lib().cdfo_seq_attn_f16(_vp(q), ldq, _vp(v), ldv, _vp(out), ldo, B, H, W, mode, int(v_f16), int(out_f16),
+                                           _stream()), "cdfo_seq_attn_f16")
+        return out
     check(_lib.lib().cdfo_seq_attn(_vp(q), ldq, _vp(v), ldv, _vp(out), ldo, B, H, W, mode, _stream()), "cdfo_seq_attn")
     return out

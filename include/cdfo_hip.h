@@ -291,6 +291,16 @@ int cdfo_rdab_prep_rng(const float* xq, int ldx, const float* vmax, long long se
 int cdfo_rdab_prep_rng_dev(const float* xq, int ldx, const float* vmax, const void* seed_dev, int draw, float* noise_out,
                            const float* wW, const float* bW, int B, long long P, float* sq, int lds_, float* vrow, int ldv,
                            float* qwin, int ldw, void* stream);
+/* RDAB.input_conv (1x1, 64 -> 128) and cdfo_rdab_prep* in ONE launch: the 128-channel product is never written.  x [B][P][ldx]
+ * fp32 (ldx >= 64), w_packed / bias: the convolution's fp32 packing [16][128][4] and bias [128] (NULL: none).  noise != NULL: the
+ * injected draws (cdfo_rdab_prep); otherwise Philox keyed by *seed_dev (if non-NULL) or seed, with the optional noise_out.
+ * vwin receives the v half of the product, which the two-kernel path reads from xq.  v_f16 (bit 0: vrow, bit 1: vwin): that output
+ * is fp16, pitch in halves, each value rounded once -- what the attention modes 20-22 do to an fp32 V while staging.  Same bits as the streaming
+ * form of cdfo_conv1x1_bf16x3 followed by cdfo_rdab_prep*.  P % 64 == 0. */
+int cdfo_rdab_prep_fused(const float* x, int ldx, const float* w_packed, const float* bias, const float* vmax,
+                         const float* noise, long long seed, const void* seed_dev, int draw, float* noise_out,
+                         const float* wW, const float* bW, int B, long long P, float* sq, int lds_, void* vrow, int ldv,
+                         float* qwin, int ldw, void* vwin, int ldvw, int v_f16, void* stream);
 int cdfo_colconv9(const float* in, int ldi, const float* wH, const float* bH, int B, int H, int W, float* out, int ldo,
                   void* stream);
 /* Evaluation metrics on the device (metric/psnr_ssim.py:278-317 calculate_psnr, :320-399 _ssim / calculate_ssim): fp64
@@ -332,6 +342,11 @@ int cdfo_qkv_dw(const float* x, int ldx, int B, int H, int W, const void* w_bf16
  * The forward's default fp16x2 arithmetic uses these (cdfo_amd/cvsr_v8.py); the fp32-grade modes and the training path do not. */
 int cdfo_seq_attn(const float* q, int ldq, const float* v, int ldv, float* out, int ldo, int B, int H, int W, int mode,
                   void* stream);
+/* Modes 20 / 21 / 22 with 16-bit operands.  v_f16: v is fp16 (ldv in halves) holding (_Float16)v, the rounding the fp32 form
+ * applies while staging: same result bit for bit at half the bytes (ldv % 8 == 0, v 16-byte aligned).  out_f16 (mode 20 only): out is fp16 (ldo in halves) and
+ * receives (_Float16)result -- the row attention's output as the V operand of the column attention.  Neither flag: cdfo_seq_attn. */
+int cdfo_seq_attn_f16(const float* q, int ldq, const void* v, int ldv, void* out, int ldo, int B, int H, int W, int mode,
+                      int v_f16, int out_f16, void* stream);
 
 /* ---- deformable convolution forward (dcn.hip) --------------------------------------------------------------
  * Replaces deform_conv_forward_cuda (ops/dcn/src/deform_conv_cuda.cpp:151-156; mask == NULL, bias == NULL) and

@@ -29,6 +29,20 @@ def main():
         ms = e0.elapsed_time(e1) / n
         flop = 3 * 2 * 2 * 64.0 * B * H * W * L      # two products, three fp16 passes each
         print(f"mode {mode} L={L}: {ms:.3f} ms  {flop / ms / 1e9:.0f} TFLOP/s issued (fp16 MFMA, 3 passes)  max|mfma - valu| = {err:.2e}")
+        if mode >= 20:
+            # the same launch with V stored as fp16 (and, row form, the output too): the rounding moves to the producer, same bits
+            vh = v.half()
+            forms = [("fp16 V", vh, torch.float32)] + ([("fp16 V, fp16 out", vh, torch.float16), ("fp16 out", v, torch.float16)] if mode == 20 else [])
+            for name, vv, odt in forms:
+                o2 = torch.empty(B, H, W, 64, dtype=odt, device="cuda")
+                for _ in range(3):
+                    K.seq_attn(q, vv, mode, out=o2)
+                e0.record()
+                for _ in range(n):
+                    K.seq_attn(q, vv, mode, out=o2)
+                e1.record()
+                torch.cuda.synchronize()
+                print(f"mode {mode} L={L}, {name}: {e0.elapsed_time(e1) / n:.3f} ms  equal: {torch.equal(o2, out.to(odt))}")
 
 
 if __name__ == "__main__":
