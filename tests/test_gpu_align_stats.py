@@ -77,6 +77,12 @@ def _errors(got, ref):
     return (got[0] - ref[0]).abs().max().item(), ((got[1] - ref[1]).abs().max() / ref[1].abs().max()).item()
 
 
+def _le(err, bound, what):
+    """the error-against-bound assertions of the persistent kernels' tests (tests/test_gpu_schedules.py records the ratios it sees
+    when it re-runs them under a CU limit)"""
+    assert err <= bound, f"{what}: {err} (bound {bound})"
+
+
 @pytest.mark.parametrize("B,H,W,sliced", [(3, 272, 480, False), (5, 72, 120, False), (1, 64, 64, False), (24, 40, 56, False),
                                           (2, 37, 53, False), (3, 48, 80, True)])
 def test_align_stats_against_float64(B, H, W, sliced):
@@ -92,7 +98,8 @@ def test_align_stats_against_float64(B, H, W, sliced):
     torch.cuda.synchronize()
     print(f"align_stats {B}x{H}x{W}{' sliced' if sliced else ''}: cosines abs {old[0]:.2e} -> {new[0]:.2e}, "
           f"means rel {old[1]:.2e} -> {new[1]:.2e}, slots {n}")
-    assert new[0] <= 4 * old[0] and new[1] <= 4 * old[1], (old, new)
+    _le(new[0], 4 * old[0], f"align_stats cosines {(old, new)}")
+    _le(new[1], 4 * old[1], f"align_stats means {(old, new)}")
 
 
 @pytest.mark.parametrize("B,H,W,nsrc", [(520, 8, 12, 3), (24, 40, 56, 3), (3, 272, 480, 3), (2, 37, 53, 1)])
@@ -116,7 +123,7 @@ def test_stream_kernel_channel_sums(B, H, W, nsrc):
     new = ((_fold_sum(part).double() / (H * W) - ref).abs().max() / scale).item()
     torch.cuda.synchronize()
     print(f"chan_sum_out {B}x{H}x{W}: means rel {old:.2e} -> {new:.2e}, slots {n}")
-    assert new <= 4 * old, (old, new)
+    _le(new, 4 * old, f"chan_sum_out means {(old, new)}")
 
 
 def _dump(path):

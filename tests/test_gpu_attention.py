@@ -51,6 +51,11 @@ def test_dwconv3x3(C, H, W):
     assert (out.permute(0, 3, 1, 2).cpu() - ref).abs().max().item() < 1e-5
 
 
+def _lt(err, bound, what):
+    """test_qkv_dw_fused's error-against-bound assertions (tests/test_gpu_schedules.py records the ratios under a CU limit)"""
+    assert err < bound, f"{what}: {err} (bound {bound})"
+
+
 @pytest.mark.parametrize("B,H,W", [(2, 12, 30), (1, 17, 45), (3, 8, 64), (1, 5, 7), (2, 6, 121)])
 def test_qkv_dw_fused(B, H, W):
     """LayerNorm -> 1x1 (64->192) -> depthwise 3x3 in one kernel vs the same chain in torch-cpu fp32."""
@@ -67,20 +72,20 @@ def test_qkv_dw_fused(B, H, W):
     out = K.qkv_dw(x.permute(0, 2, 3, 1).contiguous().cuda(), packed, wd.cuda().contiguous())
     torch.cuda.synchronize()
     err = (out.cpu().permute(0, 3, 1, 2) - ref).abs().max().item()
-    assert err < 2e-5 * max(1.0, ref.abs().max().item()), err
+    _lt(err, 2e-5 * max(1.0, ref.abs().max().item()), "qkv_dw")
     # fused Gram mode: v only + the per-head sums sum_p q k^T, sum q^2, sum k^2 in cdfo_gram_partial's layout
     v, part, n = K.qkv_dw(x.permute(0, 2, 3, 1).contiguous().cuda(), packed, wd.cuda().contiguous(), gram=True)
     v2, part2, _ = K.qkv_dw(x.permute(0, 2, 3, 1).contiguous().cuda(), packed, wd.cuda().contiguous(), gram=True)
     assert torch.equal(part, part2) and torch.equal(v, v2)          # no atomics: bit-reproducible
     torch.cuda.synchronize()
-    assert (v.cpu().permute(0, 3, 1, 2) - ref[:, 128:]).abs().max().item() < 2e-5 * max(1.0, ref.abs().max().item())
+    _lt((v.cpu().permute(0, 3, 1, 2) - ref[:, 128:]).abs().max().item(), 2e-5 * max(1.0, ref.abs().max().item()), "qkv_dw gram mode, v")
     q, k = ref[:, :64].double().reshape(B, 8, 8, H * W), ref[:, 64:128].double().reshape(B, 8, 8, H * W)
     want = torch.zeros(B, 64, 10, dtype=torch.float64)
     want[:, :, :8] = (q @ k.transpose(-1, -2)).reshape(B, 64, 8)
     want[:, :, 8] = (q * q).sum(-1).reshape(B, 64)
     want[:, :, 9] = (k * k).sum(-1).reshape(B, 64)
     got = part.cpu().double().sum(1).view(B, 64, 10)
-    assert (got - want).abs().max().item() < 1e-4 * max(1.0, want.abs().max().item()), (got - want).abs().max().item()
+    _lt((got - want).abs().max().item(), 1e-4 * max(1.0, want.abs().max().item()), "qkv_dw gram mode, slot sums")
 
 
 # ----------------------------------------------------------------------------------- seq_attn at its edge shapes (attn_cases.py)

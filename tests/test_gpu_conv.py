@@ -14,7 +14,13 @@ def _cmp(got_nhwc, ref_nchw, tol, what):
     got = got_nhwc.permute(0, 3, 1, 2).cpu()
     err = (got - ref_nchw).abs().max().item()
     scale = ref_nchw.abs().max().item()
-    assert err <= tol * max(1.0, scale), f"{what}: max-abs {err} (ref scale {scale})"
+    _le(err, tol * max(1.0, scale), f"{what}: max-abs {err} (ref scale {scale})")
+
+
+def _le(err, bound, what):
+    """every error-against-bound assertion of the persistent kernels' tests goes through here (tests/test_gpu_schedules.py records
+    the ratios it sees when it re-runs these tests under a CU limit)"""
+    assert err <= bound, f"{what} (bound {bound})"
 
 
 CASES = [
@@ -268,7 +274,7 @@ def test_conv3x3_c64_ws(Cout, H, W, B, s2d, act):
     got = got.permute(0, 3, 1, 2)
     err = (got - ref).abs().max().item()
     scale = ref.abs().max().item()
-    assert err <= 1.5e-3 * max(1.0, scale), f"ws conv: max-abs {err} (ref scale {scale})"
+    _le(err, 1.5e-3 * max(1.0, scale), f"ws conv: max-abs {err} (ref scale {scale})")
 
 
 WINO_CASES = [
@@ -311,7 +317,7 @@ def test_conv3x3_c64_wino(Cout, H, W, B, s2d, act):
     got = got.permute(0, 3, 1, 2)
     err = (got - ref).abs().max().item()
     scale = ref.abs().max().item()
-    assert err <= 1.5e-3 * max(1.0, scale), f"wino conv: max-abs {err} (ref scale {scale})"
+    _le(err, 1.5e-3 * max(1.0, scale), f"wino conv: max-abs {err} (ref scale {scale})")
     # and against the direct weights-stationary kernel on the same operands: two fp16 roundings of nearly the same number
     if H % 2 == 0:
         direct = K.from_cp16(K.conv3x3_ws(src, pc, act=act, s2d=s2d)).float().cpu()
@@ -366,11 +372,11 @@ def test_conv3x3_ring_dense(Cin, Cout, H, W, B, res, out_f16):
     _cmp(out.float(), ref, 1.5e-3 if out_f16 else 1e-4, "ring conv")
 
 
-def test_conv3x3_ring_sparse_taps_halfsplit_source():
+def test_conv3x3_ring_sparse_taps_halfsplit_source(B=2, H=36, W=44):
     """cdfo_conv_args.src_halfsplit: the four-tap ring kernel on a source whose rows are [half][W][8] gives the natural layout's result."""
     from cdfo_amd import kernels as K
     g = torch.Generator().manual_seed(12)
-    B, H, W, Cin, Cout = 2, 36, 44, 128, 64
+    Cin, Cout = 128, 64
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, 3, 3, generator=g) / (Cin * 4) ** 0.5
     masks = []
@@ -432,11 +438,11 @@ def test_resample2_chunk_planar_fp16(B, H, W, C):
     _cmp(K.from_cp16(out).float(), ref, 1e-3, "up2 -> cp16")
 
 
-def test_conv3x3_ring_second_output_chunk_planar():
+def test_conv3x3_ring_second_output_chunk_planar(B=2, H=20, W=36):
     """out2_cp16 of the ring kernel is the fp16 rounding of its fp32 result, in chunk-planar layout."""
     from cdfo_amd import kernels as K
     g = torch.Generator().manual_seed(3)
-    B, H, W, Cin, Cout = 2, 20, 36, 64, 64
+    Cin, Cout = 64, 64
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, 3, 3, generator=g) / 24.0
     pc = K.pack_conv(w.cuda(), torch.randn(Cout, generator=g).cuda())
@@ -464,11 +470,11 @@ def test_block_prologue(B, H, W):
     _cmp(K.from_cp16(d16).float(), ref_d, 1.5e-3, "block prologue, x1/2 branch")
 
 
-def test_conv3x3_ring_half_resolution_residual():
+def test_conv3x3_ring_half_resolution_residual(B=2, H=20, W=36):
     """res_up2: the ring kernel adds bilinear_x2 of a half-resolution tensor in its epilogue."""
     from cdfo_amd import kernels as K
     g = torch.Generator().manual_seed(17)
-    B, H, W, Cin, Cout = 2, 20, 36, 64, 64
+    Cin, Cout = 64, 64
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, 3, 3, generator=g) / 24.0
     b = torch.randn(Cout, generator=g)
@@ -590,14 +596,15 @@ def test_split_fp16_conv_on_ring_kernel(B, H, W):
 
 @pytest.mark.parametrize("srcs,Cout,nres,per_image", [([64], 64, 2, True), ([64, 64], 64, 1, False), ([64, 128], 64, 0, True),
                                                       ([64], 128, 0, False), ([128], 128, 1, False)])
-def test_conv1x1_stream_many_tiles_across_images(srcs, Cout, nres, per_image):
+def test_conv1x1_stream_many_tiles_across_images(srcs, Cout, nres, per_image, shape=(5, 104, 105), prec=None):
     """The persistent streaming form of the 1x1 convolution (conv1x1_stream.hip) with more tiles than workgroups, so
     that workgroups walk several tiles, cross image boundaries (weights reloaded per image) and end on a ragged tile;
     against torch, and against the one-tile-per-workgroup kernel it replaces (CDFO_CONV1X1_STREAM=0 is a process-wide
     switch, so that comparison is numerical: same split-bf16 arithmetic, fp32 accumulation)."""
     from cdfo_amd import kernels as K
     g = torch.Generator().manual_seed(sum(srcs) * 7 + Cout + nres)
-    B, H, W = 5, 104, 105                     # 10,920 pixels = 85.3 tiles per image, 430 tiles in all
+    B, H, W = shape                           # 5 x 104 x 105: 10,920 pixels = 85.3 tiles per image, 430 tiles in all
+    prec = K.PREC_BF16X3 if prec is None else prec      # (the 1x1 stream kernel has one arithmetic for both 16-bit modes)
     xs = [torch.randn(B, c, H, W, generator=g) for c in srcs]
     cin = sum(srcs)
     b = torch.randn(Cout, generator=g)
@@ -616,10 +623,10 @@ def test_conv1x1_stream_many_tiles_across_images(srcs, Cout, nres, per_image):
     for r in rs:
         ref = ref + r
     dev_r = [_nhwc(r).cuda() for r in rs] + [None, None]
-    out = K.conv([_nhwc(t).cuda() for t in xs], pc, act=K.ACT_RELU, res1=dev_r[0], res2=dev_r[1], prec=K.PREC_BF16X3)
+    out = K.conv([_nhwc(t).cuda() for t in xs], pc, act=K.ACT_RELU, res1=dev_r[0], res2=dev_r[1], prec=prec)
     torch.cuda.synchronize()
     _cmp(out, ref, 3e-5, "conv1x1 stream")
-    out2 = K.conv([_nhwc(t).cuda() for t in xs], pc, act=K.ACT_RELU, res1=dev_r[0], res2=dev_r[1], prec=K.PREC_BF16X3)
+    out2 = K.conv([_nhwc(t).cuda() for t in xs], pc, act=K.ACT_RELU, res1=dev_r[0], res2=dev_r[1], prec=prec)
     torch.cuda.synchronize()
     assert torch.equal(out, out2)             # no atomics, fixed summation order
 
@@ -700,7 +707,7 @@ def test_conv3x3_n16_matches_fp64_conv(B, H, W, act):
     torch.cuda.synchronize()
     assert tuple(out.shape) == (B, H, W, 16)
     err = (out.permute(0, 3, 1, 2).double() - ref).abs().max().item()
-    assert err <= 2e-5 * max(1.0, ref.abs().max().item()), err
+    _le(err, 2e-5 * max(1.0, ref.abs().max().item()), f"n16 conv: max-abs {err}")
 
 
 def test_conv1x1_with_its_fp16_chunk_planar_copy():
@@ -742,7 +749,7 @@ def test_conv3x3_c64_wino_up2(Cout, h, w, B, act):
     got = K.from_cp16(out).float().cpu().view(B, h, w, 2, 2, Cout).permute(0, 1, 3, 2, 4, 5).reshape(B, 2 * h, 2 * w, Cout).permute(0, 3, 1, 2)
     err = (got - ref).abs().max().item()
     scale = ref.abs().max().item()
-    assert err <= 2.5e-3 * max(1.0, scale), f"wino up2: max-abs {err} (ref scale {scale})"
+    _le(err, 2.5e-3 * max(1.0, scale), f"wino up2: max-abs {err} (ref scale {scale})")
 
 
 @pytest.mark.parametrize("B,H,W,stride,out_pad,hl", [

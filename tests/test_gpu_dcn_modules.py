@@ -107,6 +107,12 @@ def test_hip_modules_train_like_the_reference_classes(path):
     assert np.median(e_hip) <= 1e-4 and e_hip.max() <= 5e-3, rows[:5]
 
 
+def _lt(err, bound, what):
+    """the weights-stationary offset head's error-against-bound assertions (tests/test_gpu_schedules.py records the ratios it sees
+    when it re-runs them under a CU limit)"""
+    assert err < bound, f"{what}: {err} (bound {bound})"
+
+
 @pytest.mark.parametrize("prec_name", ["bf16x3", "fp16x2"])
 @pytest.mark.parametrize("shape", [(2, 24, 36), (1, 37, 64), (3, 8, 100), (2, 136, 240)])
 def test_offset_head_with_the_assembly_as_its_epilogue(shape, prec_name):
@@ -160,8 +166,10 @@ def test_offset_head_with_the_assembly_as_its_epilogue(shape, prec_name):
         K.conv_offset_mask_ws(h1, pc, off_w, mask_w, flow, mag, False)
         assert torch.isfinite(off_w).all() and torch.isfinite(mask_w).all()
         K.conv_offset_mask_ws(h2, pc, off_w, mask_w, flow, mag, True)
-        assert (off_w - off_t).abs().max().item() < 5e-5 and (mask_w - mask_t).abs().max().item() < 5e-6
-        assert (off_w.double() - off64).abs().max().item() < 3e-2 and (mask_w.double() - mask64).abs().max().item() < 3e-3
+        _lt((off_w - off_t).abs().max().item(), 5e-5, "ws offset head vs the tiled kernel, offsets")
+        _lt((mask_w - mask_t).abs().max().item(), 5e-6, "ws offset head vs the tiled kernel, masks")
+        _lt((off_w.double() - off64).abs().max().item(), 3e-2, "ws offset head vs float64, offsets")
+        _lt((mask_w.double() - mask64).abs().max().item(), 3e-3, "ws offset head vs float64, masks")
     with pytest.raises(ValueError):
         K.conv_offset_mask(o1[:, :, :W - 2], pc, off[..., :W - 2].contiguous(), mask[..., :W - 2].contiguous(),
                            flow[..., :W - 2].contiguous(), mag, False, prec)       # W % 4 != 0: the caller assembles separately

@@ -26,3 +26,19 @@ def test_kernel_variant_passes_the_per_kernel_parity_tests(env_extra, select):
     rc, out, err = clean_process_run(cmd, env=env, cwd=ROOT, timeout=600)
     assert rc == 0, f"variant {env_extra}: pytest exit {rc}\n{out[-3000:]}\n{err[-2000:]}"
     assert " passed" in out and " failed" not in out, out[-2000:]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env_extra,select", VARIANTS, ids=lambda v: "-".join(f"{k}={x}" for k, x in v.items()) if isinstance(v, dict) else v)
+def test_kernel_variant_passes_the_limited_share_cases(env_extra, select):
+    """the A/B forms have tile walks of their own: the ws / ring cases of tests/test_gpu_schedules.py (few CUs, several units per
+    workgroup, empty workgroups) with each switch flipped.  (`ws` selects the ws_plain and ws_res cases, not the offmask ones:
+    conv_offset_mask_ws launches the ring-fed kernel whatever CDFO_WS_RING says, so that switch changes nothing there.)"""
+    from conftest import clean_process_run
+    env = dict(os.environ)
+    env.update(env_extra)
+    cmd = [sys.executable, "-m", "pytest", os.path.join("tests", "test_gpu_schedules.py"), "-x", "-q", "-m", "gpu",
+           "-k", f"test_kernel_under_a_cu_limit and {select}", "-p", "no:cacheprovider"]
+    rc, out, err = clean_process_run(cmd, env=env, cwd=ROOT, timeout=600)
+    assert rc == 0, f"variant {env_extra}: pytest exit {rc}\n{out[-3000:]}\n{err[-2000:]}"
+    assert " passed" in out and " failed" not in out, out[-2000:]
