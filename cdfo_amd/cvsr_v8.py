@@ -563,12 +563,16 @@ class CVSR_V8(nn.Module):
         y = self._conv(t, w[p + "down_fused"], pad=1, res1=out)
         return (y, None) if want16 else y
 
+    def _side(self, device, count):
+        """`count` side streams of `device`, created once per (device, count): the neighbour groups ask for two or more, the
+        trunk and the feature extractor for one of their own."""
+        cache = self.__dict__.setdefault("_side_streams", {})
+        if (device, count) not in cache:
+            cache[(device, count)] = [torch.cuda.Stream(device) for _ in range(count)]
+        return cache[(device, count)]
+
     def _trunk_side(self, device):
-        cache = self.__dict__.setdefault("_trunk_side_streams", {})
-        st = cache.get(device)
-        if st is None:
-            st = cache[device] = torch.cuda.Stream(device)
-        return st
+        return self._side(device, 1)[0]
 
     def _trunk(self, w, fused):
         y = fused
@@ -622,8 +626,7 @@ class CVSR_V8(nn.Module):
 
     # -- forward ---------------------------------------------------------------------------------------------------
     def forward(self, x, mvs0, mvs1, pms, rms, ufs, pre_L1_fea=None, gumbel_uniform=None):
-        if not x.is_cuda:
-            raise NotImplementedError("CVSR_V8 (HIP): CPU tensors are not supported; there is no CPU fallback")
+        self._check("forward", x, grad_ok=True, capture_ok=True)
         with K.on_device(x):     # the operands' device becomes the current one: streams, per-device caches of the library
             training = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
             if training and torch.cuda.is_current_stream_capturing():
@@ -640,35 +643,38 @@ class CVSR_V8(nn.Module):
                         raise NotImplementedError("CVSR_V8 (HIP): fp32 parameters on the GPU expected")
                 from .cvsr_v8_train import forward_train
                 return forward_train(self, x, mvs0, mvs1, pms, rms, ufs, noise)
-            guard = self.precision == "fp16x2" and self.range_guard
-            if not guard:
-                return self._forward(x, mvs0, mvs1, pms, rms, ufs, pre_L1_fea, noise)
-            # fp16 range guard: the fp16x2 mode keeps the trunk's tensors (and the alignment's residual blocks) in fp16.  Outside
-            # fp16's comfortable range -- max |trunk input| not in [2^-6, 2^11], or a NaN / infinity in the trunk's input or output
-            # (what an overflowed fp16 store turns into) -- the forward is repeated in the split-bf16 mode (fp32 exponent range,
-            # fp32-grade products).  Two probe kernels fill a zeroed 4-int probe (trunk input: slots 0-1, trunk output: 2-3); it is
-            # copied to pinned host memory behind the last kernel and settled before the call returns: what forward returns is final.
-            capturing = torch.cuda.is_current_stream_capturing()
-            if capturing:
-                # model.capture() (graph.py): the probe is a graph node -- zeroed, filled by the two probe kernels, copied to pinned
-                # host memory behind the last kernel; CapturedForward.replay() reads it and repeats a rejected forward eagerly in bf16x3
-                probe = self.__dict__.get("_graph_probe")
-                if probe is None:
-                    raise RuntimeError("CVSR_V8 (HIP): the fp16 range guard reads probes back and cannot be captured by hand; use "
-                                       "model.capture(), whose graph carries the two probes and whose replay() reads them back")
-                probe.zero_()
-            else:
-                probe = torch.zeros(4, dtype=torch.int32, device=x.device)
-            self._probe = probe
-            try:
-                res = self._forward(x, mvs0, mvs1, pms, rms, ufs, pre_L1_fea, noise)
-            finally:
-                self._probe = None
-            if capturing:
-                return res
-            if not self._settle_range(probe):
-                return res
-            return self._range_fallback((x, mvs0, mvs1, pms, rms, ufs, pre_L1_fea, noise, self._noise_seed), None, None)
+            return self._guarded(x.device, lambda: self._forward(x, mvs0, mvs1, pms, rms, ufs, pre_L1_fea, noise))
+
+    def _guarded(self, device, run, rerun=None):
+        """``run()`` -- one inference forward of any route -- under the fp16 range guard.  The fp16x2 mode keeps the trunk's
+        tensors (and the alignment's residual blocks) in fp16.  Outside fp16's comfortable range -- max |trunk input| not in
+        [2^-6, 2^11], or a NaN / infinity in the trunk's input or output (what an overflowed fp16 store turns into) -- the forward
+        is repeated in the split-bf16 mode (fp32 exponent range, fp32-grade products), through ``rerun()`` if the route has to
+        rebuild operands first, with the Philox key of the rejected forward.  Two probe kernels fill a zeroed 4-int probe (trunk
+        input: slots 0-1, trunk output: 2-3) that `_fuse` and `_back` find in ``self._probe``; it is copied to pinned host memory
+        behind the last kernel and settled before the call returns: what an eager forward returns is final."""
+        if not (self.precision == "fp16x2" and self.range_guard):
+            return run()
+        capturing = torch.cuda.is_current_stream_capturing()
+        if capturing:
+            # model.capture() (graph.py): the probe is a graph node -- zeroed, filled by the two probe kernels, copied to pinned
+            # host memory behind the last kernel; CapturedForward.replay() reads it and repeats a rejected forward eagerly in bf16x3
+            # (through _range_fallback)
+            probe = self.__dict__.get("_graph_probe")
+            if probe is None:
+                raise RuntimeError("CVSR_V8 (HIP): the fp16 range guard reads probes back and cannot be captured by hand; use "
+                                   "model.capture(), whose graph carries the two probes and whose replay() reads them back")
+            probe.zero_()
+        else:
+            probe = torch.zeros(4, dtype=torch.int32, device=device)
+        self._probe = probe
+        try:
+            res = run()
+        finally:
+            self._probe = None
+        if capturing or not self._settle_range(probe):
+            return res
+        return self._recompute_bf16x3(rerun or run, self._noise_seed)
 
     def _settle_range(self, probe) -> bool:
         """Read a guarded forward's probe words back behind its last kernel (one host sync), set ``last_range``; True = the
@@ -732,10 +738,7 @@ class CVSR_V8(nn.Module):
         `state` goes to `forward_back`, `L1_fea` is what `forward` returns as its second output (the next call's
         `pre_L1_fea`).  A caller may run `forward_back(state)` on another stream (after making it wait for this one) while the
         next frame's `forward_front` is already running here: cdfo_amd.streaming.StreamingSR.run_pipelined does."""
-        if not x.is_cuda:
-            raise NotImplementedError("CVSR_V8 (HIP): CPU tensors are not supported; there is no CPU fallback")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("CVSR_V8 (HIP): forward_front / forward_back are inference calls -- wrap them in torch.no_grad()")
+        self._check("forward_front", x, capture_ok=True)
         with K.on_device(x):
             noise = self._resolve_noise(x, gumbel_uniform)
             fused, L1, xf = self._front(x, mvs0, mvs1, pms, rms, ufs, pre_L1_fea, noise)
@@ -748,23 +751,32 @@ class CVSR_V8(nn.Module):
             return self._back(fused, xf)
 
     # -- one sequence, K centre frames per call, features supplied by the caller (inference only) ----------------------
-    def _inference_only(self, what: str, t: torch.Tensor):
+    def _check(self, what: str, t: torch.Tensor, size=None, clip=False, grad_ok=False, capture_ok=False):
+        """The refusals the entry points share.  t: an operand of `what`, which has to live on the GPU; grad_ok / capture_ok: the
+        call also serves autograd / may be captured into a HIP graph; clip: t is the input clip x [B,7,1,H,W]; size: (H, W) of
+        the frames (read from the clip if t is one)."""
         if not t.is_cuda:
             raise NotImplementedError("CVSR_V8 (HIP): CPU tensors are not supported; there is no CPU fallback")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if not grad_ok and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError(f"CVSR_V8 (HIP): {what} is an inference call -- wrap it in torch.no_grad()")
-        if torch.cuda.is_current_stream_capturing():
+        if not capture_ok and torch.cuda.is_current_stream_capturing():
             raise NotImplementedError(f"CVSR_V8 (HIP): {what} is not captured into HIP graphs")
+        if clip:
+            if t.dim() != 5 or t.shape[1] != NFRAMES or t.shape[2] != 1:
+                raise ValueError(f"expected x of shape [B,7,1,H,W], got {tuple(t.shape)}")
+            size = t.shape[3:]
+        if size is not None:
+            H, W = size
+            if H % 8 or W % 8:
+                raise ValueError(f"H and W must be multiples of 8 (window attention, arch.py:2147,2235); got {H}x{W}")
 
     def extract_features(self, frames, pms):
         """Step 1 of the forward per frame (arch.py:4416-4427 is per image): frames, pms [F,1,H,W] -> features [F,H,W,64],
         pixel-major.  What any window of a sequence uses for frame t is extract_features(lr[t], pms[max(1, t)])."""
-        self._inference_only("extract_features", frames)
+        self._check("extract_features", frames, size=frames.shape[2:])
         F, C, H, W = frames.shape
         if C != 1 or tuple(pms.shape) != (F, 1, H, W):
             raise ValueError(f"expected frames and pms of shape [F,1,H,W], got {tuple(frames.shape)} and {tuple(pms.shape)}")
-        if H % 8 or W % 8:
-            raise ValueError(f"H and W must be multiples of 8 (window attention, arch.py:2147,2235); got {H}x{W}")
         with K.on_device(frames):
             w = self._weights()
             raw = w["raw"]
@@ -780,12 +792,10 @@ class CVSR_V8(nn.Module):
         out [K,1,4H,4W].  Steps 2-5 of ``forward`` on the same kernels; the clip-major feature tensor, its shift copy and its
         transpose never exist.  The fp16 range guard is that of ``forward``: settled before the call returns, a rejected call
         is repeated in bf16x3 from the same Lf."""
-        self._inference_only("forward_windows", x)
+        self._check("forward_windows", x, clip=True)
         Kw, N, C, H, W = x.shape
-        if N != NFRAMES or C != 1 or tuple(Lf.shape) != (N, Kw, H, W, NF):
+        if tuple(Lf.shape) != (N, Kw, H, W, NF):
             raise ValueError(f"expected x [K,7,1,H,W] and Lf [7,K,H,W,64], got {tuple(x.shape)} and {tuple(Lf.shape)}")
-        if H % 8 or W % 8:
-            raise ValueError(f"H and W must be multiples of 8 (window attention, arch.py:2147,2235); got {H}x{W}")
         if Lf.dtype != torch.float32 or not Lf.is_contiguous():
             raise ValueError("Lf must be a dense fp32 tensor")
         with K.on_device(x):
@@ -798,17 +808,7 @@ class CVSR_V8(nn.Module):
                 fused = self._fuse_windows(self._weights(), Lf, x, mvs1, rms, ufs, noise)
                 return self._back(fused, x)
 
-            if not (self.precision == "fp16x2" and self.range_guard):
-                return run()
-            self._probe = torch.zeros(4, dtype=torch.int32, device=x.device)
-            try:
-                out = run()
-                probe = self._probe
-            finally:
-                self._probe = None
-            if not self._settle_range(probe):
-                return out
-            return self._recompute_bf16x3(run, self._noise_seed)
+            return self._guarded(x.device, run)
 
     def resolve_noise_key(self, device, key: Optional[int] = None) -> int:
         """The Philox key that compensate_features draws with: `key`, or a fresh one taken from torch's default generator of
@@ -826,45 +826,25 @@ class CVSR_V8(nn.Module):
         per frame with image index 0, draw = draws[f] (default f) and the key of resolve_noise_key(): a frame's uniforms depend on
         (key, draws[f]) only, not on which other frames share the call.  Deviation from the reference, which draws per (forward,
         slot): see StreamingSR.run_chunked(share_compensation=True)."""
-        self._inference_only("compensate_features", fea)
+        self._check("compensate_features", fea, size=fea.shape[1:3])
         if fea.dim() != 4 or fea.shape[3] != NF or fea.dtype != torch.float32 or not fea.is_contiguous():
             raise ValueError(f"compensate_features: fea must be a dense fp32 [F,H,W,64] tensor, got {fea.dtype} {tuple(fea.shape)}")
         F, H, W, _ = fea.shape
         if tuple(rms.shape) != (F, 1, H, W):
             raise ValueError(f"compensate_features: rms must be [F,1,H,W] = {(F, 1, H, W)}, got {tuple(rms.shape)}")
-        if H % 8 or W % 8:
-            raise ValueError(f"H and W must be multiples of 8 (window attention, arch.py:2147,2235); got {H}x{W}")
         noise = gumbel_uniform if gumbel_uniform is not None else self.gumbel_uniform
         draws = list(range(F)) if draws is None else [int(d) for d in draws]
         if len(draws) != F or (noise is not None and len(noise) != F):
             raise ValueError(f"compensate_features: one noise tensor / one draw index per frame expected (F = {F})")
+        for f, u in enumerate(noise or ()):
+            if tuple(u.shape) != (1, NF, H, W):
+                raise ValueError(f"compensate_features: noise of frame {f} must be [1,64,{H},{W}], got {tuple(u.shape)}")
         with K.on_device(fea):
             w = self._weights()
-            raw = w["raw"]
             self.H, self.W = H, W
             self.frames_compensated += F
-            dev = fea.device
-            fea_com = K.empty_act(F, H, W, NF, dev)
-            du0 = K.empty_act(F, H // 2 + 1, W // 2 + 1, 4 * NF, dev)       # space-to-depth, + one zero row / column
-            du0[:, H // 2].zero_()
-            du0[:, :, W // 2].zero_()
-            K.stem_conv2(rms.contiguous().float(), H * W, F, H, W, raw["conv_expand_rms.weight"], raw["conv_expand_rms.bias"], fea,
-                         fea_com, w["rms_du0"][0], w["rms_du0"][1], K.ACT_RELU, du0, s2dB=True)
-            noises = []
-            for f in range(F):
-                if noise is None:
-                    cap = None
-                    if self.capture_noise is not None:
-                        cap = torch.empty((1, NF, H, W), device=dev, dtype=torch.float32)
-                        self.capture_noise.append(cap)
-                    noises.append(("rng", self._noise_seed, draws[f], cap))
-                else:
-                    u = noise[f].to(device=dev, dtype=torch.float32).contiguous()
-                    if tuple(u.shape) != (1, NF, H, W):
-                        raise ValueError(f"compensate_features: noise of frame {f} must be [1,64,{H},{W}], got {tuple(u.shape)}")
-                    noises.append(u)
-            x_n = self._rdab(w, du0, fea_com, noises)          # one image per "neighbour": the mask kernel runs per frame
-            return self._conv([fea, x_n], w["conv_expand_fea_r"], pad=1, inner=self.fea_r_single_pass)
+            # one stem launch for all frames; one image per "neighbour": the mask kernel runs per frame
+            return self._compensate(w, fea, [(rms.contiguous().float(), H * W, slice(0, F))], draws, noise)[0]
 
     def forward_windows_shared(self, Lc, comp_bank, comp_idx, x, mvs1, ufs, recompensate=None):
         """K windows of one sequence whose neighbours' compensation is banked per frame: Lc [K,H,W,64] the centres' features,
@@ -875,13 +855,11 @@ class CVSR_V8(nn.Module):
         cdfo_flow_warp_frames), temporal fusion, trunk, up-sampler.  The fp16 range guard is that of ``forward_windows``, settled
         before the call returns; a rejected call is repeated in bf16x3 -- from `recompensate()` -> (comp_bank, comp_idx) if given
         (called in the bf16x3 mode: the caller recomputes the compensation its windows use), else from the same bank."""
-        self._inference_only("forward_windows_shared", x)
+        self._check("forward_windows_shared", x, clip=True)
         Kw, N, C, H, W = x.shape
-        if N != NFRAMES or C != 1 or tuple(Lc.shape) != (Kw, H, W, NF) or comp_bank.dim() != 4 or tuple(comp_bank.shape[1:]) != (H, W, NF):
+        if tuple(Lc.shape) != (Kw, H, W, NF) or comp_bank.dim() != 4 or tuple(comp_bank.shape[1:]) != (H, W, NF):
             raise ValueError(f"expected x [K,7,1,H,W], Lc [K,H,W,64] and comp_bank [cap,H,W,64], got {tuple(x.shape)}, {tuple(Lc.shape)} "
                              f"and {tuple(comp_bank.shape)}")
-        if H % 8 or W % 8:
-            raise ValueError(f"H and W must be multiples of 8 (window attention, arch.py:2147,2235); got {H}x{W}")
         for name, t in (("Lc", Lc), ("comp_bank", comp_bank)):
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise ValueError(f"{name} must be a dense fp32 tensor")
@@ -900,24 +878,13 @@ class CVSR_V8(nn.Module):
                 fused = self._fuse_windows_shared(self._weights(), Lc, state[0], state[1], x, mvs1, ufs)
                 return self._back(fused, x)
 
-            if not (self.precision == "fp16x2" and self.range_guard):
-                return run()
-            self._probe = torch.zeros(4, dtype=torch.int32, device=x.device)
-            try:
-                out = run()
-                probe = self._probe
-            finally:
-                self._probe = None
-            if not self._settle_range(probe):
-                return out
-
             def rerun():
                 if recompensate is not None:
                     bank2, idx2 = recompensate()
                     state[0], state[1] = bank2, idx2.view(-1)
                 return run()
 
-            return self._recompute_bf16x3(rerun, self._noise_seed)
+            return self._guarded(x.device, run, rerun)
 
     def capture(self, x, mvs0, mvs1, pms, rms, ufs, pre_L1_fea=None, gumbel_uniform=None, check_range: bool = True):
         """Capture one inference forward at these operands' shapes into a HIP graph (opt-in; fixed shapes).  Returns a
@@ -958,11 +925,8 @@ class CVSR_V8(nn.Module):
         [B,H,W,64], L1 [B*7,H,W,64] clip-major, x as the contiguous fp32 tensor the skip connection reads).  `_back` is the
         rest; the split exists for callers that run the two halves of consecutive frames beside each other
         (StreamingSR.run_pipelined)."""
+        self._check("forward", x, clip=True, grad_ok=True, capture_ok=True)
         B, N, C, H, W = x.shape
-        if N != NFRAMES or C != 1:
-            raise ValueError(f"expected x of shape [B,7,1,H,W], got {tuple(x.shape)}")
-        if H % 8 or W % 8:
-            raise ValueError(f"H and W must be multiples of 8 (window attention, arch.py:2147,2235); got {H}x{W}")
         w = self._weights()
         raw = w["raw"]
         self.H, self.W = H, W
@@ -1005,11 +969,10 @@ class CVSR_V8(nn.Module):
 
     def _fuse_windows(self, w, Lf, x, mvs1, rms, ufs, gumbel_uniform, deferred_new=None):
         """Steps 2-3 of the forward from the frame-major feature stack Lf [7,B,H,W,64]: the six neighbour pipelines and the
-        temporal fusion.  x: only its device and shape are read here.  deferred_new: `_front`'s cached path at B = 1 -- the new
-        frame's feature extraction, enqueued behind the fork of the side streams.  Returns fused [B,H,W,64]."""
-        B, N, _, H, W = x.shape
-        raw = w["raw"]
-        ctr, P = self.center, H * W
+        temporal fusion.  x: only its device is read here.  gumbel_uniform: resolved by forward() -- injected tensors, or None =
+        draw inside the mask kernel.  deferred_new: `_front`'s cached path at B = 1 -- the new frame's feature extraction,
+        enqueued behind the fork of the side streams.  Returns fused [B,H,W,64]."""
+        N, ctr = NFRAMES, self.center
         nstr = int(getattr(self, "neighbour_streams", 0)) or 2
         gsz = int(getattr(self, "neighbour_group", 0)) or ctr
         # 2. per-neighbour compensation + alignment (arch.py:4443-4460)
@@ -1017,20 +980,11 @@ class CVSR_V8(nn.Module):
             ufs, rms = ufs.transpose(1, 2), rms.transpose(1, 2)
         ufs = ufs.contiguous().float()
         rms = rms.contiguous().float()
-        noise = gumbel_uniform        # resolved by forward(): injected tensors, or None = draw inside the mask kernel
         # The six neighbours share every weight of the compensation + alignment modules, so they are processed as two GROUPS of
         # three frames (frames 0-2 and 4-6 are contiguous in the frame-major feature stack): each operator runs once on 3*B
         # images instead of three times on B.  Only what reads a per-neighbour input plane (prior stems, noise draw, motion
         # field) is launched per neighbour, into slices of the group's tensors.  The two groups are independent: with
         # `neighbour_streams` > 1 they are issued on two side streams (joined before the temporal fusion).
-        main = torch.cuda.current_stream(x.device)
-        side = []
-        if nstr > 1:
-            cache = self.__dict__.setdefault("_side_streams", {})
-            side = cache.get((x.device, nstr))
-            if side is None:
-                side = cache[(x.device, nstr)] = [torch.cuda.Stream(x.device) for _ in range(nstr)]
-        keep = []
         # group size: three frames per group (one launch per operator and group, two groups on two streams) at every batch size.
         # Round 2 kept one frame per group on six streams for one or two clips; measured again in round 3 on the streamed B = 1
         # sequence (tools/bench_streaming.py, 270x480): 66.7 frames/s grouped on two streams against 62.5 (68.1 / 65.6 under
@@ -1038,63 +992,55 @@ class CVSR_V8(nn.Module):
         groups = [list(range(s, min(s + gsz, e))) for (s0, e) in ((0, ctr), (ctr + 1, N)) for s in range(s0, e, gsz)]
         if deferred_new is not None and self.new_frame_alone:
             groups = [list(range(0, ctr)), list(range(ctr + 1, N - 1)), [N - 1]]     # the new frame is a group of its own
-        # the centre features once per neighbour of a group.  Enqueued on the caller's stream BEFORE the side streams fork from
-        # it: they read xcG (Gram pass and last residual of _align), so the copy must be ordered ahead of their wait
-        xcG = Lf[ctr].repeat(gsz, 1, 1, 1) if gsz > 1 else Lf[ctr]
-        for st in side:
-            st.wait_stream(main)
-        if deferred_new is not None:
-            deferred_new()       # on the caller's stream, behind the fork: the side streams do not wait for it
-        aligned_by_frame = {}
-        draw0 = 0
-        for gi, idxs in enumerate(groups):
-            on_side = bool(side) and not (deferred_new is not None and N - 1 in idxs)
-            ctx = torch.cuda.stream(side[gi % len(side)]) if on_side else contextlib.nullcontext()
-            with ctx:
-                al = self._neighbour_group(w, raw, Lf, idxs, xcG, ufs, rms, mvs1, noise, draw0, B, H, W, P, N, keep)
-            draw0 += len(idxs)
-            if on_side:
-                al.record_stream(main)               # produced on a side stream, consumed on the caller's
-            for n, i in enumerate(idxs):
-                aligned_by_frame[i] = al[n * B:(n + 1) * B]
-        for st in side:
-            main.wait_stream(st)
-        aligned: List[torch.Tensor] = [Lf[ctr] if i == ctr else aligned_by_frame[i] for i in range(N)]
-
-        # 3. temporal fusion (arch.py:4463)
-        fused = self._conv(aligned, w["tsa_fusion"], act=K.ACT_LRELU)
-        if self._probe is not None:
-            K.range_probe(fused, self._probe[0:2])
-        return fused
+        xcG = Lf[ctr].repeat(gsz, 1, 1, 1) if gsz > 1 else Lf[ctr]      # the centre features once per neighbour of a group
+        keep = []
+        aligned = self._fork_join(x.device, nstr, groups, deferred_new, lambda gi, idxs: self._neighbour_group(
+            w, Lf, idxs, xcG, ufs, rms, mvs1, gumbel_uniform, keep))
+        return self._fuse(w, Lf[ctr], aligned)
 
     def _fuse_windows_shared(self, w, Lc, comp_bank, comp_idx, x, mvs1, ufs):
         """Steps 2b-3 of the forward with banked compensations: the two neighbour groups (slots 0-2 and 4-6) on the two side
         streams as in `_fuse_windows`, each aligning comp_bank[comp_idx[...]] to the centres; then the temporal fusion.  ufs:
         [K,1,7,H,W] dense.  Returns fused [K,H,W,64]."""
-        B, N, _, H, W = x.shape
-        raw = w["raw"]
-        ctr, P = self.center, H * W
-        main = torch.cuda.current_stream(x.device)
-        cache = self.__dict__.setdefault("_side_streams", {})
-        side = cache.get((x.device, 2))
-        if side is None:
-            side = cache[(x.device, 2)] = [torch.cuda.Stream(x.device) for _ in range(2)]
+        B, N, ctr = x.shape[0], NFRAMES, self.center
+        xcG = Lc.repeat(ctr, 1, 1, 1)
         keep = []
-        groups = [list(range(0, ctr)), list(range(ctr + 1, N))]
-        xcG = Lc.repeat(ctr, 1, 1, 1)        # on the caller's stream, before the side streams fork from it (see _fuse_windows)
+        aligned = self._fork_join(x.device, 2, [list(range(0, ctr)), list(range(ctr + 1, N))], None, lambda gi, idxs: self._align_group(
+            w, idxs, xcG, ufs, mvs1, keep, frames=(comp_bank, comp_idx[gi * ctr * B:(gi + 1) * ctr * B])))
+        return self._fuse(w, Lc, aligned)
+
+    def _fork_join(self, device, nstr, groups, deferred_new, body):
+        """The neighbour groups `groups` (lists of frame indices) beside each other: ``body(gi, idxs)`` -> the group's aligned
+        features [len(idxs)*B,H,W,64], neighbour major, issued under one of `nstr` side streams (on the caller's stream with
+        nstr = 1).  Returns {frame index: its [B,H,W,64] slice}, complete on the caller's stream.
+        The caller has enqueued the groups' common inputs -- xcG, the centre features repeated per neighbour -- on its stream
+        BEFORE this call: the side streams read them (Gram pass and last residual of _align), so that copy must be ordered ahead
+        of their wait.  deferred_new (`_front`: the new frame's feature extraction) is enqueued on the caller's stream behind the
+        fork, so the side streams do not wait for it; the group that reads the new frame then follows it on the caller's stream."""
+        main = torch.cuda.current_stream(device)
+        side = self._side(device, nstr) if nstr > 1 else []
         for st in side:
             st.wait_stream(main)
-        aligned_by_frame = {}
+        if deferred_new is not None:
+            deferred_new()
+        by_frame = {}
         for gi, idxs in enumerate(groups):
-            with torch.cuda.stream(side[gi]):
-                al = self._neighbour_group(w, raw, None, idxs, xcG, ufs, None, mvs1, None, 0, B, H, W, P, N, keep,
-                                           shared=(comp_bank, comp_idx[gi * ctr * B:(gi + 1) * ctr * B]))
-            al.record_stream(main)
+            on_side = bool(side) and not (deferred_new is not None and NFRAMES - 1 in idxs)
+            with torch.cuda.stream(side[gi % len(side)]) if on_side else contextlib.nullcontext():
+                al = body(gi, idxs)
+            if on_side:
+                al.record_stream(main)               # produced on a side stream, consumed on the caller's
+            B = al.shape[0] // len(idxs)
             for n, i in enumerate(idxs):
-                aligned_by_frame[i] = al[n * B:(n + 1) * B]
+                by_frame[i] = al[n * B:(n + 1) * B]
         for st in side:
             main.wait_stream(st)
-        fused = self._conv([Lc if i == ctr else aligned_by_frame[i] for i in range(N)], w["tsa_fusion"], act=K.ACT_LRELU)
+        return by_frame
+
+    def _fuse(self, w, centre, aligned):
+        """Step 3, temporal fusion (arch.py:4463) of the aligned neighbours {frame index: [B,H,W,64]} and the centre features;
+        the range guard's first probe reads its result, the trunk's input."""
+        fused = self._conv([centre if i == self.center else aligned[i] for i in range(NFRAMES)], w["tsa_fusion"], act=K.ACT_LRELU)
         if self._probe is not None:
             K.range_probe(fused, self._probe[0:2])
         return fused
@@ -1121,61 +1067,77 @@ class CVSR_V8(nn.Module):
             out = K.upconv_last(t, w["upconv2"], raw["conv_last.weight"], raw["conv_last.bias"], x[:, ctr], N * P)
         return out
 
-    def _neighbour_group(self, w, raw, Lf, idxs, xcG, ufs, rms, mvs1, noise, draw0, B, H, W, P, N, keep, shared=None):
-        """Neighbour frames `idxs` (consecutive) together: prior stems, RDAB compensation, conv_expand_fea_r, MV alignment
-        (arch.py:4443-4460) on [len(idxs)*B, H, W, 64] tensors, neighbour major.  shared = (comp_bank, idx): the compensation
-        of every frame exists already (compensate_features); only the partition-map stem and the alignment run, the latter
-        reading comp_bank[idx[n*B + b]] in place (Lf, rms, noise, draw0 are unused)."""
+    def _neighbour_group(self, w, Lf, idxs, xcG, ufs, rms, mvs1, noise, keep):
+        """Neighbour frames `idxs` (consecutive) of the frame-major stack Lf [7,B,H,W,64] together: RDAB compensation,
+        conv_expand_fea_r, prior stems, MV alignment (arch.py:4443-4460) on [len(idxs)*B, H, W, 64] tensors, neighbour major.
+        rms / ufs: [B,1,7,H,W] dense."""
+        N, B, H, W, _ = Lf.shape
         G = len(idxs)
-        GB = G * B
-        if shared is not None:
-            x_dev = xcG.device
-            ufs_prior = K.empty_act(GB, H, W, NF, x_dev)
+        # fea_com = fea_i + rms_prior and du0 = relu(conv_du_re.0(rms_prior)) from the residual map itself, per neighbour; a
+        # neighbour's noise draw is its rank among the six
+        stems = [(rms[:, 0, i], N * H * W, slice(n * B, (n + 1) * B)) for n, i in enumerate(idxs)]
+        draws = [i - (i > self.center) for i in idxs]
+        fea_i, x_n = self._compensate(w, Lf[idxs[0]:idxs[0] + G].view(G * B, H, W, NF), stems, draws,
+                                      None if noise is None else [noise[d] for d in draws], keep)
+        if self.debug_taps is not None:
             for n, i in enumerate(idxs):
-                K.stem_conv(ufs[:, 0, i], N * P, B, H, W, raw["conv_expand_ufs.weight"], raw["conv_expand_ufs.bias"],
-                            out=ufs_prior[n * B:(n + 1) * B])
-            al = K.empty_act(GB, H, W, NF, x_dev)
-            xc = xcG if xcG.shape[0] == GB else xcG[:GB]
-            self._align(w, xc, None, ufs_prior, [mvs1[:, i] for i in idxs], N * 2 * P, al, frames=(*shared, mvs1, idxs[0]))
-            if self.debug_taps is not None:
-                for n, i in enumerate(idxs):
-                    self.debug_taps[f"align_{i}"] = al[n * B:(n + 1) * B]
-            keep.extend([ufs_prior, xc])
-            return al
-        x_dev = Lf.device
-        feaG = Lf[idxs[0]:idxs[0] + G].view(GB, H, W, NF)
-        ufs_prior, fea_com = (K.empty_act(GB, H, W, NF, x_dev) for _ in range(2))
-        du0 = K.empty_act(GB, H // 2 + 1, W // 2 + 1, 4 * NF, x_dev)       # space-to-depth, + one zero row / column
+                self.debug_taps[f"rdab_{i}"] = x_n[n * B:(n + 1) * B]
+        return self._align_group(w, idxs, xcG, ufs, mvs1, keep, extra=fea_i)
+
+    def _compensate(self, w, fea, stems, draws, noise, keep=None):
+        """The per-frame half of a neighbour pipeline (arch.py:4443-4454) on a stack of images fea [M,H,W,64]:
+        fea_i = conv_expand_fea_r([fea, RDAB(fea + conv_expand_rms(rms))]).  stems: (rms view, batch stride, slice) -- one
+        stem launch per entry, on the residual maps of the images fea[slice] (image b of the view at b * batch stride); draws:
+        the Philox draw index of each mask launch (M / len(draws) consecutive images each); noise: the injected uniforms of each
+        mask launch instead, or None.  Returns (fea_i, x_n = the RDAB output); keep: receives the intermediates."""
+        raw = w["raw"]
+        M, H, W, _ = fea.shape
+        dev = fea.device
+        fea_com = K.empty_act(M, H, W, NF, dev)
+        du0 = K.empty_act(M, H // 2 + 1, W // 2 + 1, 4 * NF, dev)       # space-to-depth, + one zero row / column
         du0[:, H // 2].zero_()
         du0[:, :, W // 2].zero_()
-        noises = []
-        for n, i in enumerate(idxs):
-            sl = slice(n * B, (n + 1) * B)
-            K.stem_conv(ufs[:, 0, i], N * P, B, H, W, raw["conv_expand_ufs.weight"], raw["conv_expand_ufs.bias"], out=ufs_prior[sl])
-            # fea_com = fea_i + rms_prior and du0 = relu(conv_du_re.0(rms_prior)) from the residual map itself
-            K.stem_conv2(rms[:, 0, i], N * P, B, H, W, raw["conv_expand_rms.weight"], raw["conv_expand_rms.bias"], Lf[i],
+        for rms, bstride, sl in stems:
+            K.stem_conv2(rms, bstride, sl.stop - sl.start, H, W, raw["conv_expand_rms.weight"], raw["conv_expand_rms.bias"], fea[sl],
                          fea_com[sl], w["rms_du0"][0], w["rms_du0"][1], K.ACT_RELU, du0[sl], s2dB=True)
-            draw = draw0 + n
+        noises = []
+        for k, draw in enumerate(draws):
             if noise is None:
                 # the reference's default (torch.rand_like per call, arch.py:2169): the draws are generated INSIDE rdab_prep
                 # (Philox4x32-10), the [B,64,H,W] noise tensor never exists; `capture_noise` (tests) asks for a copy
                 cap = None
                 if self.capture_noise is not None:
-                    cap = torch.empty((B, NF, H, W), device=x_dev, dtype=torch.float32)
+                    cap = torch.empty((M // len(draws), NF, H, W), device=dev, dtype=torch.float32)
                     self.capture_noise.append(cap)
                 noises.append(("rng", self._noise_seed, draw, cap))
             else:
-                noises.append(noise[draw].to(device=x_dev, dtype=torch.float32).contiguous())
+                noises.append(noise[k].to(device=dev, dtype=torch.float32).contiguous())
         x_n = self._rdab(w, du0, fea_com, noises)
-        fea_i = self._conv([feaG, x_n], w["conv_expand_fea_r"], pad=1, inner=self.fea_r_single_pass)
-        al = K.empty_act(GB, H, W, NF, x_dev)
+        fea_i = self._conv([fea, x_n], w["conv_expand_fea_r"], pad=1, inner=self.fea_r_single_pass)
+        if keep is not None:
+            keep.extend([du0, fea_com, noises, x_n, fea_i])
+        return fea_i, x_n
+
+    def _align_group(self, w, idxs, xcG, ufs, mvs1, keep, extra=None, frames=None):
+        """The alignment half of a neighbour pipeline for the slots `idxs` (consecutive): the partition-map stem per slot and the
+        MV alignment (arch.py:4455-4460) of the slots' compensated features to the centres xcG.  Those features are `extra`
+        [len(idxs)*B,H,W,64], neighbour major, or with frames = (comp_bank, idx) the bank of compensate_features, read in place:
+        image n*B + b is comp_bank[idx[n*B + b]].  ufs: [B,1,7,H,W] dense, mvs1: [B,7,2,H,W] dense."""
+        raw = w["raw"]
+        B, N, _, H, W = mvs1.shape
+        GB, P = len(idxs) * B, H * W
+        ufs_prior = K.empty_act(GB, H, W, NF, xcG.device)
+        for n, i in enumerate(idxs):
+            K.stem_conv(ufs[:, 0, i], N * P, B, H, W, raw["conv_expand_ufs.weight"], raw["conv_expand_ufs.bias"],
+                        out=ufs_prior[n * B:(n + 1) * B])
+        al = K.empty_act(GB, H, W, NF, xcG.device)
         xc = xcG if xcG.shape[0] == GB else xcG[:GB]
-        self._align(w, xc, fea_i, ufs_prior, [mvs1[:, i] for i in idxs], N * 2 * P, al)
+        self._align(w, xc, extra, ufs_prior, [mvs1[:, i] for i in idxs], N * 2 * P, al,
+                    frames=None if frames is None else (*frames, mvs1, idxs[0]))
         if self.debug_taps is not None:
             for n, i in enumerate(idxs):
-                self.debug_taps[f"rdab_{i}"] = x_n[n * B:(n + 1) * B]
                 self.debug_taps[f"align_{i}"] = al[n * B:(n + 1) * B]
-        keep.extend([ufs_prior, du0, fea_com, noises, x_n, fea_i, xc])
+        keep.extend([ufs_prior, xc])
         return al
 
     @staticmethod

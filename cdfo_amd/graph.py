@@ -71,7 +71,7 @@ class CapturedForward:
         self._refresh = getattr(model, "refresh_noise_key", None) if self.draws_noise else None
         if self._refresh is not None:
             self._refresh(self.dev)
-        # the guard's probes inside the graph (CVSR_V8.forward's capturing branch reads model._graph_probe)
+        # the guard's probes inside the graph (CVSR_V8._guarded's capturing branch reads model._graph_probe)
         self.guarded = bool(check_range and getattr(model, "precision", None) == "fp16x2" and getattr(model, "range_guard", False)
                             and hasattr(model, "_range_fallback"))
         self._pending, self._seed, self.last_range_seen = False, None, None
