@@ -1296,3 +1296,49 @@ def seq_attn(q: torch.Tensor, v: torch.Tensor, mode: int, out: Optional[torch.Te
         return out
     check(_lib.lib().cdfo_seq_attn(_vp(q), ldq, _vp(v), ldv, _vp(out), ldo, B, H, W, mode, _stream()), "cdfo_seq_attn")
     return out
+
+
+# ------------------------------------------------------------------------------------- training batches and the training loss
+def train_batch(lr: torch.Tensor, pms: torch.Tensor, rms: torch.Tensor, ufs: torch.Tensor, mvl0: torch.Tensor, hr: torch.Tensor,
+                plan: torch.Tensor, crop: int):
+    """The resident clip set (cdfo_amd/train_data.py::ClipSet's tensors) and a device plan int32 [B,8] -> (x, mvs0, pms, rms, ufs, hr)
+    of B samples in one launch.  The plan's rows are the caller's to validate (ClipSet.batch does); shapes and dtypes are checked here."""
+    S, T, H, W = lr.shape
+    want = ((lr, torch.uint8, (S, T, H, W)), (pms, torch.uint8, (S, T, H, W)), (rms, torch.int8, (S, T, H, W)),
+            (ufs, torch.uint8, (S, T, ufs.shape[2] if ufs.dim() == 4 else -1, W)), (mvl0, torch.int8, (S, T, H, W, 3)),
+            (hr, torch.uint8, (S, T, 4 * H, 4 * W)))
+    for t, dtype, shape in want:
+        if not t.is_cuda or t.device != lr.device or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"train_batch: a dense {dtype} device tensor {shape} expected, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    if plan.dtype != torch.int32 or plan.dim() != 2 or plan.shape[1] != 8 or not plan.is_contiguous() or plan.device != lr.device \
+            or plan.shape[0] == 0:
+        raise ValueError("train_batch: the plan is a dense int32 [B,8] tensor on the clip set's device, B >= 1")
+    B, c, dev = int(plan.shape[0]), int(crop), lr.device
+    if c <= 0 or c % 4 or c > min(H, W):
+        raise ValueError(f"train_batch: crop must be a positive multiple of 4 that fits the {H}x{W} frames, got {crop}")
+    f32 = dict(dtype=torch.float32, device=dev)
+    x, pm = torch.empty((B, 7, 1, c, c), **f32), torch.empty((B, 7, 1, c, c), **f32)
+    rm, uf = torch.empty((B, 1, 7, c, c), **f32), torch.empty((B, 1, 7, c, c), **f32)
+    mvs0, hro = torch.empty((B, 7, 2, c, c), **f32), torch.empty((B, 1, 4 * c, 4 * c), **f32)
+    check(_lib.lib().cdfo_train_batch(_vp(lr), _vp(pms), _vp(rms), _vp(ufs), _vp(mvl0), _vp(hr), S, T, H, W, int(ufs.shape[2]), _vp(plan),
+                                      B, c, _vp(x), _vp(pm), _vp(rm), _vp(uf), _vp(mvs0), _vp(hro), _stream()), "cdfo_train_batch")
+    return x, mvs0, pm, rm, uf, hro
+
+
+CHARBONNIER_MAX_BLOCKS = 1024        # CDFO_CHARBONNIER_MAX_BLOCKS of include/cdfo_hip.h
+
+
+def charbonnier(sr: torch.Tensor, hr: torch.Tensor, eps: float):
+    """(loss fp32 scalar, g fp32 like sr): the sum of sqrt((sr - hr)^2 + eps) and its derivative by sr, one pass; no host sync."""
+    for name, t in (("sr", sr), ("hr", hr)):
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"charbonnier: {name} must be a dense fp32 device tensor, got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+    if sr.shape != hr.shape or sr.device != hr.device or sr.numel() == 0:
+        raise ValueError(f"charbonnier: sr and hr must have one non-empty shape on one device, got {tuple(sr.shape)} and {tuple(hr.shape)}")
+    n = sr.numel()
+    g = torch.empty_like(sr)
+    partial = torch.empty(CHARBONNIER_MAX_BLOCKS, dtype=torch.float64, device=sr.device)
+    loss = torch.empty((), dtype=torch.float32, device=sr.device)
+    check(_lib.lib().cdfo_charbonnier(_vp(sr), _vp(hr), C.c_longlong(n), C.c_float(eps), _vp(g), _vp(partial), CHARBONNIER_MAX_BLOCKS,
+                                      _vp(loss), _stream()), "cdfo_charbonnier")
+    return loss, g

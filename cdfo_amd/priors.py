@@ -144,14 +144,18 @@ def _filtered_rows(img: np.ndarray, filter_type: int, bpp: int = 1) -> bytes:
     return bytes(rows)
 
 
-def load_priors(side_dir: str, T: int, shape=None, depth: int = 8) -> Dict[str, np.ndarray]:
+def load_priors(side_dir: str, T: int, shape=None, depth: int = 8, own_frame0: bool = False) -> Dict[str, np.ndarray]:
     """The coding priors of a sequence of T frames: pms uint8, ufs uint8 or (16-bit PNGs) uint16 [T,H,W]; rms [T,H,W] (dtype of the
     ``*_res.npy`` files); mvl0, mvl1 [T,H,W,3].  Entry 0 (which the reference never reads: ``ii = max(1, i)``) repeats entry 1.  ``shape``: the (T,H,W) of the
     LR frames the planes must have, else ValueError.  ``depth``: the bit depth of the sequence's samples; the unfiltered planes must
     be 8-bit PNGs at depth 8 and 16-bit PNGs above it, and the partition maps 8-bit at every depth, else ValueError (a plane of the
-    wrong depth would be divided by the wrong peak without a sound)."""
+    wrong depth would be divided by the wrong peak without a sound).  ``own_frame0``: entry 0 is read from the ``00000_*`` files, as the
+    reference's TRAINING loader reads them (opt/data_LD_bi.py:74-118: every frame its own files); a missing one is then a
+    FileNotFoundError that names it.  The unfiltered planes of that layout may have more rows than the LR frames (272 beside 270)."""
 
     def per_frame(fn):
+        if own_frame0:
+            return np.stack([fn("%05d" % t) for t in range(T)])
         items = [fn("%05d" % max(1, t)) for t in range(T)] if T > 1 else [fn("%05d" % 1)]
         return np.stack(items)
 
@@ -171,15 +175,17 @@ def load_priors(side_dir: str, T: int, shape=None, depth: int = 8) -> Dict[str, 
     mvl1 = per_frame(lambda i: np.load(os.path.join(side_dir, "mvl1", i + "_mvl1.npy")))
     if shape is not None:
         for name, arr in (("pms", pms), ("ufs", ufs), ("rms", rms)):
-            if arr.shape != tuple(shape):
+            taller = own_frame0 and name == "ufs" and arr.shape[1] > shape[1] and arr.shape[::2] == tuple(shape)[::2]
+            if arr.shape != tuple(shape) and not taller:
                 raise ValueError(f"{name} planes are {arr.shape[1:]} but the LR frames are {tuple(shape)[1:]}")
     return dict(pms=pms, rms=rms, ufs=ufs, mvl0=mvl0, mvl1=mvl1)
 
 
-def load_sequence(lr_dir: str, side_dir: str) -> Dict[str, np.ndarray]:
+def load_sequence(lr_dir: str, side_dir: str, own_frame0: bool = False) -> Dict[str, np.ndarray]:
     """One sequence of the reference's test layout -> the arrays ``StreamingSR`` takes:
     lr, pms, ufs uint8 [T,H,W]; rms [T,H,W] (dtype of the ``*_res.npy`` files); mvl0, mvl1 [T,H,W,3].
-    Index t = file index t; entry 0 of the priors (which the reference never reads: ``ii = max(1, i)``) repeats entry 1."""
+    Index t = file index t; entry 0 of the priors (which the reference never reads: ``ii = max(1, i)``) repeats entry 1, unless
+    ``own_frame0`` asks for the ``00000_*`` files (`load_priors`)."""
     names = sorted(n for n in os.listdir(lr_dir) if n.lower().endswith(".png"))
     if not names:
         raise FileNotFoundError(f"no PNG frames in {lr_dir}")
@@ -187,4 +193,4 @@ def load_sequence(lr_dir: str, side_dir: str) -> Dict[str, np.ndarray]:
     if lr.dtype != np.uint8:
         raise NotImplementedError(f"{lr_dir}: only 8-bit LR frames are supported in the PNG layout, these are {lr.dtype} "
                                   f"(high bit depth goes through raw files: cdfo_amd/yuv.py)")
-    return dict(lr=lr, **load_priors(side_dir, len(names), lr.shape))
+    return dict(lr=lr, **load_priors(side_dir, len(names), lr.shape, own_frame0=own_frame0))

@@ -652,6 +652,31 @@ int cdfo_msssim_partials_u16(const unsigned short* a, int a_pitch, long long a_f
                              int b_pitch, long long b_fstride, int Hb, int Wb, int N, int crop, int peak, float* pyramid,
                              long long pyramid_bytes, double* partial, int partial_cap, int* nblocks_out, void* stream);
 
+/* ---- training batches and the training loss (train_batch.hip; cdfo_amd/train_data.py, cdfo_amd/loss.py) ----
+ * cdfo_train_batch:   the resident clip set -- lr, pms, hr unsigned and rms signed 8-bit [S][T][H][W] ([S][T][4H][4W] for hr), ufs
+ *                     [S][T][Hu][W] with Hu >= H rows indexed from the top, mvl0 signed 8-bit [S][T][H][W][3] (a, b, ref), all dense --
+ *                     -> B samples in ONE launch.  plan: B rows of 8 ints on the device, (seq, first, top, left, hflip, vflip, rot, 0):
+ *                     frames first .. first + 6 of sequence seq, cut at (top, left) to crop x crop (hr: frame first + 3, 4 crop each
+ *                     way from (4 top, 4 left)).  out[y][x] = P[top + i'][left + j'] / 255 (correctly rounded), (i, j) = rot ? (x, y)
+ *                     : (y, x), i' = vflip ? n-1-i : i, j' = hflip ? n-1-j : j.  x, pms_out: [B][7][1][c][c]; rms_out, ufs_out:
+ *                     [B][1][7][c][c]; hr_out: [B][1][4c][4c]; mvs0: [B][7][2][c][c] from mvl0 of frame first + 3 through the same
+ *                     index map: m0 = b, m1 = a, hflip negates m0, vflip m1, rot swaps them, p = m / (ref * -1) with NaN -> 0 (an
+ *                     infinity stays, as in cdfo_seq_flows), slot k = fl(p * (3 - k)) / 128, slot 3 = +0.  crop % 4 == 0,
+ *                     crop <= min(H, W), T >= 7, B <= 65535, else CDFO_EINVAL; outputs 16-byte aligned.  The caller validates the
+ *                     plan's rows; a row that does not fit the set writes nothing.
+ * cdfo_charbonnier:   sr, hr: n fp32 values each.  grad[i] = d / sqrt(d^2 + eps), d = sr[i] - hr[i]; *loss = the sum of
+ *                     sqrt(d^2 + eps), accumulated in fp64 (partials per workgroup, added in a fixed order by a second launch: no
+ *                     atomics, equal inputs give equal bits), rounded once to fp32.  Square root and division correctly rounded;
+ *                     non-finite values propagate.  partial: scratch of partial_cap doubles, 8-byte aligned; min(ceil(n / 1024),
+ *                     CDFO_CHARBONNIER_MAX_BLOCKS) are used, so CDFO_CHARBONNIER_MAX_BLOCKS always suffice (less is CDFO_EINVAL when
+ *                     it does not).  Two launches whatever n. */
+#define CDFO_CHARBONNIER_MAX_BLOCKS 1024
+int cdfo_train_batch(const unsigned char* lr, const unsigned char* pms, const signed char* rms, const unsigned char* ufs,
+                     const signed char* mvl0, const unsigned char* hr, int S, int T, int H, int W, int Hu, const int* plan, int B,
+                     int crop, float* x, float* pms_out, float* rms_out, float* ufs_out, float* mvs0, float* hr_out, void* stream);
+int cdfo_charbonnier(const float* sr, const float* hr, long long n, float eps, float* grad, double* partial, int partial_cap,
+                     float* loss, void* stream);
+
 /* ---- optional per-launch HIP-event timing on the launch stream (bench.py's live roofline figures) ----------- */
 int cdfo_prof_begin(int max_records);
 int cdfo_prof_end(int* launches, double* ms, double* flops, double* bytes, int nkid);
