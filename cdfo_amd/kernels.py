@@ -1299,30 +1299,50 @@ def seq_attn(q: torch.Tensor, v: torch.Tensor, mode: int, out: Optional[torch.Te
 
 
 # ------------------------------------------------------------------------------------- training batches and the training loss
-def train_batch(lr: torch.Tensor, pms: torch.Tensor, rms: torch.Tensor, ufs: torch.Tensor, mvl0: torch.Tensor, hr: torch.Tensor,
-                plan: torch.Tensor, crop: int):
-    """The resident clip set (cdfo_amd/train_data.py::ClipSet's tensors) and a device plan int32 [B,8] -> (x, mvs0, pms, rms, ufs, hr)
-    of B samples in one launch.  The plan's rows are the caller's to validate (ClipSet.batch does); shapes and dtypes are checked here."""
+def _train_batch(who, lr, pms, rms, ufs, mvl0, mvl1, hr, plan, crop):
+    """Both forms of a training batch: ``mvl1`` None is the LD form (cdfo_train_batch), a tensor the RA form (cdfo_train_batch_ra)."""
     S, T, H, W = lr.shape
-    want = ((lr, torch.uint8, (S, T, H, W)), (pms, torch.uint8, (S, T, H, W)), (rms, torch.int8, (S, T, H, W)),
+    want = [(lr, torch.uint8, (S, T, H, W)), (pms, torch.uint8, (S, T, H, W)), (rms, torch.int8, (S, T, H, W)),
             (ufs, torch.uint8, (S, T, ufs.shape[2] if ufs.dim() == 4 else -1, W)), (mvl0, torch.int8, (S, T, H, W, 3)),
-            (hr, torch.uint8, (S, T, 4 * H, 4 * W)))
+            (hr, torch.uint8, (S, T, 4 * H, 4 * W))]
+    if mvl1 is not None:
+        want.append((mvl1, torch.int8, (S, T, H, W, 3)))
     for t, dtype, shape in want:
         if not t.is_cuda or t.device != lr.device or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f"train_batch: a dense {dtype} device tensor {shape} expected, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            raise ValueError(f"{who}: a dense {dtype} device tensor {shape} expected, got {t.dtype} {tuple(t.shape)} on {t.device}")
     if plan.dtype != torch.int32 or plan.dim() != 2 or plan.shape[1] != 8 or not plan.is_contiguous() or plan.device != lr.device \
             or plan.shape[0] == 0:
-        raise ValueError("train_batch: the plan is a dense int32 [B,8] tensor on the clip set's device, B >= 1")
+        raise ValueError(f"{who}: the plan is a dense int32 [B,8] tensor on the clip set's device, B >= 1")
     B, c, dev = int(plan.shape[0]), int(crop), lr.device
     if c <= 0 or c % 4 or c > min(H, W):
-        raise ValueError(f"train_batch: crop must be a positive multiple of 4 that fits the {H}x{W} frames, got {crop}")
+        raise ValueError(f"{who}: crop must be a positive multiple of 4 that fits the {H}x{W} frames, got {crop}")
     f32 = dict(dtype=torch.float32, device=dev)
     x, pm = torch.empty((B, 7, 1, c, c), **f32), torch.empty((B, 7, 1, c, c), **f32)
     rm, uf = torch.empty((B, 1, 7, c, c), **f32), torch.empty((B, 1, 7, c, c), **f32)
     mvs0, hro = torch.empty((B, 7, 2, c, c), **f32), torch.empty((B, 1, 4 * c, 4 * c), **f32)
-    check(_lib.lib().cdfo_train_batch(_vp(lr), _vp(pms), _vp(rms), _vp(ufs), _vp(mvl0), _vp(hr), S, T, H, W, int(ufs.shape[2]), _vp(plan),
-                                      B, c, _vp(x), _vp(pm), _vp(rm), _vp(uf), _vp(mvs0), _vp(hro), _stream()), "cdfo_train_batch")
+    tail = (S, T, H, W, int(ufs.shape[2]), _vp(plan), B, c, _vp(x), _vp(pm), _vp(rm), _vp(uf), _vp(mvs0), _vp(hro), _stream())
+    if mvl1 is None:
+        check(_lib.lib().cdfo_train_batch(_vp(lr), _vp(pms), _vp(rms), _vp(ufs), _vp(mvl0), _vp(hr), *tail), "cdfo_train_batch")
+    else:
+        check(_lib.lib().cdfo_train_batch_ra(_vp(lr), _vp(pms), _vp(rms), _vp(ufs), _vp(mvl0), _vp(mvl1), _vp(hr), *tail),
+              "cdfo_train_batch_ra")
     return x, mvs0, pm, rm, uf, hro
+
+
+def train_batch(lr: torch.Tensor, pms: torch.Tensor, rms: torch.Tensor, ufs: torch.Tensor, mvl0: torch.Tensor, hr: torch.Tensor,
+                plan: torch.Tensor, crop: int):
+    """The resident clip set (cdfo_amd/train_data.py::ClipSet's tensors) and a device plan int32 [B,8] -> (x, mvs0, pms, rms, ufs, hr)
+    of B samples in one launch.  The plan's rows are the caller's to validate (ClipSet.batch does); shapes and dtypes are checked here."""
+    return _train_batch("train_batch", lr, pms, rms, ufs, mvl0, None, hr, plan, crop)
+
+
+def train_batch_ra(lr: torch.Tensor, pms: torch.Tensor, rms: torch.Tensor, ufs: torch.Tensor, mvl0: torch.Tensor, mvl1: torch.Tensor,
+                   hr: torch.Tensor, plan: torch.Tensor, crop: int):
+    """`train_batch` for a random-access clip set: ``mvl1`` is the second list's field, int8 and dense in ``mvl0``'s shape, and the
+    returned flow field (x, mvs, pms, rms, ufs, hr) is built from both lists (opt/data_RA_bi.py:495-533); it serves as mvs0 and mvs1."""
+    if mvl1 is None:
+        raise ValueError("train_batch_ra: mvl1 is required")
+    return _train_batch("train_batch_ra", lr, pms, rms, ufs, mvl0, mvl1, hr, plan, crop)
 
 
 CHARBONNIER_MAX_BLOCKS = 1024        # CDFO_CHARBONNIER_MAX_BLOCKS of include/cdfo_hip.h

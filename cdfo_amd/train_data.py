@@ -12,8 +12,16 @@ arithmetic bit for bit (tests/golden/train_batch_ref.npz holds the real referenc
     mvl0      int8  [S,T,H,W,3]           components (a, b, ref)
     hr        uint8 [S,T,4H,4W]           66 MB per 32-frame 1080p sequence (32 x 1080 x 1920 bytes)
 
-``mvl1`` is not stored: the reference's ``Augment`` returns an all-zero ``mvl1s_7`` (opt/data_LD_bi.py:473-489), so ``batch`` hands
-out one cached zero tensor for it.
+A set has a coding, the reference's two training configurations.  ``"LD"`` (low delay, opt/data_LD_bi.py; the default) stores no
+``mvl1``: that loader's ``Augment`` returns an all-zero ``mvl1s_7`` (:473-489), so ``batch`` hands out one cached zero tensor for it.
+``"RA"`` (random access, opt/data_RA_bi.py) also stores
+
+    mvl1      int8  [S,T,H,W,3]           the second reference list's field
+
+and builds the flow field from both lists (:495-533): list 0 feeds slots 0-2, list 1 slots 4-6, and each stands in for the other where
+a block has no reference in it (a reference component of -99).  That loader sets ``mvl1s_7 = mvl0s_7``, so ``batch`` returns ONE tensor
+as ``mvs0`` and ``mvs1``.  Everything else -- planes, plans, draw ranges -- is the same in both codings (tests/golden/
+train_batch_ra_ref.npz holds the real RA loader's outputs).
 
 A batch is described by a host plan, int32 [B,8], rows ``(seq, first, top, left, hflip, vflip, rot, 0)``: ``draw`` and ``epoch`` make
 plans with the reference's distribution (not its RNG streams), ``batch`` validates a plan on the host, uploads it and launches."""
@@ -37,9 +45,11 @@ def _clip_i8(a: np.ndarray) -> np.ndarray:
 
 
 class ClipSet:
-    def __init__(self, lr, pms, rms, ufs, mvl0, hr):
-        """Device tensors in the storage types of the module docstring (see `from_arrays` / `from_directories`)."""
-        self.lr, self.pms, self.rms, self.ufs, self.mvl0, self.hr = lr, pms, rms, ufs, mvl0, hr
+    def __init__(self, lr, pms, rms, ufs, mvl0, hr, mvl1=None):
+        """Device tensors in the storage types of the module docstring (see `from_arrays` / `from_directories`); ``mvl1`` makes the
+        set a random-access one."""
+        self.lr, self.pms, self.rms, self.ufs, self.mvl0, self.hr, self.mvl1 = lr, pms, rms, ufs, mvl0, hr, mvl1
+        self.coding = "LD" if mvl1 is None else "RA"
         self.S, self.T, self.H, self.W = (int(v) for v in lr.shape)
         self._zero_flows = {}
 
@@ -47,32 +57,40 @@ class ClipSet:
         return self.S
 
     @classmethod
-    def from_arrays(cls, lr, pms, rms, ufs, mvl0, hr, device="cuda") -> "ClipSet":
+    def from_arrays(cls, lr, pms, rms, ufs, mvl0, hr, device="cuda", *, mvl1=None, coding="LD") -> "ClipSet":
         """numpy arrays [S,T,...] -> a resident set.  Residuals and motion fields are clipped to int8 as the reference loader clips
-        them; the 8-bit planes must be uint8.  Shapes are checked against ``lr`` before anything is uploaded."""
+        them; the 8-bit planes must be uint8.  Shapes are checked against ``lr`` before anything is uploaded.  ``coding="RA"`` needs
+        ``mvl1`` (clipped and shaped like ``mvl0``), ``coding="LD"`` takes none."""
+        if coding not in ("LD", "RA"):
+            raise ValueError(f"coding is 'LD' or 'RA', got {coding!r}")
+        if (coding == "RA") != (mvl1 is not None):
+            raise ValueError("coding='RA' needs mvl1" if coding == "RA" else "coding='LD' stores no mvl1: pass coding='RA' with it")
         lr, pms, ufs, hr = (np.asarray(a) for a in (lr, pms, ufs, hr))
         if lr.ndim != 4 or lr.shape[1] < FRAMES:
             raise ValueError(f"lr must be [S,T,H,W] with T >= {FRAMES}, got {lr.shape}")
         S, T, H, W = lr.shape
         rms, mvl0 = _clip_i8(np.asarray(rms)), _clip_i8(np.asarray(mvl0))
+        lists = (("mvl0", mvl0),) if mvl1 is None else (("mvl0", mvl0), ("mvl1", _clip_i8(np.asarray(mvl1))))
         for name, a in (("lr", lr), ("pms", pms), ("ufs", ufs), ("hr", hr)):
             if a.dtype != np.uint8:
                 raise ValueError(f"{name} must be uint8, got {a.dtype}")
-        for name, a, shape in (("pms", pms, (S, T, H, W)), ("rms", rms, (S, T, H, W)), ("mvl0", mvl0, (S, T, H, W, 3)),
+        for name, a, shape in (("pms", pms, (S, T, H, W)), ("rms", rms, (S, T, H, W)), *((n, a, (S, T, H, W, 3)) for n, a in lists),
                                ("hr", hr, (S, T, 4 * H, 4 * W))):
             if a.shape != shape:
                 raise ValueError(f"{name} is {a.shape}, the LR frames {lr.shape} need {shape}")
         if ufs.ndim != 4 or ufs.shape[:2] != (S, T) or ufs.shape[3] != W or ufs.shape[2] < H:
             raise ValueError(f"ufs is {ufs.shape}, the LR frames {lr.shape} need ({S}, {T}, >= {H}, {W})")
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)      # noqa: E731
-        return cls(up(lr), up(pms), up(rms), up(ufs), up(mvl0), up(hr))
+        return cls(up(lr), up(pms), up(rms), up(ufs), up(mvl0), up(hr), *(up(a) for _, a in lists[1:]))
 
     @classmethod
-    def from_directories(cls, sequences: Sequence[Tuple[str, str, str]], device="cuda") -> "ClipSet":
+    def from_directories(cls, sequences: Sequence[Tuple[str, str, str]], device="cuda", *, coding="LD") -> "ClipSet":
         """``[(lr_dir, side_dir, hr_dir), ...]``: the layout of cdfo_amd/priors.py, every frame with its OWN prior files (the training
         loader reads ``00000_*`` too; a missing one is an error naming it), plus ``<hr_dir>/%05d.png``, 8-bit grey, 4H x 4W.  All
-        sequences must have one shape."""
-        cols = {k: [] for k in ("lr", "pms", "rms", "ufs", "mvl0", "hr")}
+        sequences must have one shape.  ``coding="RA"`` keeps the ``mvl1`` files' fields too."""
+        if coding not in ("LD", "RA"):
+            raise ValueError(f"coding is 'LD' or 'RA', got {coding!r}")
+        cols = {k: [] for k in ("lr", "pms", "rms", "ufs", "mvl0", "hr") + (("mvl1",) if coding == "RA" else ())}
         for lr_dir, side_dir, hr_dir in sequences:
             seq = load_sequence(lr_dir, side_dir, own_frame0=True)
             seq["hr"] = np.stack([read_gray_png(os.path.join(hr_dir, "%05d.png" % t)) for t in range(len(seq["lr"]))])
@@ -82,7 +100,8 @@ class ClipSet:
                 cols[k].append(seq[k])
         if not cols["lr"]:
             raise ValueError("no sequences given")
-        return cls.from_arrays(*(np.stack(cols[k]) for k in ("lr", "pms", "rms", "ufs", "mvl0", "hr")), device=device)
+        return cls.from_arrays(*(np.stack(cols[k]) for k in ("lr", "pms", "rms", "ufs", "mvl0", "hr")), device=device,
+                               mvl1=np.stack(cols["mvl1"]) if coding == "RA" else None, coding=coding)
 
     # ------------------------------------------------------------------------------------------------------------------ plans
     def draw(self, B: int, rng: np.random.Generator, crop: int = 64, seqs=None) -> np.ndarray:
@@ -126,10 +145,16 @@ class ClipSet:
     # ---------------------------------------------------------------------------------------------------------------- batches
     def batch(self, plan, crop: int = 64):
         """(x, mvs0, mvs1, pms, rms, ufs, hr), fp32 and dense, in the shapes train_LD_37.py:365-377 hands to the model and the loss:
-        x, pms [B,7,1,c,c]; mvs0, mvs1 [B,7,2,c,c]; rms, ufs [B,1,7,c,c]; hr [B,1,4c,4c].  One launch.  ``mvs1`` is a cached zero
-        tensor shared by every batch of its shape: callers must not write into it."""
+        x, pms [B,7,1,c,c]; mvs0, mvs1 [B,7,2,c,c]; rms, ufs [B,1,7,c,c]; hr [B,1,4c,4c].  One launch.  In an LD set ``mvs1`` is a
+        cached zero tensor shared by every batch of its shape; in an RA set ``mvs1`` IS ``mvs0`` (the reference's two fields are equal
+        there, train_RA_37.py:383-386).  Callers must not write into either."""
         p = self.check_plan(plan, crop)
         B = p.shape[0]
+        if self.coding == "RA":
+            with K.on_device(self.lr):
+                x, mvs, pms, rms, ufs, hr = K.train_batch_ra(self.lr, self.pms, self.rms, self.ufs, self.mvl0, self.mvl1, self.hr,
+                                                             torch.from_numpy(p).to(self.lr.device), crop)
+            return x, mvs, mvs, pms, rms, ufs, hr
         with K.on_device(self.lr):
             x, mvs0, pms, rms, ufs, hr = K.train_batch(self.lr, self.pms, self.rms, self.ufs, self.mvl0, self.hr,
                                                        torch.from_numpy(p).to(self.lr.device), crop)
@@ -138,10 +163,15 @@ class ClipSet:
         return x, mvs0, self._zero_flows[(B, crop)], pms, rms, ufs, hr
 
 
-def synthetic_arrays(S: int, T: int, H: int, W: int, seed: int = 0):
+def synthetic_arrays(S: int, T: int, H: int, W: int, seed: int = 0, coding: str = "LD"):
     """Random content for tools and tests that have no data set at hand, as (lr, pms, rms, ufs, mvl0, hr) for `ClipSet.from_arrays`:
     a smooth scene per sequence that drifts by a whole HR pixel per frame, its x4 area mean plus noise as the LR frames, block-constant
-    motion with a reference distance of -2, -1 or 1 (never 0: the flows stay finite), unfiltered planes of H + 2 rows."""
+    motion with a reference distance of -2, -1 or 1 (never 0: the flows stay finite), unfiltered planes of H + 2 rows.
+    ``coding="RA"`` returns a seventh array, ``mvl1`` (for ``from_arrays(*six, mvl1=mvl1, coding="RA")``): block-constant like
+    ``mvl0``, and a block in eight is marked -99 in list 0, one in list 1 and one in both; the other distances stay non-zero.  The
+    first six arrays of a seed do not depend on the coding except for list 0's markers."""
+    if coding not in ("LD", "RA"):
+        raise ValueError(f"coding is 'LD' or 'RA', got {coding!r}")
     rs = np.random.RandomState(seed)
     lr, hr = np.zeros((S, T, H, W), np.uint8), np.zeros((S, T, 4 * H, 4 * W), np.uint8)
     for s in range(S):
@@ -157,5 +187,14 @@ def synthetic_arrays(S: int, T: int, H: int, W: int, seed: int = 0):
     mv = rs.randint(-64, 64, (S, T, hb, wb, 3))
     mv[..., 2] = rs.choice([-2, -1, 1], size=(S, T, hb, wb))
     mvl0 = np.repeat(np.repeat(mv, 8, axis=2), 8, axis=3)[:, :, :H, :W]
-    return (lr, rs.randint(0, 256, (S, T, H, W)).astype(np.uint8), np.round(rs.randn(S, T, H, W) * 6),
-            rs.randint(0, 256, (S, T, H + 2, W)).astype(np.uint8), mvl0, hr)
+    six = (lr, rs.randint(0, 256, (S, T, H, W)).astype(np.uint8), np.round(rs.randn(S, T, H, W) * 6),
+           rs.randint(0, 256, (S, T, H + 2, W)).astype(np.uint8), mvl0, hr)
+    if coding == "LD":
+        return six
+    mv1 = rs.randint(-64, 64, (S, T, hb, wb, 3))                 # drawn after everything the LD call draws
+    mv1[..., 2] = rs.choice([-2, -1, 1], size=(S, T, hb, wb))
+    mark = rs.randint(0, 8, (S, T, hb, wb))                      # 1: list 0 has no reference, 2: list 1, 3: neither has
+    mv[..., 2][(mark == 1) | (mark == 3)] = -99
+    mv1[..., 2][(mark == 2) | (mark == 3)] = -99
+    block = lambda a: np.repeat(np.repeat(a, 8, axis=2), 8, axis=3)[:, :, :H, :W]      # noqa: E731
+    return six[:4] + (block(mv), hr, block(mv1))

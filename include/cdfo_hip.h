@@ -664,7 +664,14 @@ int cdfo_msssim_partials_u16(const unsigned short* a, int a_pitch, long long a_f
  *                     infinity stays, as in cdfo_seq_flows), slot k = fl(p * (3 - k)) / 128, slot 3 = +0.  crop % 4 == 0,
  *                     crop <= min(H, W), T >= 7, B <= 65535, else CDFO_EINVAL; outputs 16-byte aligned.  The caller validates the
  *                     plan's rows; a row that does not fit the set writes nothing.
- * cdfo_charbonnier:   sr, hr: n fp32 values each.  grad[i] = d / sqrt(d^2 + eps), d = sr[i] - hr[i]; *loss = the sum of
+ * cdfo_train_batch_ra: the random-access form (opt/data_RA_bi.py).  cdfo_train_batch's arguments plus mvl1, the second list's field,
+ *                     signed 8-bit [S][T][H][W][3] like mvl0 (null is CDFO_EINVAL); the six plane outputs, the grid and every check
+ *                     are cdfo_train_batch's.  mvs: [B][7][2][c][c] from both fields of frame first + 3, each through the index map
+ *                     and the m0 / m1 rules above: p2 = m(list 0) / (ref0 * -1), p4 = m(list 1) / ref1, NaN -> +0, an infinity stays;
+ *                     then ref0 == -99: p2 = -p4, and after that ref1 == -99: p4 = -p2 (both marked: p4 stays, p2 = -p4; the
+ *                     negations give -0 where the reference's do).  Slots 0, 1, 2 = fl(p2 * w) / 128 with w = 3, 2, 1, slot 3 = +0,
+ *                     slots 4, 5, 6 = fl(p4 * w) / 128 with w = 1, 2, 3.  The reference's mvs1 equals this field: it is written once.
+ * cdfo_charbonnier:  sr, hr: n fp32 values each.  grad[i] = d / sqrt(d^2 + eps), d = sr[i] - hr[i]; *loss = the sum of
  *                     sqrt(d^2 + eps), accumulated in fp64 (partials per workgroup, added in a fixed order by a second launch: no
  *                     atomics, equal inputs give equal bits), rounded once to fp32.  Square root and division correctly rounded;
  *                     non-finite values propagate.  partial: scratch of partial_cap doubles, 8-byte aligned; min(ceil(n / 1024),
@@ -674,6 +681,10 @@ int cdfo_msssim_partials_u16(const unsigned short* a, int a_pitch, long long a_f
 int cdfo_train_batch(const unsigned char* lr, const unsigned char* pms, const signed char* rms, const unsigned char* ufs,
                      const signed char* mvl0, const unsigned char* hr, int S, int T, int H, int W, int Hu, const int* plan, int B,
                      int crop, float* x, float* pms_out, float* rms_out, float* ufs_out, float* mvs0, float* hr_out, void* stream);
+int cdfo_train_batch_ra(const unsigned char* lr, const unsigned char* pms, const signed char* rms, const unsigned char* ufs,
+                        const signed char* mvl0, const signed char* mvl1, const unsigned char* hr, int S, int T, int H, int W, int Hu,
+                        const int* plan, int B, int crop, float* x, float* pms_out, float* rms_out, float* ufs_out, float* mvs,
+                        float* hr_out, void* stream);
 int cdfo_charbonnier(const float* sr, const float* hr, long long n, float eps, float* grad, double* partial, int partial_cap,
                      float* loss, void* stream);
 

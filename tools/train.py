@@ -1,8 +1,11 @@
-"""Train CVSR_V8 on a clip set resident on the device (cdfo_amd.train.fit; the loop of train_LD_37.py:359-402):
+"""Train CVSR_V8 on a clip set resident on the device (cdfo_amd.train.fit; the loop of train_LD_37.py:359-402 and train_RA_37.py):
 
-    python tools/train.py --seq LR_DIR SIDE_DIR HR_DIR [--seq ...] --out DIR [--epochs 30000] [--batch-size 20] [--crop 64]
+    python tools/train.py --seq LR_DIR SIDE_DIR HR_DIR [--seq ...] --out DIR [--coding LD] [--epochs 30000] [--batch-size 20] [--crop 64]
                           [--lr 1e-4] [--weight-decay 1e-5] [--val-itv 200] [--val LR_DIR SIDE_DIR GT_DIR] [--weights FILE.pth]
     python tools/train.py --synthetic S T H W --out DIR ...
+
+--coding RA trains the random-access configuration: the clip set keeps both motion lists (the mvl1 files beside mvl0) and the flow field
+is built from both (opt/data_RA_bi.py); --batch-size and --val-itv then default to 24 and 400 as in train_RA_37.py.
 
 --seq names one training sequence in the layout of cdfo_amd/priors.py (every frame with its own prior files, 00000 included) and a
 directory of 8-bit grey HR frames %05d.png.  --synthetic trains on S random sequences of T frames of H x W instead
@@ -20,17 +23,22 @@ def main():
     ap.add_argument("--synthetic", type=int, nargs=4, metavar=("S", "T", "H", "W"))
     ap.add_argument("--out", required=True)
     ap.add_argument("--epochs", type=int, default=30000)
-    ap.add_argument("--batch-size", type=int, default=20)
+    ap.add_argument("--coding", choices=("LD", "RA"), default="LD")
+    ap.add_argument("--batch-size", type=int, help="default: 20 (LD), 24 (RA)")
     ap.add_argument("--crop", type=int, default=64)
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--weight-decay", type=float, default=1e-5)
-    ap.add_argument("--val-itv", type=int, default=200)
+    ap.add_argument("--val-itv", type=int, help="default: 200 (LD), 400 (RA)")
     ap.add_argument("--val", nargs=3, metavar=("LR_DIR", "SIDE_DIR", "GT_DIR"))
     ap.add_argument("--weights")
     ap.add_argument("--seed", type=int, default=4)
     a = ap.parse_args()
     if (a.seq is None) == (a.synthetic is None):
         ap.error("--seq LR_DIR SIDE_DIR HR_DIR (once per sequence), or --synthetic S T H W")
+    if a.batch_size is None:
+        a.batch_size = 24 if a.coding == "RA" else 20
+    if a.val_itv is None:
+        a.val_itv = 400 if a.coding == "RA" else 200
     import torch
     from arch.SIDECVSR_our import CVSR_V8
     from cdfo_amd.train import fit
@@ -40,8 +48,14 @@ def main():
     if a.weights:
         model.load_state_dict(torch.load(a.weights, map_location="cpu"))
     model = model.cuda()
-    clips = ClipSet.from_arrays(*synthetic_arrays(*a.synthetic, seed=a.seed)) if a.synthetic else ClipSet.from_directories(a.seq)
-    print(f"{len(clips)} sequences of {clips.T} frames of {clips.H}x{clips.W} on the device")
+    if a.synthetic:
+        six, mvl1 = synthetic_arrays(*a.synthetic, seed=a.seed, coding=a.coding), None
+        if a.coding == "RA":
+            *six, mvl1 = six
+        clips = ClipSet.from_arrays(*six, mvl1=mvl1, coding=a.coding)
+    else:
+        clips = ClipSet.from_directories(a.seq, coding=a.coding)
+    print(f"{clips.coding}: {len(clips)} sequences of {clips.T} frames of {clips.H}x{clips.W} on the device")
     fit(model, clips, a.epochs, a.out, batch_size=a.batch_size, crop=a.crop, lr=a.lr, weight_decay=a.weight_decay, val_itv=a.val_itv,
         val=a.val, seed=a.seed)
 
