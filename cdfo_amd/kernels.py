@@ -597,6 +597,41 @@ def gather_frames(src: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tens
     return out
 
 
+def live_planes(lr: torch.Tensor, ufs: torch.Tensor, pms: torch.Tensor, rms: torch.Tensor, table: torch.Tensor, K: int, E: int,
+                Hp: int, Wp: int, peak: int, want_r: bool = True, want_r_new: bool = True):
+    """Every plane a chunk reads from the sample rings of live inference, in one launch (cdfo_live_planes).  lr, ufs: rings
+    [cap,H,W] uint8 (peak <= 255) or uint16; pms: [cap,H,W] uint8; rms: [cap,H,W] fp32; table: device int32 [14K + 2E] of ring slots
+    (win_frame[K,7], win_prior[K,7], new_frame[E], new_prior[E]).  Returns (x, r, u, lr_new, p_new, r_new): x, r, u [K,7,Hp,Wp],
+    the others [E,Hp,Wp], fp32 = sample / peak (pms / 255) zero padded; r / r_new are None when not wanted."""
+    cap, H, W = (int(v) for v in lr.shape) if lr.dim() == 3 else (0, 0, 0)
+    sample = torch.uint8 if peak <= 255 else torch.uint16
+    for name, t, dt in (("lr", lr, sample), ("ufs", ufs, sample), ("pms", pms, torch.uint8), ("rms", rms, torch.float32)):
+        if not t.is_cuda or t.device != lr.device or t.dtype != dt or tuple(t.shape) != (cap, H, W) or not t.is_contiguous():
+            raise ValueError(f"live_planes: {name} must be a dense device ring [cap,H,W] of {dt}, got {t.dtype} {tuple(t.shape)}")
+    if table.dtype != torch.int32 or table.device != lr.device or table.dim() != 1 or not table.is_contiguous() \
+            or table.numel() != 14 * K + 2 * E:
+        raise ValueError(f"live_planes: table must be a dense device int32 vector of 14 K + 2 E = {14 * K + 2 * E} slots")
+    new = lambda n, want=True: torch.empty((n, Hp, Wp), dtype=torch.float32, device=lr.device) if want else None
+    x, r, u = new(7 * K), new(7 * K, want_r), new(7 * K)
+    lr_new, p_new, r_new = new(E), new(E), new(E, want_r_new)
+    check(_lib.lib().cdfo_live_planes(_vp(lr), _vp(ufs), _vp(pms), _vp(rms), lr.element_size(), cap, H, W, _vp(table), K, E, Hp, Wp,
+                                      int(peak), _vp(x), _vp(r), _vp(u), _vp(lr_new), _vp(p_new), _vp(r_new), _stream()),
+          "cdfo_live_planes")
+    win = lambda t: None if t is None else t.view(K, 7, Hp, Wp)
+    return win(x), win(r), win(u), lr_new, p_new, r_new
+
+
+def seq_flows_ring(ring: torch.Tensor, i0: int, K: int, T_known: int, Hp: int, Wp: int) -> torch.Tensor:
+    """`seq_flows` reading the fp32 ring [cap,H,W,3] of live inference (entry e in slot e mod cap) for centres i0 .. i0+K-1.
+    T_known: the sequence's length, or 0 while the stream is open (no end rule applies, T > 1).  -> [K,7,2,Hp,Wp] fp32."""
+    if not ring.is_cuda or ring.dim() != 4 or ring.shape[3] != 3 or ring.dtype != torch.float32 or not ring.is_contiguous():
+        raise ValueError(f"seq_flows_ring: a dense fp32 device ring [cap,H,W,3] expected, got {ring.dtype} {tuple(ring.shape)}")
+    cap, H, W, _ = ring.shape
+    out = torch.empty((K, 7, 2, Hp, Wp), dtype=torch.float32, device=ring.device)
+    check(_lib.lib().cdfo_seq_flows_ring(_vp(ring), cap, H, W, i0, K, T_known, Hp, Wp, _vp(out), _stream()), "cdfo_seq_flows_ring")
+    return out
+
+
 QUANT_MODES = {"trunc": 0, "nearest": 1}        # CDFO_QUANT_* of include/cdfo_hip.h
 
 

@@ -78,17 +78,19 @@ class ChunkPlan(NamedTuple):
     compensate_priors: List[int]          # per compensated frame: the entry its rms plane is read from (max(1, .); 0 if T == 1)
 
 
-def plan_chunks(T: int, chunk: int) -> Iterator[ChunkPlan]:
+def plan_chunks(T: int, chunk: int, first: int = 0, extracted: int = 0) -> Iterator[ChunkPlan]:
     """The schedule of `StreamingSR.run_chunked` for a sequence of T frames, `chunk` centre frames per forward (the last chunk
     may be shorter).  The features a window uses for frame t are always those of (lr[t], pms[max(1, t)]), whichever step or
     slot asks, so every frame is extracted once, by the first chunk whose windows reach it, and is kept until the last window
-    that contains it has run: at most chunk + 6 frames are resident."""
+    that contains it has run: at most chunk + 6 frames are resident.  `first`, `extracted`: resume the schedule at centre `first` (a
+    multiple of `chunk`) with frames 0 .. extracted-1 already scheduled by the chunks before it (`cdfo_amd.live.LivePlanner`)."""
     if T < 1 or chunk < 1:
         raise ValueError(f"plan_chunks: T >= 1 and chunk >= 1 expected, got T = {T}, chunk = {chunk}")
+    if first < 0 or first % chunk or extracted < 0:
+        raise ValueError(f"plan_chunks: first must be a non-negative multiple of chunk and extracted >= 0, got {first}, {extracted}")
     prior = (lambda t: max(1, t)) if T > 1 else (lambda t: 0)
     half = NFRAMES // 2
-    extracted = 0                                                  # frames 0 .. extracted-1 have been scheduled
-    for c0 in range(0, T, chunk):
+    for c0 in range(first, T, chunk):                              # frames 0 .. extracted-1 have been scheduled
         centres = list(range(c0, min(c0 + chunk, T)))
         windows = [[min(max(i + n - half, 0), T - 1) for n in range(NFRAMES)] for i in centres]
         reach = windows[-1][-1] + 1
@@ -137,6 +139,65 @@ def check_noise_format(share_compensation: bool, gumbel_uniform, frame_noise, T:
                          "[1,64,H,W]); the per-step gumbel_uniform= format does not convert")
     if share_compensation and frame_noise is not None and len(frame_noise) != T:
         raise ValueError(f"frame_noise must hold one tensor per frame (T = {T}), got {len(frame_noise)}")
+
+
+def store_frames(ring: torch.Tensor, first: int, frames: torch.Tensor) -> None:
+    """frames[j] -> the ring slot of frame first + j (`bank_slot`), at most two contiguous copies."""
+    for slot, off, n in bank_runs(first, int(frames.shape[0]), int(ring.shape[0])):
+        ring[slot:slot + n].copy_(frames[off:off + n])
+
+
+def compensate_frames(model, dev, fea, frames: List[int], rms_planes, key, frame_noise):
+    """compensate_features of `frames` (their features `fea`, their rms planes [F,Hp,Wp]) with each frame's own noise: its
+    injected tensor, or draw = frame index under the sequence's key."""
+    noise = None if frame_noise is None else [frame_noise[t] for t in frames]
+    if noise is None:
+        model.resolve_noise_key(dev, key)
+    return model.compensate_features(fea, rms_planes.unsqueeze(1), gumbel_uniform=noise, draws=frames)
+
+
+def chunk_forward(model, plan: ChunkPlan, bank, lf_idx, lr_new, p_new, x, r, u, m1, noise) -> torch.Tensor:
+    """The model calls of one chunk, whoever built its inputs (`StreamingSR` from the resident sequence, `cdfo_amd.live.LiveSR`
+    from its rings): the frames the chunk is the first to reach (lr_new, p_new [E,Hp,Wp]: their LR planes and the partition maps of
+    their prior entries) are extracted into the bank (frame t lives in slot t mod capacity; what it overwrites is below
+    `plan.oldest`), the window stack is gathered from the bank, one forward at batch len(plan.centres) on x, r, u [K,7,1,Hp,Wp] and
+    the flows m1.  Returns the padded output [len(plan.centres),1,4Hp,4Wp]."""
+    from . import kernels as K
+    k = len(plan.centres)
+    if plan.extract:
+        store_frames(bank, plan.extract[0], model.extract_features(lr_new.unsqueeze(1), p_new.unsqueeze(1)))
+    Lf = K.gather_frames(bank, lf_idx).view(NFRAMES, k, *bank.shape[1:])
+    # (the model reads mvs1 only, like the reference's forward: mvl0's flows are not built)
+    return model.forward_windows(Lf, x, None, m1, r, u, gumbel_uniform=noise)
+
+
+def chunk_forward_shared(model, plan: ChunkPlan, bank, comp_bank, comp_idx, centre_idx, lr_new, p_new, r_new, x, u, m1, compensate,
+                         rms_planes_of) -> torch.Tensor:
+    """The model calls of one chunk of the shared mode: the frames it is the first to reach are extracted AND compensated (r_new
+    [E,Hp,Wp]: the residual maps of their prior entries) into the two rings, same slot in both, then one forward at batch
+    len(plan.centres) whose alignment reads the compensation ring in place.  compensate(fea, frames, rms_planes) is
+    `compensate_frames` with the sequence's key and noise; rms_planes_of(entries) builds the residual planes of a list of prior
+    entries (a repeated chunk only)."""
+    from . import kernels as K
+    dev, cap = bank.device, int(bank.shape[0])
+    if plan.extract:
+        fea = model.extract_features(lr_new.unsqueeze(1), p_new.unsqueeze(1))
+        comp = compensate(fea, plan.compensate, r_new)
+        store_frames(bank, plan.extract[0], fea)
+        store_frames(comp_bank, plan.extract[0], comp)
+    Lc = K.gather_frames(bank, centre_idx)
+
+    def recompensate():
+        # a rejected chunk (rare; called in the bf16x3 mode): the frames its windows hold, from the feature ring, into a
+        # scratch stack -- the compensation ring keeps what later chunks will read in the sequence's own arithmetic
+        prior = {t: e for w, pw in zip(plan.windows, plan.priors) for t, e in zip(w, pw)}
+        need = sorted(prior)
+        at = lambda v: torch.tensor(v, dtype=torch.int32).to(dev)
+        fea2 = K.gather_frames(bank, at([bank_slot(t, cap) for t in need]))
+        comp2 = compensate(fea2, need, rms_planes_of([prior[t] for t in need]))
+        return comp2, at([need.index(w[n]) for n in NEIGHBOUR_SLOTS for w in plan.windows])
+
+    return model.forward_windows_shared(Lc, comp_bank, comp_idx, x, m1, u, recompensate=recompensate)
 
 
 class StreamingSR:
@@ -346,25 +407,21 @@ class StreamingSR:
         overwrites is below `plan.oldest`), gather the inputs of its windows, one forward at batch len(plan.centres).  Returns the
         padded output [len(plan.centres),1,4Hp,4Wp]."""
         from . import kernels as K
-        k, cap = len(plan.centres), int(bank.shape[0])
+        k = len(plan.centres)
         noise = None
         if self.noise is not None:      # per-step format: noise[i] = the six [1,64,H,W] draws of centre i
             noise = [torch.cat([self.noise[i][d] for i in plan.centres], 0) for d in range(NFRAMES - 1)]
         torch.cuda.synchronize(self.dev)
         t0 = time.perf_counter()
         with torch.no_grad(), torch.cuda.device(self.dev):
+            lr_new = p_new = None
             if plan.extract:
-                a, b = plan.extract[0], plan.extract[-1] + 1
-                fea = self.model.extract_features(self.lr[a:b].unsqueeze(1), K.gather_frames(self.pms, extract_prior_idx).unsqueeze(1))
-                for slot, off, n in bank_runs(a, b - a, cap):
-                    bank[slot:slot + n].copy_(fea[off:off + n])
+                lr_new, p_new = self.lr[plan.extract[0]:plan.extract[-1] + 1], K.gather_frames(self.pms, extract_prior_idx)
             shape = (k, NFRAMES, 1, self.Hp, self.Wp)
-            Lf = K.gather_frames(bank, lf_idx).view(NFRAMES, k, self.Hp, self.Wp, 64)
             x = K.gather_frames(self.lr, frame_idx).view(shape)
             r, u = K.gather_frames(self.rms, prior_idx).view(shape), K.gather_frames(self.ufs, prior_idx).view(shape)
-            # (the model reads mvs1 only, like the reference's forward: mvl0's flows are not built)
             m1 = K.seq_flows(self.mvl1, plan.centres[0], k, self.Hp, self.Wp)
-            out = self.model.forward_windows(Lf, x, None, m1, r, u, gumbel_uniform=noise)
+            out = chunk_forward(self.model, plan, bank, lf_idx, lr_new, p_new, x, r, u, m1, noise)
         torch.cuda.synchronize(self.dev)
         self.seconds += time.perf_counter() - t0
         return out
@@ -398,47 +455,27 @@ class StreamingSR:
             yield p.centres, self._chunk_step_shared(p, bank, comp_bank, key, idx[:6 * k], idx[6 * k:7 * k], idx[7 * k:14 * k],
                                                      idx[14 * k:21 * k], idx[21 * k:])
 
-    def _compensate(self, fea, frames: List[int], rms_planes, key):
-        """compensate_features of `frames` (their features `fea`, their rms planes [F,Hp,Wp]) with each frame's own noise: its
-        injected tensor, or draw = frame index under the sequence's key."""
-        noise = None if self.frame_noise is None else [self.frame_noise[t] for t in frames]
-        if noise is None:
-            self.model.resolve_noise_key(self.dev, key)
-        return self.model.compensate_features(fea, rms_planes.unsqueeze(1), gumbel_uniform=noise, draws=frames)
-
     def _chunk_step_shared(self, plan: ChunkPlan, bank, comp_bank, key, comp_idx, centre_idx, frame_idx, prior_idx,
                            new_prior_idx) -> torch.Tensor:
         """One chunk of the shared mode: the frames it is the first to reach are extracted AND compensated into the two rings (same
         slot in both), then one forward at batch len(plan.centres) whose alignment reads the compensation ring in place."""
         from . import kernels as K
-        k, cap = len(plan.centres), int(bank.shape[0])
+        k = len(plan.centres)
         torch.cuda.synchronize(self.dev)
         t0 = time.perf_counter()
         with torch.no_grad(), torch.cuda.device(self.dev):
+            lr_new = p_new = r_new = None
             if plan.extract:
-                a, b = plan.extract[0], plan.extract[-1] + 1
-                fea = self.model.extract_features(self.lr[a:b].unsqueeze(1), K.gather_frames(self.pms, new_prior_idx).unsqueeze(1))
-                comp = self._compensate(fea, plan.compensate, K.gather_frames(self.rms, new_prior_idx), key)
-                for slot, off, n in bank_runs(a, b - a, cap):
-                    bank[slot:slot + n].copy_(fea[off:off + n])
-                    comp_bank[slot:slot + n].copy_(comp[off:off + n])
+                lr_new = self.lr[plan.extract[0]:plan.extract[-1] + 1]
+                p_new, r_new = K.gather_frames(self.pms, new_prior_idx), K.gather_frames(self.rms, new_prior_idx)
             shape = (k, NFRAMES, 1, self.Hp, self.Wp)
-            Lc = K.gather_frames(bank, centre_idx)
             x = K.gather_frames(self.lr, frame_idx).view(shape)
             u = K.gather_frames(self.ufs, prior_idx).view(shape)
             m1 = K.seq_flows(self.mvl1, plan.centres[0], k, self.Hp, self.Wp)
-
-            def recompensate():
-                # a rejected chunk (rare; called in the bf16x3 mode): the frames its windows hold, from the feature ring, into a
-                # scratch stack -- the compensation ring keeps what later chunks will read in the sequence's own arithmetic
-                need = sorted({t for w in plan.windows for t in w})
-                at = lambda v: torch.tensor(v, dtype=torch.int32).to(self.dev)
-                prior = (lambda t: max(1, t)) if self.T > 1 else (lambda t: 0)
-                fea2 = K.gather_frames(bank, at([bank_slot(t, cap) for t in need]))
-                comp2 = self._compensate(fea2, need, K.gather_frames(self.rms, at([prior(t) for t in need])), key)
-                return comp2, at([need.index(w[n]) for n in NEIGHBOUR_SLOTS for w in plan.windows])
-
-            out = self.model.forward_windows_shared(Lc, comp_bank, comp_idx, x, m1, u, recompensate=recompensate)
+            out = chunk_forward_shared(
+                self.model, plan, bank, comp_bank, comp_idx, centre_idx, lr_new, p_new, r_new, x, u, m1,
+                lambda fea, frames, planes: compensate_frames(self.model, self.dev, fea, frames, planes, key, self.frame_noise),
+                lambda entries: K.gather_frames(self.rms, torch.tensor(entries, dtype=torch.int32).to(self.dev)))
         torch.cuda.synchronize(self.dev)
         self.seconds += time.perf_counter() - t0
         return out

@@ -570,6 +570,26 @@ int cdfo_gather_frames(const void* src, int n_src, const int* idx, int n_dst, lo
 int cdfo_flow_warp_frames(const float* bank, int ldi, int n_bank, const int* idx, const float* mv, long long mv_kstride, int slot0,
                           int G, int K, int H, int W, int C, float* out, int ldo, void* stream);
 
+/* ---- input building of live sequence inference (live.hip; cdfo_amd/live.py::LiveSR) ----
+ * Frames arrive one at a time into rings of cap frames (frame t in slot t mod cap) that keep the files' sample types.
+ * cdfo_live_planes:   every plane a chunk of K centre frames reads from the sample rings, in one launch.  Rings of cap dense frames
+ *                     [H][W]: lr and ufs of sample_bytes = 1 (peak <= 255) or 2 bytes per sample, pms of one byte, rms fp32.
+ *                     table: 14 K + 2 E ints in DEVICE memory, ring slots: win_frame[K][7], win_prior[K][7], new_frame[E],
+ *                     new_prior[E].  Outputs, dense fp32, zero padded from H x W to Hp x Wp (Wp % 4 == 0, 16-byte aligned):
+ *                     x [K][7] = lr[win_frame] / peak, r = rms[win_prior] / peak, u = ufs[win_prior] / peak, lr_new [E] =
+ *                     lr[new_frame] / peak, p_new [E] = pms[new_prior] / 255, r_new [E] = rms[new_prior] / peak.  r and r_new may
+ *                     each be null (not written); E may be 0 (then lr_new and p_new may be null too).  Every quotient is ONE
+ *                     correctly rounded fp32 division.  A slot outside [0, cap) gives a plane of zeros (cdfo_gather_frames'
+ *                     contract).  21 K + 3 E <= 65535; offsets inside a frame and a plane are 32-bit (else CDFO_EINVAL).
+ * cdfo_seq_flows_ring: cdfo_seq_flows reading a ring [cap][H][W][3] of fp32 motion fields.  T_known: the sequence's length once the
+ *                     stream has closed, else 0 = not known yet: no end rule of modify_mv_for_end_frames applies and T > 1.  Centre
+ *                     i reads entry e = (T_known == 1 ? 0 : max(1, i)) from slot e mod cap.  out [K][7][2][Hp][Wp], bit-identical to
+ *                     cdfo_seq_flows on the whole field of T_known frames (for T_known = 0: of any length >= i0 + K + 3). */
+int cdfo_live_planes(const void* lr, const void* ufs, const unsigned char* pms, const float* rms, int sample_bytes, int cap, int H, int W,
+                     const int* table, int K, int E, int Hp, int Wp, int peak, float* x, float* r, float* u, float* lr_new, float* p_new,
+                     float* r_new, void* stream);
+int cdfo_seq_flows_ring(const float* ring, int cap, int H, int W, int i0, int K, int T_known, int Hp, int Wp, float* out, void* stream);
+
 /* ---- the output side of sequence evaluation (finish.hip; cdfo_amd/evaluate.py) ----
  * cdfo_finish_frames: K fp32 frames, read in place (frame k, row y at src + k*src_fstride + y*src_pitch, in elements; src 16-byte
  *                     aligned, pitch and stride multiples of 4), -> K 8-bit frames dst [K][Ho][Wo], packed (Wo % 4 == 0, dst 16-byte
