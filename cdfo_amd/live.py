@@ -11,19 +11,17 @@ at a time and does not know how long the stream is.  `LiveSR` is the same chunke
 * The inputs live in rings of chunk + 6 frames in the files' own sample types (frame t in slot t mod (chunk + 6), `bank_slot`);
   two launches build everything a chunk reads from them (libcdfo_hip.so: cdfo_live_planes, cdfo_seq_flows_ring), bit for bit what
   `StreamingSR` builds from the resident sequence.
-* The model calls are `streaming.chunk_forward` / `chunk_forward_shared`, the ones `run_chunked` makes, with the same shapes in the
+* The chunk step is `streaming.ChunkRunner.run`, the one `run_chunked` makes, with the same model calls on the same shapes in the
   same order: the frames are bit-identical to ``StreamingSR(...).run_chunked(chunk)`` on the completed sequence.
 """
 from __future__ import annotations
 
-import time
 from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
 
-from .streaming import (NFRAMES, ChunkPlan, bank_slot, check_noise_format, chunk_forward, chunk_forward_shared, comp_slot_table,
-                        compensate_frames, plan_chunks)
+from .streaming import NFRAMES, ChunkPlan, ChunkRunner, bank_slot, check_noise_format, check_peak, cropped, padded, plan_chunks
 
 
 class LivePlanner:
@@ -113,29 +111,26 @@ class LiveSR:
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise NotImplementedError("LiveSR needs the model on a GPU (HIP path, no CPU fallback)")
-        if isinstance(peak, bool) or not isinstance(peak, int) or not 1 <= peak <= 65535:
-            raise ValueError(f"peak must be an integer in 1 .. 65535, got {peak!r}")
+        self.peak = check_peak(peak)
         if min(int(height), int(width)) < 1:
             raise ValueError(f"LiveSR: a positive frame size expected, got {height} x {width}")
         self.shared = bool(share_compensation)
-        need = ("extract_features", "compensate_features", "forward_windows_shared") if self.shared else ("extract_features", "forward_windows")
-        if not all(hasattr(model, n) for n in need):
-            raise NotImplementedError(f"LiveSR needs a model with {' / '.join(need)} (CVSR_V8)")
-        self.model, self.dev, self.peak = model, dev, peak
+        self.model, self.dev = model, dev
         self.plan = LivePlanner(chunk)
         self.chunk, self.H, self.W = chunk, int(height), int(width)
-        self.Hp, self.Wp = (self.H + 7) // 8 * 8, (self.W + 7) // 8 * 8
+        self.Hp, self.Wp = padded(self.H, self.W)
         seq = lambda n: None if n is None else _Indexed(n) if callable(n) else n
         self.noise, self.frame_noise = seq(gumbel_uniform), seq(frame_noise)
         self._check_noise(None)
         self.sample = torch.uint8 if peak <= 255 else torch.uint16
         cap, H, W = chunk + NFRAMES - 1, self.H, self.W
+        # the feature bank, the compensation ring, the key and the counters of the stream; it waits for this stream only
+        self._runner = ChunkRunner(model, dev, self.Hp, self.Wp, cap, self.shared, self.noise, self.frame_noise,
+                                   lambda: torch.cuda.current_stream(dev).synchronize())
         new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
         # frame t lives in slot t mod cap of every ring
         self._rings = {"lr": new((cap, H, W), self.sample), "uf": new((cap, H, W), self.sample), "pm": new((cap, H, W), torch.uint8),
                        "rm": new((cap, H, W), torch.float32), "mv": new((cap, H, W, 3), torch.float32)}
-        self._bank = new((cap, self.Hp, self.Wp, 64), torch.float32)
-        self._comp_bank = torch.empty_like(self._bank) if self.shared else None
         self._copy = torch.cuda.Stream(dev)
         for t in self._rings.values():
             t.record_stream(self._copy)
@@ -144,10 +139,7 @@ class LiveSR:
         self._staged = 0                  # host frames staged so far: set _staged mod STAGING_SETS is rewritten next
         self._last_upload = None          # the event behind the newest upload on the copy stream (which runs in order)
         self._slot_read = [None] * cap    # per ring slot: the event behind the build kernels of the last chunk that read it
-        self._key = None
-        self.frames_out, self.seconds = 0, 0.0
-        self._extracted0 = int(model.frames_extracted)
-        self._compensated0 = int(getattr(model, "frames_compensated", 0))
+        self.frames_out = 0
 
     # -- what the object reports --------------------------------------------------------------------------------------------------
     @property
@@ -155,14 +147,18 @@ class LiveSR:
         return self.plan.pushed
 
     @property
+    def seconds(self) -> float:
+        return self._runner.count.seconds
+
+    @property
     def frames_extracted(self) -> int:
         """Frames sent through feature extraction since this object was made: the number pushed once `close` has returned."""
-        return self.model.frames_extracted - self._extracted0
+        return self._runner.count.frames_extracted
 
     @property
     def frames_compensated(self) -> int:
         """Frames sent through `compensate_features` (share_compensation only; a chunk the range guard repeats adds its windows')."""
-        return int(getattr(self.model, "frames_compensated", 0)) - self._compensated0
+        return self._runner.count.frames_compensated
 
     @property
     def ring_capacity(self) -> int:
@@ -171,8 +167,7 @@ class LiveSR:
     @property
     def resident_bytes(self) -> int:
         """The object's own persistent device buffers: the five input rings, the feature bank and the compensation ring."""
-        own = list(self._rings.values()) + [self._bank] + ([self._comp_bank] if self.shared else [])
-        return sum(t.numel() * t.element_size() for t in own)
+        return sum(t.numel() * t.element_size() for t in self._rings.values()) + self._runner.resident_bytes
 
     @property
     def fps(self) -> float:
@@ -242,46 +237,27 @@ class LiveSR:
         slot = lambda t: bank_slot(t, cap)
         live = [slot(t) for w in plan.windows for t in w] + [slot(e) for w in plan.priors for e in w] \
             + [slot(t) for t in plan.extract] + [slot(e) for e in plan.extract_priors]
-        if self.shared:       # the [6,K] ring slots of the neighbours and the ring slots of the centres
-            head = comp_slot_table(plan, cap) + [slot(i) for i in plan.centres]
-        else:                 # the bank slots of the window stack, slot-major
-            head = [slot(plan.windows[j][n]) for n in range(NFRAMES) for j in range(k)]
-        noise = None
-        if not self.shared and self.noise is not None:      # per-step format: noise[i] = the six [1,64,H,W] draws of centre i
-            per_centre = [self.noise[i] for i in plan.centres]
-            noise = [torch.cat([n[d] for n in per_centre], 0) for d in range(NFRAMES - 1)]
-        R = self._rings
-        cur = torch.cuda.current_stream(self.dev)
-        cur.synchronize()
-        t0 = time.perf_counter()
-        with torch.no_grad(), torch.cuda.device(self.dev):
+        head, R, head_t = self._runner.head(plan), self._rings, None
+
+        def build():          # the chunk's tables in one upload, then its inputs from the rings in two launches
+            nonlocal head_t
             tables = torch.tensor(head + live, dtype=torch.int32).to(self.dev)
-            head_t, live_t = tables[:len(head)], tables[len(head):]
+            head_t = tables[:len(head)]
+            cur = torch.cuda.current_stream(self.dev)
             if self._last_upload is not None:
                 cur.wait_event(self._last_upload)
-            x, r, u, lr_new, p_new, r_new = K.live_planes(R["lr"], R["uf"], R["pm"], R["rm"], live_t, k, E, self.Hp, self.Wp, self.peak,
-                                                          want_r=not self.shared, want_r_new=self.shared)
+            planes = K.live_planes(R["lr"], R["uf"], R["pm"], R["rm"], tables[len(head):], k, E, self.Hp, self.Wp, self.peak,
+                                   want_r=not self.shared, want_r_new=self.shared)
             m1 = K.seq_flows_ring(R["mv"], plan.centres[0], k, T_known, self.Hp, self.Wp)
             read = torch.cuda.Event()
             read.record(cur)
             for s in set(live):
                 self._slot_read[s] = read
-            shape = (k, NFRAMES, 1, self.Hp, self.Wp)
-            if not self.shared:
-                out = chunk_forward(self.model, plan, self._bank, head_t, lr_new, p_new, x.view(shape), r.view(shape), u.view(shape), m1,
-                                    noise)
-            else:
-                if self._key is None and self.frame_noise is None:
-                    self._key = self.model.resolve_noise_key(self.dev)       # one Philox key per stream, before its first extraction
-                out = chunk_forward_shared(
-                    self.model, plan, self._bank, self._comp_bank, head_t[:6 * k], head_t[6 * k:], lr_new, p_new, r_new, x.view(shape),
-                    u.view(shape), m1,
-                    lambda fea, frames, planes: compensate_frames(self.model, self.dev, fea, frames, planes, self._key, self.frame_noise),
-                    self._rms_planes)
-        cur.synchronize()
-        self.seconds += time.perf_counter() - t0
+            return (*planes, m1)
+
+        out = self._runner.run(plan, lambda: head_t, build, self._rms_planes)
         self.frames_out += k
-        return [(i, out[j:j + 1, :, :4 * self.H, :4 * self.W]) for j, i in enumerate(plan.centres)]
+        return list(zip(plan.centres, cropped(out, self.H, self.W)))
 
     def _rms_planes(self, entries: List[int]) -> torch.Tensor:
         """The residual planes [F,Hp,Wp] of a list of prior entries, from the ring (a chunk that the range guard repeats)."""

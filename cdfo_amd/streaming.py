@@ -200,6 +200,99 @@ def chunk_forward_shared(model, plan: ChunkPlan, bank, comp_bank, comp_idx, cent
     return model.forward_windows_shared(Lc, comp_bank, comp_idx, x, m1, u, recompensate=recompensate)
 
 
+def check_peak(peak) -> int:
+    if isinstance(peak, bool) or not isinstance(peak, int) or not 1 <= peak <= 65535:
+        raise ValueError(f"peak must be an integer in 1 .. 65535, got {peak!r}")
+    return peak
+
+
+def padded(H: int, W: int) -> Tuple[int, int]:
+    """H, W rounded up to multiples of 8 (window attention)."""
+    return (H + 7) // 8 * 8, (W + 7) // 8 * 8
+
+
+def cropped(out: torch.Tensor, H: int, W: int) -> List[torch.Tensor]:
+    """A chunk's padded output [K,1,4Hp,4Wp] as K frames [1,1,4H,4W]."""
+    return [out[j:j + 1, :, :4 * H, :4 * W] for j in range(int(out.shape[0]))]
+
+
+class PassCounters:
+    """Forward seconds, and what the model's counters of extracted / compensated frames have gained since this object was made."""
+
+    def __init__(self, model):
+        self.model, self.seconds = model, 0.0
+        self._extracted0, self._compensated0 = (int(getattr(model, n, 0)) for n in ("frames_extracted", "frames_compensated"))
+
+    @property
+    def frames_extracted(self) -> int:
+        return int(getattr(self.model, "frames_extracted", 0)) - self._extracted0
+
+    @property
+    def frames_compensated(self) -> int:
+        return int(getattr(self.model, "frames_compensated", 0)) - self._compensated0
+
+
+class ChunkRunner:
+    """One pass of the chunked forward (one `StreamingSR.iter_chunked` call, one `cdfo_amd.live.LiveSR` stream): all of a chunk step
+    that does not depend on where the chunk's inputs come from.  It owns the feature bank [capacity,Hp,Wp,64] and, in the shared
+    mode, the compensation ring beside it; a chunk's bank-side index table (`head`, `split_head`); the noise (`noise` per step,
+    `frame_noise` per frame; without it the shared mode takes ONE Philox key at the pass's first chunk and frame t draws with (key,
+    t) whichever chunk compensates it); the timed chunk step (`run`, between two calls of the owner's `sync`) and the counters (`count`)."""
+
+    def __init__(self, model, dev, Hp: int, Wp: int, capacity: int, shared: bool, noise, frame_noise, sync):
+        need = ("extract_features", "compensate_features", "forward_windows_shared") if shared else ("extract_features", "forward_windows")
+        if not all(hasattr(model, n) for n in need):
+            raise NotImplementedError(f"chunked inference needs a model with {' / '.join(need)} (CVSR_V8)")
+        self.model, self.count = model, PassCounters(model)
+        self.dev, self.Hp, self.Wp, self.shared, self.sync = dev, Hp, Wp, shared, sync
+        self.noise, self.frame_noise, self.key = noise, frame_noise, None
+        self.bank = torch.empty((capacity, Hp, Wp, 64), dtype=torch.float32, device=dev)
+        self.comp_bank = torch.empty_like(self.bank) if shared else None
+
+    @property
+    def resident_bytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.bank, self.comp_bank) if t is not None)
+
+    def head(self, plan: ChunkPlan) -> List[int]:
+        """The bank-side table of one chunk, 7 K entries.  Unshared: the bank slots of its window stack, slot-major.  Shared: the
+        [6,K] ring slots of its neighbours (`comp_slot_table`), then the ring slots of its centres."""
+        cap = int(self.bank.shape[0])
+        if self.shared:
+            return comp_slot_table(plan, cap) + [bank_slot(i, cap) for i in plan.centres]
+        return [bank_slot(w[n], cap) for n in range(NFRAMES) for w in plan.windows]
+
+    def split_head(self, head_t, k: int):
+        """`head(plan)` on the device -> (comp_idx [6,K] flat, centre_idx) in the shared mode, (lf_idx,) in the unshared one."""
+        return (head_t[:6 * k], head_t[6 * k:]) if self.shared else (head_t,)
+
+    def run(self, plan: ChunkPlan, head_t, build, rms_planes_of) -> torch.Tensor:
+        """One chunk, timed into `seconds`: build() -> (x, r, u, lr_new, p_new, r_new, m1), the owner's inputs (x, r, u [7K,Hp,Wp]
+        centre-major; None where the mode reads none), then `chunk_forward` / `chunk_forward_shared`, whose output it returns.
+        head_t: `head(plan)` on the device, or a callable that returns it once build() has run (an owner that uploads per chunk)."""
+        k = len(plan.centres)
+        noise = None
+        if not self.shared and self.noise is not None:      # per-step format: noise[i] = the six [1,64,H,W] draws of centre i
+            per_centre = [self.noise[i] for i in plan.centres]
+            noise = [torch.cat([n[d] for n in per_centre], 0) for d in range(NFRAMES - 1)]
+        self.sync()
+        t0 = time.perf_counter()
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            x, r, u, lr_new, p_new, r_new, m1 = build()
+            idx = self.split_head(head_t() if callable(head_t) else head_t, k)
+            x, r, u = (None if t is None else t.view(k, NFRAMES, 1, self.Hp, self.Wp) for t in (x, r, u))
+            if not self.shared:
+                out = chunk_forward(self.model, plan, self.bank, *idx, lr_new, p_new, x, r, u, m1, noise)
+            else:
+                if self.key is None and self.frame_noise is None:
+                    self.key = self.model.resolve_noise_key(self.dev)       # one Philox key per pass, before its first extraction
+                compensate = lambda fea, frames, rm: compensate_frames(self.model, self.dev, fea, frames, rm, self.key, self.frame_noise)
+                out = chunk_forward_shared(self.model, plan, self.bank, self.comp_bank, *idx, lr_new, p_new, r_new, x, u, m1, compensate,
+                                           rms_planes_of)
+        self.sync()
+        self.count.seconds += time.perf_counter() - t0
+        return out
+
+
 class StreamingSR:
     """One sequence, device resident.
 
@@ -229,11 +322,8 @@ class StreamingSR:
         as_dev = lambda t: torch.as_tensor(t).to(dev)
         lr = as_dev(lr)
         self.T, self.H, self.W = int(lr.shape[0]), int(lr.shape[1]), int(lr.shape[2])
-        self.Hp, self.Wp = (self.H + 7) // 8 * 8, (self.W + 7) // 8 * 8
-
-        if isinstance(peak, bool) or not isinstance(peak, int) or not 1 <= peak <= 65535:
-            raise ValueError(f"peak must be an integer in 1 .. 65535, got {peak!r}")
-        self.peak = peak
+        self.Hp, self.Wp = padded(self.H, self.W)
+        self.peak = check_peak(peak)
         # the divisors are device tensors: with a host scalar torch's device kernel multiplies by the rounded reciprocal, which is
         # not the correctly rounded quotient the reference's CPU `/ 255.0` (test_LD_37.py:27) and the oracle loop give
         mask_peak, sample_peak = (torch.tensor(p, dtype=torch.float32, device=dev) for p in (255.0, float(peak)))
@@ -249,9 +339,7 @@ class StreamingSR:
         self.noise = gumbel_uniform
         self.frame_noise = frame_noise
         self.fea = None
-        self.seconds = 0.0
-        self._extracted0 = int(getattr(model, "frames_extracted", 0))
-        self._compensated0 = int(getattr(model, "frames_compensated", 0))
+        self._pass = PassCounters(model)     # seconds and the frame counters: the current `ChunkRunner`'s once run_chunked has begun
         # use_graph: the cached-path forward (frames >= 1: identical shapes every step, ~700 kernel launches of a few
         # microseconds each at one clip) is captured once into a HIP graph and replayed from static buffers
         self.use_graph = use_graph
@@ -266,11 +354,7 @@ class StreamingSR:
         """Super-resolve frame i (frames must be visited in order: the feature cache slides by one frame per step)."""
         if (self.fea is None) != (i == 0):
             raise ValueError("StreamingSR.step: frames must be processed in order, starting at 0")
-        o = generate_input_index(i, NFRAMES, self.T - 1).to(self.dev)
-        po = o.clamp_min(1) if self.T > 1 else o                 # priors of frame 0 come from entry 1 (:36,53,66)
-        win = lambda t, idx: t.index_select(0, idx)[None, :, None]            # [1,7,1,H,W]
-        x, p, r, u = win(self.lr, o), win(self.pms, po), win(self.rms, po), win(self.ufs, po)
-        m0, m1 = self._mvs(self.mvl0, i), self._mvs(self.mvl1, i)
+        x, m0, m1, p, r, u = self._inputs(i)
         noise = None if self.noise is None else self.noise[i]
         if self.use_graph and i >= 1:
             return self._graph_step(x, m0, m1, p, r, u, noise)
@@ -279,7 +363,7 @@ class StreamingSR:
         with torch.no_grad():
             out, self.fea = self.model(x, m0, m1, p, r, u, self.fea, gumbel_uniform=noise)
         torch.cuda.synchronize(self.dev)
-        self.seconds += time.perf_counter() - t0
+        self._pass.seconds += time.perf_counter() - t0
         return out[..., :4 * self.H, :4 * self.W]
 
     def _graph_step(self, x, m0, m1, p, r, u, noise):
@@ -293,16 +377,16 @@ class StreamingSR:
         t0 = time.perf_counter()
         out, new_fea = self._graph(x, m0, m1, p, r, u, fea, noise)
         torch.cuda.synchronize(self.dev)
-        self.seconds += time.perf_counter() - t0
+        self._pass.seconds += time.perf_counter() - t0
         self.fea = new_fea.clone()                                   # the graph's output buffers are overwritten next step
         return out[..., :4 * self.H, :4 * self.W].clone()
 
     def _inputs(self, i: int):
         o = generate_input_index(i, NFRAMES, self.T - 1).to(self.dev)
-        po = o.clamp_min(1) if self.T > 1 else o
+        po = o.clamp_min(1) if self.T > 1 else o                 # priors of frame 0 come from entry 1 (:36,53,66)
         win = lambda t, idx: t.index_select(0, idx)[None, :, None]            # [1,7,1,H,W]
-        return (win(self.lr, o), self._mvs(self.mvl0, i), self._mvs(self.mvl1, i), win(self.pms, po), win(self.rms, po),
-                win(self.ufs, po))
+        x, p, r, u = win(self.lr, o), win(self.pms, po), win(self.rms, po), win(self.ufs, po)
+        return x, self._mvs(self.mvl0, i), self._mvs(self.mvl1, i), p, r, u
 
     def run_pipelined(self) -> List[torch.Tensor]:
         """All frames in order, software-pipelined over two streams: frame i + 1's front half (the new frame's feature
@@ -336,14 +420,14 @@ class StreamingSR:
                     out = self.model.forward_back(state)
                     outs.append(out[..., :4 * self.H, :4 * self.W])
         torch.cuda.synchronize(self.dev)
-        self.seconds = time.perf_counter() - t0
+        self._pass.seconds = time.perf_counter() - t0
         self.fea = fea
         cur.wait_stream(back)
         return outs
 
     def run(self) -> List[torch.Tensor]:
         """All frames in order; ``self.fps`` afterwards = frames / summed forward time (test_LD_22_FPS.py:192)."""
-        self.fea, self.seconds = None, 0.0
+        self.fea, self._pass.seconds = None, 0.0
         return [self.step(i) for i in range(self.T)]
 
     # -- chunked inference: `chunk` consecutive centre frames per forward against a per-frame feature bank ------------------------
@@ -369,7 +453,7 @@ class StreamingSR:
         in bf16x3 with the compensation of its frames recomputed (same noise) into a scratch stack; the ring is not rewritten."""
         outs = []
         for centres, out in self.iter_chunked(chunk, share_compensation):
-            outs.extend(out[j:j + 1, :, :4 * self.H, :4 * self.W] for j in range(len(centres)))
+            outs.extend(cropped(out, self.H, self.W))
         return outs
 
     def iter_chunked(self, chunk: int = 8, share_compensation: bool = False) -> Iterator[Tuple[List[int], torch.Tensor]]:
@@ -378,114 +462,52 @@ class StreamingSR:
         before it asks for the next one (cdfo_amd.evaluate) never holds more than one chunk of fp32 frames.  The schedule, the
         counters and ``self.seconds`` are those of `run_chunked`, which is a list-builder over this generator."""
         check_noise_format(bool(share_compensation), self.noise, self.frame_noise, getattr(self, "T", 0))
-        if share_compensation:
-            yield from self._iter_chunked_shared(int(chunk))
-            return
-        if not hasattr(self.model, "forward_windows"):
-            raise NotImplementedError("run_chunked needs a model with extract_features / forward_windows (CVSR_V8)")
-        plans = list(plan_chunks(self.T, int(chunk)))
-        self.fea, self.seconds = None, 0.0
-        self._extracted0 = self.model.frames_extracted
-        cap = bank_capacity(self.T, int(chunk))
-        bank = torch.empty((cap, self.Hp, self.Wp, 64), dtype=torch.float32, device=self.dev)
-        # every index table of the sequence in one upload: per chunk the bank slots of its window stack (slot-major), the
-        # frames and the prior entries of its windows (centre-major) and the prior entries of the frames it extracts
+        chunk, shared = int(chunk), bool(share_compensation)
+        plans = list(plan_chunks(self.T, chunk))
+        runner = ChunkRunner(self.model, self.dev, self.Hp, self.Wp, bank_capacity(self.T, chunk), shared, self.noise, self.frame_noise,
+                             lambda: torch.cuda.synchronize(self.dev))
+        self.fea, self._pass = None, runner.count        # (not the runner: its rings live as long as this generator, no longer)
+        # every index table of the sequence in one upload: per chunk the runner's bank-side table, the frames and the prior entries
+        # of its windows (centre-major) and the prior entries of the frames it extracts
         flat = []
         for p in plans:
-            flat += [bank_slot(p.windows[k][n], cap) for n in range(NFRAMES) for k in range(len(p.centres))]
-            flat += [t for w in p.windows for t in w] + [t for w in p.priors for t in w] + p.extract_priors
+            flat += runner.head(p) + [t for w in p.windows for t in w] + [t for w in p.priors for t in w] + p.extract_priors
         tables = torch.tensor(flat, dtype=torch.int32).to(self.dev)
+        from . import kernels as K
+        rms_of = lambda entries: K.gather_frames(self.rms, torch.tensor(entries, dtype=torch.int32).to(self.dev))    # a repeated chunk
         at = 0
         for p in plans:
             n7 = NFRAMES * len(p.centres)
             idx = tables[at:at + 3 * n7 + len(p.extract)]
             at += 3 * n7 + len(p.extract)
-            yield p.centres, self._chunk_step(p, bank, idx[:n7], idx[n7:2 * n7], idx[2 * n7:3 * n7], idx[3 * n7:])
+            build = lambda: self._chunk_inputs(p, shared, idx[n7:2 * n7], idx[2 * n7:3 * n7], idx[3 * n7:])
+            yield p.centres, runner.run(p, idx[:n7], build, rms_of)
 
-    def _chunk_step(self, plan: ChunkPlan, bank, lf_idx, frame_idx, prior_idx, extract_prior_idx) -> torch.Tensor:
-        """One chunk: extract the frames it is the first to reach into the bank (frame t lives in slot t mod capacity; what it
-        overwrites is below `plan.oldest`), gather the inputs of its windows, one forward at batch len(plan.centres).  Returns the
-        padded output [len(plan.centres),1,4Hp,4Wp]."""
+    def _chunk_inputs(self, plan: ChunkPlan, shared: bool, frame_idx, prior_idx, new_prior_idx):
+        """`ChunkRunner.run`'s build() from the resident planes (cdfo_gather_frames, cdfo_seq_flows): the LR, residual and unfiltered
+        planes of its windows, the planes of the frames it is the first to reach, its flows; residual map per new frame if `shared`."""
         from . import kernels as K
-        k = len(plan.centres)
-        noise = None
-        if self.noise is not None:      # per-step format: noise[i] = the six [1,64,H,W] draws of centre i
-            noise = [torch.cat([self.noise[i][d] for i in plan.centres], 0) for d in range(NFRAMES - 1)]
-        torch.cuda.synchronize(self.dev)
-        t0 = time.perf_counter()
-        with torch.no_grad(), torch.cuda.device(self.dev):
-            lr_new = p_new = None
-            if plan.extract:
-                lr_new, p_new = self.lr[plan.extract[0]:plan.extract[-1] + 1], K.gather_frames(self.pms, extract_prior_idx)
-            shape = (k, NFRAMES, 1, self.Hp, self.Wp)
-            x = K.gather_frames(self.lr, frame_idx).view(shape)
-            r, u = K.gather_frames(self.rms, prior_idx).view(shape), K.gather_frames(self.ufs, prior_idx).view(shape)
-            m1 = K.seq_flows(self.mvl1, plan.centres[0], k, self.Hp, self.Wp)
-            out = chunk_forward(self.model, plan, bank, lf_idx, lr_new, p_new, x, r, u, m1, noise)
-        torch.cuda.synchronize(self.dev)
-        self.seconds += time.perf_counter() - t0
-        return out
+        lr_new = p_new = r_new = None
+        if plan.extract:
+            lr_new, p_new = self.lr[plan.extract[0]:plan.extract[-1] + 1], K.gather_frames(self.pms, new_prior_idx)
+            r_new = K.gather_frames(self.rms, new_prior_idx) if shared else None
+        x = K.gather_frames(self.lr, frame_idx)
+        r = None if shared else K.gather_frames(self.rms, prior_idx)
+        u = K.gather_frames(self.ufs, prior_idx)
+        m1 = K.seq_flows(self.mvl1, plan.centres[0], len(plan.centres), self.Hp, self.Wp)
+        return x, r, u, lr_new, p_new, r_new, m1
 
-    # -- the same with each neighbour frame's compensation computed once (share_compensation=True) --------------------------------
-    def _iter_chunked_shared(self, chunk: int) -> Iterator[Tuple[List[int], torch.Tensor]]:
-        if not hasattr(self.model, "forward_windows_shared"):
-            raise NotImplementedError("run_chunked(share_compensation=True) needs a model with compensate_features / "
-                                      "forward_windows_shared (CVSR_V8)")
-        plans = list(plan_chunks(self.T, chunk))
-        self.fea, self.seconds = None, 0.0
-        self._extracted0, self._compensated0 = self.model.frames_extracted, self.model.frames_compensated
-        cap = bank_capacity(self.T, chunk)
-        bank = torch.empty((cap, self.Hp, self.Wp, 64), dtype=torch.float32, device=self.dev)
-        comp_bank = torch.empty_like(bank)
-        # one Philox key per sequence; frame t draws with (key, t) whichever chunk compensates it
-        key = None if self.frame_noise is not None else self.model.resolve_noise_key(self.dev)
-        # every index table of the sequence in one upload: per chunk the [6,K] ring slots of its neighbours, the ring slots of its
-        # centres, the frames and the prior entries of its windows (centre-major) and the prior entries of the frames it extracts
-        flat = []
-        for p in plans:
-            flat += comp_slot_table(p, cap) + [bank_slot(i, cap) for i in p.centres]
-            flat += [t for w in p.windows for t in w] + [t for w in p.priors for t in w] + p.compensate_priors
-        tables = torch.tensor(flat, dtype=torch.int32).to(self.dev)
-        at = 0
-        for p in plans:
-            k = len(p.centres)
-            n = 21 * k + len(p.compensate)
-            idx = tables[at:at + n]
-            at += n
-            yield p.centres, self._chunk_step_shared(p, bank, comp_bank, key, idx[:6 * k], idx[6 * k:7 * k], idx[7 * k:14 * k],
-                                                     idx[14 * k:21 * k], idx[21 * k:])
-
-    def _chunk_step_shared(self, plan: ChunkPlan, bank, comp_bank, key, comp_idx, centre_idx, frame_idx, prior_idx,
-                           new_prior_idx) -> torch.Tensor:
-        """One chunk of the shared mode: the frames it is the first to reach are extracted AND compensated into the two rings (same
-        slot in both), then one forward at batch len(plan.centres) whose alignment reads the compensation ring in place."""
-        from . import kernels as K
-        k = len(plan.centres)
-        torch.cuda.synchronize(self.dev)
-        t0 = time.perf_counter()
-        with torch.no_grad(), torch.cuda.device(self.dev):
-            lr_new = p_new = r_new = None
-            if plan.extract:
-                lr_new = self.lr[plan.extract[0]:plan.extract[-1] + 1]
-                p_new, r_new = K.gather_frames(self.pms, new_prior_idx), K.gather_frames(self.rms, new_prior_idx)
-            shape = (k, NFRAMES, 1, self.Hp, self.Wp)
-            x = K.gather_frames(self.lr, frame_idx).view(shape)
-            u = K.gather_frames(self.ufs, prior_idx).view(shape)
-            m1 = K.seq_flows(self.mvl1, plan.centres[0], k, self.Hp, self.Wp)
-            out = chunk_forward_shared(
-                self.model, plan, bank, comp_bank, comp_idx, centre_idx, lr_new, p_new, r_new, x, u, m1,
-                lambda fea, frames, planes: compensate_frames(self.model, self.dev, fea, frames, planes, key, self.frame_noise),
-                lambda entries: K.gather_frames(self.rms, torch.tensor(entries, dtype=torch.int32).to(self.dev)))
-        torch.cuda.synchronize(self.dev)
-        self.seconds += time.perf_counter() - t0
-        return out
+    @property
+    def seconds(self) -> float:
+        """Summed forward time of the current pass: `run()`, `run_pipelined()` and `run_chunked()` each start it from zero."""
+        return self._pass.seconds
 
     @property
     def frames_compensated(self) -> int:
-        """Frames the model has sent through `compensate_features` since this object was made or its last shared `run_chunked()`
+        """Frames the model has sent through `compensate_features` since this object was made or its last `run_chunked()`
         began: T for ``run_chunked(share_compensation=True)`` (a chunk that the range guard repeats adds the frames of its windows
         once more), 0 for every other mode."""
-        return self.model.frames_compensated - self._compensated0
+        return self._pass.frames_compensated
 
     @property
     def frames_extracted(self) -> int:
@@ -493,7 +515,7 @@ class StreamingSR:
         (one `run()`: 7 + (T - 1); `run_chunked()`: T).  It is the model's counter of eager extraction calls: exact for `run()`,
         `run_pipelined()` and `run_chunked()`; a forward that the fp16 range guard of `forward` repeats is counted twice (a repeated
         chunk is not: it reuses the bank), and replays of a HIP graph (`use_graph=True`) are not counted, only the capture is."""
-        return self.model.frames_extracted - self._extracted0
+        return self._pass.frames_extracted
 
     @property
     def fps(self) -> float:

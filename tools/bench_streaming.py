@@ -5,7 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from arch.SIDECVSR_our import CVSR_V8
-from cdfo_amd.streaming import StreamingSR
+from cdfo_amd.streaming import ChunkRunner, StreamingSR
 
 
 def _synthetic(T, H, W):
@@ -106,7 +106,7 @@ def _phases(model, s, chunk, share=False):
     chunk step (the rest = input building, the copy into the bank, the up-sampler), summed over one pass of the sequence.
     share: the shared-compensation mode -- compensation is a row of its own, "alignment + fusion" is what is left of the
     neighbour phase, and the indexed warp (one launch per neighbour group, timed on its side stream) is reported per chunk."""
-    marks = {}
+    marks, keep_run = {}, ChunkRunner.run             # the whole chunk step of either mode
 
     def wrap(name, fn):
         def f(*a, **kw):
@@ -124,12 +124,12 @@ def _phases(model, s, chunk, share=False):
         keep_warp = K.flow_warp_frames
         model.extract_features, model.compensate_features = wrap("feature extraction", model.extract_features), wrap("compensation", model.compensate_features)
         model._fuse_windows_shared, model._trunk = wrap("alignment + fusion", model._fuse_windows_shared), wrap("trunk", model._trunk)
-        s._chunk_step_shared, K.flow_warp_frames = wrap("whole chunk step", s._chunk_step_shared), wrap("flow_warp_frames", keep_warp)
+        ChunkRunner.run, K.flow_warp_frames = wrap("whole chunk step", keep_run), wrap("flow_warp_frames", keep_warp)
         try:
             s.run_chunked(chunk, share_compensation=True)
         finally:
-            del model.extract_features, model.compensate_features, model._fuse_windows_shared, model._trunk, s._chunk_step_shared
-            K.flow_warp_frames = keep_warp
+            del model.extract_features, model.compensate_features, model._fuse_windows_shared, model._trunk
+            ChunkRunner.run, K.flow_warp_frames = keep_run, keep_warp
         torch.cuda.synchronize()
         warp = marks.pop("flow_warp_frames")
         ms = {k: sum(a.elapsed_time(b) for a, b in v) for k, v in marks.items()}
@@ -140,13 +140,14 @@ def _phases(model, s, chunk, share=False):
               f"{sum(a.elapsed_time(b) for a, b in warp) / nchunks:.3f} ms per chunk ({len(warp) // nchunks} launches)", flush=True)
         return
     s.run_chunked(chunk)
-    keep = model.extract_features, model._fuse_windows, model._trunk, s._chunk_step
+    keep = model.extract_features, model._fuse_windows, model._trunk
     model.extract_features, model._fuse_windows = wrap("feature extraction", keep[0]), wrap("neighbour pipelines + fusion", keep[1])
-    model._trunk, s._chunk_step = wrap("trunk", keep[2]), wrap("whole chunk step", keep[3])
+    model._trunk, ChunkRunner.run = wrap("trunk", keep[2]), wrap("whole chunk step", keep_run)
     try:
         s.run_chunked(chunk)
     finally:
-        del model.extract_features, model._fuse_windows, model._trunk, s._chunk_step
+        del model.extract_features, model._fuse_windows, model._trunk
+        ChunkRunner.run = keep_run
     torch.cuda.synchronize()
     ms = {k: sum(a.elapsed_time(b) for a, b in v) for k, v in marks.items()}
     rest = ms["whole chunk step"] - sum(v for k, v in ms.items() if k != "whole chunk step")
