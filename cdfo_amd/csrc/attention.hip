@@ -183,13 +183,11 @@ __global__ __launch_bounds__(ST_THREADS) void rdab_prep_kernel_fused(rf_args a) 
   // ---- the weights (the same for every image) -> LDS, split bf16 hi | lo, rows permuted (as conv1x1_stream_kernel)
   for (int i = tid; i < 16 * NCB * 64; i += ST_THREADS) {
     const int rowpos = i % (NCB * 64), kg = i / (NCB * 64);
-    const int n = st_chan_of_row(rowpos);
+    const int n = mfma_row_channel(rowpos);
     const f32x4 wv = *reinterpret_cast<const f32x4*>(a.w + ((long long)kg * (NCB * 64) + n) * 4);
     const int c = kg >> 2, hh = (kg >> 1) & 1, j0 = (kg & 1) * 4;
     u32x2 hi, lo;
-    hi[0] = pack_bf16(wv[0], wv[1]); hi[1] = pack_bf16(wv[2], wv[3]);
-    lo[0] = pack_bf16(wv[0] - bf16_round(wv[0]), wv[1] - bf16_round(wv[1]));
-    lo[1] = pack_bf16(wv[2] - bf16_round(wv[2]), wv[3] - bf16_round(wv[3]));
+    split4_bf16(wv, hi, lo);
     const int off = ((c * 2 + hh) * (NCB * 64) + rowpos) * 16 + j0 * 2;
     *reinterpret_cast<u32x2*>(sWh + off) = hi;
     *reinterpret_cast<u32x2*>(sWl + off) = lo;
@@ -221,17 +219,12 @@ __global__ __launch_bounds__(ST_THREADS) void rdab_prep_kernel_fused(rf_args a) 
       const long long p0 = (img_t0 + it - (long long)b * a.tiles_per_image) * 128 + wave * 32;      // first pixel (inside image b)
       const long long rows_left = a.P - p0;                              // may be <= 0: everything out of range
       const float* base = a.x + ((long long)b * a.P + (rows_left > 0 ? p0 : 0)) * a.ldx;
-      const unsigned long long pb = reinterpret_cast<unsigned long long>(base);
-      i32x4 rsrc;
-      rsrc[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)pb);
-      rsrc[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(pb >> 32));
       const long long bytes = rows_left > 0 ? (rows_left < 32 ? rows_left : 32) * (long long)a.ldx * 4 : 0;
-      rsrc[2] = __builtin_amdgcn_readfirstlane((int)bytes);              // lanes beyond the image read zeros
-      rsrc[3] = 0x00020000;
+      const i32x4 rsrc = lds_dma_rsrc_uniform(base, (unsigned)bytes);      // lanes beyond the image read zeros
       unsigned voff[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) voff[q] = (unsigned)(d_px[q] * a.ldx * 4 + d_part[q] * 16);
-      st_dma8(voff, rsrc, __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(it % NS) * ST_STAGE));
+      lds_dma0(voff, rsrc, __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(it % NS) * ST_STAGE));
     };
     for (; issued < NS - 1 && issued < n_items; ++issued) issue(issued);
 
@@ -251,12 +244,7 @@ __global__ __launch_bounds__(ST_THREADS) void rdab_prep_kernel_fused(rf_args a) 
         const f32x4 v0 = *reinterpret_cast<const f32x4*>(st + part_off(c * 4 + h * 2));
         const f32x4 v1 = *reinterpret_cast<const f32x4*>(st + part_off(c * 4 + h * 2 + 1));
         union { unsigned u[4]; bf16x8_t v; } ph, pl;
-        ph.u[0] = pack_bf16(v0[0], v0[1]); ph.u[1] = pack_bf16(v0[2], v0[3]);
-        ph.u[2] = pack_bf16(v1[0], v1[1]); ph.u[3] = pack_bf16(v1[2], v1[3]);
-        pl.u[0] = pack_bf16(v0[0] - bf16_round(v0[0]), v0[1] - bf16_round(v0[1]));
-        pl.u[1] = pack_bf16(v0[2] - bf16_round(v0[2]), v0[3] - bf16_round(v0[3]));
-        pl.u[2] = pack_bf16(v1[0] - bf16_round(v1[0]), v1[1] - bf16_round(v1[1]));
-        pl.u[3] = pack_bf16(v1[2] - bf16_round(v1[2]), v1[3] - bf16_round(v1[3]));
+        split8_bf16(v0, v1, ph.u, pl.u);
         const int wrow = (c * 2 + h) * (NCB * 64) + r;
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb)
@@ -270,7 +258,7 @@ __global__ __launch_bounds__(ST_THREADS) void rdab_prep_kernel_fused(rf_args a) 
           }
       }
       // the next request overwrites the stage of item it - 1; this item's fragment reads have returned (the MFMAs consumed them)
-      if (issued < n_items) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); issue(issued); ++issued; }
+      if (issued < n_items) { wait_lgkm<0>(); issue(issued); ++issued; }
 
       const long long pin = (img_t0 + it - (long long)b * a.tiles_per_image) * 128 + wave * 32 + r;
       if (pin - r >= a.P) continue;                  // P % 32 == 0: a wave's 32 pixels lie inside the image or all beyond it

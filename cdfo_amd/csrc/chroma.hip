@@ -27,7 +27,6 @@ namespace {
 constexpr int CU_TW = 32, CU_TH = 16;                   // source pixels of one tile
 constexpr int CU_IW = CU_TW + 4, CU_IH = CU_TH + 4;     // with the halo: source q-2 .. q+2 feeds outputs 4q .. 4q+3
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // the four outputs 4q .. 4q+3 from the five sources q-2 .. q+2, scaled by 128
 __device__ __forceinline__ i32x4 up4_taps(int a, int b, int c, int d, int e) {

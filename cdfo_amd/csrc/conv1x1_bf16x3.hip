@@ -25,7 +25,6 @@ constexpr int EPI_RS = 68;                      // floats per pixel row in the e
 constexpr int EPI_BYTES = 4 * 32 * EPI_RS * 4;  // 34,816
 constexpr int MAXCB = 4;                        // up to 256 output channels
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ void split_store(unsigned char* dst_hi, int lo_delta, const f32x4 v) {
   u32x2 hi, lo;

@@ -89,10 +89,6 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
   const unsigned char* scale_slots = smem + ring_off + 4 * NS * ST_STAGE + wave * 512;
   const unsigned scale_lds = (unsigned)(unsigned long long)(smem) + ring_off + 4 * NS * ST_STAGE + wave * 512;
 
-  // MFMA row m of a 32-channel block holds channel (m>>4)*16 + ((m>>2)&1)*8 + ((m>>3)&1)*4 + (m&3) (see conv3x3_ws.hip):
-  // a lane's accumulator registers then are 8 consecutive channels of each 16-channel group
-  auto chan_of_row = [](int n) { const int m = n & 31; return (n & ~31) + ((m >> 4) & 1) * 16 + ((m >> 2) & 1) * 8 + ((m >> 3) & 1) * 4 + (m & 3); };
-
   // this workgroup's contiguous tile range
   const long long t_lo = a.tiles * blockIdx.x / gridDim.x, t_hi = a.tiles * (blockIdx.x + 1) / gridDim.x;
   if (t_lo >= t_hi) return;
@@ -113,9 +109,7 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
 
   // TAPS: A operand of the second product = w_last^T (row = tap, rows 9..31 zero), fp16 hi | lo, in registers for the whole launch:
   // lane (r = tap, h) holds channels 16 s4 + 8 h .. + 7
-  typedef _Float16 st_h8 __attribute__((ext_vector_type(8)));
-  typedef unsigned st_u4 __attribute__((ext_vector_type(4)));
-  st_h8 twh[TAPS ? 4 : 1], twl[TAPS ? 4 : 1];
+  f16x8_t twh[TAPS ? 4 : 1], twl[TAPS ? 4 : 1];
   if (TAPS) {
 #pragma unroll
     for (int s4 = 0; s4 < 4; ++s4)
@@ -138,14 +132,12 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
       const int ngrp = (a.Cin >> 2) * NCB * 64;                          // (group of 4 input channels, row position)
       for (int i = tid; i < ngrp; i += ST_THREADS) {
         const int rowpos = i % (NCB * 64), kg = i / (NCB * 64);
-        const int n = chan_of_row(rowpos);
+        const int n = mfma_row_channel(rowpos);
         f32x4 wv = {0.f, 0.f, 0.f, 0.f};
         if (n < a.CoutP) wv = *reinterpret_cast<const f32x4*>(wb + ((long long)kg * a.CoutP + n) * 4);
         const int c = kg >> 2, hh = (kg >> 1) & 1, j0 = (kg & 1) * 4;
         u32x2 hi, lo;
-        hi[0] = pack_bf16(wv[0], wv[1]); hi[1] = pack_bf16(wv[2], wv[3]);
-        lo[0] = pack_bf16(wv[0] - bf16_round(wv[0]), wv[1] - bf16_round(wv[1]));
-        lo[1] = pack_bf16(wv[2] - bf16_round(wv[2]), wv[3] - bf16_round(wv[3]));
+        split4_bf16(wv, hi, lo);
         const int off = ((c * 2 + hh) * (NCB * 64) + rowpos) * 16 + j0 * 2;
         *reinterpret_cast<u32x2*>(sWh + off) = hi;
         *reinterpret_cast<u32x2*>(sWl + off) = lo;
@@ -167,13 +159,9 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
         // operations retire in order, so the slot is valid once any item of this tile has landed (the hand-counted waits below,
         // which one more older piece only makes more conservative).
         const long long rows = a.P - p0;
-        const unsigned long long pb = reinterpret_cast<unsigned long long>(a.res_scale + (long long)b * a.P + (rows > 0 ? p0 : 0));
-        i32x4 rs;
-        rs[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)pb);
-        rs[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(pb >> 32));
-        rs[2] = __builtin_amdgcn_readfirstlane((int)(rows > 0 ? (rows < 32 ? rows : 32) * 4 : 0));      // beyond the image: zeros
-        rs[3] = 0x00020000;
-        st_dma1((unsigned)r * 4, rs, __builtin_amdgcn_readfirstlane(scale_lds + (unsigned)(tile & 1) * 256));
+        const i32x4 rs = lds_dma_rsrc_uniform(a.res_scale + (long long)b * a.P + (rows > 0 ? p0 : 0),
+                                              (unsigned)(rows > 0 ? (rows < 32 ? rows : 32) * 4 : 0));      // beyond the image: zeros
+        lds_dma0_dword((unsigned)r * 4, rs, __builtin_amdgcn_readfirstlane(scale_lds + (unsigned)(tile & 1) * 256));
       }
       st_item src;
       int chan0;
@@ -186,17 +174,13 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
       // descriptor based at the wave's first pixel: offsets stay small whatever the tensor's size
       const long long rows_left = a.P - p0;                               // may be <= 0: everything out of range
       const float* base = src.base + ((long long)b * a.P + (rows_left > 0 ? p0 : 0)) * src.ld + chan0;
-      const unsigned long long pb = reinterpret_cast<unsigned long long>(base);
-      i32x4 rsrc;
-      rsrc[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)pb);
-      rsrc[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(pb >> 32));
+      i32x4 rsrc = lds_dma_rsrc_uniform(base, 0u);
       const long long bytes = rows_left > 0 ? (rows_left < 32 ? rows_left : 32) * (long long)src.ld * 4 : 0;
-      rsrc[2] = __builtin_amdgcn_readfirstlane((int)bytes);               // lanes beyond the image read zeros
-      rsrc[3] = 0x00020000;
+      lds_dma_rsrc_resize_uniform(rsrc, (unsigned)bytes);                 // lanes beyond the image read zeros
       unsigned voff[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) voff[q] = (unsigned)(d_px[q] * src.ld * 4 + d_part[q] * 16);
-      st_dma8(voff, rsrc, __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(it % NS) * ST_STAGE));
+      lds_dma0(voff, rsrc, __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(it % NS) * ST_STAGE));
     };
     for (; issued < NS - 1 && issued < n_items; ++issued) issue(issued);
 
@@ -213,7 +197,7 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
       if (TAPS) {
         // two-stage ring (the 64 KB weight image leaves room for no more): the stage of item it - 1 was consumed in the previous
         // trip, so item it + 1 is requested NOW and lands behind this tile's products and tap epilogue
-        if (issued < n_items) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); issue(issued); ++issued; }
+        if (issued < n_items) { wait_lgkm<0>(); issue(issued); ++issued; }
       }
       if (k == 0) {
 #pragma unroll
@@ -230,12 +214,7 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
           const f32x4 v0 = *reinterpret_cast<const f32x4*>(st + part_off(c * 4 + h * 2));
           const f32x4 v1 = *reinterpret_cast<const f32x4*>(st + part_off(c * 4 + h * 2 + 1));
           union { unsigned u[4]; bf16x8_t v; } ph, pl;
-          ph.u[0] = pack_bf16(v0[0], v0[1]); ph.u[1] = pack_bf16(v0[2], v0[3]);
-          ph.u[2] = pack_bf16(v1[0], v1[1]); ph.u[3] = pack_bf16(v1[2], v1[3]);
-          pl.u[0] = pack_bf16(v0[0] - bf16_round(v0[0]), v0[1] - bf16_round(v0[1]));
-          pl.u[1] = pack_bf16(v0[2] - bf16_round(v0[2]), v0[3] - bf16_round(v0[3]));
-          pl.u[2] = pack_bf16(v1[0] - bf16_round(v1[0]), v1[1] - bf16_round(v1[1]));
-          pl.u[3] = pack_bf16(v1[2] - bf16_round(v1[2]), v1[3] - bf16_round(v1[3]));
+          split8_bf16(v0, v1, ph.u, pl.u);
           const int wrow = ((k * 4 + c) * 2 + h) * (NCB * 64) + r;
 #pragma unroll
           for (int cb = 0; cb < NCB; ++cb)
@@ -282,7 +261,7 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
       }
       // the stage may be overwritten once its reads have returned: the next DMA below targets the stage of item it-1... wait
       // for this item's own LDS reads too (they were consumed by the MFMAs / adds above, so they have returned)
-      if (!TAPS && issued < n_items) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); issue(issued); ++issued; }
+      if (!TAPS && issued < n_items) { wait_lgkm<0>(); issue(issued); ++issued; }
       if (k == items_per_tile - 1) {
         // ---- store: 32 contiguous bytes per lane and 16-channel group
         const long long tile = img_t0 + it / items_per_tile;
@@ -367,8 +346,8 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
 #pragma unroll
               for (int j = 0; j < 4; ++j)
                 split_pair_f16(acc[cb][s4 >> 1][8 * (s4 & 1) + 2 * j] * sc, acc[cb][s4 >> 1][8 * (s4 & 1) + 2 * j + 1] * sc, hh[j], ll[j]);
-              const st_u4 hu = {hh[0], hh[1], hh[2], hh[3]}, lu = {ll[0], ll[1], ll[2], ll[3]};
-              const st_h8 yh = __builtin_bit_cast(st_h8, hu), yl = __builtin_bit_cast(st_h8, lu);
+              const u32x4 hu = {hh[0], hh[1], hh[2], hh[3]}, lu = {ll[0], ll[1], ll[2], ll[3]};
+              const f16x8_t yh = __builtin_bit_cast(f16x8_t, hu), yl = __builtin_bit_cast(f16x8_t, lu);
               tacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(twl[s4], yh, tacc, 0, 0, 0);
               tacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(twh[s4], yl, tacc, 0, 0, 0);
               tacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(twh[s4], yh, tacc, 0, 0, 0);
@@ -474,7 +453,6 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
   float* sBias = reinterpret_cast<float*>(smem + 2 * w_half);
   unsigned char* ring = smem + ring_off + wave * NS * ST_STAGE;
   const unsigned ring_lds = (unsigned)(unsigned long long)(smem) + ring_off + wave * NS * ST_STAGE;
-  auto chan_of_row = [](int n) { const int m = n & 31; return (n & ~31) + ((m >> 4) & 1) * 16 + ((m >> 2) & 1) * 8 + ((m >> 3) & 1) * 4 + (m & 3); };
 
   const long long t_lo = a.tiles * blockIdx.x / gridDim.x, t_hi = a.tiles * (blockIdx.x + 1) / gridDim.x;
   if (t_lo >= t_hi) return;
@@ -492,13 +470,11 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
   // ---- the weights (the same for every image) -> LDS, split bf16 hi | lo, rows permuted
   for (int i = tid; i < (128 >> 2) * 64; i += ST_THREADS) {
     const int rowpos = i % 64, kg = i / 64;
-    const int n = chan_of_row(rowpos);
+    const int n = mfma_row_channel(rowpos);
     const f32x4 wv = *reinterpret_cast<const f32x4*>(a.w + ((long long)kg * 64 + n) * 4);
     const int c = kg >> 2, hh = (kg >> 1) & 1, j0 = (kg & 1) * 4;
     u32x2 hi, lo;
-    hi[0] = pack_bf16(wv[0], wv[1]); hi[1] = pack_bf16(wv[2], wv[3]);
-    lo[0] = pack_bf16(wv[0] - bf16_round(wv[0]), wv[1] - bf16_round(wv[1]));
-    lo[1] = pack_bf16(wv[2] - bf16_round(wv[2]), wv[3] - bf16_round(wv[3]));
+    split4_bf16(wv, hi, lo);
     const int off = ((c * 2 + hh) * 64 + rowpos) * 16 + j0 * 2;
     *reinterpret_cast<u32x2*>(sWh + off) = hi;
     *reinterpret_cast<u32x2*>(sWl + off) = lo;
@@ -522,17 +498,13 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
       const long long p0 = (tile - (long long)b * a.tiles_per_image) * 128 + wave * 32;
       const long long rows_left = a.P - p0;                               // may be <= 0: everything out of range
       const float* base = src.base + ((long long)b * a.P + (rows_left > 0 ? p0 : 0)) * src.ld + src.ch0;
-      const unsigned long long pb = reinterpret_cast<unsigned long long>(base);
-      i32x4 rsrc;
-      rsrc[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)pb);
-      rsrc[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(pb >> 32));
+      i32x4 rsrc = lds_dma_rsrc_uniform(base, 0u);
       const long long bytes = rows_left > 0 ? (rows_left < 32 ? rows_left : 32) * (long long)src.ld * 4 : 0;
-      rsrc[2] = __builtin_amdgcn_readfirstlane((int)bytes);               // lanes beyond the image read zeros
-      rsrc[3] = 0x00020000;
+      lds_dma_rsrc_resize_uniform(rsrc, (unsigned)bytes);                 // lanes beyond the image read zeros
       unsigned voff[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) voff[q] = (unsigned)(d_px[q] * src.ld * 4 + d_part[q] * 16);
-      st_dma8(voff, rsrc, __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(it % NS) * ST_STAGE));
+      lds_dma0(voff, rsrc, __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(it % NS) * ST_STAGE));
     };
     for (; issued < NS - 1 && issued < n_items; ++issued) issue(issued);
 
@@ -557,12 +529,7 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
           const f32x4 v0 = *reinterpret_cast<const f32x4*>(st + part_off(c * 4 + h * 2));
           const f32x4 v1 = *reinterpret_cast<const f32x4*>(st + part_off(c * 4 + h * 2 + 1));
           union { unsigned u[4]; bf16x8_t v; } ph, pl;
-          ph.u[0] = pack_bf16(v0[0], v0[1]); ph.u[1] = pack_bf16(v0[2], v0[3]);
-          ph.u[2] = pack_bf16(v1[0], v1[1]); ph.u[3] = pack_bf16(v1[2], v1[3]);
-          pl.u[0] = pack_bf16(v0[0] - bf16_round(v0[0]), v0[1] - bf16_round(v0[1]));
-          pl.u[1] = pack_bf16(v0[2] - bf16_round(v0[2]), v0[3] - bf16_round(v0[3]));
-          pl.u[2] = pack_bf16(v1[0] - bf16_round(v1[0]), v1[1] - bf16_round(v1[1]));
-          pl.u[3] = pack_bf16(v1[2] - bf16_round(v1[2]), v1[3] - bf16_round(v1[3]));
+          split8_bf16(v0, v1, ph.u, pl.u);
           const int wrow = ((k * 4 + c) * 2 + h) * 64 + r;
 #pragma unroll
           for (int ni = 0; ni < 2; ++ni) {
@@ -626,7 +593,7 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
         sk += tk;
       }
       // this item's (and the kf stage's) LDS reads have returned before the next request overwrites the stage of item it - 1
-      if (issued < n_items) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); issue(issued); ++issued; }
+      if (issued < n_items) { wait_lgkm<0>(); issue(issued); ++issued; }
     }
 
     // ---- leaving image b: the four waves' sums (each in stage 0 of its idle ring) -> this workgroup's slot, waves in index order

@@ -42,10 +42,6 @@ constexpr int W_HALF = 9 * 2 * 64 * 16;          // 18,432 B: [tap][h][64 cout][
 enum { M_BF16X3 = CDFO_PREC_BF16X3, M_BF16 = CDFO_PREC_BF16, M_FP16X2 = CDFO_PREC_FP16X2, M_FP16IN = CDFO_PREC_FP16,
        M_FP16X1 = CDFO_PREC_FP16X1 };
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 template <int MODE> struct Fmt;
 template <> struct Fmt<M_BF16X3> { using frag = bf16x8_t; static constexpr bool ALO = true, WLO = true; };

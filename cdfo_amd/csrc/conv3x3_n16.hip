@@ -14,7 +14,7 @@
 //     registers -- 144 VGPRs beside the 44 of the halo prefetch -- hipcc spills and the launch is 70 % slower: measured);
 //   * a wave owns one tile row = two 16-pixel MFMA columns; its accumulator registers are 4 consecutive output channels of one
 //     pixel: the epilogue (bias, activation) stores 16 bytes per lane, 1 KiB contiguous per wave-instruction.
-#include "common.h"
+#include "numeric.h"
 
 namespace {
 
@@ -27,9 +27,6 @@ constexpr int N16_LDS = N16_W_BYTES + N16_A_BYTES;     // 123,904
 constexpr int N16_ITEMS = N16_NPIX * 16;               // float4 items of a halo tile
 constexpr int N16_NL = (N16_ITEMS + N16_THREADS - 1) / N16_THREADS;                      // 11 loads per thread
 
-typedef __bf16 n16_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned n16_u32x2 __attribute__((ext_vector_type(2)));
-
 struct n16_args {
   const float* x; int ldx;
   int B, H, W;
@@ -39,12 +36,6 @@ struct n16_args {
   float* out; int ldo;
   int tiles_x, tiles_y, ntiles;
 };
-
-__device__ __forceinline__ unsigned n16_pack(float a, float b) {
-  const __bf16 ha = (__bf16)a, hb = (__bf16)b;
-  return (unsigned)__builtin_bit_cast(unsigned short, ha) | ((unsigned)__builtin_bit_cast(unsigned short, hb) << 16);
-}
-__device__ __forceinline__ float n16_round(float a) { return (float)(__bf16)a; }
 
 __global__ __launch_bounds__(N16_THREADS) void conv3x3_c64_n16_kernel(n16_args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -93,14 +84,12 @@ __global__ __launch_bounds__(N16_THREADS) void conv3x3_c64_n16_kernel(n16_args a
       const int item = tid + N16_THREADS * k, p = item >> 4, q = item & 15;
       if (item < N16_ITEMS) {
         const f32x4 v = (pre_ok >> k) & 1u ? pre[k] : f32x4{0.f, 0.f, 0.f, 0.f};
-        n16_u32x2 hi, lo;
-        hi[0] = n16_pack(v[0], v[1]); hi[1] = n16_pack(v[2], v[3]);
-        lo[0] = n16_pack(v[0] - n16_round(v[0]), v[1] - n16_round(v[1]));
-        lo[1] = n16_pack(v[2] - n16_round(v[2]), v[3] - n16_round(v[3]));
+        u32x2 hi, lo;
+        split4_bf16(v, hi, lo);
         const int chunk = q >> 1, sw = p & 15;
         unsigned char* rec = sA + p * 256 + (q & 1) * 8;
-        *reinterpret_cast<n16_u32x2*>(rec + ((chunk ^ sw) << 4)) = hi;
-        *reinterpret_cast<n16_u32x2*>(rec + (((8 + chunk) ^ sw) << 4)) = lo;
+        *reinterpret_cast<u32x2*>(rec + ((chunk ^ sw) << 4)) = hi;
+        *reinterpret_cast<u32x2*>(rec + (((8 + chunk) ^ sw) << 4)) = lo;
       }
     }
     const int tn = t + 1;
@@ -119,14 +108,14 @@ __global__ __launch_bounds__(N16_THREADS) void conv3x3_c64_n16_kernel(n16_args a
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         const int s = tap * 2 + half;
-        const n16_bf16x8 whs = *reinterpret_cast<const n16_bf16x8*>(sW + (s * 2 + 0) * 1024 + lane * 16);
-        const n16_bf16x8 wls = *reinterpret_cast<const n16_bf16x8*>(sW + (s * 2 + 1) * 1024 + lane * 16);
+        const bf16x8_t whs = *reinterpret_cast<const bf16x8_t*>(sW + (s * 2 + 0) * 1024 + lane * 16);
+        const bf16x8_t wls = *reinterpret_cast<const bf16x8_t*>(sW + (s * 2 + 1) * 1024 + lane * 16);
         const int chunk = 4 * half + kg;                      // channels 32 half + 8 kg .. + 7
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           const int p = (wave + dy) * N16_HC + 16 * c + n + dx, sw = p & 15;
-          const n16_bf16x8 ah = *reinterpret_cast<const n16_bf16x8*>(sA + p * 256 + ((chunk ^ sw) << 4));
-          const n16_bf16x8 al = *reinterpret_cast<const n16_bf16x8*>(sA + p * 256 + (((8 + chunk) ^ sw) << 4));
+          const bf16x8_t ah = *reinterpret_cast<const bf16x8_t*>(sA + p * 256 + ((chunk ^ sw) << 4));
+          const bf16x8_t al = *reinterpret_cast<const bf16x8_t*>(sA + p * 256 + (((8 + chunk) ^ sw) << 4));
           acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whs, al, acc[c], 0, 0, 0);
           acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wls, ah, acc[c], 0, 0, 0);
           acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whs, ah, acc[c], 0, 0, 0);

@@ -25,7 +25,7 @@
 //     registers, 32 contiguous bytes per lane -- no LDS transpose, no extra barrier; the residual values are fetched
 //     while the tile's last chunk computes.
 // DMA completion is hand-counted (hipcc does not see inline-asm memory operations); the rules sit next to each wait.
-#include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -47,8 +47,6 @@ template <bool SPARSE> struct RingLds {
   static constexpr int TOTAL = WINTAB + (SPARSE ? 1024 : 0);
 };
 
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct ring_extra {
   const void* src;            // fp16 chunk-planar [B][nc][H][W][16]
@@ -65,36 +63,9 @@ struct ring_extra {
 };
 __device__ __forceinline__ bool rg_touch_on(const ring_extra& e) { return e.touch != 0; }
 
-// one 1 KiB LDS-DMA piece: lane l writes LDS bytes lds + 16 l from (buffer base + voff + soff).  rsrc / soff / lds must
-// be wave-uniform values the compiler can keep in SGPRs (readfirstlane them).
-__device__ __forceinline__ void rg_dma1(unsigned voff, i32x4 rsrc, unsigned soff, unsigned lds) {
-  unsigned keep;
-  asm volatile(
-      "s_nop 4\n\t"
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %4\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds)
-      : "memory");
-}
-
-__device__ __forceinline__ i32x4 rg_rsrc(const void* base, unsigned bytes) {
-  const unsigned long long p = reinterpret_cast<unsigned long long>(base);
-  i32x4 r;
-  r[0] = (int)(unsigned)p;
-  r[1] = (int)(unsigned)(p >> 32);
-  r[2] = (int)bytes;
-  r[3] = 0x00020000;
-  return r;
-}
-
 constexpr int RG_PROBE_UNIT = 3;      // dbg 16: the tile (ordinal within the workgroup) whose chunks are stamped
 template <int V> struct IntC { static constexpr int value = V; };
 
-template <int N> __device__ __forceinline__ void rg_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void rg_wait_vm_lgkm0() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory"); }
 
 // DBG (developer ablations, tools/bench_ring.py): 1 = skip the MFMAs, 2 = skip the DMA, 4 = MFMA-shape clock experiment (wrong
 // arithmetic), 8 = skip the epilogue, 16 = timeline
@@ -154,19 +125,16 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_kernel(cdfo_conv_args
       const int q = (wave - ACT_WAVES) * PPW + j;
       d_iy[j] = q < TAPS * 2 ? 0 : 1 << 20;
       d_ix[j] = 0;
-      // LDS position `lane` of a slab row = MFMA row m of 32-channel block (lane >> 5); it holds output channel
-      // (m>>4)*16 + ((m>>2)&1)*8 + ((m>>3)&1)*4 + (m&3), so that the accumulator registers of a lane are 8 consecutive
-      // channels of each 16-channel chunk (see the epilogue)
-      const int m = lane & 31;
-      const int chan = (lane & 32) + ((m >> 4) & 1) * 16 + ((m >> 2) & 1) * 8 + ((m >> 3) & 1) * 4 + (m & 3);
-      d_rel[j] = (q * e.CoutP + chan) * 16;
+      // LDS position `lane` of a slab row = MFMA row (lane & 31) of 32-channel block (lane >> 5): the accumulator registers of a
+      // lane are 8 consecutive channels of each 16-channel chunk (see the epilogue)
+      d_rel[j] = (q * e.CoutP + MFMA_ROW_CHANNEL(lane)) * 16;
       dst_off[j] = q < TAPS * 2 ? RG_ACT + q * 1024 : -1;      // padding piece -> dump
     }
   }
   const unsigned plane = (unsigned)(H * W) * 32u;                 // bytes of one 16-channel plane
   const unsigned wchunk = (unsigned)(TAPS * 2 * e.CoutP) * 16u;   // bytes of one chunk's weight slab (all output blocks)
   const unsigned img_bytes = plane * (unsigned)e.src_planes;
-  const i32x4 rsrc_w = rg_rsrc(e.w, (unsigned)e.w_bytes);
+  const i32x4 rsrc_w = lds_dma_rsrc(e.w, (unsigned)e.w_bytes);
 
   // ---- fragment read offsets: tile rows 2w..2w+3 of the halo, column offset dx, this lane's pixel r
   int p_off[12];
@@ -198,7 +166,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_kernel(cdfo_conv_args
       int b, oy0, ox0, n0;
       unit_coords(iu, b, oy0, ox0, n0);
       if (!loader_w) {
-        rsrc_i = rg_rsrc(static_cast<const unsigned char*>(e.src) + (unsigned long long)b * img_bytes, img_bytes);
+        rsrc_i = lds_dma_rsrc(static_cast<const unsigned char*>(e.src) + (unsigned long long)b * img_bytes, img_bytes);
         const int base = e.halfsplit ? ((oy0 - 1) * 2 * W + (ox0 - 1)) * 16 : ((oy0 - 1) * W + (ox0 - 1)) * 32;
 #pragma unroll
         for (int j = 0; j < PPW; ++j) {
@@ -221,7 +189,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_kernel(cdfo_conv_args
     if (DBG & 2) return;
     if (!loader) return;
     const unsigned dst = __builtin_amdgcn_readfirstlane(dst_off[j] >= 0 ? stage_i + (unsigned)dst_off[j] : lds0 + (unsigned)L::DUMP);
-    rg_dma1(voff[j], rsrc_i, soff_i, dst);
+    lds_dma1(voff[j], rsrc_i, soff_i, dst);
   };
   auto issue_end = [&]() {
     ++gi;
@@ -276,7 +244,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_kernel(cdfo_conv_args
     const unsigned edst = lds0 + (unsigned)L::ETILE + (unsigned)(wave * (RG_ET_PIECES / 8)) * 1024u;
     if (SPARSE && a.res_up2) {
       const int Hd = H >> 1, Wd = W >> 1;
-      ersrc = rg_rsrc(a.res_up2 + (long long)b * Hd * Wd * a.ldru, (unsigned)(Hd * Wd * a.ldru) * 4u);
+      ersrc = lds_dma_rsrc(a.res_up2 + (long long)b * Hd * Wd * a.ldru, (unsigned)(Hd * Wd * a.ldru) * 4u);
 #pragma unroll
       for (int k = 0; k < 4; ++k) ersrc[k] = __builtin_amdgcn_readfirstlane(ersrc[k]);
 #pragma unroll
@@ -305,8 +273,8 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_kernel(cdfo_conv_args
       //     "at most (NS - 2) PPW outstanding" is the only bound that implies batch g has landed whatever else is in flight.
       //     (2) my fragment reads of batch g-1 have RETURNED (its stage is overwritten after the barrier).  Then the
       //     barrier: everyone's pieces of g are in LDS, nobody still reads the stage of g-1.
-      if (g + RG_NS - 2 >= total) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      else rg_wait_vm_lgkm0<(RG_NS - 2) * PPW>();
+      if (g + RG_NS - 2 >= total) wait_vm_lgkm0<0>();
+      else wait_vm_lgkm0<(RG_NS - 2) * PPW>();
       static_assert((RG_NS - 2) * PPW < 64, "vmcnt is a 6-bit counter");
       stamp(1);
       __builtin_amdgcn_s_barrier();
@@ -383,7 +351,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_kernel(cdfo_conv_args
       if (do_issue) issue_end();
       if (DBG & 16) {
         stamp(8);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         if (ord == RG_PROBE_UNIT && c >= 8 && c < 12 && lane == 0) {
           unsigned long long* cb = reinterpret_cast<unsigned long long*>(const_cast<float*>(a.res2)) +
                                    (((long long)blockIdx.x * 8 + wave) * 4 + (c - 8)) * 10;
@@ -396,7 +364,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_kernel(cdfo_conv_args
       // (NS - 2) PPW pieces to be pending) retire them within the next two chunks.
       if (SPARSE && c == 0 && a.res_up2 && !(DBG & 2)) {
 #pragma unroll
-        for (int j = 0; j < RG_ET_PIECES / 8; ++j) rg_dma1(evoff[j], ersrc, 0u, __builtin_amdgcn_readfirstlane(edst + j * 1024));
+        for (int j = 0; j < RG_ET_PIECES / 8; ++j) lds_dma1(evoff[j], ersrc, 0u, __builtin_amdgcn_readfirstlane(edst + j * 1024));
       }
     };
 
@@ -624,7 +592,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
     const unsigned plane = (unsigned)(H * W) * 32u;
     const unsigned wchunk = (unsigned)(TAPS * 2 * e.CoutP) * 16u;
     const unsigned img_bytes = plane * (unsigned)e.src_planes;
-    const i32x4 rsrc_w = rg_rsrc(e.w, (unsigned)e.w_bytes);
+    const i32x4 rsrc_w = lds_dma_rsrc(e.w, (unsigned)e.w_bytes);
     int iu = 0, ic = 0, gi = 0;
     unsigned voff[PPW];
     i32x4 rsrc_i = rsrc_w;
@@ -634,7 +602,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
         int b, oy0, ox0, n0;
         unit_coords(iu, b, oy0, ox0, n0);
         if (!loader_w) {
-          rsrc_i = rg_rsrc(static_cast<const unsigned char*>(e.src) + (unsigned long long)b * img_bytes, img_bytes);
+          rsrc_i = lds_dma_rsrc(static_cast<const unsigned char*>(e.src) + (unsigned long long)b * img_bytes, img_bytes);
           const int base = e.halfsplit ? ((oy0 - 1) * 2 * W + (ox0 - 1)) * 16 : ((oy0 - 1) * W + (ox0 - 1)) * 32;
 #pragma unroll
           for (int j = 0; j < PPW; ++j) {
@@ -656,7 +624,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
 #pragma unroll
         for (int j = 0; j < PPW; ++j) {
           const unsigned dst = __builtin_amdgcn_readfirstlane(dst_off[j] >= 0 ? stage_i + (unsigned)dst_off[j] : lds0 + (unsigned)L::DUMP);
-          rg_dma1(voff[j], rsrc_i, soff_i, dst);
+          lds_dma1(voff[j], rsrc_i, soff_i, dst);
         }
       }
       ++gi;
@@ -687,7 +655,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
       unit_coords(ord, ub, uoy0, uox0, un0);
       if (etile) {
         const int Hd = H >> 1, Wd = W >> 1;
-        ersrc = rg_rsrc(a.res_up2 + (long long)ub * Hd * Wd * a.ldru, (unsigned)(Hd * Wd * a.ldru) * 4u);
+        ersrc = lds_dma_rsrc(a.res_up2 + (long long)ub * Hd * Wd * a.ldru, (unsigned)(Hd * Wd * a.ldru) * 4u);
 #pragma unroll
         for (int k = 0; k < 4; ++k) ersrc[k] = __builtin_amdgcn_readfirstlane(ersrc[k]);
 #pragma unroll
@@ -702,7 +670,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
         }
       }
       if (touch) {
-        trsrc = rg_rsrc(a.res1 + (long long)ub * H * W * a.ldr1, (unsigned)(H * W * a.ldr1) * 4u);
+        trsrc = lds_dma_rsrc(a.res1 + (long long)ub * H * W * a.ldr1, (unsigned)(H * W * a.ldr1) * 4u);
 #pragma unroll
         for (int k = 0; k < 4; ++k) trsrc[k] = __builtin_amdgcn_readfirstlane(trsrc[k]);
       }
@@ -715,13 +683,13 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
         // nothing else)
         {
           const int allow = (RG_NS - 2) * PPW + ex_prev1 + (RG_NS > 3 ? ex_prev2 : 0);
-          if (g + RG_NS - 2 >= total) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          else if (allow == (RG_NS - 2) * PPW) rg_wait_vm<(RG_NS - 2) * PPW>();
-          else if (allow == (RG_NS - 2) * PPW + EPC) rg_wait_vm<(RG_NS - 2) * PPW + EPC>();
-          else if (allow == (RG_NS - 2) * PPW + TPC) rg_wait_vm<(RG_NS - 2) * PPW + TPC>();
-          else if (allow == (RG_NS - 2) * PPW + 2 * EPC) rg_wait_vm<(RG_NS - 2) * PPW + 2 * EPC>();
-          else if (allow == (RG_NS - 2) * PPW + 2 * TPC) rg_wait_vm<(RG_NS - 2) * PPW + 2 * TPC>();
-          else rg_wait_vm<(RG_NS - 2) * PPW>();      // (any other mix: the plain bound is always safe)
+          if (g + RG_NS - 2 >= total) wait_vm<0>();
+          else if (allow == (RG_NS - 2) * PPW) wait_vm<(RG_NS - 2) * PPW>();
+          else if (allow == (RG_NS - 2) * PPW + EPC) wait_vm<(RG_NS - 2) * PPW + EPC>();
+          else if (allow == (RG_NS - 2) * PPW + TPC) wait_vm<(RG_NS - 2) * PPW + TPC>();
+          else if (allow == (RG_NS - 2) * PPW + 2 * EPC) wait_vm<(RG_NS - 2) * PPW + 2 * EPC>();
+          else if (allow == (RG_NS - 2) * PPW + 2 * TPC) wait_vm<(RG_NS - 2) * PPW + 2 * TPC>();
+          else wait_vm<(RG_NS - 2) * PPW>();      // (any other mix: the plain bound is always safe)
           static_assert((RG_NS - 2) * PPW + 2 * TPC < 64, "vmcnt is a 6-bit counter");
         }
         __builtin_amdgcn_s_barrier();
@@ -734,8 +702,8 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
 #pragma unroll
           for (int k = 0; k < EPP / EPC; ++k)
             if (c == k) {
-              rg_dma1(evoff[2 * k], ersrc, 0u, __builtin_amdgcn_readfirstlane(edst + (2 * k) * 1024));
-              rg_dma1(evoff[2 * k + 1], ersrc, 0u, __builtin_amdgcn_readfirstlane(edst + (2 * k + 1) * 1024));
+              lds_dma1(evoff[2 * k], ersrc, 0u, __builtin_amdgcn_readfirstlane(edst + (2 * k) * 1024));
+              lds_dma1(evoff[2 * k + 1], ersrc, 0u, __builtin_amdgcn_readfirstlane(edst + (2 * k + 1) * 1024));
             }
           extras += EPC;
         }
@@ -746,7 +714,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
             const int pid = pw * (TCH * TPC) + (c - t0) * TPC + j;
             const int gy = uoy0 + (pid >> 3), gx = uox0 + (pid & 7) * 4 + (lane >> 4);
             const unsigned vo = (gy < H && gx < W) ? (unsigned)((gy * W + gx) * a.ldr1 + un0 + (lane & 15) * 4) * 4u : 0x80000000u;
-            rg_dma1(vo, trsrc, 0u, dump);
+            lds_dma1(vo, trsrc, 0u, dump);
           }
           extras += TPC;
         }
@@ -784,7 +752,7 @@ __global__ __launch_bounds__(RG_THREADS) void conv3x3_ring_split_kernel(cdfo_con
     unit_coords(ord, b, oy0, ox0, n0);
     const int oyw = oy0 + wave * CR;
     auto chunk = [&](int c) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // my fragment reads of batch g-1 have returned
+      wait_lgkm<0>();      // my fragment reads of batch g-1 have returned
       __builtin_amdgcn_s_barrier();
       const unsigned char* sW = smem + (g % RG_NS) * STAGE + w16;
       // four sub-steps: (tap pair, rows 0-1), (pair, rows 2-3); the weight fragments of a pair serve both

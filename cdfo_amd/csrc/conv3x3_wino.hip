@@ -30,15 +30,11 @@
 //     batch n computes;
 //   * the epilogue of a completed row is lane-local: 4 adds per output channel (the output transform), activation, fp16, two
 //     8-byte stores (columns 2t, 2t + 1) into the chunk-planar result [B][Cout/16][H][W][16] or its space-to-depth form.
-#include "common.h"
+#include "lds_dma.h"
 #include <type_traits>
 
 namespace {
 
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int WN_THREADS = 512;
 constexpr int WN_ROWS = 3;                       // input rows per batch (= the period of the rolling accumulator sets)
@@ -61,7 +57,6 @@ struct wino_args {
   unsigned long long* clk;                       // dbg 512: s_memtime stamps [workgroup][wave][8] of one steady-state batch
 };
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // The pixel loads are compiler-visible buffer loads: their data crosses basic blocks in REGISTERS (issued in one batch, consumed in
 // the next), and hipcc may copy such registers at a control-flow merge -- with inline-assembly loads it did so while the data was
@@ -165,7 +160,7 @@ __global__ __launch_bounds__(WN_THREADS) void conv3x3_c64_wino_kernel(wino_args 
     for (int j = 0; j < WN_ROWS; ++j) {
       const int y = i0 + j;
       const int rowok = -(int)(y >= 0 && y < H && y <= y1);      // all ones / zero: scalar masks, no branch
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(base), 0, (int)img_bytes & rowok, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(base), 0, (int)img_bytes & rowok, BUFFER_RSRC_WORD3);
       const int so = (y * W * 32) & rowok;
       if (DBG & 2) {
         raw[j][0] = u32x4{va, vb, (unsigned)so, 0u}; raw[j][1] = u32x4{vb, va, 0u, (unsigned)so};
@@ -197,7 +192,7 @@ __global__ __launch_bounds__(WN_THREADS) void conv3x3_c64_wino_kernel(wino_args 
     const int row = min(max(base + s_r, 0), Hl - 1), col = min(max((x0 >> 1) - 1 + s_px, 0), Wl - 1);
     const unsigned vo = su < 432 ? s_const + (unsigned)(row * Wl + col) * 32u : 0x80000000u;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.src) + (long long)b * img_bytes, 0,
-                                                                        (int)img_bytes, 0x00020000);
+                                                                        (int)img_bytes, BUFFER_RSRC_WORD3);
     if (DBG & 2) sreg = u32x4{vo, vo, vo, vo};
     else sreg = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)vo, 0, 0));
   };
@@ -252,7 +247,7 @@ __global__ __launch_bounds__(WN_THREADS) void conv3x3_c64_wino_kernel(wino_args 
   // any wave passes barrier n; a wave that is still in batch n's third row reads slot n % 3.
   auto sync = [&]() {
     if (DBG & 16) return;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();
   };
   f16x8_t fv[2][4];     // V fragments [K half][xi] of the row in flight (steady state; carried from batch to batch)
@@ -320,7 +315,7 @@ __global__ __launch_bounds__(WN_THREADS) void conv3x3_c64_wino_kernel(wino_args 
     const unsigned char* vbase = smem + lane16 + voff;
     const unsigned char* vnext = smem + lane16 + voff_next;
     const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(a.out) + (long long)b * out_img_bytes,
-                                                                        0, (int)out_img_bytes, 0x00020000);
+                                                                        0, (int)out_img_bytes, BUFFER_RSRC_WORD3);
     if constexpr (ALL) {
       // steady state.  The eight V fragments of a row are requested in one go -- those of row j + 1 right behind row j's MFMAs, i.e.
       // BEFORE row j's epilogue, whose vector work covers their latency (with reads only two fragments ahead of their MFMAs every
@@ -393,7 +388,7 @@ __global__ __launch_bounds__(WN_THREADS) void conv3x3_c64_wino_kernel(wino_args 
       row(std::integral_constant<int, 2>{});
       if (DBG & 512) {
         stamp(7);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         if (a.clk && n == 8 && lane == 0) {
           unsigned long long* c = a.clk + ((long long)blockIdx.x * 8 + wave) * 8;
 #pragma unroll
@@ -471,7 +466,7 @@ __global__ __launch_bounds__(WN_THREADS) void conv3x3_c64_wino_kernel(wino_args 
       issue_loads(1, va, vb, b, y0, y1, i0);
     }
     if (!(DBG & 4)) {      // two out-of-range (dropped) stores stand for "the previous batch's rows 1 and 2" in the wait counts
-      const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(a.out), 0, 0, 0x00020000);
+      const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(a.out), 0, 0, BUFFER_RSRC_WORD3);
 #pragma unroll
       for (int i = 0; i < 2; ++i) __builtin_amdgcn_raw_buffer_store_b128(u32x4{0u, 0u, 0u, 0u}, r0, (int)0x80000000u, 0, 0);
     }

@@ -27,7 +27,7 @@
 //
 // DMA completion is tracked by hand (hipcc does not count inline-asm memory operations) with counted s_waitcnt; the
 // rules are written next to each wait.
-#include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -44,10 +44,6 @@ template <int NW> struct WsLds {
 };
 constexpr int WS_IW = 34, WS_NPIX = 4 * 34;
 
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct ws_args {
   const void* src; unsigned src_bytes;
@@ -63,28 +59,6 @@ struct ws_args {
   // offset / mask epilogue (conv3x3_c64_wsq_kernel<0, true>; cdfo_conv3x3_c64_ws_offmask): see cdfo_hip.h, CDFO_STORE_OFFMASK
   float* om_offset; float* om_mask; const float* om_flow; long long om_flow_bstride; float om_mag; int om_accumulate; int om_cout;
 };
-
-// five 1 KiB LDS-DMA pieces: lane l of piece k writes LDS bytes lds + 1024 k + 16 l from (buffer base + voff[k] + soff)
-__device__ __forceinline__ void ws_dma5(const unsigned (&voff)[5], i32x4 rsrc, unsigned soff, unsigned lds) {
-  unsigned keep;
-  asm volatile(
-      "s_nop 4\n\t"
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %7\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %1, %6, %8 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %2, %6, %8 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %3, %6, %8 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %4, %6, %8 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %5, %6, %8 offen lds\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "s"(rsrc), "s"(lds), "s"(soff)
-      : "memory", "scc");
-}
 
 // DBG (developer ablations): 1 = skip the MFMAs, 2 = skip the DMA, 8 = skip the epilogue, 64 = no start-up stagger,
 // 128 = clock probe
@@ -109,15 +83,13 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_c64_ws_kernel(ws_args a) {
   const int H = a.H, W = a.W;
 
   // ---- one-time: this workgroup's weight block and bias
-  // MFMA row m = 8j + 4h + k of a 32-channel block holds channel (j>>1)*16 + h*8 + (j&1)*4 + k, so that a lane's
-  // accumulators (fixed h; j, k = register index) are 8 consecutive channels of each 16-channel chunk
-  auto chan_of_row = [](int n) { const int m = n & 31; return (n & 32) + ((m >> 4) & 1) * 16 + ((m >> 2) & 1) * 8 + ((m >> 3) & 1) * 4 + (m & 3); };
+  // (rows permuted: mfma_row_channel, so that a lane's accumulators are 8 consecutive channels of each 16-channel chunk)
   for (int i = tid; i < WS_W_BYTES / 16; i += WS_THREADS) {
     const int row = i >> 6, n = i & 63;          // row = (chunk*9 + tap)*2 + k-half
     *reinterpret_cast<u32x4*>(smem + i * 16) =
-        *reinterpret_cast<const u32x4*>(a.w + ((long long)row * a.CoutP + n0 + chan_of_row(n)) * 8);
+        *reinterpret_cast<const u32x4*>(a.w + ((long long)row * a.CoutP + n0 + mfma_row_channel(n)) * 8);
   }
-  if (tid < 64) reinterpret_cast<float*>(smem + WS_BIAS_OFF)[tid] = a.bias ? a.bias[n0 + chan_of_row(tid)] : 0.f;
+  if (tid < 64) reinterpret_cast<float*>(smem + WS_BIAS_OFF)[tid] = a.bias ? a.bias[n0 + mfma_row_channel(tid)] : 0.f;
   unsigned* s_next = reinterpret_cast<unsigned*>(smem + WS_CNT_OFF);
   if (tid == 0) *s_next = NW;                    // tiles 0..NW-1 of the workgroup go to its waves, the rest first come first served
   __syncthreads();
@@ -146,14 +118,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_c64_ws_kernel(ws_args a) {
   unsigned char* stg = smem + WS_STG_OFF + wave * (NBUF * WS_BUF);
   const unsigned stg_lds = (unsigned)(unsigned long long)(smem) + WS_STG_OFF + wave * (NBUF * WS_BUF);
 
-  i32x4 rsrc;
-  {
-    const unsigned long long p = reinterpret_cast<unsigned long long>(a.src);
-    rsrc[0] = (int)(unsigned)p;
-    rsrc[1] = (int)(unsigned)(p >> 32);
-    rsrc[2] = (int)a.src_bytes;
-    rsrc[3] = 0x00020000;
-  }
+  const i32x4 rsrc = lds_dma_rsrc(a.src, a.src_bytes);
   const int tiles_x = (W + 31) >> 5, hp = H >> 1;
   const int total = a.B * hp * tiles_x;
   const unsigned plane = (unsigned)(H * W) * 32u;        // bytes of one 16-channel plane of one image
@@ -188,7 +153,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_c64_ws_kernel(ws_args a) {
 
   if (u < total) {
     make_desc(u);
-    if (!(DBG & 2)) ws_dma5(voff, rsrc, soff0, stg_lds);
+    if (!(DBG & 2)) lds_dma<5>(voff, rsrc, soff0, stg_lds);
   }
   // Start-up stagger.  The waves run the same program with no barrier, so the two waves of a SIMD (w, w+4) would stay
   // in lockstep -- sharing the matrix pipe during their MFMA phases and leaving it idle during their simultaneous
@@ -219,7 +184,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_c64_ws_kernel(ws_args a) {
       // stores and LDS-DMA loads retire in issue order; measured: VGPR loads and LDS-DMA loads do NOT -- a vmcnt(5)
       // behind 16 residual loads + 5 DMA pieces returned before the older residual loads had landed -- so counted waits
       // here only ever count younger DMA pieces, which do retire in order among themselves.)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vm<0>();
       const unsigned char* sA = stg + (NBUF == 2 ? (c & 1) * WS_BUF : 0);
       const unsigned char* sWc = sWl + c * (9 * 2 * 64 * 16);
       f16x8_t fp[2][2], fw[2][2];                // [parity][mi / ni]: fragments are read one tap ahead
@@ -243,7 +208,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_c64_ws_kernel(ws_args a) {
           // cycles; issuing without this wait corrupted ~1 tile per launch).  LDS operations of a wave return in
           // order and the 8 reads of taps 0 and 1 above are younger than all of them, so "at most 8 outstanding"
           // is enough -- and free, those 8 are about to be waited for anyway.
-          asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
+          wait_lgkm<8>();
           if (RES && c == 3) {
             // 16 residual loads: pixel (row cy0 + mi, column cx0 + r), channels n0 + ni*32 + jj*16 + h*8 + 4*hf .. +3.
             // Always issued (a masked pixel reads its clamped neighbour), so that the wait below can count them.
@@ -257,10 +222,10 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_c64_ws_kernel(ws_args a) {
           }
           if (NBUF == 2) {
             if (c < 3) {
-              if (!(DBG & 2)) ws_dma5(voff, rsrc, soff0 + (unsigned)(c + 1) * plane, stg_lds + ((c + 1) & 1) * WS_BUF);
+              if (!(DBG & 2)) lds_dma<5>(voff, rsrc, soff0 + (unsigned)(c + 1) * plane, stg_lds + ((c + 1) & 1) * WS_BUF);
             } else if ((unext = grab()) < total) {
               make_desc(unext);
-              if (!(DBG & 2)) ws_dma5(voff, rsrc, soff0, stg_lds);
+              if (!(DBG & 2)) lds_dma<5>(voff, rsrc, soff0, stg_lds);
             }
           }
         }
@@ -268,12 +233,12 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_c64_ws_kernel(ws_args a) {
           // single staging buffer: the next chunk's DMA may only be issued once EVERY fragment read of this chunk has
           // returned (tap 8's were issued one tap ago); it then flies behind tap 8's MFMAs and, between tiles, the epilogue,
           // while the SIMD's other two waves keep the matrix pipe busy
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          wait_lgkm<0>();
           if (c < 3) {
-            if (!(DBG & 2)) ws_dma5(voff, rsrc, soff0 + (unsigned)(c + 1) * plane, stg_lds);
+            if (!(DBG & 2)) lds_dma<5>(voff, rsrc, soff0 + (unsigned)(c + 1) * plane, stg_lds);
           } else if ((unext = grab()) < total) {
             make_desc(unext);
-            if (!(DBG & 2)) ws_dma5(voff, rsrc, soff0, stg_lds);
+            if (!(DBG & 2)) lds_dma<5>(voff, rsrc, soff0, stg_lds);
           }
         }
         const int par = t & 1;
@@ -430,34 +395,6 @@ constexpr int WQ_W_OFF = 2 * WQ_NS * WQ_ACT;           // 90,112
 constexpr int WQ_TOTAL = WQ_W_OFF + WS_W_BYTES;        // 163,840 bytes
 static_assert(WQ_TOTAL <= 160 * 1024, "LDS budget");
 
-// six / five 1 KiB LDS-DMA pieces into consecutive kilobytes, ONE asm block each (m0 is live across the pieces; see ws_dma5)
-__device__ __forceinline__ void wr_dma6(const unsigned (&voff)[6], i32x4 rsrc, unsigned soff, unsigned lds) {
-  unsigned keep;
-  asm volatile(
-      "s_nop 4\n\t"
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %8\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %1, %7, %9 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %2, %7, %9 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %3, %7, %9 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %4, %7, %9 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %5, %7, %9 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %6, %7, %9 offen lds\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "v"(voff[5]), "s"(rsrc), "s"(lds), "s"(soff)
-      : "memory", "scc");
-}
-__device__ __forceinline__ void wr_dma5(const unsigned (&voff)[6], i32x4 rsrc, unsigned soff, unsigned lds) {
-  const unsigned v5[5] = {voff[0], voff[1], voff[2], voff[3], voff[4]};
-  ws_dma5(v5, rsrc, soff, lds);
-}
-
 // DBG: 1 = skip the MFMAs, 2 = skip the DMA, 8 = skip the epilogue (developer ablations); 32 = timeline probe: a.clk receives
 // s_memtime stamps [workgroup][wave 0-11][4][8] of the consumers' third tile (rows 0 / 1 = its two steps: entry, barrier passed,
 // after taps 2 / 5 / 8, end) and, in slot 6 of rows 0 / 1 / 2, the epilogue-start times of the fourth, fifth and 25th tile
@@ -523,11 +460,7 @@ __global__ __launch_bounds__(WR_THREADS) void conv3x3_c64_wsq_kernel(ws_args a) 
       d_ix[j] = ix;
       d_rel[j] = (iy * W + ix) * 32 + half * 16;
     }
-    i32x4 rsrc;
-    {
-      const unsigned long long p = reinterpret_cast<unsigned long long>(a.src);
-      rsrc[0] = (int)(unsigned)p; rsrc[1] = (int)(unsigned)(p >> 32); rsrc[2] = (int)a.src_bytes; rsrc[3] = 0x00020000;
-    }
+    const i32x4 rsrc = lds_dma_rsrc(a.src, a.src_bytes);
     int iu = 0, ic = 0, gi = 0;
     unsigned voff[6], soff0 = 0;
     auto issue_batch = [&]() {
@@ -549,8 +482,8 @@ __global__ __launch_bounds__(WR_THREADS) void conv3x3_c64_wsq_kernel(ws_args a) 
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
           const unsigned soff = __builtin_amdgcn_readfirstlane(soff0 + (unsigned)(ic * 2 + pl) * plane);
-          if (six) wr_dma6(voff, rsrc, soff, dst + pl * WQ_PLANE);
-          else wr_dma5(voff, rsrc, soff, dst + pl * WQ_PLANE);
+          if (six) lds_dma<6>(voff, rsrc, soff, dst + pl * WQ_PLANE);
+          else lds_dma<5>(voff, rsrc, soff, dst + pl * WQ_PLANE);
         }
       }
       ++gi;
@@ -560,7 +493,7 @@ __global__ __launch_bounds__(WR_THREADS) void conv3x3_c64_wsq_kernel(ws_args a) 
     for (int s = 0; s < nsteps; ++s) {
       const int g = s - lag;
       // two stages: batch g is the only thing of mine in flight when I wait for it
-      if (g >= 0 && g < nbatch) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (g >= 0 && g < nbatch) wait_vm<0>();
       __builtin_amdgcn_s_barrier();
       if (g >= 0 && g + 1 < nbatch) issue_batch();      // into the stage of batch g-1: nobody reads it behind this barrier
     }
@@ -591,7 +524,7 @@ __global__ __launch_bounds__(WR_THREADS) void conv3x3_c64_wsq_kernel(ws_args a) 
     }
 
   for (int s = 0; s < lag; ++s) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();
   }
   int g = 0;
@@ -608,7 +541,7 @@ __global__ __launch_bounds__(WR_THREADS) void conv3x3_c64_wsq_kernel(ws_args a) 
     for (int c = 0; c < 2; ++c, ++g) {
       unsigned long long ts[6] = {0, 0, 0, 0, 0, 0};      // dbg 32: step entry, barrier passed, after taps 2 / 5 / 8, step end
       if (DBG & 32) asm volatile("s_memtime %0" : "=s"(ts[0]) : : "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // my fragment reads of batch g-1 have returned
+      wait_lgkm<0>();      // my fragment reads of batch g-1 have returned
       __builtin_amdgcn_s_barrier();
       if (DBG & 32) asm volatile("s_memtime %0" : "=s"(ts[1]) : : "memory");
       // Issue priority.  A SIMD's two consumers do not share the matrix pipe evenly: the older wave (group A) takes its MFMAs
@@ -649,7 +582,7 @@ __global__ __launch_bounds__(WR_THREADS) void conv3x3_c64_wsq_kernel(ws_args a) 
       }
       if (DBG & 32) {
         asm volatile("s_memtime %0" : "=s"(ts[5]) : : "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         if (a.clk && ord == 2 && lane == 0) {
           unsigned long long* cbuf = a.clk + (((long long)blockIdx.x * 12 + wave) * 4 + c) * 8;
 #pragma unroll
@@ -660,7 +593,7 @@ __global__ __launch_bounds__(WR_THREADS) void conv3x3_c64_wsq_kernel(ws_args a) 
     if (DBG & 32) {
       unsigned long long te = 0;
       asm volatile("s_memtime %0" : "=s"(te) : : "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lgkm<0>();
       if (a.clk && (ord == 3 || ord == 4 || ord == 24) && lane == 0)       // epilogue-start times: undisturbed tile period(s)
         a.clk[(((long long)blockIdx.x * 12 + wave) * 4 + (ord == 24 ? 2 : ord - 3)) * 8 + 6] = te;
     }
@@ -684,9 +617,9 @@ __global__ __launch_bounds__(WR_THREADS) void conv3x3_c64_wsq_kernel(ws_args a) 
       const int third = a.om_cout / 3;
       const unsigned P4 = (unsigned)(H * W) * 4u;
       const __amdgpu_buffer_rsrc_t r_off = __builtin_amdgcn_make_buffer_rsrc(a.om_offset + (long long)cb * 2 * third * (H * W), 0,
-                                                                             (int)(2 * third * P4), 0x00020000);
+                                                                             (int)(2 * third * P4), BUFFER_RSRC_WORD3);
       const __amdgpu_buffer_rsrc_t r_msk = __builtin_amdgcn_make_buffer_rsrc(a.om_mask + (long long)cb * third * (H * W), 0,
-                                                                             (int)(third * P4), 0x00020000);
+                                                                             (int)(third * P4), BUFFER_RSRC_WORD3);
       bool ok[4];
       unsigned vo[2][4];
 #pragma unroll
@@ -816,7 +749,7 @@ __global__ __launch_bounds__(WR_THREADS) void conv3x3_c64_wsq_kernel(ws_args a) 
     }
   }
   for (int s = lag; s < WQ_LAG; ++s) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();
   }
 }

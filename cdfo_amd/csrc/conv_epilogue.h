@@ -69,7 +69,6 @@ __device__ __forceinline__ void conv_tile_epilogue_impl(const cdfo_conv_args& a,
       if (r2row) v += *reinterpret_cast<const f32x4*>(r2row + xi * a.ldr2);
       const int eoff = s2d ? (xi >> 1) * a.ldo + (xi & 1) * a.Cout : xi * ostep;
       if (a.out_f16) {
-        typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
         f16x4_t hv;
 #pragma unroll
         for (int k = 0; k < 4; ++k) hv[k] = (_Float16)v[k];

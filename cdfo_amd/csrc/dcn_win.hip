@@ -25,6 +25,7 @@
 //     cdfo_dcn_forward re-runs the exact-fp32 kernel, as for dcn_fast.
 // HBM roofline: (C + 3*dg*9 + Co) * 4 bytes per output pixel; offsets + mask are 77 % of it and are read
 // exactly once, coalesced (each half-wave reads 128-byte rows of one tap plane).
+#include "lds_dma.h"
 #include "numeric.h"
 
 typedef _Float16 wn_h8 __attribute__((ext_vector_type(8)));
@@ -91,7 +92,6 @@ __device__ __forceinline__ float wn_bload_nt(__amdgpu_buffer_rsrc_t r, unsigned 
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 2));
 }
 __device__ __forceinline__ f32x4 wn_bload4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   return __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
 }
 
@@ -127,11 +127,11 @@ __global__ __launch_bounds__(WN_THREADS) void dcn_win_kernel(WinArgs a) {
   const int cdg4 = (a.C / a.dg) >> 2;                            // 4-channel blocks per deformable group
   // per-image buffer descriptors (wave-uniform): 32-bit lane offsets + scalar offsets, hardware zero fill out of range
   const float* const in_b = a.in + (long long)b * a.C * HW;
-  const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in_b), 0, a.C * HW * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in_b), 0, a.C * HW * 4, BUFFER_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t r_off = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.offset + (long long)b * a.dg * 2 * WN_T * P), 0, a.dg * 2 * WN_T * P * 4, 0x00020000);
+      const_cast<float*>(a.offset + (long long)b * a.dg * 2 * WN_T * P), 0, a.dg * 2 * WN_T * P * 4, BUFFER_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t r_msk = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(MASK ? a.mask + (long long)b * a.dg * WN_T * P : a.offset), 0, a.dg * WN_T * P * 4, 0x00020000);
+      const_cast<float*>(MASK ? a.mask + (long long)b * a.dg * WN_T * P : a.offset), 0, a.dg * WN_T * P * 4, BUFFER_RSRC_WORD3);
 
   // ---- the chunk's two 4-channel blocks belong to the two half-waves: lanes 0-31 sample block 0, lanes 32-63 block 1, both at
   // taps (2 s, 2 s + 1) in K step s (tap 9 of step 4 is a zero pad: skipped at compile time).  Taps are compile-time constants

@@ -104,19 +104,6 @@ __global__ __launch_bounds__(256) void finish_kernel(const float* __restrict__ s
 }
 
 // ------------------------------------------------------------------------------------------------- cdfo_metric_partials_u8
-__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
-  __syncthreads();
-  return t;   // valid in thread 0
-}
-
 __global__ __launch_bounds__(256) void sqdiff_u8_kernel(const unsigned char* __restrict__ a, int a_pitch, long long a_fstride,
                                                         const unsigned char* __restrict__ b, int b_pitch, long long b_fstride,
                                                         int Hm, int Wm, int crop, double* __restrict__ partial) {

@@ -4,7 +4,7 @@
 // applied first, e.g. 255 for network outputs in [0,1]; `clamp` != 0 clamps to [0,255] and `round8` != 0 rounds to
 // integers like the PNG the reference writes); `crop` border pixels are dropped.  All sums are in fp64, as in the
 // reference.
-#include "common.h"
+#include "numeric.h"
 
 namespace {
 
@@ -13,19 +13,6 @@ __device__ __forceinline__ double load_px(const float* p, float scale, int clamp
   if (clamp) v = fminf(fmaxf(v, 0.f), 255.f);
   if (round8) v = rintf(v);
   return (double)v;
-}
-
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
-  __syncthreads();
-  return t;   // valid in thread 0
 }
 
 // partial[n][blockIdx.x] = sum over this block's pixels of (a - b)^2 inside the cropped region
@@ -42,7 +29,7 @@ __global__ __launch_bounds__(256) void sqdiff_kernel(const float* __restrict__ a
     const double d = load_px(a + o, scale, clamp, round8) - load_px(b + o, scale, clamp, round8);
     s += d * d;
   }
-  s = block_sum(s, sh);
+  s = block_sum_f64(s, sh);
   if (threadIdx.x == 0) partial[(long long)n * gridDim.x + blockIdx.x] = s;
 }
 
@@ -77,7 +64,7 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ a, 
     const double v1 = s11 - m1 * m1, v2 = s22 - m2 * m2, c = s12 - m1 * m2;
     acc += ((2 * m1 * m2 + C1) * (2 * c + C2)) / ((m1 * m1 + m2 * m2 + C1) * (v1 + v2 + C2));
   }
-  acc = block_sum(acc, sh);
+  acc = block_sum_f64(acc, sh);
   if (threadIdx.x == 0) partial[(long long)n * gridDim.x + blockIdx.x] = acc;
 }
 

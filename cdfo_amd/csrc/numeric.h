@@ -1,11 +1,9 @@
 // Device numerics that more than one translation unit needs: the split-precision conversions, the Philox generator, the
-// DPP row sum, the DCN power-of-two scale and the workgroup's 64-bit integer sum.  Two of them are contracts BETWEEN kernels
+// DPP row sum, the DCN power-of-two scale and the workgroup's 64-bit integer and fp64 sums.  Two of them are contracts BETWEEN kernels
 // (philox4x32_10: inference and training draw the same noise for one seed; pow2_scale: both DCN paths scale alike), so each
 // has exactly one definition here.
 #pragma once
 #include "common.h"
-
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // two fp32 -> one register of two bf16 (round to nearest even), a in the low half
 __device__ __forceinline__ unsigned pack_bf16(float a, float b) {
@@ -19,6 +17,16 @@ __device__ __forceinline__ void split4_bf16(const f32x4 v, u32x2& hi, u32x2& lo)
   hi[1] = pack_bf16(v[2], v[3]);
   lo[0] = pack_bf16(v[0] - bf16_round(v[0]), v[1] - bf16_round(v[1]));
   lo[1] = pack_bf16(v[2] - bf16_round(v[2]), v[3] - bf16_round(v[3]));
+}
+
+// eight fp32 -> the MFMA operand registers of their bf16 hi and lo parts
+__device__ __forceinline__ void split8_bf16(const f32x4 v0, const f32x4 v1, unsigned (&hi)[4], unsigned (&lo)[4]) {
+  hi[0] = pack_bf16(v0[0], v0[1]); hi[1] = pack_bf16(v0[2], v0[3]);
+  hi[2] = pack_bf16(v1[0], v1[1]); hi[3] = pack_bf16(v1[2], v1[3]);
+  lo[0] = pack_bf16(v0[0] - bf16_round(v0[0]), v0[1] - bf16_round(v0[1]));
+  lo[1] = pack_bf16(v0[2] - bf16_round(v0[2]), v0[3] - bf16_round(v0[3]));
+  lo[2] = pack_bf16(v1[0] - bf16_round(v1[0]), v1[1] - bf16_round(v1[1]));
+  lo[3] = pack_bf16(v1[2] - bf16_round(v1[2]), v1[3] - bf16_round(v1[3]));
 }
 
 // Two fp32 values -> packed fp16 hi (round to nearest) and packed fp16 lo = fp16(v - hi), four instructions per pair:
@@ -81,6 +89,20 @@ __device__ __forceinline__ long long block_sum_i64(long long v, long long* sh) {
   long long t = 0;
   if (threadIdx.x == 0)
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
+  return t;   // valid in thread 0
+}
+
+// the fp64 sum over a workgroup of whole waves (sh: one slot per wave, free again on return); the total is valid in thread 0
+__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  double t = 0.0;
+  if (threadIdx.x == 0)
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
+  __syncthreads();
   return t;   // valid in thread 0
 }
 

@@ -143,7 +143,6 @@ __global__ __launch_bounds__(256) void layernorm64_cp16hl_kernel(const float* __
                                                                  const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, long long npix, long long P,
                                                                  _Float16* __restrict__ out) {
-  typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
   const int cg = threadIdx.x & 15;
   const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + cg * 4);
   const f32x4 be = *reinterpret_cast<const f32x4*>(beta + cg * 4);
@@ -289,7 +288,6 @@ __global__ __launch_bounds__(256) void up2_kernel(const float* __restrict__ in, 
     const f32x4 v11 = *reinterpret_cast<const f32x4*>(base + ((long long)y1 * W + x1) * ldi);
     f32x4 v = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
     if (out_f16) {   // fp16 result (feeds a single-pass fp16 convolution): ldo counts halves
-      typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
       f16x4_t hv;
 #pragma unroll
       for (int k = 0; k < 4; ++k) hv[k] = (_Float16)v[k];
@@ -310,7 +308,6 @@ __global__ __launch_bounds__(256) void up2_cp16_kernel(const float* __restrict__
                                                        _Float16* __restrict__ out) {
   const int Ho = H * 2, Wo = W * 2, nc = C >> 4;
   const long long total = (long long)B * nc * (H + 1) * (W + 1) * 4;
-  typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
        i += (long long)gridDim.x * blockDim.x) {
     const int g = i & 3;

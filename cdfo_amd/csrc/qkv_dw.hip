@@ -22,7 +22,7 @@
 //     workgroup's own slot of gram[b] when the workgroup moves to another image -- no atomics anywhere, so the sums
 //     (and the forward) are bit-reproducible: q and k never reach HBM (3.7 GB written + 3.7 GB re-read per round at 56
 //     frames of 272x480).
-#include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(Q2_THREADS) void qkv_dw2_kernel(qd_args a) {
     const unsigned char* const fr_r = sF + hx * Q2_FPX + 16 * kg;
     // (d) consumer: pixels 3 pb .. 3 pb + 2, channel group cg;  (e) store: pixel tid >> 4, 16-byte part tid & 15
     const int ox = x0 + 3 * pb;
-    const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(a.out + (long long)b * H * W * a.ldo, 0, H * W * a.ldo * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(a.out + (long long)b * H * W * a.ldo, 0, H * W * a.ldo * 4, BUFFER_RSRC_WORD3);
     const int spx = tid >> 4, sq16 = tid & 15;
     f32x4 S1[3], S2[3];                                     // running depthwise sums of output rows r-1 and r (per pixel)
 #pragma unroll
@@ -549,7 +549,6 @@ __global__ __launch_bounds__(Q2_THREADS) void qkv_dw2_kernel(qd_args a) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(sV + (oy & 1) * (Q2_VROW / 4) + spx * Q2_VPX + 4 * sq16);
         const bool st = spx < Q2_TC && x0 + spx < W && oy >= ya && oy < yb;
         const unsigned vo = st ? (unsigned)(((oy * W + x0 + spx) * a.ldo + 4 * sq16) * 4) : 0x80000000u;
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r_out, (int)vo, 0, 0);
       }
       if (TL) {

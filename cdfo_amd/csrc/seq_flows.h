@@ -3,11 +3,10 @@
 // values, and the per-pixel body of cdfo_seq_flows / cdfo_seq_flows_ring: test_LD_22_FPS.py's mv2mvs (:100-122) and
 // modify_mv_for_end_frames (:200-225), bit for bit.
 #pragma once
-#include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t frame_rsrc(const unsigned char* base, int bytes) {
   // wave-uniform by construction (kernel arguments and blockIdx only); readfirstlane makes that provable, so the loads are not
@@ -15,7 +14,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t frame_rsrc(const unsigned char
   const unsigned long long p = reinterpret_cast<unsigned long long>(base);
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)p), hi = __builtin_amdgcn_readfirstlane((unsigned)(p >> 32));
   void* q = reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(q, 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+  return __builtin_amdgcn_make_buffer_rsrc(q, 0, __builtin_amdgcn_readfirstlane(bytes), BUFFER_RSRC_WORD3);
 }
 
 template <typename T> __device__ __forceinline__ float mv_to_float(T v) { return (float)v; }

@@ -81,7 +81,6 @@ __global__ __launch_bounds__(256) void small_conv3x3_kernel(const float* __restr
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[e] = act_apply(acc[e], act);
     if (out_hl) {        // fp16 hi | lo planes, chunk-planar [B][2][Ho*Wo][16]: the split-fp16 source of cdfo_conv3x3_ring
-      typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
       f16x4_t hi, lo;
 #pragma unroll
       for (int e = 0; e < 4; ++e) { hi[e] = (_Float16)acc[e]; lo[e] = (_Float16)(acc[e] - (float)hi[e]); }
@@ -294,7 +293,6 @@ __global__ __launch_bounds__(256) void small_conv16_px4_kernel(const float* __re
 #pragma unroll
       for (int e = 0; e < 4; ++e) a4[e] = act_apply(a4[e], act);
       if (out_hl) {        // fp16 hi | lo planes, chunk-planar [B][2][Ho*Wo][16]: the split-fp16 source of cdfo_conv3x3_ring
-        typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
         f16x4_t hi, lo;
 #pragma unroll
         for (int e = 0; e < 4; ++e) { hi[e] = (_Float16)a4[e]; lo[e] = (_Float16)(a4[e] - (float)hi[e]); }

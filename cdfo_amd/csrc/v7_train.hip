@@ -11,7 +11,8 @@
 
 namespace {
 
-__device__ __forceinline__ float row16_sum(float v) {
+// (a shuffle butterfly over 16 lanes: another summation order than numeric.h's DPP row16_sum, hence another name)
+__device__ __forceinline__ float shfl16_sum(float v) {
 #pragma unroll
   for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(256) void dot_plane_kernel(const float* __restrict_
   if (p >= npix) return;
   const f32x4 va = *reinterpret_cast<const f32x4*>(a + p * lda + l * 4);
   const f32x4 vb = *reinterpret_cast<const f32x4*>(b + p * ldb + l * 4);
-  const float s = row16_sum((va[0] * vb[0] + va[1] * vb[1]) + (va[2] * vb[2] + va[3] * vb[3]));
+  const float s = shfl16_sum((va[0] * vb[0] + va[1] * vb[1]) + (va[2] * vb[2] + va[3] * vb[3]));
   if (l == 0) out[p] = s;
 }
 
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(256) void softmax64_bwd_kernel(const float* __restr
   if (p >= npix) return;
   const f32x4 vr = *reinterpret_cast<const f32x4*>(r + p * ldr + l * 4);
   const f32x4 vg = *reinterpret_cast<const f32x4*>(dm + p * ldm + l * 4);
-  const float s = row16_sum((vr[0] * vg[0] + vr[1] * vg[1]) + (vr[2] * vg[2] + vr[3] * vg[3]));
+  const float s = shfl16_sum((vr[0] * vg[0] + vr[1] * vg[1]) + (vr[2] * vg[2] + vr[3] * vg[3]));
   f32x4 o;
 #pragma unroll
   for (int k = 0; k < 4; ++k) o[k] = vr[k] * (vg[k] - s);
