@@ -22,7 +22,10 @@ the frames go to the host on a copy stream into pinned buffers and the sink's po
 slot's device buffers are written again only after the event behind that copy, its pinned buffers only after the sink's tasks.  So
 nothing relies on the allocator's stream bookkeeping, no fp32 output frame outlives its chunk, and the memory held does not depend
 on the sequence's length.  ``msssim=True`` adds the luma's five-scale MS-SSIM (`metrics.msssim_components`)
-on the frames SSIM runs on; its pyramid scratch exists once, the launch stream orders its use.
+on the frames SSIM runs on; its pyramid scratch exists once, the launch stream orders its use.  ``niqe=`` a pristine model adds the
+reference's no-reference metric (metric/cal_VideoLQ.py scores every output frame with metric/niqe.py) on the chunk's 8-bit luma, with or
+without ground truth (`metrics.niqe_features_u8`): seven launches behind ``cdfo_finish_frames`` on the main
+stream, no wait for the device; the scores are formed on the host after the last chunk.
 
 Deliberate deviation: ``cal_psnr_ssim`` sends single-channel frames through ``to_y_channel``, an fp32 ``/255*255`` round
 trip, and takes fp32 means.  The metric semantics here are the project's established ones, ``oracle/metrics_ref.py``: fp64 on the
@@ -62,15 +65,22 @@ class SequenceResult(NamedTuple):
     seconds_total: float        # the whole call: reading the files, the forwards, metrics, downloads, PNG encoding
     msssim: np.ndarray = _NO_FRAMES                 # fp64 [T] with ``msssim=True`` and ground truth, else empty
     mean_msssim: float = float("nan")
+    niqe: np.ndarray = _NO_FRAMES                   # fp64 [T] with ``niqe=`` a model (ground truth or not), else empty
+    mean_niqe: float = float("nan")
 
 
 def format_log(result: SequenceResult, name: str) -> str:
-    """The reference's log line (psnr_ssim.py:481); with MS-SSIM figures, `` MS-SSIM: %.5f`` behind it."""
-    return '%s Average PSNR/SSIM: %.3f/%.5f' % (name, result.mean_psnr, result.mean_ssim) + _msssim_suffix(result)
+    """The reference's log line (psnr_ssim.py:481); with MS-SSIM figures, `` MS-SSIM: %.5f`` behind it, with NIQE figures
+    `` NIQE: %.5f`` behind that."""
+    return '%s Average PSNR/SSIM: %.3f/%.5f' % (name, result.mean_psnr, result.mean_ssim) + _msssim_suffix(result) + _niqe_suffix(result)
 
 
 def _msssim_suffix(result) -> str:
     return ' MS-SSIM: %.5f' % result.mean_msssim if len(result.msssim) else ''
+
+
+def _niqe_suffix(result) -> str:
+    return ' NIQE: %.5f' % result.mean_niqe if len(result.niqe) else ''
 
 
 def quantise_numpy(x: np.ndarray, mode: str = "trunc", peak: int = 255) -> np.ndarray:
@@ -122,6 +132,23 @@ def _check_regions(lr, gt, crop_border: int, ccrop: int) -> None:
 def _check_msssim(lr, gt, crop_border: int) -> None:
     """MS-SSIM's five scales need `metrics.msssim_min_size` samples each way inside the border (ValueError, naming the size)."""
     M.msssim_region(4 * lr.shape[0], 4 * lr.shape[1], *gt.shape, crop_border)
+
+
+def _check_niqe(lr, niqe):
+    """The pristine model of a ``niqe=`` argument (None: the metric is off), before any device work: `metrics.niqe_params`' checks;
+    ValueError above 8 bits (the reference defines the metric on 0 .. 255 integers) and for x4 frames below one 96 x 96 block."""
+    if niqe is None:
+        return None
+    params = niqe if isinstance(niqe, M.NiqeParams) else M.niqe_params(niqe)
+    if lr.dtype != torch.uint8:
+        raise ValueError(f"niqe: the metric is defined on 8-bit samples, the format's peak is {lr.peak}")
+    M.niqe_region(4 * lr.shape[0], 4 * lr.shape[1])
+    return params
+
+
+def _niqe(features: np.ndarray, params) -> np.ndarray:
+    """Per-frame NIQE from the loop's features; empty where it has none."""
+    return np.atleast_1d(M.niqe_from_features(features, params)) if len(features) else np.zeros(0, np.float64)
 
 
 def _psnr(sse: np.ndarray, shape, gt_shape, crop: int, peak: int) -> np.ndarray:
@@ -235,14 +262,17 @@ class _Slots:
 
 
 def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: int, ccrop: int, quantise: str, workers: int,
-                msssim: bool = False):
+                msssim: bool = False, niqe: bool = False):
     """The chunk loop of both evaluators.  ``lr``: the LR sequence as a frame source (its counts, shapes, dtype and peak; its frames
     come from ``load``).  ``load()`` -> (`StreamingSR`, (u, v) LR chroma planes [T,h,w] or None); it runs after the first
     ground-truth reads have been handed to the pool.  ``gt``: a frame source or None.  ``sink``: a frame sink or None.
     ``msssim``: with ground truth, `metrics.msssim_components` on the frames SSIM runs on, on the main stream; its pyramid scratch
-    exists once (every call that writes or reads it is on that stream, which orders them).
-    -> (the `StreamingSR`, sse_y int64 [T], sse_uv int64 [2,T], ssim fp64 [T], MS-SSIM components fp64 [T,5,2]); the arrays are empty
-    without ground truth (sse_uv without chroma, the components without ``msssim``).  The module's docstring has the order of events."""
+    exists once (every call that writes or reads it is on that stream, which orders them).  ``niqe``: `metrics.niqe_features_u8` on the
+    chunk's 8-bit luma, with or without ground truth, on the main stream too, its scratch held the same way; like SSIM's sums the
+    features stay on the device until the last chunk.
+    -> (the `StreamingSR`, sse_y int64 [T], sse_uv int64 [2,T], ssim fp64 [T], MS-SSIM components fp64 [T,5,2], NIQE features fp64
+    [T,nb,36]); the arrays are empty without ground truth (sse_uv without chroma, the components without ``msssim``), the features
+    without ``niqe``.  The module's docstring has the order of events."""
     T, kmax, kind, peak = lr.frames, min(chunk, lr.frames), lr.dtype, lr.peak
     has_c = lr.chroma_shape is not None
     out_y, out_c = (shape and (4 * shape[0], 4 * shape[1]) for shape in (lr.shape, lr.chroma_shape))      # None stays None
@@ -276,6 +306,7 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
             ms_scratch = None
             if msssim and gt is not None:
                 ms_scratch = M.msssim_scratch(kmax, *M.msssim_region(*out_y, *gt_y, crop), dev)
+            nq, nq_scratch = [], M.niqe_scratch(kmax, *M.niqe_region(*out_y), dev) if niqe else None
             chunks = s.iter_chunked(chunk, share_compensation)
             for c in range((T + chunk - 1) // chunk):
                 u, d = up[c], down[c]
@@ -312,6 +343,8 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
                     ssim.append(M.ssim_u8(y8, gy, crop) if kind == torch.uint8 else M.ssim_u16(y8, gy, crop, peak))
                     if ms_scratch is not None:
                         ms.append(M.msssim_components(y8, gy, crop, None if kind == torch.uint8 else peak, ms_scratch))
+                if nq_scratch is not None:
+                    nq.append(M.niqe_features_u8(y8, nq_scratch))
                 if sink is not None:
                     ready = torch.cuda.Event()
                     ready.record(main)
@@ -327,7 +360,7 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
             main.wait_stream(copy)
             host = lambda parts, dim, empty: torch.cat(parts, dim=dim).cpu().numpy() if parts else np.zeros(empty, np.int64)
             result = (s, host(sse_y, 0, 0), host(sse_c, 1, (2, 0)), host(ssim, 0, 0).astype(np.float64),
-                      host(ms, 0, (0, 5, 2)).astype(np.float64))
+                      host(ms, 0, (0, 5, 2)).astype(np.float64), host(nq, 0, (0, 1, 36)).astype(np.float64))
             torch.cuda.synchronize(dev)
     return result
 
@@ -335,7 +368,7 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
 def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] = None, save_dir: Optional[str] = None, chunk: int = 8,
                       share_compensation: bool = False, crop_border: int = 4, quantise: str = "trunc", workers: int = 8,
                       png_level: int = 6, gumbel_uniform: Optional[Sequence] = None,
-                      frame_noise: Optional[Sequence] = None, msssim: bool = False) -> SequenceResult:
+                      frame_noise: Optional[Sequence] = None, msssim: bool = False, niqe=None) -> SequenceResult:
     """Super-resolve the sequence in ``lr_dir`` / ``side_dir`` (the reference's test layout, see cdfo_amd/priors.py) with ``model`` (on a
     GPU), ``chunk`` centre frames per forward.  ``save_dir``: write every frame as an 8-bit PNG under its LR file name.  ``gt_dir``:
     per-frame PSNR / SSIM of the 8-bit frames against ``<gt_dir>/%05d.png`` over the common size less ``crop_border``.
@@ -343,10 +376,13 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
     most 16.  ``gumbel_uniform`` / ``frame_noise``: injected noise, per step or per frame, as `StreamingSR` takes it; without it the
     default mode draws per forward call, so its frames depend on the chunk size (the shared mode's never do).  ``msssim``: with
     ground truth, per-frame five-scale MS-SSIM (`metrics.msssim_u8`) as well; the region inside the border must then be at least
-    `metrics.msssim_min_size` each way."""
+    `metrics.msssim_min_size` each way.  ``niqe``: the pristine model of the no-reference metric NIQE, a path or arrays as
+    `metrics.niqe_params` takes them (the project ships no model); every output frame is then scored (`metrics.niqe_u8`, lower is
+    better), WITH OR WITHOUT ground truth; the x4 frames must hold one 96 x 96 block."""
     workers, chunk = _check_args(workers, quantise, chunk)
     t_start = time.perf_counter()
     lr = _PngSource(lr_dir)
+    nq_params = _check_niqe(lr, niqe)
     gt = sink = None
     if gt_dir is not None:
         gt = _PngSource(gt_dir, ["%05d.png" % t for t in range(lr.frames)])
@@ -361,9 +397,11 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
         return StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"], gumbel_uniform=gumbel_uniform,
                            frame_noise=frame_noise), None
 
-    s, sse, _, ssim, ms = _run_chunks(lr, load, gt, sink, chunk, share_compensation, crop_border, 0, quantise, workers, msssim)
-    psnr, ms = _psnr(sse, lr.shape, gt and gt.shape, crop_border, 255), M.msssim_from_components(ms)
-    return SequenceResult(psnr, ssim, _mean(psnr), _mean(ssim), lr.frames, s.seconds, time.perf_counter() - t_start, ms, _mean(ms))
+    s, sse, _, ssim, ms, nq = _run_chunks(lr, load, gt, sink, chunk, share_compensation, crop_border, 0, quantise, workers, msssim,
+                                          nq_params is not None)
+    psnr, ms, nq = _psnr(sse, lr.shape, gt and gt.shape, crop_border, 255), M.msssim_from_components(ms), _niqe(nq, nq_params)
+    return SequenceResult(psnr, ssim, _mean(psnr), _mean(ssim), lr.frames, s.seconds, time.perf_counter() - t_start, ms, _mean(ms),
+                          nq, _mean(nq))
 
 
 class YuvResult(NamedTuple):
@@ -382,12 +420,15 @@ class YuvResult(NamedTuple):
     seconds_total: float        # the whole call
     msssim: np.ndarray = _NO_FRAMES                 # of the luma; fp64 [T] with ``msssim=True`` and ground truth, else empty
     mean_msssim: float = float("nan")
+    niqe: np.ndarray = _NO_FRAMES                   # of the luma; fp64 [T] with ``niqe=`` a model (ground truth or not), else empty
+    mean_niqe: float = float("nan")
 
 
 def format_log_yuv(result: YuvResult, name: str) -> str:
     """`format_log` for a 4:2:0 result: the luma figures in the reference's places, then the chroma and the combined PSNR."""
     return '%s Average PSNR/SSIM: %.3f/%.5f PSNR-U/V/YUV: %.3f/%.3f/%.3f' % (
-        name, result.mean_psnr_y, result.mean_ssim_y, result.mean_psnr_u, result.mean_psnr_v, result.mean_psnr_yuv) + _msssim_suffix(result)
+        name, result.mean_psnr_y, result.mean_ssim_y, result.mean_psnr_u, result.mean_psnr_v, result.mean_psnr_yuv) + _msssim_suffix(result) + \
+        _niqe_suffix(result)
 
 
 def chroma_crop(crop_border: int, chroma: str = "420") -> int:
@@ -407,7 +448,7 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
                  save_yuv: Optional[str] = None, chunk: int = 8, share_compensation: bool = False, crop_border: int = 4,
                  quantise: str = "trunc", workers: int = 8, gumbel_uniform: Optional[Sequence] = None,
                  frame_noise: Optional[Sequence] = None, gt_size: Optional[Tuple[int, int]] = None,
-                 pix_fmt: str = "yuv420p", msssim: bool = False) -> YuvResult:
+                 pix_fmt: str = "yuv420p", msssim: bool = False, niqe=None) -> YuvResult:
     """`evaluate_sequence` on raw 8-bit I420 files (cdfo_amd/yuv.py).  ``lr_yuv``: the LR sequence, ``width`` x ``height`` (even);
     the coding priors stay in ``side_dir``.  The luma goes the way it goes there (`StreamingSR.iter_chunked`, ``finish_frames`` with the
     PSNR numerator, ``ssim_u8``).  The chroma never passes through the model: per chunk the U and V planes of its centre frames are
@@ -421,13 +462,16 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     uint16 samples and every figure is on the 0 .. 2**depth - 1 scale; the unfiltered planes and residuals in ``side_dir`` are at that
     depth too (16-bit PNGs, wider NPYs), the partition maps stay 8-bit masks.  ``gray*``: no chroma work, ``psnr_u`` / ``psnr_v`` are
     empty and ``psnr_yuv`` is ``psnr_y``.  ``yuv444p*``: chroma planes of the luma's size, their border ``crop_border``.
-    ``msssim``: as `evaluate_sequence`'s, on the luma (`metrics.msssim_u8` / `msssim_u16` with the format's peak)."""
+    ``msssim``: as `evaluate_sequence`'s, on the luma (`metrics.msssim_u8` / `msssim_u16` with the format's peak).  ``niqe``: as
+    `evaluate_sequence`'s, on the luma of 8-bit formats; above 8 bits it is a ValueError (the reference defines the metric on 0 .. 255
+    integers)."""
     fmt = parse_pix_fmt(pix_fmt)
     workers, chunk = _check_args(workers, quantise, chunk)
     t_start = time.perf_counter()
     ccrop = chroma_crop(crop_border, fmt.chroma)
     with YuvReader(lr_yuv, width, height, fmt) as head:
         lr = _YuvSource(head)
+    nq_params = _check_niqe(lr, niqe)
     gt = reader = writer = None
     try:
         if gt_yuv is not None:
@@ -447,8 +491,8 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
             return StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"],
                                gumbel_uniform=gumbel_uniform, frame_noise=frame_noise, peak=fmt.peak), lr_c
 
-        s, sse_y, sse_c, ssim, ms = _run_chunks(lr, load, gt, writer and _YuvSink(writer), chunk, share_compensation, crop_border, ccrop,
-                                                quantise, workers, msssim)
+        s, sse_y, sse_c, ssim, ms, nq = _run_chunks(lr, load, gt, writer and _YuvSink(writer), chunk, share_compensation, crop_border,
+                                                    ccrop, quantise, workers, msssim, nq_params is not None)
     finally:
         if writer is not None:
             writer.close()
@@ -457,9 +501,9 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     py = _psnr(sse_y, lr.shape, gt and gt.shape, crop_border, fmt.peak)
     pu, pv = (_psnr(e, lr.chroma_shape, gt and gt.chroma_shape, ccrop, fmt.peak) for e in sse_c)
     pyuv = psnr_yuv(py, pu, pv) if lr.chroma_shape is not None else py
-    ms = M.msssim_from_components(ms)
+    ms, nq = M.msssim_from_components(ms), _niqe(nq, nq_params)
     return YuvResult(py, pu, pv, ssim, pyuv, _mean(py), _mean(pu), _mean(pv), _mean(ssim), _mean(pyuv), lr.frames, s.seconds,
-                     time.perf_counter() - t_start, ms, _mean(ms))
+                     time.perf_counter() - t_start, ms, _mean(ms), nq, _mean(nq))
 
 
 def _write_synthetic(root: str, T: int, H: int, W: int, seed: int, put_lr, put_gt, peak: int = 255) -> str:

@@ -10,6 +10,7 @@ import ctypes as C
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib, switches
@@ -731,6 +732,91 @@ def chroma_up4(src: torch.Tensor, gt: Optional[torch.Tensor] = None, crop: int =
         raise ValueError(f"chroma_up4: src holds no pixels: {tuple(s.shape)}")
     return _write_samples("chroma_up4", s, (_vp(s), sp, C.c_longlong(ss), N, h, w), N, 4 * h, 4 * w, kind, peak, (), gt, crop, dst,
                           "src", "one plane per source plane (N")
+
+
+# ---- NIQE's block features (csrc/niqe.hip); cdfo_amd/metrics.py builds the window and the table and puts the launches together ----
+def _f64_out(out: Optional[torch.Tensor], shape: tuple, like: torch.Tensor, name: str) -> torch.Tensor:
+    """A dense fp64 destination of ``shape`` on ``like``'s device: ``out`` validated, or a new tensor."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float64, device=like.device)
+    if out.dtype != torch.float64 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != like.device:
+        raise ValueError(f"{name}: out must be a dense fp64 {list(shape)} tensor on the source's device, got {out.dtype} "
+                         f"{tuple(out.shape)} strides {out.stride()} on {out.device}")
+    return out
+
+
+def _niqe_region(name: str, H: int, W: int, rows: int, cols: int, N: int):
+    rows, cols = int(rows), int(cols)
+    if N <= 0 or not 0 < rows <= H or not 0 < cols <= W:
+        raise ValueError(f"{name}: a region of {rows} x {cols} does not lie in {N} frames of {H} x {W}")
+    return rows, cols
+
+
+def niqe_mscn(src: torch.Tensor, rows: int, cols: int, window, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src: uint8 or fp64 frames [K,H,W] (or [H,W]) on the device with contiguous rows, read in place (pitch and frame stride may
+    exceed the frame) -> fp64 [K,rows,cols]: the MSCN map of the top-left ``rows`` x ``cols``, (x - mu) / (sigma + 1) under the 7 x 7
+    ``window`` (49 fp64 values, a host array), the samples beyond the REGION's edge replaced by the edge sample."""
+    if src.dtype not in (torch.uint8, torch.float64):
+        raise ValueError(f"niqe_mscn: uint8 or fp64 frames expected, got {src.dtype}")
+    s, N, H, W, sp, ss = _sample_frames(src, "niqe_mscn: src", src.dtype)
+    rows, cols = _niqe_region("niqe_mscn", H, W, rows, cols, N)
+    win = np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
+    if win.size != 49:
+        raise ValueError(f"niqe_mscn: a window of 7 x 7 values expected, got {win.size}")
+    out = _f64_out(out, (N, rows, cols), s, "niqe_mscn")
+    entry = "cdfo_niqe_mscn_u8" if src.dtype == torch.uint8 else "cdfo_niqe_mscn_f64"
+    with on_device(s):
+        check(getattr(_lib.lib(), entry)(_vp(s), sp, C.c_longlong(ss), N, rows, cols, C.c_void_p(win.ctypes.data), _vp(out), _stream()),
+              entry)
+    return out
+
+
+def niqe_half(src: torch.Tensor, rows: int, cols: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src: uint8 frames as `niqe_mscn` takes them -> fp64 [K,rows/2,cols/2]: the top-left ``rows`` x ``cols`` (even) at half size,
+    the fixed 8 taps of include/cdfo_hip.h on x / 255 down the columns, then along the rows, times 255; not rounded."""
+    s, N, H, W, sp, ss = _sample_frames(src, "niqe_half: src", torch.uint8)
+    rows, cols = _niqe_region("niqe_half", H, W, rows, cols, N)
+    if rows % 2 or cols % 2 or min(rows, cols) < 8:
+        raise ValueError(f"niqe_half: an even region of at least 8 x 8 expected, got {rows} x {cols}")
+    out = _f64_out(out, (N, rows // 2, cols // 2), s, "niqe_half")
+    with on_device(s):
+        check(_lib.lib().cdfo_niqe_half(_vp(s), sp, C.c_longlong(ss), N, rows, cols, _vp(out), _stream()), "cdfo_niqe_half")
+    return out
+
+
+def niqe_block_sums(mscn: torch.Tensor, block: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mscn: dense fp64 [K,R,C], ``block`` divides R and C -> fp64 [K,nb,5,6]: per block (block (ih, iw) at iw * (R / block) + ih) and
+    map -- x and its four products with a circular neighbour inside the block -- the counts of negative and of positive samples, the
+    sums of squares over each, of magnitudes and of squares.  Fixed summation order: equal inputs give equal bits."""
+    block = int(block)
+    if not mscn.is_cuda or mscn.dtype != torch.float64 or mscn.dim() != 3 or not mscn.is_contiguous() or mscn.shape[0] == 0:
+        raise ValueError(f"niqe_block_sums: a dense device fp64 tensor [K,R,C] expected, got {mscn.dtype} {tuple(mscn.shape)} strides "
+                         f"{mscn.stride()}")
+    N, R, Cc = (int(v) for v in mscn.shape)
+    if not 2 <= block <= 96 or R < block or Cc < block or R % block or Cc % block:
+        raise ValueError(f"niqe_block_sums: blocks of {block} (2 .. 96) do not tile {R} x {Cc}")
+    out = _f64_out(out, (N, (R // block) * (Cc // block), 5, 6), mscn, "niqe_block_sums")
+    with on_device(mscn):
+        check(_lib.lib().cdfo_niqe_block_sums(_vp(mscn), N, R, Cc, block, _vp(out), _stream()), "cdfo_niqe_block_sums")
+    return out
+
+
+def niqe_features(sums: torch.Tensor, count: int, table: torch.Tensor, scale: int, out: torch.Tensor) -> torch.Tensor:
+    """sums: dense fp64 [K,nb,5,6] of blocks of ``count`` samples; table: fp64 [2,9801] on the device (gam, r_gam) -> the 18 features of
+    scale ``scale`` (0 or 1) of each block into its half of ``out``, dense fp64 [K,nb,36], which is returned."""
+    if not sums.is_cuda or sums.dtype != torch.float64 or sums.dim() != 4 or tuple(sums.shape[2:]) != (5, 6) or not sums.is_contiguous() \
+            or sums.shape[0] == 0 or sums.shape[1] == 0:
+        raise ValueError(f"niqe_features: dense device fp64 sums [K,nb,5,6] expected, got {sums.dtype} {tuple(sums.shape)}")
+    N, nb = int(sums.shape[0]), int(sums.shape[1])
+    if table.dtype != torch.float64 or tuple(table.shape) != (2, 9801) or not table.is_contiguous() or table.device != sums.device:
+        raise ValueError(f"niqe_features: the table must be a dense fp64 [2,9801] tensor on {sums.device}")
+    if scale not in (0, 1) or int(count) <= 0:
+        raise ValueError(f"niqe_features: scale 0 or 1 and a positive sample count expected, got {scale!r} and {count!r}")
+    out = _f64_out(out, (N, nb, 36), sums, "niqe_features")
+    with on_device(sums):
+        check(_lib.lib().cdfo_niqe_features(_vp(sums), N, nb, int(count), _vp(table), int(scale), _vp(out), _stream()),
+              "cdfo_niqe_features")
+    return out
 
 
 def stem_conv(img: torch.Tensor, img_bstride: int, B: int, H: int, W: int, w: torch.Tensor, bias: torch.Tensor,

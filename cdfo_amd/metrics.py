@@ -13,16 +13,23 @@ bit-identical to the fp64 restatement of the reference's calculate_psnr on the s
 
 ``msssim_u8`` / ``msssim_u16``: five-scale MS-SSIM of such stacks, the project's own definition (DESIGN.md section 5.000000000;
 tests/msssim_ref.py is its numpy statement).  The device leaves ten means per frame, the host combines them in fp64.
+
+``niqe_u8``: the reference's no-reference metric (metric/niqe.py) of 8-bit luma frames, against a pristine model the caller brings
+(``niqe_params``).  The device leaves 36 features per 96 x 96 block (``niqe_features_u8``), the host forms the score in fp64
+(``niqe_from_features``); DESIGN.md has the definition, tests/niqe_ref.py is its numpy statement.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from . import kernels as K
 from .kernels import _sample_frames, _stream, _vp, on_device
 
 
@@ -227,3 +234,176 @@ def msssim_u16(img1: torch.Tensor, img2: torch.Tensor, crop_border: int, peak: i
     if peak is None:
         raise ValueError("msssim_u16: uint16 samples need their peak (2**depth - 1)")
     return _msssim(img1, img2, crop_border, peak, components)
+
+
+# ---- NIQE: the reference's no-reference metric on the 8-bit luma (DESIGN.md has the definition; the kernels are in csrc/niqe.hip) ----
+NIQE_BLOCK = 96                                         # scale 1's blocks; scale 2's are 48 x 48 of the half image
+NIQE_TABLE = 9801
+_niqe_host = {}                                         # "window" and "table": built once per process
+_niqe_tables = {}                                       # the table on a device: uploaded once per process and device
+
+
+class NiqeParams(NamedTuple):
+    """The pristine model NIQE scores against: the mean [36] and covariance [36,36] of the features of natural images."""
+    mu: np.ndarray
+    cov: np.ndarray
+
+
+def niqe_params(source) -> NiqeParams:
+    """The pristine model from ``source``: a path to an ``.npz`` with the keys ``mu_prisparam`` [36] and ``cov_prisparam`` [36,36], or to
+    a MATLAB ``.mat`` file with them (the reference's niqe_modelparameters.mat; needs scipy), or a pair of arrays, or a `NiqeParams`.
+    The project ships NO model file: the published model is the reference's data, so ``source`` is always the caller's.  fp64; the
+    shapes are checked, and that the covariance is finite and symmetric."""
+    if isinstance(source, (str, os.PathLike)):
+        path = os.fspath(source)
+        if path.lower().endswith(".mat"):
+            try:
+                import scipy.io
+            except ImportError as e:
+                raise ImportError(f"{path}: reading a .mat model needs scipy; convert it to an .npz with the keys mu_prisparam and "
+                                  "cov_prisparam") from e
+            held = scipy.io.loadmat(path)
+        else:
+            with np.load(path) as f:
+                held = {k: f[k] for k in f.files}
+        missing = [k for k in ("mu_prisparam", "cov_prisparam") if k not in held]
+        if missing:
+            raise ValueError(f"{path}: no {' / '.join(missing)} in the model file")
+        mu, cov = held["mu_prisparam"], held["cov_prisparam"]
+    else:
+        mu, cov = source
+    mu, cov = np.array(mu, dtype=np.float64).reshape(-1), np.array(cov, dtype=np.float64)
+    if mu.shape != (36,) or cov.shape != (36, 36):
+        raise ValueError(f"NIQE model: a mean of 36 values and a covariance [36,36] expected, got {mu.shape} and {cov.shape}")
+    if not (np.isfinite(mu).all() and np.isfinite(cov).all()):
+        raise ValueError("NIQE model: the mean and the covariance must be finite")
+    if not np.allclose(cov, cov.T, rtol=1e-9, atol=1e-12):
+        raise ValueError("NIQE model: the covariance is not symmetric")
+    return NiqeParams(mu, cov)
+
+
+def niqe_window() -> np.ndarray:
+    """fp64 [7,7]: MATLAB's fspecial('gaussian', 7, 7/6) as the reference builds it -- exp(-(x^2 + y^2) / (2 sigma^2)), entries below
+    eps * max zeroed, normalised, then ROUNDED TO fp32 and widened, so it is no separable product."""
+    if "window" not in _niqe_host:
+        sigma = 7.0 / 6
+        y, x = np.ogrid[-3.0:4.0, -3.0:4.0]
+        h = np.exp(-(x * x + y * y) / (2.0 * sigma * sigma))
+        h[h < np.finfo(np.float64).eps * h.max()] = 0
+        h /= h.sum()
+        h = h.astype(np.float32).astype(np.float64)
+        h.setflags(write=False)
+        _niqe_host["window"] = h
+    return _niqe_host["window"]
+
+
+def niqe_table() -> np.ndarray:
+    """fp64 [2,9801]: gam, the float32 ``arange(0.2, 10.001, 0.001)`` widened, and r_gam = exp(2 lgamma(2/gam) - lgamma(1/gam) -
+    lgamma(3/gam)).  gam comes from torch's arange on the CPU, as the reference's does: it steps in fp32 inside a vector and a fifth of its
+    entries are one fp32 ulp away from float32(0.2 + 0.001 k); the alphas among the features are entries of this table."""
+    if "table" not in _niqe_host:
+        gam = torch.arange(0.2, 10 + 0.001, 0.001, dtype=torch.float32, device="cpu").numpy().astype(np.float64)
+        if gam.shape != (NIQE_TABLE,):
+            raise RuntimeError(f"the NIQE table has {gam.shape[0]} entries, {NIQE_TABLE} expected")
+        r = np.array([math.exp(2 * math.lgamma(2.0 / g) - (math.lgamma(1.0 / g) + math.lgamma(3.0 / g))) for g in gam])
+        t = np.stack([gam, r])
+        t.setflags(write=False)
+        _niqe_host["table"] = t
+    return _niqe_host["table"]
+
+
+def _niqe_table_on(device) -> torch.Tensor:
+    device = torch.device(device)
+    if device not in _niqe_tables:
+        _niqe_tables[device] = torch.from_numpy(niqe_table().copy()).to(device)
+    return _niqe_tables[device]
+
+
+def niqe_region(h: int, w: int):
+    """(rows, columns) NIQE runs over: the top-left whole 96 x 96 blocks of an h x w frame.  ValueError below one block."""
+    R, Cc = NIQE_BLOCK * (int(h) // NIQE_BLOCK), NIQE_BLOCK * (int(w) // NIQE_BLOCK)
+    if R == 0 or Cc == 0:
+        raise ValueError(f"NIQE needs at least one {NIQE_BLOCK} x {NIQE_BLOCK} block, the frames are {h} x {w}")
+    return R, Cc
+
+
+class NiqeScratch:
+    """What `niqe_features_u8` needs beside its frames, for up to ``frames`` frames with a region of ``rows`` x ``cols`` (`niqe_region`):
+    the MSCN maps of both scales, the half image and the sums.  Calls that share one must be ordered, which one stream does."""
+
+    def __init__(self, frames: int, rows: int, cols: int, device):
+        frames, rows, cols = int(frames), int(rows), int(cols)
+        if frames <= 0 or rows <= 0 or cols <= 0 or rows % NIQE_BLOCK or cols % NIQE_BLOCK:
+            raise ValueError(f"no NIQE region of {rows} x {cols} for {frames} frames: whole {NIQE_BLOCK} x {NIQE_BLOCK} blocks expected")
+        f64 = lambda n: torch.empty(n, dtype=torch.float64, device=device)
+        self.mscn1, self.half, self.mscn2 = f64(frames * rows * cols), f64(frames * rows * cols // 4), f64(frames * rows * cols // 4)
+        self.blocks = (rows // NIQE_BLOCK) * (cols // NIQE_BLOCK)
+        self.sums = f64(2 * frames * self.blocks * 30)
+        self.frames, self.rows, self.cols, self.device = frames, rows, cols, self.mscn1.device
+
+
+def niqe_scratch(n: int, rows: int, cols: int, device) -> NiqeScratch:
+    """A `NiqeScratch` for ``n`` frames: what `niqe_features_u8` makes per call unless it is handed one."""
+    return NiqeScratch(n, rows, cols, device)
+
+
+def niqe_features_u8(frames: torch.Tensor, scratch: NiqeScratch = None) -> torch.Tensor:
+    """fp64 device tensor [K,nb,36]: per frame and 96 x 96 block (block (ih, iw) at row iw * nh + ih, the reference's order) the 18
+    features of scale 1 and the 18 of scale 2.  ``frames``: uint8 [K,H,W] (or [H,W]) on the device with contiguous rows, read in place
+    over their top-left `niqe_region`.  Seven launches on the current stream; with a ``scratch`` (`niqe_scratch`, for at least K frames
+    of this region on this device) nothing here allocates beyond the result, and nothing waits for the device."""
+    a, N, H, W, _, _ = _sample_frames(frames, "frames", torch.uint8)
+    if N == 0:
+        raise ValueError("niqe_features_u8: no frames")
+    R, Cc = niqe_region(H, W)
+    if scratch is None:
+        scratch = NiqeScratch(N, R, Cc, a.device)
+    elif not isinstance(scratch, NiqeScratch) or scratch.device != a.device or scratch.frames < N or (scratch.rows, scratch.cols) != (R, Cc):
+        raise ValueError(f"scratch: a niqe_scratch for at least {N} frames of {R} x {Cc} on {a.device} expected")
+    nb, B = scratch.blocks, NIQE_BLOCK
+    with on_device(a):
+        table, window = _niqe_table_on(a.device), niqe_window()
+        out = torch.empty((N, nb, 36), dtype=torch.float64, device=a.device)
+        m1 = K.niqe_mscn(a, R, Cc, window, scratch.mscn1[:N * R * Cc].view(N, R, Cc))
+        hf = K.niqe_half(a, R, Cc, scratch.half[:N * R * Cc // 4].view(N, R // 2, Cc // 2))
+        m2 = K.niqe_mscn(hf, R // 2, Cc // 2, window, scratch.mscn2[:N * R * Cc // 4].view(N, R // 2, Cc // 2))
+        s = scratch.sums[:2 * N * nb * 30].view(2, N, nb, 5, 6)
+        K.niqe_features(K.niqe_block_sums(m1, B, s[0]), B * B, table, 0, out)
+        K.niqe_features(K.niqe_block_sums(m2, B // 2, s[1]), B * B // 4, table, 1, out)
+    return out
+
+
+def niqe_from_features(F, params) -> np.ndarray:
+    """fp64 numpy [K] from features [K,nb,36] (or [nb,36] -> a 0-d array), on the host in fp64: with mu the per-column mean over the
+    blocks that ignores NaN entries and cov the sample covariance (divisor n - 1) of the blocks WITHOUT a NaN (one such block: the
+    zero matrix), sqrt(d pinv((cov_pris + cov) / 2) d^T), d = mu_pris - mu.  NaN where no block is complete.  ``params``: what
+    `niqe_params` takes."""
+    params = params if isinstance(params, NiqeParams) else niqe_params(params)
+    F = F.detach().cpu().numpy() if isinstance(F, torch.Tensor) else np.asarray(F)
+    F = F.astype(np.float64)
+    if F.ndim not in (2, 3) or F.shape[-1] != 36 or F.shape[-2] == 0:
+        raise ValueError(f"features [K,nb,36] expected, got {F.shape}")
+    scores = np.full(F.shape[:-2], np.nan, np.float64)
+    for at in np.ndindex(*F.shape[:-2]):
+        f = F[at]
+        nan = np.isnan(f)
+        rows = f[~nan.any(axis=1)]
+        if len(rows) == 0:
+            continue
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mu = np.where(nan, 0.0, f).sum(axis=0) / (~nan).sum(axis=0)
+        cov = np.zeros((36, 36), np.float64)
+        if len(rows) > 1:
+            c = rows - rows.mean(axis=0)
+            cov = c.T @ c / (len(rows) - 1)
+        d = params.mu - mu
+        with np.errstate(invalid="ignore"):
+            scores[at] = np.sqrt(d @ np.linalg.pinv((params.cov + cov) / 2) @ d)
+    return scores
+
+
+def niqe_u8(frames: torch.Tensor, params) -> np.ndarray:
+    """Per-frame NIQE (lower is better) of uint8 [K,H,W] device frames, fp64 numpy [K] on the host: `niqe_features_u8` on the device,
+    `niqe_from_features` on the host.  ``params``: the caller's pristine model (`niqe_params`); the project ships none."""
+    params = params if isinstance(params, NiqeParams) else niqe_params(params)
+    return np.atleast_1d(niqe_from_features(niqe_features_u8(frames), params))

@@ -672,6 +672,32 @@ int cdfo_msssim_partials_u16(const unsigned short* a, int a_pitch, long long a_f
                              int b_pitch, long long b_fstride, int Hb, int Wb, int N, int crop, int peak, float* pyramid,
                              long long pyramid_bytes, double* partial, int partial_cap, int* nblocks_out, void* stream);
 
+/* ---- NIQE's block features of 8-bit luma frames (niqe.hip; cdfo_amd/metrics.py: niqe_features_u8; DESIGN.md has the definition) ----
+ * Every buffer but the frames is fp64 and 8-byte aligned (else CDFO_EALIGN); sizes, pitches and strides are in samples; K <= 65535
+ * frames per launch, all on `stream`.  The region R x C is the frames' top-left 96 floor(H/96) x 96 floor(W/96); nothing outside it is
+ * read.
+ * cdfo_niqe_mscn_u8 / _f64: dst [K][R][C] = (x - mu) / (sigma + 1), mu = sum h x and sigma = sqrt(|sum h x^2 - mu^2| + 2^-52) over the
+ *                     7 x 7 window `window` (49 doubles in HOST memory, row-major, copied into the launch), the samples beyond the
+ *                     region's edge replaced by the edge sample.  src: frame n at src + n fstride, rows at `pitch` >= C.
+ * cdfo_niqe_half:     dst [K][R/2][C/2]: x / 255.0, the taps (-3, -9, 29, 111, 111, 29, -9, -3) / 256 at the inputs 2i-3 .. 2i+4 down
+ *                     the columns, then along the rows, mirrored at the region's edge with the edge sample repeated, times 255.0.
+ *                     R and C even, at least 8.
+ * cdfo_niqe_block_sums: mscn dense [K][R][C], B x B blocks (2 <= B <= 96 divides R and C); sums [K][nb][5][6], nb = (R/B)(C/B), block
+ *                     (ih, iw) at iw (R/B) + ih: for the maps x and x * x[(i-a) mod B][(j-b) mod B], (a,b) = (0,1), (1,0), (1,1), (1,-1),
+ *                     the counts of v < 0 and v > 0, the sums of v^2 over each, of |v| and of v^2.  Fixed order, no atomics: equal
+ *                     inputs give equal bits.
+ * cdfo_niqe_features: from those sums of blocks of `count` samples and the device table (gam [CDFO_NIQE_TABLE], then r_gam
+ *                     [CDFO_NIQE_TABLE]) the 18 features of each block into features[(n nb + b) 36 + 18 scale ...], scale 0 or 1:
+ *                     the index is the first minimum of |r_gam - rn|, 0 when rn is NaN. */
+#define CDFO_NIQE_TABLE 9801
+int cdfo_niqe_mscn_u8(const unsigned char* src, int pitch, long long fstride, int K, int R, int C, const double* window, double* dst,
+                      void* stream);
+int cdfo_niqe_mscn_f64(const double* src, int pitch, long long fstride, int K, int R, int C, const double* window, double* dst,
+                       void* stream);
+int cdfo_niqe_half(const unsigned char* src, int pitch, long long fstride, int K, int R, int C, double* dst, void* stream);
+int cdfo_niqe_block_sums(const double* mscn, int K, int R, int C, int B, double* sums, void* stream);
+int cdfo_niqe_features(const double* sums, int K, int nb, int count, const double* table, int scale, double* features, void* stream);
+
 /* ---- training batches and the training loss (train_batch.hip; cdfo_amd/train_data.py, cdfo_amd/loss.py) ----
  * cdfo_train_batch:   the resident clip set -- lr, pms, hr unsigned and rms signed 8-bit [S][T][H][W] ([S][T][4H][4W] for hr), ufs
  *                     [S][T][Hu][W] with Hu >= H rows indexed from the top, mvl0 signed 8-bit [S][T][H][W][3] (a, b, ref), all dense --

@@ -5,6 +5,7 @@
     python tools/bench_evaluate.py --yuv [--size T H W] [--chunk K] [--repeats R]    the PNG path against the raw 4:2:0 path
     python tools/bench_evaluate.py --yuv --pix-fmt NAME [--size T H W] ...           evaluate_yuv at NAME against 8-bit yuv420p
     python tools/bench_evaluate.py --msssim [--yuv] [--size T H W] [--chunk K] [--repeats R]    MS-SSIM: the kernels, and the option on / off
+    python tools/bench_evaluate.py --niqe PARAMS [--yuv] [--size T H W] [--chunk K] [--repeats R]    NIQE: the kernels, and the option on / off
 
 Sequence benchmark, one process, one warm-up pass then R passes each, medians: run_chunked alone; evaluate_sequence with metrics
 only; with metrics and PNG writing at 8 and 16 workers; and the per-chunk times of the finish kernel and the two 8-bit metric
@@ -18,10 +19,13 @@ file, on 8-bit yuv420p and on NAME in the same process (the 8-bit run is the bas
 of correlated 1080 x 1920 pairs, from events; then evaluate_sequence (with --yuv: evaluate_yuv) with metrics only, ``msssim`` off and
 on in alternating passes of one process.  (Against another commit there is no switch: export that commit into a directory of its own,
 build it there, and run this tool, or a pass set of evaluate_yuv, from each tree in fresh processes in alternation on one box; DESIGN.md
-section 5.000000000 has the figures taken that way.)"""
+section 5.000000000 has the figures taken that way.)  --niqe PARAMS (a pristine model, `metrics.niqe_params`): the seven launches of
+`niqe_features_u8` beside ssim_u8 and msssim_u8 on one chunk of 1080 x 1920 frames in alternating passes, and each of its kernels
+alone, from events; then the evaluator with metrics only, ``niqe`` off and on in alternating passes of one process."""
 import os
 import sys
 import tempfile
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -257,8 +261,77 @@ def msssim():
               f"{' '.join('%.2f' % f for f in fps[True])}; median {on:.2f} ({on / off:.4f} of off)", flush=True)
 
 
+def niqe():
+    from arch.SIDECVSR_our import CVSR_V8
+    from cdfo_amd import kernels as K
+    from cdfo_amd import metrics as M
+    from cdfo_amd.evaluate import evaluate_sequence, evaluate_yuv, write_synthetic_sequence, write_synthetic_sequence_yuv
+    params = M.niqe_params(sys.argv[sys.argv.index("--niqe") + 1])
+    T, H, W = _arg("--size", 3, [64, 270, 480])
+    chunk, reps = _arg("--chunk", 1, 8), _arg("--repeats", 1, 5)
+    rs = np.random.RandomState(0)
+    a = rs.randint(0, 256, (chunk, 4 * H, 4 * W))
+    b = np.clip(a + np.rint(20 * rs.randn(*a.shape)).astype(np.int64), 0, 255)
+    a, b = torch.from_numpy(a.astype(np.uint8)).cuda(), torch.from_numpy(b.astype(np.uint8)).cuda()
+    R, Cc = M.niqe_region(4 * H, 4 * W)
+    nq, ms = M.niqe_scratch(chunk, R, Cc, a.device), M.msssim_scratch(chunk, *M.msssim_region(4 * H, 4 * W, 4 * H, 4 * W, 4), a.device)
+    forms = (("ssim_u8", lambda: M.ssim_u8(a, b, 4)), ("msssim_components", lambda: M.msssim_components(a, b, 4, None, ms)),
+             ("niqe_features_u8", lambda: M.niqe_features_u8(a, nq)))
+    times = {name: [] for name, _ in forms}
+    for name, fn in forms:
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(5):                                       # alternating forms: drift of the box falls on all alike
+        for name, fn in forms:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1))
+    med = {name: float(np.median(v)) for name, v in times.items()}
+    print(f"chunk of {chunk} frames {4 * H}x{4 * W} (NIQE region {R}x{Cc}; wrappers included, scratch held), median of 5 alternating passes: "
+          + "; ".join(f"{name} {med[name]:.3f} ms (passes {' '.join('%.3f' % x for x in times[name])})" for name, _ in forms)
+          + f": NIQE's features x{med['niqe_features_u8'] / med['ssim_u8']:.2f} of SSIM, x{med['niqe_features_u8'] / med['msssim_components']:.2f} "
+          f"of MS-SSIM's means, {med['niqe_features_u8'] / chunk:.3f} ms per frame", flush=True)
+    win, table = M.niqe_window(), M._niqe_table_on(a.device)
+    m1, hf = K.niqe_mscn(a, R, Cc, win), K.niqe_half(a, R, Cc)
+    m2 = K.niqe_mscn(hf, R // 2, Cc // 2, win)
+    s1, s2 = K.niqe_block_sums(m1, 96), K.niqe_block_sums(m2, 48)
+    out = torch.empty((chunk, s1.shape[1], 36), dtype=torch.float64, device=a.device)
+    split = (("mscn_u8", lambda: K.niqe_mscn(a, R, Cc, win, m1)), ("half", lambda: K.niqe_half(a, R, Cc, hf)),
+             ("mscn_f64", lambda: K.niqe_mscn(hf, R // 2, Cc // 2, win, m2)), ("block_sums 96", lambda: K.niqe_block_sums(m1, 96, s1)),
+             ("block_sums 48", lambda: K.niqe_block_sums(m2, 48, s2)), ("features x2", lambda: (K.niqe_features(s1, 9216, table, 0, out),
+                                                                                              K.niqe_features(s2, 2304, table, 1, out))))
+    print("the split, median of 5 each (wrapper included): " + "; ".join(f"{name} {_median_ms(fn)[0]:.3f} ms" for name, fn in split), flush=True)
+    t0 = time.perf_counter()
+    scores = M.niqe_from_features(out, params)
+    print(f"niqe_from_features on the host, {chunk} frames of {s1.shape[1]} blocks: {(time.perf_counter() - t0) * 1e3:.2f} ms "
+          f"(scores of the noise frames {scores.min():.2f} .. {scores.max():.2f})", flush=True)
+    model = CVSR_V8().cuda().eval()
+    with tempfile.TemporaryDirectory() as tmp:
+        if "--yuv" in sys.argv:
+            lr, side, gt = write_synthetic_sequence_yuv(tmp, T, H, W)
+            run = lambda on: evaluate_yuv(model, lr, W, H, side, gt_yuv=gt, chunk=chunk, niqe=params if on else None)
+        else:
+            lr, side, gt = write_synthetic_sequence(tmp, T, H, W)
+            run = lambda on: evaluate_sequence(model, lr, side, gt_dir=gt, chunk=chunk, niqe=params if on else None)
+        run(False), run(True)
+        fps = {False: [], True: []}
+        for _ in range(reps):                                # alternating passes: drift of the box falls on both alike
+            for on in (False, True):
+                r = run(on)
+                fps[on].append(r.frames / r.seconds_total)
+        off, on = float(np.median(fps[False])), float(np.median(fps[True]))
+        print(f"{'evaluate_yuv' if '--yuv' in sys.argv else 'evaluate_sequence'}, metrics only, {T} frames {H}x{W}, chunk {chunk}, end to "
+              f"end frames/s: niqe off per pass {' '.join('%.2f' % f for f in fps[False])}; median {off:.2f}; niqe on per pass "
+              f"{' '.join('%.2f' % f for f in fps[True])}; median {on:.2f} ({on / off:.4f} of off)", flush=True)
+
+
 if __name__ == "__main__":
-    if "--msssim" in sys.argv:
+    if "--niqe" in sys.argv:
+        niqe()
+    elif "--msssim" in sys.argv:
         msssim()
     elif "--ssim" in sys.argv:
         ssim_ab()
