@@ -25,7 +25,9 @@ on the sequence's length.  ``msssim=True`` adds the luma's five-scale MS-SSIM (`
 on the frames SSIM runs on; its pyramid scratch exists once, the launch stream orders its use.  ``niqe=`` a pristine model adds the
 reference's no-reference metric (metric/cal_VideoLQ.py scores every output frame with metric/niqe.py) on the chunk's 8-bit luma, with or
 without ground truth (`metrics.niqe_features_u8`): seven launches behind ``cdfo_finish_frames`` on the main
-stream, no wait for the device; the scores are formed on the host after the last chunk.
+stream, no wait for the device; the scores are formed on the host after the last chunk.  ``brisque=`` a support-vector model adds the
+reference's other live no-reference figure (metric/brisque.py) the same way (`metrics.brisque_features_u8`, DESIGN.md section
+5.00000000000000): seven launches of its own per chunk, 36 features per frame kept on the device until the last chunk.
 
 Deliberate deviation: ``cal_psnr_ssim`` sends single-channel frames through ``to_y_channel``, an fp32 ``/255*255`` round
 trip, and takes fp32 means.  The metric semantics here are the project's established ones, ``oracle/metrics_ref.py``: fp64 on the
@@ -67,12 +69,15 @@ class SequenceResult(NamedTuple):
     mean_msssim: float = float("nan")
     niqe: np.ndarray = _NO_FRAMES                   # fp64 [T] with ``niqe=`` a model (ground truth or not), else empty
     mean_niqe: float = float("nan")
+    brisque: np.ndarray = _NO_FRAMES                # fp64 [T] with ``brisque=`` a model (ground truth or not), else empty
+    mean_brisque: float = float("nan")
 
 
 def format_log(result: SequenceResult, name: str) -> str:
     """The reference's log line (psnr_ssim.py:481); with MS-SSIM figures, `` MS-SSIM: %.5f`` behind it, with NIQE figures
-    `` NIQE: %.5f`` behind that."""
-    return '%s Average PSNR/SSIM: %.3f/%.5f' % (name, result.mean_psnr, result.mean_ssim) + _msssim_suffix(result) + _niqe_suffix(result)
+    `` NIQE: %.5f`` behind that, with BRISQUE figures `` BRISQUE: %.5f`` last."""
+    return '%s Average PSNR/SSIM: %.3f/%.5f' % (name, result.mean_psnr, result.mean_ssim) + _msssim_suffix(result) + _niqe_suffix(result) + \
+        _brisque_suffix(result)
 
 
 def _msssim_suffix(result) -> str:
@@ -81,6 +86,10 @@ def _msssim_suffix(result) -> str:
 
 def _niqe_suffix(result) -> str:
     return ' NIQE: %.5f' % result.mean_niqe if len(result.niqe) else ''
+
+
+def _brisque_suffix(result) -> str:
+    return ' BRISQUE: %.5f' % result.mean_brisque if len(result.brisque) else ''
 
 
 def quantise_numpy(x: np.ndarray, mode: str = "trunc", peak: int = 255) -> np.ndarray:
@@ -149,6 +158,23 @@ def _check_niqe(lr, niqe):
 def _niqe(features: np.ndarray, params) -> np.ndarray:
     """Per-frame NIQE from the loop's features; empty where it has none."""
     return np.atleast_1d(M.niqe_from_features(features, params)) if len(features) else np.zeros(0, np.float64)
+
+
+def _check_brisque(lr, brisque):
+    """The model of a ``brisque=`` argument (None: the metric is off), before any device work: `metrics.brisque_params`' checks;
+    ValueError above 8 bits (the reference defines the metric on 0 .. 255 integers) and for x4 frames below 16 x 16."""
+    if brisque is None:
+        return None
+    params = brisque if isinstance(brisque, M.BrisqueParams) else M.brisque_params(brisque)
+    if lr.dtype != torch.uint8:
+        raise ValueError(f"brisque: the metric is defined on 8-bit samples, the format's peak is {lr.peak}")
+    M.brisque_size(4 * lr.shape[0], 4 * lr.shape[1])
+    return params
+
+
+def _brisque(features: np.ndarray, params) -> np.ndarray:
+    """Per-frame BRISQUE from the loop's features; empty where it has none."""
+    return np.atleast_1d(M.brisque_from_features(features, params)) if len(features) else np.zeros(0, np.float64)
 
 
 def _psnr(sse: np.ndarray, shape, gt_shape, crop: int, peak: int) -> np.ndarray:
@@ -262,17 +288,17 @@ class _Slots:
 
 
 def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: int, ccrop: int, quantise: str, workers: int,
-                msssim: bool = False, niqe: bool = False):
+                msssim: bool = False, niqe: bool = False, brisque: bool = False):
     """The chunk loop of both evaluators.  ``lr``: the LR sequence as a frame source (its counts, shapes, dtype and peak; its frames
     come from ``load``).  ``load()`` -> (`StreamingSR`, (u, v) LR chroma planes [T,h,w] or None); it runs after the first
     ground-truth reads have been handed to the pool.  ``gt``: a frame source or None.  ``sink``: a frame sink or None.
     ``msssim``: with ground truth, `metrics.msssim_components` on the frames SSIM runs on, on the main stream; its pyramid scratch
     exists once (every call that writes or reads it is on that stream, which orders them).  ``niqe``: `metrics.niqe_features_u8` on the
     chunk's 8-bit luma, with or without ground truth, on the main stream too, its scratch held the same way; like SSIM's sums the
-    features stay on the device until the last chunk.
+    features stay on the device until the last chunk.  ``brisque``: `metrics.brisque_features_u8` likewise, behind NIQE's launches.
     -> (the `StreamingSR`, sse_y int64 [T], sse_uv int64 [2,T], ssim fp64 [T], MS-SSIM components fp64 [T,5,2], NIQE features fp64
-    [T,nb,36]); the arrays are empty without ground truth (sse_uv without chroma, the components without ``msssim``), the features
-    without ``niqe``.  The module's docstring has the order of events."""
+    [T,nb,36], BRISQUE features fp64 [T,36]); the arrays are empty without ground truth (sse_uv without chroma, the components
+    without ``msssim``), the features without ``niqe`` / ``brisque``.  The module's docstring has the order of events."""
     T, kmax, kind, peak = lr.frames, min(chunk, lr.frames), lr.dtype, lr.peak
     has_c = lr.chroma_shape is not None
     out_y, out_c = (shape and (4 * shape[0], 4 * shape[1]) for shape in (lr.shape, lr.chroma_shape))      # None stays None
@@ -307,6 +333,7 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
             if msssim and gt is not None:
                 ms_scratch = M.msssim_scratch(kmax, *M.msssim_region(*out_y, *gt_y, crop), dev)
             nq, nq_scratch = [], M.niqe_scratch(kmax, *M.niqe_region(*out_y), dev) if niqe else None
+            bq, bq_scratch = [], M.brisque_scratch(kmax, *out_y, dev) if brisque else None
             chunks = s.iter_chunked(chunk, share_compensation)
             for c in range((T + chunk - 1) // chunk):
                 u, d = up[c], down[c]
@@ -345,6 +372,8 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
                         ms.append(M.msssim_components(y8, gy, crop, None if kind == torch.uint8 else peak, ms_scratch))
                 if nq_scratch is not None:
                     nq.append(M.niqe_features_u8(y8, nq_scratch))
+                if bq_scratch is not None:
+                    bq.append(M.brisque_features_u8(y8, bq_scratch))
                 if sink is not None:
                     ready = torch.cuda.Event()
                     ready.record(main)
@@ -360,7 +389,8 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
             main.wait_stream(copy)
             host = lambda parts, dim, empty: torch.cat(parts, dim=dim).cpu().numpy() if parts else np.zeros(empty, np.int64)
             result = (s, host(sse_y, 0, 0), host(sse_c, 1, (2, 0)), host(ssim, 0, 0).astype(np.float64),
-                      host(ms, 0, (0, 5, 2)).astype(np.float64), host(nq, 0, (0, 1, 36)).astype(np.float64))
+                      host(ms, 0, (0, 5, 2)).astype(np.float64), host(nq, 0, (0, 1, 36)).astype(np.float64),
+                      host(bq, 0, (0, 36)).astype(np.float64))
             torch.cuda.synchronize(dev)
     return result
 
@@ -368,7 +398,7 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
 def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] = None, save_dir: Optional[str] = None, chunk: int = 8,
                       share_compensation: bool = False, crop_border: int = 4, quantise: str = "trunc", workers: int = 8,
                       png_level: int = 6, gumbel_uniform: Optional[Sequence] = None,
-                      frame_noise: Optional[Sequence] = None, msssim: bool = False, niqe=None) -> SequenceResult:
+                      frame_noise: Optional[Sequence] = None, msssim: bool = False, niqe=None, brisque=None) -> SequenceResult:
     """Super-resolve the sequence in ``lr_dir`` / ``side_dir`` (the reference's test layout, see cdfo_amd/priors.py) with ``model`` (on a
     GPU), ``chunk`` centre frames per forward.  ``save_dir``: write every frame as an 8-bit PNG under its LR file name.  ``gt_dir``:
     per-frame PSNR / SSIM of the 8-bit frames against ``<gt_dir>/%05d.png`` over the common size less ``crop_border``.
@@ -378,11 +408,15 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
     ground truth, per-frame five-scale MS-SSIM (`metrics.msssim_u8`) as well; the region inside the border must then be at least
     `metrics.msssim_min_size` each way.  ``niqe``: the pristine model of the no-reference metric NIQE, a path or arrays as
     `metrics.niqe_params` takes them (the project ships no model); every output frame is then scored (`metrics.niqe_u8`, lower is
-    better), WITH OR WITHOUT ground truth; the x4 frames must hold one 96 x 96 block."""
+    better), WITH OR WITHOUT ground truth; the x4 frames must hold one 96 x 96 block.  ``brisque``: the support-vector model of the
+    no-reference metric BRISQUE, a path, the five arrays or a `metrics.BrisqueParams` (`metrics.brisque_params`; the project ships no
+    model); every output frame is then scored as well (`metrics.brisque_u8`, lower is better), with or without ground truth; the x4
+    frames must be at least 16 x 16."""
     workers, chunk = _check_args(workers, quantise, chunk)
     t_start = time.perf_counter()
     lr = _PngSource(lr_dir)
     nq_params = _check_niqe(lr, niqe)
+    bq_params = _check_brisque(lr, brisque)
     gt = sink = None
     if gt_dir is not None:
         gt = _PngSource(gt_dir, ["%05d.png" % t for t in range(lr.frames)])
@@ -397,11 +431,12 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
         return StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"], gumbel_uniform=gumbel_uniform,
                            frame_noise=frame_noise), None
 
-    s, sse, _, ssim, ms, nq = _run_chunks(lr, load, gt, sink, chunk, share_compensation, crop_border, 0, quantise, workers, msssim,
-                                          nq_params is not None)
+    s, sse, _, ssim, ms, nq, bq = _run_chunks(lr, load, gt, sink, chunk, share_compensation, crop_border, 0, quantise, workers, msssim,
+                                              nq_params is not None, bq_params is not None)
     psnr, ms, nq = _psnr(sse, lr.shape, gt and gt.shape, crop_border, 255), M.msssim_from_components(ms), _niqe(nq, nq_params)
+    bq = _brisque(bq, bq_params)
     return SequenceResult(psnr, ssim, _mean(psnr), _mean(ssim), lr.frames, s.seconds, time.perf_counter() - t_start, ms, _mean(ms),
-                          nq, _mean(nq))
+                          nq, _mean(nq), bq, _mean(bq))
 
 
 class YuvResult(NamedTuple):
@@ -422,13 +457,15 @@ class YuvResult(NamedTuple):
     mean_msssim: float = float("nan")
     niqe: np.ndarray = _NO_FRAMES                   # of the luma; fp64 [T] with ``niqe=`` a model (ground truth or not), else empty
     mean_niqe: float = float("nan")
+    brisque: np.ndarray = _NO_FRAMES                # of the luma; fp64 [T] with ``brisque=`` a model (ground truth or not), else empty
+    mean_brisque: float = float("nan")
 
 
 def format_log_yuv(result: YuvResult, name: str) -> str:
     """`format_log` for a 4:2:0 result: the luma figures in the reference's places, then the chroma and the combined PSNR."""
     return '%s Average PSNR/SSIM: %.3f/%.5f PSNR-U/V/YUV: %.3f/%.3f/%.3f' % (
         name, result.mean_psnr_y, result.mean_ssim_y, result.mean_psnr_u, result.mean_psnr_v, result.mean_psnr_yuv) + _msssim_suffix(result) + \
-        _niqe_suffix(result)
+        _niqe_suffix(result) + _brisque_suffix(result)
 
 
 def chroma_crop(crop_border: int, chroma: str = "420") -> int:
@@ -448,7 +485,7 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
                  save_yuv: Optional[str] = None, chunk: int = 8, share_compensation: bool = False, crop_border: int = 4,
                  quantise: str = "trunc", workers: int = 8, gumbel_uniform: Optional[Sequence] = None,
                  frame_noise: Optional[Sequence] = None, gt_size: Optional[Tuple[int, int]] = None,
-                 pix_fmt: str = "yuv420p", msssim: bool = False, niqe=None) -> YuvResult:
+                 pix_fmt: str = "yuv420p", msssim: bool = False, niqe=None, brisque=None) -> YuvResult:
     """`evaluate_sequence` on raw 8-bit I420 files (cdfo_amd/yuv.py).  ``lr_yuv``: the LR sequence, ``width`` x ``height`` (even);
     the coding priors stay in ``side_dir``.  The luma goes the way it goes there (`StreamingSR.iter_chunked`, ``finish_frames`` with the
     PSNR numerator, ``ssim_u8``).  The chroma never passes through the model: per chunk the U and V planes of its centre frames are
@@ -464,7 +501,7 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     empty and ``psnr_yuv`` is ``psnr_y``.  ``yuv444p*``: chroma planes of the luma's size, their border ``crop_border``.
     ``msssim``: as `evaluate_sequence`'s, on the luma (`metrics.msssim_u8` / `msssim_u16` with the format's peak).  ``niqe``: as
     `evaluate_sequence`'s, on the luma of 8-bit formats; above 8 bits it is a ValueError (the reference defines the metric on 0 .. 255
-    integers)."""
+    integers).  ``brisque``: as `evaluate_sequence`'s, with the same restriction to 8-bit formats."""
     fmt = parse_pix_fmt(pix_fmt)
     workers, chunk = _check_args(workers, quantise, chunk)
     t_start = time.perf_counter()
@@ -472,6 +509,7 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     with YuvReader(lr_yuv, width, height, fmt) as head:
         lr = _YuvSource(head)
     nq_params = _check_niqe(lr, niqe)
+    bq_params = _check_brisque(lr, brisque)
     gt = reader = writer = None
     try:
         if gt_yuv is not None:
@@ -491,8 +529,8 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
             return StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"],
                                gumbel_uniform=gumbel_uniform, frame_noise=frame_noise, peak=fmt.peak), lr_c
 
-        s, sse_y, sse_c, ssim, ms, nq = _run_chunks(lr, load, gt, writer and _YuvSink(writer), chunk, share_compensation, crop_border,
-                                                    ccrop, quantise, workers, msssim, nq_params is not None)
+        s, sse_y, sse_c, ssim, ms, nq, bq = _run_chunks(lr, load, gt, writer and _YuvSink(writer), chunk, share_compensation, crop_border,
+                                                        ccrop, quantise, workers, msssim, nq_params is not None, bq_params is not None)
     finally:
         if writer is not None:
             writer.close()
@@ -501,9 +539,9 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     py = _psnr(sse_y, lr.shape, gt and gt.shape, crop_border, fmt.peak)
     pu, pv = (_psnr(e, lr.chroma_shape, gt and gt.chroma_shape, ccrop, fmt.peak) for e in sse_c)
     pyuv = psnr_yuv(py, pu, pv) if lr.chroma_shape is not None else py
-    ms, nq = M.msssim_from_components(ms), _niqe(nq, nq_params)
+    ms, nq, bq = M.msssim_from_components(ms), _niqe(nq, nq_params), _brisque(bq, bq_params)
     return YuvResult(py, pu, pv, ssim, pyuv, _mean(py), _mean(pu), _mean(pv), _mean(ssim), _mean(pyuv), lr.frames, s.seconds,
-                     time.perf_counter() - t_start, ms, _mean(ms), nq, _mean(nq))
+                     time.perf_counter() - t_start, ms, _mean(ms), nq, _mean(nq), bq, _mean(bq))
 
 
 def _write_synthetic(root: str, T: int, H: int, W: int, seed: int, put_lr, put_gt, peak: int = 255) -> str:

@@ -819,6 +819,76 @@ def niqe_features(sums: torch.Tensor, count: int, table: torch.Tensor, scale: in
     return out
 
 
+# ---- BRISQUE's features (csrc/brisque.hip); cdfo_amd/metrics.py builds the window and the table and puts the launches together ----
+BRISQUE_STRIP = 16                                      # CDFO_BRISQUE_STRIP: rows per workgroup of `brisque_sums`
+
+
+def brisque_mscn(src: torch.Tensor, window, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src: uint8 or fp64 frames [K,H,W] (or [H,W]) on the device with contiguous rows, read in place (pitch and frame stride may
+    exceed the frame) -> fp64 [K,H,W]: the MSCN map of the whole frame, (x - mu) / (sigma + 1) under the 7 x 7 ``window`` (49 fp64
+    values, a host array) with the reference's epsilon 2^-23 under the root, the samples beyond the FRAME's edge zero."""
+    if src.dtype not in (torch.uint8, torch.float64):
+        raise ValueError(f"brisque_mscn: uint8 or fp64 frames expected, got {src.dtype}")
+    s, N, H, W, sp, ss = _sample_frames(src, "brisque_mscn: src", src.dtype)
+    if N <= 0 or H <= 0 or W <= 0:
+        raise ValueError(f"brisque_mscn: no samples in {N} frames of {H} x {W}")
+    win = np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
+    if win.size != 49:
+        raise ValueError(f"brisque_mscn: a window of 7 x 7 values expected, got {win.size}")
+    out = _f64_out(out, (N, H, W), s, "brisque_mscn")
+    entry = "cdfo_brisque_mscn_u8" if src.dtype == torch.uint8 else "cdfo_brisque_mscn_f64"
+    with on_device(s):
+        check(getattr(_lib.lib(), entry)(_vp(s), sp, C.c_longlong(ss), N, H, W, C.c_void_p(win.ctypes.data), _vp(out), _stream()), entry)
+    return out
+
+
+def brisque_half(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src: uint8 frames as `brisque_mscn` takes them, at least 8 x 8 -> fp64 [K,ceil(H/2),ceil(W/2)]: the frame at half size, the fixed
+    8 taps of include/cdfo_hip.h on x itself down the columns, then along the rows, the edge sample repeated; odd sizes are legal;
+    not rounded."""
+    s, N, H, W, sp, ss = _sample_frames(src, "brisque_half: src", torch.uint8)
+    if N <= 0 or min(H, W) < 8:
+        raise ValueError(f"brisque_half: frames of at least 8 x 8 expected, got {N} of {H} x {W}")
+    out = _f64_out(out, (N, (H + 1) // 2, (W + 1) // 2), s, "brisque_half")
+    with on_device(s):
+        check(_lib.lib().cdfo_brisque_half(_vp(s), sp, C.c_longlong(ss), N, H, W, _vp(out), _stream()), "cdfo_brisque_half")
+    return out
+
+
+def brisque_sums(mscn: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mscn: dense fp64 [K,H,W] -> fp64 [K,G,5,6], G = ceil(H / 16): per strip of 16 rows and map -- x and its four products with the
+    partner at (r, c-1), (r-1, c), (r-1, c-1), (r+1, c-1), circular over the WHOLE frame -- the counts of negative and of positive
+    samples, the sums of squares over each, of magnitudes and of squares.  G depends on the shape alone and the summation order is
+    fixed: equal inputs give equal bits on any device."""
+    if not mscn.is_cuda or mscn.dtype != torch.float64 or mscn.dim() != 3 or not mscn.is_contiguous() or mscn.shape[0] == 0 \
+            or min(mscn.shape[1:]) < 2:
+        raise ValueError(f"brisque_sums: a dense device fp64 tensor [K,H,W] of at least 2 x 2 expected, got {mscn.dtype} "
+                         f"{tuple(mscn.shape)} strides {mscn.stride()}")
+    N, H, W = (int(v) for v in mscn.shape)
+    out = _f64_out(out, (N, (H + BRISQUE_STRIP - 1) // BRISQUE_STRIP, 5, 6), mscn, "brisque_sums")
+    with on_device(mscn):
+        check(_lib.lib().cdfo_brisque_sums(_vp(mscn), N, H, W, _vp(out), _stream()), "cdfo_brisque_sums")
+    return out
+
+
+def brisque_features(partials: torch.Tensor, count: int, table: torch.Tensor, scale: int, out: torch.Tensor) -> torch.Tensor:
+    """partials: dense fp64 [K,G,5,6] of maps of ``count`` samples; table: fp64 [3,9801] on the device (gam, r_gam, r_ggd) -> the 18
+    features of scale ``scale`` (0 or 1) of each frame into its half of ``out``, dense fp64 [K,36], which is returned."""
+    if not partials.is_cuda or partials.dtype != torch.float64 or partials.dim() != 4 or tuple(partials.shape[2:]) != (5, 6) \
+            or not partials.is_contiguous() or partials.shape[0] == 0 or partials.shape[1] == 0:
+        raise ValueError(f"brisque_features: dense device fp64 partials [K,G,5,6] expected, got {partials.dtype} {tuple(partials.shape)}")
+    N, G = int(partials.shape[0]), int(partials.shape[1])
+    if table.dtype != torch.float64 or tuple(table.shape) != (3, 9801) or not table.is_contiguous() or table.device != partials.device:
+        raise ValueError(f"brisque_features: the table must be a dense fp64 [3,9801] tensor on {partials.device}")
+    if scale not in (0, 1) or int(count) <= 0:
+        raise ValueError(f"brisque_features: scale 0 or 1 and a positive sample count expected, got {scale!r} and {count!r}")
+    out = _f64_out(out, (N, 36), partials, "brisque_features")
+    with on_device(partials):
+        check(_lib.lib().cdfo_brisque_features(_vp(partials), N, G, int(count), _vp(table), int(scale), _vp(out), _stream()),
+              "cdfo_brisque_features")
+    return out
+
+
 def stem_conv(img: torch.Tensor, img_bstride: int, B: int, H: int, W: int, w: torch.Tensor, bias: torch.Tensor,
               act: int = ACT_NONE, add: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
               out2: Optional[torch.Tensor] = None):

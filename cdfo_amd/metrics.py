@@ -17,6 +17,10 @@ tests/msssim_ref.py is its numpy statement).  The device leaves ten means per fr
 ``niqe_u8``: the reference's no-reference metric (metric/niqe.py) of 8-bit luma frames, against a pristine model the caller brings
 (``niqe_params``).  The device leaves 36 features per 96 x 96 block (``niqe_features_u8``), the host forms the score in fp64
 (``niqe_from_features``); DESIGN.md has the definition, tests/niqe_ref.py is its numpy statement.
+
+``brisque_u8``: the reference's other live no-reference metric (metric/brisque.py) of such frames, with a support-vector model the
+caller brings (``brisque_params``).  The device leaves 36 features per frame (``brisque_features_u8``), the host forms the score in
+fp64 (``brisque_from_features``); DESIGN.md has the definition, tests/brisque_ref.py is its numpy statement.
 """
 from __future__ import annotations
 
@@ -407,3 +411,159 @@ def niqe_u8(frames: torch.Tensor, params) -> np.ndarray:
     `niqe_from_features` on the host.  ``params``: the caller's pristine model (`niqe_params`); the project ships none."""
     params = params if isinstance(params, NiqeParams) else niqe_params(params)
     return np.atleast_1d(niqe_from_features(niqe_features_u8(frames), params))
+
+
+# ---- BRISQUE: the reference's second no-reference metric on the 8-bit luma (DESIGN.md has the definition; csrc/brisque.hip) ----
+BRISQUE_MIN = 16                                        # the smallest frame, each way; scale 2 is then 8 x 8
+BRISQUE_TABLE = NIQE_TABLE
+_brisque_host = {}                                      # "table": built once per process (the window is NIQE's)
+_brisque_tables = {}                                    # the table on a device: uploaded once per process and device
+
+
+class BrisqueParams(NamedTuple):
+    """The model BRISQUE scores with: an RBF support-vector regression on the 36 features scaled to -1 .. 1."""
+    sv: np.ndarray                  # fp64 [n,36]
+    sv_coef: np.ndarray             # fp64 [n]
+    feature_ranges: np.ndarray      # fp64 [36,2]: (lo, hi) per feature
+    gamma: float
+    rho: float
+
+
+def brisque_params(source) -> BrisqueParams:
+    """The model from ``source``: a path to an ``.npz`` with the keys ``sv`` [n,36], ``sv_coef`` [n], ``feature_ranges`` [36,2],
+    ``gamma`` and ``rho``, or those five as a sequence, or a `BrisqueParams`.  The project ships NO model: the published one is the
+    reference's data, so ``source`` is always the caller's (tools/gen_brisque_fixture.py --model-out writes such a file from a copy
+    of the reference).  fp64; the shapes are checked, n >= 1, every number finite, hi != lo in every range."""
+    if isinstance(source, (str, os.PathLike)):
+        path = os.fspath(source)
+        with np.load(path) as f:
+            held = {k: f[k] for k in f.files}
+        missing = [k for k in BrisqueParams._fields if k not in held]
+        if missing:
+            raise ValueError(f"{path}: no {' / '.join(missing)} in the model file")
+        source = [held[k] for k in BrisqueParams._fields]
+    source = tuple(source)
+    if len(source) != 5:
+        raise ValueError(f"BRISQUE model: sv, sv_coef, feature_ranges, gamma and rho expected, got {len(source)} items")
+    sv, coef, ranges, gamma, rho = (np.array(x, dtype=np.float64) for x in source)
+    if coef.ndim == 2 and 1 in coef.shape:
+        coef = coef.reshape(-1)
+    if sv.ndim != 2 or sv.shape[1] != 36 or sv.shape[0] < 1 or coef.shape != (sv.shape[0],) or ranges.shape != (36, 2):
+        raise ValueError(f"BRISQUE model: support vectors [n,36] with n >= 1, n coefficients and ranges [36,2] expected, got {sv.shape}, "
+                         f"{coef.shape} and {ranges.shape}")
+    if gamma.size != 1 or rho.size != 1:
+        raise ValueError(f"BRISQUE model: gamma and rho are scalars, got {gamma.shape} and {rho.shape}")
+    if not all(np.isfinite(x).all() for x in (sv, coef, ranges, gamma, rho)):
+        raise ValueError("BRISQUE model: every number must be finite")
+    if (ranges[:, 0] == ranges[:, 1]).any():
+        raise ValueError("BRISQUE model: a feature range with hi == lo")
+    return BrisqueParams(sv, coef, ranges, float(gamma.reshape(())), float(rho.reshape(())))
+
+
+def brisque_window() -> np.ndarray:
+    """fp64 [7,7]: the reference's fspecial(7, 7/6) rounded to fp32 and widened -- NIQE's window (`niqe_window`)."""
+    return niqe_window()
+
+
+def brisque_table() -> np.ndarray:
+    """fp64 [3,9801]: gam and r_gam of `niqe_table`, and r_ggd = exp(lgamma(1/gam) + lgamma(3/gam) - 2 lgamma(2/gam)), the row the
+    symmetric fit of the map itself is searched in (the reference's estimate_ggd_param)."""
+    if "table" not in _brisque_host:
+        gam, r_gam = niqe_table()
+        r_ggd = np.array([math.exp(math.lgamma(1.0 / g) + math.lgamma(3.0 / g) - 2 * math.lgamma(2.0 / g)) for g in gam])
+        t = np.stack([gam, r_gam, r_ggd])
+        t.setflags(write=False)
+        _brisque_host["table"] = t
+    return _brisque_host["table"]
+
+
+def _brisque_table_on(device) -> torch.Tensor:
+    device = torch.device(device)
+    if device not in _brisque_tables:
+        _brisque_tables[device] = torch.from_numpy(brisque_table().copy()).to(device)
+    return _brisque_tables[device]
+
+
+def brisque_size(h: int, w: int):
+    """(h, w) as ints; ValueError below 16 x 16 (scale 2's half image must hold the 7 x 7 window and the 8 taps' mirror)."""
+    h, w = int(h), int(w)
+    if h < BRISQUE_MIN or w < BRISQUE_MIN:
+        raise ValueError(f"BRISQUE needs frames of at least {BRISQUE_MIN} x {BRISQUE_MIN}, got {h} x {w}")
+    return h, w
+
+
+class BrisqueScratch:
+    """What `brisque_features_u8` needs beside its frames, for up to ``frames`` frames of ``h`` x ``w``: the MSCN maps of both scales,
+    the half image and the strips' sums.  Calls that share one must be ordered, which one stream does."""
+
+    def __init__(self, frames: int, h: int, w: int, device):
+        frames = int(frames)
+        h, w = brisque_size(h, w)
+        if frames <= 0:
+            raise ValueError(f"no BRISQUE scratch for {frames} frames")
+        hh, wh = (h + 1) // 2, (w + 1) // 2
+        f64 = lambda n: torch.empty(n, dtype=torch.float64, device=device)
+        self.mscn1, self.half, self.mscn2 = f64(frames * h * w), f64(frames * hh * wh), f64(frames * hh * wh)
+        self.strips = ((h + K.BRISQUE_STRIP - 1) // K.BRISQUE_STRIP, (hh + K.BRISQUE_STRIP - 1) // K.BRISQUE_STRIP)
+        self.sums = f64(frames * sum(self.strips) * 30)
+        self.frames, self.h, self.w, self.device = frames, h, w, self.mscn1.device
+
+
+def brisque_scratch(n: int, h: int, w: int, device) -> BrisqueScratch:
+    """A `BrisqueScratch` for ``n`` frames: what `brisque_features_u8` makes per call unless it is handed one."""
+    return BrisqueScratch(n, h, w, device)
+
+
+def brisque_features_u8(frames: torch.Tensor, scratch: BrisqueScratch = None) -> torch.Tensor:
+    """fp64 device tensor [K,36]: per frame the 18 features of scale 1 and the 18 of scale 2 (half size).  ``frames``: uint8 [K,H,W]
+    (or [H,W]) on the device with contiguous rows, read in place, at least 16 x 16.  Seven launches on the current stream whatever K
+    is; with a ``scratch`` (`brisque_scratch`, for at least K frames of this size on this device) nothing here allocates beyond the
+    result, and nothing waits for the device.  A frame whose fit is undefined (all samples equal; a product map with no sample of one
+    sign) gets NaN among its features, where the reference asserts; the other frames of the call are untouched by it."""
+    a, N, H, W, _, _ = _sample_frames(frames, "frames", torch.uint8)
+    if N == 0:
+        raise ValueError("brisque_features_u8: no frames")
+    H, W = brisque_size(H, W)
+    if scratch is None:
+        scratch = BrisqueScratch(N, H, W, a.device)
+    elif not isinstance(scratch, BrisqueScratch) or scratch.device != a.device or scratch.frames < N or (scratch.h, scratch.w) != (H, W):
+        raise ValueError(f"scratch: a brisque_scratch for at least {N} frames of {H} x {W} on {a.device} expected")
+    Hh, Wh = (H + 1) // 2, (W + 1) // 2
+    g1, g2 = scratch.strips
+    with on_device(a):
+        table, window = _brisque_table_on(a.device), brisque_window()
+        out = torch.empty((N, 36), dtype=torch.float64, device=a.device)
+        m1 = K.brisque_mscn(a, window, scratch.mscn1[:N * H * W].view(N, H, W))
+        hf = K.brisque_half(a, scratch.half[:N * Hh * Wh].view(N, Hh, Wh))
+        m2 = K.brisque_mscn(hf, window, scratch.mscn2[:N * Hh * Wh].view(N, Hh, Wh))
+        s1 = scratch.sums[:N * g1 * 30].view(N, g1, 5, 6)
+        s2 = scratch.sums[N * g1 * 30:N * (g1 + g2) * 30].view(N, g2, 5, 6)
+        K.brisque_features(K.brisque_sums(m1, s1), H * W, table, 0, out)
+        K.brisque_features(K.brisque_sums(m2, s2), Hh * Wh, table, 1, out)
+    return out
+
+
+def brisque_from_features(F, params) -> np.ndarray:
+    """fp64 numpy [K] from features [K,36] (or [36] -> a 0-d array), on the host in fp64: z = -1 + 2 (f - lo) / (hi - lo), then
+    sum_i coef_i exp(-gamma |z - sv_i|^2) - rho (lower is better).  NaN where a feature is NaN.  ``params``: what `brisque_params`
+    takes."""
+    params = params if isinstance(params, BrisqueParams) else brisque_params(params)
+    F = F.detach().cpu().numpy() if isinstance(F, torch.Tensor) else np.asarray(F)
+    F = F.astype(np.float64)
+    if F.ndim not in (1, 2) or F.shape[-1] != 36:
+        raise ValueError(f"features [K,36] expected, got {F.shape}")
+    lo, hi = params.feature_ranges[:, 0], params.feature_ranges[:, 1]
+    scores = np.full(F.shape[:-1], np.nan, np.float64)
+    for at in np.ndindex(*F.shape[:-1]):
+        z = -1.0 + 2.0 * (F[at] - lo) / (hi - lo)
+        d = ((z[None, :] - params.sv) ** 2).sum(axis=1)
+        scores[at] = (params.sv_coef * np.exp(-params.gamma * d)).sum() - params.rho
+    return scores
+
+
+def brisque_u8(frames: torch.Tensor, params) -> np.ndarray:
+    """Per-frame BRISQUE (lower is better) of uint8 [K,H,W] device frames, fp64 numpy [K] on the host: `brisque_features_u8` on the
+    device, `brisque_from_features` on the host.  ``params``: the caller's model (`brisque_params`), checked before any device work;
+    the project ships none."""
+    params = params if isinstance(params, BrisqueParams) else brisque_params(params)
+    return np.atleast_1d(brisque_from_features(brisque_features_u8(frames), params))

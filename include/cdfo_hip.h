@@ -698,6 +698,34 @@ int cdfo_niqe_half(const unsigned char* src, int pitch, long long fstride, int K
 int cdfo_niqe_block_sums(const double* mscn, int K, int R, int C, int B, double* sums, void* stream);
 int cdfo_niqe_features(const double* sums, int K, int nb, int count, const double* table, int scale, double* features, void* stream);
 
+/* ---- BRISQUE's 36 features of 8-bit luma frames (brisque.hip; cdfo_amd/metrics.py: brisque_features_u8; DESIGN.md has the definition) ----
+ * NIQE's sibling over the WHOLE H x W frame.  Every buffer but the frames is fp64 and 8-byte aligned (else CDFO_EALIGN); sizes, pitches
+ * and strides are in samples; K <= 65535 frames per launch, all on `stream`.
+ * cdfo_brisque_mscn_u8 / _f64: dst [K][H][W] = (x - mu) / (sigma + 1), mu = sum h x and sigma = sqrt(|sum h x^2 - mu^2| + 2^-23) over
+ *                     the 7 x 7 window `window` (49 doubles in HOST memory, row-major, copied into the launch), the samples beyond the
+ *                     FRAME's edge ZERO.  src: frame n at src + n fstride, rows at `pitch` >= W.
+ * cdfo_brisque_half:  dst [K][ceil(H/2)][ceil(W/2)]: the taps (-3, -9, 29, 111, 111, 29, -9, -3) / 256 on x itself at the inputs
+ *                     2i-3 .. 2i+4 down the columns, then along the rows, mirrored at the frame's edge with the edge sample repeated;
+ *                     not rounded.  H and W at least 8, odd sizes included.
+ * cdfo_brisque_sums:  mscn dense [K][H][W] (H, W >= 2); partials [K][G][5][6], G = ceil(H / CDFO_BRISQUE_STRIP), strip g the rows
+ *                     16 g .. 16 g + 15: for the maps x and x * x[(i-a) mod H][(j-b) mod W], (a,b) = (0,1), (1,0), (1,1), (-1,1), the
+ *                     counts of v < 0 and v > 0, the sums of v^2 over each, of |v| and of v^2.  G depends on the shape alone, the
+ *                     order is fixed and there are no atomics: equal inputs give equal bits on any device.
+ * cdfo_brisque_features: adds the G strips in index order and writes, from those sums over `count` = H W samples and the device table
+ *                     (gam, r_gam, r_ggd, CDFO_BRISQUE_TABLE entries each), the 18 features of each frame into
+ *                     features[n 36 + 18 scale ...], scale 0 or 1: the map's symmetric fit (first minimum of |r_ggd - rho|), its four
+ *                     products' asymmetric fits (|r_gam - rn|); index 0 where the searched value is NaN. */
+#define CDFO_BRISQUE_TABLE 9801
+#define CDFO_BRISQUE_STRIP 16
+int cdfo_brisque_mscn_u8(const unsigned char* src, int pitch, long long fstride, int K, int H, int W, const double* window, double* dst,
+                         void* stream);
+int cdfo_brisque_mscn_f64(const double* src, int pitch, long long fstride, int K, int H, int W, const double* window, double* dst,
+                          void* stream);
+int cdfo_brisque_half(const unsigned char* src, int pitch, long long fstride, int K, int H, int W, double* dst, void* stream);
+int cdfo_brisque_sums(const double* mscn, int K, int H, int W, double* partials, void* stream);
+int cdfo_brisque_features(const double* partials, int K, int G, int count, const double* table, int scale, double* features,
+                          void* stream);
+
 /* ---- training batches and the training loss (train_batch.hip; cdfo_amd/train_data.py, cdfo_amd/loss.py) ----
  * cdfo_train_batch:   the resident clip set -- lr, pms, hr unsigned and rms signed 8-bit [S][T][H][W] ([S][T][4H][4W] for hr), ufs
  *                     [S][T][Hu][W] with Hu >= H rows indexed from the top, mvl0 signed 8-bit [S][T][H][W][3] (a, b, ref), all dense --

@@ -6,6 +6,7 @@
     python tools/bench_evaluate.py --yuv --pix-fmt NAME [--size T H W] ...           evaluate_yuv at NAME against 8-bit yuv420p
     python tools/bench_evaluate.py --msssim [--yuv] [--size T H W] [--chunk K] [--repeats R]    MS-SSIM: the kernels, and the option on / off
     python tools/bench_evaluate.py --niqe PARAMS [--yuv] [--size T H W] [--chunk K] [--repeats R]    NIQE: the kernels, and the option on / off
+    python tools/bench_evaluate.py --brisque MODEL [--niqe PARAMS] [--yuv] [--size T H W] [--chunk K] [--repeats R]    BRISQUE likewise
 
 Sequence benchmark, one process, one warm-up pass then R passes each, medians: run_chunked alone; evaluate_sequence with metrics
 only; with metrics and PNG writing at 8 and 16 workers; and the per-chunk times of the finish kernel and the two 8-bit metric
@@ -21,7 +22,9 @@ on in alternating passes of one process.  (Against another commit there is no sw
 build it there, and run this tool, or a pass set of evaluate_yuv, from each tree in fresh processes in alternation on one box; DESIGN.md
 section 5.000000000 has the figures taken that way.)  --niqe PARAMS (a pristine model, `metrics.niqe_params`): the seven launches of
 `niqe_features_u8` beside ssim_u8 and msssim_u8 on one chunk of 1080 x 1920 frames in alternating passes, and each of its kernels
-alone, from events; then the evaluator with metrics only, ``niqe`` off and on in alternating passes of one process."""
+alone, from events; then the evaluator with metrics only, ``niqe`` off and on in alternating passes of one process.  --brisque MODEL
+(a support-vector model, `metrics.brisque_params`): the seven launches of `brisque_features_u8` beside ssim_u8 (and, with --niqe
+PARAMS, `niqe_features_u8`) on the same chunk, each of its kernels alone, and the evaluator with ``brisque`` off and on."""
 import os
 import sys
 import tempfile
@@ -328,8 +331,79 @@ def niqe():
               f"{' '.join('%.2f' % f for f in fps[True])}; median {on:.2f} ({on / off:.4f} of off)", flush=True)
 
 
-if __name__ == "__main__":
+def brisque():
+    from arch.SIDECVSR_our import CVSR_V8
+    from cdfo_amd import kernels as K
+    from cdfo_amd import metrics as M
+    from cdfo_amd.evaluate import evaluate_sequence, evaluate_yuv, write_synthetic_sequence, write_synthetic_sequence_yuv
+    params = M.brisque_params(sys.argv[sys.argv.index("--brisque") + 1])
+    T, H, W = _arg("--size", 3, [64, 270, 480])
+    chunk, reps = _arg("--chunk", 1, 8), _arg("--repeats", 1, 5)
+    rs = np.random.RandomState(0)
+    a = rs.randint(0, 256, (chunk, 4 * H, 4 * W))
+    b = np.clip(a + np.rint(20 * rs.randn(*a.shape)).astype(np.int64), 0, 255)
+    a, b = torch.from_numpy(a.astype(np.uint8)).cuda(), torch.from_numpy(b.astype(np.uint8)).cuda()
+    bq = M.brisque_scratch(chunk, 4 * H, 4 * W, a.device)
+    forms = [("ssim_u8", lambda: M.ssim_u8(a, b, 4)), ("brisque_features_u8", lambda: M.brisque_features_u8(a, bq))]
     if "--niqe" in sys.argv:
+        nq = M.niqe_scratch(chunk, *M.niqe_region(4 * H, 4 * W), a.device)
+        forms.insert(1, ("niqe_features_u8", lambda: M.niqe_features_u8(a, nq)))
+    times = {name: [] for name, _ in forms}
+    for name, fn in forms:
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(5):                                       # alternating forms: drift of the box falls on all alike
+        for name, fn in forms:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1))
+    med = {name: float(np.median(v)) for name, v in times.items()}
+    print(f"chunk of {chunk} frames {4 * H}x{4 * W} (wrappers included, scratch held), median of 5 alternating passes: "
+          + "; ".join(f"{name} {med[name]:.3f} ms (passes {' '.join('%.3f' % x for x in times[name])})" for name, _ in forms)
+          + f": BRISQUE's features x{med['brisque_features_u8'] / med['ssim_u8']:.2f} of SSIM, {med['brisque_features_u8'] / chunk:.3f} ms "
+          "per frame", flush=True)
+    win, table = M.brisque_window(), M._brisque_table_on(a.device)
+    m1, hf = K.brisque_mscn(a, win), K.brisque_half(a)
+    m2 = K.brisque_mscn(hf, win)
+    s1, s2 = K.brisque_sums(m1), K.brisque_sums(m2)
+    out = torch.empty((chunk, 36), dtype=torch.float64, device=a.device)
+    n1, n2 = m1.shape[1] * m1.shape[2], m2.shape[1] * m2.shape[2]
+    split = (("mscn_u8", lambda: K.brisque_mscn(a, win, m1)), ("half", lambda: K.brisque_half(a, hf)),
+             ("mscn_f64", lambda: K.brisque_mscn(hf, win, m2)), ("sums scale 1", lambda: K.brisque_sums(m1, s1)),
+             ("sums scale 2", lambda: K.brisque_sums(m2, s2)), ("features x2", lambda: (K.brisque_features(s1, n1, table, 0, out),
+                                                                                       K.brisque_features(s2, n2, table, 1, out))))
+    print("the split, median of 5 each (wrapper included): " + "; ".join(f"{name} {_median_ms(fn)[0]:.3f} ms" for name, fn in split), flush=True)
+    t0 = time.perf_counter()
+    scores = M.brisque_from_features(out, params)
+    print(f"brisque_from_features on the host, {chunk} frames, {len(params.sv)} support vectors: {(time.perf_counter() - t0) * 1e3:.2f} ms "
+          f"(scores of the noise frames {scores.min():.2f} .. {scores.max():.2f})", flush=True)
+    model = CVSR_V8().cuda().eval()
+    with tempfile.TemporaryDirectory() as tmp:
+        if "--yuv" in sys.argv:
+            lr, side, gt = write_synthetic_sequence_yuv(tmp, T, H, W)
+            run = lambda on: evaluate_yuv(model, lr, W, H, side, gt_yuv=gt, chunk=chunk, brisque=params if on else None)
+        else:
+            lr, side, gt = write_synthetic_sequence(tmp, T, H, W)
+            run = lambda on: evaluate_sequence(model, lr, side, gt_dir=gt, chunk=chunk, brisque=params if on else None)
+        run(False), run(True)
+        fps = {False: [], True: []}
+        for _ in range(reps):                                # alternating passes: drift of the box falls on both alike
+            for on in (False, True):
+                r = run(on)
+                fps[on].append(r.frames / r.seconds_total)
+        off, on = float(np.median(fps[False])), float(np.median(fps[True]))
+        print(f"{'evaluate_yuv' if '--yuv' in sys.argv else 'evaluate_sequence'}, metrics only, {T} frames {H}x{W}, chunk {chunk}, end to "
+              f"end frames/s: brisque off per pass {' '.join('%.2f' % f for f in fps[False])}; median {off:.2f}; brisque on per pass "
+              f"{' '.join('%.2f' % f for f in fps[True])}; median {on:.2f} ({on / off:.4f} of off)", flush=True)
+
+
+if __name__ == "__main__":
+    if "--brisque" in sys.argv:
+        brisque()
+    elif "--niqe" in sys.argv:
         niqe()
     elif "--msssim" in sys.argv:
         msssim()
