@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
       for (int t = 0; t < 9; ++t) s += v[t] * wr[t][j];
       o[j] = act_apply(s, act);
     }
-    *reinterpret_cast<f32x4*>(out + p * ldo + cg * 4) = o;
+    if (out) *reinterpret_cast<f32x4*>(out + p * ldo + cg * 4) = o;     // null: only out2 = result + add is wanted
     if (out2) {
       const f32x4 ad = *reinterpret_cast<const f32x4*>(add + p * lda + cg * 4);
       *reinterpret_cast<f32x4*>(out2 + p * ldo2 + cg * 4) = o + ad;
@@ -489,9 +489,9 @@ inline int grid_for(long long threads) {
 extern "C" int cdfo_stem_conv(const float* img, long long img_bstride, const float* w, const float* bias, int B, int H,
                               int W, int act, float* out, int ldo, const float* add, int lda, float* out2, int ldo2,
                               void* stream) {
-  if (B <= 0 || H <= 0 || W <= 0 || ldo % 4 || (out2 && (!add || lda % 4 || ldo2 % 4))) return CDFO_EINVAL;
+  if (B <= 0 || H <= 0 || W <= 0 || ldo % 4 || (out2 && (!add || lda % 4 || ldo2 % 4)) || (!out && !out2)) return CDFO_EINVAL;
   if (!aligned16(out) || (out2 && (!aligned16(out2) || !aligned16(add)))) return CDFO_EALIGN;
-  CdfoProfScope prof(static_cast<hipStream_t>(stream), KID_STEM, 2.0*9*64*(double)B*H*W, 4.0*(double)B*H*W*(1+64+(out2?128:0)));
+  CdfoProfScope prof(static_cast<hipStream_t>(stream), KID_STEM, 2.0*9*64*(double)B*H*W, 4.0*(double)B*H*W*(1+(out?64:0)+(out2?128:0)));
   hipLaunchKernelGGL(stem_conv_kernel, dim3(grid_for((long long)B * H * W * 16)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), img, img_bstride, w, bias, B, H, W, act, out, ldo, add, lda, out2,
                      ldo2);

@@ -156,7 +156,10 @@ class CVSR_V8(nn.Module):
         self.attn_pv_single = not switches.get("CDFO_ATTN_PV3")    # see _rdab (developer A/B: CDFO_ATTN_PV3=1 -> three passes)
         # see _rdab (developer A/B: CDFO_RDAB_FUSED=0 -> input_conv and the mask kernel as two launches, every V operand fp32)
         self.rdab_fused = switches.get("CDFO_RDAB_FUSED")
-        self.neighbour_group = 0        # frames per neighbour group: 0 = auto = 3
+        # the one-channel prior planes stay one-channel inside their consumers (see _compensate: the mask statistics straight from
+        # the residual maps; developer A/B: CDFO_PRIOR_STEMS=0 -> du0 written by the stem kernel and read back by a convolution)
+        self.prior_stems = switches.get("CDFO_PRIOR_STEMS")
+        self.neighbour_group = 0       # frames per neighbour group: 0 = auto = 3
         # cached-feature call on one sequence (B = 1): the group of frames 0-2 (cached features only) starts beside the new
         # frame's feature extraction instead of behind it (see _forward)
         self.overlap_new_frame = switches.get("CDFO_OVERLAP_NEW")
@@ -302,6 +305,8 @@ class CVSR_V8(nn.Module):
         # conv_du_re.2 (3x3, stride 2, pad 2) over the space-to-depth form of its input [H/2+1, W/2+1, 4*64] (written that way by
         # the stem kernel): a stride-1 pad-1 convolution with a per-chunk tap mask (K.pack_conv_s2p2_s2d)
         w["RDAB.conv_du_re.2_s2d"] = K.pack_conv_s2p2_s2d(sd["RDAB.conv_du_re.2.weight"], sd["RDAB.conv_du_re.2.bias"])
+        # ... and the same weights as bf16 hi | lo for K.rdab_stats, which forms du0 in registers and leaves only the channel sums
+        w["RDAB.conv_du_re.2_stats"] = K.pack_rdab_stats(sd["RDAB.conv_du_re.2.weight"])
         w[fe + "side_to_feaoneUDSA.body.0_n16"] = K.pack_conv_n16(sd[fe + "side_to_feaoneUDSA.body.0.weight"])
         w["udsa_head"] = K.pack_udsa_head(sd[fe + "side_to_feaoneUDSA.body.0.weight"], sd[fe + "side_to_feaoneUDSA.body.0.bias"],
                                           sd["conv_second.weight"], sd["conv_second.bias"])
@@ -398,19 +403,23 @@ class CVSR_V8(nn.Module):
                 x1 = self._conv(ln, w[p + "conv"], pad=1, res1=x1, res2=x2, exact=True)
         return x1
 
-    def _rdab(self, w, du0, x, noises):
+    def _rdab(self, w, du0, x, noises, stats=None):
         """LLongRangAttention (arch.py:2179-2249) on a GROUP of neighbour frames at once: du0 / x are [G*B,H,W,64] (neighbour
         major; du0 = relu(conv_du_re.0(res)) of the module's residual-map input in space-to-depth form, computed by the stem
-        kernel), `noises` one
+        kernel -- or None with `stats`, the mask statistics that K.rdab_stats formed from the residual maps), `noises` one
         entry per neighbour -- the module's weights are shared by all neighbours, only the noise draw (and with it the mask
         kernel's launch) is per neighbour."""
         raw = w["raw"]
         GB, H, W, _ = x.shape
         G = len(noises)
         B = GB // G
-        t = self._conv(du0, w["RDAB.conv_du_re.2_s2d"], pad=1, act=K.ACT_RELU, exact=True)     # [GB, H/2+1, W/2+1, 64]
-        part, n = K.chan_sum_partial(t)
-        vmax = K.vec_mlp(part, n, t.shape[1] * t.shape[2], raw["RDAB.conv_du_re2.0.weight"],
+        if stats is not None:      # (partials, slots, pixel count) of K.rdab_stats: du0 and t were never written
+            part, n, count = stats
+        else:
+            t = self._conv(du0, w["RDAB.conv_du_re.2_s2d"], pad=1, act=K.ACT_RELU, exact=True)     # [GB, H/2+1, W/2+1, 64]
+            part, n = K.chan_sum_partial(t)
+            count = t.shape[1] * t.shape[2]
+        vmax = K.vec_mlp(part, n, count, raw["RDAB.conv_du_re2.0.weight"],
                          raw["RDAB.conv_du_re2.0.bias"], 64, K.ACT_RELU)
         # fp16x2 (default): the probabilities-times-values product of the three attentions on single-fp16 operands (modes 20-22:
         # error <= 2^-11 max|v|, measured ~1e-5 |v|; the scores keep their three split-fp16 passes); fp32-grade modes: all three passes
@@ -1094,12 +1103,21 @@ class CVSR_V8(nn.Module):
         M, H, W, _ = fea.shape
         dev = fea.device
         fea_com = K.empty_act(M, H, W, NF, dev)
-        du0 = K.empty_act(M, H // 2 + 1, W // 2 + 1, 4 * NF, dev)       # space-to-depth, + one zero row / column
-        du0[:, H // 2].zero_()
-        du0[:, :, W // 2].zero_()
-        for rms, bstride, sl in stems:
-            K.stem_conv2(rms, bstride, sl.stop - sl.start, H, W, raw["conv_expand_rms.weight"], raw["conv_expand_rms.bias"], fea[sl],
-                         fea_com[sl], w["rms_du0"][0], w["rms_du0"][1], K.ACT_RELU, du0[sl], s2dB=True)
+        du0 = stats = None
+        if self.prior_stems and self.precision != "f32" and not self.istraining and K.rdab_stats_ok(H, W):
+            # du0 has one consumer, a convolution whose result has one consumer, the global average pool: K.rdab_stats goes from the
+            # residual maps to the pool's partial sums, and the stem only adds conv_expand_rms(rms) to the features
+            stats = self._mask_stats(w, stems, M, H, W)
+            for rms, bstride, sl in stems:
+                K.stem_conv(rms, bstride, sl.stop - sl.start, H, W, raw["conv_expand_rms.weight"], raw["conv_expand_rms.bias"],
+                            add=fea[sl], out2=fea_com[sl], write_out=False)
+        else:
+            du0 = K.empty_act(M, H // 2 + 1, W // 2 + 1, 4 * NF, dev)       # space-to-depth, + one zero row / column
+            du0[:, H // 2].zero_()
+            du0[:, :, W // 2].zero_()
+            for rms, bstride, sl in stems:
+                K.stem_conv2(rms, bstride, sl.stop - sl.start, H, W, raw["conv_expand_rms.weight"], raw["conv_expand_rms.bias"],
+                             fea[sl], fea_com[sl], w["rms_du0"][0], w["rms_du0"][1], K.ACT_RELU, du0[sl], s2dB=True)
         noises = []
         for k, draw in enumerate(draws):
             if noise is None:
@@ -1112,11 +1130,31 @@ class CVSR_V8(nn.Module):
                 noises.append(("rng", self._noise_seed, draw, cap))
             else:
                 noises.append(noise[k].to(device=dev, dtype=torch.float32).contiguous())
-        x_n = self._rdab(w, du0, fea_com, noises)
+        x_n = self._rdab(w, du0, fea_com, noises, stats)
         fea_i = self._conv([fea, x_n], w["conv_expand_fea_r"], pad=1, inner=self.fea_r_single_pass)
         if keep is not None:
-            keep.extend([du0, fea_com, noises, x_n, fea_i])
+            keep.extend([du0, stats, fea_com, noises, x_n, fea_i])
         return fea_i, x_n
+
+    @staticmethod
+    def _mask_stats(w, stems, M, H, W):
+        """K.rdab_stats over the stems of `_compensate` (M images in all): one launch where the stems' planes lie at one stride
+        behind each other (consecutive slots of one [B,1,7,H,W] tensor), else one launch per stem.  Returns (partials, slots,
+        pixel count)."""
+        args = (*w["rms_du0"], w["RDAB.conv_du_re.2_stats"], w["raw"]["RDAB.conv_du_re.2.bias"])
+        v0, s_b, sl0 = stems[0]
+        Bi = sl0.stop - sl0.start
+        step = (stems[1][0].data_ptr() - v0.data_ptr()) // 4 if len(stems) > 1 else 0
+        if step >= 0 and all(v.untyped_storage().data_ptr() == v0.untyped_storage().data_ptr() and bs == s_b
+                             and (sl.start, sl.stop) == (k * Bi, (k + 1) * Bi) and v.data_ptr() == v0.data_ptr() + 4 * k * step
+                             for k, (v, bs, sl) in enumerate(stems)):
+            return K.rdab_stats(v0, Bi, s_b, step, M, H, W, *args)
+        count = (H // 2 + 1) * (W // 2 + 1)
+        n = K.nchunks_for(count)
+        part = torch.empty((M, n, 64), dtype=torch.float32, device=v0.device)
+        for v, bs, sl in stems:
+            K.rdab_stats(v, sl.stop - sl.start, bs, 0, sl.stop - sl.start, H, W, *args, out=part[sl])
+        return part, n, count
 
     def _align_group(self, w, idxs, xcG, ufs, mvs1, keep, extra=None, frames=None):
         """The alignment half of a neighbour pipeline for the slots `idxs` (consecutive): the partition-map stem per slot and the

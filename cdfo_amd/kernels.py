@@ -891,10 +891,14 @@ def brisque_features(partials: torch.Tensor, count: int, table: torch.Tensor, sc
 
 def stem_conv(img: torch.Tensor, img_bstride: int, B: int, H: int, W: int, w: torch.Tensor, bias: torch.Tensor,
               act: int = ACT_NONE, add: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-              out2: Optional[torch.Tensor] = None):
+              out2: Optional[torch.Tensor] = None, write_out: bool = True):
     """img: any fp32 device tensor whose element [b][y][x] sits at data_ptr + (b*img_bstride + y*W + x)*4.
-    out / out2: optional dense [B,H,W,64] destinations (slices of a larger batch)."""
-    if out is None:
+    out / out2: optional dense [B,H,W,64] destinations (slices of a larger batch).  write_out=False (with add): only
+    out2 = conv + add is written and returned."""
+    if not write_out:
+        if add is None or out is not None:
+            raise ValueError("stem_conv: write_out=False needs add and no out")
+    elif out is None:
         out = empty_act(B, H, W, 64, img.device)
     elif tuple(out.shape) != (B, H, W, 64) or not out.is_contiguous():
         raise ValueError("stem_conv: out must be a dense [B,H,W,64] tensor")
@@ -910,6 +914,8 @@ def stem_conv(img: torch.Tensor, img_bstride: int, B: int, H: int, W: int, w: to
         out2 = None
     check(_lib.lib().cdfo_stem_conv(_vp(img), C.c_longlong(img_bstride), _vp(w), _vp(bias), B, H, W, act, _vp(out), 64,
                                     _vp(add), lda, _vp(out2), ldo2, _stream()), "cdfo_stem_conv")
+    if not write_out:
+        return out2
     return (out, out2) if add is not None else out
 
 
@@ -1263,6 +1269,55 @@ def chan_sum_partial(x: torch.Tensor):
     check(_lib.lib().cdfo_chan_sum_partial(_vp(x), ld, B, C.c_longlong(H * W), n, _vp(part), _stream()),
           "cdfo_chan_sum_partial")
     return part, n
+
+
+def pack_rdab_stats(w2: torch.Tensor) -> torch.Tensor:
+    """conv_du_re.2's weight [64,64,3,3] as rdab_stats reads it: bf16 hi | lo = bf16(w - hi), [2][9 taps][4 k-steps][2 k-halves][64 out][8].
+    Element j of k-step c, half h is input channel 16 c + 8 (j >> 2) + 4 h + (j & 3): the order in which a lane of the 32x32 MFMA
+    holds the accumulators of the product that forms du0, so that they become the next product's operand in place."""
+    if tuple(w2.shape) != (64, 64, 3, 3):
+        raise ValueError(f"pack_rdab_stats: a [64,64,3,3] weight expected, got {tuple(w2.shape)}")
+    w = w2.detach().float().permute(2, 3, 1, 0).reshape(9, 4, 2, 2, 4, 64).permute(0, 1, 3, 5, 2, 4).reshape(9, 4, 2, 64, 8)
+    hi = w.to(torch.bfloat16)
+    return torch.stack([hi, (w - hi.float()).to(torch.bfloat16)]).contiguous()
+
+
+def rdab_stats_ok(H: int, W: int) -> bool:
+    """Inside the contract of rdab_stats: an even-sized map (conv_du_re.2's stride-2 output grid is then (H/2+1) x (W/2+1), as the
+    space-to-depth path has it) whose pixel indices fit 32 bits."""
+    return H > 0 and W > 0 and H % 2 == 0 and W % 2 == 0 and H * W < (1 << 30)
+
+
+def rdab_stats(img: torch.Tensor, Bi: int, s_b: int, s_g: int, B: int, H: int, W: int, w0: torch.Tensor, b0: torch.Tensor,
+               w2_packed: torch.Tensor, b2: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """LLongRangAttention's mask statistics from the residual maps themselves: returns (part [B,n,64], n, count) with part the
+    channel sums, in chan_sum_partial's layout, of relu(conv_du_re.2(du0)) over its count = (H/2+1)(W/2+1) output pixels, du0 =
+    relu(stencil(img; w0, b0)) on the H x W grid and zero outside it.  Neither du0 nor the convolution's result is allocated.
+    img: an fp32 device tensor; image m's dense H x W plane starts (m % Bi) * s_b + (m // Bi) * s_g elements behind its first
+    element (for maps[:, 0, i:i+G] of a [B,1,7,H,W] tensor: Bi = B, s_b = 7 H W, s_g = H W).  w0 / b0: compose_stem_1x1's stencil;
+    w2_packed: pack_rdab_stats; out: optional dense [B,n,64] destination (a slice of a larger batch).  Fixed-order sums."""
+    if not rdab_stats_ok(H, W):
+        raise ValueError(f"rdab_stats: an even-sized map expected, got {H} x {W} (use stem_conv2 + conv + chan_sum_partial)")
+    if img.dtype != torch.float32 or not img.is_cuda or B <= 0 or Bi <= 0 or s_b < 0 or s_g < 0:
+        raise ValueError("rdab_stats: an fp32 device tensor, B, Bi > 0 and non-negative strides expected")
+    last = (min(B, Bi) - 1) * s_b + ((B - 1) // Bi) * s_g + H * W
+    if last > img.untyped_storage().nbytes() // 4 - img.storage_offset():
+        raise ValueError("rdab_stats: the planes reach beyond the tensor's storage")
+    if (w2_packed.dtype != torch.bfloat16 or tuple(w2_packed.shape) != (2, 9, 4, 2, 64, 8) or not w2_packed.is_contiguous()
+            or tuple(w0.shape) != (64, 1, 3, 3) or not w0.is_contiguous() or w0.dtype != torch.float32
+            or any(t.numel() != 64 or t.dtype != torch.float32 or not t.is_contiguous() for t in (b0, b2))
+            or any(t.device != img.device for t in (w0, b0, w2_packed, b2))):
+        raise ValueError("rdab_stats: w0 [64,1,3,3], b0 [64], b2 [64] fp32 and pack_rdab_stats' image expected on the maps' device")
+    count = (H // 2 + 1) * (W // 2 + 1)
+    n = nchunks_for(count)
+    if out is None:
+        out = torch.empty((B, n, 64), dtype=torch.float32, device=img.device)
+    elif tuple(out.shape) != (B, n, 64) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != img.device:
+        raise ValueError(f"rdab_stats: out must be a dense fp32 [{B},{n},64] tensor on the maps' device")
+    with on_device(img):
+        check(_lib.lib().cdfo_rdab_stats(_vp(img), Bi, C.c_longlong(s_b), C.c_longlong(s_g), _vp(w0), _vp(b0), _vp(w2_packed),
+                                         _vp(b2), B, H, W, n, _vp(out), _stream()), "cdfo_rdab_stats")
+    return out, n, count
 
 
 def gram_partial(q: torch.Tensor, k: torch.Tensor, ch_per_head: int):

@@ -192,7 +192,8 @@ int cdfo_range_probe(const float* x, long long n, void* slots2, void* stream);
 
 /* ---- bandwidth-bound pixel-major kernels (pointwise.hip) ------------------------------------------------- */
 /* 3x3 conv 1 -> 64 channels on a single-channel plane [B][H][W] (image pitch img_bstride floats); raw OIHW weight
- * [64][1][3][3]; optional second output out2 = result + add.  arch/SIDECVSR_our.py:4379-4384,4417-4418,4446-4449. */
+ * [64][1][3][3]; optional second output out2 = result + add; with out2, out may be NULL (the result itself is not written).
+ * arch/SIDECVSR_our.py:4379-4384,4417-4418,4446-4449. */
 int cdfo_stem_conv(const float* img, long long img_bstride, const float* w, const float* bias, int B, int H, int W,
                    int act, float* out, int ldo, const float* add, int lda, float* out2, int ldo2, void* stream);
 /* two 1 -> 64 3x3 convolutions of the same plane in one pass: outA = conv(img; wA, bA) + add, outB = actB(conv(img; wB, bB))
@@ -247,6 +248,17 @@ int cdfo_spatial_gate16(const float* in, int ldi, const float* w, const float* b
 
 /* ---- reductions + per-image weight folding of the channel attentions (stats.hip) --------------------------- */
 int cdfo_chan_sum_partial(const float* in, int ldi, int B, long long P, int nchunk, float* partial, void* stream);
+/* LLongRangAttention's mask statistics from the one-channel residual maps themselves (rdab_stats.hip; arch.py:2148-2152, 2200-2203):
+ * partial [B][nchunk][64], cdfo_chan_sum_partial's layout (every slot written, fixed order: equal inputs give equal bits), of
+ *   relu(conv3x3 stride 2 pad 2 (du0; w2, b2)) over its (H/2+1) x (W/2+1) output pixels,
+ *   du0 = relu(stencil9(img; w0, b0)) on the H x W grid (the map zero-padded) and ZERO outside the grid,
+ * with neither du0 nor the convolution's result written.  Split-bf16 MFMA in three passes, fp32 accumulation.  Image m's plane
+ * (H x W fp32, dense rows) starts at img + (m % Bi) s_b + (m / Bi) s_g floats.  w0 [64][9], b0 [64]: the composed 1 -> 64 stencil;
+ * w2_packed: the 3x3 weights as bf16 hi | lo, [2][9 taps][4 k-steps c][2 k-halves h][64 out][8], element j = input channel
+ * 16 c + 8 (j >> 2) + 4 h + (j & 3) (147456 bytes, 16-byte aligned; kernels.py: pack_rdab_stats); b2 [64].  du0 is itself formed
+ * by a split-bf16 product (the tap's nine neighbours and a constant 1 against [w0 | b0]).  H, W even, H W < 2^30, else CDFO_EINVAL. */
+int cdfo_rdab_stats(const float* img, int Bi, long long s_b, long long s_g, const float* w0, const float* b0,
+                    const void* w2_packed, const float* b2, int B, int H, int W, int nchunk, float* partial, void* stream);
 int cdfo_gram_partial(const float* q, int ldq, const float* k, int ldk, int B, long long P, int ch_per_head, int nchunk,
                       float* partial, void* stream);
 /* DualAttAlignment's statistics in one pass (arch/SIDECVSR_our.py:3455-3480): kf = act(W . [x0; x1] + bias) (1x1, 128 -> 64, split-bf16
