@@ -7,7 +7,7 @@
 //   colconv9    : directH1_conv, the 9-tap conv along H on sparse_q (arch.py:2225).
 //   seq_attn    : softmax(Q Q^T) V over a row, a column or an 8x8 window, one query per lane, keys streamed through
 //                 wave-uniform (scalar) loads, online softmax in registers.
-#include "stream_ring.h"
+#include "plane_chunk.h"
 
 namespace {
 
@@ -148,9 +148,13 @@ struct rf_args {
   float* sq; int lds_; float* qwin; int ldw;
   void* vrow; int ldv; void* vwin; int ldvw;     // fp32 or fp16, pitches in elements
   unsigned long long seed; unsigned draw; float* noise_out; const unsigned long long* seed_dev;
+  // PLANE form: the convolution's input is x + stencil9(plane) (fea + conv_expand_rms(rms), arch.py:4446-4449) and only x is in
+  // memory; the stencil's part joins the product as the plane chunk of plane_chunk.h, plane.w = input_conv . [w_s | b_s], [128][16]
+  pc_plane plane;
 };
 
-template <bool RNG, typename VT, typename WT>      // VT: vrow, WT: window V
+// PLANE is a template parameter: the other form's instructions stay what they were
+template <bool RNG, typename VT, typename WT, bool PLANE = false>      // VT: vrow, WT: window V
 __global__ __launch_bounds__(ST_THREADS) void rdab_prep_kernel_fused(rf_args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rf_smem[];
   constexpr int NCB = 2;
@@ -167,6 +171,11 @@ __global__ __launch_bounds__(ST_THREADS) void rdab_prep_kernel_fused(rf_args a) 
   float* ev = sBias + NCB * 64;
   unsigned char* ring = rf_smem + ring_off + wave * NS * ST_STAGE;
   const unsigned ring_lds = (unsigned)(unsigned long long)(rf_smem) + ring_off + wave * NS * ST_STAGE;
+  // PLANE: behind the rings the chunk's weight image hi | lo, then NS tap slots per wave, indexed like the ring (one item per tile)
+  unsigned char* sPh = rf_smem + ring_off + 4 * NS * ST_STAGE;
+  unsigned char* sPl = sPh + pc_weight_bytes(NCB) / 2;
+  const unsigned char* tap_slots = sPh + pc_weight_bytes(NCB) + wave * NS * PC_SLOT;
+  const unsigned tap_lds = (unsigned)(unsigned long long)(rf_smem) + ring_off + 4 * NS * ST_STAGE + pc_weight_bytes(NCB) + wave * NS * PC_SLOT;
 
   const long long t_lo = a.tiles * blockIdx.x / gridDim.x, t_hi = a.tiles * (blockIdx.x + 1) / gridDim.x;
   if (t_lo >= t_hi) return;
@@ -180,6 +189,7 @@ __global__ __launch_bounds__(ST_THREADS) void rdab_prep_kernel_fused(rf_args a) 
   }
   auto part_off = [&](int q) { return r * 256 + ((q ^ (r & 15)) << 4); };
 
+  if (PLANE) pc_load_weights<NCB>(a.plane.w, NCB * 64, sPh, sPl, tid);      // (the barriers of the first image's trip publish them)
   // ---- the weights (the same for every image) -> LDS, split bf16 hi | lo, rows permuted (as conv1x1_stream_kernel)
   for (int i = tid; i < 16 * NCB * 64; i += ST_THREADS) {
     const int rowpos = i % (NCB * 64), kg = i / (NCB * 64);
@@ -221,6 +231,8 @@ __global__ __launch_bounds__(ST_THREADS) void rdab_prep_kernel_fused(rf_args a) 
       const float* base = a.x + ((long long)b * a.P + (rows_left > 0 ? p0 : 0)) * a.ldx;
       const long long bytes = rows_left > 0 ? (rows_left < 32 ? rows_left : 32) * (long long)a.ldx * 4 : 0;
       const i32x4 rsrc = lds_dma_rsrc_uniform(base, (unsigned)bytes);      // lanes beyond the image read zeros
+      if (PLANE)                 // the tile's taps, ahead of its item: in order behind it, so landed when it has (plane_chunk.h)
+        pc_issue(pc_image(a.plane, b), (int)a.P, a.plane.W, (int)p0, lane, tap_lds + (unsigned)(it % NS) * PC_SLOT);
       unsigned voff[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) voff[q] = (unsigned)(d_px[q] * a.ldx * 4 + d_part[q] * 16);
@@ -238,6 +250,14 @@ __global__ __launch_bounds__(ST_THREADS) void rdab_prep_kernel_fused(rf_args a) 
         for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
           for (int e = 0; e < 16; ++e) acc[cb][ni][e] = 0.f;
+      if (PLANE) {
+        // the plane chunk's k-step opens the product; its slot is read here, before the request below can reuse any slot.  The
+        // hand-counted wait above stays valid: the three older pieces of every tile only make it more conservative
+        const int p = (int)((img_t0 + it - (long long)b * a.tiles_per_image) * 128) + wave * 32 + r;
+        unsigned thi[4], tlo[4];
+        pc_operand(tap_slots + (it % NS) * PC_SLOT, r, h, p, (int)a.P, a.plane.W, thi, tlo);
+        pc_mfma<NCB>(sPh, sPl, r, h, thi, tlo, acc);
+      }
       // ---- the K block, as conv1x1_stream_kernel: this lane's operand = channels c*16 + h*8 .. +7 of pixel r
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -892,10 +912,11 @@ extern "C" int cdfo_rdab_prep_rng_dev(const float* xq, int ldx, const float* vma
 // with (seed_dev ? *seed_dev : seed, draw) and the optional noise_out (cdfo_rdab_prep_rng / _rng_dev).  v_f16 bit 0: vrow, bit 1: vwin
 // (the v half of the product, which the two-kernel path reads from xq) is fp16 with its pitch in halves.  Results equal those of
 // cdfo_conv1x1_bf16x3's streaming kernel followed by cdfo_rdab_prep* bit for bit (fp16: rounded once).
-extern "C" int cdfo_rdab_prep_fused(const float* x, int ldx, const float* w_packed, const float* bias, const float* vmax,
-                                    const float* noise, long long seed, const void* seed_dev, int draw, float* noise_out,
-                                    const float* wW, const float* bW, int B, long long P, float* sq, int lds_, void* vrow, int ldv,
-                                    float* qwin, int ldw, void* vwin, int ldvw, int v_f16, void* stream) {
+// plane != null: the PLANE form (cdfo_rdab_prep_fused_plane)
+static int rdab_prep_fused_launch(const float* x, int ldx, const float* w_packed, const float* bias, const float* vmax,
+                                  const float* noise, long long seed, const void* seed_dev, int draw, float* noise_out,
+                                  const float* wW, const float* bW, int B, long long P, float* sq, int lds_, void* vrow, int ldv,
+                                  float* qwin, int ldw, void* vwin, int ldvw, int v_f16, const pc_plane* plane, void* stream) {
   if (B <= 0 || P <= 0 || P % 64 || P >= (1ll << 32) || ldx < 64 || ldx % 4 || (long long)ldx * 4 * 32 >= (1ll << 31) || lds_ % 4 ||
       ldw % 4 || ldv % 8 || ldvw % 8 || !x || !w_packed || !vmax || !wW || !bW)
     return CDFO_EINVAL;
@@ -912,13 +933,27 @@ extern "C" int cdfo_rdab_prep_fused(const float* x, int ldx, const float* w_pack
   s.seed_dev = static_cast<const unsigned long long*>(seed_dev);
   int grid;
   if (!st_tiling(B, P, s.tiles_per_image, s.tiles, grid)) return CDFO_EINVAL;
-  const int lds = st_lds_bytes(1, 2, s.ns) + 64 * 4;
+  const int lds = st_lds_bytes(1, 2, s.ns) + 64 * 4 + (plane ? pc_lds_bytes(2, s.ns) : 0);
   const double px = (double)B * P;
   if (v_f16 < 0 || v_f16 > 3) return CDFO_EINVAL;
-  CdfoProfScope prof(st, KID_RDAB_PREP, 2.0 * px * 128 * 64,
-                     px * (4.0 * (64 + 128 + (noise ? 64 : 0)) + ((v_f16 & 1) ? 2.0 : 4.0) * 64 + ((v_f16 & 2) ? 2.0 : 4.0) * 64));
-  static CdfoAttrOnce once[8];
+  // (the plane chunk: one k-step of 16 and 4 bytes per pixel more)
+  CdfoProfScope prof(st, KID_RDAB_PREP, 2.0 * px * 128 * (plane ? 80 : 64),
+                     px * (4.0 * (64 + 128 + (noise ? 64 : 0) + (plane ? 1 : 0)) + ((v_f16 & 1) ? 2.0 : 4.0) * 64 + ((v_f16 & 2) ? 2.0 : 4.0) * 64));
+  static CdfoAttrOnce once[8], once_pl[8];
   typedef _Float16 h;
+  if (plane) {
+    s.plane = *plane;
+    switch ((noise ? 0 : 4) + v_f16) {
+      case 0: return st_launch(rdab_prep_kernel_fused<false, float, float, true>, once_pl[0], grid, lds, st, s);
+      case 1: return st_launch(rdab_prep_kernel_fused<false, h, float, true>, once_pl[1], grid, lds, st, s);
+      case 2: return st_launch(rdab_prep_kernel_fused<false, float, h, true>, once_pl[2], grid, lds, st, s);
+      case 3: return st_launch(rdab_prep_kernel_fused<false, h, h, true>, once_pl[3], grid, lds, st, s);
+      case 4: return st_launch(rdab_prep_kernel_fused<true, float, float, true>, once_pl[4], grid, lds, st, s);
+      case 5: return st_launch(rdab_prep_kernel_fused<true, h, float, true>, once_pl[5], grid, lds, st, s);
+      case 6: return st_launch(rdab_prep_kernel_fused<true, float, h, true>, once_pl[6], grid, lds, st, s);
+      default: return st_launch(rdab_prep_kernel_fused<true, h, h, true>, once_pl[7], grid, lds, st, s);
+    }
+  }
   switch ((noise ? 0 : 4) + v_f16) {
     case 0: return st_launch(rdab_prep_kernel_fused<false, float, float>, once[0], grid, lds, st, s);
     case 1: return st_launch(rdab_prep_kernel_fused<false, h, float>, once[1], grid, lds, st, s);
@@ -1012,4 +1047,27 @@ extern "C" int cdfo_seq_attn_f16(const float* q, int ldq, const void* v, int ldv
   if (rc) return rc;
   CDFO_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int cdfo_rdab_prep_fused(const float* x, int ldx, const float* w_packed, const float* bias, const float* vmax,
+                                    const float* noise, long long seed, const void* seed_dev, int draw, float* noise_out,
+                                    const float* wW, const float* bW, int B, long long P, float* sq, int lds_, void* vrow, int ldv,
+                                    float* qwin, int ldw, void* vwin, int ldvw, int v_f16, void* stream) {
+  return rdab_prep_fused_launch(x, ldx, w_packed, bias, vmax, noise, seed, seed_dev, draw, noise_out, wW, bW, B, P, sq, lds_, vrow, ldv,
+                                qwin, ldw, vwin, ldvw, v_f16, nullptr, stream);
+}
+
+// cdfo_rdab_prep_fused on x + stencil9(plane; w_s, b_s) with only x in memory: image b's plane (W pixels per row, P / W rows, dense
+// fp32) at plane + (b % plane_Bi) plane_sb + (b / plane_Bi) plane_sg floats; plane_w [128][16] = input_conv . [w_s | b_s] | zeros
+extern "C" int cdfo_rdab_prep_fused_plane(const float* x, int ldx, const float* w_packed, const float* bias, const float* vmax,
+                                          const float* noise, long long seed, const void* seed_dev, int draw, float* noise_out,
+                                          const float* wW, const float* bW, int B, long long P, float* sq, int lds_, void* vrow,
+                                          int ldv, float* qwin, int ldw, void* vwin, int ldvw, int v_f16, const float* plane,
+                                          int plane_Bi, long long plane_sb, long long plane_sg, int W, const float* plane_w,
+                                          void* stream) {
+  if (!plane || !plane_w || plane_Bi <= 0 || plane_sb < 0 || plane_sg < 0 || !pc_shape_ok(P, W)) return CDFO_EINVAL;
+  if (!aligned16(plane_w)) return CDFO_EALIGN;
+  const pc_plane pl = {plane, plane_Bi, plane_sb, plane_sg, W, plane_w, 0};
+  return rdab_prep_fused_launch(x, ldx, w_packed, bias, vmax, noise, seed, seed_dev, draw, noise_out, wW, bW, B, P, sq, lds_, vrow, ldv,
+                                qwin, ldw, vwin, ldvw, v_f16, &pl, stream);
 }

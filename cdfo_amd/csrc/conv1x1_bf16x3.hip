@@ -12,6 +12,7 @@
 // pixel-shuffle store); every source must be a multiple of 64 channels wide.  Replaces the 1x1 convolutions of the
 // CVSR_V8 path (qkv, project_out folded, input_conv, fuse, fusion_out, down.0 / up.0, tsa_fusion, upconv1/2).
 #include "numeric.h"
+#include "plane_chunk.h"      // pc_plane: the optional plane operand, streaming form only
 
 namespace {
 
@@ -244,11 +245,12 @@ __global__ __launch_bounds__(256, 2) void conv1x1_bf16x3_kernel(cdfo_conv_args a
 }  // namespace
 
 // conv1x1_stream.hip: the persistent LDS-DMA streaming form (plain store, CoutP <= 128, weights + rings within LDS)
-int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st);
+int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st, const pc_plane* plane = nullptr);
 extern "C" int cdfo_layernorm64_cp16hl(const float* in, int ldi, const float* gamma, const float* beta, int B, long long P,
                                        void* out, void* stream);
 
-extern "C" int cdfo_conv1x1_bf16x3(const cdfo_conv_args* pa, void* stream) {
+// pl != null: cdfo_conv1x1_bf16x3_plane
+static int conv1x1_bf16x3(const cdfo_conv_args* pa, const pc_plane* pl, void* stream) {
   const cdfo_conv_args& a = *pa;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (a.nsrc < 1 || a.nsrc > CDFO_MAXSRC || a.B <= 0 || a.ks != 1 || a.stride != 1 || a.pad != 0) return CDFO_EINVAL;
@@ -275,6 +277,14 @@ extern "C" int cdfo_conv1x1_bf16x3(const cdfo_conv_args* pa, void* stream) {
   if (!ln_out && a.ln_gamma && !(a.nsrc == 1 && a.cs[0] == 64 && a.ln_beta && aligned16(a.ln_gamma) && aligned16(a.ln_beta))) return CDFO_EINVAL;
   const long long P = (long long)a.H * a.W;
   if (a.res2_pixscale && (!a.res2 || taps)) return CDFO_EINVAL;
+  if (pl) {
+    // one more operand, stencil9 of a one-channel plane, inside the product: only the streaming kernel has that form, and a launch
+    // outside its contract is an error (the caller materialises the operand instead)
+    if (!pl->base || !pl->w || pl->Bi <= 0 || pl->s_b < 0 || pl->s_g < 0 || taps) return CDFO_EINVAL;
+    if (!aligned16(pl->w) || pl->w_bstride % 4 || (a.chan_sum_out && !aligned16(a.chan_sum_out))) return CDFO_EALIGN;
+    const int r = cdfo_conv1x1_stream_try(a, st, pl);
+    return r == 1 ? 0 : (r == 0 ? CDFO_EINVAL : r);
+  }
   if (a.chan_sum_out) {
     // channel sums of the result: from the streaming kernel's epilogue, else (outside its contract / switched off) a pass of their own
     if (a.Cout != 64 || a.CoutP != 64 || a.store_mode != CDFO_STORE_PLAIN || a.chan_sum_slots <= 0 || !aligned16(a.chan_sum_out)) return CDFO_EINVAL;
@@ -329,4 +339,12 @@ extern "C" int cdfo_conv1x1_bf16x3(const cdfo_conv_args* pa, void* stream) {
   }
   CDFO_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int cdfo_conv1x1_bf16x3(const cdfo_conv_args* pa, void* stream) { return conv1x1_bf16x3(pa, nullptr, stream); }
+
+extern "C" int cdfo_conv1x1_bf16x3_plane(const cdfo_conv_args* pa, const float* plane, int plane_Bi, long long plane_sb,
+                                         long long plane_sg, const float* plane_w, long long plane_w_bstride, void* stream) {
+  const pc_plane pl = {plane, plane_Bi, plane_sb, plane_sg, 0, plane_w, plane_w_bstride};      // (W: the argument block's)
+  return conv1x1_bf16x3(pa, &pl, stream);
 }

@@ -21,7 +21,7 @@
 //     straight from registers.
 // Contract: cdfo_conv_args as cdfo_conv1x1_bf16x3 with plain store, Cin % 64 == 0 per source, Cout % 8 == 0,
 // CoutP in {64, 128}, weights + ring within the CU's LDS (Cin * CoutP <= 192 * 64); everything else stays on that kernel.
-#include "stream_ring.h"
+#include "plane_chunk.h"
 
 namespace {
 
@@ -51,6 +51,9 @@ struct st_args {
   // (cdfo_chan_sum_partial's layout; the buffer is zeroed by the caller).  The values are in the epilogue's registers: the global
   // average pool that follows (CALayer, arch.py:3493) needs no pass of its own over the tensor
   float* csum; int csum_slots;
+  // PLANE form: one more 64-channel operand of the product, stencil9 of a one-channel plane, as the plane chunk of plane_chunk.h
+  // (plane.w: [CoutP][16] per image, the product's weights for that operand composed with the stencil); plane.base == nullptr: absent
+  pc_plane plane;
 };
 
 // The persistent kernels here cut the stream of `tiles` 128-pixel tiles into `grid` contiguous ranges [tiles w / grid, tiles (w + 1) /
@@ -70,8 +73,10 @@ inline int st_slots(int B, int tiles_per_image, int grid) {
 
 // NCB: 64-wide output-channel blocks (1, 2; 4 in the TAPS form)
 // CSUM (NCB == 1): also the channel sums of the result, see st_args.csum
-template <int NCB, bool TAPS = false, bool CSUM = false>
+// PLANE: the plane chunk of st_args.plane joins the product (a template parameter: the other forms' instructions stay what they were)
+template <int NCB, bool TAPS = false, bool CSUM = false, bool PLANE = false>
 __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
+  static_assert(!(PLANE && TAPS), "the TAPS form takes no plane chunk");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -88,6 +93,11 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
   // res_scale: two 256-byte slots per wave (tile parity) behind the rings
   const unsigned char* scale_slots = smem + ring_off + 4 * NS * ST_STAGE + wave * 512;
   const unsigned scale_lds = (unsigned)(unsigned long long)(smem) + ring_off + 4 * NS * ST_STAGE + wave * 512;
+  // PLANE (never together with res_scale): behind the rings the chunk's weight image hi | lo, then NS tap slots per wave
+  unsigned char* sPh = smem + ring_off + 4 * NS * ST_STAGE;
+  unsigned char* sPl = sPh + pc_weight_bytes(NCB) / 2;
+  const unsigned char* tap_slots = sPh + pc_weight_bytes(NCB) + wave * NS * PC_SLOT;
+  const unsigned tap_lds = (unsigned)(unsigned long long)(smem) + ring_off + 4 * NS * ST_STAGE + pc_weight_bytes(NCB) + wave * NS * PC_SLOT;
 
   // this workgroup's contiguous tile range
   const long long t_lo = a.tiles * blockIdx.x / gridDim.x, t_hi = a.tiles * (blockIdx.x + 1) / gridDim.x;
@@ -143,6 +153,7 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
         *reinterpret_cast<u32x2*>(sWl + off) = lo;
       }
       for (int i = tid; i < NCB * 64; i += ST_THREADS) sBias[i] = (a.bias && i < a.Cout) ? a.bias[i] : 0.f;   // by channel
+      if (PLANE) pc_load_weights<NCB>(a.plane.w + (long long)b * a.plane.w_bstride, a.CoutP, sPh, sPl, tid);
     }
     __syncthreads();
 
@@ -163,6 +174,8 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
                                               (unsigned)(rows > 0 ? (rows < 32 ? rows : 32) * 4 : 0));      // beyond the image: zeros
         lds_dma0_dword((unsigned)r * 4, rs, __builtin_amdgcn_readfirstlane(scale_lds + (unsigned)(tile & 1) * 256));
       }
+      if (PLANE && k == 0)       // the tile's taps, ahead of its first item like the factors above (plane_chunk.h)
+        pc_issue(pc_image(a.plane, b), (int)a.P, a.plane.W, (int)p0, lane, tap_lds + (unsigned)((it / items_per_tile) % NS) * PC_SLOT);
       st_item src;
       int chan0;
       if (k < nkb) { src = a.act[k]; chan0 = src.ch0; }
@@ -206,6 +219,14 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
           for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[cb][ni][e] = 0.f;
+        if (PLANE) {
+          // the plane chunk's k-step opens the tile's product: its slot landed before this item (requested ahead of it) and is
+          // read here, before the request below can reuse any slot (plane_chunk.h)
+          const int p = (int)((img_t0 + it / items_per_tile - (long long)b * a.tiles_per_image) * 128) + wave * 32 + r;
+          unsigned thi[4], tlo[4];
+          pc_operand(tap_slots + ((it / items_per_tile) % NS) * PC_SLOT, r, h, p, (int)a.P, a.plane.W, thi, tlo);
+          pc_mfma<NCB>(sPh, sPl, r, h, thi, tlo, acc);
+        }
       }
       if (k < nkb) {
         // ---- one K block: 4 chunks of 16 channels; this lane's operand = channels c*16 + h*8 .. +7 of pixel r
@@ -686,9 +707,11 @@ extern "C" int cdfo_align_stats(const float* x0, int ld0, const float* x1, int l
 
 // Returns 1 when the streaming kernel took the launch, 0 when the shapes are outside its contract (the caller falls back to
 // cdfo_conv1x1_bf16x3), < 0 / hipError_t on errors.  Same argument block as cdfo_conv1x1_bf16x3.
-int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st) {
+// plane != null: the PLANE form, or 0
+int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st, const pc_plane* pl) {
   const bool ln_out = a.out2_cp16 != nullptr;      // post-LayerNorm hi | lo second output (checked by the caller: Cout == 64)
   const bool taps = a.store_mode == CDFO_STORE_TAPS9;
+  if (taps && pl) return 0;
   if (taps) {
     // upconv2 + conv_last's tap sums (checked by the caller: Cout = CoutP = 256, res2 = conv_last.weight [64][9], no res1)
     if (a.Cin != 64 || a.nsrc != 1 || a.ldo % 4 || a.ldo < 12 || a.ln_gamma || ln_out || (long long)a.ld[0] * 4 * 32 >= (1ll << 31)) return 0;
@@ -709,13 +732,16 @@ int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st) {
     return e == 0 ? 1 : e;
   }
   if (a.store_mode != CDFO_STORE_PLAIN || (a.ln_gamma && !ln_out) || a.CoutP % 64 || a.CoutP > 128 || a.Cout % 8) return 0;      // (ln_out without ln_gamma: plain fp16 copy)
+  const bool plane = pl != nullptr;
+  // the plane chunk: 64 output channels, no second output, no scaled residual (its LDS lies where the factors' slots would)
+  if (plane && (a.CoutP != 64 || ln_out || a.res2_pixscale || !pc_shape_ok((long long)a.H * a.W, a.W))) return 0;
   if (ln_out && (a.CoutP != 64 || a.Cout != 64)) return 0;
   if (a.chan_sum_out && (a.CoutP != 64 || a.Cout != 64 || ln_out || a.chan_sum_slots <= 0)) return 0;   // the caller sums in a pass of its own
   const int ncb = a.CoutP / 64, nkb = a.Cin / 64;
   if (nkb < 1 || nkb > CDFO_MAXSRC * 4) return 0;
   const int w_bytes = st_weight_bytes(nkb, ncb);
   const int scale_bytes = (a.res2 && a.res2_pixscale) ? 4 * 512 : 0;      // two tile-parity slots per wave
-  int ns = (ST_MAX_LDS - scale_bytes - w_bytes) / (4 * ST_STAGE);
+  int ns = plane ? (ST_MAX_LDS - w_bytes - pc_weight_bytes(ncb)) / (4 * (ST_STAGE + PC_SLOT)) : (ST_MAX_LDS - scale_bytes - w_bytes) / (4 * ST_STAGE);
   if (ns > ST_MAXNS) ns = ST_MAXNS;
   if (scale_bytes) {
     // the per-pixel factors of tile t + 2 are requested with item (t + 2, 0), NS - 1 items ahead of consumption, into the slot tile t
@@ -746,15 +772,23 @@ int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st) {
   s.ns = ns;
   int grid;
   if (!st_tiling(a.B, P, s.tiles_per_image, s.tiles, grid)) return CDFO_EINVAL;
-  const int lds = st_lds_bytes(nkb, ncb, ns) + scale_bytes;
+  const int lds = st_lds_bytes(nkb, ncb, ns) + scale_bytes + (plane ? pc_lds_bytes(ncb, ns) : 0);
   const double px = (double)a.B * P;
-  CdfoProfScope prof(st, KID_CONV1, 2.0 * px * a.Cout * a.Cin, 4.0 * (px * a.Cout * (1 + nr) + px * a.Cin + (double)a.Cin * a.Cout));
+  if (plane) { s.plane = *pl; s.plane.W = a.W; }
+  // (the plane chunk: one k-step of 16 and 4 bytes per pixel more)
+  CdfoProfScope prof(st, KID_CONV1, 2.0 * px * a.Cout * (a.Cin + (plane ? 16 : 0)),
+                     4.0 * (px * a.Cout * (1 + nr) + px * a.Cin + (plane ? px : 0.0) + (double)a.Cin * a.Cout));
   if (a.chan_sum_out) {
     // (checked above: ncb == 1, Cout == 64) the result's channel sums from the epilogue's registers, one slot per (image, workgroup segment)
     if (a.chan_sum_slots < st_slots(a.B, s.tiles_per_image, grid)) return 0;
     s.csum = a.chan_sum_out; s.csum_slots = a.chan_sum_slots;
   }
-  static CdfoAttrOnce once_csum, once1, once2;
+  static CdfoAttrOnce once_csum, once1, once2, once_pl, once_pl_csum;
+  if (plane) {
+    const int e = a.chan_sum_out ? st_launch(conv1x1_stream_kernel<1, false, true, true>, once_pl_csum, grid, lds, st, s)
+                                 : st_launch(conv1x1_stream_kernel<1, false, false, true>, once_pl, grid, lds, st, s);
+    return e == 0 ? 1 : e;
+  }
   const int e = a.chan_sum_out ? st_launch(conv1x1_stream_kernel<1, false, true>, once_csum, grid, lds, st, s)
                 : ncb == 1     ? st_launch(conv1x1_stream_kernel<1>, once1, grid, lds, st, s)
                                : st_launch(conv1x1_stream_kernel<2>, once2, grid, lds, st, s);

@@ -159,6 +159,11 @@ class CVSR_V8(nn.Module):
         # the one-channel prior planes stay one-channel inside their consumers (see _compensate: the mask statistics straight from
         # the residual maps; developer A/B: CDFO_PRIOR_STEMS=0 -> du0 written by the stem kernel and read back by a convolution)
         self.prior_stems = switches.get("CDFO_PRIOR_STEMS")
+        # ... and fea_com = fea + conv_expand_rms(rms) is never written: its two readers (the mask kernel's input_conv, RDAB.fuse's
+        # residual) read fea and take the stencil's part as one more k-step built from the residual map (see _compensate, _rdab;
+        # developer A/B: CDFO_INLINE_RMS=0 -> the stem kernel writes fea_com).  Needs prior_stems: without it the stem launch that
+        # writes du0 writes fea_com anyway
+        self.inline_rms = switches.get("CDFO_INLINE_RMS")
         self.neighbour_group = 0       # frames per neighbour group: 0 = auto = 3
         # cached-feature call on one sequence (B = 1): the group of frames 0-2 (cached features only) starts beside the new
         # frame's feature extraction instead of behind it (see _forward)
@@ -307,6 +312,12 @@ class CVSR_V8(nn.Module):
         w["RDAB.conv_du_re.2_s2d"] = K.pack_conv_s2p2_s2d(sd["RDAB.conv_du_re.2.weight"], sd["RDAB.conv_du_re.2.bias"])
         # ... and the same weights as bf16 hi | lo for K.rdab_stats, which forms du0 in registers and leaves only the channel sums
         w["RDAB.conv_du_re.2_stats"] = K.pack_rdab_stats(sd["RDAB.conv_du_re.2.weight"])
+        # conv_expand_rms as the plane chunk of the stream kernels (K.pack_plane_chunk): by itself where fea_com is a residual
+        # (RDAB.fuse), composed with input_conv (whose own bias stays in the kernel's bias table) where it is the convolution's input
+        w["rms_chunk"] = K.pack_plane_chunk(sd["conv_expand_rms.weight"], sd["conv_expand_rms.bias"])
+        w["rms_chunk_input_conv"] = K.pack_plane_chunk(*K.compose_stem_1x1(
+            sd["conv_expand_rms.weight"], sd["conv_expand_rms.bias"], sd["RDAB.input_conv.weight"],
+            torch.zeros_like(sd["RDAB.input_conv.bias"])))
         w[fe + "side_to_feaoneUDSA.body.0_n16"] = K.pack_conv_n16(sd[fe + "side_to_feaoneUDSA.body.0.weight"])
         w["udsa_head"] = K.pack_udsa_head(sd[fe + "side_to_feaoneUDSA.body.0.weight"], sd[fe + "side_to_feaoneUDSA.body.0.bias"],
                                           sd["conv_second.weight"], sd["conv_second.bias"])
@@ -403,8 +414,11 @@ class CVSR_V8(nn.Module):
                 x1 = self._conv(ln, w[p + "conv"], pad=1, res1=x1, res2=x2, exact=True)
         return x1
 
-    def _rdab(self, w, du0, x, noises, stats=None):
-        """LLongRangAttention (arch.py:2179-2249) on a GROUP of neighbour frames at once: du0 / x are [G*B,H,W,64] (neighbour
+    def _rdab(self, w, du0, x, noises, stats=None, rms_planes=None):
+        """rms_planes = (view, Bi, s_b, s_g) (K.conv's plane addressing over the GB images; the images of one noise lie inside one
+        block of Bi): the module's input is x + conv_expand_rms(plane) and only x is in memory -- the mask kernel and RDAB.fuse
+        build the stencil's part from the residual maps (needs the fused mask kernel).
+        LLongRangAttention (arch.py:2179-2249) on a GROUP of neighbour frames at once: du0 / x are [G*B,H,W,64] (neighbour
         major; du0 = relu(conv_du_re.0(res)) of the module's residual-map input in space-to-depth form, computed by the stem
         kernel -- or None with `stats`, the mask statistics that K.rdab_stats formed from the residual maps), `noises` one
         entry per neighbour -- the module's weights are shared by all neighbours, only the noise draw (and with it the mask
@@ -425,7 +439,10 @@ class CVSR_V8(nn.Module):
         # error <= 2^-11 max|v|, measured ~1e-5 |v|; the scores keep their three split-fp16 passes); fp32-grade modes: all three passes
         am = 20 if self.precision == "fp16x2" and self.attn_pv_single else 0
         wW, bW = raw["RDAB.directW1_conv.weight"], raw["RDAB.directW1_conv.bias"]
-        if self.rdab_fused and self.precision != "f32" and K.rdab_prep_fused_ok(x, w["RDAB.input_conv"]):
+        fused_prep = self.rdab_fused and self.precision != "f32" and K.rdab_prep_fused_ok(x, w["RDAB.input_conv"])
+        if rms_planes is not None and not (fused_prep and rms_planes[1] % B == 0):
+            raise ValueError("_rdab: rms_planes needs the fused mask kernel and each noise's images inside one block of planes")
+        if fused_prep:
             # input_conv inside the mask kernel: its 128-channel result is never written.  Modes 20-22 round every V once to fp16
             # while staging, so the V operands of the column and window attentions (the row attention's output, the window V) are
             # stored that way: same bits.  vrow stays fp32: the row form measured slower on an fp16 V
@@ -434,8 +451,14 @@ class CVSR_V8(nn.Module):
             vwin = torch.empty((GB, H, W, 64), dtype=vdt, device=x.device)
             for g, noise in enumerate(noises):
                 sl = slice(g * B, (g + 1) * B)
+                plane = None
+                if rms_planes is not None:      # this noise's planes: images g B .. g B + B - 1 of the addressing, inside one block
+                    view, Bi, s_b, s_g = rms_planes
+                    off = (g * B % Bi) * s_b + (g * B // Bi) * s_g
+                    first = view.as_strided((1,), (1,), view.storage_offset() + off)      # (no copy: an address in the storage)
+                    plane = (first, B, s_b, 0, w["rms_chunk_input_conv"])
                 K.rdab_prep_fused(x[sl], w["RDAB.input_conv"], vmax[sl], noise, wW, bW, v_f16=(False, am == 20),
-                                  outs=(sq[sl], vrow[sl], qwin[sl], vwin[sl]))
+                                  outs=(sq[sl], vrow[sl], qwin[sl], vwin[sl]), plane=plane)
         else:
             vdt = torch.float32
             xq = self._conv(x, w["RDAB.input_conv"])
@@ -454,6 +477,8 @@ class CVSR_V8(nn.Module):
         qc = K.colconv9(sq, raw["RDAB.directH1_conv.weight"], raw["RDAB.directH1_conv.bias"])
         K.seq_attn(qc, rowo, am + 1, out=cat[..., 0:64])
         K.seq_attn(qwin, vwin, am + 2, out=cat[..., 64:128])
+        if rms_planes is not None:      # the residual is x + conv_expand_rms(plane): the stencil's part goes through the product
+            return self._conv(cat, w["RDAB.fuse"], res1=x, plane=(*rms_planes, w["rms_chunk"]))
         return self._conv(cat, w["RDAB.fuse"], res1=x)
 
     def _align(self, w, xc, extra, pred, mvs, mv_bstride, out, frames=None):
@@ -1102,16 +1127,22 @@ class CVSR_V8(nn.Module):
         raw = w["raw"]
         M, H, W, _ = fea.shape
         dev = fea.device
-        fea_com = K.empty_act(M, H, W, NF, dev)
-        du0 = stats = None
+        du0 = stats = planes = None
         if self.prior_stems and self.precision != "f32" and not self.istraining and K.rdab_stats_ok(H, W):
             # du0 has one consumer, a convolution whose result has one consumer, the global average pool: K.rdab_stats goes from the
             # residual maps to the pool's partial sums, and the stem only adds conv_expand_rms(rms) to the features
             stats = self._mask_stats(w, stems, M, H, W)
+            planes = self._inline_rms_planes(w, fea, stems, len(draws))
+        if planes is not None:
+            # ... and that sum has two consumers, both matrix products over the pixel's channels: they read fea and the residual map
+            fea_com = None
+        elif stats is not None:
+            fea_com = K.empty_act(M, H, W, NF, dev)
             for rms, bstride, sl in stems:
                 K.stem_conv(rms, bstride, sl.stop - sl.start, H, W, raw["conv_expand_rms.weight"], raw["conv_expand_rms.bias"],
                             add=fea[sl], out2=fea_com[sl], write_out=False)
         else:
+            fea_com = K.empty_act(M, H, W, NF, dev)
             du0 = K.empty_act(M, H // 2 + 1, W // 2 + 1, 4 * NF, dev)       # space-to-depth, + one zero row / column
             du0[:, H // 2].zero_()
             du0[:, :, W // 2].zero_()
@@ -1130,11 +1161,42 @@ class CVSR_V8(nn.Module):
                 noises.append(("rng", self._noise_seed, draw, cap))
             else:
                 noises.append(noise[k].to(device=dev, dtype=torch.float32).contiguous())
-        x_n = self._rdab(w, du0, fea_com, noises, stats)
+        if planes is not None:
+            x_n = self._rdab(w, du0, fea, noises, stats, rms_planes=planes)
+        else:
+            x_n = self._rdab(w, du0, fea_com, noises, stats)
         fea_i = self._conv([fea, x_n], w["conv_expand_fea_r"], pad=1, inner=self.fea_r_single_pass)
         if keep is not None:
             keep.extend([du0, stats, fea_com, noises, x_n, fea_i])
         return fea_i, x_n
+
+    @staticmethod
+    def _affine_stems(stems):
+        """(view, Bi, s_b, s_g) where the stems' planes lie at one stride behind each other (consecutive slots of one [B,1,7,H,W]
+        tensor) and their slices tile the image stack in order: image m's plane at view + (m % Bi) s_b + (m // Bi) s_g.  Else None."""
+        v0, s_b, sl0 = stems[0]
+        Bi = sl0.stop - sl0.start
+        step = (stems[1][0].data_ptr() - v0.data_ptr()) // 4 if len(stems) > 1 else 0
+        if step >= 0 and all(v.untyped_storage().data_ptr() == v0.untyped_storage().data_ptr() and bs == s_b
+                             and (sl.start, sl.stop) == (k * Bi, (k + 1) * Bi) and v.data_ptr() == v0.data_ptr() + 4 * k * step
+                             for k, (v, bs, sl) in enumerate(stems)):
+            return v0, Bi, s_b, step
+        return None
+
+    def _inline_rms_planes(self, w, fea, stems, nnoise):
+        """The plane addressing for _rdab where fea_com need not be written (model.inline_rms): the composed tables are packed, the
+        mask kernel is the fused one, the planes are affine and inside the plane chunk's contract, and the images of one noise
+        (M / nnoise consecutive ones) lie inside one stem -- a neighbour group's one noise per stem, compensate_features' one
+        stem for all frames with a noise each: which path a frame takes must not depend on how many frames share the call.  Else
+        None: the stem kernel writes fea_com (stems without a common stride stay on that path)."""
+        M, H, W, _ = fea.shape
+        if not (self.inline_rms and "rms_chunk" in w and self.rdab_fused and K.plane_ok(H, W) and M % nnoise == 0
+                and K.rdab_prep_fused_ok(fea, w["RDAB.input_conv"])):
+            return None
+        aff = self._affine_stems(stems)
+        if aff is None or aff[1] % (M // nnoise) or any(v.dtype != torch.float32 for v, _, _ in stems):
+            return None
+        return aff
 
     @staticmethod
     def _mask_stats(w, stems, M, H, W):
@@ -1142,16 +1204,13 @@ class CVSR_V8(nn.Module):
         behind each other (consecutive slots of one [B,1,7,H,W] tensor), else one launch per stem.  Returns (partials, slots,
         pixel count)."""
         args = (*w["rms_du0"], w["RDAB.conv_du_re.2_stats"], w["raw"]["RDAB.conv_du_re.2.bias"])
-        v0, s_b, sl0 = stems[0]
-        Bi = sl0.stop - sl0.start
-        step = (stems[1][0].data_ptr() - v0.data_ptr()) // 4 if len(stems) > 1 else 0
-        if step >= 0 and all(v.untyped_storage().data_ptr() == v0.untyped_storage().data_ptr() and bs == s_b
-                             and (sl.start, sl.stop) == (k * Bi, (k + 1) * Bi) and v.data_ptr() == v0.data_ptr() + 4 * k * step
-                             for k, (v, bs, sl) in enumerate(stems)):
+        aff = CVSR_V8._affine_stems(stems)
+        if aff is not None:
+            v0, Bi, s_b, step = aff
             return K.rdab_stats(v0, Bi, s_b, step, M, H, W, *args)
         count = (H // 2 + 1) * (W // 2 + 1)
         n = K.nchunks_for(count)
-        part = torch.empty((M, n, 64), dtype=torch.float32, device=v0.device)
+        part = torch.empty((M, n, 64), dtype=torch.float32, device=stems[0][0].device)
         for v, bs, sl in stems:
             K.rdab_stats(v, sl.stop - sl.start, bs, 0, sl.stop - sl.start, H, W, *args, out=part[sl])
         return part, n, count

@@ -198,6 +198,41 @@ def _bind_res2_scale(a: ConvArgs, res2: Optional[torch.Tensor], res2_scale: Opti
         a.res2_pixscale = res2_scale.data_ptr()
 
 
+def pack_plane_chunk(w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """A one-channel 3x3 stencil (w [Co,1,3,3], b [Co]; where it feeds a 1x1 product, composed with it by compose_stem_1x1) as the weight
+    table of the stream kernels' plane chunk: fp32 [Co,16] = nine taps | bias | six zeros (csrc/plane_chunk.h)."""
+    Co = w.shape[0]
+    if tuple(w.shape) != (Co, 1, 3, 3) or tuple(b.shape) != (Co,):
+        raise ValueError("pack_plane_chunk: a [Co,1,3,3] stencil and its [Co] bias expected")
+    t = torch.zeros((Co, 16), dtype=torch.float32, device=w.device)
+    t[:, :9] = w.detach().float().reshape(Co, 9)
+    t[:, 9] = b.detach().float()
+    return t
+
+
+def plane_ok(H: int, W: int) -> bool:
+    """The shapes the plane chunk's 32-bit tap indices cover."""
+    return H > 0 and W > 0 and H * W + 2 * W + 64 < (1 << 29)
+
+
+def _plane_args(plane, B: int, H: int, W: int, Co: int, who: str):
+    """plane = (view, Bi, s_b, s_g, table[, table image stride]): image b's dense H x W fp32 plane at view.data_ptr() + 4 * ((b % Bi) * s_b +
+    (b // Bi) * s_g), all B of them inside view's storage; table: pack_plane_chunk's [Co,16] (or [B,Co,16] with its stride Co * 16)."""
+    view, Bi, s_b, s_g, table = plane[:5]
+    tstride = plane[5] if len(plane) > 5 else 0
+    if view.dtype != torch.float32 or table.dtype != torch.float32 or not table.is_contiguous() or view.device != table.device:
+        raise ValueError(f"{who}: the plane and its weight table must be fp32 tensors on one device")
+    if not plane_ok(H, W) or Bi <= 0 or s_b < 0 or s_g < 0:
+        raise ValueError(f"{who}: plane shape / strides outside the plane chunk's contract")
+    last = max((b % Bi) * s_b + (b // Bi) * s_g for b in range(B))
+    first = (view.data_ptr() - view.untyped_storage().data_ptr()) // 4
+    if (first + last + H * W) * 4 > view.untyped_storage().nbytes():
+        raise ValueError(f"{who}: the planes of {B} images leave the plane tensor's storage")
+    if tuple(table.shape[-2:]) != (Co, 16) or (tstride and (table.dim() != 3 or table.shape[0] != B or tstride != Co * 16)):
+        raise ValueError(f"{who}: the plane's weight table must be [{Co},16] (per image: [{B},{Co},16])")
+    return view, int(Bi), int(s_b), int(s_g), table, int(tstride)
+
+
 def _conv_args(srcs, pc: PackedConv, *, stride: int = 1, pad: int = 0, act: int = ACT_NONE, src_dtype=torch.float32,
                cp16: bool = False, store_mode: int = 0, out: Optional[torch.Tensor] = None, out_f16: bool = False,
                ldo: Optional[int] = None):
@@ -248,8 +283,11 @@ def conv(srcs: Sequence[torch.Tensor], pc: PackedConv, *, stride: int = 1, pad: 
          res1: Optional[torch.Tensor] = None, res2: Optional[torch.Tensor] = None,
          out: Optional[torch.Tensor] = None, prec: int = PREC_F32,
          ln: Optional[tuple] = None, s2d: bool = False, out_f16: bool = False, ln_out: Optional[tuple] = None,
-         res2_scale: Optional[torch.Tensor] = None, cp16_out: bool = False, chan_sum_out: bool = False):
-    """chan_sum_out (64-channel result): also the per-image channel sums of the result as partials; the call returns (out, part, n)
+         res2_scale: Optional[torch.Tensor] = None, cp16_out: bool = False, chan_sum_out: bool = False, plane=None):
+    """plane = (view, Bi, s_b, s_g, table) (streaming 1x1 kernel, 64-channel result; raises elsewhere): one more 64-channel operand of the
+    product that is a 3x3 stencil of the one-channel planes `view` addresses (see _plane_args) and is never materialised; table:
+    pack_plane_chunk of the product's weights for that operand composed with the stencil, [64,16] or per image [B,64,16] + stride.
+    chan_sum_out (64-channel result): also the per-image channel sums of the result as partials; the call returns (out, part, n)
     as `chan_sum_partial(out)` would give them (the streaming 1x1 kernel sums in its epilogue, every other path runs that pass).
     cp16_out (1x1, Cout = 64, 16-bit modes): also the fp16 chunk-planar copy [B,4,H,W,16] of the result (to_cp16 of the returned
     tensor) from the same kernel; the call then returns the pair (out, copy).
@@ -263,6 +301,8 @@ def conv(srcs: Sequence[torch.Tensor], pc: PackedConv, *, stride: int = 1, pad: 
             raise ValueError("conv: chan_sum_out needs a plain fp32 64-channel result")
         if not (prec != PREC_F32 and pc.ks == 1 and stride == 1 and pad == 0 and pc.CoutP == 64 and ln is None
                 and all(s.dtype == torch.float32 and s.shape[3] % 64 == 0 for s in srcs)):
+            if plane is not None:
+                raise ValueError("conv: a plane operand needs the streaming 1x1 kernel")
             o = conv(srcs, pc, stride=stride, pad=pad, act=act, res1=res1, res2=res2, out=out, prec=prec, ln=ln, res2_scale=res2_scale)
             return (o, *chan_sum_partial(o))
     src_f16 = srcs[0].dtype == torch.float16       # Block_'s fp16 body intermediate (single source, 1-pass fp16 MFMA)
@@ -275,6 +315,19 @@ def conv(srcs: Sequence[torch.Tensor], pc: PackedConv, *, stride: int = 1, pad: 
     B, Ho, Wo = a.B, a.Ho, a.Wo
     _bind_res(res1, res2, B, Ho, Wo, pc.Cout, a)
     _bind_res2_scale(a, res2, res2_scale)
+    if plane is not None:
+        if not (prec != PREC_F32 and pc.ks == 1 and stride == 1 and pad == 0 and pc.CoutP == 64 and ln is None and ln_out is None
+                and not cp16_out and res2_scale is None and not src_f16 and not out_f16
+                and all(s.shape[3] % 64 == 0 for s in srcs)):
+            raise ValueError("conv: a plane operand needs the streaming 1x1 kernel (split-bf16, plain 64-channel result)")
+        view, Bi, s_b, s_g, table, tstride = _plane_args(plane, B, a.H, a.W, 64, "conv")
+        if chan_sum_out:
+            n = align_stats_slots(B, Ho * Wo)
+            part = torch.zeros((B, n, 64), dtype=torch.float32, device=out.device)
+            a.chan_sum_out, a.chan_sum_slots = part.data_ptr(), n
+        check(_lib.lib().cdfo_conv1x1_bf16x3_plane(C.byref(a), _vp(view), Bi, C.c_longlong(s_b), C.c_longlong(s_g), _vp(table),
+                                                   C.c_longlong(tstride), _stream()), "cdfo_conv1x1_bf16x3_plane")
+        return (out, part, n) if chan_sum_out else out
     if (prec != PREC_F32 and pc.wq is not None and stride == 1 and pad == 1 and pc.w_bstride == 0):
         a.prec = prec
         a.CoutP = pc.CoutP16
@@ -1455,8 +1508,10 @@ def rdab_prep_fused_ok(x: torch.Tensor, pc: PackedConv) -> bool:
 
 
 def rdab_prep_fused(x: torch.Tensor, pc: PackedConv, vmax: torch.Tensor, noise, wW: torch.Tensor, bW: torch.Tensor,
-                    v_f16: bool = False, outs=None):
-    """conv(x, pc) (RDAB.input_conv, 64 -> 128 = q | v) followed by rdab_prep / rdab_prep_rng in ONE launch: the 128-channel product
+                    v_f16: bool = False, outs=None, plane=None):
+    """plane = (view, Bi, s_b, s_g, table): the convolution runs on x + stencil9(plane) with only x in memory (see conv's `plane`;
+    table = pack_plane_chunk(*compose_stem_1x1(stencil, input_conv without its bias)), [128,16]).
+    conv(x, pc) (RDAB.input_conv, 64 -> 128 = q | v) followed by rdab_prep / rdab_prep_rng in ONE launch: the 128-channel product
     is never written.  noise: the injected fp32 [B,64,H,W] draws, or ("rng", seed, draw, noise_out) as rdab_prep_rng takes them.
     Returns (sq, vrow, qwin, vwin) -- vwin = the v half of the product, which the two-kernel path reads from xq[..., 64:].
     v_f16 (a bool for both, or a pair (vrow, vwin)): that output as fp16, each value rounded once (what seq_attn's modes 20-22 do
@@ -1488,10 +1543,15 @@ def rdab_prep_fused(x: torch.Tensor, pc: PackedConv, vmax: torch.Tensor, noise, 
         noise_in = noise
         if tuple(noise.shape) != (B, 64, H, W) or not noise.is_contiguous() or noise.dtype != torch.float32:
             raise ValueError("rdab_prep_fused: noise must be a contiguous fp32 [B,64,H,W] tensor")
-    check(_lib.lib().cdfo_rdab_prep_fused(_vp(x), ld, _vp(pc.w), _vp(pc.bias), _vp(vmax), _vp(noise_in), C.c_longlong(seed),
-                                          _vp(seed_dev), draw, _vp(noise_out), _vp(wW), _vp(bW), B, C.c_longlong(H * W),
-                                          _vp(sq), 64, _vp(vrow), 64, _vp(qwin), 64, _vp(vwin), 64, int(row16) + 2 * int(win16), _stream()),
-          "cdfo_rdab_prep_fused")
+    args = (_vp(x), ld, _vp(pc.w), _vp(pc.bias), _vp(vmax), _vp(noise_in), C.c_longlong(seed), _vp(seed_dev), draw, _vp(noise_out),
+            _vp(wW), _vp(bW), B, C.c_longlong(H * W), _vp(sq), 64, _vp(vrow), 64, _vp(qwin), 64, _vp(vwin), 64,
+            int(row16) + 2 * int(win16))
+    if plane is not None:
+        view, Bi, s_b, s_g, table, _ = _plane_args(plane[:5], B, H, W, 128, "rdab_prep_fused")
+        check(_lib.lib().cdfo_rdab_prep_fused_plane(*args, _vp(view), Bi, C.c_longlong(s_b), C.c_longlong(s_g), W, _vp(table), _stream()),
+              "cdfo_rdab_prep_fused_plane")
+    else:
+        check(_lib.lib().cdfo_rdab_prep_fused(*args, _stream()), "cdfo_rdab_prep_fused")
     return sq, vrow, qwin, vwin
 
 

@@ -174,6 +174,15 @@ int cdfo_to_cp16(const float* in, int ldi, int B, long long P, int C, void* out_
  * fp16 hi | lo chunk-planar planes [B][8][P][16] (what cdfo_layernorm64_cp16hl would produce from `out`); with out2_cp16 set and
  * ln_gamma == ln_beta == NULL (round 4) the second output is the result itself as fp16 chunk-planar [B][4][P][16] (= cdfo_to_cp16(out)).  */
 int cdfo_conv1x1_bf16x3(const cdfo_conv_args* a, void* stream);
+/* The same with one more 64-channel operand of the product that is a 3x3 stencil (zero padding) of a ONE-channel H x W plane and is
+ * never materialised (streaming form only: plain store, Cout <= CoutP = 64, no out2_cp16, no res2_pixscale, H W + 2 W + 64 < 2^29;
+ * CDFO_EINVAL otherwise -- there is no other kernel for it).  Image b's plane (dense fp32 rows) starts at plane + (b % plane_Bi) plane_sb
+ * + (b / plane_Bi) plane_sg floats.  plane_w [CoutP][16] fp32, 16-byte aligned, image pitch plane_w_bstride floats (0: shared): row n =
+ * sum_c W[n][c] w_s[c][0..8] | sum_c W[n][c] b_s[c] | six zeros, W the product's weights for that operand (the identity where the operand
+ * is simply added to the result), (w_s, b_s) the stencil.  It enters the product as one split-bf16 k-step of 16 (the nine neighbours and a
+ * constant 1, built in registers) before bias and activation; a->chan_sum_out works as without it.  */
+int cdfo_conv1x1_bf16x3_plane(const cdfo_conv_args* a, const float* plane, int plane_Bi, long long plane_sb, long long plane_sg,
+                              const float* plane_w, long long plane_w_bstride, void* stream);
 
 /* Upsampler tail without the HR feature map (arch.py:4474-4480).  cdfo_conv1x1_bf16x3 with a->store_mode =
  * CDFO_STORE_TAPS9 (upconv2: Cout = 256, pixel-shuffle weight packing, LeakyReLU; a->res2 = conv_last.weight
@@ -313,6 +322,17 @@ int cdfo_rdab_prep_fused(const float* x, int ldx, const float* w_packed, const f
                          const float* noise, long long seed, const void* seed_dev, int draw, float* noise_out,
                          const float* wW, const float* bW, int B, long long P, float* sq, int lds_, void* vrow, int ldv,
                          float* qwin, int ldw, void* vwin, int ldvw, int v_f16, void* stream);
+/* cdfo_rdab_prep_fused on x + stencil9(plane; w_s, b_s) (fea_com = fea + conv_expand_rms(rms), arch.py:4446-4449) with only x in
+ * memory: the stencil's part joins the product as one split-bf16 k-step of 16 whose pixel operand (nine neighbours, zero padding, and a
+ * constant 1) is built from the one-channel plane.  Image b's plane (P / W rows of W pixels, dense fp32) starts at plane +
+ * (b % plane_Bi) plane_sb + (b / plane_Bi) plane_sg floats; plane_w [128][16] fp32, 16-byte aligned: row n = sum_c Wconv[n][c] w_s[c][0..8]
+ * | sum_c Wconv[n][c] b_s[c] | six zeros.  The mask depends on vmax and the draws alone and is the same as on the materialised sum; q and
+ * v agree with it to the product's fp32-grade rounding.  P + 2 W + 64 < 2^29. */
+int cdfo_rdab_prep_fused_plane(const float* x, int ldx, const float* w_packed, const float* bias, const float* vmax,
+                               const float* noise, long long seed, const void* seed_dev, int draw, float* noise_out,
+                               const float* wW, const float* bW, int B, long long P, float* sq, int lds_, void* vrow, int ldv,
+                               float* qwin, int ldw, void* vwin, int ldvw, int v_f16, const float* plane, int plane_Bi,
+                               long long plane_sb, long long plane_sg, int W, const float* plane_w, void* stream);
 int cdfo_colconv9(const float* in, int ldi, const float* wH, const float* bH, int B, int H, int W, float* out, int ldo,
                   void* stream);
 /* Evaluation metrics on the device (metric/psnr_ssim.py:278-317 calculate_psnr, :320-399 _ssim / calculate_ssim): fp64
