@@ -27,7 +27,10 @@ reference's no-reference metric (metric/cal_VideoLQ.py scores every output frame
 without ground truth (`metrics.niqe_features_u8`): seven launches behind ``cdfo_finish_frames`` on the main
 stream, no wait for the device; the scores are formed on the host after the last chunk.  ``brisque=`` a support-vector model adds the
 reference's other live no-reference figure (metric/brisque.py) the same way (`metrics.brisque_features_u8`, DESIGN.md section
-5.00000000000000): seven launches of its own per chunk, 36 features per frame kept on the device until the last chunk.
+5.00000000000000): seven launches of its own per chunk, 36 features per frame kept on the device until the last chunk.  ``tof=True``
+adds the reference's temporal-consistency figure tOF (metric/psnr_ssim.py: calculate_tOF) with ground truth on 8-bit luma: the
+Farneback flows of the chunk's ground-truth pairs and result pairs go through the same launches behind BRISQUE's
+(`metrics.tof_frames_u8`), the frame in front of the chunk carried on the device.
 
 Deliberate deviation: ``cal_psnr_ssim`` sends single-channel frames through ``to_y_channel``, an fp32 ``/255*255`` round
 trip, and takes fp32 means.  The metric semantics here are the project's established ones, ``oracle/metrics_ref.py``: fp64 on the
@@ -71,13 +74,15 @@ class SequenceResult(NamedTuple):
     mean_niqe: float = float("nan")
     brisque: np.ndarray = _NO_FRAMES                # fp64 [T] with ``brisque=`` a model (ground truth or not), else empty
     mean_brisque: float = float("nan")
+    tof: np.ndarray = _NO_FRAMES                    # fp64 [T] with ``tof=True`` (needs ground truth), else empty
+    mean_tof: float = float("nan")
 
 
 def format_log(result: SequenceResult, name: str) -> str:
     """The reference's log line (psnr_ssim.py:481); with MS-SSIM figures, `` MS-SSIM: %.5f`` behind it, with NIQE figures
-    `` NIQE: %.5f`` behind that, with BRISQUE figures `` BRISQUE: %.5f`` last."""
+    `` NIQE: %.5f`` behind that, with BRISQUE figures `` BRISQUE: %.5f``, with tOF figures `` tOF: %.5f`` last."""
     return '%s Average PSNR/SSIM: %.3f/%.5f' % (name, result.mean_psnr, result.mean_ssim) + _msssim_suffix(result) + _niqe_suffix(result) + \
-        _brisque_suffix(result)
+        _brisque_suffix(result) + _tof_suffix(result)
 
 
 def _msssim_suffix(result) -> str:
@@ -90,6 +95,10 @@ def _niqe_suffix(result) -> str:
 
 def _brisque_suffix(result) -> str:
     return ' BRISQUE: %.5f' % result.mean_brisque if len(result.brisque) else ''
+
+
+def _tof_suffix(result) -> str:
+    return ' tOF: %.5f' % result.mean_tof if len(result.tof) else ''
 
 
 def quantise_numpy(x: np.ndarray, mode: str = "trunc", peak: int = 255) -> np.ndarray:
@@ -175,6 +184,19 @@ def _check_brisque(lr, brisque):
 def _brisque(features: np.ndarray, params) -> np.ndarray:
     """Per-frame BRISQUE from the loop's features; empty where it has none."""
     return np.atleast_1d(M.brisque_from_features(features, params)) if len(features) else np.zeros(0, np.float64)
+
+
+def _check_tof(lr, gt, tof) -> bool:
+    """Whether tOF runs, before any device work: ValueError without ground truth, above 8 bits (the reference computes the flow of
+    8-bit images) and for a common region below 32 x 32 (`metrics.tof_size`)."""
+    if not tof:
+        return False
+    if gt is None:
+        raise ValueError("tof: the metric compares the result's flow with the ground truth's, and there is no ground truth")
+    if lr.dtype != torch.uint8:
+        raise ValueError(f"tof: the metric is defined on 8-bit samples, the format's peak is {lr.peak}")
+    M.tof_size(min(4 * lr.shape[0], gt.shape[0]), min(4 * lr.shape[1], gt.shape[1]))
+    return True
 
 
 def _psnr(sse: np.ndarray, shape, gt_shape, crop: int, peak: int) -> np.ndarray:
@@ -288,7 +310,7 @@ class _Slots:
 
 
 def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: int, ccrop: int, quantise: str, workers: int,
-                msssim: bool = False, niqe: bool = False, brisque: bool = False):
+                msssim: bool = False, niqe: bool = False, brisque: bool = False, tof: bool = False):
     """The chunk loop of both evaluators.  ``lr``: the LR sequence as a frame source (its counts, shapes, dtype and peak; its frames
     come from ``load``).  ``load()`` -> (`StreamingSR`, (u, v) LR chroma planes [T,h,w] or None); it runs after the first
     ground-truth reads have been handed to the pool.  ``gt``: a frame source or None.  ``sink``: a frame sink or None.
@@ -296,9 +318,12 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
     exists once (every call that writes or reads it is on that stream, which orders them).  ``niqe``: `metrics.niqe_features_u8` on the
     chunk's 8-bit luma, with or without ground truth, on the main stream too, its scratch held the same way; like SSIM's sums the
     features stay on the device until the last chunk.  ``brisque``: `metrics.brisque_features_u8` likewise, behind NIQE's launches.
+    ``tof``: with ground truth, `metrics.tof_frames_u8` behind those, its scratch held once as well; the last ground-truth frame and
+    the last result frame of a chunk are copied into two one-frame buffers, the next chunk's first pair.
     -> (the `StreamingSR`, sse_y int64 [T], sse_uv int64 [2,T], ssim fp64 [T], MS-SSIM components fp64 [T,5,2], NIQE features fp64
-    [T,nb,36], BRISQUE features fp64 [T,36]); the arrays are empty without ground truth (sse_uv without chroma, the components
-    without ``msssim``), the features without ``niqe`` / ``brisque``.  The module's docstring has the order of events."""
+    [T,nb,36], BRISQUE features fp64 [T,36], tOF fp64 [T]); the arrays are empty without ground truth (sse_uv without chroma, the
+    components without ``msssim``, tOF without ``tof``), the features without ``niqe`` / ``brisque``.  The module's docstring has the
+    order of events."""
     T, kmax, kind, peak = lr.frames, min(chunk, lr.frames), lr.dtype, lr.peak
     has_c = lr.chroma_shape is not None
     out_y, out_c = (shape and (4 * shape[0], 4 * shape[1]) for shape in (lr.shape, lr.chroma_shape))      # None stays None
@@ -334,6 +359,10 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
                 ms_scratch = M.msssim_scratch(kmax, *M.msssim_region(*out_y, *gt_y, crop), dev)
             nq, nq_scratch = [], M.niqe_scratch(kmax, *M.niqe_region(*out_y), dev) if niqe else None
             bq, bq_scratch = [], M.brisque_scratch(kmax, *out_y, dev) if brisque else None
+            tf, tf_scratch, tf_gt, tf_sr = [], None, None, None
+            if tof and gt is not None:
+                tf_scratch = M.tof_scratch(2 * kmax, min(out_y[0], gt_y[0]), min(out_y[1], gt_y[1]), dev)
+                tf_carry = (on_dev(gt_y), on_dev(out_y))          # the frames in front of the next chunk: ground truth, result
             chunks = s.iter_chunked(chunk, share_compensation)
             for c in range((T + chunk - 1) // chunk):
                 u, d = up[c], down[c]
@@ -374,6 +403,11 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
                     nq.append(M.niqe_features_u8(y8, nq_scratch))
                 if bq_scratch is not None:
                     bq.append(M.brisque_features_u8(y8, bq_scratch))
+                if tf_scratch is not None:
+                    tf.append(M.tof_frames_u8(gy, y8, tf_gt, tf_sr, tf_scratch))
+                    tf_gt, tf_sr = tf_carry
+                    tf_gt.copy_(gy[k - 1])
+                    tf_sr.copy_(y8[k - 1])
                 if sink is not None:
                     ready = torch.cuda.Event()
                     ready.record(main)
@@ -390,7 +424,7 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
             host = lambda parts, dim, empty: torch.cat(parts, dim=dim).cpu().numpy() if parts else np.zeros(empty, np.int64)
             result = (s, host(sse_y, 0, 0), host(sse_c, 1, (2, 0)), host(ssim, 0, 0).astype(np.float64),
                       host(ms, 0, (0, 5, 2)).astype(np.float64), host(nq, 0, (0, 1, 36)).astype(np.float64),
-                      host(bq, 0, (0, 36)).astype(np.float64))
+                      host(bq, 0, (0, 36)).astype(np.float64), host(tf, 0, 0).astype(np.float64))
             torch.cuda.synchronize(dev)
     return result
 
@@ -398,7 +432,8 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
 def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] = None, save_dir: Optional[str] = None, chunk: int = 8,
                       share_compensation: bool = False, crop_border: int = 4, quantise: str = "trunc", workers: int = 8,
                       png_level: int = 6, gumbel_uniform: Optional[Sequence] = None,
-                      frame_noise: Optional[Sequence] = None, msssim: bool = False, niqe=None, brisque=None) -> SequenceResult:
+                      frame_noise: Optional[Sequence] = None, msssim: bool = False, niqe=None, brisque=None,
+                      tof: bool = False) -> SequenceResult:
     """Super-resolve the sequence in ``lr_dir`` / ``side_dir`` (the reference's test layout, see cdfo_amd/priors.py) with ``model`` (on a
     GPU), ``chunk`` centre frames per forward.  ``save_dir``: write every frame as an 8-bit PNG under its LR file name.  ``gt_dir``:
     per-frame PSNR / SSIM of the 8-bit frames against ``<gt_dir>/%05d.png`` over the common size less ``crop_border``.
@@ -411,7 +446,9 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
     better), WITH OR WITHOUT ground truth; the x4 frames must hold one 96 x 96 block.  ``brisque``: the support-vector model of the
     no-reference metric BRISQUE, a path, the five arrays or a `metrics.BrisqueParams` (`metrics.brisque_params`; the project ships no
     model); every output frame is then scored as well (`metrics.brisque_u8`, lower is better), with or without ground truth; the x4
-    frames must be at least 16 x 16."""
+    frames must be at least 16 x 16.  ``tof``: with ground truth, per-frame tOF as well (`metrics.tof_u8`: the mean distance between
+    the Farneback flow of consecutive ground-truth frames and that of consecutive result frames over the whole common region, no
+    border dropped; lower is better); the region must be at least 32 x 32, and without ground truth it is a ValueError."""
     workers, chunk = _check_args(workers, quantise, chunk)
     t_start = time.perf_counter()
     lr = _PngSource(lr_dir)
@@ -423,6 +460,7 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
         _check_regions(lr, gt, crop_border, 0)
         if msssim:
             _check_msssim(lr, gt, crop_border)
+    tof = _check_tof(lr, gt, tof)
     if save_dir is not None:
         sink = _PngSink(save_dir, lr.names, png_level)   # the result PNGs take the LR frames' names (test_LD_37.py:180)
 
@@ -431,12 +469,12 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
         return StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"], gumbel_uniform=gumbel_uniform,
                            frame_noise=frame_noise), None
 
-    s, sse, _, ssim, ms, nq, bq = _run_chunks(lr, load, gt, sink, chunk, share_compensation, crop_border, 0, quantise, workers, msssim,
-                                              nq_params is not None, bq_params is not None)
+    s, sse, _, ssim, ms, nq, bq, tf = _run_chunks(lr, load, gt, sink, chunk, share_compensation, crop_border, 0, quantise, workers,
+                                                  msssim, nq_params is not None, bq_params is not None, tof)
     psnr, ms, nq = _psnr(sse, lr.shape, gt and gt.shape, crop_border, 255), M.msssim_from_components(ms), _niqe(nq, nq_params)
     bq = _brisque(bq, bq_params)
     return SequenceResult(psnr, ssim, _mean(psnr), _mean(ssim), lr.frames, s.seconds, time.perf_counter() - t_start, ms, _mean(ms),
-                          nq, _mean(nq), bq, _mean(bq))
+                          nq, _mean(nq), bq, _mean(bq), tf, _mean(tf))
 
 
 class YuvResult(NamedTuple):
@@ -459,13 +497,15 @@ class YuvResult(NamedTuple):
     mean_niqe: float = float("nan")
     brisque: np.ndarray = _NO_FRAMES                # of the luma; fp64 [T] with ``brisque=`` a model (ground truth or not), else empty
     mean_brisque: float = float("nan")
+    tof: np.ndarray = _NO_FRAMES                    # of the luma; fp64 [T] with ``tof=True`` (needs ground truth), else empty
+    mean_tof: float = float("nan")
 
 
 def format_log_yuv(result: YuvResult, name: str) -> str:
     """`format_log` for a 4:2:0 result: the luma figures in the reference's places, then the chroma and the combined PSNR."""
     return '%s Average PSNR/SSIM: %.3f/%.5f PSNR-U/V/YUV: %.3f/%.3f/%.3f' % (
         name, result.mean_psnr_y, result.mean_ssim_y, result.mean_psnr_u, result.mean_psnr_v, result.mean_psnr_yuv) + _msssim_suffix(result) + \
-        _niqe_suffix(result) + _brisque_suffix(result)
+        _niqe_suffix(result) + _brisque_suffix(result) + _tof_suffix(result)
 
 
 def chroma_crop(crop_border: int, chroma: str = "420") -> int:
@@ -485,7 +525,7 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
                  save_yuv: Optional[str] = None, chunk: int = 8, share_compensation: bool = False, crop_border: int = 4,
                  quantise: str = "trunc", workers: int = 8, gumbel_uniform: Optional[Sequence] = None,
                  frame_noise: Optional[Sequence] = None, gt_size: Optional[Tuple[int, int]] = None,
-                 pix_fmt: str = "yuv420p", msssim: bool = False, niqe=None, brisque=None) -> YuvResult:
+                 pix_fmt: str = "yuv420p", msssim: bool = False, niqe=None, brisque=None, tof: bool = False) -> YuvResult:
     """`evaluate_sequence` on raw 8-bit I420 files (cdfo_amd/yuv.py).  ``lr_yuv``: the LR sequence, ``width`` x ``height`` (even);
     the coding priors stay in ``side_dir``.  The luma goes the way it goes there (`StreamingSR.iter_chunked`, ``finish_frames`` with the
     PSNR numerator, ``ssim_u8``).  The chroma never passes through the model: per chunk the U and V planes of its centre frames are
@@ -501,7 +541,8 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     empty and ``psnr_yuv`` is ``psnr_y``.  ``yuv444p*``: chroma planes of the luma's size, their border ``crop_border``.
     ``msssim``: as `evaluate_sequence`'s, on the luma (`metrics.msssim_u8` / `msssim_u16` with the format's peak).  ``niqe``: as
     `evaluate_sequence`'s, on the luma of 8-bit formats; above 8 bits it is a ValueError (the reference defines the metric on 0 .. 255
-    integers).  ``brisque``: as `evaluate_sequence`'s, with the same restriction to 8-bit formats."""
+    integers).  ``brisque``: as `evaluate_sequence`'s, with the same restriction to 8-bit formats.  ``tof``: as `evaluate_sequence`'s, on
+    the luma of 8-bit formats with ground truth."""
     fmt = parse_pix_fmt(pix_fmt)
     workers, chunk = _check_args(workers, quantise, chunk)
     t_start = time.perf_counter()
@@ -521,6 +562,7 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
             _check_regions(lr, gt, crop_border, ccrop)
             if msssim:
                 _check_msssim(lr, gt, crop_border)
+        tof = _check_tof(lr, gt, tof)
         writer = YuvWriter(save_yuv, 4 * width, 4 * height, fmt) if save_yuv is not None else None
 
         def load():
@@ -529,8 +571,9 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
             return StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"],
                                gumbel_uniform=gumbel_uniform, frame_noise=frame_noise, peak=fmt.peak), lr_c
 
-        s, sse_y, sse_c, ssim, ms, nq, bq = _run_chunks(lr, load, gt, writer and _YuvSink(writer), chunk, share_compensation, crop_border,
-                                                        ccrop, quantise, workers, msssim, nq_params is not None, bq_params is not None)
+        s, sse_y, sse_c, ssim, ms, nq, bq, tf = _run_chunks(lr, load, gt, writer and _YuvSink(writer), chunk, share_compensation,
+                                                            crop_border, ccrop, quantise, workers, msssim, nq_params is not None,
+                                                            bq_params is not None, tof)
     finally:
         if writer is not None:
             writer.close()
@@ -541,7 +584,7 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     pyuv = psnr_yuv(py, pu, pv) if lr.chroma_shape is not None else py
     ms, nq, bq = M.msssim_from_components(ms), _niqe(nq, nq_params), _brisque(bq, bq_params)
     return YuvResult(py, pu, pv, ssim, pyuv, _mean(py), _mean(pu), _mean(pv), _mean(ssim), _mean(pyuv), lr.frames, s.seconds,
-                     time.perf_counter() - t_start, ms, _mean(ms), nq, _mean(nq), bq, _mean(bq))
+                     time.perf_counter() - t_start, ms, _mean(ms), nq, _mean(nq), bq, _mean(bq), tf, _mean(tf))
 
 
 def _write_synthetic(root: str, T: int, H: int, W: int, seed: int, put_lr, put_gt, peak: int = 255) -> str:

@@ -942,6 +942,114 @@ def brisque_features(partials: torch.Tensor, count: int, table: torch.Tensor, sc
     return out
 
 
+# ---- tOF's Farneback flow (csrc/tof.hip); cdfo_amd/metrics.py builds the taps and puts the stages together ----
+TOF_MIN, TOF_MAX_TAPS, TOF_STRIP = 32, 19, 16           # CDFO_TOF_MIN, CDFO_TOF_MAX_TAPS, CDFO_TOF_STRIP
+
+
+def _tof_f64(t: torch.Tensor, dims: int, name: str) -> tuple:
+    """The shape of a dense device fp64 tensor of ``dims`` dimensions with no empty one."""
+    if not t.is_cuda or t.dtype != torch.float64 or t.dim() != dims or not t.is_contiguous() or 0 in t.shape:
+        raise ValueError(f"{name}: a dense device fp64 tensor of {dims} dimensions expected, got {t.dtype} {tuple(t.shape)} "
+                         f"strides {t.stride()}")
+    return tuple(int(v) for v in t.shape)
+
+
+def tof_level(prev: torch.Tensor, cur: torch.Tensor, h: int, w: int, taps, first: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """prev, cur: uint8 frames [K,H,W] (or [H,W]) on the device with contiguous rows, read in place -> fp64 [K,2,h,w]: per pair the
+    level image of its previous frame and of its current one, smoothed with the odd number of ``taps`` (a host array, at most 19)
+    down the columns and along the rows, reflect-101, then resized to h x w bilinearly.  Pair j is (prev[j], cur[j]); with ``first``
+    (uint8 [H,W]) it is (first, cur[0]) for j = 0 and (prev[j - 1], cur[j]) beyond, so ``prev`` may then be ``cur`` itself."""
+    c, N, H, W, cp, cs = _sample_frames(cur, "tof_level: cur", torch.uint8)
+    p, Np, Hp, Wp, pp, ps = _sample_frames(prev, "tof_level: prev", torch.uint8)
+    f = fp = None
+    if first is not None:
+        f, Nf, Hf, Wf, fp, _ = _sample_frames(first, "tof_level: first", torch.uint8)
+        if (Nf, Hf, Wf) != (1, H, W) or f.device != c.device:
+            raise ValueError(f"tof_level: first must be one frame of {H} x {W} on cur's device, got {tuple(f.shape)}")
+    if N <= 0 or (Hp, Wp) != (H, W) or Np < (N if first is None else N - 1) or p.device != c.device:
+        raise ValueError(f"tof_level: prev {tuple(p.shape)} does not pair with cur {tuple(c.shape)}")
+    h, w = int(h), int(w)
+    if min(H, W) < TOF_MIN or not 0 < h <= H or not 0 < w <= W:
+        raise ValueError(f"tof_level: frames of at least {TOF_MIN} x {TOF_MIN} and a level no larger expected, got {H} x {W} -> {h} x {w}")
+    t = np.ascontiguousarray(taps, dtype=np.float64).reshape(-1)
+    if not 3 <= t.size <= TOF_MAX_TAPS or t.size % 2 == 0 or t.size // 2 >= min(H, W):
+        raise ValueError(f"tof_level: an odd number of taps in 3 .. {TOF_MAX_TAPS} expected, got {t.size}")
+    out = _f64_out(out, (N, 2, h, w), c, "tof_level")
+    with on_device(c):
+        check(_lib.lib().cdfo_tof_level_u8(_vp(p), pp, C.c_longlong(ps), _vp(c), cp, C.c_longlong(cs), _vp(f), fp or 0, N, H, W, h, w,
+                                           C.c_void_p(t.ctypes.data), int(t.size), _vp(out), _stream()), "cdfo_tof_level_u8")
+    return out
+
+
+def tof_polyexp(img: torch.Tensor, kernels, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """img: dense fp64 [...,h,w] -> fp64 [...,5,h,w] = (b_x, b_y, a_xx, a_yy, a_xy), the edge sample repeated.  ``kernels``: 37 fp64
+    values on the host, the taps g, x g, x^2 g (11 each) and the inverse Gram matrix's entries [1][1], [0][3], [3][3], [5][5]."""
+    shape = _tof_f64(img, img.dim(), "tof_polyexp: img")
+    if len(shape) < 2:
+        raise ValueError(f"tof_polyexp: images [...,h,w] expected, got {shape}")
+    k = np.ascontiguousarray(kernels, dtype=np.float64).reshape(-1)
+    if k.size != 37:
+        raise ValueError(f"tof_polyexp: 37 kernel values expected, got {k.size}")
+    h, w = shape[-2:]
+    out = _f64_out(out, shape[:-2] + (5, h, w), img, "tof_polyexp")
+    with on_device(img):
+        check(_lib.lib().cdfo_tof_polyexp(_vp(img), int(np.prod(shape[:-2], dtype=np.int64)), h, w, C.c_void_p(k.ctypes.data), _vp(out),
+                                          _stream()), "cdfo_tof_polyexp")
+    return out
+
+
+def tof_matrices(R: torch.Tensor, flow: Optional[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """R: dense fp64 [N,2,5,h,w] (per pair the previous frame's expansion, then the current one's); flow: dense fp64 [N,h,w,2] or
+    None for zeros -> fp64 [N,5,h,w]: the planes of the normal equations, border factors applied."""
+    N, two, five, h, w = _tof_f64(R, 5, "tof_matrices: R")
+    if (two, five) != (2, 5) or min(h, w) < 2:
+        raise ValueError(f"tof_matrices: R [N,2,5,h,w] of at least 2 x 2 expected, got {tuple(R.shape)}")
+    if flow is not None and (_tof_f64(flow, 4, "tof_matrices: flow") != (N, h, w, 2) or flow.device != R.device):
+        raise ValueError(f"tof_matrices: flow [{N},{h},{w},2] on R's device expected, got {tuple(flow.shape)}")
+    out = _f64_out(out, (N, 5, h, w), R, "tof_matrices")
+    with on_device(R):
+        check(_lib.lib().cdfo_tof_matrices(_vp(R), _vp(flow), N, h, w, _vp(out), _stream()), "cdfo_tof_matrices")
+    return out
+
+
+def tof_blur_solve(M: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """M: dense fp64 [N,5,h,w] -> the flow fp64 [N,h,w,2]: the 15 x 15 box mean of each plane (direct sums in a fixed order, the edge
+    sample repeated), then the 2 x 2 solve."""
+    N, five, h, w = _tof_f64(M, 4, "tof_blur_solve: M")
+    if five != 5:
+        raise ValueError(f"tof_blur_solve: M [N,5,h,w] expected, got {tuple(M.shape)}")
+    out = _f64_out(out, (N, h, w, 2), M, "tof_blur_solve")
+    with on_device(M):
+        check(_lib.lib().cdfo_tof_blur_solve(_vp(M), N, h, w, _vp(out), _stream()), "cdfo_tof_blur_solve")
+    return out
+
+
+def tof_flow_up(flow: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """flow: dense fp64 [N,hp,wp,2] -> fp64 [N,h,w,2]: the flow on the next stage's grid (bilinear, both taps clamped), times 2."""
+    N, hp, wp, two = _tof_f64(flow, 4, "tof_flow_up: flow")
+    h, w = int(h), int(w)
+    if two != 2 or h <= 0 or w <= 0:
+        raise ValueError(f"tof_flow_up: flow [N,hp,wp,2] and a size expected, got {tuple(flow.shape)} -> {h} x {w}")
+    out = _f64_out(out, (N, h, w, 2), flow, "tof_flow_up")
+    with on_device(flow):
+        check(_lib.lib().cdfo_tof_flow_up(_vp(flow), N, hp, wp, h, w, _vp(out), _stream()), "cdfo_tof_flow_up")
+    return out
+
+
+def tof_epe(a: torch.Tensor, b: torch.Tensor, partials: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a, b: dense fp64 flows [K,h,w,2] -> fp64 [K]: the mean endpoint distance per frame.  Strips of 16 rows are summed by one
+    workgroup each, then added in index order by one workgroup per frame: the order depends on the shape alone."""
+    K_, h, w, two = _tof_f64(a, 4, "tof_epe: a")
+    if two != 2 or _tof_f64(b, 4, "tof_epe: b") != (K_, h, w, 2) or b.device != a.device:
+        raise ValueError(f"tof_epe: two flows [K,h,w,2] on one device expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    partials = _f64_out(partials, (K_, (h + TOF_STRIP - 1) // TOF_STRIP), a, "tof_epe: partials")
+    out = _f64_out(out, (K_,), a, "tof_epe")
+    with on_device(a):
+        check(_lib.lib().cdfo_tof_epe(_vp(a), _vp(b), K_, h, w, _vp(partials), _vp(out), _stream()), "cdfo_tof_epe")
+    return out
+
+
 def stem_conv(img: torch.Tensor, img_bstride: int, B: int, H: int, W: int, w: torch.Tensor, bias: torch.Tensor,
               act: int = ACT_NONE, add: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
               out2: Optional[torch.Tensor] = None, write_out: bool = True):

@@ -21,6 +21,11 @@ tests/msssim_ref.py is its numpy statement).  The device leaves ten means per fr
 ``brisque_u8``: the reference's other live no-reference metric (metric/brisque.py) of such frames, with a support-vector model the
 caller brings (``brisque_params``).  The device leaves 36 features per frame (``brisque_features_u8``), the host forms the score in
 fp64 (``brisque_from_features``); DESIGN.md has the definition, tests/brisque_ref.py is its numpy statement.
+
+``tof_u8``: the reference's temporal-consistency figure tOF (metric/psnr_ssim.py: calculate_tOF) of two such stacks, ground truth and
+result: the mean endpoint distance between their dense Farneback flows (``farneback_u8``; per chunk ``tof_frames_u8``).  The
+definition is the project's own, after the algorithm OpenCV documents, with the reference's arguments; cv2 parity is unpinned.
+DESIGN.md has the definition, tests/tof_ref.py is its numpy statement.
 """
 from __future__ import annotations
 
@@ -567,3 +572,179 @@ def brisque_u8(frames: torch.Tensor, params) -> np.ndarray:
     the project ships none."""
     params = params if isinstance(params, BrisqueParams) else brisque_params(params)
     return np.atleast_1d(brisque_from_features(brisque_features_u8(frames), params))
+
+
+# ---- tOF: the distance between the Farneback flows of ground truth and result (DESIGN.md has the definition; csrc/tof.hip) ----
+TOF_MIN = K.TOF_MIN                                     # the smallest region, each way
+TOF_LEVELS, TOF_WINSIZE, TOF_ITERATIONS, TOF_POLY_N, TOF_POLY_SIGMA = 3, 15, 3, 5, 1.2      # the reference's arguments
+_tof_host = {}                                          # the taps per stage and the expansion's kernels: built once per process
+
+
+def tof_size(h: int, w: int):
+    """[(k, h_k, w_k)] for the stages k = L .. 0 of an h x w region, coarsest first: a stage exists while both sides scaled by
+    0.5^k stay at least 32, at most three beyond the full size; sizes round half to even.  ValueError below 32 x 32."""
+    h, w = int(h), int(w)
+    if h < TOF_MIN or w < TOF_MIN:
+        raise ValueError(f"tOF needs a region of at least {TOF_MIN} x {TOF_MIN}, got {h} x {w}")
+    L, s = 0, 1.0
+    for k in range(TOF_LEVELS):
+        s *= 0.5
+        if w * s < TOF_MIN or h * s < TOF_MIN:
+            break
+        L = k + 1
+    return [(k, int(np.rint(h * 0.5 ** k)), int(np.rint(w * 0.5 ** k))) for k in range(L, -1, -1)]
+
+
+def tof_taps(k: int) -> np.ndarray:
+    """The smoothing taps of stage k: sigma = (2^k - 1) / 2, max(rint(5 sigma) | 1, 3) taps of a normalised Gaussian; [1/4, 1/2, 1/4]
+    at sigma = 0."""
+    if ("taps", k) not in _tof_host:
+        sigma = (1.0 / 0.5 ** k - 1.0) / 2.0
+        n = max(int(np.rint(5.0 * sigma)) | 1, 3)
+        if sigma == 0.0:
+            t = np.array([0.25, 0.5, 0.25])
+        else:
+            x = np.arange(n, dtype=np.float64) - (n - 1) // 2
+            t = np.exp(-(x * x) / (2.0 * sigma * sigma))
+            t = t / t.sum()
+        t.setflags(write=False)
+        _tof_host["taps", k] = t
+    return _tof_host["taps", k]
+
+
+def tof_poly_kernels() -> np.ndarray:
+    """fp64 [37]: the expansion's taps g, x g, x^2 g over x = -5 .. 5 (g the normalised Gaussian of sigma 1.2), then the entries
+    [1][1], [0][3], [3][3], [5][5] of the inverse Gram matrix of 1, x, y, x^2, y^2, xy under g (x) g -- the ones symmetry leaves."""
+    if "poly" not in _tof_host:
+        x = np.arange(-TOF_POLY_N, TOF_POLY_N + 1, dtype=np.float64)
+        g = np.exp(-(x * x) / (2.0 * TOF_POLY_SIGMA * TOF_POLY_SIGMA))
+        g = g / g.sum()
+        X, Y = np.meshgrid(x, x)
+        basis = np.stack([np.ones_like(X), X, Y, X * X, Y * Y, X * Y]).reshape(6, -1)
+        inv = np.linalg.inv((basis * np.outer(g, g).reshape(-1)) @ basis.T)
+        k = np.concatenate([g, x * g, x * x * g, [inv[1, 1], inv[0, 3], inv[3, 3], inv[5, 5]]])
+        k.setflags(write=False)
+        _tof_host["poly"] = k
+    return _tof_host["poly"]
+
+
+class TofScratch:
+    """What the Farneback launches need beside their frames, for groups of up to ``pairs`` frame pairs of an ``h`` x ``w`` region:
+    per pair two level images, their ten coefficient planes, five planes of normal equations and two flows, all fp64 (21 values per
+    pixel and pair), and the strips' sums.  ``nbytes``: its size.  Calls that share one must be ordered, which one stream does."""
+
+    def __init__(self, pairs: int, h: int, w: int, device):
+        pairs = int(pairs)
+        self.stages = tof_size(h, w)
+        if pairs <= 0:
+            raise ValueError(f"no tOF scratch for {pairs} pairs")
+        h, w = int(h), int(w)
+        f64 = lambda n: torch.empty(n, dtype=torch.float64, device=device)
+        px = pairs * h * w
+        self.img, self.R, self.M, self.flow, self.up = f64(2 * px), f64(10 * px), f64(5 * px), f64(2 * px), f64(2 * px)
+        self.partials = f64(pairs * ((h + K.TOF_STRIP - 1) // K.TOF_STRIP))
+        self.pairs, self.h, self.w, self.device = pairs, h, w, self.img.device
+        self.nbytes = 8 * sum(t.numel() for t in (self.img, self.R, self.M, self.flow, self.up, self.partials))
+
+
+def tof_scratch(n: int, h: int, w: int, device) -> TofScratch:
+    """A `TofScratch` for groups of ``n`` pairs: what `farneback_u8` and `tof_frames_u8` make per call unless they are handed one."""
+    return TofScratch(n, h, w, device)
+
+
+def _tof_scratch_for(scratch, pairs: int, h: int, w: int, device) -> TofScratch:
+    if scratch is None:
+        return TofScratch(min(pairs, 8), h, w, device)
+    if not isinstance(scratch, TofScratch) or scratch.device != device or (scratch.h, scratch.w) != (h, w):
+        raise ValueError(f"scratch: a tof_scratch for a region of {h} x {w} on {device} expected")
+    return scratch
+
+
+def _farneback(s: TofScratch, N: int, level, out: torch.Tensor = None) -> torch.Tensor:
+    """The stages of N <= s.pairs pairs.  ``level(k, h, w, taps, img)`` fills the level images [N,2,h,w] of stage k.  -> the flow
+    [N,h,w,2], in ``out`` or in the scratch (valid until its next use)."""
+    kern, flow = tof_poly_kernels(), None
+    for k, h, w in s.stages:
+        px = N * h * w
+        img = s.img[:2 * px].view(N, 2, h, w)
+        level(k, h, w, tof_taps(k), img)
+        R = K.tof_polyexp(img, kern, s.R[:10 * px].view(N, 2, 5, h, w))
+        if flow is not None:
+            flow = K.tof_flow_up(flow, h, w, s.up[:2 * px].view(N, h, w, 2))
+        M = s.M[:5 * px].view(N, 5, h, w)
+        K.tof_matrices(R, flow, M)
+        for i in range(TOF_ITERATIONS):
+            last = k == 0 and i + 1 == TOF_ITERATIONS
+            flow = K.tof_blur_solve(M, out if last and out is not None else s.flow[:2 * px].view(N, h, w, 2))
+            if i + 1 < TOF_ITERATIONS:
+                K.tof_matrices(R, flow, M)
+    return flow
+
+
+def farneback_u8(prev: torch.Tensor, cur: torch.Tensor, scratch: TofScratch = None) -> torch.Tensor:
+    """fp64 device tensor [N,H,W,2]: the dense flow (dx, dy) from ``prev[j]`` to ``cur[j]``, the project's statement of Farneback's
+    algorithm with the reference's arguments (pyr_scale 0.5, levels 3, winsize 15, iterations 3, poly_n 5, poly_sigma 1.2, flags 0;
+    cv2 parity unpinned).  ``prev``, ``cur``: uint8 [N,H,W] (or [H,W]) on the device with contiguous rows, read in place, at least
+    32 x 32.  The pairs go through the launches together, in groups of the ``scratch``'s size (`tof_scratch`)."""
+    c, N, H, W, _, _ = _sample_frames(cur, "cur", torch.uint8)
+    p, Np, Hp, Wp, _, _ = _sample_frames(prev, "prev", torch.uint8)
+    if N == 0 or (Np, Hp, Wp) != (N, H, W) or p.device != c.device:
+        raise ValueError(f"farneback_u8: two stacks of one shape on one device expected, got {tuple(p.shape)} and {tuple(c.shape)}")
+    tof_size(H, W)
+    with on_device(c):
+        s = _tof_scratch_for(scratch, N, H, W, c.device)
+        out = torch.empty((N, H, W, 2), dtype=torch.float64, device=c.device)
+        for g0 in range(0, N, s.pairs):
+            g1 = min(g0 + s.pairs, N)
+            _farneback(s, g1 - g0, lambda k, h, w, taps, img: K.tof_level(p[g0:g1], c[g0:g1], h, w, taps, out=img), out[g0:g1])
+    return out
+
+
+def tof_frames_u8(gt: torch.Tensor, sr: torch.Tensor, gt_prev: torch.Tensor = None, sr_prev: torch.Tensor = None,
+                  scratch: TofScratch = None) -> torch.Tensor:
+    """fp64 device tensor [k]: tOF of the k frames of a chunk, the mean over the common top-left region of the endpoint distance
+    between the flow (gt[t-1], gt[t]) and the flow (sr[t-1], sr[t]).  ``gt``, ``sr``: uint8 [k,H,W] on the device with contiguous
+    rows, of possibly different sizes, the region at least 32 x 32.  ``gt_prev`` / ``sr_prev``: the frame in front of the chunk
+    (uint8 [H,W], the size of its stack), or None at the start of a sequence, where frame 0 is its own previous frame (the
+    reference's rule; the flow of that pair is computed, it is not zero).  Ground-truth and result pairs share every launch but the
+    level images'; a ``scratch`` for 2 k pairs takes the chunk in one group, a smaller one in several; nothing waits for the device."""
+    g, k, Hg, Wg, _, _ = _sample_frames(gt, "gt", torch.uint8)
+    r, kr, Hr, Wr, _, _ = _sample_frames(sr, "sr", torch.uint8)
+    if k == 0 or kr != k or r.device != g.device:
+        raise ValueError(f"tof_frames_u8: two stacks of one length on one device expected, got {tuple(g.shape)} and {tuple(r.shape)}")
+    H, W = min(Hg, Hr), min(Wg, Wr)
+    tof_size(H, W)
+    firsts = []
+    for name, stack, first in (("gt_prev", g, gt_prev), ("sr_prev", r, sr_prev)):
+        if first is None:
+            first = stack[0]
+        elif not first.is_cuda or first.dtype != torch.uint8 or tuple(first.shape) != tuple(stack.shape[1:]) or first.device != g.device:
+            raise ValueError(f"tof_frames_u8: {name} must be a uint8 frame {tuple(stack.shape[1:])} on the stacks' device")
+        firsts.append(first[:H, :W])
+    g, r = g[:, :H, :W], r[:, :H, :W]
+    with on_device(g):
+        s = _tof_scratch_for(scratch, 2 * k, H, W, g.device)
+        if s.pairs < 2:
+            raise ValueError("tof_frames_u8: the scratch must hold at least two pairs")
+        out, m = torch.empty(k, dtype=torch.float64, device=g.device), s.pairs // 2
+        for f0 in range(0, k, m):
+            f1 = min(f0 + m, k)
+            n = f1 - f0
+
+            def level(kk, h, w, taps, img):
+                for half, (stack, first) in enumerate(((g, firsts[0]), (r, firsts[1]))):
+                    dst = img[half * n:(half + 1) * n]
+                    if f0 == 0:
+                        K.tof_level(stack[:f1], stack[:f1], h, w, taps, first=first, out=dst)
+                    else:
+                        K.tof_level(stack[f0 - 1:f1 - 1], stack[f0:f1], h, w, taps, out=dst)
+
+            flow = _farneback(s, 2 * n, level)
+            K.tof_epe(flow[:n], flow[n:], s.partials[:n * ((H + K.TOF_STRIP - 1) // K.TOF_STRIP)].view(n, -1), out[f0:f1])
+    return out
+
+
+def tof_u8(gt: torch.Tensor, sr: torch.Tensor) -> np.ndarray:
+    """Per-frame tOF (lower is better) of two uint8 [T,H,W] device stacks, ground truth and result, fp64 numpy [T] on the host:
+    `tof_frames_u8` on the whole sequence, frame 0 against itself."""
+    return tof_frames_u8(gt, sr).cpu().numpy()

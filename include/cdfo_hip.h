@@ -758,6 +758,39 @@ int cdfo_brisque_sums(const double* mscn, int K, int H, int W, double* partials,
 int cdfo_brisque_features(const double* partials, int K, int G, int count, const double* table, int scale, double* features,
                           void* stream);
 
+/* ---- tOF: the dense Farneback flow of 8-bit luma pairs and the distance of two flows (tof.hip; cdfo_amd/metrics.py: farneback_u8,
+ * tof_frames_u8; DESIGN.md has the definition, the project's own: cv2 parity unpinned) ----
+ * Pairs are the batch dimension.  Every buffer but the frames is fp64, dense and 8-byte aligned, the flows 16-byte aligned (else
+ * CDFO_EALIGN); sizes, pitches and strides are in samples; at most 65535 pairs (32767 for the level images) per launch, all on
+ * `stream`.  Grids depend on the shapes alone, every sum has a fixed order and there are no atomics: equal inputs give equal bits.
+ * cdfo_tof_level_u8:  dst [K][2][h][w]: for pair j the level image of its previous frame, then of its current one, frame `cur + j
+ *                     cstride` with rows at `cpitch`.  The previous frame is `prev + j pstride` when `first` is NULL; else it is
+ *                     `first` (rows at `fpitch`) for pair 0 and `prev + (j - 1) pstride` beyond, the form of a chunk whose pair j
+ *                     is (frame j - 1, frame j) with a carried frame in front.  The H x W region of each frame (at least
+ *                     CDFO_TOF_MIN each way) is smoothed with the `ntaps` (odd, 3 .. CDFO_TOF_MAX_TAPS; doubles in HOST memory)
+ *                     down the columns and then along the rows, reflect-101, and resized to h x w (h <= H, w <= W) bilinearly: the
+ *                     source coordinate (i + 1/2) (N / n) - 1/2, both taps clamped, the weight from the unclamped floor.
+ * cdfo_tof_polyexp:   img [N][h][w] -> R [N][5][h][w] = (b_x, b_y, a_xx, a_yy, a_xy), the edge sample repeated.  `kernels`: 37 doubles
+ *                     in HOST memory: the 11 taps g, x g, x^2 g, then the inverse Gram matrix's entries [1][1], [0][3], [3][3], [5][5].
+ * cdfo_tof_matrices:  R [N][2][5][h][w] (a pair's previous, then current expansion) and flow [N][h][w][2] (dx, dy; NULL: zeros) ->
+ *                     M [N][5][h][w], the normal equations' planes with the border factors applied.
+ * cdfo_tof_blur_solve: M -> flow [N][h][w][2]: the 15 x 15 box mean of each plane (direct sums, rows first, the edge sample
+ *                     repeated, / 225), then the 2 x 2 solve with 1e-3 added to the determinant.
+ * cdfo_tof_flow_up:   src [N][hp][wp][2] -> dst [N][h][w][2]: the bilinear resize above, times 2.
+ * cdfo_tof_epe:       flows a, b [K][h][w][2] -> out [K]: the mean over h w pixels of |a - b|; partials [K][G], G = ceil(h /
+ *                     CDFO_TOF_STRIP), holds the strips' sums, which one workgroup per frame adds in index order (two launches). */
+#define CDFO_TOF_MIN 32
+#define CDFO_TOF_MAX_TAPS 19
+#define CDFO_TOF_STRIP 16
+int cdfo_tof_level_u8(const unsigned char* prev, int ppitch, long long pstride, const unsigned char* cur, int cpitch, long long cstride,
+                      const unsigned char* first, int fpitch, int K, int H, int W, int h, int w, const double* taps, int ntaps,
+                      double* dst, void* stream);
+int cdfo_tof_polyexp(const double* img, int N, int h, int w, const double* kernels, double* R, void* stream);
+int cdfo_tof_matrices(const double* R, const double* flow, int N, int h, int w, double* M, void* stream);
+int cdfo_tof_blur_solve(const double* M, int N, int h, int w, double* flow, void* stream);
+int cdfo_tof_flow_up(const double* src, int N, int hp, int wp, int h, int w, double* dst, void* stream);
+int cdfo_tof_epe(const double* a, const double* b, int K, int h, int w, double* partials, double* out, void* stream);
+
 /* ---- training batches and the training loss (train_batch.hip; cdfo_amd/train_data.py, cdfo_amd/loss.py) ----
  * cdfo_train_batch:   the resident clip set -- lr, pms, hr unsigned and rms signed 8-bit [S][T][H][W] ([S][T][4H][4W] for hr), ufs
  *                     [S][T][Hu][W] with Hu >= H rows indexed from the top, mvl0 signed 8-bit [S][T][H][W][3] (a, b, ref), all dense --

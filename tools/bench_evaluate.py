@@ -7,6 +7,7 @@
     python tools/bench_evaluate.py --msssim [--yuv] [--size T H W] [--chunk K] [--repeats R]    MS-SSIM: the kernels, and the option on / off
     python tools/bench_evaluate.py --niqe PARAMS [--yuv] [--size T H W] [--chunk K] [--repeats R]    NIQE: the kernels, and the option on / off
     python tools/bench_evaluate.py --brisque MODEL [--niqe PARAMS] [--yuv] [--size T H W] [--chunk K] [--repeats R]    BRISQUE likewise
+    python tools/bench_evaluate.py --tof [--niqe PARAMS] [--yuv] [--size T H W] [--chunk K] [--repeats R]    tOF: the kernels, and the option on / off
 
 Sequence benchmark, one process, one warm-up pass then R passes each, medians: run_chunked alone; evaluate_sequence with metrics
 only; with metrics and PNG writing at 8 and 16 workers; and the per-chunk times of the finish kernel and the two 8-bit metric
@@ -24,7 +25,9 @@ section 5.000000000 has the figures taken that way.)  --niqe PARAMS (a pristine 
 `niqe_features_u8` beside ssim_u8 and msssim_u8 on one chunk of 1080 x 1920 frames in alternating passes, and each of its kernels
 alone, from events; then the evaluator with metrics only, ``niqe`` off and on in alternating passes of one process.  --brisque MODEL
 (a support-vector model, `metrics.brisque_params`): the seven launches of `brisque_features_u8` beside ssim_u8 (and, with --niqe
-PARAMS, `niqe_features_u8`) on the same chunk, each of its kernels alone, and the evaluator with ``brisque`` off and on."""
+PARAMS, `niqe_features_u8`) on the same chunk, each of its kernels alone, and the evaluator with ``brisque`` off and on.  --tof:
+the launches of `tof_frames_u8` on the same chunk (2 K Farneback pairs, the scratch held) beside ssim_u8 (and, with --niqe PARAMS,
+`niqe_features_u8`), each kernel's share summed over the stages, and the evaluator with ``tof`` off and on."""
 import os
 import sys
 import tempfile
@@ -400,8 +403,89 @@ def brisque():
               f"{' '.join('%.2f' % f for f in fps[True])}; median {on:.2f} ({on / off:.4f} of off)", flush=True)
 
 
+def tof():
+    from arch.SIDECVSR_our import CVSR_V8
+    from cdfo_amd import kernels as K
+    from cdfo_amd import metrics as M
+    from cdfo_amd.evaluate import evaluate_sequence, evaluate_yuv, write_synthetic_sequence, write_synthetic_sequence_yuv
+    T, H, W = _arg("--size", 3, [64, 270, 480])
+    chunk, reps = _arg("--chunk", 1, 8), _arg("--repeats", 1, 5)
+    rs = np.random.RandomState(0)
+    a = rs.randint(0, 256, (chunk, 4 * H, 4 * W))
+    b = np.clip(a + np.rint(20 * rs.randn(*a.shape)).astype(np.int64), 0, 255)
+    a, b = torch.from_numpy(a.astype(np.uint8)).cuda(), torch.from_numpy(b.astype(np.uint8)).cuda()
+    ts = M.tof_scratch(2 * chunk, 4 * H, 4 * W, a.device)
+    forms = [("ssim_u8", lambda: M.ssim_u8(a, b, 4)), ("tof_frames_u8", lambda: M.tof_frames_u8(a, b, a[0], b[0], ts))]
+    if "--niqe" in sys.argv:
+        params = M.niqe_params(sys.argv[sys.argv.index("--niqe") + 1])
+        nq = M.niqe_scratch(chunk, *M.niqe_region(4 * H, 4 * W), a.device)
+        forms.insert(1, ("niqe_features_u8", lambda: M.niqe_features_u8(a, nq)))
+    times = {name: [] for name, _ in forms}
+    for name, fn in forms:
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(5):                                       # alternating forms: drift of the box falls on all alike
+        for name, fn in forms:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1))
+    med = {name: float(np.median(v)) for name, v in times.items()}
+    stages = M.tof_size(4 * H, 4 * W)
+    print(f"chunk of {chunk} frames {4 * H}x{4 * W} = {2 * chunk} pairs, {len(stages)} stages (wrappers included, scratch of {ts.nbytes} bytes "
+          "held), median of 5 alternating passes: "
+          + "; ".join(f"{name} {med[name]:.3f} ms (passes {' '.join('%.3f' % x for x in times[name])})" for name, _ in forms)
+          + f": tOF x{med['tof_frames_u8'] / med['ssim_u8']:.1f} of SSIM, {med['tof_frames_u8'] / chunk:.3f} ms per frame", flush=True)
+    # the split: each kernel on the chunk's 2 K pairs, summed over the stages it runs at (and the times it runs there)
+    N, kern = 2 * chunk, M.tof_poly_kernels()
+    split = {"level_u8 x2": 0.0, "polyexp": 0.0, "flow_up": 0.0, "matrices x3": 0.0, "blur_solve x3": 0.0}
+    prev = None
+    for k, h, w in stages:
+        img = torch.empty((N, 2, h, w), dtype=torch.float64, device=a.device)
+        level = lambda: (K.tof_level(a, a, h, w, M.tof_taps(k), first=a[0], out=img[:chunk]),
+                         K.tof_level(b, b, h, w, M.tof_taps(k), first=b[0], out=img[chunk:]))
+        split["level_u8 x2"] += _median_ms(level)[0]
+        R = K.tof_polyexp(img, kern)
+        split["polyexp"] += _median_ms(lambda: K.tof_polyexp(img, kern, R))[0]
+        flow = None
+        if prev is not None:
+            flow = K.tof_flow_up(prev, h, w)
+            split["flow_up"] += _median_ms(lambda: K.tof_flow_up(prev, h, w, flow))[0]
+        Mx = K.tof_matrices(R, flow)
+        split["matrices x3"] += 3 * _median_ms(lambda: K.tof_matrices(R, flow, Mx))[0]
+        prev = K.tof_blur_solve(Mx)
+        split["blur_solve x3"] += 3 * _median_ms(lambda: K.tof_blur_solve(Mx, prev))[0]
+        del img, R, Mx
+    split["epe"] = _median_ms(lambda: K.tof_epe(prev[:chunk], prev[chunk:]))[0]
+    del prev
+    print("the split over all stages, medians of 5 each (wrapper included): " + "; ".join(f"{n} {v:.3f} ms" for n, v in split.items())
+          + f"; sum {sum(split.values()):.3f} ms", flush=True)
+    model = CVSR_V8().cuda().eval()
+    with tempfile.TemporaryDirectory() as tmp:
+        if "--yuv" in sys.argv:
+            lr, side, gt = write_synthetic_sequence_yuv(tmp, T, H, W)
+            run = lambda on: evaluate_yuv(model, lr, W, H, side, gt_yuv=gt, chunk=chunk, tof=on)
+        else:
+            lr, side, gt = write_synthetic_sequence(tmp, T, H, W)
+            run = lambda on: evaluate_sequence(model, lr, side, gt_dir=gt, chunk=chunk, tof=on)
+        run(False), run(True)
+        fps = {False: [], True: []}
+        for _ in range(reps):                                # alternating passes: drift of the box falls on both alike
+            for on in (False, True):
+                r = run(on)
+                fps[on].append(r.frames / r.seconds_total)
+        off, on = float(np.median(fps[False])), float(np.median(fps[True]))
+        print(f"{'evaluate_yuv' if '--yuv' in sys.argv else 'evaluate_sequence'}, metrics only, {T} frames {H}x{W}, chunk {chunk}, end to "
+              f"end frames/s: tof off per pass {' '.join('%.2f' % f for f in fps[False])}; median {off:.2f}; tof on per pass "
+              f"{' '.join('%.2f' % f for f in fps[True])}; median {on:.2f} ({on / off:.4f} of off); mean tOF {r.mean_tof:.5f}", flush=True)
+
+
 if __name__ == "__main__":
-    if "--brisque" in sys.argv:
+    if "--tof" in sys.argv:
+        tof()
+    elif "--brisque" in sys.argv:
         brisque()
     elif "--niqe" in sys.argv:
         niqe()
