@@ -1,0 +1,267 @@
+// LPIPS' own kernels: what a VGG-shaped trunk needs beside the 3x3 convolutions of conv_igemm.hip, and the distance of two feature
+// stacks (DESIGN.md has the definition, tests/lpips_ref.py its torch statement; cdfo_amd/metrics.py: lpips_layers_u8 puts a chunk's
+// launches together).
+//   cdfo_lpips_stem_u8   8-bit luma read in place -> ReLU(conv1_1) as NHWC fp32: the scaling to three channels, the zero padding of
+//                        the SCALED tensor and the 27-tap convolution in one pass, halo tile and weights through LDS
+//   cdfo_lpips_pool2     NHWC fp32 2 x 2 / 2 maximum with floor, 16 bytes per lane, bit-exact
+//   cdfo_lpips_dist      two NHWC fp32 stacks and lin [C] -> fp64 partial sums per (frame, strip of rows): lanes over a pixel's
+//                        channels, the two norms and the weighted squared differences reduced by a butterfly of fixed order
+//   cdfo_lpips_fold      the strips of every layer added in index order and divided by the layer's pixel count, one launch
+// The trunk is fp32 up to and including the ReLU outputs; everything behind the features is fp64.  Grids and summation orders
+// depend on the shapes alone and nothing is atomic: equal inputs give equal bits, d(a, a) is exactly 0 and d(a, b) has the bits of
+// d(b, a) (both norms are formed the same way and (x - y)^2 = (y - x)^2 exactly).  All stores are vector stores.
+#include "common.h"
+
+namespace {
+
+inline bool fits32(long long rows, long long pitch) { return rows * pitch <= 0x7fffffffLL; }
+
+constexpr int LP_T = 16;                                // the stem's tile, 16 x 16 pixels of an 18 x 18 halo
+constexpr int LP_HALO = LP_T + 2;
+
+// grid (tiles across, tiles down, frame), dynamic LDS: 3 halo planes, 27 C0 weights as [tap][channel], C0 biases.
+// A sample v becomes x = v / 255 (normalize: 2 x - 1), then channel c = (x - shift_c) / scale_c; beyond the region the SCALED tensor
+// is zero.  Item i of a tile is (pixel i / (C0 / 4), channel quad i % (C0 / 4)): neighbouring lanes hold neighbouring quads of one
+// pixel, so a wave's stores are contiguous runs of a pixel's channels and its halo reads are broadcasts.
+__global__ __launch_bounds__(256) void lpips_stem_kernel(const unsigned char* __restrict__ src, int pitch, long long fstride, int h, int w,
+                                                         const float* __restrict__ weight, const float* __restrict__ bias, int C0,
+                                                         int normalize, float* __restrict__ dst) {
+  extern __shared__ __attribute__((aligned(16))) float lp_smem[];
+  float* sIn = lp_smem;                                 // [3][LP_HALO][LP_HALO], padded to a multiple of 4 floats
+  float* sW = lp_smem + 3 * LP_HALO * LP_HALO;          // [27][C0]  (3 * 18 * 18 = 972 floats: 16-byte aligned)
+  float* sB = sW + 27 * C0;
+  const int n = blockIdx.z, y0 = blockIdx.y * LP_T, x0 = blockIdx.x * LP_T;
+  const unsigned char* p = src + (long long)n * fstride;
+  const float shift[3] = {-.030f, -.088f, -.188f}, scale[3] = {.458f, .448f, .450f};
+  for (int i = threadIdx.x; i < LP_HALO * LP_HALO; i += 256) {
+    const int r = i / LP_HALO, c = i - r * LP_HALO;
+    const int y = y0 + r - 1, x = x0 + c - 1;
+    const bool inside = y >= 0 && y < h && x >= 0 && x < w;
+    float v = inside ? (float)p[y * pitch + x] / 255.f : 0.f;
+    if (normalize) v = 2.f * v - 1.f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) sIn[ch * LP_HALO * LP_HALO + i] = inside ? (v - shift[ch]) / scale[ch] : 0.f;
+  }
+  for (int i = threadIdx.x; i < 27 * C0; i += 256) {    // OIHW [C0][3][3][3] -> [tap = ci * 9 + ky * 3 + kx][C0]
+    const int t = i / C0, co = i - t * C0;
+    sW[i] = weight[co * 27 + t];
+  }
+  for (int i = threadIdx.x; i < C0; i += 256) sB[i] = bias[i];
+  __syncthreads();
+  const int CQ = C0 >> 2;
+  float* out = dst + (long long)n * h * w * C0;
+  for (int i = threadIdx.x; i < LP_T * LP_T * CQ; i += 256) {
+    const int px = i / CQ, q = i - px * CQ;
+    const int r = px / LP_T, c = px - r * LP_T;
+    if (y0 + r >= h || x0 + c >= w) continue;
+    f32x4 acc = *reinterpret_cast<const f32x4*>(sB + 4 * q);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+          const float v = sIn[ch * LP_HALO * LP_HALO + (r + ky) * LP_HALO + c + kx];
+          acc += v * *reinterpret_cast<const f32x4*>(sW + (ch * 9 + ky * 3 + kx) * C0 + 4 * q);
+        }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = acc[e] > 0.f ? acc[e] : 0.f;
+    *reinterpret_cast<f32x4*>(out + ((long long)(y0 + r) * w + x0 + c) * C0 + 4 * q) = acc;
+  }
+}
+
+// ATen's rule, in its order: a later sample replaces the maximum if it is larger or a NaN
+__device__ __forceinline__ f32x4 lpips_max4(f32x4 m, f32x4 v) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) m[e] = (v[e] > m[e] || v[e] != v[e]) ? v[e] : m[e];
+  return m;
+}
+
+// one thread per output channel quad: total = N * (H / 2) * (W / 2) * (C / 4)
+__global__ __launch_bounds__(256) void lpips_pool2_kernel(const float* __restrict__ src, int H, int W, int C, long long total,
+                                                          float* __restrict__ dst) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int CQ = C >> 2, Ho = H >> 1, Wo = W >> 1;
+  const int q = (int)(i % CQ);
+  long long rest = i / CQ;
+  const int x = (int)(rest % Wo);
+  rest /= Wo;
+  const int y = (int)(rest % Ho);
+  const long long n = rest / Ho;
+  const float* p = src + (((n * H + 2 * y) * W + 2 * x) * (long long)C) + 4 * q;
+  f32x4 m = *reinterpret_cast<const f32x4*>(p);
+  m = lpips_max4(m, *reinterpret_cast<const f32x4*>(p + C));
+  m = lpips_max4(m, *reinterpret_cast<const f32x4*>(p + (long long)W * C));
+  m = lpips_max4(m, *reinterpret_cast<const f32x4*>(p + (long long)W * C + C));
+  *reinterpret_cast<f32x4*>(dst + 4 * i) = m;
+}
+
+// grid (strip, frame), LP_DT threads: sixteen waves per strip keep enough loads in flight for a kernel that only streams.  L lanes
+// (a power of two, 4 .. 64, at least C / 4 below 64) share a pixel: lane s of a group takes the channel quads s, s + L, ...; a
+// workgroup holds LP_DT / L pixels at a time, group j the strip's pixels j, j + LP_DT / L, ...  A lane keeps its first LP_KEEP quads
+// of both stacks in registers between the two passes (all of them up to C = 512), and reads any beyond again.
+// Per pixel: the two sums of squares (each lane its quads in order, then the group's butterfly, after which every lane of the group
+// holds the same bits), the roots, then the weighted squared differences the same way.  Lane 0 of a group adds its pixels' values
+// in order; thread 0 adds the groups in index order.
+constexpr int LP_DT = 1024, LP_KEEP = 2;
+
+__global__ __launch_bounds__(LP_DT) void lpips_dist_kernel(const float* __restrict__ fa, const float* __restrict__ fb,
+                                                         const double* __restrict__ lin, int h, int w, int C, int L,
+                                                         double* __restrict__ partials) {
+  __shared__ double sh[LP_DT / 4];
+  const int n = blockIdx.y, r0 = blockIdx.x * CDFO_LPIPS_STRIP;
+  const int rows = h - r0 < CDFO_LPIPS_STRIP ? h - r0 : CDFO_LPIPS_STRIP;
+  const int CQ = C >> 2, groups = LP_DT / L, grp = threadIdx.x / L, s = threadIdx.x - grp * L;
+  const long long base = ((long long)n * h + r0) * w * C;
+  const float* pa = fa + base;
+  const float* pb = fb + base;
+  double acc = 0.0;
+  for (int px = grp; px < rows * w; px += groups) {     // the lanes of a group leave together: the butterflies stay inside a group
+    const float* a = pa + (long long)px * C;
+    const float* b = pb + (long long)px * C;
+    double na = 0.0, nb = 0.0;
+    f32x4 ka[LP_KEEP], kb[LP_KEEP];
+#pragma unroll
+    for (int j = 0; j < LP_KEEP; ++j)
+      if (s + j * L < CQ) {
+        ka[j] = *reinterpret_cast<const f32x4*>(a + 4 * (s + j * L));
+        kb[j] = *reinterpret_cast<const f32x4*>(b + 4 * (s + j * L));
+      }
+#pragma unroll
+    for (int j = 0; j < LP_KEEP; ++j)
+      if (s + j * L < CQ) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          na += (double)ka[j][e] * (double)ka[j][e];
+          nb += (double)kb[j][e] * (double)kb[j][e];
+        }
+      }
+    for (int q = s + LP_KEEP * L; q < CQ; q += L) {
+      const f32x4 va = *reinterpret_cast<const f32x4*>(a + 4 * q), vb = *reinterpret_cast<const f32x4*>(b + 4 * q);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        na += (double)va[e] * (double)va[e];
+        nb += (double)vb[e] * (double)vb[e];
+      }
+    }
+    for (int o = L >> 1; o > 0; o >>= 1) {
+      na += __shfl_xor(na, o, 64);
+      nb += __shfl_xor(nb, o, 64);
+    }
+    const double da = sqrt(na) + 1e-10, db = sqrt(nb) + 1e-10;
+    double d = 0.0;
+#pragma unroll
+    for (int j = 0; j < LP_KEEP; ++j)
+      if (s + j * L < CQ) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const double t = (double)ka[j][e] / da - (double)kb[j][e] / db;
+          d += lin[4 * (s + j * L) + e] * (t * t);
+        }
+      }
+    for (int q = s + LP_KEEP * L; q < CQ; q += L) {
+      const f32x4 va = *reinterpret_cast<const f32x4*>(a + 4 * q), vb = *reinterpret_cast<const f32x4*>(b + 4 * q);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const double t = (double)va[e] / da - (double)vb[e] / db;
+        d += lin[4 * q + e] * (t * t);
+      }
+    }
+    for (int o = L >> 1; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+    acc += d;
+  }
+  if (s == 0) sh[grp] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int j = 0; j < groups; ++j) t += sh[j];
+    partials[(long long)n * gridDim.x + blockIdx.x] = t;
+  }
+}
+
+struct LpipsFold {
+  int strips[CDFO_LPIPS_MAX_LAYERS];
+  long long first[CDFO_LPIPS_MAX_LAYERS];               // where layer k's [N][strips[k]] block begins
+  double count[CDFO_LPIPS_MAX_LAYERS];
+};
+
+// one thread per (frame, layer)
+__global__ __launch_bounds__(64) void lpips_fold_kernel(const double* __restrict__ partials, int N, int layers, LpipsFold f,
+                                                        double* __restrict__ out) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= N * layers) return;
+  const int n = i / layers, k = i - n * layers;
+  const double* p = partials + f.first[k] + (long long)n * f.strips[k];
+  double t = 0.0;
+  for (int g = 0; g < f.strips[k]; ++g) t += p[g];
+  out[i] = t / f.count[k];
+}
+
+}  // namespace
+
+extern "C" int cdfo_lpips_stem_u8(const unsigned char* src, int pitch, long long fstride, int N, int h, int w, const float* weight,
+                                  const float* bias, int C0, int normalize, float* dst, void* stream) {
+  if (!src || !weight || !bias || !dst || N <= 0 || N > 65535 || h <= 0 || w <= 0 || pitch < w || fstride < 0) return CDFO_EINVAL;
+  if (C0 <= 0 || C0 % 16 || C0 > CDFO_LPIPS_STEM_MAXC) return CDFO_EINVAL;
+  if (!fits32(h, pitch) || cdiv(h, LP_T) > 65535) return CDFO_EINVAL;                          // 32-bit offsets inside a frame
+  if (!aligned16(dst) || (reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(bias)) & 3u) return CDFO_EALIGN;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const double px = (double)N * h * w;
+  CdfoProfScope prof(st, KID_LAYOUT, 2.0 * 27 * C0 * px, (1.0 + 4.0 * C0) * px);
+  const int lds = (3 * LP_HALO * LP_HALO + 28 * C0) * (int)sizeof(float);
+  hipLaunchKernelGGL(lpips_stem_kernel, dim3((unsigned)cdiv(w, LP_T), (unsigned)cdiv(h, LP_T), (unsigned)N), dim3(256), lds, st, src, pitch,
+                     fstride, h, w, weight, bias, C0, normalize ? 1 : 0, dst);
+  CDFO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cdfo_lpips_pool2(const float* src, int N, int H, int W, int C, float* dst, void* stream) {
+  if (!src || !dst || N <= 0 || H < 2 || W < 2 || C <= 0 || C % 4) return CDFO_EINVAL;
+  if (!aligned16(src) || !aligned16(dst)) return CDFO_EALIGN;
+  const long long total = (long long)N * (H / 2) * (W / 2) * (C / 4);
+  if ((total + 255) / 256 > 0x7fffffffLL) return CDFO_EINVAL;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  CdfoProfScope prof(st, KID_LAYOUT, 12.0 * total, 80.0 * total);
+  hipLaunchKernelGGL(lpips_pool2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, H, W, C, total, dst);
+  CDFO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cdfo_lpips_dist(const float* fa, const float* fb, const double* lin, int N, int h, int w, int C, double* partials,
+                               void* stream) {
+  if (!fa || !fb || !lin || !partials || N <= 0 || N > 65535 || h <= 0 || w <= 0 || C <= 0 || C % 4) return CDFO_EINVAL;
+  if (!fits32(CDFO_LPIPS_STRIP, w)) return CDFO_EINVAL;                                         // a strip's pixel index is an int
+  if (!aligned16(fa) || !aligned16(fb) || (reinterpret_cast<uintptr_t>(lin) | reinterpret_cast<uintptr_t>(partials)) & 7u)
+    return CDFO_EALIGN;
+  int L = 4;
+  while (L < C / 4 && L < 64) L *= 2;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const double el = (double)N * h * w * C;
+  CdfoProfScope prof(st, KID_LAYOUT, 12.0 * el, 8.0 * el);
+  hipLaunchKernelGGL(lpips_dist_kernel, dim3((unsigned)cdiv(h, CDFO_LPIPS_STRIP), (unsigned)N), dim3(LP_DT), 0, st, fa, fb, lin, h, w, C, L,
+                     partials);
+  CDFO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cdfo_lpips_fold(const double* partials, int N, int layers, const int* strips, const long long* counts, double* out,
+                               void* stream) {
+  if (!partials || !strips || !counts || !out || N <= 0 || layers <= 0 || layers > CDFO_LPIPS_MAX_LAYERS) return CDFO_EINVAL;
+  if ((long long)N * layers > 0x7fffffffLL) return CDFO_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(out)) & 7u) return CDFO_EALIGN;
+  LpipsFold f;
+  long long at = 0;
+  for (int k = 0; k < layers; ++k) {
+    if (strips[k] <= 0 || counts[k] <= 0) return CDFO_EINVAL;
+    f.strips[k] = strips[k];
+    f.first[k] = at;
+    f.count[k] = (double)counts[k];
+    at += (long long)N * strips[k];
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  CdfoProfScope prof(st, KID_LAYOUT, (double)at, 8.0 * at);
+  hipLaunchKernelGGL(lpips_fold_kernel, dim3((unsigned)cdiv(N * layers, 64)), dim3(64), 0, st, partials, N, layers, f, out);
+  CDFO_LAUNCH_CHECK();
+  return 0;
+}

@@ -30,7 +30,9 @@ reference's other live no-reference figure (metric/brisque.py) the same way (`me
 5.00000000000000): seven launches of its own per chunk, 36 features per frame kept on the device until the last chunk.  ``tof=True``
 adds the reference's temporal-consistency figure tOF (metric/psnr_ssim.py: calculate_tOF) with ground truth on 8-bit luma: the
 Farneback flows of the chunk's ground-truth pairs and result pairs go through the same launches behind BRISQUE's
-(`metrics.tof_frames_u8`), the frame in front of the chunk carried on the device.
+(`metrics.tof_frames_u8`), the frame in front of the chunk carried on the device.  ``lpips=`` a
+model adds LPIPS, the learned perceptual distance to the ground truth, on 8-bit luma (`metrics.lpips_layers_u8`, DESIGN.md section
+5.0000000000000000): a VGG-shaped trunk in fp32 behind tOF's launches, five layer values per frame kept on the device until the last chunk.
 
 Deliberate deviation: ``cal_psnr_ssim`` sends single-channel frames through ``to_y_channel``, an fp32 ``/255*255`` round
 trip, and takes fp32 means.  The metric semantics here are the project's established ones, ``oracle/metrics_ref.py``: fp64 on the
@@ -76,13 +78,15 @@ class SequenceResult(NamedTuple):
     mean_brisque: float = float("nan")
     tof: np.ndarray = _NO_FRAMES                    # fp64 [T] with ``tof=True`` (needs ground truth), else empty
     mean_tof: float = float("nan")
+    lpips: np.ndarray = _NO_FRAMES                  # fp64 [T] with ``lpips=`` a model (needs ground truth), else empty
+    mean_lpips: float = float("nan")
 
 
 def format_log(result: SequenceResult, name: str) -> str:
     """The reference's log line (psnr_ssim.py:481); with MS-SSIM figures, `` MS-SSIM: %.5f`` behind it, with NIQE figures
-    `` NIQE: %.5f`` behind that, with BRISQUE figures `` BRISQUE: %.5f``, with tOF figures `` tOF: %.5f`` last."""
+    `` NIQE: %.5f`` behind that, with BRISQUE figures `` BRISQUE: %.5f``, with tOF figures `` tOF: %.5f``, with LPIPS figures `` LPIPS: %.5f`` last."""
     return '%s Average PSNR/SSIM: %.3f/%.5f' % (name, result.mean_psnr, result.mean_ssim) + _msssim_suffix(result) + _niqe_suffix(result) + \
-        _brisque_suffix(result) + _tof_suffix(result)
+        _brisque_suffix(result) + _tof_suffix(result) + _lpips_suffix(result)
 
 
 def _msssim_suffix(result) -> str:
@@ -99,6 +103,10 @@ def _brisque_suffix(result) -> str:
 
 def _tof_suffix(result) -> str:
     return ' tOF: %.5f' % result.mean_tof if len(result.tof) else ''
+
+
+def _lpips_suffix(result) -> str:
+    return ' LPIPS: %.5f' % result.mean_lpips if len(result.lpips) else ''
 
 
 def quantise_numpy(x: np.ndarray, mode: str = "trunc", peak: int = 255) -> np.ndarray:
@@ -197,6 +205,24 @@ def _check_tof(lr, gt, tof) -> bool:
         raise ValueError(f"tof: the metric is defined on 8-bit samples, the format's peak is {lr.peak}")
     M.tof_size(min(4 * lr.shape[0], gt.shape[0]), min(4 * lr.shape[1], gt.shape[1]))
     return True
+
+
+def _check_lpips(lr, gt, lpips):
+    """The model of an ``lpips=`` argument (None: the metric is off), before any device work: `metrics.lpips_params`' checks;
+    ValueError without ground truth, above 8 bits and for a common region below 16 x 16 (`metrics.lpips_size`)."""
+    if lpips is None:
+        return None
+    if gt is None:
+        raise ValueError("lpips: the metric is a distance to the ground truth, and there is no ground truth")
+    if lr.dtype != torch.uint8:
+        raise ValueError(f"lpips: the metric is defined on 8-bit samples, the format's peak is {lr.peak}")
+    M.lpips_size(min(4 * lr.shape[0], gt.shape[0]), min(4 * lr.shape[1], gt.shape[1]))
+    return M.lpips_params(lpips)
+
+
+def _lpips(layers: np.ndarray) -> np.ndarray:
+    """Per-frame LPIPS from the loop's layer values; empty where it has none."""
+    return np.atleast_1d(M.lpips_from_layers(layers)) if len(layers) else np.zeros(0, np.float64)
 
 
 def _psnr(sse: np.ndarray, shape, gt_shape, crop: int, peak: int) -> np.ndarray:
@@ -310,7 +336,7 @@ class _Slots:
 
 
 def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: int, ccrop: int, quantise: str, workers: int,
-                msssim: bool = False, niqe: bool = False, brisque: bool = False, tof: bool = False):
+                msssim: bool = False, niqe: bool = False, brisque: bool = False, tof: bool = False, lpips=None):
     """The chunk loop of both evaluators.  ``lr``: the LR sequence as a frame source (its counts, shapes, dtype and peak; its frames
     come from ``load``).  ``load()`` -> (`StreamingSR`, (u, v) LR chroma planes [T,h,w] or None); it runs after the first
     ground-truth reads have been handed to the pool.  ``gt``: a frame source or None.  ``sink``: a frame sink or None.
@@ -319,10 +345,12 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
     chunk's 8-bit luma, with or without ground truth, on the main stream too, its scratch held the same way; like SSIM's sums the
     features stay on the device until the last chunk.  ``brisque``: `metrics.brisque_features_u8` likewise, behind NIQE's launches.
     ``tof``: with ground truth, `metrics.tof_frames_u8` behind those, its scratch held once as well; the last ground-truth frame and
-    the last result frame of a chunk are copied into two one-frame buffers, the next chunk's first pair.
+    the last result frame of a chunk are copied into two one-frame buffers, the next chunk's first pair.  ``lpips``: an
+    `metrics.LpipsParams` or None; with ground truth, `metrics.lpips_layers_u8` behind tOF's launches, its scratch held once too.
     -> (the `StreamingSR`, sse_y int64 [T], sse_uv int64 [2,T], ssim fp64 [T], MS-SSIM components fp64 [T,5,2], NIQE features fp64
-    [T,nb,36], BRISQUE features fp64 [T,36], tOF fp64 [T]); the arrays are empty without ground truth (sse_uv without chroma, the
-    components without ``msssim``, tOF without ``tof``), the features without ``niqe`` / ``brisque``.  The module's docstring has the
+    [T,nb,36], BRISQUE features fp64 [T,36], tOF fp64 [T], LPIPS layer values fp64 [T,5]); the arrays are empty without ground truth
+    (sse_uv without chroma, the components without ``msssim``, tOF without ``tof``, the layer values without ``lpips``), the features
+    without ``niqe`` / ``brisque``.  The module's docstring has the
     order of events."""
     T, kmax, kind, peak = lr.frames, min(chunk, lr.frames), lr.dtype, lr.peak
     has_c = lr.chroma_shape is not None
@@ -363,6 +391,9 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
             if tof and gt is not None:
                 tf_scratch = M.tof_scratch(2 * kmax, min(out_y[0], gt_y[0]), min(out_y[1], gt_y[1]), dev)
                 tf_carry = (on_dev(gt_y), on_dev(out_y))          # the frames in front of the next chunk: ground truth, result
+            lp, lp_scratch = [], None
+            if lpips is not None and gt is not None:
+                lp_scratch = M.lpips_scratch(kmax, min(out_y[0], gt_y[0]), min(out_y[1], gt_y[1]), lpips, dev)
             chunks = s.iter_chunked(chunk, share_compensation)
             for c in range((T + chunk - 1) // chunk):
                 u, d = up[c], down[c]
@@ -408,6 +439,8 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
                     tf_gt, tf_sr = tf_carry
                     tf_gt.copy_(gy[k - 1])
                     tf_sr.copy_(y8[k - 1])
+                if lp_scratch is not None:
+                    lp.append(M.lpips_layers_u8(y8, gy, lpips, lp_scratch))
                 if sink is not None:
                     ready = torch.cuda.Event()
                     ready.record(main)
@@ -424,7 +457,8 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
             host = lambda parts, dim, empty: torch.cat(parts, dim=dim).cpu().numpy() if parts else np.zeros(empty, np.int64)
             result = (s, host(sse_y, 0, 0), host(sse_c, 1, (2, 0)), host(ssim, 0, 0).astype(np.float64),
                       host(ms, 0, (0, 5, 2)).astype(np.float64), host(nq, 0, (0, 1, 36)).astype(np.float64),
-                      host(bq, 0, (0, 36)).astype(np.float64), host(tf, 0, 0).astype(np.float64))
+                      host(bq, 0, (0, 36)).astype(np.float64), host(tf, 0, 0).astype(np.float64),
+                      host(lp, 0, (0, 5)).astype(np.float64))
             torch.cuda.synchronize(dev)
     return result
 
@@ -433,7 +467,7 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
                       share_compensation: bool = False, crop_border: int = 4, quantise: str = "trunc", workers: int = 8,
                       png_level: int = 6, gumbel_uniform: Optional[Sequence] = None,
                       frame_noise: Optional[Sequence] = None, msssim: bool = False, niqe=None, brisque=None,
-                      tof: bool = False) -> SequenceResult:
+                      tof: bool = False, lpips=None) -> SequenceResult:
     """Super-resolve the sequence in ``lr_dir`` / ``side_dir`` (the reference's test layout, see cdfo_amd/priors.py) with ``model`` (on a
     GPU), ``chunk`` centre frames per forward.  ``save_dir``: write every frame as an 8-bit PNG under its LR file name.  ``gt_dir``:
     per-frame PSNR / SSIM of the 8-bit frames against ``<gt_dir>/%05d.png`` over the common size less ``crop_border``.
@@ -448,7 +482,11 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
     model); every output frame is then scored as well (`metrics.brisque_u8`, lower is better), with or without ground truth; the x4
     frames must be at least 16 x 16.  ``tof``: with ground truth, per-frame tOF as well (`metrics.tof_u8`: the mean distance between
     the Farneback flow of consecutive ground-truth frames and that of consecutive result frames over the whole common region, no
-    border dropped; lower is better); the region must be at least 32 x 32, and without ground truth it is a ValueError."""
+    border dropped; lower is better); the region must be at least 32 x 32, and without ground truth it is a ValueError.
+    ``lpips``: the model of the learned perceptual distance LPIPS, a path, the arrays or a `metrics.LpipsParams` (`metrics.lpips_params`;
+    the project ships no model, and parity with the ``lpips`` package is unpinned); with ground truth every frame's distance to it is
+    then reported as well (`metrics.lpips_u8`: VGG-shaped trunk on the luma over the whole common region, lower is better); the
+    region must be at least 16 x 16, and without ground truth it is a ValueError."""
     workers, chunk = _check_args(workers, quantise, chunk)
     t_start = time.perf_counter()
     lr = _PngSource(lr_dir)
@@ -461,6 +499,7 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
         if msssim:
             _check_msssim(lr, gt, crop_border)
     tof = _check_tof(lr, gt, tof)
+    lp_params = _check_lpips(lr, gt, lpips)
     if save_dir is not None:
         sink = _PngSink(save_dir, lr.names, png_level)   # the result PNGs take the LR frames' names (test_LD_37.py:180)
 
@@ -469,12 +508,12 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
         return StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"], gumbel_uniform=gumbel_uniform,
                            frame_noise=frame_noise), None
 
-    s, sse, _, ssim, ms, nq, bq, tf = _run_chunks(lr, load, gt, sink, chunk, share_compensation, crop_border, 0, quantise, workers,
-                                                  msssim, nq_params is not None, bq_params is not None, tof)
+    s, sse, _, ssim, ms, nq, bq, tf, lp = _run_chunks(lr, load, gt, sink, chunk, share_compensation, crop_border, 0, quantise, workers,
+                                                      msssim, nq_params is not None, bq_params is not None, tof, lp_params)
     psnr, ms, nq = _psnr(sse, lr.shape, gt and gt.shape, crop_border, 255), M.msssim_from_components(ms), _niqe(nq, nq_params)
-    bq = _brisque(bq, bq_params)
+    bq, lp = _brisque(bq, bq_params), _lpips(lp)
     return SequenceResult(psnr, ssim, _mean(psnr), _mean(ssim), lr.frames, s.seconds, time.perf_counter() - t_start, ms, _mean(ms),
-                          nq, _mean(nq), bq, _mean(bq), tf, _mean(tf))
+                          nq, _mean(nq), bq, _mean(bq), tf, _mean(tf), lp, _mean(lp))
 
 
 class YuvResult(NamedTuple):
@@ -499,13 +538,15 @@ class YuvResult(NamedTuple):
     mean_brisque: float = float("nan")
     tof: np.ndarray = _NO_FRAMES                    # of the luma; fp64 [T] with ``tof=True`` (needs ground truth), else empty
     mean_tof: float = float("nan")
+    lpips: np.ndarray = _NO_FRAMES                  # of the luma; fp64 [T] with ``lpips=`` a model (needs ground truth), else empty
+    mean_lpips: float = float("nan")
 
 
 def format_log_yuv(result: YuvResult, name: str) -> str:
     """`format_log` for a 4:2:0 result: the luma figures in the reference's places, then the chroma and the combined PSNR."""
     return '%s Average PSNR/SSIM: %.3f/%.5f PSNR-U/V/YUV: %.3f/%.3f/%.3f' % (
         name, result.mean_psnr_y, result.mean_ssim_y, result.mean_psnr_u, result.mean_psnr_v, result.mean_psnr_yuv) + _msssim_suffix(result) + \
-        _niqe_suffix(result) + _brisque_suffix(result) + _tof_suffix(result)
+        _niqe_suffix(result) + _brisque_suffix(result) + _tof_suffix(result) + _lpips_suffix(result)
 
 
 def chroma_crop(crop_border: int, chroma: str = "420") -> int:
@@ -525,7 +566,8 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
                  save_yuv: Optional[str] = None, chunk: int = 8, share_compensation: bool = False, crop_border: int = 4,
                  quantise: str = "trunc", workers: int = 8, gumbel_uniform: Optional[Sequence] = None,
                  frame_noise: Optional[Sequence] = None, gt_size: Optional[Tuple[int, int]] = None,
-                 pix_fmt: str = "yuv420p", msssim: bool = False, niqe=None, brisque=None, tof: bool = False) -> YuvResult:
+                 pix_fmt: str = "yuv420p", msssim: bool = False, niqe=None, brisque=None, tof: bool = False,
+                 lpips=None) -> YuvResult:
     """`evaluate_sequence` on raw 8-bit I420 files (cdfo_amd/yuv.py).  ``lr_yuv``: the LR sequence, ``width`` x ``height`` (even);
     the coding priors stay in ``side_dir``.  The luma goes the way it goes there (`StreamingSR.iter_chunked`, ``finish_frames`` with the
     PSNR numerator, ``ssim_u8``).  The chroma never passes through the model: per chunk the U and V planes of its centre frames are
@@ -542,7 +584,8 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     ``msssim``: as `evaluate_sequence`'s, on the luma (`metrics.msssim_u8` / `msssim_u16` with the format's peak).  ``niqe``: as
     `evaluate_sequence`'s, on the luma of 8-bit formats; above 8 bits it is a ValueError (the reference defines the metric on 0 .. 255
     integers).  ``brisque``: as `evaluate_sequence`'s, with the same restriction to 8-bit formats.  ``tof``: as `evaluate_sequence`'s, on
-    the luma of 8-bit formats with ground truth."""
+    the luma of 8-bit formats with ground truth.  ``lpips``: as `evaluate_sequence`'s, on the luma only, of 8-bit formats with ground
+    truth."""
     fmt = parse_pix_fmt(pix_fmt)
     workers, chunk = _check_args(workers, quantise, chunk)
     t_start = time.perf_counter()
@@ -563,6 +606,7 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
             if msssim:
                 _check_msssim(lr, gt, crop_border)
         tof = _check_tof(lr, gt, tof)
+        lp_params = _check_lpips(lr, gt, lpips)
         writer = YuvWriter(save_yuv, 4 * width, 4 * height, fmt) if save_yuv is not None else None
 
         def load():
@@ -571,9 +615,9 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
             return StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"],
                                gumbel_uniform=gumbel_uniform, frame_noise=frame_noise, peak=fmt.peak), lr_c
 
-        s, sse_y, sse_c, ssim, ms, nq, bq, tf = _run_chunks(lr, load, gt, writer and _YuvSink(writer), chunk, share_compensation,
-                                                            crop_border, ccrop, quantise, workers, msssim, nq_params is not None,
-                                                            bq_params is not None, tof)
+        s, sse_y, sse_c, ssim, ms, nq, bq, tf, lp = _run_chunks(lr, load, gt, writer and _YuvSink(writer), chunk, share_compensation,
+                                                                crop_border, ccrop, quantise, workers, msssim, nq_params is not None,
+                                                                bq_params is not None, tof, lp_params)
     finally:
         if writer is not None:
             writer.close()
@@ -582,9 +626,9 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     py = _psnr(sse_y, lr.shape, gt and gt.shape, crop_border, fmt.peak)
     pu, pv = (_psnr(e, lr.chroma_shape, gt and gt.chroma_shape, ccrop, fmt.peak) for e in sse_c)
     pyuv = psnr_yuv(py, pu, pv) if lr.chroma_shape is not None else py
-    ms, nq, bq = M.msssim_from_components(ms), _niqe(nq, nq_params), _brisque(bq, bq_params)
+    ms, nq, bq, lp = M.msssim_from_components(ms), _niqe(nq, nq_params), _brisque(bq, bq_params), _lpips(lp)
     return YuvResult(py, pu, pv, ssim, pyuv, _mean(py), _mean(pu), _mean(pv), _mean(ssim), _mean(pyuv), lr.frames, s.seconds,
-                     time.perf_counter() - t_start, ms, _mean(ms), nq, _mean(nq), bq, _mean(bq), tf, _mean(tf))
+                     time.perf_counter() - t_start, ms, _mean(ms), nq, _mean(nq), bq, _mean(bq), tf, _mean(tf), lp, _mean(lp))
 
 
 def _write_synthetic(root: str, T: int, H: int, W: int, seed: int, put_lr, put_gt, peak: int = 255) -> str:

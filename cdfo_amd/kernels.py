@@ -1050,6 +1050,97 @@ def tof_epe(a: torch.Tensor, b: torch.Tensor, partials: Optional[torch.Tensor] =
     return out
 
 
+# ---- LPIPS' own kernels (csrc/lpips.hip); cdfo_amd/metrics.py packs the model and puts the trunk and the distances together ----
+LPIPS_MIN, LPIPS_STRIP, LPIPS_STEM_MAXC, LPIPS_MAX_LAYERS = 16, 2, 256, 8       # CDFO_LPIPS_* of include/cdfo_hip.h
+
+
+def _lpips_act(t: torch.Tensor, name: str) -> tuple:
+    """The shape of a dense device NHWC fp32 stack [N,h,w,C] with no empty dimension and C a multiple of 4."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous() \
+            or 0 in t.shape or t.shape[3] % 4:
+        raise ValueError(f"{name}: a dense device fp32 tensor [N,h,w,C] with C a multiple of 4 expected, got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    return tuple(int(v) for v in t.shape)
+
+
+def _lpips_out(out: Optional[torch.Tensor], shape: tuple, like: torch.Tensor, name: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != like.device:
+        raise ValueError(f"{name}: out must be a dense fp32 {list(shape)} tensor on the source's device, got {out.dtype} "
+                         f"{tuple(out.shape)} strides {out.stride()} on {out.device}")
+    return out
+
+
+def lpips_stem(frames: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, normalize: bool = True,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """frames: uint8 [N,h,w] (or [h,w]) on the device with contiguous rows, read in place (a view of larger frames is a region);
+    weight fp32 [C0,3,3,3] and bias fp32 [C0] on the same device, C0 a multiple of 16, at most 256 -> fp32 [N,h,w,C0]: ReLU of the
+    trunk's first convolution on the three scaled channels of the luma (``normalize``: samples to -1 .. 1 first), zeros round the
+    SCALED tensor."""
+    f, N, h, w, fp, fs = _sample_frames(frames, "lpips_stem: frames", torch.uint8)
+    if N <= 0 or h <= 0 or w <= 0:
+        raise ValueError(f"lpips_stem: no samples in {N} frames of {h} x {w}")
+    for name, t in (("weight", weight), ("bias", bias)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != f.device:
+            raise ValueError(f"lpips_stem: {name} must be a dense fp32 tensor on the frames' device")
+    C0 = int(weight.shape[0]) if weight.dim() else 0
+    if tuple(weight.shape) != (C0, 3, 3, 3) or tuple(bias.shape) != (C0,) or C0 == 0 or C0 % 16 or C0 > LPIPS_STEM_MAXC:
+        raise ValueError(f"lpips_stem: weight [C0,3,3,3] and bias [C0] with C0 a multiple of 16 up to {LPIPS_STEM_MAXC} expected, got "
+                         f"{tuple(weight.shape)} and {tuple(bias.shape)}")
+    out = _lpips_out(out, (N, h, w, C0), f, "lpips_stem")
+    with on_device(f):
+        check(_lib.lib().cdfo_lpips_stem_u8(_vp(f), fp, C.c_longlong(fs), N, h, w, _vp(weight), _vp(bias), C0, int(bool(normalize)),
+                                            _vp(out), _stream()), "cdfo_lpips_stem_u8")
+    return out
+
+
+def lpips_pool2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x: dense fp32 [N,H,W,C] on the device, at least 2 x 2, C a multiple of 4 -> fp32 [N,H//2,W//2,C]: the 2 x 2 / stride 2
+    maximum, odd sizes floored; bit-equal to ``torch.max_pool2d``."""
+    N, H, W, Cc = _lpips_act(x, "lpips_pool2: x")
+    if H < 2 or W < 2:
+        raise ValueError(f"lpips_pool2: at least 2 x 2 expected, got {H} x {W}")
+    out = _lpips_out(out, (N, H // 2, W // 2, Cc), x, "lpips_pool2")
+    with on_device(x):
+        check(_lib.lib().cdfo_lpips_pool2(_vp(x), N, H, W, Cc, _vp(out), _stream()), "cdfo_lpips_pool2")
+    return out
+
+
+def lpips_dist(fa: torch.Tensor, fb: torch.Tensor, lin: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fa, fb: dense fp32 [N,h,w,C] on one device; lin: dense fp64 [C] there -> fp64 [N,G], G = ceil(h / 2): per strip of two rows
+    the sum over its pixels of sum_c lin[c] (fa_c / (|fa| + 1e-10) - fb_c / (|fb| + 1e-10))^2, in fp64 and in a fixed order."""
+    N, h, w, Cc = _lpips_act(fa, "lpips_dist: fa")
+    if _lpips_act(fb, "lpips_dist: fb") != (N, h, w, Cc) or fb.device != fa.device:
+        raise ValueError(f"lpips_dist: two stacks of one shape on one device expected, got {tuple(fa.shape)} and {tuple(fb.shape)}")
+    if not isinstance(lin, torch.Tensor) or lin.dtype != torch.float64 or tuple(lin.shape) != (Cc,) or not lin.is_contiguous() \
+            or lin.device != fa.device:
+        raise ValueError(f"lpips_dist: lin must be a dense fp64 [{Cc}] tensor on the stacks' device")
+    out = _f64_out(out, (N, (h + LPIPS_STRIP - 1) // LPIPS_STRIP), fa, "lpips_dist")
+    with on_device(fa):
+        check(_lib.lib().cdfo_lpips_dist(_vp(fa), _vp(fb), _vp(lin), N, h, w, Cc, _vp(out), _stream()), "cdfo_lpips_dist")
+    return out
+
+
+def lpips_fold(partials: torch.Tensor, N: int, strips, counts, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """partials: dense fp64 [N * sum(strips)] on the device, layer k's [N,strips[k]] block behind layer k - 1's -> fp64 [N,layers]:
+    the strips of each (frame, layer) added in index order and divided by counts[k] (the layer's pixels); one launch."""
+    N = int(N)
+    strips, counts = [int(v) for v in strips], [int(v) for v in counts]
+    if N <= 0 or not 0 < len(strips) <= LPIPS_MAX_LAYERS or len(counts) != len(strips) or min(strips) <= 0 or min(counts) <= 0:
+        raise ValueError(f"lpips_fold: frames and 1 .. {LPIPS_MAX_LAYERS} positive strip and pixel counts expected, got {N}, {strips}, "
+                         f"{counts}")
+    if not isinstance(partials, torch.Tensor) or not partials.is_cuda or partials.dtype != torch.float64 or partials.dim() != 1 \
+            or not partials.is_contiguous() or partials.numel() != N * sum(strips):
+        raise ValueError(f"lpips_fold: a dense device fp64 tensor of {N * sum(strips)} partial sums expected, got "
+                         f"{getattr(partials, 'dtype', type(partials))} {tuple(getattr(partials, 'shape', ()))}")
+    out = _f64_out(out, (N, len(strips)), partials, "lpips_fold")
+    g, n = (C.c_int * len(strips))(*strips), (C.c_longlong * len(counts))(*counts)
+    with on_device(partials):
+        check(_lib.lib().cdfo_lpips_fold(_vp(partials), N, len(strips), g, n, _vp(out), _stream()), "cdfo_lpips_fold")
+    return out
+
+
 def stem_conv(img: torch.Tensor, img_bstride: int, B: int, H: int, W: int, w: torch.Tensor, bias: torch.Tensor,
               act: int = ACT_NONE, add: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
               out2: Optional[torch.Tensor] = None, write_out: bool = True):

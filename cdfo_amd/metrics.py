@@ -26,12 +26,20 @@ fp64 (``brisque_from_features``); DESIGN.md has the definition, tests/brisque_re
 result: the mean endpoint distance between their dense Farneback flows (``farneback_u8``; per chunk ``tof_frames_u8``).  The
 definition is the project's own, after the algorithm OpenCV documents, with the reference's arguments; cv2 parity is unpinned.
 DESIGN.md has the definition, tests/tof_ref.py is its numpy statement.
+
+``lpips_u8``: LPIPS, the learned perceptual distance of a result to its ground truth, on the luma with a VGG-shaped trunk and a model
+the caller brings (``lpips_params``; the project ships none).  The trunk runs in fp32 on the matrix cores (``kernels.conv``), the
+distance behind the features in fp64; the device leaves five layer values per frame (``lpips_layers_u8``), the host adds them
+(``lpips_from_layers``).  The definition is the project's own; parity with the ``lpips`` package is unpinned.  DESIGN.md has the
+definition, tests/lpips_ref.py is its torch statement.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
 import os
+from collections.abc import Mapping
+from types import SimpleNamespace
 from typing import NamedTuple
 
 import numpy as np
@@ -748,3 +756,242 @@ def tof_u8(gt: torch.Tensor, sr: torch.Tensor) -> np.ndarray:
     """Per-frame tOF (lower is better) of two uint8 [T,H,W] device stacks, ground truth and result, fp64 numpy [T] on the host:
     `tof_frames_u8` on the whole sequence, frame 0 against itself."""
     return tof_frames_u8(gt, sr).cpu().numpy()
+
+
+# ---- LPIPS: the learned perceptual distance of result and ground truth, VGG-shaped trunk (DESIGN.md has the definition; csrc/lpips.hip) ----
+LPIPS_MIN = K.LPIPS_MIN                                 # the smallest region, each way: stage 5 is then 1 x 1
+LPIPS_STAGES = (2, 2, 3, 3, 3)                          # convolutions per stage; a 2 x 2 / 2 max-pool opens stages 2 .. 5
+LPIPS_WIDTHS = (64, 128, 256, 512, 512)                 # the published net's stage widths; a model's own are data
+LPIPS_TRUNK_KEYS = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)     # features.<i> of a VGG16 state dict, in order
+LPIPS_CONVS = sum(LPIPS_STAGES)
+
+
+class LpipsParams:
+    """The model LPIPS scores with: the trunk's 13 convolutions and the five per-channel weights of the distance."""
+
+    def __init__(self, weights, biases, lins):
+        self.weights = tuple(weights)                   # 13 x fp32 [Cout,Cin,3,3]
+        self.biases = tuple(biases)                     # 13 x fp32 [Cout]
+        self.lins = tuple(lins)                         # 5 x fp64 [C_k]
+        self.widths = tuple(int(l.shape[0]) for l in self.lins)
+        self._device = {}                               # the packed model per device: uploaded and packed once
+
+    def arrays(self) -> dict:
+        """The model as the mapping `lpips_params` reads: w0 .. w12, b0 .. b12, lin0 .. lin4."""
+        d = {f"w{i}": w for i, w in enumerate(self.weights)}
+        d.update({f"b{i}": b for i, b in enumerate(self.biases)})
+        d.update({f"lin{k}": l for k, l in enumerate(self.lins)})
+        return d
+
+
+def _lpips_state_dict(x, what: str) -> dict:
+    """A torch checkpoint (a path, read with torch.load alone, or the state dict itself) as {name: numpy array}."""
+    if isinstance(x, (str, os.PathLike)):
+        x = torch.load(os.fspath(x), map_location="cpu", weights_only=True)
+    if not isinstance(x, Mapping):
+        raise ValueError(f"LPIPS model: the {what} must be a state dict or a path to one, got {type(x).__name__}")
+    return {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in x.items()}
+
+
+def lpips_params(source) -> LpipsParams:
+    """The model from ``source``: a path to an ``.npz`` with ``w0`` .. ``w12`` ([Cout,Cin,3,3]), ``b0`` .. ``b12`` and ``lin0`` .. ``lin4``
+    ([C_k]); a mapping of those arrays; a pair (trunk, head) of torch checkpoints -- paths or state dicts, the trunk with VGG16's
+    ``features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.weight`` / ``.bias`` names, the head with ``lin{k}.model.1.weight`` -- or an
+    `LpipsParams`.  The project ships NO model (tools/make_lpips_model.py writes the ``.npz`` from a user's checkpoints).  Checked:
+    the topology (3 input channels, stages of 2, 2, 3, 3, 3 convolutions of one width each, every input width the width before),
+    widths that are multiples of 16 (the first at most 256), one weight per channel in every lin, every number finite."""
+    if isinstance(source, LpipsParams):
+        return source
+    if isinstance(source, (str, os.PathLike)):
+        path = os.fspath(source)
+        with np.load(path) as f:
+            source = {k: f[k] for k in f.files}
+    if not isinstance(source, Mapping):
+        pair = tuple(source)
+        if len(pair) != 2:
+            raise ValueError(f"LPIPS model: an .npz, a mapping of its arrays or a (trunk, head) pair of checkpoints expected, got {len(pair)} items")
+        trunk, head = _lpips_state_dict(pair[0], "trunk"), _lpips_state_dict(pair[1], "head")
+        source = {}
+        for i, key in enumerate(LPIPS_TRUNK_KEYS):
+            for short, kind in (("w", "weight"), ("b", "bias")):
+                if f"features.{key}.{kind}" not in trunk:
+                    raise ValueError(f"LPIPS model: no features.{key}.{kind} in the trunk's state dict")
+                source[f"{short}{i}"] = trunk[f"features.{key}.{kind}"]
+        for k in range(5):
+            if f"lin{k}.model.1.weight" not in head:
+                raise ValueError(f"LPIPS model: no lin{k}.model.1.weight in the head's state dict")
+            source[f"lin{k}"] = head[f"lin{k}.model.1.weight"]
+    names = [f"w{i}" for i in range(LPIPS_CONVS)] + [f"b{i}" for i in range(LPIPS_CONVS)] + [f"lin{k}" for k in range(5)]
+    missing = [n for n in names if n not in source]
+    if missing:
+        raise ValueError(f"LPIPS model: no {' / '.join(missing)} in the model")
+    ws = [np.ascontiguousarray(source[f"w{i}"], dtype=np.float32) for i in range(LPIPS_CONVS)]
+    bs = [np.ascontiguousarray(source[f"b{i}"], dtype=np.float32) for i in range(LPIPS_CONVS)]
+    lins = [np.array(source[f"lin{k}"], dtype=np.float64) for k in range(5)]
+    cin, i = 3, 0
+    for k, convs in enumerate(LPIPS_STAGES):
+        width = int(ws[i].shape[0]) if ws[i].ndim == 4 else 0
+        if width <= 0 or width % 16 or (k == 0 and width > K.LPIPS_STEM_MAXC):
+            raise ValueError(f"LPIPS model: stage {k + 1} has width {width}; widths are multiples of 16 (the first at most "
+                             f"{K.LPIPS_STEM_MAXC})")
+        for _ in range(convs):
+            if ws[i].shape != (width, cin, 3, 3) or bs[i].shape != (width,):
+                raise ValueError(f"LPIPS model: convolution {i} of stage {k + 1} must be [{width},{cin},3,3] with {width} biases, got "
+                                 f"{ws[i].shape} and {bs[i].shape}")
+            cin, i = width, i + 1
+        if lins[k].size != width or lins[k].ndim < 1 or max(lins[k].shape) != width:
+            raise ValueError(f"LPIPS model: lin{k} must hold {width} weights, got {lins[k].shape}")
+        lins[k] = np.ascontiguousarray(lins[k].reshape(-1))
+    if not all(np.isfinite(x).all() for x in ws + bs + lins):
+        raise ValueError("LPIPS model: every number must be finite")
+    for x in ws + bs + lins:
+        x.setflags(write=False)
+    return LpipsParams(ws, bs, lins)
+
+
+def lpips_random_params(widths=LPIPS_WIDTHS, seed: int = 0) -> LpipsParams:
+    """A He-initialised model of the given stage widths for tests and benchmarks: weights N(0, 2 / (9 Cin)), biases N(0, 0.05^2),
+    lin weights uniform in 0 .. 1 / C_k (the published ones are non-negative too).  It measures nothing perceptual."""
+    widths = tuple(int(v) for v in widths)
+    if len(widths) != 5:
+        raise ValueError(f"five stage widths expected, got {widths}")
+    rs = np.random.RandomState(seed)
+    arrays, cin, i = {}, 3, 0
+    for k, convs in enumerate(LPIPS_STAGES):
+        for _ in range(convs):
+            arrays[f"w{i}"] = (rs.standard_normal((widths[k], cin, 3, 3)) * math.sqrt(2.0 / (9 * cin))).astype(np.float32)
+            arrays[f"b{i}"] = (rs.standard_normal(widths[k]) * 0.05).astype(np.float32)
+            cin, i = widths[k], i + 1
+        arrays[f"lin{k}"] = (rs.uniform(0.0, 1.0, widths[k]) / widths[k]).astype(np.float32)
+    return lpips_params(arrays)
+
+
+def lpips_size(h: int, w: int):
+    """[(h_k, w_k)] of the five taps of an h x w region: each stage halves the one before, odd sizes floored.  ValueError below
+    16 x 16, where stage 5 would be empty."""
+    h, w = int(h), int(w)
+    if h < LPIPS_MIN or w < LPIPS_MIN:
+        raise ValueError(f"LPIPS needs a region of at least {LPIPS_MIN} x {LPIPS_MIN}, got {h} x {w}")
+    return [(h >> k, w >> k) for k in range(5)]
+
+
+def _lpips_widths(model) -> tuple:
+    widths = model.widths if isinstance(model, LpipsParams) else tuple(int(v) for v in model)
+    if len(widths) != 5 or min(widths) <= 0 or any(v % 16 for v in widths):
+        raise ValueError(f"five stage widths, multiples of 16, expected, got {widths}")
+    return widths
+
+
+class LpipsScratch:
+    """What `lpips_layers_u8` needs beside its frames for an ``h`` x ``w`` region and a trunk of the given stage widths: two ping-pong
+    fp32 feature buffers, each the largest activation of ``pairs`` (result, ground truth) pairs -- the trunk takes that many pairs per
+    pass whatever the chunk's size is -- and the distance's strip sums for up to ``frames`` frames per call.  ``nbytes``: its size
+    (`LpipsScratch.bytes_for` gives it without allocating).  Calls that share one must be ordered, which one stream does."""
+
+    @staticmethod
+    def _plan(pairs: int, h: int, w: int, widths, frames: int):
+        sizes = lpips_size(h, w)
+        widths = _lpips_widths(widths)
+        pairs, frames = int(pairs), int(frames)
+        if pairs <= 0 or frames <= 0:
+            raise ValueError(f"no LPIPS scratch for {pairs} pairs per pass and {frames} frames")
+        act = 2 * pairs * max(hk * wk * c for (hk, wk), c in zip(sizes, widths))
+        strips = tuple((hk + K.LPIPS_STRIP - 1) // K.LPIPS_STRIP for hk, _ in sizes)
+        return sizes, widths, pairs, frames, act, strips
+
+    @staticmethod
+    def bytes_for(pairs: int, h: int, w: int, widths=LPIPS_WIDTHS, frames: int = 8) -> int:
+        _, _, _, frames, act, strips = LpipsScratch._plan(pairs, h, w, widths, frames)
+        return 2 * 4 * act + 8 * frames * sum(strips)
+
+    def __init__(self, pairs: int, h: int, w: int, widths, frames: int, device):
+        self.sizes, self.widths, self.pairs, self.frames, act, self.strips = self._plan(pairs, h, w, widths, frames)
+        self.a = torch.empty(act, dtype=torch.float32, device=device)
+        self.b = torch.empty(act, dtype=torch.float32, device=device)
+        self.partials = torch.empty(self.frames * sum(self.strips), dtype=torch.float64, device=device)
+        self.h, self.w, self.device = int(h), int(w), self.a.device
+        self.nbytes = 4 * (self.a.numel() + self.b.numel()) + 8 * self.partials.numel()
+
+
+def lpips_scratch(n: int, h: int, w: int, model, device, pairs: int = 1) -> LpipsScratch:
+    """An `LpipsScratch` for calls of up to ``n`` frames of an ``h`` x ``w`` region: what `lpips_layers_u8` makes per call unless it
+    is handed one.  ``model``: an `LpipsParams` or the five stage widths.  ``pairs``: the pairs per pass of the trunk."""
+    return LpipsScratch(pairs, h, w, model, n, device)
+
+
+def _lpips_on(params: LpipsParams, device):
+    """The model on a device: the stem's weights as they are, the other twelve convolutions packed by `kernels.pack_conv`, the lin
+    weights in fp64.  Built once per model and device."""
+    device = torch.device(device)
+    if device not in params._device:
+        t = lambda a, dt: torch.from_numpy(np.array(a)).to(device=device, dtype=dt).contiguous()
+        with torch.cuda.device(device):
+            convs = [K.pack_conv(t(w, torch.float32), t(b, torch.float32)) for w, b in zip(params.weights[1:], params.biases[1:])]
+        params._device[device] = SimpleNamespace(w0=t(params.weights[0], torch.float32), b0=t(params.biases[0], torch.float32),
+                                                 convs=convs, lins=[t(l, torch.float64) for l in params.lins])
+    return params._device[device]
+
+
+def lpips_layers_u8(sr: torch.Tensor, gt: torch.Tensor, params, scratch: LpipsScratch = None, normalize: bool = True) -> torch.Tensor:
+    """fp64 device tensor [N,5]: per frame the five layer distances d_k of ``sr[j]`` to ``gt[j]`` over their common top-left region
+    (no border dropped), whose sum is LPIPS.  ``sr``, ``gt``: uint8 [N,H,W] (or [H,W]) on the device with contiguous rows, of possibly
+    different sizes, read in place; the region at least 16 x 16.  ``params``: what `lpips_params` takes.  ``normalize``: samples to
+    -1 .. 1 before the trunk's scaling (the default, and what the evaluators use); False feeds v / 255.  Result and ground truth of
+    ``scratch.pairs`` frames go through the trunk as ONE batch, so equal frames see equal arithmetic and score exactly 0; every
+    convolution writes into the scratch, and with a ``scratch`` (`lpips_scratch`) nothing here allocates beyond the result and
+    nothing waits for the device.  A pass is 2 + 12 + 4 + 5 launches, the call one more."""
+    a, N, Ha, Wa, _, _ = _sample_frames(sr, "sr", torch.uint8)
+    b, Nb, Hb, Wb, _, _ = _sample_frames(gt, "gt", torch.uint8)
+    if N == 0 or Nb != N or a.device != b.device:
+        raise ValueError(f"lpips_layers_u8: two stacks of one length on one device expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    h, w = min(Ha, Hb), min(Wa, Wb)
+    sizes = lpips_size(h, w)
+    params = lpips_params(params)
+    widths = params.widths
+    if scratch is None:
+        scratch = LpipsScratch(1, h, w, widths, N, a.device)
+    elif not isinstance(scratch, LpipsScratch) or scratch.device != a.device or (scratch.h, scratch.w) != (h, w) \
+            or scratch.widths != widths or scratch.frames < N:
+        raise ValueError(f"scratch: an lpips_scratch for at least {N} frames of a {h} x {w} region and widths {widths} on {a.device} expected")
+    a, b = a[:, :h, :w], b[:, :h, :w]
+    strips = scratch.strips
+    with on_device(a):
+        m = _lpips_on(params, a.device)
+        partials = scratch.partials[:N * sum(strips)]
+        first = [N * sum(strips[:k]) for k in range(5)]
+        for g0 in range(0, N, scratch.pairs):
+            g1 = min(g0 + scratch.pairs, N)
+            n = g1 - g0
+            act = lambda buf, k, c: buf[:2 * n * sizes[k][0] * sizes[k][1] * c].view(2 * n, sizes[k][0], sizes[k][1], c)
+            cur, other = scratch.a, scratch.b
+            x = act(cur, 0, widths[0])
+            K.lpips_stem(a[g0:g1], m.w0, m.b0, normalize, out=x[:n])
+            K.lpips_stem(b[g0:g1], m.w0, m.b0, normalize, out=x[n:])
+            i = 0
+            for k, convs in enumerate(LPIPS_STAGES):
+                if k:
+                    x = K.lpips_pool2(x, act(other, k, widths[k - 1]))
+                    cur, other = other, cur
+                for _ in range(convs - (k == 0)):
+                    x = K.conv(x, m.convs[i], pad=1, act=K.ACT_RELU, prec=K.PREC_F32, out=act(other, k, widths[k]))
+                    cur, other = other, cur
+                    i += 1
+                K.lpips_dist(x[:n], x[n:], m.lins[k], partials[first[k]:first[k] + N * strips[k]].view(N, strips[k])[g0:g1])
+        return K.lpips_fold(partials, N, strips, [hk * wk for hk, wk in sizes])
+
+
+def lpips_from_layers(layers) -> np.ndarray:
+    """fp64 numpy [N] from layer values [N,5] (or [5] -> a 0-d array), on the host: (((d_0 + d_1) + d_2) + d_3) + d_4."""
+    L = layers.detach().cpu().numpy() if isinstance(layers, torch.Tensor) else np.asarray(layers)
+    L = L.astype(np.float64)
+    if L.ndim not in (1, 2) or L.shape[-1] != 5:
+        raise ValueError(f"layer values [N,5] expected, got {L.shape}")
+    return (((L[..., 0] + L[..., 1]) + L[..., 2]) + L[..., 3]) + L[..., 4]
+
+
+def lpips_u8(sr: torch.Tensor, gt: torch.Tensor, params, normalize: bool = True, scratch: LpipsScratch = None) -> np.ndarray:
+    """Per-frame LPIPS (lower is better) of two uint8 [N,H,W] device stacks, result and ground truth, fp64 numpy [N] on the host:
+    `lpips_layers_u8` on the device, `lpips_from_layers` on the host.  ``params``: the caller's model (`lpips_params`), checked before
+    any device work; the project ships none, and parity with the ``lpips`` package is unpinned."""
+    params = lpips_params(params)
+    return np.atleast_1d(lpips_from_layers(lpips_layers_u8(sr, gt, params, scratch, normalize)))

@@ -791,6 +791,34 @@ int cdfo_tof_blur_solve(const double* M, int N, int h, int w, double* flow, void
 int cdfo_tof_flow_up(const double* src, int N, int hp, int wp, int h, int w, double* dst, void* stream);
 int cdfo_tof_epe(const double* a, const double* b, int K, int h, int w, double* partials, double* out, void* stream);
 
+/* ---- LPIPS: what a VGG-shaped trunk needs beside cdfo_conv_igemm, and the distance of two feature stacks (lpips.hip;
+ * cdfo_amd/metrics.py: lpips_layers_u8; DESIGN.md has the definition, the project's own: parity with the lpips package unpinned) ----
+ * Activations are dense NHWC fp32, 16-byte aligned (else CDFO_EALIGN); everything behind the features is fp64.  Grids and summation
+ * orders depend on the shapes alone and there are no atomics: equal inputs give equal bits, the distance of equal stacks is exactly
+ * 0 and swapping the stacks keeps its bits.  All on `stream`; at most 65535 frames per launch of the stem and of the distance.
+ * cdfo_lpips_stem_u8: N 8-bit frames, frame j at `src + j fstride` with rows at `pitch`, region h x w -> dst [N][h][w][C0] =
+ *                     ReLU(conv1_1): a sample v becomes x = v / 255, with `normalize` 2 x - 1, then the three channels (x -
+ *                     shift_c) / scale_c, shift = (-.030, -.088, -.188), scale = (.458, .448, .450); the SCALED tensor is padded
+ *                     with zeros; weight [C0][3][3][3] and bias [C0] fp32 on the device, C0 a multiple of 16, at most
+ *                     CDFO_LPIPS_STEM_MAXC.
+ * cdfo_lpips_pool2:   src [N][H][W][C] -> dst [N][H/2][W/2][C], the maximum of each 2 x 2 block (odd sizes floor; a NaN wins), C a
+ *                     multiple of 4.  Bit-exact.
+ * cdfo_lpips_dist:    fa, fb [N][h][w][C], lin [C] fp64 -> partials [N][G], G = ceil(h / CDFO_LPIPS_STRIP): per strip of rows the
+ *                     sum over its pixels of sum_c lin[c] (fa_c / (|fa| + 1e-10) - fb_c / (|fb| + 1e-10))^2, |.| the root of the
+ *                     pixel's sum of squares over the channels.  C a multiple of 4.
+ * cdfo_lpips_fold:    partials: the layers' [N][strips[k]] blocks one behind the other -> out [N][layers], the strips of (frame,
+ *                     layer) added in index order and divided by counts[k].  `strips` and `counts` are in HOST memory, at most
+ *                     CDFO_LPIPS_MAX_LAYERS of each. */
+#define CDFO_LPIPS_MIN 16
+#define CDFO_LPIPS_STRIP 2
+#define CDFO_LPIPS_STEM_MAXC 256
+#define CDFO_LPIPS_MAX_LAYERS 8
+int cdfo_lpips_stem_u8(const unsigned char* src, int pitch, long long fstride, int N, int h, int w, const float* weight,
+                       const float* bias, int C0, int normalize, float* dst, void* stream);
+int cdfo_lpips_pool2(const float* src, int N, int H, int W, int C, float* dst, void* stream);
+int cdfo_lpips_dist(const float* fa, const float* fb, const double* lin, int N, int h, int w, int C, double* partials, void* stream);
+int cdfo_lpips_fold(const double* partials, int N, int layers, const int* strips, const long long* counts, double* out, void* stream);
+
 /* ---- training batches and the training loss (train_batch.hip; cdfo_amd/train_data.py, cdfo_amd/loss.py) ----
  * cdfo_train_batch:   the resident clip set -- lr, pms, hr unsigned and rms signed 8-bit [S][T][H][W] ([S][T][4H][4W] for hr), ufs
  *                     [S][T][Hu][W] with Hu >= H rows indexed from the top, mvl0 signed 8-bit [S][T][H][W][3] (a, b, ref), all dense --

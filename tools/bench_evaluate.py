@@ -8,6 +8,7 @@
     python tools/bench_evaluate.py --niqe PARAMS [--yuv] [--size T H W] [--chunk K] [--repeats R]    NIQE: the kernels, and the option on / off
     python tools/bench_evaluate.py --brisque MODEL [--niqe PARAMS] [--yuv] [--size T H W] [--chunk K] [--repeats R]    BRISQUE likewise
     python tools/bench_evaluate.py --tof [--niqe PARAMS] [--yuv] [--size T H W] [--chunk K] [--repeats R]    tOF: the kernels, and the option on / off
+    python tools/bench_evaluate.py --lpips MODEL|random [--yuv] [--size T H W] [--chunk K] [--repeats R] [--only kernels|evaluator]    LPIPS likewise
 
 Sequence benchmark, one process, one warm-up pass then R passes each, medians: run_chunked alone; evaluate_sequence with metrics
 only; with metrics and PNG writing at 8 and 16 workers; and the per-chunk times of the finish kernel and the two 8-bit metric
@@ -27,7 +28,11 @@ alone, from events; then the evaluator with metrics only, ``niqe`` off and on in
 (a support-vector model, `metrics.brisque_params`): the seven launches of `brisque_features_u8` beside ssim_u8 (and, with --niqe
 PARAMS, `niqe_features_u8`) on the same chunk, each of its kernels alone, and the evaluator with ``brisque`` off and on.  --tof:
 the launches of `tof_frames_u8` on the same chunk (2 K Farneback pairs, the scratch held) beside ssim_u8 (and, with --niqe PARAMS,
-`niqe_features_u8`), each kernel's share summed over the stages, and the evaluator with ``tof`` off and on."""
+`niqe_features_u8`), each kernel's share summed over the stages, and the evaluator with ``tof`` off and on.  --lpips MODEL (a model
+file, `metrics.lpips_params`; ``random``: He-initialised weights of the published widths, which cost what real ones cost): the
+launches of `lpips_layers_u8` on the same chunk (K pairs through the trunk one pair per pass, the scratch held) beside ssim_u8, the
+split per stage -- stem, the convolutions of each stage, the pools, the distances, the fold -- from events round every launch, and
+the evaluator with ``lpips`` off and on; --only kernels / --only evaluator runs one half."""
 import os
 import sys
 import tempfile
@@ -482,8 +487,116 @@ def tof():
               f"{' '.join('%.2f' % f for f in fps[True])}; median {on:.2f} ({on / off:.4f} of off); mean tOF {r.mean_tof:.5f}", flush=True)
 
 
+def lpips():
+    from arch.SIDECVSR_our import CVSR_V8
+    from cdfo_amd import kernels as K
+    from cdfo_amd import metrics as M
+    from cdfo_amd.evaluate import evaluate_sequence, evaluate_yuv, write_synthetic_sequence, write_synthetic_sequence_yuv
+    source = sys.argv[sys.argv.index("--lpips") + 1]
+    params = M.lpips_random_params() if source == "random" else M.lpips_params(source)
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
+    T, H, W = _arg("--size", 3, [64, 270, 480])
+    chunk, reps = _arg("--chunk", 1, 8), _arg("--repeats", 1, 5)
+    if only != "evaluator":
+        rs = np.random.RandomState(0)
+        a = rs.randint(0, 256, (chunk, 4 * H, 4 * W))
+        b = np.clip(a + np.rint(20 * rs.randn(*a.shape)).astype(np.int64), 0, 255)
+        a, b = torch.from_numpy(a.astype(np.uint8)).cuda(), torch.from_numpy(b.astype(np.uint8)).cuda()
+        ls = M.lpips_scratch(chunk, 4 * H, 4 * W, params, a.device)
+        forms = [("ssim_u8", lambda: M.ssim_u8(a, b, 4)), ("lpips_layers_u8", lambda: M.lpips_layers_u8(a, b, params, ls))]
+        times = {name: [] for name, _ in forms}
+        for name, fn in forms:
+            fn()
+        torch.cuda.synchronize()
+        for _ in range(5):                                   # alternating forms: drift of the box falls on all alike
+            for name, fn in forms:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[name].append(e0.elapsed_time(e1))
+        med = {name: float(np.median(v)) for name, v in times.items()}
+        print(f"chunk of {chunk} pairs {4 * H}x{4 * W}, widths {params.widths} (wrappers included, scratch of {ls.nbytes} bytes held, "
+              f"{ls.pairs} pair per pass), median of 5 alternating passes: "
+              + "; ".join(f"{name} {med[name]:.3f} ms (passes {' '.join('%.3f' % x for x in times[name])})" for name, _ in forms)
+              + f": LPIPS x{med['lpips_layers_u8'] / med['ssim_u8']:.0f} of SSIM, {med['lpips_layers_u8'] / chunk:.3f} ms per pair", flush=True)
+        # the split: `lpips_layers_u8`'s own launches with events round each, summed per kind over the chunk's passes
+        m, sizes, widths = M._lpips_on(params, a.device), ls.sizes, params.widths
+        first = [chunk * sum(ls.strips[:k]) for k in range(5)]
+        partials = ls.partials[:chunk * sum(ls.strips)]
+
+        def one_chunk():
+            marks = []
+
+            def timed(label, fn):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                out = fn()
+                e1.record()
+                marks.append((label, e0, e1))
+                return out
+
+            for j in range(chunk):
+                act = lambda buf, k, c: buf[:2 * sizes[k][0] * sizes[k][1] * c].view(2, sizes[k][0], sizes[k][1], c)
+                cur, other = ls.a, ls.b
+                x = act(cur, 0, widths[0])
+                timed("stem x2", lambda: (K.lpips_stem(a[j:j + 1], m.w0, m.b0, True, out=x[:1]), K.lpips_stem(b[j:j + 1], m.w0, m.b0, True, out=x[1:])))
+                i = 0
+                for k, convs in enumerate(M.LPIPS_STAGES):
+                    if k:
+                        x = timed("pools", lambda: K.lpips_pool2(x, act(other, k, widths[k - 1])))
+                        cur, other = other, cur
+                    for _ in range(convs - (k == 0)):
+                        x = timed(f"convs stage {k + 1}", lambda: K.conv(x, m.convs[i], pad=1, act=K.ACT_RELU, prec=K.PREC_F32,
+                                                                          out=act(other, k, widths[k])))
+                        cur, other = other, cur
+                        i += 1
+                    timed("dist", lambda: K.lpips_dist(x[:1], x[1:], m.lins[k],
+                                                       partials[first[k]:first[k] + chunk * ls.strips[k]].view(chunk, ls.strips[k])[j:j + 1]))
+            timed("fold", lambda: K.lpips_fold(partials, chunk, ls.strips, [hk * wk for hk, wk in sizes]))
+            torch.cuda.synchronize()
+            sums = {}
+            for label, e0, e1 in marks:
+                sums[label] = sums.get(label, 0.0) + e0.elapsed_time(e1)
+            return sums
+
+        one_chunk()
+        passes = [one_chunk() for _ in range(5)]
+        split = {label: float(np.median([p[label] for p in passes])) for label in passes[0]}
+        flop = 2.0 * 9 * sum(w.shape[0] * w.shape[1] * sizes[k][0] * sizes[k][1]
+                             for k, n in enumerate(M.LPIPS_STAGES) for w in params.weights[sum(M.LPIPS_STAGES[:k]):sum(M.LPIPS_STAGES[:k]) + n])
+        conv_ms = sum(v for n, v in split.items() if n.startswith("convs") or n.startswith("stem"))
+        print(f"the split over the chunk's {chunk} passes, medians of 5 (wrapper included): " + "; ".join(f"{n} {v:.3f} ms" for n, v in split.items())
+              + f"; sum {sum(split.values()):.3f} ms; the trunk is {2 * flop / 1e12:.3f} TFLOP per pair: {2 * flop * chunk / conv_ms / 1e9:.1f} TFLOP/s "
+              "over the stem and the convolutions", flush=True)
+        del a, b, ls, partials
+    if only == "kernels":
+        return
+    model = CVSR_V8().cuda().eval()
+    with tempfile.TemporaryDirectory() as tmp:
+        if "--yuv" in sys.argv:
+            lr, side, gt = write_synthetic_sequence_yuv(tmp, T, H, W)
+            run = lambda on: evaluate_yuv(model, lr, W, H, side, gt_yuv=gt, chunk=chunk, lpips=params if on else None)
+        else:
+            lr, side, gt = write_synthetic_sequence(tmp, T, H, W)
+            run = lambda on: evaluate_sequence(model, lr, side, gt_dir=gt, chunk=chunk, lpips=params if on else None)
+        run(False), run(True)
+        fps = {False: [], True: []}
+        for _ in range(reps):                                # alternating passes: drift of the box falls on both alike
+            for on in (False, True):
+                r = run(on)
+                fps[on].append(r.frames / r.seconds_total)
+        off, on = float(np.median(fps[False])), float(np.median(fps[True]))
+        print(f"{'evaluate_yuv' if '--yuv' in sys.argv else 'evaluate_sequence'}, metrics only, {T} frames {H}x{W}, chunk {chunk}, end to "
+              f"end frames/s: lpips off per pass {' '.join('%.2f' % f for f in fps[False])}; median {off:.2f}; lpips on per pass "
+              f"{' '.join('%.2f' % f for f in fps[True])}; median {on:.2f} ({on / off:.4f} of off); mean LPIPS {r.mean_lpips:.5f}", flush=True)
+
+
 if __name__ == "__main__":
-    if "--tof" in sys.argv:
+    if "--lpips" in sys.argv:
+        lpips()
+    elif "--tof" in sys.argv:
         tof()
     elif "--brisque" in sys.argv:
         brisque()

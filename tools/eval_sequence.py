@@ -2,6 +2,7 @@
 
     python tools/eval_sequence.py --lr LR_DIR --side SIDE_DIR [--gt GT_DIR] [--out SAVE_DIR] [--chunk 8] [--share] [--workers 8]
                                   [--weights FILE.pth] [--name SEQUENCE] [--msssim] [--niqe PARAMS] [--brisque MODEL] [--tof]
+                                  [--lpips MODEL]
     python tools/eval_sequence.py --synthetic T H W [--out SAVE_DIR] ...
     python tools/eval_sequence.py --lr-yuv FILE --size W H --side SIDE_DIR [--gt-yuv FILE [--gt-size W H]] [--out-yuv FILE] ...
     python tools/eval_sequence.py --synthetic T H W --yuv [--out-yuv FILE] ...
@@ -21,6 +22,10 @@ the log line, or on the line of its own.
 --tof (any 8-bit form, with ground truth): the temporal-consistency figure tOF, the mean distance between the Farneback flow of consecutive
 ground-truth frames and that of consecutive result frames (cdfo_amd.metrics.tof_u8; the definition is the project's own, cv2 parity
 unpinned); `` tOF: %.5f`` last on the log line.  The common region must be at least 32 x 32.
+--lpips MODEL (any 8-bit form, with ground truth): LPIPS, the learned perceptual distance of every result frame's luma to the ground
+truth through a VGG-shaped trunk (cdfo_amd.metrics.lpips_u8), with the model in MODEL, an .npz with w0 .. w12, b0 .. b12 and lin0 ..
+lin4 (cdfo_amd.metrics.lpips_params; the project ships no model, tools/make_lpips_model.py writes one from a user's checkpoints;
+parity with the lpips package is unpinned); `` LPIPS: %.5f`` last on the log line.  The common region must be at least 16 x 16.
 
 Prints the reference's log line and frames/s, forward only and end to end.  --synthetic writes a random sequence of T frames of
 H x W with 4H x 4W ground truth into a temporary directory and evaluates that (with --weights absent the model is randomly
@@ -55,6 +60,7 @@ def main():
     ap.add_argument("--niqe", metavar="PARAMS", help="score every output frame with NIQE against this pristine model (.npz or .mat)")
     ap.add_argument("--brisque", metavar="MODEL", help="score every output frame with BRISQUE with this support-vector model (.npz)")
     ap.add_argument("--tof", action="store_true", help="report the luma's tOF (Farneback flow of result against ground truth) as well")
+    ap.add_argument("--lpips", metavar="MODEL", help="report the luma's LPIPS against the ground truth with this model (.npz) as well")
     ap.add_argument("--pix-fmt", default="yuv420p", help="the format of the raw files (cdfo_amd.yuv.parse_pix_fmt); default yuv420p")
     a = ap.parse_args()
     yuv = a.lr_yuv is not None or a.yuv
@@ -82,13 +88,13 @@ def main():
                 (lr, side, gt), size = write_synthetic_sequence_yuv(tmp, T, H, W, pix_fmt=a.pix_fmt), (W, H)
             r = evaluate_yuv(model, lr, size[0], size[1], side, gt_yuv=gt, save_yuv=a.out_yuv, chunk=a.chunk,
                              share_compensation=a.share, workers=a.workers, gt_size=tuple(a.gt_size) if a.gt_size else None,
-                             pix_fmt=a.pix_fmt, msssim=a.msssim, niqe=a.niqe, brisque=a.brisque, tof=a.tof)
+                             pix_fmt=a.pix_fmt, msssim=a.msssim, niqe=a.niqe, brisque=a.brisque, tof=a.tof, lpips=a.lpips)
         else:
             lr, side, gt = a.lr, a.side, a.gt
             if a.synthetic is not None:
                 lr, side, gt = write_synthetic_sequence(tmp, *a.synthetic)
             r = evaluate_sequence(model, lr, side, gt_dir=gt, save_dir=a.out, chunk=a.chunk, share_compensation=a.share,
-                                  workers=a.workers, msssim=a.msssim, niqe=a.niqe, brisque=a.brisque, tof=a.tof)
+                                  workers=a.workers, msssim=a.msssim, niqe=a.niqe, brisque=a.brisque, tof=a.tof, lpips=a.lpips)
     name = a.name or os.path.basename(os.path.normpath(lr if a.synthetic is None else "synthetic"))
     if gt is not None:
         print(format_log_yuv(r, name) if yuv else format_log(r, name))
