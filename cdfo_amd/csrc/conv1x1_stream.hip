@@ -456,17 +456,21 @@ struct sg_args {
   const float* w; const float* bias; int act_fn;      // packed [128/4][64][4] weights, optional bias
   long long P; int tiles_per_image; long long tiles;
   float* gram; float* sum0; float* sum1; int slots;
+  // PLANE form: x1 = stencil9 of a one-channel plane and never in memory.  src = {x0, q}; plane.w: the image-independent chunk table
+  // W1 . [w_s | b_s] of the product's second half; stencil: the un-composed table [w_s | b_s] ([64][16]) that turns the ten tap sums
+  // of a segment into sum1
+  pc_plane plane; const float* stencil;
 };
 
 constexpr int SG_NS = 3;
 
-template <int CH>
+template <int CH, bool PLANE = false>
 __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int NS = SG_NS, NKB = 2, IPT = 3, GS = CH + 2;
+  constexpr int NS = SG_NS, NKB = PLANE ? 1 : 2, IPT = NKB + 1, GS = CH + 2;
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // LDS map as conv1x1_stream_kernel<1>: weights hi | lo (16 KB each) | bias | 4 waves x NS stages
+  // LDS map as conv1x1_stream_kernel<1>: weights hi | lo (8 KB per K block each) | bias | 4 waves x NS stages
   constexpr int w_half = NKB * 4 * 2 * 64 * 16;
   constexpr int ring_off = 2 * w_half + 64 * 4;
   unsigned char* sWh = smem;
@@ -474,6 +478,11 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
   float* sBias = reinterpret_cast<float*>(smem + 2 * w_half);
   unsigned char* ring = smem + ring_off + wave * NS * ST_STAGE;
   const unsigned ring_lds = (unsigned)(unsigned long long)(smem) + ring_off + wave * NS * ST_STAGE;
+  // PLANE: behind the rings the chunk's weight image hi | lo, then NS tap slots per wave (as conv1x1_stream_kernel)
+  unsigned char* sPh = smem + ring_off + 4 * NS * ST_STAGE;
+  unsigned char* sPl = sPh + pc_weight_bytes(1) / 2;
+  const unsigned char* tap_slots = sPh + pc_weight_bytes(1) + wave * NS * PC_SLOT;
+  const unsigned tap_lds = (unsigned)(unsigned long long)(smem) + ring_off + 4 * NS * ST_STAGE + pc_weight_bytes(1) + wave * NS * PC_SLOT;
 
   const long long t_lo = a.tiles * blockIdx.x / gridDim.x, t_hi = a.tiles * (blockIdx.x + 1) / gridDim.x;
   if (t_lo >= t_hi) return;
@@ -489,7 +498,7 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
   auto part_off = [&](int q) { return r * 256 + ((q ^ (r & 15)) << 4); };
 
   // ---- the weights (the same for every image) -> LDS, split bf16 hi | lo, rows permuted
-  for (int i = tid; i < (128 >> 2) * 64; i += ST_THREADS) {
+  for (int i = tid; i < (NKB * 64 >> 2) * 64; i += ST_THREADS) {      // PLANE: the first 64 input channels of the 128 -> 64 packing
     const int rowpos = i % 64, kg = i / 64;
     const int n = mfma_row_channel(rowpos);
     const f32x4 wv = *reinterpret_cast<const f32x4*>(a.w + ((long long)kg * 64 + n) * 4);
@@ -501,6 +510,7 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
     *reinterpret_cast<u32x2*>(sWl + off) = lo;
   }
   for (int i = tid; i < 64; i += ST_THREADS) sBias[i] = a.bias ? a.bias[i] : 0.f;
+  if (PLANE) pc_load_weights<1>(a.plane.w, 64, sPh, sPl, tid);      // (the barrier of the first image's trip publishes them)
 
   // lane c of the statistics phases: channel c of q / kf / x0 / x1 of pixel p sits at p*256 + (((c >> 2) ^ (p & 15)) << 4) + (c & 3)*4
   const int c_part = lane >> 2, c_sub = (lane & 3) * 4, h_part = (lane / CH) * CH / 4;
@@ -517,6 +527,8 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
       const long long tile = img_t0 + it / IPT;
       const st_item src = a.src[(int)(it % IPT)];
       const long long p0 = (tile - (long long)b * a.tiles_per_image) * 128 + wave * 32;
+      if (PLANE && it % IPT == 0)      // the tile's taps, ahead of its first item (plane_chunk.h; the slot rules with ipt = 2)
+        pc_issue(pc_image(a.plane, b), (int)a.P, a.plane.W, (int)p0, lane, tap_lds + (unsigned)((it / IPT) % NS) * PC_SLOT);
       const long long rows_left = a.P - p0;                               // may be <= 0: everything out of range
       const float* base = src.base + ((long long)b * a.P + (rows_left > 0 ? p0 : 0)) * src.ld + src.ch0;
       i32x4 rsrc = lds_dma_rsrc_uniform(base, 0u);
@@ -531,11 +543,22 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
 
     f32x16 acc[2];
     float g[CH], sq = 0.f, sk = 0.f, sx[2] = {0.f, 0.f};     // the segment's running sums of lane c
+    // PLANE: this lane's running sums of the nine taps of its pixels as they enter the product, and the count of pixels inside
+    float ts[PLANE ? 10 : 1];
+#pragma unroll
+    for (int j = 0; j < (PLANE ? 10 : 1); ++j) ts[j] = 0.f;
 #pragma unroll
     for (int j = 0; j < CH; ++j) g[j] = 0.f;
     for (long long it = 0; it < n_items; ++it) {
       const int k = (int)(it % IPT);
-      st_wait_landed(issued - it - 1);
+      if (!PLANE) st_wait_landed(issued - it - 1);
+      else {
+        // IPT = 2, NS = 3: the requests run NS - 1 = 2 items ahead, so at most ONE item younger than `it` is in flight.  The order of
+        // the wave's pieces is ... [x0(t): 8] [q(t): 8] [taps(t + 1): 3] [x0(t + 1): 8] [q(t + 1): 8] ...
+        if (issued - it - 1 == 0) wait_vm<0>();      // the segment's last item: nothing younger, 0
+        else if (k == 0) wait_vm<8>();               // x0(t): q(t) is younger, 8 pieces; taps(t) are older than x0(t): landed with it
+        else wait_vm<11>();                          // q(t): taps(t + 1) and x0(t + 1) are younger, 3 + 8 = 11 pieces
+      }
       const unsigned char* st = ring + (it % NS) * ST_STAGE;
       if (k == 0) {
 #pragma unroll
@@ -567,6 +590,21 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
         for (int p = 0; p < 32; ++p)
           t4[p & 3] += *reinterpret_cast<const float*>(st + p * 256 + ((c_part ^ (p & 15)) << 4) + c_sub);
         sx[k] += (t4[0] + t4[1]) + (t4[2] + t4[3]);
+        if (PLANE) {
+          // the plane chunk's k-step closes the tile's product (x1 = stencil9 of the plane): the tile's slot landed before x0 (requested
+          // ahead of it) and is read here, with the tile's first item, before the request below can reuse any slot (plane_chunk.h)
+          const int p = (int)((img_t0 + it / IPT - (long long)b * a.tiles_per_image) * 128) + wave * 32 + r;
+          unsigned thi[4], tlo[4];
+          float t9[9];
+          pc_operand<true>(tap_slots + ((it / IPT) % NS) * PC_SLOT, r, h, p, (int)a.P, a.plane.W, thi, tlo, t9);
+          f32x16 pacc[1][2] = {{acc[0], acc[1]}};
+          pc_mfma<1>(sPh, sPl, r, h, thi, tlo, pacc);
+          acc[0] = pacc[0][0];
+          acc[1] = pacc[0][1];
+#pragma unroll
+          for (int j = 0; j < 9; ++j) ts[j] += t9[j];
+          ts[PLANE ? 9 : 0] += p < (int)a.P ? 1.f : 0.f;
+        }
         if (k == NKB - 1) {      // bias + activation: acc[ni][8 jj + q] = kf channel ni*32 + jj*16 + h*8 + q of pixel r; zero beyond the image
           const long long pin = (img_t0 + it / IPT - (long long)b * a.tiles_per_image) * 128 + wave * 32 + r;
           const bool inside = pin < a.P;
@@ -579,7 +617,8 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
             }
         }
       } else {
-        // ---- q has landed: kf -> the stage of the item before (free until the request below), then row c of the Gram
+        // ---- q has landed: kf -> the stage of the item before (x1's; PLANE: x0's -- already in the accumulators and in sx[0], free
+        // until the request below), then row c of the Gram
         unsigned char* kst = ring + ((it - 1) % NS) * ST_STAGE;
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
@@ -625,7 +664,17 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
       red[lane * GS + CH] = sq;
       red[lane * GS + CH + 1] = sk;
       red[64 * GS + lane] = sx[0];
-      red[64 * GS + 64 + lane] = sx[1];
+      if (!PLANE) red[64 * GS + 64 + lane] = sx[1];
+      else {
+        // the ten tap sums over the wave's 32 pixels, a fixed tree (both k-halves hold the same taps): ten numbers per wave
+#pragma unroll
+        for (int j = 0; j < 10; ++j) {
+          float v = ts[j];
+#pragma unroll
+          for (int m = 1; m < 32; m <<= 1) v += __shfl_xor(v, m, 64);
+          if (lane == 0) red[64 * GS + 64 + j] = v;
+        }
+      }
       __syncthreads();
       const int slot = (int)(blockIdx.x - st_owner((long long)b * a.tiles_per_image, a.tiles, gridDim.x));
       if (slot >= 0 && slot < a.slots) {
@@ -638,7 +687,19 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
           const float v = (r0[i] + r1[i]) + (r2[i] + r3[i]);
           if (i < 64 * GS) a.gram[bs * (64 * GS) + i] = v;
           else if (i < 64 * GS + 64) a.sum0[bs * 64 + (i - 64 * GS)] = v;
-          else a.sum1[bs * 64 + (i - 64 * GS - 64)] = v;
+          else if (!PLANE) a.sum1[bs * 64 + (i - 64 * GS - 64)] = v;
+          else {
+            // sum1[c] = sum_t w_s[c][t] S_t + b_s[c] count: the channel sum of stencil9 over the segment from its ten tap sums
+            // (waves in index order like every other sum here, then t ascending)
+            const int c = i - 64 * GS - 64;
+            float s1 = 0.f;
+#pragma unroll
+            for (int j = 0; j < 10; ++j) {
+              const int o = 64 * GS + 64 + j;
+              s1 = fmaf(a.stencil[c * 16 + j], (r0[o] + r1[o]) + (r2[o] + r3[o]), s1);
+            }
+            a.sum1[bs * 64 + c] = s1;
+          }
         }
       }
     }
@@ -675,34 +736,68 @@ extern "C" int cdfo_align_stats_slots(int B, long long P) {
   return cdfo_stream_slots_for_grid(B, P, cus);
 }
 
-extern "C" int cdfo_align_stats(const float* x0, int ld0, const float* x1, int ld1, const float* q, int ldq, const float* w_packed,
-                                const float* bias, int act, int ch_per_head, int B, long long P, int nslots, float* gram_partial,
-                                float* sum0_partial, float* sum1_partial, void* stream) {
-  if (B <= 0 || P <= 0 || nslots <= 0 || !x0 || !x1 || !q || !w_packed || !gram_partial || !sum0_partial || !sum1_partial) return CDFO_EINVAL;
+// pl != null: cdfo_align_stats_plane (x1 is the plane's stencil: x1 == null, ld1 unused)
+static int align_stats(const float* x0, int ld0, const float* x1, int ld1, const float* q, int ldq, const float* w_packed, const float* bias,
+                       int act, int ch_per_head, int B, long long P, int nslots, float* gram_partial, float* sum0_partial,
+                       float* sum1_partial, const pc_plane* pl, const float* stencil, void* stream) {
+  if (B <= 0 || P <= 0 || nslots <= 0 || !x0 || (!x1 && !pl) || !q || !w_packed || !gram_partial || !sum0_partial || !sum1_partial) return CDFO_EINVAL;
   if (act != CDFO_ACT_NONE && act != CDFO_ACT_LRELU && act != CDFO_ACT_RELU) return CDFO_EINVAL;
   if (ch_per_head != 8 && ch_per_head != 16) return CDFO_EINVAL;
-  const int lds_[3] = {ld0, ld1, ldq};
+  const int lds_[3] = {ld0, pl ? 64 : ld1, ldq};
   for (int i = 0; i < 3; ++i)
     if (lds_[i] < 64 || lds_[i] % 4 || (long long)lds_[i] * 4 * 32 >= (1ll << 31)) return CDFO_EINVAL;
   if (!aligned16(x0) || !aligned16(x1) || !aligned16(q) || !aligned16(w_packed) || !aligned16(gram_partial) || !aligned16(sum0_partial) ||
       !aligned16(sum1_partial))
     return CDFO_EALIGN;
   if ((P + 127) / 128 > 0x7fffffff / 2) return CDFO_EINVAL;
+  if (pl) {
+    // a plane outside the chunk's contract is an error: there is no other kernel for this form
+    if (!pl->base || !pl->w || !stencil || pl->Bi <= 0 || pl->s_b < 0 || pl->s_g < 0 || !pc_shape_ok(P, pl->W)) return CDFO_EINVAL;
+    if ((unsigned long long)pl->base % 4 || !aligned16(pl->w) || !aligned16(stencil)) return CDFO_EALIGN;
+  }
   hipStream_t st = static_cast<hipStream_t>(stream);
   sg_args s{};
-  s.src[0] = {x0, ld0, 0}; s.src[1] = {x1, ld1, 0}; s.src[2] = {q, ldq, 0};
+  s.src[0] = {x0, ld0, 0};
+  if (pl) { s.src[1] = {q, ldq, 0}; s.plane = *pl; s.stencil = stencil; }
+  else { s.src[1] = {x1, ld1, 0}; s.src[2] = {q, ldq, 0}; }
   s.w = w_packed; s.bias = bias; s.act_fn = act;
   s.P = P;
   s.gram = gram_partial; s.sum0 = sum0_partial; s.sum1 = sum1_partial; s.slots = nslots;
   int grid;
   if (!st_tiling(B, P, s.tiles_per_image, s.tiles, grid)) return CDFO_EINVAL;
   if (nslots < st_slots(B, s.tiles_per_image, grid)) return CDFO_EINVAL;
-  const int lds = st_lds_bytes(2, 1, SG_NS);
   const double px = (double)B * P;
+  if (pl) {
+    const int lds = st_lds_bytes(1, 1, SG_NS) + pc_lds_bytes(1, SG_NS);
+    static_assert(st_lds_bytes(1, 1, SG_NS) + pc_lds_bytes(1, SG_NS) <= ST_MAX_LDS, "the PLANE form's LDS (128256 bytes)");
+    // (the plane chunk: one k-step of 16 instead of a K block of 64, 4 bytes per pixel instead of 256)
+    CdfoProfScope prof(st, KID_GRAM, px * (2.0 * 80 * 64 + 2.0 * 64 * 18), 4.0 * 129 * px);
+    static CdfoAttrOnce once8p, once16p;
+    return ch_per_head == 16 ? st_launch(align_gram_partial_kernel<16, true>, once16p, grid, lds, st, s)
+                             : st_launch(align_gram_partial_kernel<8, true>, once8p, grid, lds, st, s);
+  }
+  const int lds = st_lds_bytes(2, 1, SG_NS);
   CdfoProfScope prof(st, KID_GRAM, px * (2.0 * 128 * 64 + 2.0 * 64 * 18), 4.0 * 192 * px);
   static CdfoAttrOnce once8, once16;
   return ch_per_head == 16 ? st_launch(align_gram_partial_kernel<16>, once16, grid, lds, st, s)
                            : st_launch(align_gram_partial_kernel<8>, once8, grid, lds, st, s);
+}
+
+extern "C" int cdfo_align_stats(const float* x0, int ld0, const float* x1, int ld1, const float* q, int ldq, const float* w_packed,
+                                const float* bias, int act, int ch_per_head, int B, long long P, int nslots, float* gram_partial,
+                                float* sum0_partial, float* sum1_partial, void* stream) {
+  if (!x1) return CDFO_EINVAL;
+  return align_stats(x0, ld0, x1, ld1, q, ldq, w_packed, bias, act, ch_per_head, B, P, nslots, gram_partial, sum0_partial, sum1_partial,
+                     nullptr, nullptr, stream);
+}
+
+extern "C" int cdfo_align_stats_plane(const float* x0, int ld0, const float* q, int ldq, const float* w_packed, const float* bias, int act,
+                                      int ch_per_head, int B, long long P, int nslots, float* gram_partial, float* sum0_partial,
+                                      float* sum1_partial, const float* plane, int plane_Bi, long long plane_sb, long long plane_sg,
+                                      int W, const float* plane_w, const float* stencil_w, void* stream) {
+  const pc_plane pl = {plane, plane_Bi, plane_sb, plane_sg, W, plane_w, 0};
+  return align_stats(x0, ld0, nullptr, 0, q, ldq, w_packed, bias, act, ch_per_head, B, P, nslots, gram_partial, sum0_partial, sum1_partial,
+                     &pl, stencil_w, stream);
 }
 
 // Returns 1 when the streaming kernel took the launch, 0 when the shapes are outside its contract (the caller falls back to

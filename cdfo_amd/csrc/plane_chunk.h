@@ -73,9 +73,11 @@ __device__ __forceinline__ void pc_issue(const float* img, int P, int W, int p0,
   }
 }
 
-// the pixel operand of lane (r, h): pixel p = p0 + r of the image, in column x = p % W; `slot` has landed
+// the pixel operand of lane (r, h): pixel p = p0 + r of the image, in column x = p % W; `slot` has landed.  TAPS_OUT: taps[0..8] also
+// receive the nine taps as they enter the product (zero outside the image and beyond its last pixel), for a caller that sums them
+template <bool TAPS_OUT = false>
 __device__ __forceinline__ void pc_operand(const unsigned char* slot, int r, int h, int p, int P, int W, unsigned (&hi)[4],
-                                           unsigned (&lo)[4]) {
+                                           unsigned (&lo)[4], float* taps = nullptr) {
   const int x = p % W;
   const bool inside = p < P, lok = inside && x > 0, rok = inside && x + 1 < W;
   float t[9];
@@ -93,6 +95,10 @@ __device__ __forceinline__ void pc_operand(const unsigned char* slot, int r, int
     v1[j] = h ? 0.f : t[4 + j];
   }
   split8_bf16(v0, v1, hi, lo);
+  if constexpr (TAPS_OUT) {
+#pragma unroll
+    for (int j = 0; j < 9; ++j) taps[j] = t[j];
+  }
 }
 
 // the chunk's k-step for NCB blocks of 64 output channels: acc[cb][ni] += W_chunk . operand (hi*lo + lo*hi + hi*hi)

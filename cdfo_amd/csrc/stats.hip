@@ -132,6 +132,10 @@ __global__ __launch_bounds__(256) void mdta_fold_kernel(const float* __restrict_
 // Wf = fusion_out = [Wa | Wb], g1/g2 = conv_du(avgpool(warped/pred)):
 //   relu(Wf . cat[P A (g1*warped) + P A (g2*pred), x]) = relu([Wa P A diag(g1) | Wa P A diag(g2) | Wb] . cat[warped,pred,x])
 // -> per-image packed 1x1 weights for Cin = 192.
+// PLANE (pred = stencil9 of a one-channel plane, stencil = its table [w_s | b_s] as [64][16]): with M1 / M2 the first two blocks above,
+// wout = the packed weights [M1 | Wb] for Cin = 128 over cat[warped, x], and tables[b] = M2 . [w_s | b_s] ([64][16], columns 10..15
+// zero): the plane chunk's weights of the same product (plane_chunk.h).  One body: M1, M2, Wb and the gates cannot drift apart.
+template <bool PLANE>
 __global__ __launch_bounds__(256) void align_fold_kernel(const float* __restrict__ gram_partial, int nchunk_g,
                                                          const float* __restrict__ sum_warp,
                                                          const float* __restrict__ sum_pred, int nchunk_s, float inv_P,
@@ -139,8 +143,10 @@ __global__ __launch_bounds__(256) void align_fold_kernel(const float* __restrict
                                                          const float* __restrict__ du0_w, const float* __restrict__ du0_b,
                                                          const float* __restrict__ du2_w, const float* __restrict__ du2_b,
                                                          const float* __restrict__ proj, const float* __restrict__ wf,
-                                                         float* __restrict__ wout) {
+                                                         float* __restrict__ wout, const float* __restrict__ stencil,
+                                                         float* __restrict__ tables) {
   constexpr int CH = 16;
+  __shared__ float M2[PLANE ? 64 * 64 : 1];
   __shared__ float stats[64 * (CH + 2)];
   __shared__ float attn[64 * CH];
   __shared__ float Q[64 * 64];
@@ -179,15 +185,28 @@ __global__ __launch_bounds__(256) void align_fold_kernel(const float* __restrict
     Q[idx] = s;
   }
   __syncthreads();
-  float* wo = wout + (long long)b * (192 * 64);
+  float* wo = wout + (long long)b * ((PLANE ? 128 : 192) * 64);
   for (int idx = threadIdx.x; idx < 4096; idx += blockDim.x) {
     const int o = idx >> 6, i = idx & 63, hb = (i / CH) * CH, j = i - hb;
     float r = 0.f;
 #pragma unroll
-    for (int cc = 0; cc < CH; ++cc) r += Q[o * 64 + hb + cc] * attn[(hb + cc) * CH + j];
+    for (int cc = 0; cc < CH; ++cc) r = fmaf(Q[o * 64 + hb + cc], attn[(hb + cc) * CH + j], r);      // (spelled out: both forms fuse alike)
     wo[((i >> 2) * 64 + o) * 4 + (i & 3)] = r * gate[0][i];
-    wo[(((64 + i) >> 2) * 64 + o) * 4 + (i & 3)] = r * gate[1][i];
-    wo[(((128 + i) >> 2) * 64 + o) * 4 + (i & 3)] = wf[o * 128 + 64 + i];
+    if (PLANE) M2[idx] = r * gate[1][i];
+    else wo[(((64 + i) >> 2) * 64 + o) * 4 + (i & 3)] = r * gate[1][i];
+    wo[((((PLANE ? 64 : 128) + i) >> 2) * 64 + o) * 4 + (i & 3)] = wf[o * 128 + 64 + i];
+  }
+  if (PLANE) {
+    // tables[b][o][j] = sum_i M2[o][i] stencil[i][j], i ascending, accumulated in double and rounded once
+    __syncthreads();
+    float* tb = tables + (long long)b * (64 * 16);
+    for (int idx = threadIdx.x; idx < 64 * 16; idx += blockDim.x) {
+      const int o = idx >> 4, j = idx & 15;
+      double s = 0.0;
+      if (j < 10)
+        for (int i = 0; i < 64; ++i) s = fma((double)M2[o * 64 + i], (double)stencil[i * 16 + j], s);
+      tb[idx] = (float)s;
+    }
   }
 }
 
@@ -266,9 +285,24 @@ extern "C" int cdfo_align_fold(const float* gram_partial, int nchunk_g, const fl
                                const float* fusion_w, int B, float* wout, void* stream) {
   if (B <= 0 || nchunk_g <= 0 || nchunk_s <= 0 || P <= 0) return CDFO_EINVAL;
   CdfoProfScope prof(static_cast<hipStream_t>(stream), KID_FOLD, 0, 0);
-  hipLaunchKernelGGL(align_fold_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), gram_partial, nchunk_g,
+  hipLaunchKernelGGL(align_fold_kernel<false>, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), gram_partial, nchunk_g,
                      sum_warp, sum_pred, nchunk_s, 1.0f / (float)P, temperature, du0_w, du0_b, du2_w, du2_b, proj_w,
-                     fusion_w, wout);
+                     fusion_w, wout, nullptr, nullptr);
+  CDFO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cdfo_align_fold_plane(const float* gram_partial, int nchunk_g, const float* sum_warp, const float* sum_pred,
+                                     int nchunk_s, long long P, const float* temperature, const float* du0_w,
+                                     const float* du0_b, const float* du2_w, const float* du2_b, const float* proj_w,
+                                     const float* fusion_w, const float* stencil_w, int B, float* wout, float* tables,
+                                     void* stream) {
+  if (B <= 0 || nchunk_g <= 0 || nchunk_s <= 0 || P <= 0 || !stencil_w || !wout || !tables) return CDFO_EINVAL;
+  if (!aligned16(wout) || !aligned16(tables)) return CDFO_EALIGN;
+  CdfoProfScope prof(static_cast<hipStream_t>(stream), KID_FOLD, 0, 0);
+  hipLaunchKernelGGL(align_fold_kernel<true>, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), gram_partial, nchunk_g,
+                     sum_warp, sum_pred, nchunk_s, 1.0f / (float)P, temperature, du0_w, du0_b, du2_w, du2_b, proj_w,
+                     fusion_w, wout, stencil_w, tables);
   CDFO_LAUNCH_CHECK();
   return 0;
 }

@@ -30,8 +30,8 @@ inline bool st_tiling(int B, long long P, int& tiles_per_image, long long& tiles
   return cus > 0;
 }
 // the kernels' LDS map: split weights hi | lo and the bias in front of the rings
-inline int st_weight_bytes(int nkb, int ncb) { return 2 * (nkb * 4 * 2 * ncb * 64 * 16) + ncb * 64 * 4; }
-inline int st_lds_bytes(int nkb, int ncb, int ns) { return st_weight_bytes(nkb, ncb) + 4 * ns * ST_STAGE; }
+constexpr int st_weight_bytes(int nkb, int ncb) { return 2 * (nkb * 4 * 2 * ncb * 64 * 16) + ncb * 64 * 4; }
+constexpr int st_lds_bytes(int nkb, int ncb, int ns) { return st_weight_bytes(nkb, ncb) + 4 * ns * ST_STAGE; }
 
 // `once`: the call site's static table, one per kernel instantiation.  Returns 0 or the hipError_t.
 template <class KernelPtr, class Args>

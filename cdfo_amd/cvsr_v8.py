@@ -164,7 +164,11 @@ class CVSR_V8(nn.Module):
         # developer A/B: CDFO_INLINE_RMS=0 -> the stem kernel writes fea_com).  Needs prior_stems: without it the stem launch that
         # writes du0 writes fea_com anyway
         self.inline_rms = switches.get("CDFO_INLINE_RMS")
-        self.neighbour_group = 0       # frames per neighbour group: 0 = auto = 3
+        # ... and ufs_prior = conv_expand_ufs(ufs) is never written either: its two readers (the alignment's statistics pass and the
+        # folded 192 -> 64 convolution) take it as the plane chunk of their products from the partition map (see _align_group, _align;
+        # developer A/B: CDFO_INLINE_UFS=0 -> one stem launch per neighbour writes ufs_prior).  Needs align_stats
+        self.inline_ufs = switches.get("CDFO_INLINE_UFS")
+        self.neighbour_group = 0      # frames per neighbour group: 0 = auto = 3
         # cached-feature call on one sequence (B = 1): the group of frames 0-2 (cached features only) starts beside the new
         # frame's feature extraction instead of behind it (see _forward)
         self.overlap_new_frame = switches.get("CDFO_OVERLAP_NEW")
@@ -318,6 +322,12 @@ class CVSR_V8(nn.Module):
         w["rms_chunk_input_conv"] = K.pack_plane_chunk(*K.compose_stem_1x1(
             sd["conv_expand_rms.weight"], sd["conv_expand_rms.bias"], sd["RDAB.input_conv.weight"],
             torch.zeros_like(sd["RDAB.input_conv.bias"])))
+        # conv_expand_ufs likewise: by itself (the statistics kernel's channel sums of ufs_prior from the map's tap sums, and what
+        # align_fold_plane composes with the per-image M2), and composed with the second half of fusion_out.0 for that kernel's kf
+        w["ufs_chunk"] = K.pack_plane_chunk(sd["conv_expand_ufs.weight"], sd["conv_expand_ufs.bias"])
+        fo = sd["MV_deform_align.fusion_out.0.weight"]
+        w["ufs_chunk_fusion_out"] = K.pack_plane_chunk(*K.compose_stem_1x1(
+            sd["conv_expand_ufs.weight"], sd["conv_expand_ufs.bias"], fo[:, 64:], fo.new_zeros(fo.shape[0])))
         w[fe + "side_to_feaoneUDSA.body.0_n16"] = K.pack_conv_n16(sd[fe + "side_to_feaoneUDSA.body.0.weight"])
         w["udsa_head"] = K.pack_udsa_head(sd[fe + "side_to_feaoneUDSA.body.0.weight"], sd[fe + "side_to_feaoneUDSA.body.0.bias"],
                                           sd["conv_second.weight"], sd["conv_second.bias"])
@@ -481,11 +491,12 @@ class CVSR_V8(nn.Module):
             return self._conv(cat, w["RDAB.fuse"], res1=x, plane=(*rms_planes, w["rms_chunk"]))
         return self._conv(cat, w["RDAB.fuse"], res1=x)
 
-    def _align(self, w, xc, extra, pred, mvs, mv_bstride, out, frames=None):
+    def _align(self, w, xc, extra, pred, mvs, mv_bstride, out, frames=None, ufs_planes=None):
         """DualAttAlignment (arch.py:3455-3496) on a group of neighbours: xc / extra / pred / out are [G*B,H,W,64] (xc = the
         centre frame's features repeated per neighbour), mvs one motion field view per neighbour.  frames (shared compensation):
         (bank, idx, mvs1, slot0) -- `extra` is None and image g*B + b is bank[idx[g*B + b]], warped in place by one launch with
-        the flow of window b at slot slot0 + g of mvs1 [B,7,2,H,W]."""
+        the flow of window b at slot slot0 + g of mvs1 [B,7,2,H,W].  ufs_planes (model.inline_ufs, with pred = None): the plane
+        addressing (view, Bi, s_b, s_g) of the partition maps whose conv_expand_ufs stencil pred is; it stays inside the products."""
         raw = w["raw"]
         a = "MV_deform_align."
         GB, H, W, _ = xc.shape
@@ -497,22 +508,28 @@ class CVSR_V8(nn.Module):
         for g, mv in enumerate(mvs if frames is None else ()):
             K.flow_warp(extra[g * B:(g + 1) * B], mv, mv_bstride, out=warped[g * B:(g + 1) * B])
         fused = self.precision != "f32" and self.align_stats
-        if fused:
+        fold_args = (raw[a + "temperature"], raw[a + "conv_du.0.weight"], raw[a + "conv_du.0.bias"], raw[a + "conv_du.2.weight"],
+                     raw[a + "conv_du.2.bias"], raw[a + "project_out.weight"], raw[a + "fusion_out.0.weight"])
+        if ufs_planes is not None:
+            # pred has two readers, both products over the pixel's channels: each takes it as one more k-step of ten numbers per pixel
+            # built from the partition map (the statistics pass with fusion_out.0's second half composed in, the folded convolution
+            # with the per-image M2), and the channel sums of pred come from the map's tap sums
+            gp, sw, sp, ng = K.align_stats(warped, None, xc, w[a + "fusion_out.0"], K.ACT_RELU, 16,
+                                           plane=(*ufs_planes, w["ufs_chunk_fusion_out"], w["ufs_chunk"]))
+            fold128, tables = K.align_fold_plane(gp, ng, sw, sp, ng, H * W, *fold_args, w["ufs_chunk"])
+            o, part, n = self._conv([warped, xc], fold128, act=K.ACT_RELU, chan_sum_out=True, plane=(*ufs_planes, tables, 64 * 16))
+        elif fused:
             # kf = relu(fusion_out.0([warped, pred])) has one consumer, the Gram: one pass over warped, pred, xc forms it tile by tile
             # and leaves the Gram and the two channel sums; kf never reaches memory
             gp, sw, sp, ng = K.align_stats(warped, pred, xc, w[a + "fusion_out.0"], K.ACT_RELU, 16)
-            ns = ng
+            fold = K.align_fold(gp, ng, sw, sp, ng, H * W, *fold_args)
+            o, part, n = self._conv([warped, pred, xc], fold, act=K.ACT_RELU, chan_sum_out=True)     # CALayer's pool from the epilogue
         else:
             kf = self._conv([warped, pred], w[a + "fusion_out.0"], act=K.ACT_RELU)
             gp, ng = K.gram_partial(xc, kf, 16)
             sw, ns = K.chan_sum_partial(warped)
             sp, _ = K.chan_sum_partial(pred)
-        fold = K.align_fold(gp, ng, sw, sp, ns, H * W, raw[a + "temperature"], raw[a + "conv_du.0.weight"],
-                            raw[a + "conv_du.0.bias"], raw[a + "conv_du.2.weight"], raw[a + "conv_du.2.bias"],
-                            raw[a + "project_out.weight"], raw[a + "fusion_out.0.weight"])
-        if fused:
-            o, part, n = self._conv([warped, pred, xc], fold, act=K.ACT_RELU, chan_sum_out=True)     # CALayer's pool from the epilogue
-        else:
+            fold = K.align_fold(gp, ng, sw, sp, ns, H * W, *fold_args)
             o = self._conv([warped, pred, xc], fold, act=K.ACT_RELU)
             part, n = K.chan_sum_partial(o)
         gate = K.vec_mlp(part, n, H * W, raw[a + "CALayer.conv_du.0.weight"], raw[a + "CALayer.conv_du.0.bias"], 64,
@@ -1223,18 +1240,26 @@ class CVSR_V8(nn.Module):
         raw = w["raw"]
         B, N, _, H, W = mvs1.shape
         GB, P = len(idxs) * B, H * W
-        ufs_prior = K.empty_act(GB, H, W, NF, xcG.device)
-        for n, i in enumerate(idxs):
-            K.stem_conv(ufs[:, 0, i], N * P, B, H, W, raw["conv_expand_ufs.weight"], raw["conv_expand_ufs.bias"],
-                        out=ufs_prior[n * B:(n + 1) * B])
+        # model.inline_ufs: ufs_prior has two readers, both matrix products over the pixel's channels -- they read the partition map
+        # itself.  The slots of a group are consecutive, so image n*B + b's plane lies at ufs[b, 0, idxs[0] + n]: always affine.  The
+        # same conditions for both callers: which path a frame takes must not depend on how many frames share the call
+        planes = ufs_prior = None
+        if (self.inline_ufs and "ufs_chunk" in w and self.precision != "f32" and not self.istraining and self.align_stats
+                and K.plane_ok(H, W) and ufs.dtype == torch.float32 and ufs.is_contiguous()):
+            planes = (ufs[:, 0, idxs[0]], B, N * P, P)
+        else:
+            ufs_prior = K.empty_act(GB, H, W, NF, xcG.device)
+            for n, i in enumerate(idxs):
+                K.stem_conv(ufs[:, 0, i], N * P, B, H, W, raw["conv_expand_ufs.weight"], raw["conv_expand_ufs.bias"],
+                            out=ufs_prior[n * B:(n + 1) * B])
         al = K.empty_act(GB, H, W, NF, xcG.device)
         xc = xcG if xcG.shape[0] == GB else xcG[:GB]
         self._align(w, xc, extra, ufs_prior, [mvs1[:, i] for i in idxs], N * 2 * P, al,
-                    frames=None if frames is None else (*frames, mvs1, idxs[0]))
+                    frames=None if frames is None else (*frames, mvs1, idxs[0]), ufs_planes=planes)
         if self.debug_taps is not None:
             for n, i in enumerate(idxs):
                 self.debug_taps[f"align_{i}"] = al[n * B:(n + 1) * B]
-        keep.extend([ufs_prior, xc])
+        keep.extend([xc] if ufs_prior is None else [ufs_prior, xc])
         return al
 
     @staticmethod

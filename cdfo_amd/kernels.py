@@ -1591,12 +1591,17 @@ def align_stats_slots(B: int, P: int) -> int:
     return n
 
 
-def align_stats(x0: torch.Tensor, x1: torch.Tensor, q: torch.Tensor, pc: PackedConv, act: int, ch_per_head: int):
+def align_stats(x0: torch.Tensor, x1: Optional[torch.Tensor], q: torch.Tensor, pc: PackedConv, act: int, ch_per_head: int, plane=None):
     """The statistics of DualAttAlignment in one pass over x0, x1, q ([B,H,W,64] each, any pixel pitch): with
     kf = act(conv1x1([x0, x1], pc)) (128 -> 64, never written) returns (gram, sum0, sum1, n) = gram_partial(q, kf, ch_per_head)[0],
-    chan_sum_partial(x0)[0], chan_sum_partial(x1)[0] with n partial slots each (fixed-order sums: run-to-run identical)."""
+    chan_sum_partial(x0)[0], chan_sum_partial(x1)[0] with n partial slots each (fixed-order sums: run-to-run identical).
+    plane = (view, Bi, s_b, s_g, table, stencil) with x1 = None: x1 is the 3x3 stencil `stencil` (pack_plane_chunk of it) of the
+    one-channel planes `view` addresses (see _plane_args) and is never materialised; table: pack_plane_chunk of pc's second half
+    composed with the stencil (compose_stem_1x1).  sum1 is then formed from the planes' tap sums."""
+    if (x1 is None) != (plane is not None):
+        raise ValueError("align_stats: either x1 or the plane it is a stencil of")
     B, H, W, c0, ld0 = _chk_act(x0, "x0")
-    b1, h1, w1, c1, ld1 = _chk_act(x1, "x1")
+    b1, h1, w1, c1, ld1 = (B, H, W, 64, 0) if x1 is None else _chk_act(x1, "x1")
     bq, hq, wq, cq, ldq = _chk_act(q, "q")
     if (b1, h1, w1) != (B, H, W) or (bq, hq, wq) != (B, H, W) or (c0, c1, cq) != (64, 64, 64):
         raise ValueError("align_stats: three [B,H,W,64] operands expected")
@@ -1608,6 +1613,16 @@ def align_stats(x0: torch.Tensor, x1: torch.Tensor, q: torch.Tensor, pc: PackedC
     gram = buf[:B * n * gs].view(B, n, gs)
     s0 = buf[B * n * gs:B * n * (gs + 64)].view(B, n, 64)
     s1 = buf[B * n * (gs + 64):].view(B, n, 64)
+    if plane is not None:
+        view, Bi, s_b, s_g, table, _ = _plane_args(plane[:5], B, H, W, 64, "align_stats")
+        stencil = plane[5]
+        if (tuple(stencil.shape) != (64, 16) or stencil.dtype != torch.float32 or not stencil.is_contiguous()
+                or stencil.device != table.device or table.dim() != 2):
+            raise ValueError("align_stats: the stencil's table and the composed table must be fp32 [64,16] (pack_plane_chunk)")
+        check(_lib.lib().cdfo_align_stats_plane(_vp(x0), ld0, _vp(q), ldq, _vp(pc.w), _vp(pc.bias), act, ch_per_head, B,
+                                                C.c_longlong(H * W), n, _vp(gram), _vp(s0), _vp(s1), _vp(view), Bi, C.c_longlong(s_b),
+                                                C.c_longlong(s_g), W, _vp(table), _vp(stencil), _stream()), "cdfo_align_stats_plane")
+        return gram, s0, s1, n
     check(_lib.lib().cdfo_align_stats(_vp(x0), ld0, _vp(x1), ld1, _vp(q), ldq, _vp(pc.w), _vp(pc.bias), act, ch_per_head, B,
                                       C.c_longlong(H * W), n, _vp(gram), _vp(s0), _vp(s1), _stream()), "cdfo_align_stats")
     return gram, s0, s1, n
@@ -1647,6 +1662,21 @@ def align_fold(gpart, ng, sw, sp, ns, P, temperature, du0_w, du0_b, du2_w, du2_b
                                      _vp(du0_w), _vp(du0_b), _vp(du2_w), _vp(du2_b), _vp(proj_w), _vp(fusion_w), B,
                                      _vp(wout), _stream()), "cdfo_align_fold")
     return PackedConv(wout, None, 64, 192, 1, 64, False, 192 * 64)
+
+
+def align_fold_plane(gpart, ng, sw, sp, ns, P, temperature, du0_w, du0_b, du2_w, du2_b, proj_w, fusion_w, stencil):
+    """align_fold where pred stays a one-channel plane (stencil: pack_plane_chunk of its 3x3 stem): returns (PackedConv 128 -> 64 over
+    cat[warped, x] = align_fold's columns [M1 | Wb], bit for bit; tables [B,64,16] = M2 . [w_s | b_s], the per-image plane tables of
+    conv(..., plane=(..., tables, 64 * 16)))."""
+    B = gpart.shape[0]
+    if tuple(stencil.shape) != (64, 16) or stencil.dtype != torch.float32 or not stencil.is_contiguous():
+        raise ValueError("align_fold_plane: the stencil's table must be fp32 [64,16] (pack_plane_chunk)")
+    wout = torch.empty((B, 128 * 64), dtype=torch.float32, device=gpart.device)
+    tables = torch.empty((B, 64, 16), dtype=torch.float32, device=gpart.device)
+    check(_lib.lib().cdfo_align_fold_plane(_vp(gpart), ng, _vp(sw), _vp(sp), ns, C.c_longlong(P), _vp(temperature),
+                                           _vp(du0_w), _vp(du0_b), _vp(du2_w), _vp(du2_b), _vp(proj_w), _vp(fusion_w), _vp(stencil),
+                                           B, _vp(wout), _vp(tables), _stream()), "cdfo_align_fold_plane")
+    return PackedConv(wout, None, 64, 128, 1, 64, False, 128 * 64), tables
 
 
 def vec_mlp(part: torch.Tensor, n: int, P: int, w1, b1, c1: int, act1: int, w2=None, b2=None, c2: int = 0,

@@ -285,6 +285,17 @@ int cdfo_stream_slot_of(int B, long long P, int grid, int wg, int b);
 int cdfo_align_stats(const float* x0, int ld0, const float* x1, int ld1, const float* q, int ldq, const float* w_packed,
                      const float* bias, int act, int ch_per_head, int B, long long P, int nslots, float* gram_partial,
                      float* sum0_partial, float* sum1_partial, void* stream);
+/* The same where x1 = stencil9(plane; w_s, b_s) (zero padding) of a ONE-channel W-pixel-wide plane per image and is never materialised:
+ * image b's plane (dense fp32 rows, P = H W pixels) starts at plane + (b % plane_Bi) plane_sb + (b / plane_Bi) plane_sg floats.
+ * w_packed / bias: as above (the 128 -> 64 packing; its second half is not read); plane_w [64][16] fp32: the product's second half
+ * composed with the stencil, row n = sum_c W[n][64 + c] w_s[c][0..8] | sum_c W[n][64 + c] b_s[c] | six zeros, one split-bf16 k-step of
+ * 16 behind the K block of x0; stencil_w [64][16] fp32: w_s[c][0..8] | b_s[c] | six zeros, from which sum1_partial[b][slot][c] =
+ * sum_t w_s[c][t] S_t + b_s[c] count is formed out of the segment's nine tap sums S_t and its pixel count (fixed order).  Both tables
+ * 16-byte aligned.  P % W == 0, P + 2 W + 64 < 2^29, else CDFO_EINVAL: there is no other kernel for this form.  */
+int cdfo_align_stats_plane(const float* x0, int ld0, const float* q, int ldq, const float* w_packed, const float* bias, int act,
+                           int ch_per_head, int B, long long P, int nslots, float* gram_partial, float* sum0_partial,
+                           float* sum1_partial, const float* plane, int plane_Bi, long long plane_sb, long long plane_sg, int W,
+                           const float* plane_w, const float* stencil_w, void* stream);
 /* MDTA (arch.py:1555-1575): wout[b] = packed 1x1 weights (64->64) = project_out x blockdiag(softmax(...)). */
 int cdfo_mdta_fold(const float* partial, int nchunk, const float* temperature, const float* proj_w, int B, float* wout,
                    void* stream);
@@ -292,6 +303,14 @@ int cdfo_mdta_fold(const float* partial, int nchunk, const float* temperature, c
 int cdfo_align_fold(const float* gram_partial, int nchunk_g, const float* sum_warp, const float* sum_pred, int nchunk_s,
                     long long P, const float* temperature, const float* du0_w, const float* du0_b, const float* du2_w,
                     const float* du2_b, const float* proj_w, const float* fusion_w, int B, float* wout, void* stream);
+/* The same where pred = stencil9(plane; w_s, b_s) stays a one-channel plane (stencil_w [64][16]: w_s[c][0..8] | b_s[c] | zeros): with
+ * [M1 | M2 | Wb] the three 64-column blocks of cdfo_align_fold's weights, wout[b] = packed 1x1 weights (128->64) [M1 | Wb] over
+ * cat[warped, x] (bit-equal to those columns) and tables[b] = M2 . [w_s | b_s] as [64][16] fp32, columns 10..15 zero: the per-image
+ * plane_w of cdfo_conv1x1_bf16x3_plane (image pitch 64 * 16).  wout, tables 16-byte aligned.  */
+int cdfo_align_fold_plane(const float* gram_partial, int nchunk_g, const float* sum_warp, const float* sum_pred, int nchunk_s,
+                          long long P, const float* temperature, const float* du0_w, const float* du0_b, const float* du2_w,
+                          const float* du2_b, const float* proj_w, const float* fusion_w, const float* stencil_w, int B,
+                          float* wout, float* tables, void* stream);
 /* out[b] = act2(W2 act1(W1 mean_b + b1) + b2) from channel-sum partials (CALayer / conv_du_re2). */
 int cdfo_vec_mlp(const float* sum_partial, int nchunk, long long P, const float* w1, const float* b1, int c1, int act1,
                  const float* w2, const float* b2, int c2, int act2, int B, float* out, void* stream);

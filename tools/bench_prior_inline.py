@@ -2,8 +2,10 @@
 each changed launch next to what it replaces.
   rms half (model.inline_rms): 3 x stem_conv (fea_com = fea + conv_expand_rms(rms)) + 3 x rdab_prep_fused(fea_com) + RDAB.fuse with
       res1 = fea_com   against   3 x rdab_prep_fused(fea, plane) + RDAB.fuse with res1 = fea and the plane.
-  K-block form (not used by the model yet): 3 x stem_conv (the 64-channel operand) + the per-image 192 -> 64 convolution with channel sums
-      against   the 128 -> 64 convolution with the plane."""
+  K-block form: 3 x stem_conv (the 64-channel operand) + the per-image 192 -> 64 convolution with channel sums
+      against   the 128 -> 64 convolution with the plane.
+  ufs half (model.inline_ufs), the alignment's whole chain: 3 x stem_conv (ufs_prior) + align_stats + align_fold + the 192 -> 64
+      convolution with channel sums   against   align_stats(plane) + align_fold_plane + the 128 -> 64 convolution with the plane."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -78,6 +80,23 @@ def main():
     t = [_time(f) for f in (stems_k, k_old, k_new)]
     print(f"K-block form {G}x{B}x{H}x{W}: stem_conv x3 {t[0]:.4f} + 192->64 with sums {t[1]:.4f} = {t[0] + t[1]:.4f} ms;  "
           f"128->64 with the plane and sums {t[2]:.4f} ms")
+
+    # the alignment half: statistics, fold and the folded convolution on both paths
+    q = r(M, H, W, 64)
+    t_stats = K.pack_plane_chunk(*K.compose_stem_1x1(ws, bs, wf[:, 64:], torch.zeros_like(bs)))
+    par = (r(4).abs() + 0.5, r(4, 64) * 0.2, r(4) * 0.1, r(64, 4) * 0.5, r(64) * 0.1, r(64, 64) / 8, wf.view(64, 128).contiguous())
+    st_old = lambda: K.align_stats(x0, pred, q, pcf, K.ACT_RELU, 16)
+    st_new = lambda: K.align_stats(x0, None, q, pcf, K.ACT_RELU, 16, plane=(*addr, t_stats, t_res))
+    gp, s0, s1, n = st_old()
+    fo_old = lambda: K.align_fold(gp, n, s0, s1, n, P, *par)
+    fo_new = lambda: K.align_fold_plane(gp, n, s0, s1, n, P, *par, t_res)
+    f192, (f128, ftab) = fo_old(), fo_new()
+    c_old = lambda: K.conv([x0, pred, q], f192, act=K.ACT_RELU, out=out, prec=K.PREC_FP16X2, chan_sum_out=True)
+    c_new = lambda: K.conv([x0, q], f128, act=K.ACT_RELU, out=out, prec=K.PREC_FP16X2, chan_sum_out=True, plane=(*addr, ftab, 1024))
+    t = [_time(f) for f in (stems_k, st_old, fo_old, c_old, st_new, fo_new, c_new)]
+    print(f"ufs half {G}x{B}x{H}x{W}: stem_conv x3 {t[0]:.4f} + align_stats {t[1]:.4f} + align_fold {t[2]:.4f} + 192->64 with sums {t[3]:.4f} = "
+          f"{sum(t[:4]):.4f} ms;  with the plane: align_stats {t[4]:.4f} + align_fold_plane {t[5]:.4f} + 128->64 with sums {t[6]:.4f} = "
+          f"{sum(t[4:]):.4f} ms")
 
 
 if __name__ == "__main__":
