@@ -8,6 +8,8 @@
 //   seq_attn    : softmax(Q Q^T) V over a row, a column or an 8x8 window, one query per lane, keys streamed through
 //                 wave-uniform (scalar) loads, online softmax in registers.
 #include "plane_chunk.h"
+#include "image_map.h"
+#include <type_traits>
 
 namespace {
 
@@ -152,10 +154,15 @@ struct rf_args {
   // memory; the stencil's part joins the product as the plane chunk of plane_chunk.h, plane.w = input_conv . [w_s | b_s], [128][16]
   pc_plane plane;
 };
+// MAP form: where the images of x lie (image_map.h).  A block of its own that only the MAP instantiations take: the other forms'
+// kernel arguments, and with them their instructions, stay what they were
+struct rf_args_map : rf_args {
+  im_map x_map;
+};
 
-// PLANE is a template parameter: the other form's instructions stay what they were
-template <bool RNG, typename VT, typename WT, bool PLANE = false>      // VT: vrow, WT: window V
-__global__ __launch_bounds__(ST_THREADS) void rdab_prep_kernel_fused(rf_args a) {
+// PLANE is a template parameter: the other form's instructions stay what they were; so is MAP
+template <bool RNG, typename VT, typename WT, bool PLANE = false, bool MAP = false>      // VT: vrow, WT: window V
+__global__ __launch_bounds__(ST_THREADS) void rdab_prep_kernel_fused(std::conditional_t<MAP, rf_args_map, rf_args> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rf_smem[];
   constexpr int NCB = 2;
   constexpr bool VH = sizeof(VT) == 2, WH = sizeof(WT) == 2;
@@ -228,7 +235,11 @@ __global__ __launch_bounds__(ST_THREADS) void rdab_prep_kernel_fused(rf_args a) 
     auto issue = [&](long long it) {
       const long long p0 = (img_t0 + it - (long long)b * a.tiles_per_image) * 128 + wave * 32;      // first pixel (inside image b)
       const long long rows_left = a.P - p0;                              // may be <= 0: everything out of range
-      const float* base = a.x + ((long long)b * a.P + (rows_left > 0 ? p0 : 0)) * a.ldx;
+      // (MAP: image b lies where x_map says; the descriptor still ends with this image's last pixel)
+      long long img = 0;
+      if constexpr (MAP) img = im_offset(a.x_map, b);
+      const float* base = MAP ? a.x + img + (rows_left > 0 ? p0 : 0) * a.ldx
+                              : a.x + ((long long)b * a.P + (rows_left > 0 ? p0 : 0)) * a.ldx;
       const long long bytes = rows_left > 0 ? (rows_left < 32 ? rows_left : 32) * (long long)a.ldx * 4 : 0;
       const i32x4 rsrc = lds_dma_rsrc_uniform(base, (unsigned)bytes);      // lanes beyond the image read zeros
       if (PLANE)                 // the tile's taps, ahead of its item: in order behind it, so landed when it has (plane_chunk.h)
@@ -916,7 +927,9 @@ extern "C" int cdfo_rdab_prep_rng_dev(const float* xq, int ldx, const float* vma
 static int rdab_prep_fused_launch(const float* x, int ldx, const float* w_packed, const float* bias, const float* vmax,
                                   const float* noise, long long seed, const void* seed_dev, int draw, float* noise_out,
                                   const float* wW, const float* bW, int B, long long P, float* sq, int lds_, void* vrow, int ldv,
-                                  float* qwin, int ldw, void* vwin, int ldvw, int v_f16, const pc_plane* plane, void* stream) {
+                                  float* qwin, int ldw, void* vwin, int ldvw, int v_f16, const pc_plane* plane, void* stream,
+                                  const im_map* xm = nullptr) {
+  if (xm && (!plane || !im_map_ok(*xm))) return CDFO_EINVAL;      // the mapped form exists beside the plane chunk only
   if (B <= 0 || P <= 0 || P % 64 || P >= (1ll << 32) || ldx < 64 || ldx % 4 || (long long)ldx * 4 * 32 >= (1ll << 31) || lds_ % 4 ||
       ldw % 4 || ldv % 8 || ldvw % 8 || !x || !w_packed || !vmax || !wW || !bW)
     return CDFO_EINVAL;
@@ -925,7 +938,8 @@ static int rdab_prep_fused_launch(const float* x, int ldx, const float* w_packed
       (reinterpret_cast<uintptr_t>(seed_dev) & 7u))
     return CDFO_EALIGN;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  rf_args s{};
+  rf_args_map sm{};
+  rf_args& s = sm;
   s.x = x; s.ldx = ldx; s.w = w_packed; s.bias = bias; s.vmax = vmax; s.noise = noise; s.wW = wW; s.bW = bW;
   s.P = P; s.ns = 3;
   s.sq = sq; s.lds_ = lds_; s.qwin = qwin; s.ldw = ldw; s.vrow = vrow; s.ldv = ldv; s.vwin = vwin; s.ldvw = ldvw;
@@ -939,8 +953,22 @@ static int rdab_prep_fused_launch(const float* x, int ldx, const float* w_packed
   // (the plane chunk: one k-step of 16 and 4 bytes per pixel more)
   CdfoProfScope prof(st, KID_RDAB_PREP, 2.0 * px * 128 * (plane ? 80 : 64),
                      px * (4.0 * (64 + 128 + (noise ? 64 : 0) + (plane ? 1 : 0)) + ((v_f16 & 1) ? 2.0 : 4.0) * 64 + ((v_f16 & 2) ? 2.0 : 4.0) * 64));
-  static CdfoAttrOnce once[8], once_pl[8];
+  static CdfoAttrOnce once[8], once_pl[8], once_map[8];
   typedef _Float16 h;
+  if (xm) {
+    s.plane = *plane;
+    sm.x_map = *xm;
+    switch ((noise ? 0 : 4) + v_f16) {
+      case 0: return st_launch(rdab_prep_kernel_fused<false, float, float, true, true>, once_map[0], grid, lds, st, sm);
+      case 1: return st_launch(rdab_prep_kernel_fused<false, h, float, true, true>, once_map[1], grid, lds, st, sm);
+      case 2: return st_launch(rdab_prep_kernel_fused<false, float, h, true, true>, once_map[2], grid, lds, st, sm);
+      case 3: return st_launch(rdab_prep_kernel_fused<false, h, h, true, true>, once_map[3], grid, lds, st, sm);
+      case 4: return st_launch(rdab_prep_kernel_fused<true, float, float, true, true>, once_map[4], grid, lds, st, sm);
+      case 5: return st_launch(rdab_prep_kernel_fused<true, h, float, true, true>, once_map[5], grid, lds, st, sm);
+      case 6: return st_launch(rdab_prep_kernel_fused<true, float, h, true, true>, once_map[6], grid, lds, st, sm);
+      default: return st_launch(rdab_prep_kernel_fused<true, h, h, true, true>, once_map[7], grid, lds, st, sm);
+    }
+  }
   if (plane) {
     s.plane = *plane;
     switch ((noise ? 0 : 4) + v_f16) {
@@ -1070,4 +1098,20 @@ extern "C" int cdfo_rdab_prep_fused_plane(const float* x, int ldx, const float* 
   const pc_plane pl = {plane, plane_Bi, plane_sb, plane_sg, W, plane_w, 0};
   return rdab_prep_fused_launch(x, ldx, w_packed, bias, vmax, noise, seed, seed_dev, draw, noise_out, wW, bW, B, P, sq, lds_, vrow, ldv,
                                 qwin, ldw, vwin, ldvw, v_f16, &pl, stream);
+}
+
+// cdfo_rdab_prep_fused_plane with x read through an image map: image b of x starts at x + (b % x_Bi) x_sb + (b / x_Bi) x_sg floats
+// (image_map.h).  Same results bit for bit as on the dense copy of those images.
+extern "C" int cdfo_rdab_prep_fused_plane_map(const float* x, int ldx, int x_Bi, long long x_sb, long long x_sg, const float* w_packed,
+                                              const float* bias, const float* vmax, const float* noise, long long seed,
+                                              const void* seed_dev, int draw, float* noise_out, const float* wW, const float* bW, int B,
+                                              long long P, float* sq, int lds_, void* vrow, int ldv, float* qwin, int ldw, void* vwin,
+                                              int ldvw, int v_f16, const float* plane, int plane_Bi, long long plane_sb,
+                                              long long plane_sg, int W, const float* plane_w, void* stream) {
+  if (!plane || !plane_w || plane_Bi <= 0 || plane_sb < 0 || plane_sg < 0 || !pc_shape_ok(P, W)) return CDFO_EINVAL;
+  if (!aligned16(plane_w)) return CDFO_EALIGN;
+  const pc_plane pl = {plane, plane_Bi, plane_sb, plane_sg, W, plane_w, 0};
+  const im_map xm = {x_Bi, x_sb, x_sg};
+  return rdab_prep_fused_launch(x, ldx, w_packed, bias, vmax, noise, seed, seed_dev, draw, noise_out, wW, bW, B, P, sq, lds_, vrow, ldv,
+                                qwin, ldw, vwin, ldvw, v_f16, &pl, stream, &xm);
 }

@@ -13,6 +13,8 @@
 // CVSR_V8 path (qkv, project_out folded, input_conv, fuse, fusion_out, down.0 / up.0, tsa_fusion, upconv1/2).
 #include "numeric.h"
 #include "plane_chunk.h"      // pc_plane: the optional plane operand, streaming form only
+#include "image_map.h"
+#include <type_traits>
 
 namespace {
 
@@ -34,14 +36,21 @@ __device__ __forceinline__ void split_store(unsigned char* dst_hi, int lo_delta,
   *reinterpret_cast<u32x2*>(dst_hi + lo_delta) = lo;
 }
 
+// MAP form: where the images of every source lie (image_map.h).  A block of its own that only the MAP instantiation takes: the other
+// forms' kernel arguments, and with them their instructions, stay what they were
+struct c1_args_map : cdfo_conv_args {
+  im_map src_map[CDFO_MAXSRC];
+};
+
 // NCB: number of 64-wide output-channel blocks (1..4).
 // TAPS (CDFO_STORE_TAPS9, upconv2 of arch.py:4474-4476 only): instead of the pixel-shuffled 64-channel HR feature map,
 // store for every HR pixel the nine per-tap channel sums t_k = sum_c w_last[c][k] * act(y)[c] of the 3x3 conv_last that
 // follows: 36 bytes per HR pixel instead of 256 (the 4.3 GB HR map is never written nor read back).  The sums are a second
 // matrix product in the epilogue (round 2; as sixteen-lane DPP reductions they were 1 150 vector instructions per lane and
 // output block and made the launch 2.06 ms long).
-template <int NCB, bool TAPS = false>
-__global__ __launch_bounds__(256, 2) void conv1x1_bf16x3_kernel(cdfo_conv_args a) {
+// MAP: the sources' images lie where c1_args_map.src_map says (residuals and the result stay dense)
+template <int NCB, bool TAPS = false, bool MAP = false>
+__global__ __launch_bounds__(256, 2) void conv1x1_bf16x3_kernel(std::conditional_t<MAP, c1_args_map, cdfo_conv_args> a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[A_BYTES + W_BYTES];
   static_assert(EPI_BYTES <= A_BYTES + W_BYTES, "the epilogue transpose reuses the staging buffers");
   unsigned char* sA = smem;
@@ -72,6 +81,9 @@ __global__ __launch_bounds__(256, 2) void conv1x1_bf16x3_kernel(cdfo_conv_args a
     while (ch0 >= s_base + a.cs[s_idx]) { s_base += a.cs[s_idx]; ++s_idx; }
     const float* src = a.src[s_idx] + (ch0 - s_base);
     const int ld = a.ld[s_idx];
+    // MAP: image b of this source starts im_offset floats behind its first image, not b P ld -- the loads below index from there,
+    // and stay inside the image (pixels beyond it are clamped to its first)
+    if constexpr (MAP) src += im_offset(a.src_map[s_idx], b) - (long long)b * P * ld;
     __syncthreads();   // previous K block's MFMAs are done with sA / sW
     // ---- stage 128 pixels x 64 channels: 8 float4 per thread, all loads first
     f32x4 v[8];
@@ -245,12 +257,12 @@ __global__ __launch_bounds__(256, 2) void conv1x1_bf16x3_kernel(cdfo_conv_args a
 }  // namespace
 
 // conv1x1_stream.hip: the persistent LDS-DMA streaming form (plain store, CoutP <= 128, weights + rings within LDS)
-int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st, const pc_plane* plane = nullptr);
+int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st, const pc_plane* plane = nullptr, const im_map* maps = nullptr);
 extern "C" int cdfo_layernorm64_cp16hl(const float* in, int ldi, const float* gamma, const float* beta, int B, long long P,
                                        void* out, void* stream);
 
-// pl != null: cdfo_conv1x1_bf16x3_plane
-static int conv1x1_bf16x3(const cdfo_conv_args* pa, const pc_plane* pl, void* stream) {
+// pl != null: cdfo_conv1x1_bf16x3_plane; maps != null: cdfo_conv1x1_bf16x3_map
+static int conv1x1_bf16x3(const cdfo_conv_args* pa, const pc_plane* pl, void* stream, const im_map* maps = nullptr) {
   const cdfo_conv_args& a = *pa;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (a.nsrc < 1 || a.nsrc > CDFO_MAXSRC || a.B <= 0 || a.ks != 1 || a.stride != 1 || a.pad != 0) return CDFO_EINVAL;
@@ -282,8 +294,31 @@ static int conv1x1_bf16x3(const cdfo_conv_args* pa, const pc_plane* pl, void* st
     // outside its contract is an error (the caller materialises the operand instead)
     if (!pl->base || !pl->w || pl->Bi <= 0 || pl->s_b < 0 || pl->s_g < 0 || taps) return CDFO_EINVAL;
     if (!aligned16(pl->w) || pl->w_bstride % 4 || (a.chan_sum_out && !aligned16(a.chan_sum_out))) return CDFO_EALIGN;
-    const int r = cdfo_conv1x1_stream_try(a, st, pl);
+    const int r = cdfo_conv1x1_stream_try(a, st, pl, maps);
     return r == 1 ? 0 : (r == 0 ? CDFO_EINVAL : r);
+  }
+  if (maps) {
+    // mapped operands: the streaming kernel where the launch is inside its contract (there also for the residuals), else the
+    // one-tile-per-workgroup kernel below for a plain 64-channel product of mapped sources.  Anything else is an error: the caller
+    // materialises the operand instead (cdfo_conv1x1_map_ok says which, without a launch)
+    if (taps || ln_out || a.ln_gamma || a.res2_pixscale || a.store_mode != CDFO_STORE_PLAIN || a.CoutP != 64) return CDFO_EINVAL;
+    if (a.chan_sum_out && (a.Cout != 64 || a.chan_sum_slots <= 0 || !aligned16(a.chan_sum_out))) return CDFO_EINVAL;
+    // (with the streaming kernel switched off the dense launch would run on another kernel: no mapped form then)
+    static const bool use_stream = cdfo_switch("CDFO_CONV1X1_STREAM", 1) != 0;
+    if (!use_stream) return CDFO_EINVAL;
+    const int r = cdfo_conv1x1_stream_try(a, st, nullptr, maps);
+    if (r == 1) return 0;
+    if (r != 0) return r;
+    if (a.chan_sum_out || maps[CDFO_MAXSRC].Bi || maps[CDFO_MAXSRC + 1].Bi) return CDFO_EINVAL;
+    c1_args_map am{};
+    static_cast<cdfo_conv_args&>(am) = a;
+    for (int i = 0; i < a.nsrc; ++i) am.src_map[i] = maps[i].Bi ? maps[i] : im_dense(a.B, P, a.ld[i]);
+    dim3 grid((unsigned)((P + PXT - 1) / PXT), a.B);
+    const double px = (double)a.B * P;
+    CdfoProfScope prof(st, KID_CONV1, 2.0 * px * a.Cout * a.Cin, 4.0 * (px * a.Cout + px * a.Cin + (double)a.Cin * a.Cout));
+    hipLaunchKernelGGL((conv1x1_bf16x3_kernel<1, false, true>), grid, dim3(256), 0, st, am);
+    CDFO_LAUNCH_CHECK();
+    return 0;
   }
   if (a.chan_sum_out) {
     // channel sums of the result: from the streaming kernel's epilogue, else (outside its contract / switched off) a pass of their own
@@ -347,4 +382,33 @@ extern "C" int cdfo_conv1x1_bf16x3_plane(const cdfo_conv_args* pa, const float* 
                                          long long plane_sg, const float* plane_w, long long plane_w_bstride, void* stream) {
   const pc_plane pl = {plane, plane_Bi, plane_sb, plane_sg, 0, plane_w, plane_w_bstride};      // (W: the argument block's)
   return conv1x1_bf16x3(pa, &pl, stream);
+}
+
+// cdfo_conv1x1_bf16x3 (plane == null) / cdfo_conv1x1_bf16x3_plane on operands read through image maps (image_map.h).  maps: CDFO_MAXSRC + 2
+// triples (Bi, s_b, s_g) -- entry i for source i, entries CDFO_MAXSRC and CDFO_MAXSRC + 1 for res1 and res2; Bi == 0: that operand is dense.  Image b of
+// a mapped operand starts at its pointer + (b % Bi) s_b + (b / Bi) s_g floats.  64-channel plain results only; same bits as on the
+// dense copies of those images.
+extern "C" int cdfo_conv1x1_bf16x3_map(const cdfo_conv_args* pa, const long long* maps, const float* plane, int plane_Bi,
+                                       long long plane_sb, long long plane_sg, const float* plane_w, long long plane_w_bstride,
+                                       void* stream) {
+  if (!pa || !maps) return CDFO_EINVAL;
+  im_map m[CDFO_MAXSRC + 2];
+  for (int i = 0; i < CDFO_MAXSRC + 2; ++i) {
+    m[i] = im_map{(int)maps[3 * i], maps[3 * i + 1], maps[3 * i + 2]};
+    if (maps[3 * i] < 0 || maps[3 * i] > 0x7fffffff || (m[i].Bi && !im_map_ok(m[i]))) return CDFO_EINVAL;
+  }
+  if (!plane) return conv1x1_bf16x3(pa, nullptr, stream, m);
+  const pc_plane pl = {plane, plane_Bi, plane_sb, plane_sg, 0, plane_w, plane_w_bstride};
+  return conv1x1_bf16x3(pa, &pl, stream, m);
+}
+
+// Whether cdfo_conv1x1_bf16x3_map takes a launch of this form (pure host arithmetic): Cin input channels in 64-channel sources, 64 output
+// channels; with_plane / with_res / with_csum: a plane operand, a mapped residual or the channel sums, which only the streaming kernel has
+extern "C" int cdfo_conv1x1_map_ok(int Cin, int with_plane, int with_res, int with_csum) {
+  if (Cin <= 0 || Cin % 64 || Cin / 64 > CDFO_MAXSRC * 4) return 0;
+  if (!with_plane && cdfo_switch("CDFO_CONV1X1_STREAM", 1) == 0) return 0;
+  const int w_bytes = st_weight_bytes(Cin / 64, 1);      // the ring stages left beside the weights, as cdfo_conv1x1_stream_try counts them
+  const int ns = with_plane ? (ST_MAX_LDS - w_bytes - pc_weight_bytes(1)) / (4 * (ST_STAGE + PC_SLOT)) : (ST_MAX_LDS - w_bytes) / (4 * ST_STAGE);
+  const bool stream_fits = ns >= 3;
+  return stream_fits || !(with_plane || with_res || with_csum) ? 1 : 0;
 }

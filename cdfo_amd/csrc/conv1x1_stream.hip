@@ -22,6 +22,8 @@
 // Contract: cdfo_conv_args as cdfo_conv1x1_bf16x3 with plain store, Cin % 64 == 0 per source, Cout % 8 == 0,
 // CoutP in {64, 128}, weights + ring within the CU's LDS (Cin * CoutP <= 192 * 64); everything else stays on that kernel.
 #include "plane_chunk.h"
+#include "image_map.h"
+#include <type_traits>
 
 namespace {
 
@@ -55,6 +57,11 @@ struct st_args {
   // (plane.w: [CoutP][16] per image, the product's weights for that operand composed with the stencil); plane.base == nullptr: absent
   pc_plane plane;
 };
+// MAP form: where the images of every item lie (image_map.h); act_map[k] belongs to act[k], res_map[i] to res[i].  A block of its own
+// that only the MAP instantiations take: the other forms' kernel arguments, and with them their instructions, stay what they were
+struct st_args_map : st_args {
+  im_map act_map[CDFO_MAXSRC * 4], res_map[2];
+};
 
 // The persistent kernels here cut the stream of `tiles` 128-pixel tiles into `grid` contiguous ranges [tiles w / grid, tiles (w + 1) /
 // grid).  st_owner: the workgroup whose range holds tile t.  A workgroup's partial sums over its tiles of image b go to slot
@@ -74,9 +81,11 @@ inline int st_slots(int B, int tiles_per_image, int grid) {
 // NCB: 64-wide output-channel blocks (1, 2; 4 in the TAPS form)
 // CSUM (NCB == 1): also the channel sums of the result, see st_args.csum
 // PLANE: the plane chunk of st_args.plane joins the product (a template parameter: the other forms' instructions stay what they were)
-template <int NCB, bool TAPS = false, bool CSUM = false, bool PLANE = false>
-__global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
+// MAP: the items' images lie where st_args.act_map / res_map say (a template parameter for the same reason)
+template <int NCB, bool TAPS = false, bool CSUM = false, bool PLANE = false, bool MAP = false>
+__global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(std::conditional_t<MAP, st_args_map, st_args> a) {
   static_assert(!(PLANE && TAPS), "the TAPS form takes no plane chunk");
+  static_assert(!(MAP && TAPS), "the TAPS form takes no image map");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -178,15 +187,19 @@ __global__ __launch_bounds__(ST_THREADS) void conv1x1_stream_kernel(st_args a) {
         pc_issue(pc_image(a.plane, b), (int)a.P, a.plane.W, (int)p0, lane, tap_lds + (unsigned)((it / items_per_tile) % NS) * PC_SLOT);
       st_item src;
       int chan0;
-      if (k < nkb) { src = a.act[k]; chan0 = src.ch0; }
+      long long img = 0;         // MAP: floats from the item's first image to image b -- the one place an item's image is located
+      if (k < nkb) { src = a.act[k]; chan0 = src.ch0; if constexpr (MAP) img = im_offset(a.act_map[k], b); }
       else {                     // residual operands are packed from slot 0 by the host wrapper
         const int j = k - nkb;
         src = a.res[j / NCB];
         chan0 = (j % NCB) * 64;
+        if constexpr (MAP) img = im_offset(a.res_map[j / NCB], b);
       }
       // descriptor based at the wave's first pixel: offsets stay small whatever the tensor's size
       const long long rows_left = a.P - p0;                               // may be <= 0: everything out of range
-      const float* base = src.base + ((long long)b * a.P + (rows_left > 0 ? p0 : 0)) * src.ld + chan0;
+      // (MAP: the descriptor below still ends with this image's last pixel, so no lane reads a neighbouring slot of a stack)
+      const float* base = MAP ? src.base + img + (rows_left > 0 ? p0 : 0) * src.ld + chan0
+                              : src.base + ((long long)b * a.P + (rows_left > 0 ? p0 : 0)) * src.ld + chan0;
       i32x4 rsrc = lds_dma_rsrc_uniform(base, 0u);
       const long long bytes = rows_left > 0 ? (rows_left < 32 ? rows_left : 32) * (long long)src.ld * 4 : 0;
       lds_dma_rsrc_resize_uniform(rsrc, (unsigned)bytes);                 // lanes beyond the image read zeros
@@ -461,11 +474,15 @@ struct sg_args {
   // of a segment into sum1
   pc_plane plane; const float* stencil;
 };
+// MAP form: where the images of q lie (image_map.h); x0 and x1 stay dense.  A block of its own, as st_args_map
+struct sg_args_map : sg_args {
+  im_map q_map;
+};
 
 constexpr int SG_NS = 3;
 
-template <int CH, bool PLANE = false>
-__global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args a) {
+template <int CH, bool PLANE = false, bool MAP = false>
+__global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(std::conditional_t<MAP, sg_args_map, sg_args> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NS = SG_NS, NKB = PLANE ? 1 : 2, IPT = NKB + 1, GS = CH + 2;
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r = lane & 31;
@@ -530,7 +547,11 @@ __global__ __launch_bounds__(ST_THREADS) void align_gram_partial_kernel(sg_args 
       if (PLANE && it % IPT == 0)      // the tile's taps, ahead of its first item (plane_chunk.h; the slot rules with ipt = 2)
         pc_issue(pc_image(a.plane, b), (int)a.P, a.plane.W, (int)p0, lane, tap_lds + (unsigned)((it / IPT) % NS) * PC_SLOT);
       const long long rows_left = a.P - p0;                               // may be <= 0: everything out of range
+      // (MAP: q, the tile's last item, lies where q_map says; the descriptor still ends with this image's last pixel)
       const float* base = src.base + ((long long)b * a.P + (rows_left > 0 ? p0 : 0)) * src.ld + src.ch0;
+      if constexpr (MAP) {
+        if (it % IPT == IPT - 1) base = src.base + im_offset(a.q_map, b) + (rows_left > 0 ? p0 : 0) * src.ld + src.ch0;
+      }
       i32x4 rsrc = lds_dma_rsrc_uniform(base, 0u);
       const long long bytes = rows_left > 0 ? (rows_left < 32 ? rows_left : 32) * (long long)src.ld * 4 : 0;
       lds_dma_rsrc_resize_uniform(rsrc, (unsigned)bytes);                 // lanes beyond the image read zeros
@@ -739,7 +760,8 @@ extern "C" int cdfo_align_stats_slots(int B, long long P) {
 // pl != null: cdfo_align_stats_plane (x1 is the plane's stencil: x1 == null, ld1 unused)
 static int align_stats(const float* x0, int ld0, const float* x1, int ld1, const float* q, int ldq, const float* w_packed, const float* bias,
                        int act, int ch_per_head, int B, long long P, int nslots, float* gram_partial, float* sum0_partial,
-                       float* sum1_partial, const pc_plane* pl, const float* stencil, void* stream) {
+                       float* sum1_partial, const pc_plane* pl, const float* stencil, const im_map* qm, void* stream) {
+  if (qm && !im_map_ok(*qm)) return CDFO_EINVAL;
   if (B <= 0 || P <= 0 || nslots <= 0 || !x0 || (!x1 && !pl) || !q || !w_packed || !gram_partial || !sum0_partial || !sum1_partial) return CDFO_EINVAL;
   if (act != CDFO_ACT_NONE && act != CDFO_ACT_LRELU && act != CDFO_ACT_RELU) return CDFO_EINVAL;
   if (ch_per_head != 8 && ch_per_head != 16) return CDFO_EINVAL;
@@ -756,13 +778,15 @@ static int align_stats(const float* x0, int ld0, const float* x1, int ld1, const
     if ((unsigned long long)pl->base % 4 || !aligned16(pl->w) || !aligned16(stencil)) return CDFO_EALIGN;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  sg_args s{};
+  sg_args_map sm{};
+  sg_args& s = sm;
   s.src[0] = {x0, ld0, 0};
   if (pl) { s.src[1] = {q, ldq, 0}; s.plane = *pl; s.stencil = stencil; }
   else { s.src[1] = {x1, ld1, 0}; s.src[2] = {q, ldq, 0}; }
   s.w = w_packed; s.bias = bias; s.act_fn = act;
   s.P = P;
   s.gram = gram_partial; s.sum0 = sum0_partial; s.sum1 = sum1_partial; s.slots = nslots;
+  if (qm) sm.q_map = *qm;
   int grid;
   if (!st_tiling(B, P, s.tiles_per_image, s.tiles, grid)) return CDFO_EINVAL;
   if (nslots < st_slots(B, s.tiles_per_image, grid)) return CDFO_EINVAL;
@@ -772,13 +796,19 @@ static int align_stats(const float* x0, int ld0, const float* x1, int ld1, const
     static_assert(st_lds_bytes(1, 1, SG_NS) + pc_lds_bytes(1, SG_NS) <= ST_MAX_LDS, "the PLANE form's LDS (128256 bytes)");
     // (the plane chunk: one k-step of 16 instead of a K block of 64, 4 bytes per pixel instead of 256)
     CdfoProfScope prof(st, KID_GRAM, px * (2.0 * 80 * 64 + 2.0 * 64 * 18), 4.0 * 129 * px);
-    static CdfoAttrOnce once8p, once16p;
+    static CdfoAttrOnce once8p, once16p, once8pm, once16pm;
+    if (qm)
+      return ch_per_head == 16 ? st_launch(align_gram_partial_kernel<16, true, true>, once16pm, grid, lds, st, sm)
+                               : st_launch(align_gram_partial_kernel<8, true, true>, once8pm, grid, lds, st, sm);
     return ch_per_head == 16 ? st_launch(align_gram_partial_kernel<16, true>, once16p, grid, lds, st, s)
                              : st_launch(align_gram_partial_kernel<8, true>, once8p, grid, lds, st, s);
   }
   const int lds = st_lds_bytes(2, 1, SG_NS);
   CdfoProfScope prof(st, KID_GRAM, px * (2.0 * 128 * 64 + 2.0 * 64 * 18), 4.0 * 192 * px);
-  static CdfoAttrOnce once8, once16;
+  static CdfoAttrOnce once8, once16, once8m, once16m;
+  if (qm)
+    return ch_per_head == 16 ? st_launch(align_gram_partial_kernel<16, false, true>, once16m, grid, lds, st, sm)
+                             : st_launch(align_gram_partial_kernel<8, false, true>, once8m, grid, lds, st, sm);
   return ch_per_head == 16 ? st_launch(align_gram_partial_kernel<16>, once16, grid, lds, st, s)
                            : st_launch(align_gram_partial_kernel<8>, once8, grid, lds, st, s);
 }
@@ -788,7 +818,7 @@ extern "C" int cdfo_align_stats(const float* x0, int ld0, const float* x1, int l
                                 float* sum0_partial, float* sum1_partial, void* stream) {
   if (!x1) return CDFO_EINVAL;
   return align_stats(x0, ld0, x1, ld1, q, ldq, w_packed, bias, act, ch_per_head, B, P, nslots, gram_partial, sum0_partial, sum1_partial,
-                     nullptr, nullptr, stream);
+                     nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int cdfo_align_stats_plane(const float* x0, int ld0, const float* q, int ldq, const float* w_packed, const float* bias, int act,
@@ -797,16 +827,36 @@ extern "C" int cdfo_align_stats_plane(const float* x0, int ld0, const float* q, 
                                       int W, const float* plane_w, const float* stencil_w, void* stream) {
   const pc_plane pl = {plane, plane_Bi, plane_sb, plane_sg, W, plane_w, 0};
   return align_stats(x0, ld0, nullptr, 0, q, ldq, w_packed, bias, act, ch_per_head, B, P, nslots, gram_partial, sum0_partial, sum1_partial,
-                     &pl, stencil_w, stream);
+                     &pl, stencil_w, nullptr, stream);
+}
+
+// cdfo_align_stats (plane == null: x1 in memory) / cdfo_align_stats_plane with q read through an image map: image b of q starts at
+// q + (b % q_Bi) q_sb + (b / q_Bi) q_sg floats (image_map.h).  Same results bit for bit as on the dense copy of those images.
+extern "C" int cdfo_align_stats_map(const float* x0, int ld0, const float* x1, int ld1, const float* q, int ldq, int q_Bi, long long q_sb,
+                                    long long q_sg, const float* w_packed, const float* bias, int act, int ch_per_head, int B, long long P,
+                                    int nslots, float* gram_partial, float* sum0_partial, float* sum1_partial, const float* plane,
+                                    int plane_Bi, long long plane_sb, long long plane_sg, int W, const float* plane_w,
+                                    const float* stencil_w, void* stream) {
+  const im_map qm = {q_Bi, q_sb, q_sg};
+  if (!plane) {
+    if (!x1) return CDFO_EINVAL;
+    return align_stats(x0, ld0, x1, ld1, q, ldq, w_packed, bias, act, ch_per_head, B, P, nslots, gram_partial, sum0_partial, sum1_partial,
+                       nullptr, nullptr, &qm, stream);
+  }
+  const pc_plane pl = {plane, plane_Bi, plane_sb, plane_sg, W, plane_w, 0};
+  return align_stats(x0, ld0, nullptr, 0, q, ldq, w_packed, bias, act, ch_per_head, B, P, nslots, gram_partial, sum0_partial, sum1_partial,
+                     &pl, stencil_w, &qm, stream);
 }
 
 // Returns 1 when the streaming kernel took the launch, 0 when the shapes are outside its contract (the caller falls back to
 // cdfo_conv1x1_bf16x3), < 0 / hipError_t on errors.  Same argument block as cdfo_conv1x1_bf16x3.
 // plane != null: the PLANE form, or 0
-int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st, const pc_plane* pl) {
+// maps != null: the MAP form -- maps[i] locates the images of source i (i < nsrc), maps[CDFO_MAXSRC] / [CDFO_MAXSRC + 1] those of res1 /
+// res2; Bi == 0: that operand is dense.  64 output channels, no second output, no scaled residual; or 0
+int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st, const pc_plane* pl, const im_map* maps) {
   const bool ln_out = a.out2_cp16 != nullptr;      // post-LayerNorm hi | lo second output (checked by the caller: Cout == 64)
   const bool taps = a.store_mode == CDFO_STORE_TAPS9;
-  if (taps && pl) return 0;
+  if (taps && (pl || maps)) return 0;
   if (taps) {
     // upconv2 + conv_last's tap sums (checked by the caller: Cout = CoutP = 256, res2 = conv_last.weight [64][9], no res1)
     if (a.Cin != 64 || a.nsrc != 1 || a.ldo % 4 || a.ldo < 12 || a.ln_gamma || ln_out || (long long)a.ld[0] * 4 * 32 >= (1ll << 31)) return 0;
@@ -831,6 +881,7 @@ int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st, const pc_pl
   // the plane chunk: 64 output channels, no second output, no scaled residual (its LDS lies where the factors' slots would)
   if (plane && (a.CoutP != 64 || ln_out || a.res2_pixscale || !pc_shape_ok((long long)a.H * a.W, a.W))) return 0;
   if (ln_out && (a.CoutP != 64 || a.Cout != 64)) return 0;
+  if (maps && (a.CoutP != 64 || ln_out || a.res2_pixscale)) return 0;
   if (a.chan_sum_out && (a.CoutP != 64 || a.Cout != 64 || ln_out || a.chan_sum_slots <= 0)) return 0;   // the caller sums in a pass of its own
   const int ncb = a.CoutP / 64, nkb = a.Cin / 64;
   if (nkb < 1 || nkb > CDFO_MAXSRC * 4) return 0;
@@ -846,19 +897,34 @@ int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st, const pc_pl
   }
   if (ns < 3) return 0;
   const long long P = (long long)a.H * a.W;
-  st_args s{};
+  st_args_map sm{};
+  st_args& s = sm;
   int k = 0;
   for (int i = 0; i < a.nsrc; ++i) {
     if ((long long)a.ld[i] * 4 * 32 >= (1ll << 31)) return 0;
-    for (int c = 0; c < a.cs[i]; c += 64) { s.act[k].base = a.src[i]; s.act[k].ld = a.ld[i]; s.act[k].ch0 = c; ++k; }
+    for (int c = 0; c < a.cs[i]; c += 64) {
+      s.act[k].base = a.src[i]; s.act[k].ld = a.ld[i]; s.act[k].ch0 = c;
+      if (maps) sm.act_map[k] = maps[i].Bi ? maps[i] : im_dense(a.B, P, a.ld[i]);
+      ++k;
+    }
   }
   if (k != nkb) return 0;
   s.nkb = nkb;
   // residual operands are staged 64 channels at a time: they must be at least NCB*64 channels wide in memory terms only
   // where Cout needs it (a narrower tensor would be read past its pitch): require ld >= CoutP
   int nr = 0;
-  if (a.res1) { if (a.ldr1 < a.CoutP) return 0; s.res[nr].base = a.res1; s.res[nr].ld = a.ldr1; ++nr; }
-  if (a.res2) { if (a.ldr2 < a.CoutP) return 0; s.res[nr].base = a.res2; s.res[nr].ld = a.ldr2; ++nr; }
+  if (a.res1) {
+    if (a.ldr1 < a.CoutP) return 0;
+    s.res[nr].base = a.res1; s.res[nr].ld = a.ldr1;
+    if (maps) sm.res_map[nr] = maps[CDFO_MAXSRC].Bi ? maps[CDFO_MAXSRC] : im_dense(a.B, P, a.ldr1);
+    ++nr;
+  }
+  if (a.res2) {
+    if (a.ldr2 < a.CoutP) return 0;
+    s.res[nr].base = a.res2; s.res[nr].ld = a.ldr2;
+    if (maps) sm.res_map[nr] = maps[CDFO_MAXSRC + 1].Bi ? maps[CDFO_MAXSRC + 1] : im_dense(a.B, P, a.ldr2);
+    ++nr;
+  }
   s.res_scale = a.res2 ? a.res2_pixscale : nullptr;
   s.w = a.w; s.w_bstride = a.w_bstride; s.bias = a.bias;
   s.Cin = a.Cin; s.Cout = a.Cout; s.CoutP = a.CoutP; s.act_fn = a.act;
@@ -878,7 +944,14 @@ int cdfo_conv1x1_stream_try(const cdfo_conv_args& a, hipStream_t st, const pc_pl
     if (a.chan_sum_slots < st_slots(a.B, s.tiles_per_image, grid)) return 0;
     s.csum = a.chan_sum_out; s.csum_slots = a.chan_sum_slots;
   }
-  static CdfoAttrOnce once_csum, once1, once2, once_pl, once_pl_csum;
+  static CdfoAttrOnce once_csum, once1, once2, once_pl, once_pl_csum, once_map[4];
+  if (maps) {
+    const int e = plane ? (a.chan_sum_out ? st_launch(conv1x1_stream_kernel<1, false, true, true, true>, once_map[3], grid, lds, st, sm)
+                                          : st_launch(conv1x1_stream_kernel<1, false, false, true, true>, once_map[2], grid, lds, st, sm))
+                        : (a.chan_sum_out ? st_launch(conv1x1_stream_kernel<1, false, true, false, true>, once_map[1], grid, lds, st, sm)
+                                          : st_launch(conv1x1_stream_kernel<1, false, false, false, true>, once_map[0], grid, lds, st, sm));
+    return e == 0 ? 1 : e;
+  }
   if (plane) {
     const int e = a.chan_sum_out ? st_launch(conv1x1_stream_kernel<1, false, true, true>, once_pl_csum, grid, lds, st, s)
                                  : st_launch(conv1x1_stream_kernel<1, false, false, true>, once_pl, grid, lds, st, s);

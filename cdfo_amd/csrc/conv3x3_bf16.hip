@@ -31,6 +31,8 @@
 // full HBM time unless another workgroup's MFMAs cover them.
 #include "common.h"
 #include "conv_epilogue.h"
+#include "image_map.h"
+#include <type_traits>
 
 constexpr int PIXB_F32SRC = 80;   // LDS bytes per staged pixel when converting from fp32: 32 B hi | 32 B lo | 16 B pad
 
@@ -145,8 +147,15 @@ __device__ __forceinline__ void offmask_finish(const cdfo_conv_args& a, const Of
 // 4 = skip the per-chunk convert + LDS writes, 8 = skip the epilogue (store one value), 16 = skip the barriers
 // NT: 32-channel output tiles per workgroup (2 = 64 output channels; 1 for convolutions with <= 32 output channels, e.g.
 // UDSA's 64 -> 16: half the MFMAs and half the weight-fragment reads of the padded 64-wide tile)
-template <int MODE, int WAVES_PER_SIMD, int DBG, int NT = 2>
-__global__ __launch_bounds__(256, WAVES_PER_SIMD) void conv3x3_mma16_kernel(cdfo_conv_args a) {
+// MAP: the images of source 0 lie where c3_args_map.src0_map says (image_map.h); the other sources, the residuals and the result stay
+// dense.  c3_args_map is a block of its own that only the MAP instantiations take: the other forms' kernel arguments, and with them
+// their instructions, stay what they were
+struct c3_args_map : cdfo_conv_args {
+  im_map src0_map;
+};
+
+template <int MODE, int WAVES_PER_SIMD, int DBG, int NT = 2, bool MAP = false>
+__global__ __launch_bounds__(256, WAVES_PER_SIMD) void conv3x3_mma16_kernel(std::conditional_t<MAP, c3_args_map, cdfo_conv_args> a) {
   using F = Fmt<MODE>;
   using frag_t = typename F::frag;
   constexpr bool F16 = MODE == M_FP16X2 || MODE == M_FP16IN || MODE == M_FP16X1;
@@ -224,6 +233,9 @@ __global__ __launch_bounds__(256, WAVES_PER_SIMD) void conv3x3_mma16_kernel(cdfo
       }
     } else {
       const float* src = a.src[s_idx] + (ch0 - s_base);
+      // MAP: image b of source 0 starts im_offset floats behind its first image, not b H W ld (a_pix counts from the dense stack's
+      // start); only pixels inside image b are loaded
+      if constexpr (MAP) { if (s_idx == 0) src += im_offset(a.src0_map, b) - (long long)b * a.H * a.W * ld; }
 #pragma unroll
       for (int s = 0; s < NA; ++s) {
         const int q = (tid + 256 * s) & 3;
@@ -409,9 +421,16 @@ __global__ void pack16_kernel(const float* __restrict__ w, unsigned short* __res
 
 }  // namespace
 
-extern "C" int cdfo_conv3x3_bf16(const cdfo_conv_args* pa, void* stream) {
+// m0 != null: cdfo_conv3x3_bf16_map
+static int conv3x3_bf16(const cdfo_conv_args* pa, const im_map* m0, void* stream) {
   const cdfo_conv_args& a = *pa;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (m0) {      // the forms that read pixel-major fp32 sources into 64 output channels, plain store
+    const int pr = a.prec & 255;
+    if (!im_map_ok(*m0) || (a.prec >> 8) || (pr != CDFO_PREC_BF16X3 && pr != CDFO_PREC_FP16X2) || a.src_f16 || a.Cout <= 32 ||
+        a.store_mode != CDFO_STORE_PLAIN)
+      return CDFO_EINVAL;
+  }
   if (a.nsrc < 1 || a.nsrc > CDFO_MAXSRC || a.B <= 0 || a.ks != 3 || a.stride != 1 || a.pad != 1) return CDFO_EINVAL;
   if (a.act == CDFO_ACT_SIGMOID) return CDFO_EINVAL;   // conv epilogues support none / LeakyReLU / ReLU
   if (a.out2_cp16 || a.res_up2 || a.src_plane_wrap || a.res2_pixscale || a.chan_sum_out) return CDFO_EINVAL;
@@ -443,6 +462,15 @@ extern "C" int cdfo_conv3x3_bf16(const cdfo_conv_args* pa, void* stream) {
   CdfoProfScope prof(st, KID_CONV3_WIDE, 2.0 * px * a.Cout * a.Cin * 9,
                      4.0 * (px * a.Cout + px * a.Cin + 9.0 * a.Cin * a.Cout));
   const int dbg = a.prec >> 8, prec = a.prec & 255;
+  if (m0) {
+    c3_args_map am{};
+    static_cast<cdfo_conv_args&>(am) = a;
+    am.src0_map = *m0;
+    if (prec == CDFO_PREC_BF16X3) hipLaunchKernelGGL((conv3x3_mma16_kernel<M_BF16X3, 2, 0, 2, true>), grid, dim3(256), 0, st, am);
+    else hipLaunchKernelGGL((conv3x3_mma16_kernel<M_FP16X2, 2, 0, 2, true>), grid, dim3(256), 0, st, am);
+    CDFO_LAUNCH_CHECK();
+    return 0;
+  }
   if (dbg) {   // developer ablations of the split-bf16 kernel: developer builds only
 #ifdef CDFO_DEV_ABLATIONS
     if (prec != CDFO_PREC_BF16X3) return CDFO_EINVAL;
@@ -475,6 +503,15 @@ extern "C" int cdfo_conv3x3_bf16(const cdfo_conv_args* pa, void* stream) {
   }
   CDFO_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int cdfo_conv3x3_bf16(const cdfo_conv_args* pa, void* stream) { return conv3x3_bf16(pa, nullptr, stream); }
+
+// cdfo_conv3x3_bf16 (split-bf16 or split-fp16, 64-wide plain result) with source 0 read through an image map: its image b starts at
+// src[0] + (b % s0_Bi) s0_sb + (b / s0_Bi) s0_sg floats (image_map.h).  Same results bit for bit as on the dense copy of those images.
+extern "C" int cdfo_conv3x3_bf16_map(const cdfo_conv_args* pa, int s0_Bi, long long s0_sb, long long s0_sg, void* stream) {
+  const im_map m = {s0_Bi, s0_sb, s0_sg};
+  return conv3x3_bf16(pa, &m, stream);
 }
 
 static int pack16_launch(const float* w, void* packed, int Cout, int Cin, bool f16, void* stream) {

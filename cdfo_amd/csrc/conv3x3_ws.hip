@@ -28,6 +28,8 @@
 // DMA completion is tracked by hand (hipcc does not count inline-asm memory operations) with counted s_waitcnt; the
 // rules are written next to each wait.
 #include "lds_dma.h"
+#include "image_map.h"
+#include <type_traits>
 
 namespace {
 
@@ -60,14 +62,22 @@ struct ws_args {
   float* om_offset; float* om_mask; const float* om_flow; long long om_flow_bstride; float om_mag; int om_accumulate; int om_cout;
 };
 
+// MAP form of the residual kernel: where the images of res2 lie (image_map.h).  A block of its own that only the MAP instantiation
+// takes: the other forms' kernel arguments, and with them their instructions, stay what they were
+struct ws_args_map : ws_args {
+  im_map res2_map;
+};
+
 // DBG (developer ablations): 1 = skip the MFMAs, 2 = skip the DMA, 8 = skip the epilogue, 64 = no start-up stagger,
 // 128 = clock probe
 // RES: residual form -- fp32 pixel-major output with one or two fp32 residual inputs (ResidualBlock_noBN's second
 // convolution, arch.py:261-262), optionally also the fp16 chunk-planar copy.  The residual values of a tile are fetched
 // by inline-asm loads while its last chunk computes (hipcc would wait for a visible load with vmcnt(0) and so drain the
 // DMA that is in flight behind it) and consumed behind a counted wait.
-template <int DBG, bool RES = false, int NW = 8>
-__global__ __launch_bounds__(NW * 64) void conv3x3_c64_ws_kernel(ws_args a) {
+// MAP (RES form): res2's images lie where ws_args_map.res2_map says
+template <int DBG, bool RES = false, int NW = 8, bool MAP = false>
+__global__ __launch_bounds__(NW * 64) void conv3x3_c64_ws_kernel(std::conditional_t<MAP, ws_args_map, ws_args> a) {
+  static_assert(!MAP || RES, "only the residual form takes an image map");
   constexpr int WS_THREADS = NW * 64, NBUF = WsLds<NW>::NBUF, WS_CNT_OFF = WsLds<NW>::CNT_OFF;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r = lane & 31;
@@ -296,6 +306,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_c64_ws_kernel(ws_args a) {
             if (!xok) continue;
             if (a.res2) {
               const float* p2 = a.res2 + pix * a.ldr2 + n;
+              if constexpr (MAP) p2 = a.res2 + im_offset(a.res2_map, cb) + ((long long)y * W + x) * a.ldr2 + n;
               v0 += *reinterpret_cast<const f32x4*>(p2);
               v1 += *reinterpret_cast<const f32x4*>(p2 + 4);
             }
@@ -897,10 +908,12 @@ extern "C" int cdfo_conv3x3_c64_ws_offmask(const void* src_cp16, int B, int H, i
   return 0;
 }
 
-extern "C" int cdfo_conv3x3_c64_ws_res(const void* src_cp16, int B, int H, int W, const void* w_f16, int CoutP,
-                                       const float* bias, int Cout, int act, float* out, int ldo, const float* res1,
-                                       int ldr1, const float* res2, int ldr2, void* out2_cp16, void* stream) {
+// r2m != null: cdfo_conv3x3_c64_ws_res_map
+static int conv3x3_c64_ws_res(const void* src_cp16, int B, int H, int W, const void* w_f16, int CoutP,
+                              const float* bias, int Cout, int act, float* out, int ldo, const float* res1,
+                              int ldr1, const float* res2, int ldr2, void* out2_cp16, const im_map* r2m, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (r2m && (!res2 || !im_map_ok(*r2m))) return CDFO_EINVAL;
   if (B <= 0 || H <= 0 || W <= 0 || (H & 1) || Cout <= 0 || Cout % 64 || CoutP < Cout || CoutP % 64) return CDFO_EINVAL;
   if (act == CDFO_ACT_SIGMOID || !out || !res1 || ldo % 4 || ldo < Cout || ldr1 % 4 || ldr1 < Cout) return CDFO_EINVAL;
   if (res2 && (ldr2 % 4 || ldr2 < Cout)) return CDFO_EINVAL;
@@ -914,7 +927,8 @@ extern "C" int cdfo_conv3x3_c64_ws_res(const void* src_cp16, int B, int H, int W
   const int nco = Cout / 64;
   int qn = (cus / 8) / nco;
   if (qn < 1) qn = 1;
-  ws_args a;
+  ws_args_map am{};
+  ws_args& a = am;
   a.src = src_cp16; a.src_bytes = (unsigned)src_bytes;
   a.B = B; a.H = H; a.W = W;
   a.w = static_cast<const unsigned short*>(w_f16); a.CoutP = CoutP;
@@ -924,10 +938,35 @@ extern "C" int cdfo_conv3x3_c64_ws_res(const void* src_cp16, int B, int H, int W
   a.clk = nullptr;
   const double px = (double)B * H * W;
   CdfoProfScope prof(st, KID_CONV3_WS_RES, 2.0 * px * Cout * 64 * 9, px * (2.0 * 64 + 8.0 * Cout + (res2 ? 4.0 * Cout : 0.0)));
+  if (r2m) {
+    am.res2_map = *r2m;
+    static CdfoAttrOnce once_map;
+    const hipError_t e = cdfo_set_max_lds(once_map, reinterpret_cast<const void*>(conv3x3_c64_ws_kernel<0, true, 8, true>), WsLds<8>::TOTAL);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((conv3x3_c64_ws_kernel<0, true, 8, true>), dim3(8 * qn * nco), dim3(8 * 64), WsLds<8>::TOTAL, st, am);
+    CDFO_LAUNCH_CHECK();
+    return 0;
+  }
   const int rc = ws_launch<0, true>(a, 8 * qn * nco, st);
   if (rc) return rc;
   CDFO_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int cdfo_conv3x3_c64_ws_res(const void* src_cp16, int B, int H, int W, const void* w_f16, int CoutP,
+                                       const float* bias, int Cout, int act, float* out, int ldo, const float* res1,
+                                       int ldr1, const float* res2, int ldr2, void* out2_cp16, void* stream) {
+  return conv3x3_c64_ws_res(src_cp16, B, H, W, w_f16, CoutP, bias, Cout, act, out, ldo, res1, ldr1, res2, ldr2, out2_cp16, nullptr, stream);
+}
+
+// cdfo_conv3x3_c64_ws_res with res2 read through an image map: image b of res2 starts at res2 + (b % r2_Bi) r2_sb + (b / r2_Bi) r2_sg
+// floats (image_map.h).  Same results bit for bit as on the dense copy of those images.
+extern "C" int cdfo_conv3x3_c64_ws_res_map(const void* src_cp16, int B, int H, int W, const void* w_f16, int CoutP,
+                                           const float* bias, int Cout, int act, float* out, int ldo, const float* res1,
+                                           int ldr1, const float* res2, int ldr2, int r2_Bi, long long r2_sb, long long r2_sg,
+                                           void* out2_cp16, void* stream) {
+  const im_map m = {r2_Bi, r2_sb, r2_sg};
+  return conv3x3_c64_ws_res(src_cp16, B, H, W, w_f16, CoutP, bias, Cout, act, out, ldo, res1, ldr1, res2, ldr2, out2_cp16, &m, stream);
 }
 
 extern "C" int cdfo_to_cp16(const float* in, int ldi, int B, long long P, int C, void* out_cp16, void* stream) {

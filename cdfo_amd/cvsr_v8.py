@@ -133,6 +133,26 @@ def _register(root: nn.Module, key: str, param: nn.Parameter):
 
 
 # ------------------------------------------------------------------------------------------------ the module
+class _FeatureStack:
+    """The frames' features of B clips where they lie: frame i of clip b starts i * s_f + b * s_c floats behind T's first element
+    (clip-major L1 [B*7,H,W,64]: s_f = P 64, s_c = 7 P 64; a frame-major window stack [7,B,H,W,64]: s_f = B P 64, s_c = P 64).  The
+    neighbour phase takes its operands from it as image maps (K.image_map): nothing is copied."""
+
+    def __init__(self, T, B, H, W, s_f, s_c):
+        self.T, self.B, self.H, self.W, self.s_f, self.s_c = T, B, H, W, s_f, s_c
+
+    def _first(self, i):
+        return self.T.as_strided((self.H, self.W, NF), (self.W * NF, NF, 1), self.T.storage_offset() + i * self.s_f)
+
+    def group(self, i0, G):
+        """Frames i0 .. i0 + G - 1 of every clip, neighbour major: [G*B,H,W,64]."""
+        return K.image_map(self._first(i0), G * self.B, self.B, self.s_c, self.s_f)
+
+    def frame(self, i, times=1):
+        """Frame i of every clip, addressed `times` times over: [times*B,H,W,64]."""
+        return K.image_map(self._first(i), times * self.B, self.B, self.s_c, 0)
+
+
 class CVSR_V8(nn.Module):
     def __init__(self, nf=64, nframes=7, fea_ext_RBs=7, SCGs=4, istraining=False):
         super().__init__()
@@ -168,6 +188,10 @@ class CVSR_V8(nn.Module):
         # folded 192 -> 64 convolution) take it as the plane chunk of their products from the partition map (see _align_group, _align;
         # developer A/B: CDFO_INLINE_UFS=0 -> one stem launch per neighbour writes ufs_prior).  Needs align_stats
         self.inline_ufs = switches.get("CDFO_INLINE_UFS")
+        # ... and the neighbour phase reads the feature stack where the extractor wrote it: no frame-major copy, no centre features
+        # repeated per neighbour -- its seven readers take an image map (see _stack_inplace; developer A/B: CDFO_STACK_INPLACE=0 ->
+        # K.swap_outer and the repeat of the rounds before)
+        self.stack_inplace = switches.get("CDFO_STACK_INPLACE")
         self.neighbour_group = 0      # frames per neighbour group: 0 = auto = 3
         # cached-feature call on one sequence (B = 1): the group of frames 0-2 (cached features only) starts beside the new
         # frame's feature extraction instead of behind it (see _forward)
@@ -467,9 +491,12 @@ class CVSR_V8(nn.Module):
                     off = (g * B % Bi) * s_b + (g * B // Bi) * s_g
                     first = view.as_strided((1,), (1,), view.storage_offset() + off)      # (no copy: an address in the storage)
                     plane = (first, B, s_b, 0, w["rms_chunk_input_conv"])
-                K.rdab_prep_fused(x[sl], w["RDAB.input_conv"], vmax[sl], noise, wW, bW, v_f16=(False, am == 20),
+                xs = x.sub(sl.start, B) if isinstance(x, K.ImageMap) else x[sl]      # (a mapped stack: this noise's images as a map of their own)
+                K.rdab_prep_fused(xs, w["RDAB.input_conv"], vmax[sl], noise, wW, bW, v_f16=(False, am == 20),
                                   outs=(sq[sl], vrow[sl], qwin[sl], vwin[sl]), plane=plane)
         else:
+            if isinstance(x, K.ImageMap):
+                raise ValueError("_rdab: a mapped x needs the fused mask kernel (_stack_inplace decides before the first launch)")
             vdt = torch.float32
             xq = self._conv(x, w["RDAB.input_conv"])
             vwin = xq[..., 64:128]
@@ -1015,12 +1042,44 @@ class CVSR_V8(nn.Module):
                 deferred_new = new_frame_features
             else:
                 new_frame_features()
-        Lf = (K.swap_outer(L1, B, N) if B > 1 else L1).view(N, B, H, W, NF)   # frame-major views for the loop
+        if self._stack_inplace(w, B, H, W):
+            Lf = _FeatureStack(L1, B, H, W, P * NF, N * P * NF)                # the stack as it lies: clip-major
+        else:
+            Lf = (K.swap_outer(L1, B, N) if B > 1 else L1).view(N, B, H, W, NF)   # frame-major views for the loop
         return self._fuse_windows(w, Lf, x, mvs1, rms, ufs, gumbel_uniform, deferred_new), L1, x
 
+    def _stack_inplace(self, w, B, H, W) -> bool:
+        """The one predicate of the in-place neighbour phase, evaluated before its first launch; it decides for the whole forward.  True:
+        the seven readers of the feature stack -- the mask kernel's x, RDAB.fuse's residual, source 0 of conv_expand_fea_r, the
+        alignment's statistics (q), its folded convolution (second source), the last ResidualBlock's res2, tsa_fusion's centre --
+        all take an image map at this shape in the form this forward runs them in.  Else the forward is launch for launch the one
+        without the switch.  Both give the same bits, so the choice may depend on shape and mode."""
+        if not self.stack_inplace or self.precision == "f32" or self.istraining:
+            return False
+        prec = self.PRECISIONS[self.precision]
+        a = "MV_deform_align."
+        G = int(getattr(self, "neighbour_group", 0)) or self.center
+        # the forms of the default path: the mask statistics from the residual maps and fea_com inside the products (_compensate,
+        # _inline_rms_planes), the alignment on its one-pass statistics (_align), the ResidualBlocks on the Block_ kernels (fast16)
+        rms_inline = (self.prior_stems and K.rdab_stats_ok(H, W) and self.inline_rms and "rms_chunk" in w and self.rdab_fused
+                      and K.plane_ok(H, W) and (H * W) % 64 == 0)
+        ufs_inline = self.inline_ufs and "ufs_chunk" in w and K.plane_ok(H, W)
+        fast16 = (self.precision == "fp16x2" and H % 2 == 0
+                  and all(w[a + n].wh is not None for n in ("ResidualBlock.conv1", "ResidualBlock.conv2", "ResidualBlock1.conv1", "ResidualBlock1.conv2")))
+        fea_r_prec = K.PREC_FP16X1 if self.fea_r_single_pass and prec == K.PREC_FP16X2 else prec
+        return bool(rms_inline and self.align_stats and fast16
+                    and K.rdab_prep_fused_map_ok(plane=True)
+                    and K.conv_map_ok(w["RDAB.fuse"], prec, plane=True, res=True)
+                    and K.conv_map_ok(w["conv_expand_fea_r"], fea_r_prec, pad=1)
+                    and (not ufs_inline or K.conv1x1_map_ok(128, plane=True, chan_sum=True))      # the folded convolution: with the
+                    and K.conv1x1_map_ok(192, chan_sum=True)                                    # partition map inside, or with pred
+                    and K.ws_res_map_ok(G * B, H, W)
+                    and K.conv_map_ok(w["tsa_fusion"], prec))
+
     def _fuse_windows(self, w, Lf, x, mvs1, rms, ufs, gumbel_uniform, deferred_new=None):
-        """Steps 2-3 of the forward from the frame-major feature stack Lf [7,B,H,W,64]: the six neighbour pipelines and the
-        temporal fusion.  x: only its device is read here.  gumbel_uniform: resolved by forward() -- injected tensors, or None =
+        """Steps 2-3 of the forward from the frame-major feature stack Lf [7,B,H,W,64], or from a _FeatureStack (the stack as it lies
+        in memory, read in place; a frame-major tensor is read that way too where _stack_inplace allows): the six neighbour pipelines
+        and the temporal fusion.  x: only its device is read here.  gumbel_uniform: resolved by forward() -- injected tensors, or None =
         draw inside the mask kernel.  deferred_new: `_front`'s cached path at B = 1 -- the new frame's feature extraction,
         enqueued behind the fork of the side streams.  Returns fused [B,H,W,64]."""
         N, ctr = NFRAMES, self.center
@@ -1043,18 +1102,28 @@ class CVSR_V8(nn.Module):
         groups = [list(range(s, min(s + gsz, e))) for (s0, e) in ((0, ctr), (ctr + 1, N)) for s in range(s0, e, gsz)]
         if deferred_new is not None and self.new_frame_alone:
             groups = [list(range(0, ctr)), list(range(ctr + 1, N - 1)), [N - 1]]     # the new frame is a group of its own
-        xcG = Lf[ctr].repeat(gsz, 1, 1, 1) if gsz > 1 else Lf[ctr]      # the centre features once per neighbour of a group
+        if not isinstance(Lf, _FeatureStack) and self._stack_inplace(w, Lf.shape[1], Lf.shape[2], Lf.shape[3]):
+            _, B, H, W, _ = Lf.shape
+            Lf = _FeatureStack(Lf, B, H, W, B * H * W * NF, H * W * NF)         # frame-major: the same path with its own strides
+        if isinstance(Lf, _FeatureStack):
+            xcG, centre = Lf.frame(ctr, times=gsz), Lf.frame(ctr)               # the centre of every clip, addressed once per neighbour
+        else:
+            xcG = Lf[ctr].repeat(gsz, 1, 1, 1) if gsz > 1 else Lf[ctr]      # the centre features once per neighbour of a group
+            centre = Lf[ctr]
         keep = []
         aligned = self._fork_join(x.device, nstr, groups, deferred_new, lambda gi, idxs: self._neighbour_group(
             w, Lf, idxs, xcG, ufs, rms, mvs1, gumbel_uniform, keep))
-        return self._fuse(w, Lf[ctr], aligned)
+        return self._fuse(w, centre, aligned)
 
     def _fuse_windows_shared(self, w, Lc, comp_bank, comp_idx, x, mvs1, ufs):
         """Steps 2b-3 of the forward with banked compensations: the two neighbour groups (slots 0-2 and 4-6) on the two side
         streams as in `_fuse_windows`, each aligning comp_bank[comp_idx[...]] to the centres; then the temporal fusion.  ufs:
         [K,1,7,H,W] dense.  Returns fused [K,H,W,64]."""
         B, N, ctr = x.shape[0], NFRAMES, self.center
-        xcG = Lc.repeat(ctr, 1, 1, 1)
+        if self._stack_inplace(w, B, Lc.shape[1], Lc.shape[2]):
+            xcG = K.image_map(Lc[0], ctr * B, B, Lc.stride(0), 0)             # the centres, addressed once per neighbour
+        else:
+            xcG = Lc.repeat(ctr, 1, 1, 1)
         keep = []
         aligned = self._fork_join(x.device, 2, [list(range(0, ctr)), list(range(ctr + 1, N))], None, lambda gi, idxs: self._align_group(
             w, idxs, xcG, ufs, mvs1, keep, frames=(comp_bank, comp_idx[gi * ctr * B:(gi + 1) * ctr * B])))
@@ -1064,9 +1133,10 @@ class CVSR_V8(nn.Module):
         """The neighbour groups `groups` (lists of frame indices) beside each other: ``body(gi, idxs)`` -> the group's aligned
         features [len(idxs)*B,H,W,64], neighbour major, issued under one of `nstr` side streams (on the caller's stream with
         nstr = 1).  Returns {frame index: its [B,H,W,64] slice}, complete on the caller's stream.
-        The caller has enqueued the groups' common inputs -- xcG, the centre features repeated per neighbour -- on its stream
-        BEFORE this call: the side streams read them (Gram pass and last residual of _align), so that copy must be ordered ahead
-        of their wait.  deferred_new (`_front`: the new frame's feature extraction) is enqueued on the caller's stream behind the
+        The groups' common inputs -- the feature stack, and xcG, the centre features per neighbour -- are complete on the caller's
+        stream BEFORE this call: the side streams read them (Gram pass and last residual of _align) behind their wait.  Read in place
+        (_stack_inplace) xcG is an image map of the stack and nothing is enqueued for it; else it is a copy on the caller's stream,
+        ordered ahead of the wait like the stack.  deferred_new (`_front`: the new frame's feature extraction) is enqueued on the caller's stream behind the
         fork, so the side streams do not wait for it; the group that reads the new frame then follows it on the caller's stream."""
         main = torch.cuda.current_stream(device)
         side = self._side(device, nstr) if nstr > 1 else []
@@ -1122,13 +1192,17 @@ class CVSR_V8(nn.Module):
         """Neighbour frames `idxs` (consecutive) of the frame-major stack Lf [7,B,H,W,64] together: RDAB compensation,
         conv_expand_fea_r, prior stems, MV alignment (arch.py:4443-4460) on [len(idxs)*B, H, W, 64] tensors, neighbour major.
         rms / ufs: [B,1,7,H,W] dense."""
-        N, B, H, W, _ = Lf.shape
+        if isinstance(Lf, _FeatureStack):
+            N, B, H, W = NFRAMES, Lf.B, Lf.H, Lf.W
+        else:
+            N, B, H, W, _ = Lf.shape
         G = len(idxs)
+        fea = Lf.group(idxs[0], G) if isinstance(Lf, _FeatureStack) else Lf[idxs[0]:idxs[0] + G].view(G * B, H, W, NF)
         # fea_com = fea_i + rms_prior and du0 = relu(conv_du_re.0(rms_prior)) from the residual map itself, per neighbour; a
         # neighbour's noise draw is its rank among the six
         stems = [(rms[:, 0, i], N * H * W, slice(n * B, (n + 1) * B)) for n, i in enumerate(idxs)]
         draws = [i - (i > self.center) for i in idxs]
-        fea_i, x_n = self._compensate(w, Lf[idxs[0]:idxs[0] + G].view(G * B, H, W, NF), stems, draws,
+        fea_i, x_n = self._compensate(w, fea, stems, draws,
                                       None if noise is None else [noise[d] for d in draws], keep)
         if self.debug_taps is not None:
             for n, i in enumerate(idxs):
@@ -1150,6 +1224,8 @@ class CVSR_V8(nn.Module):
             # residual maps to the pool's partial sums, and the stem only adds conv_expand_rms(rms) to the features
             stats = self._mask_stats(w, stems, M, H, W)
             planes = self._inline_rms_planes(w, fea, stems, len(draws))
+        if planes is None and isinstance(fea, K.ImageMap):
+            raise ValueError("_compensate: a mapped stack needs the inline residual planes (_stack_inplace decides before the first launch)")
         if planes is not None:
             # ... and that sum has two consumers, both matrix products over the pixel's channels: they read fea and the residual map
             fea_com = None
@@ -1253,7 +1329,7 @@ class CVSR_V8(nn.Module):
                 K.stem_conv(ufs[:, 0, i], N * P, B, H, W, raw["conv_expand_ufs.weight"], raw["conv_expand_ufs.bias"],
                             out=ufs_prior[n * B:(n + 1) * B])
         al = K.empty_act(GB, H, W, NF, xcG.device)
-        xc = xcG if xcG.shape[0] == GB else xcG[:GB]
+        xc = xcG if xcG.shape[0] == GB else (xcG.sub(0, GB) if isinstance(xcG, K.ImageMap) else xcG[:GB])
         self._align(w, xc, extra, ufs_prior, [mvs1[:, i] for i in idxs], N * 2 * P, al,
                     frames=None if frames is None else (*frames, mvs1, idxs[0]), ufs_planes=planes)
         if self.debug_taps is not None:

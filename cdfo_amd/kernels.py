@@ -34,7 +34,87 @@ def on_device(t: torch.Tensor):
     return torch.cuda.device(t.device)
 
 
+class ImageMap:
+    """M images of a pixel-major fp32 operand [M,H,W,C >= 64] that are not one dense block: image m starts
+    ``(m % Bi) * s_b + (m // Bi) * s_g`` floats behind the first one (csrc/image_map.h); inside an image nothing changes (pixel
+    pitch ld, dense pixels).  Built and validated by `image_map`; the wrappers that name a mapped operand take it where they take
+    the dense tensor [M,H,W,C] and give the same bits."""
+    __slots__ = ("first", "M", "Bi", "s_b", "s_g")
+
+    def __init__(self, first, M, Bi, s_b, s_g):
+        self.first, self.M, self.Bi, self.s_b, self.s_g = first, M, Bi, s_b, s_g
+
+    shape = property(lambda self: (self.M, *self.first.shape))
+    dtype = property(lambda self: self.first.dtype)
+    device = property(lambda self: self.first.device)
+    is_cuda = property(lambda self: self.first.is_cuda)
+    ld = property(lambda self: self.first.stride(1))
+
+    def dim(self) -> int:
+        return 4
+
+    def data_ptr(self) -> int:
+        return self.first.data_ptr()
+
+    def offset(self, m: int) -> int:
+        """Floats from the first image to image m."""
+        return (m % self.Bi) * self.s_b + (m // self.Bi) * self.s_g
+
+    def image(self, m: int) -> torch.Tensor:
+        """Image m as a view [H,W,C] of the operand's storage."""
+        f = self.first
+        return f.as_strided(f.shape, f.stride(), f.storage_offset() + self.offset(m))
+
+    def dense(self) -> torch.Tensor:
+        """The materialised copy [M,H,W,C] (tests, and the paths that take no map)."""
+        return torch.stack([self.image(m) for m in range(self.M)])
+
+    def triple(self):
+        return self.Bi, self.s_b, self.s_g
+
+    def sub(self, start: int, count: int) -> "ImageMap":
+        """Images start .. start + count - 1 as a map of their own (start must open a block of Bi images: the form stays affine)."""
+        if start % self.Bi or start < 0 or count <= 0 or start + count > self.M:
+            raise ValueError(f"ImageMap.sub({start}, {count}): the slice must start a block of {self.Bi} images inside the {self.M}")
+        f = self.first
+        return ImageMap(f.as_strided(f.shape, f.stride(), f.storage_offset() + (start // self.Bi) * self.s_g), count, self.Bi, self.s_b, self.s_g)
+
+
+def image_map(first: torch.Tensor, M: int, Bi: int, s_b: int, s_g: int) -> ImageMap:
+    """The one place an image map is built and validated.  first: the FIRST image as a view [H,W,C >= 64] (fp32, channels contiguous,
+    rows dense at its pixel pitch); image m of the M lies (m % Bi) * s_b + (m // Bi) * s_g floats behind it, all inside first's
+    storage.  Strides are non-negative multiples of 4 floats (every image stays 16-byte aligned).  The three shapes of the neighbour
+    phase over a stack whose clips lie s_c and whose frames lie s_f floats apart:
+      frames i0 .. i0 + G - 1 of every clip, neighbour major   first = frame i0 of clip 0, M = G B, Bi = B, s_b = s_c, s_g = s_f
+      one frame of every clip                                   first = that frame of clip 0, M = Bi = B, s_b = s_c, s_g = 0
+      one frame of every clip, once per neighbour of a group    the same with M = G B"""
+    if first.dtype != torch.float32 or first.dim() != 3 or first.stride(2) != 1:
+        raise ValueError(f"image_map: the first image must be an fp32 [H,W,C] view with contiguous channels, got {first.dtype} "
+                         f"{tuple(first.shape)} strides {first.stride()}")
+    H, W, Cc = first.shape
+    ld = first.stride(1)
+    if Cc < 64 or ld < Cc or ld % 4 or (H > 1 and first.stride(0) != W * ld):
+        raise ValueError(f"image_map: rows must be densely packed at a pixel pitch ld >= C >= 64, ld % 4 == 0; strides {first.stride()}")
+    M, Bi, s_b, s_g = int(M), int(Bi), int(s_b), int(s_g)
+    if M <= 0 or Bi <= 0 or s_b < 0 or s_g < 0 or s_b % 4 or s_g % 4 or first.storage_offset() % 4:
+        raise ValueError(f"image_map: M = {M}, Bi = {Bi}, s_b = {s_b}, s_g = {s_g}: positive counts and non-negative strides that are "
+                         "multiples of 4 floats expected")
+    last = max((m % Bi) * s_b + (m // Bi) * s_g for m in range(M))
+    if (first.storage_offset() + last + (H * W - 1) * ld + Cc) * 4 > first.untyped_storage().nbytes():
+        raise ValueError(f"image_map: the {M} images leave the tensor's storage")
+    return ImageMap(first, M, Bi, s_b, s_g)
+
+
+def _is_map(t) -> bool:
+    return isinstance(t, ImageMap)
+
+
 def _chk_act(t: torch.Tensor, name: str = "tensor", dtype=torch.float32):
+    if _is_map(t):      # validated by image_map; what is left is the device
+        if dtype != torch.float32:
+            raise ValueError(f"{name}: an image map describes an fp32 operand")
+        _chk_act(t.first.unsqueeze(0), name)
+        return (*t.shape, t.ld)
     if not t.is_cuda:
         raise NotImplementedError(f"{name}: the HIP path needs device tensors (no CPU fallback)")
     if t.device.index != torch.cuda.current_device():
@@ -294,8 +374,13 @@ def conv(srcs: Sequence[torch.Tensor], pc: PackedConv, *, stride: int = 1, pad: 
     res2_scale [B,H,W]: res2 enters the sum as res2 * res2_scale[pixel] (streaming 1x1 kernel only; raises elsewhere).
     ln_out = (gamma, beta) (1x1, Cout = 64, 16-bit modes): also LayerNorm64 of the RESULT as fp16 hi | lo planes
     [B,8,H,W,16] (layernorm64_hl of the returned tensor); the call then returns the pair (out, planes)."""
-    if isinstance(srcs, torch.Tensor):
+    if isinstance(srcs, (torch.Tensor, ImageMap)):
         srcs = [srcs]
+    if any(_is_map(t) for t in (*srcs, res1, res2)):
+        if ln is not None or s2d or out_f16 or ln_out is not None or res2_scale is not None or cp16_out:
+            raise ValueError("conv: a mapped operand needs a plain fp32 64-channel result (no LayerNorm, no second output)")
+        return _conv_mapped(srcs, pc, stride=stride, pad=pad, act=act, res1=res1, res2=res2, out=out, prec=prec,
+                            chan_sum_out=chan_sum_out, plane=plane)
     if chan_sum_out:
         if cp16_out or ln_out is not None or out_f16 or s2d or pc.shuffle2 or pc.Cout != 64:
             raise ValueError("conv: chan_sum_out needs a plain fp32 64-channel result")
@@ -368,6 +453,60 @@ def conv(srcs: Sequence[torch.Tensor], pc: PackedConv, *, stride: int = 1, pad: 
     if cp16_out:
         return out, to_cp16(out)
     return out
+
+
+def conv_map_ok(pc: PackedConv, prec: int, *, pad: int = 0, plane: bool = False, res: bool = False, chan_sum: bool = False,
+                src0_only: bool = True) -> bool:
+    """Whether conv() takes image maps for this convolution: a 1x1 with a 64-channel result on the split-bf16 kernels (plane: with a
+    plane operand; res: a residual is mapped; chan_sum: with chan_sum_out -- those three need the streaming kernel, which holds up to
+    192 input channels), or the tiled 3x3 kernel in split-bf16 / split-fp16 with only source 0 mapped."""
+    if prec == PREC_F32 or pc.shuffle2:
+        return False
+    if pc.ks == 1 and pad == 0:
+        return pc.CoutP == 64 and pc.Cout % 8 == 0 and conv1x1_map_ok(pc.Cin, plane=plane, res=res, chan_sum=chan_sum)
+    return (pc.ks == 3 and pad == 1 and prec in (PREC_BF16X3, PREC_FP16X2) and pc.wq is not None and pc.w_bstride == 0 and pc.Cout > 32
+            and src0_only and not (plane or res or chan_sum))
+
+
+def conv1x1_map_ok(Cin: int, *, plane: bool = False, res: bool = False, chan_sum: bool = False) -> bool:
+    """cdfo_conv1x1_map_ok: whether the mapped 1x1 entry point takes Cin input channels -> 64 with these features (host arithmetic)."""
+    return Cin % 64 == 0 and bool(_lib.lib().cdfo_conv1x1_map_ok(Cin, int(plane), int(res), int(chan_sum)))
+
+
+def _conv_mapped(srcs, pc: PackedConv, *, stride, pad, act, res1, res2, out, prec, chan_sum_out, plane):
+    """conv() where a source or a residual is an ImageMap (see conv_map_ok)."""
+    smap, rmap = [_is_map(s) for s in srcs], [_is_map(res1), _is_map(res2)]
+    if stride != 1 or not conv_map_ok(pc, prec, pad=pad, plane=plane is not None, res=any(rmap), chan_sum=chan_sum_out,
+                                      src0_only=not any(smap[1:])):
+        raise ValueError("conv: no kernel of this convolution takes these operands through an image map (conv_map_ok)")
+    a, out = _conv_args(srcs, pc, stride=1, pad=pad, act=act, out=out)
+    B, Ho, Wo = a.B, a.Ho, a.Wo
+    _bind_res(res1, res2, B, Ho, Wo, pc.Cout, a)
+    if pc.ks == 3:
+        a.prec = prec
+        a.CoutP = pc.CoutP16
+        a.w = (pc.wh if prec == PREC_FP16X2 else pc.wq).data_ptr()
+        a.tap_mask = _vp(pc.tap_mask)
+        Bi, s_b, s_g = srcs[0].triple()
+        check(_lib.lib().cdfo_conv3x3_bf16_map(C.byref(a), Bi, C.c_longlong(s_b), C.c_longlong(s_g), _stream()), "cdfo_conv3x3_bf16_map")
+        return out
+    if any(s.shape[3] % 64 for s in srcs):
+        raise ValueError("conv: the mapped 1x1 kernels need 64-channel sources")
+    maps = (C.c_longlong * (3 * (len(a.src) + 2)))()
+    for i, t in (*enumerate(srcs), (len(a.src), res1), (len(a.src) + 1, res2)):
+        if _is_map(t):
+            maps[3 * i:3 * i + 3] = t.triple()
+    pl = (None, 0, 0, 0, None, 0)
+    if plane is not None:
+        pl = _plane_args(plane, B, a.H, a.W, 64, "conv")
+    part = n = None
+    if chan_sum_out:
+        n = align_stats_slots(B, Ho * Wo)
+        part = torch.zeros((B, n, 64), dtype=torch.float32, device=out.device)
+        a.chan_sum_out, a.chan_sum_slots = part.data_ptr(), n
+    check(_lib.lib().cdfo_conv1x1_bf16x3_map(C.byref(a), maps, _vp(pl[0]), pl[1], C.c_longlong(pl[2]), C.c_longlong(pl[3]), _vp(pl[4]),
+                                             C.c_longlong(pl[5]), _stream()), "cdfo_conv1x1_bf16x3_map")
+    return (out, part, n) if chan_sum_out else out
 
 
 @contextlib.contextmanager
@@ -526,7 +665,7 @@ def conv3x3_ws_res(src: torch.Tensor, pc: PackedConv, *, res1: torch.Tensor, res
                    act: int = ACT_NONE, out: Optional[torch.Tensor] = None,
                    out2_cp16: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Residual form of conv3x3_ws: fp32 pixel-major act(conv + bias) + res1 (+ res2); optionally also the fp16
-    chunk-planar copy of the result (out2_cp16 [B,Cout/16,H,W,16])."""
+    chunk-planar copy of the result (out2_cp16 [B,Cout/16,H,W,16]).  res2 may be an ImageMap (one launch: ws_res_map_ok)."""
     B, _, H, W = _chk_cp16(src, "conv3x3_ws_res")
     if pc.wh is None or pc.Cin != 64 or pc.ks != 3 or pc.Cout % 64:
         raise ValueError("conv3x3_ws_res: needs a 3x3 weight with 64 input channels and Cout % 64 == 0")
@@ -537,12 +676,25 @@ def conv3x3_ws_res(src: torch.Tensor, pc: PackedConv, *, res1: torch.Tensor, res
     if out2_cp16 is not None and (out2_cp16.dtype != torch.float16 or not out2_cp16.is_contiguous()
                                   or tuple(out2_cp16.shape) != (B, pc.Cout // 16, H, W, 16)):
         raise ValueError("conv3x3_ws_res: out2_cp16 must be a contiguous fp16 [B,Cout/16,H,W,16] tensor")
+    if _is_map(res2):
+        if not ws_res_map_ok(B, H, W):
+            raise ValueError("conv3x3_ws_res: a mapped res2 needs a batch that one launch takes (ws_res_map_ok)")
+        Bi, s_b, s_g = res2.triple()
+        check(_lib.lib().cdfo_conv3x3_c64_ws_res_map(
+            _vp(src), B, H, W, _vp(pc.wh), pc.CoutP16, _vp(pc.bias), pc.Cout, act, _vp(out), ldo, _vp(res1), lds[0], _vp(res2), lds[1],
+            Bi, C.c_longlong(s_b), C.c_longlong(s_g), _vp(out2_cp16), _stream()), "cdfo_conv3x3_c64_ws_res_map")
+        return out
     for sl in _batch_slices(B, H, W, "conv3x3_ws_res"):
         check(_lib.lib().cdfo_conv3x3_c64_ws_res(
             _vp(src[sl]), sl.stop - sl.start, H, W, _vp(pc.wh), pc.CoutP16, _vp(pc.bias), pc.Cout, act, _vp(out[sl]), ldo,
             _vp(res1[sl]), lds[0], _vp(None if res2 is None else res2[sl]), lds[1],
             _vp(None if out2_cp16 is None else out2_cp16[sl]), _stream()), "cdfo_conv3x3_c64_ws_res")
     return out
+
+
+def ws_res_map_ok(B: int, H: int, W: int) -> bool:
+    """conv3x3_ws_res takes a mapped res2 where the batch is one launch (the map counts images from the launch's first)."""
+    return 4 * H * W * 32 < (1 << 31) and len(list(_batch_slices(B, H, W, "conv3x3_ws_res"))) == 1
 
 
 def from_cp16(t: torch.Tensor) -> torch.Tensor:
@@ -1597,7 +1749,7 @@ def align_stats(x0: torch.Tensor, x1: Optional[torch.Tensor], q: torch.Tensor, p
     chan_sum_partial(x0)[0], chan_sum_partial(x1)[0] with n partial slots each (fixed-order sums: run-to-run identical).
     plane = (view, Bi, s_b, s_g, table, stencil) with x1 = None: x1 is the 3x3 stencil `stencil` (pack_plane_chunk of it) of the
     one-channel planes `view` addresses (see _plane_args) and is never materialised; table: pack_plane_chunk of pc's second half
-    composed with the stencil (compose_stem_1x1).  sum1 is then formed from the planes' tap sums."""
+    composed with the stencil (compose_stem_1x1).  sum1 is then formed from the planes' tap sums.  q may be an ImageMap."""
     if (x1 is None) != (plane is not None):
         raise ValueError("align_stats: either x1 or the plane it is a stencil of")
     B, H, W, c0, ld0 = _chk_act(x0, "x0")
@@ -1613,12 +1765,21 @@ def align_stats(x0: torch.Tensor, x1: Optional[torch.Tensor], q: torch.Tensor, p
     gram = buf[:B * n * gs].view(B, n, gs)
     s0 = buf[B * n * gs:B * n * (gs + 64)].view(B, n, 64)
     s1 = buf[B * n * (gs + 64):].view(B, n, 64)
+    view, Bi, s_b, s_g, table, stencil = None, 0, 0, 0, None, None
     if plane is not None:
         view, Bi, s_b, s_g, table, _ = _plane_args(plane[:5], B, H, W, 64, "align_stats")
         stencil = plane[5]
         if (tuple(stencil.shape) != (64, 16) or stencil.dtype != torch.float32 or not stencil.is_contiguous()
                 or stencil.device != table.device or table.dim() != 2):
             raise ValueError("align_stats: the stencil's table and the composed table must be fp32 [64,16] (pack_plane_chunk)")
+    if _is_map(q):
+        qB, qsb, qsg = q.triple()
+        check(_lib.lib().cdfo_align_stats_map(_vp(x0), ld0, _vp(x1), ld1, _vp(q), ldq, qB, C.c_longlong(qsb), C.c_longlong(qsg), _vp(pc.w),
+                                              _vp(pc.bias), act, ch_per_head, B, C.c_longlong(H * W), n, _vp(gram), _vp(s0), _vp(s1),
+                                              _vp(view), Bi, C.c_longlong(s_b), C.c_longlong(s_g), W, _vp(table), _vp(stencil), _stream()),
+              "cdfo_align_stats_map")
+        return gram, s0, s1, n
+    if plane is not None:
         check(_lib.lib().cdfo_align_stats_plane(_vp(x0), ld0, _vp(q), ldq, _vp(pc.w), _vp(pc.bias), act, ch_per_head, B,
                                                 C.c_longlong(H * W), n, _vp(gram), _vp(s0), _vp(s1), _vp(view), Bi, C.c_longlong(s_b),
                                                 C.c_longlong(s_g), W, _vp(table), _vp(stencil), _stream()), "cdfo_align_stats_plane")
@@ -1736,6 +1897,11 @@ def rdab_prep_fused_ok(x: torch.Tensor, pc: PackedConv) -> bool:
             and pc.Cout == 128 and pc.CoutP == 128 and pc.w_bstride == 0 and not pc.shuffle2)
 
 
+def rdab_prep_fused_map_ok(plane: bool) -> bool:
+    """rdab_prep_fused takes a mapped x in its plane form only (the form of the default path)."""
+    return bool(plane)
+
+
 def rdab_prep_fused(x: torch.Tensor, pc: PackedConv, vmax: torch.Tensor, noise, wW: torch.Tensor, bW: torch.Tensor,
                     v_f16: bool = False, outs=None, plane=None):
     """plane = (view, Bi, s_b, s_g, table): the convolution runs on x + stencil9(plane) with only x in memory (see conv's `plane`;
@@ -1744,7 +1910,8 @@ def rdab_prep_fused(x: torch.Tensor, pc: PackedConv, vmax: torch.Tensor, noise, 
     is never written.  noise: the injected fp32 [B,64,H,W] draws, or ("rng", seed, draw, noise_out) as rdab_prep_rng takes them.
     Returns (sq, vrow, qwin, vwin) -- vwin = the v half of the product, which the two-kernel path reads from xq[..., 64:].
     v_f16 (a bool for both, or a pair (vrow, vwin)): that output as fp16, each value rounded once (what seq_attn's modes 20-22 do
-    to an fp32 V while staging).  outs: the four [B,H,W,64] result tensors, dense, of those dtypes."""
+    to an fp32 V while staging).  outs: the four [B,H,W,64] result tensors, dense, of those dtypes.  x may be an ImageMap
+    (beside a plane: rdab_prep_fused_map_ok)."""
     B, H, W, Cc, ld = _chk_act(x, "x")
     if not rdab_prep_fused_ok(x, pc):
         raise ValueError("rdab_prep_fused: a 64 -> 128 1x1 convolution over H*W % 64 == 0 pixels expected (use conv + rdab_prep)")
@@ -1775,7 +1942,15 @@ def rdab_prep_fused(x: torch.Tensor, pc: PackedConv, vmax: torch.Tensor, noise, 
     args = (_vp(x), ld, _vp(pc.w), _vp(pc.bias), _vp(vmax), _vp(noise_in), C.c_longlong(seed), _vp(seed_dev), draw, _vp(noise_out),
             _vp(wW), _vp(bW), B, C.c_longlong(H * W), _vp(sq), 64, _vp(vrow), 64, _vp(qwin), 64, _vp(vwin), 64,
             int(row16) + 2 * int(win16))
-    if plane is not None:
+    if _is_map(x):
+        if plane is None:
+            raise ValueError("rdab_prep_fused: a mapped x needs the plane form (rdab_prep_fused_map_ok)")
+        view, Bi, s_b, s_g, table, _ = _plane_args(plane[:5], B, H, W, 128, "rdab_prep_fused")
+        xB, xsb, xsg = x.triple()
+        check(_lib.lib().cdfo_rdab_prep_fused_plane_map(args[0], ld, xB, C.c_longlong(xsb), C.c_longlong(xsg), *args[2:], _vp(view), Bi,
+                                                        C.c_longlong(s_b), C.c_longlong(s_g), W, _vp(table), _stream()),
+              "cdfo_rdab_prep_fused_plane_map")
+    elif plane is not None:
         view, Bi, s_b, s_g, table, _ = _plane_args(plane[:5], B, H, W, 128, "rdab_prep_fused")
         check(_lib.lib().cdfo_rdab_prep_fused_plane(*args, _vp(view), Bi, C.c_longlong(s_b), C.c_longlong(s_g), W, _vp(table), _stream()),
               "cdfo_rdab_prep_fused_plane")

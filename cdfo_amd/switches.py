@@ -58,6 +58,7 @@ TABLE = (
     Switch("CDFO_PRIOR_STEMS", 1, ONOFF, "python", "0: LLongRangAttention's mask statistics through memory: du0 written by the stem kernel, read back by conv_du_re.2, its result summed by a third launch (model.prior_stems)"),
     Switch("CDFO_INLINE_RMS", 1, ONOFF, "python", "0: fea_com = fea + conv_expand_rms(rms) written by the stem kernel and read by the mask kernel and RDAB.fuse, instead of built inside their products from the residual map; needs CDFO_PRIOR_STEMS (model.inline_rms)"),
     Switch("CDFO_INLINE_UFS", 1, ONOFF, "python", "0: ufs_prior = conv_expand_ufs(ufs) written by one stem launch per neighbour and read by DualAttAlignment's statistics pass and its folded 192 -> 64 convolution, instead of built inside their products from the partition map; needs CDFO_ALIGN_STATS (model.inline_ufs)"),
+    Switch("CDFO_STACK_INPLACE", 1, ONOFF, "python", "0: the neighbour phase reads a frame-major copy of the feature stack (K.swap_outer) and the centre features repeated per neighbour, instead of the stack where the extractor wrote it through image maps in its seven readers (model.stack_inplace)"),
     # --- HIP layer (csrc/) --------------------------------------------------------------------------------------------------
     Switch("CDFO_WS_RING", 1, ONOFF, "hip", "0: Block_.body[0] on the private-halo kernel of rounds 1-2 instead of the ring-fed wave-specialised one"),
     Switch("CDFO_WS_WAVES", 12, INT, "hip", "8: two instead of three waves per SIMD in the private-halo weights-stationary kernel", (8, 12)),

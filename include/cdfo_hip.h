@@ -104,6 +104,13 @@ int cdfo_pack_conv_weight(const float* w_oihw, float* packed, int Cout, int Cin,
  * CDFO_PREC_FP16X1 (fp32 source rounded once to fp16 while staging, fp16 weights, one pass: used for the convolutions
  * INSIDE Block_, where the oracle emulation shows the forward's error is set by the weight rounding alone).  */
 int cdfo_conv3x3_bf16(const cdfo_conv_args* a, void* stream);
+/* Image maps (csrc/image_map.h): a pixel-major fp32 operand [M][P][ld >= 64] whose images are not one dense block is described by its
+ * first image's pointer and (Bi, s_b, s_g): image m starts at pointer + (m % Bi) s_b + (m / Bi) s_g floats (Bi > 0, strides >= 0 and
+ * multiples of 4); inside an image nothing changes.  The *_map entry points read ONE named operand that way and give the bits their
+ * dense forms give on the dense copy of those images; a launch outside a mapped form's contract is CDFO_EINVAL.
+ * cdfo_conv3x3_bf16_map: cdfo_conv3x3_bf16 (a->prec = CDFO_PREC_BF16X3 or CDFO_PREC_FP16X2, fp32 sources, Cout > 32, plain store) with
+ * source 0 mapped.  */
+int cdfo_conv3x3_bf16_map(const cdfo_conv_args* a, int s0_Bi, long long s0_sb, long long s0_sg, void* stream);
 int cdfo_pack_conv3x3_bf16(const float* w_oihw, void* packed, int Cout, int Cin, void* stream);
 int cdfo_pack_conv3x3_f16(const float* w_oihw, void* packed, int Cout, int Cin, void* stream);
 
@@ -158,6 +165,10 @@ int cdfo_conv3x3_c64_ws_offmask(const void* src_cp16, int B, int H, int W, const
 int cdfo_conv3x3_c64_ws_res(const void* src_cp16, int B, int H, int W, const void* w_f16, int CoutP, const float* bias,
                             int Cout, int act, float* out, int ldo, const float* res1, int ldr1, const float* res2,
                             int ldr2, void* out2_cp16, void* stream);
+/* The same with res2 (required) read through an image map (see cdfo_conv3x3_bf16_map).  */
+int cdfo_conv3x3_c64_ws_res_map(const void* src_cp16, int B, int H, int W, const void* w_f16, int CoutP, const float* bias,
+                                int Cout, int act, float* out, int ldo, const float* res1, int ldr1, const float* res2,
+                                int ldr2, int r2_Bi, long long r2_sb, long long r2_sg, void* out2_cp16, void* stream);
 /* 3x3 / stride 1 / pad 1 convolution of an fp16 chunk-planar source (a->src[0] = [B][Cin/16][H][W][16], a->src_f16 = 1,
  * a->ld[0] = 16, a->cs[0] = Cin) as a persistent kernel fed by an LDS-DMA ring: Block_.body[2] (256 -> 64) and the
  * composed stride-2 convolution of Block_'s double-resolution branch.  a->w: fp16 [Cin/16][taps][2][CoutP][8] with
@@ -183,6 +194,15 @@ int cdfo_conv1x1_bf16x3(const cdfo_conv_args* a, void* stream);
  * constant 1, built in registers) before bias and activation; a->chan_sum_out works as without it.  */
 int cdfo_conv1x1_bf16x3_plane(const cdfo_conv_args* a, const float* plane, int plane_Bi, long long plane_sb, long long plane_sg,
                               const float* plane_w, long long plane_w_bstride, void* stream);
+/* cdfo_conv1x1_bf16x3 (plane == NULL) / cdfo_conv1x1_bf16x3_plane with operands read through image maps (see cdfo_conv3x3_bf16_map).
+ * maps: CDFO_MAXSRC + 2 triples (Bi, s_b, s_g): entry i for source i, entries CDFO_MAXSRC and CDFO_MAXSRC + 1 for res1 and res2;
+ * Bi == 0: that operand is dense.  Plain store, CoutP = 64, no out2_cp16, no LayerNorm, no res2_pixscale.  The streaming kernel takes
+ * every such launch inside its own contract; outside it (Cin > 192) only mapped SOURCES of a product without plane, channel sums or
+ * mapped residuals are taken.  cdfo_conv1x1_map_ok: 1 when a launch of Cin input channels with / without a plane operand, a mapped
+ * residual, channel sums is taken (host arithmetic, no launch), else 0.  */
+int cdfo_conv1x1_bf16x3_map(const cdfo_conv_args* a, const long long* maps, const float* plane, int plane_Bi, long long plane_sb,
+                            long long plane_sg, const float* plane_w, long long plane_w_bstride, void* stream);
+int cdfo_conv1x1_map_ok(int Cin, int with_plane, int with_res, int with_csum);
 
 /* Upsampler tail without the HR feature map (arch.py:4474-4480).  cdfo_conv1x1_bf16x3 with a->store_mode =
  * CDFO_STORE_TAPS9 (upconv2: Cout = 256, pixel-shuffle weight packing, LeakyReLU; a->res2 = conv_last.weight
@@ -296,6 +316,12 @@ int cdfo_align_stats_plane(const float* x0, int ld0, const float* q, int ldq, co
                            int ch_per_head, int B, long long P, int nslots, float* gram_partial, float* sum0_partial,
                            float* sum1_partial, const float* plane, int plane_Bi, long long plane_sb, long long plane_sg, int W,
                            const float* plane_w, const float* stencil_w, void* stream);
+/* cdfo_align_stats (plane == NULL) / cdfo_align_stats_plane (x1 == NULL, ld1 unused) with q read through an image map (see
+ * cdfo_conv3x3_bf16_map).  */
+int cdfo_align_stats_map(const float* x0, int ld0, const float* x1, int ld1, const float* q, int ldq, int q_Bi, long long q_sb,
+                         long long q_sg, const float* w_packed, const float* bias, int act, int ch_per_head, int B, long long P,
+                         int nslots, float* gram_partial, float* sum0_partial, float* sum1_partial, const float* plane, int plane_Bi,
+                         long long plane_sb, long long plane_sg, int W, const float* plane_w, const float* stencil_w, void* stream);
 /* MDTA (arch.py:1555-1575): wout[b] = packed 1x1 weights (64->64) = project_out x blockdiag(softmax(...)). */
 int cdfo_mdta_fold(const float* partial, int nchunk, const float* temperature, const float* proj_w, int B, float* wout,
                    void* stream);
@@ -352,6 +378,13 @@ int cdfo_rdab_prep_fused_plane(const float* x, int ldx, const float* w_packed, c
                                const float* wW, const float* bW, int B, long long P, float* sq, int lds_, void* vrow, int ldv,
                                float* qwin, int ldw, void* vwin, int ldvw, int v_f16, const float* plane, int plane_Bi,
                                long long plane_sb, long long plane_sg, int W, const float* plane_w, void* stream);
+/* cdfo_rdab_prep_fused_plane with x read through an image map (see cdfo_conv3x3_bf16_map).  */
+int cdfo_rdab_prep_fused_plane_map(const float* x, int ldx, int x_Bi, long long x_sb, long long x_sg, const float* w_packed,
+                                   const float* bias, const float* vmax, const float* noise, long long seed, const void* seed_dev,
+                                   int draw, float* noise_out, const float* wW, const float* bW, int B, long long P, float* sq,
+                                   int lds_, void* vrow, int ldv, float* qwin, int ldw, void* vwin, int ldvw, int v_f16,
+                                   const float* plane, int plane_Bi, long long plane_sb, long long plane_sg, int W,
+                                   const float* plane_w, void* stream);
 int cdfo_colconv9(const float* in, int ldi, const float* wH, const float* bH, int B, int H, int W, float* out, int ldo,
                   void* stream);
 /* Evaluation metrics on the device (metric/psnr_ssim.py:278-317 calculate_psnr, :320-399 _ssim / calculate_ssim): fp64
