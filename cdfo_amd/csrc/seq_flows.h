@@ -2,6 +2,7 @@
 // chunk + 6 frames).  A frame descriptor whose range check returns zero outside the frame, the loads of a motion field's twelve
 // values, and the per-pixel body of cdfo_seq_flows / cdfo_seq_flows_ring: test_LD_22_FPS.py's mv2mvs (:100-122) and
 // modify_mv_for_end_frames (:200-225), bit for bit.
+// seq_flows_ra_pixels is the same body for the random-access field (both lists, seq_flows_ra.hip).
 #pragma once
 #include "lds_dma.h"
 
@@ -77,6 +78,67 @@ __device__ __forceinline__ void seq_flows_pixels(const T* __restrict__ field, in
     }
   }
   // modify_mv_for_end_frames, the six rules in the reference's order (they overlap in sequences shorter than six frames)
+#pragma unroll
+  for (int c = 0; c < 2; ++c)
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      auto& a = v;
+      if (i == 0) a[0][c][p] = a[1][c][p] = a[2][c][p] = 0.f;
+      if (i == 1) { a[0][c][p] = a[2][c][p]; a[1][c][p] = a[2][c][p]; }
+      if (i == 2) a[0][c][p] = a[1][c][p];
+      if (i == Tn - 1) a[4][c][p] = a[5][c][p] = a[6][c][p] = 0.f;
+      if (i == Tn - 2) { a[5][c][p] = a[4][c][p]; a[6][c][p] = a[4][c][p]; }
+      if (i == Tn - 3) a[6][c][p] = a[5][c][p];
+    }
+  const long long plane = (long long)Hp * Wp;
+  o += (long long)y * Wp + x;
+#pragma unroll
+  for (int s = 0; s < 7; ++s)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      f32x4 q = {v[s][c][0], v[s][c][1], v[s][c][2], v[s][c][3]};
+      *reinterpret_cast<f32x4*>(o + (s * 2 + c) * plane) = q;
+    }
+}
+
+// The random-access form (cdfo_seq_flows_ra / cdfo_seq_flows_ra_ring, seq_flows_ra.hip): the same four pixels, stores and end rules,
+// from BOTH lists' fields of the entry the centre reads.  Slots 0-2 come from list 0 (p2 = m / (ref * -1)), slots 4-6 from list 1
+// (p4 = m / ref); a pixel with no reference in one list (ref == -99 after the conversion to fp32) takes the other list's vector,
+// negated: opt/data_RA_bi.py's field as cdfo_train_batch_ra builds it, without the flips.
+template <typename T>
+__device__ __forceinline__ void seq_flows_ra_pixels(const T* __restrict__ field0, const T* __restrict__ field1, int H, int W, int i, int Tn,
+                                                    int Hp, int Wp, int y, int x, float* __restrict__ o) {
+  const int n = H * W * 3;
+  float m0[12], m1[12];
+  // padding rows start beyond the field: every element is out of range
+  const int e0 = y < H ? (y * W + x) * 3 : n;
+  load_mv12<T>(field0, e0, n, m0);
+  load_mv12<T>(field1, e0, n, m1);
+  float v[7][2][4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const bool inside = y < H && x + p < W;
+    // Each step is one correctly rounded fp32 operation, in the order of streaming.mv2mvs_ra.
+    const float d0 = m0[3 * p + 2] * -1.0f, d1 = m1[3 * p + 2];
+    float p2[2] = {__fdiv_rn(m0[3 * p + 1], d0), __fdiv_rn(m0[3 * p + 0], d0)};
+    float p4[2] = {__fdiv_rn(m1[3 * p + 1], d1), __fdiv_rn(m1[3 * p + 0], d1)};
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      if (p2[c] != p2[c]) p2[c] = 0.f;
+      if (p4[c] != p4[c]) p4[c] = 0.f;
+    }
+    if (m0[3 * p + 2] == -99.0f) { p2[0] = -p4[0]; p2[1] = -p4[1]; }
+    if (m1[3 * p + 2] == -99.0f) { p4[0] = -p2[0]; p4[1] = -p2[1]; }   // after the line above: both marked leaves p4 as it was
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int s = 0; s < 7; ++s) {
+        const float sc = (float)(s < 3 ? 3 - s : s - 3);
+        const float r = s == 3 ? 0.f : __fdiv_rn(__fmul_rn(s < 3 ? p2[c] : p4[c], sc), 128.0f);
+        v[s][c][p] = inside ? r : 0.f;                         // zero padding to Hp x Wp
+      }
+  }
+  // modify_mv_for_end_frames, as in seq_flows_pixels
 #pragma unroll
   for (int c = 0; c < 2; ++c)
 #pragma unroll

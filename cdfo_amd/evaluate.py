@@ -52,7 +52,7 @@ import torch
 from . import kernels as K
 from . import metrics as M
 from .priors import load_sequence, read_gray_png, write_gray_png
-from .streaming import StreamingSR
+from .streaming import StreamingSR, check_coding
 from .yuv import YuvReader, YuvWriter, load_sequence_yuv, parse_pix_fmt
 
 MAX_WORKERS = 16
@@ -467,7 +467,7 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
                       share_compensation: bool = False, crop_border: int = 4, quantise: str = "trunc", workers: int = 8,
                       png_level: int = 6, gumbel_uniform: Optional[Sequence] = None,
                       frame_noise: Optional[Sequence] = None, msssim: bool = False, niqe=None, brisque=None,
-                      tof: bool = False, lpips=None) -> SequenceResult:
+                      tof: bool = False, lpips=None, coding: str = "LD") -> SequenceResult:
     """Super-resolve the sequence in ``lr_dir`` / ``side_dir`` (the reference's test layout, see cdfo_amd/priors.py) with ``model`` (on a
     GPU), ``chunk`` centre frames per forward.  ``save_dir``: write every frame as an 8-bit PNG under its LR file name.  ``gt_dir``:
     per-frame PSNR / SSIM of the 8-bit frames against ``<gt_dir>/%05d.png`` over the common size less ``crop_border``.
@@ -486,8 +486,10 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
     ``lpips``: the model of the learned perceptual distance LPIPS, a path, the arrays or a `metrics.LpipsParams` (`metrics.lpips_params`;
     the project ships no model, and parity with the ``lpips`` package is unpinned); with ground truth every frame's distance to it is
     then reported as well (`metrics.lpips_u8`: VGG-shaped trunk on the luma over the whole common region, lower is better); the
-    region must be at least 16 x 16, and without ground truth it is a ValueError."""
+    region must be at least 16 x 16, and without ground truth it is a ValueError.  ``coding``: `StreamingSR`'s ("LD": the reference's
+    flows from list 1; "RA": the random-access field from both lists, for a model trained on it)."""
     workers, chunk = _check_args(workers, quantise, chunk)
+    check_coding(coding)
     t_start = time.perf_counter()
     lr = _PngSource(lr_dir)
     nq_params = _check_niqe(lr, niqe)
@@ -506,7 +508,7 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
     def load():
         seq = load_sequence(lr_dir, side_dir)
         return StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"], gumbel_uniform=gumbel_uniform,
-                           frame_noise=frame_noise), None
+                           frame_noise=frame_noise, coding=coding), None
 
     s, sse, _, ssim, ms, nq, bq, tf, lp = _run_chunks(lr, load, gt, sink, chunk, share_compensation, crop_border, 0, quantise, workers,
                                                       msssim, nq_params is not None, bq_params is not None, tof, lp_params)
@@ -567,7 +569,7 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
                  quantise: str = "trunc", workers: int = 8, gumbel_uniform: Optional[Sequence] = None,
                  frame_noise: Optional[Sequence] = None, gt_size: Optional[Tuple[int, int]] = None,
                  pix_fmt: str = "yuv420p", msssim: bool = False, niqe=None, brisque=None, tof: bool = False,
-                 lpips=None) -> YuvResult:
+                 lpips=None, coding: str = "LD") -> YuvResult:
     """`evaluate_sequence` on raw 8-bit I420 files (cdfo_amd/yuv.py).  ``lr_yuv``: the LR sequence, ``width`` x ``height`` (even);
     the coding priors stay in ``side_dir``.  The luma goes the way it goes there (`StreamingSR.iter_chunked`, ``finish_frames`` with the
     PSNR numerator, ``ssim_u8``).  The chroma never passes through the model: per chunk the U and V planes of its centre frames are
@@ -585,8 +587,9 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     `evaluate_sequence`'s, on the luma of 8-bit formats; above 8 bits it is a ValueError (the reference defines the metric on 0 .. 255
     integers).  ``brisque``: as `evaluate_sequence`'s, with the same restriction to 8-bit formats.  ``tof``: as `evaluate_sequence`'s, on
     the luma of 8-bit formats with ground truth.  ``lpips``: as `evaluate_sequence`'s, on the luma only, of 8-bit formats with ground
-    truth."""
+    truth.  ``coding``: as `evaluate_sequence`'s."""
     fmt = parse_pix_fmt(pix_fmt)
+    check_coding(coding)
     workers, chunk = _check_args(workers, quantise, chunk)
     t_start = time.perf_counter()
     ccrop = chroma_crop(crop_border, fmt.chroma)
@@ -613,7 +616,7 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
             seq = load_sequence_yuv(lr_yuv, width, height, side_dir, fmt)
             lr_c = (seq["u"], seq["v"]) if "u" in seq else None
             return StreamingSR(model, seq["lr"], seq["pms"], seq["rms"], seq["ufs"], seq["mvl0"], seq["mvl1"],
-                               gumbel_uniform=gumbel_uniform, frame_noise=frame_noise, peak=fmt.peak), lr_c
+                               gumbel_uniform=gumbel_uniform, frame_noise=frame_noise, peak=fmt.peak, coding=coding), lr_c
 
         s, sse_y, sse_c, ssim, ms, nq, bq, tf, lp = _run_chunks(lr, load, gt, writer and _YuvSink(writer), chunk, share_compensation,
                                                                 crop_border, ccrop, quantise, workers, msssim, nq_params is not None,
@@ -631,12 +634,15 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
                      time.perf_counter() - t_start, ms, _mean(ms), nq, _mean(nq), bq, _mean(bq), tf, _mean(tf), lp, _mean(lp))
 
 
-def _write_synthetic(root: str, T: int, H: int, W: int, seed: int, put_lr, put_gt, peak: int = 255) -> str:
+def _write_synthetic(root: str, T: int, H: int, W: int, seed: int, put_lr, put_gt, peak: int = 255, markers: bool = False) -> str:
     """The random content of the synthetic writers, drawn in one fixed order: per frame the LR luma to ``put_lr(t, frame)``, the
     4H x 4W ground-truth luma to ``put_gt(t, frame)`` (None: not drawn), then the frame's coding priors into ``<root>/side``, which
     is returned.  ``peak`` above 255: samples over 0 .. peak as uint16, the unfiltered planes as 16-bit PNGs, the residuals scaled to
-    the depth as int16; the partition maps stay 8-bit."""
+    the depth as int16; the partition maps stay 8-bit.  ``markers``: about three motion blocks in eight of every frame carry the
+    random-access streams' "no reference in this list" mark, -99 in the reference component, in list 0, in list 1 or in both; the marks
+    come from a generator of their own, so every other byte is what it is without them."""
     rs = np.random.RandomState(seed)
+    rm = np.random.RandomState((seed + 0x51ED270B) % (1 << 32)) if markers else None
     kind, gain = (np.uint8, 1) if peak == 255 else (np.uint16, (peak + 1) // 256)
     side = os.path.join(root, "side")
     for d in (os.path.join(side, n) for n in ("part_m", "res", "unfiltered", "mvl0", "mvl1")):
@@ -652,32 +658,39 @@ def _write_synthetic(root: str, T: int, H: int, W: int, seed: int, put_lr, put_g
             write_gray_png(os.path.join(side, "unfiltered", i + "_unflt.png"), rs.randint(0, peak + 1, (H, W)).astype(kind))
             res = np.clip(np.round(rs.randn(H, W, 3) * (6 * gain)), -128 * gain, 128 * gain - 1).astype(np.int8 if gain == 1 else np.int16)
             np.save(os.path.join(side, "res", i + "_res.npy"), res)
-            for name in ("mvl0", "mvl1"):            # block-constant motion, a reference distance of -2, -1 or 1
+            marks = rm.randint(0, 8, (hb, wb)) if markers else None      # 1: list 0 marked, 2: list 1, 3: both, else neither
+            for bit, name in ((1, "mvl0"), (2, "mvl1")):                 # block-constant motion, a reference distance of -2, -1 or 1
                 mv = rs.randint(-64, 64, (hb, wb, 3)).astype(np.int16)
                 mv[..., 2] = rs.choice([-2, -1, 1], size=(hb, wb))
+                if marks is not None:
+                    mv[(marks < 4) & ((marks & bit) != 0), 2] = -99
                 mv = np.repeat(np.repeat(mv, 8, axis=0), 8, axis=1)[:H, :W]
                 np.save(os.path.join(side, name, i + "_" + name + ".npy"), mv)
     return side
 
 
-def write_synthetic_sequence(root: str, T: int, H: int, W: int, seed: int = 0, gt: bool = True):
+def write_synthetic_sequence(root: str, T: int, H: int, W: int, seed: int = 0, gt: bool = True, markers: bool = False):
     """A random sequence of T frames of H x W in the reference's layout under ``root`` (lr/, side/..., and gt/ with 4H x 4W frames):
-    (lr_dir, side_dir, gt_dir or None).  For tools and benchmarks that have no data set at hand."""
+    (lr_dir, side_dir, gt_dir or None).  For tools and benchmarks that have no data set at hand.  ``markers``: some motion blocks
+    carry the random-access mark -99 in list 0, list 1 or both (`_write_synthetic`); every other byte is unchanged."""
     lr_dir, gt_dir = os.path.join(root, "lr"), os.path.join(root, "gt")
     os.makedirs(lr_dir, exist_ok=True)
     if gt:
         os.makedirs(gt_dir, exist_ok=True)
     side = _write_synthetic(root, T, H, W, seed, lambda t, f: write_gray_png(os.path.join(lr_dir, "%05d.png" % t), f),
-                            (lambda t, f: write_gray_png(os.path.join(gt_dir, "%05d.png" % t), f, level=1)) if gt else None)
+                            (lambda t, f: write_gray_png(os.path.join(gt_dir, "%05d.png" % t), f, level=1)) if gt else None,
+                            markers=markers)
     return lr_dir, side, (gt_dir if gt else None)
 
 
-def write_synthetic_sequence_yuv(root: str, T: int, H: int, W: int, seed: int = 0, gt: bool = True, pix_fmt: str = "yuv420p"):
+def write_synthetic_sequence_yuv(root: str, T: int, H: int, W: int, seed: int = 0, gt: bool = True, pix_fmt: str = "yuv420p",
+                                 markers: bool = False):
     """`write_synthetic_sequence` with the frames in raw I420 files: the same luma and the same coding priors for the same ``seed``,
     plus random chroma (a generator of its own, so the luma's draws are those of the PNG layout).  H and W even.
     (lr_yuv, side_dir, gt_yuv or None); the files are ``<root>/lr_WxH.yuv`` and ``<root>/gt_4Wx4H.yuv``.
     ``pix_fmt``: another format of cdfo_amd/yuv.py (H and W even for 4:2:0 only).  Above 8 bits every plane draws from the whole
-    0 .. 2**depth - 1, the priors are at that depth, and each chroma plane holds both ends of the range."""
+    0 .. 2**depth - 1, the priors are at that depth, and each chroma plane holds both ends of the range.  ``markers``: as
+    `write_synthetic_sequence`'s."""
     fmt = parse_pix_fmt(pix_fmt)
     rc = np.random.RandomState((seed + 0x9E3779B9) % (1 << 32))
     lr_yuv, gt_yuv = os.path.join(root, "lr_%dx%d.yuv" % (W, H)), os.path.join(root, "gt_%dx%d.yuv" % (4 * W, 4 * H))
@@ -698,7 +711,7 @@ def write_synthetic_sequence_yuv(root: str, T: int, H: int, W: int, seed: int = 
         gw = YuvWriter(gt_yuv, 4 * W, 4 * H, fmt) if gt else None
         try:
             side = _write_synthetic(root, T, H, W, seed, lambda t, f: lw.append(f, *planes(H, W)),
-                                    (lambda t, f: gw.append(f, *planes(4 * H, 4 * W))) if gt else None, fmt.peak)
+                                    (lambda t, f: gw.append(f, *planes(4 * H, 4 * W))) if gt else None, fmt.peak, markers)
         finally:
             if gw is not None:
                 gw.close()

@@ -15,6 +15,7 @@ import torch
 
 from . import _lib, switches
 from ._lib import CdfoError, ConvArgs, _vp, check
+from .streaming import check_ra_lists
 
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3
 PREC_F32, PREC_BF16X3, PREC_BF16, PREC_FP16X2, PREC_FP16, PREC_FP16X1 = 0, 1, 2, 3, 4, 5
@@ -835,6 +836,35 @@ def seq_flows_ring(ring: torch.Tensor, i0: int, K: int, T_known: int, Hp: int, W
     cap, H, W, _ = ring.shape
     out = torch.empty((K, 7, 2, Hp, Wp), dtype=torch.float32, device=ring.device)
     check(_lib.lib().cdfo_seq_flows_ring(_vp(ring), cap, H, W, i0, K, T_known, Hp, Wp, _vp(out), _stream()), "cdfo_seq_flows_ring")
+    return out
+
+
+def seq_flows_ra(mv0: torch.Tensor, mv1: torch.Tensor, i0: int, K: int, Hp: int, Wp: int) -> torch.Tensor:
+    """`seq_flows` for the random-access field: mv0, mv1: both lists' motion fields [T,H,W,3] of one sequence (device, one dtype) ->
+    the flows of centre frames i0 .. i0+K-1, [K,7,2,Hp,Wp] fp32: streaming.mv2mvs_ra + modify_mv_for_end_frames of each centre,
+    bit for bit, in one launch (cdfo_seq_flows_ra)."""
+    check_ra_lists("seq_flows_ra", mv0, mv1)
+    if not mv0.is_cuda or mv0.dim() != 4 or mv0.shape[3] != 3 or mv0.dtype not in _MV_DTYPES:
+        raise ValueError(f"seq_flows_ra: device tensors [T,H,W,3] of a real dtype expected, got {mv0.dtype} {tuple(mv0.shape)}")
+    mv0, mv1 = (m if m.is_contiguous() else m.contiguous() for m in (mv0, mv1))
+    T, H, W, _ = mv0.shape
+    out = torch.empty((K, 7, 2, Hp, Wp), dtype=torch.float32, device=mv0.device)
+    check(_lib.lib().cdfo_seq_flows_ra(_vp(mv0), _vp(mv1), _MV_DTYPES[mv0.dtype], T, H, W, i0, K, Hp, Wp, _vp(out), _stream()),
+          "cdfo_seq_flows_ra")
+    return out
+
+
+def seq_flows_ra_ring(ring0: torch.Tensor, ring1: torch.Tensor, i0: int, K: int, T_known: int, Hp: int, Wp: int) -> torch.Tensor:
+    """`seq_flows_ra` reading the two fp32 rings [cap,H,W,3] of live inference (entry e of both lists in slot e mod cap) for centres
+    i0 .. i0+K-1.  T_known: the sequence's length, or 0 while the stream is open (no end rule applies, T > 1).  -> [K,7,2,Hp,Wp]."""
+    check_ra_lists("seq_flows_ra_ring", ring0, ring1)
+    if not ring0.is_cuda or ring0.dim() != 4 or ring0.shape[3] != 3 or ring0.dtype != torch.float32 or not ring0.is_contiguous() \
+            or not ring1.is_contiguous():
+        raise ValueError(f"seq_flows_ra_ring: dense fp32 device rings [cap,H,W,3] expected, got {ring0.dtype} {tuple(ring0.shape)}")
+    cap, H, W, _ = ring0.shape
+    out = torch.empty((K, 7, 2, Hp, Wp), dtype=torch.float32, device=ring0.device)
+    check(_lib.lib().cdfo_seq_flows_ra_ring(_vp(ring0), _vp(ring1), cap, H, W, i0, K, T_known, Hp, Wp, _vp(out), _stream()),
+          "cdfo_seq_flows_ra_ring")
     return out
 
 

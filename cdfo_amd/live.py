@@ -21,7 +21,8 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from .streaming import NFRAMES, ChunkPlan, ChunkRunner, bank_slot, check_noise_format, check_peak, cropped, padded, plan_chunks
+from .streaming import (NFRAMES, ChunkPlan, ChunkRunner, bank_slot, check_coding, check_noise_format, check_peak, cropped, padded,
+                        plan_chunks)
 
 
 class LivePlanner:
@@ -72,6 +73,14 @@ class _Indexed:
         return self.fn(i)
 
 
+def check_push_lists(coding: str, mvl0) -> None:
+    """Which motion lists a push must carry: list 1 always, list 0 exactly when the stream builds the random-access field."""
+    if coding == "RA" and mvl0 is None:
+        raise ValueError("LiveSR.push: coding='RA' builds its flows from both lists: pass mvl0= with every frame")
+    if coding != "RA" and mvl0 is not None:
+        raise ValueError("LiveSR.push: mvl0 is read by coding='RA' only; this stream was opened with coding='LD', which would drop it")
+
+
 _REAL = (torch.float16, torch.bfloat16, torch.float32, torch.float64, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64,
          torch.uint16)
 STAGING_SETS = 2
@@ -102,12 +111,18 @@ class LiveSR:
     an upload into a ring slot waits for the build kernels of the last chunk that read the slot's previous frame, and the host
     rewrites a staging buffer only after that buffer's own upload has completed.
 
+    coding="RA" (opt-in; "LD" is everything above, unchanged): the stream builds `StreamingSR`'s random-access field
+    (`streaming.mv2mvs_ra`): ``push(lr, pm, rm, uf, mvl1, mvl0)`` takes list 0's field as well (same shape and dtype as mvl1), a second
+    fp32 motion ring and a staging buffer of its own in each set hold it, and the chunk's flows come from cdfo_seq_flows_ra_ring.  The
+    frames are then bit-identical to ``StreamingSR(..., coding="RA").run_chunked(chunk, share_compensation)``.
+
     Noise: gumbel_uniform (per centre frame: six draws [1,64,Hp,Wp]) and frame_noise (per frame, read by share_compensation only)
     are a sequence or a callable of the index, under `check_noise_format`'s rules.  Without them the unshared mode draws per forward
     call like `run_chunked`, and the shared mode takes one Philox key per stream before its first extraction, draw = frame index."""
 
     def __init__(self, model, height: int, width: int, chunk: int = 8, share_compensation: bool = False, peak: int = 255,
-                 gumbel_uniform=None, frame_noise=None):
+                 gumbel_uniform=None, frame_noise=None, coding: str = "LD"):
+        self.coding = check_coding(coding)
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise NotImplementedError("LiveSR needs the model on a GPU (HIP path, no CPU fallback)")
@@ -131,6 +146,8 @@ class LiveSR:
         # frame t lives in slot t mod cap of every ring
         self._rings = {"lr": new((cap, H, W), self.sample), "uf": new((cap, H, W), self.sample), "pm": new((cap, H, W), torch.uint8),
                        "rm": new((cap, H, W), torch.float32), "mv": new((cap, H, W, 3), torch.float32)}
+        if self.coding == "RA":           # list 0's fields beside list 1's, with a staging buffer of their own in each set
+            self._rings["mv0"] = new((cap, H, W, 3), torch.float32)
         self._copy = torch.cuda.Stream(dev)
         for t in self._rings.values():
             t.record_stream(self._copy)
@@ -166,7 +183,8 @@ class LiveSR:
 
     @property
     def resident_bytes(self) -> int:
-        """The object's own persistent device buffers: the five input rings, the feature bank and the compensation ring."""
+        """The object's own persistent device buffers: the five input rings (six with coding="RA": list 0's motion ring), the feature
+        bank and the compensation ring."""
         return sum(t.numel() * t.element_size() for t in self._rings.values()) + self._runner.resident_bytes
 
     @property
@@ -191,15 +209,21 @@ class LiveSR:
             raise ValueError(f"LiveSR.push: {name} lives on {t.device}; a host array or a tensor on {self.dev} expected")
         return t
 
-    def push(self, lr, pm, rm, uf, mvl1) -> List[Tuple[int, torch.Tensor]]:
-        """One frame and its priors.  Returns the frames of the chunk this push made runnable, complete, or []."""
+    def push(self, lr, pm, rm, uf, mvl1, mvl0=None) -> List[Tuple[int, torch.Tensor]]:
+        """One frame and its priors.  Returns the frames of the chunk this push made runnable, complete, or [].  mvl0: list 0's field
+        of the frame, required with coding="RA" and refused (ValueError) with coding="LD", which would never read it."""
         if self.plan.closed:
             raise RuntimeError("LiveSR.push after close()")
+        check_push_lists(self.coding, mvl0)
         from . import kernels as K
         hw = (self.H, self.W)
         frame = {"lr": self._checked("lr", lr, hw, (self.sample,)), "pm": self._checked("pm", pm, hw, (torch.uint8,)),
                  "rm": self._checked("rm", rm, hw, _REAL), "uf": self._checked("uf", uf, hw, (self.sample,)),
                  "mv": self._checked("mvl1", mvl1, hw + (3,), tuple(K._MV_DTYPES))}
+        if self.coding == "RA":
+            frame["mv0"] = self._checked("mvl0", mvl0, hw + (3,), tuple(K._MV_DTYPES))
+            if frame["mv0"].dtype != frame["mv"].dtype:      # one rule decides what marks a block: both lists in one type
+                raise ValueError(f"LiveSR.push: mvl0 and mvl1 must be of one dtype, got {frame['mv0'].dtype} and {frame['mv'].dtype}")
         slot = bank_slot(self.plan.pushed, self.ring_capacity)
         host = {k: t for k, t in frame.items() if not t.is_cuda}
         with torch.cuda.device(self.dev):
@@ -248,7 +272,10 @@ class LiveSR:
                 cur.wait_event(self._last_upload)
             planes = K.live_planes(R["lr"], R["uf"], R["pm"], R["rm"], tables[len(head):], k, E, self.Hp, self.Wp, self.peak,
                                    want_r=not self.shared, want_r_new=self.shared)
-            m1 = K.seq_flows_ring(R["mv"], plan.centres[0], k, T_known, self.Hp, self.Wp)
+            if self.coding == "RA":
+                m1 = K.seq_flows_ra_ring(R["mv0"], R["mv"], plan.centres[0], k, T_known, self.Hp, self.Wp)
+            else:
+                m1 = K.seq_flows_ring(R["mv"], plan.centres[0], k, T_known, self.Hp, self.Wp)
             read = torch.cuda.Event()
             read.record(cur)
             for s in set(live):

@@ -45,6 +45,48 @@ def mv2mvs(mv: torch.Tensor) -> torch.Tensor:
     return out / (4.0 * 32.0)
 
 
+CODINGS = ("LD", "RA")
+RA_MARK = -99.0             # a block with no reference in a list carries this in its reference component (opt/data_RA_bi.py)
+
+
+def check_coding(coding) -> str:
+    if coding not in CODINGS:
+        raise ValueError(f"coding must be one of {CODINGS}, got {coding!r}")
+    return coding
+
+
+def check_ra_lists(who: str, mv0: torch.Tensor, mv1: torch.Tensor) -> None:
+    """The two lists of a random-access field are read together, element by element: one shape, one dtype, one device."""
+    if mv0.shape != mv1.shape or mv0.dtype != mv1.dtype or mv0.device != mv1.device:
+        raise ValueError(f"{who}: the two motion lists must agree in shape, dtype and device, got {mv0.dtype} {tuple(mv0.shape)} on "
+                         f"{mv0.device} and {mv1.dtype} {tuple(mv1.shape)} on {mv1.device}")
+
+
+def mv2mvs_ra(mv0: torch.Tensor, mv1: torch.Tensor) -> torch.Tensor:
+    """The random-access field of one frame, opt/data_RA_bi.py's rule without the flips (tests/train_batch_ra_ref.py::flows):
+    mv0, mv1: [H,W,3] of the two lists (one dtype, one device) -> flows [7,2,H,W] in pixels.  Slots 0-2 come from list 0
+    (``/ (ref * -1)``), slots 4-6 from list 1 (``/ ref``), NaN -> 0 and x / 0 stays inf as in `mv2mvs`; a block with no reference in
+    one list (``ref == -99`` after the conversion to fp32) takes the other list's vector, negated.  Nothing is clipped."""
+    check_ra_lists("mv2mvs_ra", mv0, mv1)
+    if mv0.dim() != 3 or mv0.shape[2] != 3:
+        raise ValueError(f"mv2mvs_ra: fields [H,W,3] expected, got {tuple(mv0.shape)}")
+    m0, m1 = mv0.to(torch.float32), mv1.to(torch.float32)
+
+    def vector(m, d):                                          # components swapped, NaN -> +0
+        fx, fy = m[..., 1] / d, m[..., 0] / d
+        return torch.stack([torch.where(torch.isnan(fx), torch.zeros_like(fx), fx),
+                            torch.where(torch.isnan(fy), torch.zeros_like(fy), fy)], 0)      # [2,H,W]
+
+    p2, p4 = vector(m0, m0[..., 2] * -1.0), vector(m1, m1[..., 2])
+    p2 = torch.where(m0[..., 2] == RA_MARK, -p4, p2)
+    p4 = torch.where(m1[..., 2] == RA_MARK, -p2, p4)           # p2 after the line above: both marked leaves p4 as it was
+    w = torch.tensor([3.0, 2.0, 1.0], device=m0.device).view(3, 1, 1, 1)
+    out = torch.zeros((NFRAMES,) + tuple(p2.shape), dtype=torch.float32, device=m0.device)
+    out[0:3] = p2.unsqueeze(0) * w
+    out[4:7] = p4.unsqueeze(0) * w.flip(0)
+    return out / (4.0 * 32.0)
+
+
 def modify_mv_for_end_frames(i: int, mvs: torch.Tensor, max_idx: int) -> torch.Tensor:
     """test_LD_22_FPS.py:200-225 on mvs [B,7,2,H,W], in place; max_idx = number of frames in the sequence."""
     if i == 0:
@@ -307,6 +349,12 @@ class StreamingSR:
     peak: the largest sample of lr, rms and ufs, 2**depth - 1 (255: 8-bit files).  The three are divided by it, and pms, a mask that is
     8-bit at every depth, by 255: true fp32 divisions, so a sequence and its samples times 257 at peak 65535 give the same planes.
 
+    coding: "LD" (the default: the reference's evaluation loops, `mv2mvs` on list 1 alone, mvl0 unread) or "RA" (opt-in, the project's
+    own definition for a model trained on the random-access loader's field): every path builds its flows from BOTH lists with
+    `mv2mvs_ra` -- past slots from list 0, future slots from list 1, a block with no reference in one list borrowing the other's
+    vector negated -- at the entry the LD rule reads, followed by the same end rules; `run_chunked` builds them with
+    ``kernels.seq_flows_ra``.  The model reads mvs1 only; `step` passes the one field for both arguments, as the RA loader does.
+
     Deliberate deviations from the reference loop: the sequence is device resident and windows are gathered by index;
     `run_chunked` extracts each frame once (same arithmetic per output frame); ``run_chunked(share_compensation=True)`` -- opt-in
     -- also compensates each neighbour frame once, with one Gumbel draw per frame where the reference draws per (step, slot).
@@ -314,7 +362,10 @@ class StreamingSR:
 
     def __init__(self, model, lr, pms, rms, ufs, mvl0, mvl1, device: Optional[torch.device] = None,
                  gumbel_uniform: Optional[Sequence] = None, use_graph: bool = False, frame_noise: Optional[Sequence] = None,
-                 peak: int = 255):
+                 peak: int = 255, coding: str = "LD"):
+        self.coding = check_coding(coding)
+        if coding == "RA":                   # the two lists are read pixel by pixel together: judged before anything is uploaded
+            check_ra_lists("StreamingSR(coding='RA')", torch.as_tensor(mvl0), torch.as_tensor(mvl1))
         dev = torch.device(device) if device is not None else next(model.parameters()).device
         if dev.type != "cuda":
             raise NotImplementedError("StreamingSR needs the model on a GPU (HIP path, no CPU fallback)")
@@ -348,6 +399,12 @@ class StreamingSR:
     def _mvs(self, mvl: torch.Tensor, i: int) -> torch.Tensor:
         m = torch.zeros((NFRAMES, 2, self.Hp, self.Wp), dtype=torch.float32, device=self.dev)
         m[:, :, :self.H, :self.W] = mv2mvs(mvl[max(1, i) if self.T > 1 else 0])
+        return modify_mv_for_end_frames(i, m.unsqueeze(0), self.T)
+
+    def _mvs_ra(self, i: int) -> torch.Tensor:
+        e = max(1, i) if self.T > 1 else 0
+        m = torch.zeros((NFRAMES, 2, self.Hp, self.Wp), dtype=torch.float32, device=self.dev)
+        m[:, :, :self.H, :self.W] = mv2mvs_ra(self.mvl0[e], self.mvl1[e])
         return modify_mv_for_end_frames(i, m.unsqueeze(0), self.T)
 
     def step(self, i: int) -> torch.Tensor:
@@ -386,6 +443,9 @@ class StreamingSR:
         po = o.clamp_min(1) if self.T > 1 else o                 # priors of frame 0 come from entry 1 (:36,53,66)
         win = lambda t, idx: t.index_select(0, idx)[None, :, None]            # [1,7,1,H,W]
         x, p, r, u = win(self.lr, o), win(self.pms, po), win(self.rms, po), win(self.ufs, po)
+        if self.coding == "RA":                                  # one field for both arguments, as the RA loader hands it out
+            m = self._mvs_ra(i)
+            return x, m, m, p, r, u
         return x, self._mvs(self.mvl0, i), self._mvs(self.mvl1, i), p, r, u
 
     def run_pipelined(self) -> List[torch.Tensor]:
@@ -494,7 +554,10 @@ class StreamingSR:
         x = K.gather_frames(self.lr, frame_idx)
         r = None if shared else K.gather_frames(self.rms, prior_idx)
         u = K.gather_frames(self.ufs, prior_idx)
-        m1 = K.seq_flows(self.mvl1, plan.centres[0], len(plan.centres), self.Hp, self.Wp)
+        if self.coding == "RA":
+            m1 = K.seq_flows_ra(self.mvl0, self.mvl1, plan.centres[0], len(plan.centres), self.Hp, self.Wp)
+        else:
+            m1 = K.seq_flows(self.mvl1, plan.centres[0], len(plan.centres), self.Hp, self.Wp)
         return x, r, u, lr_new, p_new, r_new, m1
 
     @property

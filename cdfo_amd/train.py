@@ -24,12 +24,15 @@ def learning_rate(lr0: float, epoch: int) -> float:
 
 def fit(model, clips: ClipSet, epochs: int, out_dir: str, batch_size: int = 20, crop: int = 64, lr: float = 1e-4,
         weight_decay: float = 1e-5, val_itv: int = 200, val: Optional[Sequence[str]] = None, seed: int = 4, start_epoch: int = 0,
-        log: Callable[[str], None] = print) -> List[float]:
+        log: Callable[[str], None] = print, val_coding: str = "LD") -> List[float]:
     """Train ``model`` (a ``CVSR_V8`` on the clip set's device) for epochs ``start_epoch .. epochs - 1``; returns the epochs' average
     losses.  Adam with ``lr`` and ``weight_decay``; the rate of each epoch is set directly (`learning_rate`).  Every ``val_itv`` epochs
     ``state_dict()`` goes to ``<out_dir>/ckpt/epoch-N.pth`` and, with ``val = (lr_dir, side_dir, gt_dir)``, that sequence is evaluated
-    (`evaluate_sequence`) and its PSNR and SSIM are logged.  ``seed`` seeds the plans' generator."""
+    (`evaluate_sequence`) and its PSNR and SSIM are logged.  ``seed`` seeds the plans' generator.  ``val_coding``: the ``coding`` of that
+    evaluation ("RA": the validation flows are the random-access loader's field, what a ``ClipSet(..., coding="RA")`` trains on)."""
     from .evaluate import evaluate_sequence
+    from .streaming import check_coding
+    check_coding(val_coding)
     os.makedirs(os.path.join(out_dir, "ckpt"), exist_ok=True)
     rng = np.random.default_rng(seed)
     optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
@@ -56,7 +59,7 @@ def fit(model, clips: ClipSet, epochs: int, out_dir: str, batch_size: int = 20, 
             if val is not None:
                 model.eval()
                 with torch.no_grad():
-                    r = evaluate_sequence(model, val[0], val[1], gt_dir=val[2])
+                    r = evaluate_sequence(model, val[0], val[1], gt_dir=val[2], coding=val_coding)
                 model.train()
                 log('PSNR:%f, SSIM: %f' % (r.mean_psnr, r.mean_ssim))
     return averages

@@ -674,6 +674,27 @@ int cdfo_live_planes(const void* lr, const void* ufs, const unsigned char* pms, 
                      float* r_new, void* stream);
 int cdfo_seq_flows_ring(const float* ring, int cap, int H, int W, int i0, int K, int T_known, int Hp, int Wp, float* out, void* stream);
 
+/* ---- the random-access forms of the two flow builders (seq_flows_ra.hip; StreamingSR / LiveSR with coding="RA") ----
+ * cdfo_seq_flows_ra:  cdfo_seq_flows from BOTH lists' fields mv0, mv1 [T][H][W][3] (one element type `dtype`, any CDFO_MV_*), for a model
+ *                     trained on the random-access loader's field (opt/data_RA_bi.py, cdfo_train_batch_ra).  Centre i reads both lists
+ *                     at entry max(1, i) (entry 0 if T == 1).  Per pixel, (a, b, ref) converted to fp32 first, every step one correctly
+ *                     rounded fp32 operation:
+ *                         p2 = (b0 / (ref0 * -1), a0 / (ref0 * -1))      NaN -> +0, an infinity stays
+ *                         p4 = (b1 / ref1,        a1 / ref1)             NaN -> +0, an infinity stays
+ *                         ref0 == -99: p2 = -p4;   then ref1 == -99: p4 = -p2
+ *                         slots 0, 1, 2 = fl(p2 * w) / 128, w = 3, 2, 1;  slot 3 = +0;  slots 4, 5, 6 = fl(p4 * w) / 128, w = 1, 2, 3
+ *                     then modify_mv_for_end_frames for centre i in a sequence of T frames, zero padded from H x W to Hp x Wp
+ *                     (Wp % 4 == 0).  The marker is tested on the converted value (== -99.0f): an unsigned field never marks.  Nothing
+ *                     is clipped.  out [K][7][2][Hp][Wp] fp32, 16-byte aligned; bit-identical to cdfo_amd.streaming.mv2mvs_ra +
+ *                     modify_mv_for_end_frames.  K <= 65535; offsets inside a field are 32-bit (else CDFO_EINVAL).
+ * cdfo_seq_flows_ra_ring: cdfo_seq_flows_ra reading two fp32 rings [cap][H][W][3] (entry e of both lists in slot e mod cap), with
+ *                     T_known as in cdfo_seq_flows_ring (0: the end is not known yet, no end rule applies and T > 1).  Bit-identical to
+ *                     cdfo_seq_flows_ra on the whole fields of T_known frames (for T_known = 0: of any length >= i0 + K + 3). */
+int cdfo_seq_flows_ra(const void* mv0, const void* mv1, int dtype, int T, int H, int W, int i0, int K, int Hp, int Wp, float* out,
+                      void* stream);
+int cdfo_seq_flows_ra_ring(const float* ring0, const float* ring1, int cap, int H, int W, int i0, int K, int T_known, int Hp, int Wp,
+                           float* out, void* stream);
+
 /* ---- the output side of sequence evaluation (finish.hip; cdfo_amd/evaluate.py) ----
  * cdfo_finish_frames: K fp32 frames, read in place (frame k, row y at src + k*src_fstride + y*src_pitch, in elements; src 16-byte
  *                     aligned, pitch and stride multiples of 4), -> K 8-bit frames dst [K][Ho][Wo], packed (Wo % 4 == 0, dst 16-byte

@@ -8,21 +8,35 @@ from arch.SIDECVSR_our import CVSR_V8
 from cdfo_amd.streaming import ChunkRunner, StreamingSR
 
 
-def _synthetic(T, H, W):
-    """One synthetic sequence: 8-bit planes, a residual map, two decoder motion fields that are constant on 8x8 blocks."""
+def _coding():
+    """--coding {LD,RA}: `StreamingSR`'s coding of every mode of this run (LD when absent)."""
+    coding = sys.argv[sys.argv.index("--coding") + 1] if "--coding" in sys.argv else "LD"
+    if coding not in ("LD", "RA"):
+        sys.exit("--coding LD or --coding RA")
+    return coding
+
+
+def _synthetic(T, H, W, markers=False):
+    """One synthetic sequence: 8-bit planes, a residual map, two decoder motion fields that are constant on 8x8 blocks.  markers: about
+    three blocks in eight carry the random-access mark -99 in list 0, list 1 or both, drawn from a generator of their own."""
     rs = np.random.RandomState(0)
     u8 = lambda: rs.randint(0, 256, size=(T, H, W)).astype(np.uint8)
     lr, pms, ufs = u8(), u8(), u8()
     rms = np.clip(np.round(rs.randn(T, H, W) * 6), -128, 127).astype(np.float32)
     mv = rs.randint(-64, 64, size=(2, T, (H + 7) // 8, (W + 7) // 8, 3)).astype(np.float32)
     mv[..., 2] = rs.choice([-2.0, -1.0, 1.0], size=mv.shape[:-1])
+    if markers:
+        marks = np.random.RandomState(1).randint(0, 8, size=mv.shape[1:-1])      # 1: list 0 marked, 2: list 1, 3: both, else neither
+        for l, bit in ((0, 1), (1, 2)):
+            mv[l][(marks < 4) & ((marks & bit) != 0), 2] = -99.0
     mv = np.repeat(np.repeat(mv, 8, axis=2), 8, axis=3)[:, :, :H, :W]
     return lr, pms, rms, ufs, mv
 
 
 def main():
-    T, H, W = int(sys.argv[1]) if len(sys.argv) > 1 else 24, 270, 480
-    lr, pms, rms, ufs, mv = _synthetic(T, H, W)
+    T, H, W = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 24, 270, 480
+    coding = _coding()
+    lr, pms, rms, ufs, mv = _synthetic(T, H, W, coding == "RA")
     model = CVSR_V8()
     model = model.cuda().eval()
     # (HIP graph, neighbour streams, frames per group, group of frames 0-2 beside the new frame's feature extraction, new frame alone)
@@ -30,7 +44,7 @@ def main():
                                              (True, 2, 3, True, False), (False, 2, 3, True, True), (True, 2, 3, True, True),
                                              (True, 1, 3, False, False)):
         model.neighbour_streams, model.neighbour_group, model.overlap_new_frame, model.new_frame_alone = nstr, grp, ovl, alone
-        s = StreamingSR(model, lr, pms, rms, ufs, mv[0], mv[1], use_graph=use_graph)
+        s = StreamingSR(model, lr, pms, rms, ufs, mv[0], mv[1], use_graph=use_graph, coding=coding)
         s.run()                               # warm-up (weight packing, first-touch allocations, graph capture)
         outs = s.run()
         print(f"streaming, 1 sequence of {T} frames {H}x{W} -> {tuple(outs[0].shape)}, HIP graph {use_graph}, neighbour streams {nstr}, frames per group {grp}, overlap {ovl}, new frame alone {alone}: "
@@ -42,9 +56,10 @@ def pipelined():
     if "--size" in sys.argv:
         k = sys.argv.index("--size")
         T, H, W = int(sys.argv[k + 1]), int(sys.argv[k + 2]), int(sys.argv[k + 3])
-    lr, pms, rms, ufs, mv = _synthetic(T, H, W)
+    coding = _coding()
+    lr, pms, rms, ufs, mv = _synthetic(T, H, W, coding == "RA")
     model = CVSR_V8().cuda().eval()
-    s = StreamingSR(model, lr, pms, rms, ufs, mv[0], mv[1])
+    s = StreamingSR(model, lr, pms, rms, ufs, mv[0], mv[1], coding=coding)
     s.run()
     s.run()
     print(f"streaming, sequential loop (per-frame timing), {T} frames {H}x{W}: {s.fps:.2f} frames/s", flush=True)
@@ -59,7 +74,8 @@ def chunked():
     sequence in one process; after a warm-up pass each mode runs R times and every repeat's frames/s is printed (the spread,
     not one number).  --only-chunk skips the three one-frame modes (for a kernel trace of the chunked path alone); --phases adds an event breakdown of
     one pass per chunk size; --share adds run_chunked(K, share_compensation=True) rows (and their --phases breakdown, with the
-    per-frame compensation and the indexed warp as rows of their own)."""
+    per-frame compensation and the indexed warp as rows of their own); --coding RA runs every mode on the random-access field (both
+    motion lists, some blocks marked) in place of the LD rule."""
     T, H, W = 64, 270, 480
     if "--size" in sys.argv:
         k = sys.argv.index("--size")
@@ -70,7 +86,8 @@ def chunked():
     while k < len(sys.argv) and sys.argv[k].isdigit():
         chunks.append(int(sys.argv[k]))
         k += 1
-    lr, pms, rms, ufs, mv = _synthetic(T, H, W)
+    coding = _coding()
+    lr, pms, rms, ufs, mv = _synthetic(T, H, W, coding == "RA")
     model = CVSR_V8().cuda().eval()
 
     def report(name, make, loop):
@@ -80,11 +97,11 @@ def chunked():
         for _ in range(reps):
             loop(s)
             fps.append(s.fps)
-        print(f"{name}, {T} frames {H}x{W}: frames/s per repeat {' '.join('%.2f' % f for f in fps)}; median {np.median(fps):.2f}, "
+        print(f"{name}{', coding RA' if coding == 'RA' else ''}, {T} frames {H}x{W}: frames/s per repeat {' '.join('%.2f' % f for f in fps)}; median {np.median(fps):.2f}, "
               f"min {min(fps):.2f}, max {max(fps):.2f}" + (f"; frames extracted per pass {s.frames_extracted}" if "chunk" in name else "")
               + (f", compensated {s.frames_compensated}" if "share" in name else ""), flush=True)
 
-    seq = lambda **kw: StreamingSR(model, lr, pms, rms, ufs, mv[0], mv[1], **kw)
+    seq = lambda **kw: StreamingSR(model, lr, pms, rms, ufs, mv[0], mv[1], coding=coding, **kw)
     if "--only-chunk" not in sys.argv:
         report("run() (per-frame timing, B=1)", seq, lambda s: s.run())
         report("run() under HIP-graph replay", lambda: seq(use_graph=True), lambda s: s.run())

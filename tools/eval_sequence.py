@@ -62,6 +62,8 @@ def main():
     ap.add_argument("--tof", action="store_true", help="report the luma's tOF (Farneback flow of result against ground truth) as well")
     ap.add_argument("--lpips", metavar="MODEL", help="report the luma's LPIPS against the ground truth with this model (.npz) as well")
     ap.add_argument("--pix-fmt", default="yuv420p", help="the format of the raw files (cdfo_amd.yuv.parse_pix_fmt); default yuv420p")
+    ap.add_argument("--coding", choices=("LD", "RA"), default="LD",
+                    help="RA: flows from both motion lists, for a model trained on the random-access field (--synthetic then marks blocks)")
     a = ap.parse_args()
     yuv = a.lr_yuv is not None or a.yuv
     if a.lr_yuv is not None and not (a.size and a.side):
@@ -85,16 +87,18 @@ def main():
             lr, side, gt, size = a.lr_yuv, a.side, a.gt_yuv, a.size
             if a.synthetic is not None:
                 T, H, W = a.synthetic
-                (lr, side, gt), size = write_synthetic_sequence_yuv(tmp, T, H, W, pix_fmt=a.pix_fmt), (W, H)
+                (lr, side, gt), size = write_synthetic_sequence_yuv(tmp, T, H, W, pix_fmt=a.pix_fmt, markers=a.coding == "RA"), (W, H)
             r = evaluate_yuv(model, lr, size[0], size[1], side, gt_yuv=gt, save_yuv=a.out_yuv, chunk=a.chunk,
                              share_compensation=a.share, workers=a.workers, gt_size=tuple(a.gt_size) if a.gt_size else None,
-                             pix_fmt=a.pix_fmt, msssim=a.msssim, niqe=a.niqe, brisque=a.brisque, tof=a.tof, lpips=a.lpips)
+                             pix_fmt=a.pix_fmt, msssim=a.msssim, niqe=a.niqe, brisque=a.brisque, tof=a.tof, lpips=a.lpips,
+                             coding=a.coding)
         else:
             lr, side, gt = a.lr, a.side, a.gt
             if a.synthetic is not None:
-                lr, side, gt = write_synthetic_sequence(tmp, *a.synthetic)
+                lr, side, gt = write_synthetic_sequence(tmp, *a.synthetic, markers=a.coding == "RA")
             r = evaluate_sequence(model, lr, side, gt_dir=gt, save_dir=a.out, chunk=a.chunk, share_compensation=a.share,
-                                  workers=a.workers, msssim=a.msssim, niqe=a.niqe, brisque=a.brisque, tof=a.tof, lpips=a.lpips)
+                                  workers=a.workers, msssim=a.msssim, niqe=a.niqe, brisque=a.brisque, tof=a.tof, lpips=a.lpips,
+                                  coding=a.coding)
     name = a.name or os.path.basename(os.path.normpath(lr if a.synthetic is None else "synthetic"))
     if gt is not None:
         print(format_log_yuv(r, name) if yuv else format_log(r, name))

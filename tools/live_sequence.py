@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--share", action="store_true", help="share_compensation=True (opt-in, see cdfo_amd/streaming.py)")
     ap.add_argument("--weights")
     ap.add_argument("--synthetic", type=int, nargs=3, metavar=("T", "H", "W"))
+    ap.add_argument("--coding", choices=("LD", "RA"), default="LD",
+                    help="RA: list 0's field is pushed as well and the flows come from both lists (--synthetic then marks blocks)")
     a = ap.parse_args()
     if a.synthetic is None and not (a.lr and a.side):
         ap.error("--lr and --side, or --synthetic T H W")
@@ -44,7 +46,7 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         lr_dir, side = a.lr, a.side
         if a.synthetic is not None:
-            lr_dir, side, _ = write_synthetic_sequence(tmp, *a.synthetic, gt=False)
+            lr_dir, side, _ = write_synthetic_sequence(tmp, *a.synthetic, gt=False, markers=a.coding == "RA")
         names = sorted(n for n in os.listdir(lr_dir) if n.lower().endswith(".png"))
         if not names:
             raise FileNotFoundError(f"no PNG frames in {lr_dir}")
@@ -67,12 +69,14 @@ def main():
             rm = np.load(os.path.join(side, "res", i + "_res.npy"))[:, :, 0]
             mv = np.load(os.path.join(side, "mvl1", i + "_mvl1.npy"))
             if s is None:
-                s = LiveSR(model, lr.shape[0], lr.shape[1], chunk=a.chunk, share_compensation=a.share)
-            deliver(s.push(lr, pm, rm, uf, mv))
+                s = LiveSR(model, lr.shape[0], lr.shape[1], chunk=a.chunk, share_compensation=a.share, coding=a.coding)
+            mv0 = np.load(os.path.join(side, "mvl0", i + "_mvl0.npy")) if a.coding == "RA" else None
+            deliver(s.push(lr, pm, rm, uf, mv, mv0))
         deliver(s.close())
         torch.cuda.synchronize()
         total = time.perf_counter() - t0
-    print(f"{len(names)} frames of {s.H}x{s.W} pushed one at a time, chunk {a.chunk}{', shared compensation' if a.share else ''}: "
+    print(f"{len(names)} frames of {s.H}x{s.W} pushed one at a time, chunk {a.chunk}{', shared compensation' if a.share else ''}"
+          f"{', coding RA' if a.coding == 'RA' else ''}: "
           f"{s.fps:.2f} frames/s forward only, {len(names) / total:.2f} frames/s end to end (files read"
           f"{', PNGs written' if a.out else ''}); rings of {s.ring_capacity} frames, {s.resident_bytes / 2 ** 20:.1f} MiB resident, "
           f"torch.cuda.max_memory_allocated {torch.cuda.max_memory_allocated() / 2 ** 20:.1f} MiB")

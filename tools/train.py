@@ -1,7 +1,7 @@
 """Train CVSR_V8 on a clip set resident on the device (cdfo_amd.train.fit; the loop of train_LD_37.py:359-402 and train_RA_37.py):
 
     python tools/train.py --seq LR_DIR SIDE_DIR HR_DIR [--seq ...] --out DIR [--coding LD] [--epochs 30000] [--batch-size 20] [--crop 64]
-                          [--lr 1e-4] [--weight-decay 1e-5] [--val-itv 200] [--val LR_DIR SIDE_DIR GT_DIR] [--weights FILE.pth]
+                          [--lr 1e-4] [--weight-decay 1e-5] [--val-itv 200] [--val LR_DIR SIDE_DIR GT_DIR] [--val-coding LD] [--weights FILE.pth]
     python tools/train.py --synthetic S T H W --out DIR ...
 
 --coding RA trains the random-access configuration: the clip set keeps both motion lists (the mvl1 files beside mvl0) and the flow field
@@ -30,6 +30,8 @@ def main():
     ap.add_argument("--weight-decay", type=float, default=1e-5)
     ap.add_argument("--val-itv", type=int, help="default: 200 (LD), 400 (RA)")
     ap.add_argument("--val", nargs=3, metavar=("LR_DIR", "SIDE_DIR", "GT_DIR"))
+    ap.add_argument("--val-coding", choices=("LD", "RA"), default="LD",
+                    help="the flows of the --val evaluation: LD (the reference's, list 1 alone) or RA (the field --coding RA trains on)")
     ap.add_argument("--weights")
     ap.add_argument("--seed", type=int, default=4)
     a = ap.parse_args()
@@ -57,7 +59,7 @@ def main():
         clips = ClipSet.from_directories(a.seq, coding=a.coding)
     print(f"{clips.coding}: {len(clips)} sequences of {clips.T} frames of {clips.H}x{clips.W} on the device")
     fit(model, clips, a.epochs, a.out, batch_size=a.batch_size, crop=a.crop, lr=a.lr, weight_decay=a.weight_decay, val_itv=a.val_itv,
-        val=a.val, seed=a.seed)
+        val=a.val, seed=a.seed, val_coding=a.val_coding)
 
 
 if __name__ == "__main__":
