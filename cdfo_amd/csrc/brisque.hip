@@ -2,6 +2,7 @@
 // cdfo_amd/metrics.py: brisque_features_u8 makes the seven launches of a chunk and the score from the features on the host).
 //   cdfo_brisque_mscn_u8 / _f64  (x - mu) / (sigma + 1) with the 7 x 7 window over the WHOLE frame, zeros beyond its edge, fp64 out
 //   cdfo_brisque_half            the fixed 8-tap half-size filter on x, rows then columns, the edge sample repeated, ceil(n / 2) outputs
+//   cdfo_brisque_mscn_u16 / cdfo_brisque_half_u16   the two on 16-bit samples of a peak of 1 .. 65535: x = 255 v / peak (metric_sample.h)
 //   cdfo_brisque_sums            per (strip of rows, frame) the thirty moment sums of the five maps, partners circular over the frame
 //   cdfo_brisque_features        the strips added in order, the table searches (one wave each) and the 18 features of one scale
 // The sibling of niqe.hip, which stays as it is: the extent, the padding, the epsilon, the fourth partner and the symmetric fit all
@@ -9,6 +10,7 @@
 // the statement is: the taps in the statement's order, and no contraction of a multiply with the add behind it (the pragma below).
 // All stores are vector stores; there are no atomics.
 #include "common.h"
+#include "metric_sample.h"
 #include "numeric.h"
 
 #pragma clang fp contract(off)
@@ -21,17 +23,18 @@ struct BrisqueWindow { double h[49]; };
 
 constexpr int BQ_TW = 64, BQ_TH = 16;                 // the MSCN tile; its apron is 3 samples each way
 
-// grid (tiles across, tiles down, frame).  T: unsigned char (a frame, read in place) or double (the half image).
-template <typename T>
+// grid (tiles across, tiles down, frame).  T: unsigned char or unsigned short (a frame, read in place; the latter with its peak
+// behind dst) or double (the half image).
+template <typename T, typename... P>
 __global__ __launch_bounds__(256) void brisque_mscn_kernel(const T* __restrict__ src, int pitch, long long fstride, int H, int W,
-                                                           BrisqueWindow win, double* __restrict__ dst) {
+                                                           BrisqueWindow win, double* __restrict__ dst, P... peak) {
   __shared__ double t[BQ_TH + 6][BQ_TW + 6];
   const int n = blockIdx.z, y0 = blockIdx.y * BQ_TH, x0 = blockIdx.x * BQ_TW;
   const T* p = src + (long long)n * fstride;
   for (int i = threadIdx.x; i < (BQ_TH + 6) * (BQ_TW + 6); i += 256) {
     const int r = i / (BQ_TW + 6), c = i - r * (BQ_TW + 6);
     const int y = y0 + r - 3, x = x0 + c - 3;
-    t[r][c] = (y >= 0 && y < H && x >= 0 && x < W) ? (double)p[y * pitch + x] : 0.0;      // zeros beyond the FRAME
+    t[r][c] = (y >= 0 && y < H && x >= 0 && x < W) ? metric_sample(p[y * pitch + x], peak...) : 0.0;      // zeros beyond the FRAME
   }
   __syncthreads();
   double* out = dst + (long long)n * H * W;
@@ -59,18 +62,19 @@ __device__ __forceinline__ int brisque_mirror(int i, int n) {   // [a,b,c] -> [c
   return i < 0 ? 0 : i > n - 1 ? n - 1 : i;
 }
 
-// grid (tiles across, tiles down, frame) over the ceil(H/2) x ceil(W/2) outputs
-__global__ __launch_bounds__(256) void brisque_half_kernel(const unsigned char* __restrict__ src, int pitch, long long fstride, int H, int W,
-                                                           double* __restrict__ dst) {
+// grid (tiles across, tiles down, frame) over the ceil(H/2) x ceil(W/2) outputs.  T, peak: as brisque_mscn_kernel's.
+template <typename T, typename... P>
+__global__ __launch_bounds__(256) void brisque_half_kernel(const T* __restrict__ src, int pitch, long long fstride, int H, int W,
+                                                           double* __restrict__ dst, P... peak) {
   constexpr int IN = 2 * BQ_HT + 6;
   __shared__ double tin[IN][IN], mid[BQ_HT][IN];
   const double w[8] = {-3.0 / 256, -9.0 / 256, 29.0 / 256, 111.0 / 256, 111.0 / 256, 29.0 / 256, -9.0 / 256, -3.0 / 256};
   const int n = blockIdx.z, oy0 = blockIdx.y * BQ_HT, ox0 = blockIdx.x * BQ_HT;
-  const unsigned char* p = src + (long long)n * fstride;
+  const T* p = src + (long long)n * fstride;
   for (int i = threadIdx.x; i < IN * IN; i += 256) {
     const int r = i / IN, c = i - r * IN;
     const int y = brisque_mirror(2 * oy0 - 3 + r, H), x = brisque_mirror(2 * ox0 - 3 + c, W);
-    tin[r][c] = (double)p[y * pitch + x];
+    tin[r][c] = metric_sample(p[y * pitch + x], peak...);
   }
   __syncthreads();
   for (int i = threadIdx.x; i < BQ_HT * IN; i += 256) {   // rows first: output row r of inputs 2r-3 .. 2r+4
@@ -181,8 +185,9 @@ __global__ __launch_bounds__(320) void brisque_features_kernel(const double* __r
   }
 }
 
-template <typename T>
-int brisque_mscn(const T* src, int pitch, long long fstride, int K, int H, int W, const double* window, double* dst, void* stream) {
+// peak: empty, or the peak of 16-bit samples, checked by the entry point
+template <typename T, typename... P>
+int brisque_mscn(const T* src, int pitch, long long fstride, int K, int H, int W, const double* window, double* dst, void* stream, P... peak) {
   if (!src || !window || !dst || K <= 0 || K > 65535 || H <= 0 || W <= 0 || pitch < W || fstride < 0) return CDFO_EINVAL;
   if (!fits32(H, pitch) || !fits32(H, W) || cdiv(H, BQ_TH) > 65535) return CDFO_EINVAL;        // 32-bit offsets inside a frame
   if ((reinterpret_cast<uintptr_t>(dst) & 7u) || (reinterpret_cast<uintptr_t>(src) & (sizeof(T) - 1))) return CDFO_EALIGN;
@@ -190,8 +195,21 @@ int brisque_mscn(const T* src, int pitch, long long fstride, int K, int H, int W
   for (int i = 0; i < 49; ++i) win.h[i] = window[i];
   hipStream_t st = static_cast<hipStream_t>(stream);
   CdfoProfScope prof(st, KID_LAYOUT, 5.0 * 49 * K * (double)H * W, (sizeof(T) + 8.0) * K * (double)H * W);
-  hipLaunchKernelGGL(brisque_mscn_kernel<T>, dim3((unsigned)cdiv(W, BQ_TW), (unsigned)cdiv(H, BQ_TH), (unsigned)K), dim3(256), 0, st, src,
-                     pitch, fstride, H, W, win, dst);
+  hipLaunchKernelGGL((brisque_mscn_kernel<T, P...>), dim3((unsigned)cdiv(W, BQ_TW), (unsigned)cdiv(H, BQ_TH), (unsigned)K), dim3(256), 0, st, src,
+                     pitch, fstride, H, W, win, dst, peak...);
+  CDFO_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T, typename... P>
+int brisque_half(const T* src, int pitch, long long fstride, int K, int H, int W, double* dst, void* stream, P... peak) {
+  if (!src || !dst || K <= 0 || K > 65535 || H < 8 || W < 8 || pitch < W || fstride < 0) return CDFO_EINVAL;
+  if (!fits32(H, pitch) || cdiv((H + 1) / 2, BQ_HT) > 65535) return CDFO_EINVAL;               // 32-bit offsets inside a frame
+  if ((reinterpret_cast<uintptr_t>(dst) & 7u) || (reinterpret_cast<uintptr_t>(src) & (sizeof(T) - 1))) return CDFO_EALIGN;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  CdfoProfScope prof(st, KID_LAYOUT, 2.0 * 8 * K * 0.75 * H * W, K * (double)H * W * (2.0 + sizeof(T)));
+  hipLaunchKernelGGL((brisque_half_kernel<T, P...>), dim3((unsigned)cdiv((W + 1) / 2, BQ_HT), (unsigned)cdiv((H + 1) / 2, BQ_HT), (unsigned)K),
+                     dim3(256), 0, st, src, pitch, fstride, H, W, dst, peak...);
   CDFO_LAUNCH_CHECK();
   return 0;
 }
@@ -208,16 +226,20 @@ extern "C" int cdfo_brisque_mscn_f64(const double* src, int pitch, long long fst
   return brisque_mscn<double>(src, pitch, fstride, K, H, W, window, dst, stream);
 }
 
+extern "C" int cdfo_brisque_mscn_u16(const unsigned short* src, int pitch, long long fstride, int K, int H, int W, const double* window,
+                                     double* dst, int peak, void* stream) {
+  if (peak < 1 || peak > 65535) return CDFO_EINVAL;
+  return brisque_mscn<unsigned short>(src, pitch, fstride, K, H, W, window, dst, stream, (double)peak);
+}
+
 extern "C" int cdfo_brisque_half(const unsigned char* src, int pitch, long long fstride, int K, int H, int W, double* dst, void* stream) {
-  if (!src || !dst || K <= 0 || K > 65535 || H < 8 || W < 8 || pitch < W || fstride < 0) return CDFO_EINVAL;
-  if (!fits32(H, pitch) || cdiv((H + 1) / 2, BQ_HT) > 65535) return CDFO_EINVAL;               // 32-bit offsets inside a frame
-  if (reinterpret_cast<uintptr_t>(dst) & 7u) return CDFO_EALIGN;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  CdfoProfScope prof(st, KID_LAYOUT, 2.0 * 8 * K * 0.75 * H * W, K * (double)H * W * 3.0);
-  hipLaunchKernelGGL(brisque_half_kernel, dim3((unsigned)cdiv((W + 1) / 2, BQ_HT), (unsigned)cdiv((H + 1) / 2, BQ_HT), (unsigned)K), dim3(256),
-                     0, st, src, pitch, fstride, H, W, dst);
-  CDFO_LAUNCH_CHECK();
-  return 0;
+  return brisque_half<unsigned char>(src, pitch, fstride, K, H, W, dst, stream);
+}
+
+extern "C" int cdfo_brisque_half_u16(const unsigned short* src, int pitch, long long fstride, int K, int H, int W, double* dst, int peak,
+                                     void* stream) {
+  if (peak < 1 || peak > 65535) return CDFO_EINVAL;
+  return brisque_half<unsigned short>(src, pitch, fstride, K, H, W, dst, stream, (double)peak);
 }
 
 extern "C" int cdfo_brisque_sums(const double* mscn, int K, int H, int W, double* partials, void* stream) {

@@ -3,6 +3,7 @@
 // launches together).
 //   cdfo_lpips_stem_u8   8-bit luma read in place -> ReLU(conv1_1) as NHWC fp32: the scaling to three channels, the zero padding of
 //                        the SCALED tensor and the 27-tap convolution in one pass, halo tile and weights through LDS
+//   cdfo_lpips_stem_u16  the same of 16-bit luma of a peak of 1 .. 65535: v / peak where the 8-bit form has v / 255
 //   cdfo_lpips_pool2     NHWC fp32 2 x 2 / 2 maximum with floor, 16 bytes per lane, bit-exact
 //   cdfo_lpips_dist      two NHWC fp32 stacks and lin [C] -> fp64 partial sums per (frame, strip of rows): lanes over a pixel's
 //                        channels, the two norms and the weighted squared differences reduced by a butterfly of fixed order
@@ -11,6 +12,7 @@
 // depend on the shapes alone and nothing is atomic: equal inputs give equal bits, d(a, a) is exactly 0 and d(a, b) has the bits of
 // d(b, a) (both norms are formed the same way and (x - y)^2 = (y - x)^2 exactly).  All stores are vector stores.
 #include "common.h"
+#include "metric_sample.h"
 
 namespace {
 
@@ -23,21 +25,23 @@ constexpr int LP_HALO = LP_T + 2;
 // A sample v becomes x = v / 255 (normalize: 2 x - 1), then channel c = (x - shift_c) / scale_c; beyond the region the SCALED tensor
 // is zero.  Item i of a tile is (pixel i / (C0 / 4), channel quad i % (C0 / 4)): neighbouring lanes hold neighbouring quads of one
 // pixel, so a wave's stores are contiguous runs of a pixel's channels and its halo reads are broadcasts.
-__global__ __launch_bounds__(256) void lpips_stem_kernel(const unsigned char* __restrict__ src, int pitch, long long fstride, int h, int w,
+// T: unsigned char, or unsigned short with the samples' peak behind dst: x = v / peak (metric_sample.h).
+template <typename T, typename... P>
+__global__ __launch_bounds__(256) void lpips_stem_kernel(const T* __restrict__ src, int pitch, long long fstride, int h, int w,
                                                          const float* __restrict__ weight, const float* __restrict__ bias, int C0,
-                                                         int normalize, float* __restrict__ dst) {
+                                                         int normalize, float* __restrict__ dst, P... peak) {
   extern __shared__ __attribute__((aligned(16))) float lp_smem[];
   float* sIn = lp_smem;                                 // [3][LP_HALO][LP_HALO], padded to a multiple of 4 floats
   float* sW = lp_smem + 3 * LP_HALO * LP_HALO;          // [27][C0]  (3 * 18 * 18 = 972 floats: 16-byte aligned)
   float* sB = sW + 27 * C0;
   const int n = blockIdx.z, y0 = blockIdx.y * LP_T, x0 = blockIdx.x * LP_T;
-  const unsigned char* p = src + (long long)n * fstride;
+  const T* p = src + (long long)n * fstride;
   const float shift[3] = {-.030f, -.088f, -.188f}, scale[3] = {.458f, .448f, .450f};
   for (int i = threadIdx.x; i < LP_HALO * LP_HALO; i += 256) {
     const int r = i / LP_HALO, c = i - r * LP_HALO;
     const int y = y0 + r - 1, x = x0 + c - 1;
     const bool inside = y >= 0 && y < h && x >= 0 && x < w;
-    float v = inside ? (float)p[y * pitch + x] / 255.f : 0.f;
+    float v = inside ? unit_sample(p[y * pitch + x], peak...) : 0.f;
     if (normalize) v = 2.f * v - 1.f;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) sIn[ch * LP_HALO * LP_HALO + i] = inside ? (v - shift[ch]) / scale[ch] : 0.f;
@@ -198,22 +202,36 @@ __global__ __launch_bounds__(64) void lpips_fold_kernel(const double* __restrict
   out[i] = t / f.count[k];
 }
 
-}  // namespace
-
-extern "C" int cdfo_lpips_stem_u8(const unsigned char* src, int pitch, long long fstride, int N, int h, int w, const float* weight,
-                                  const float* bias, int C0, int normalize, float* dst, void* stream) {
+// peak: empty, or the peak of 16-bit samples, checked by the entry point
+template <typename T, typename... P>
+int lpips_stem(const T* src, int pitch, long long fstride, int N, int h, int w, const float* weight, const float* bias, int C0, int normalize,
+               float* dst, void* stream, P... peak) {
   if (!src || !weight || !bias || !dst || N <= 0 || N > 65535 || h <= 0 || w <= 0 || pitch < w || fstride < 0) return CDFO_EINVAL;
   if (C0 <= 0 || C0 % 16 || C0 > CDFO_LPIPS_STEM_MAXC) return CDFO_EINVAL;
   if (!fits32(h, pitch) || cdiv(h, LP_T) > 65535) return CDFO_EINVAL;                          // 32-bit offsets inside a frame
   if (!aligned16(dst) || (reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(bias)) & 3u) return CDFO_EALIGN;
+  if (reinterpret_cast<uintptr_t>(src) & (sizeof(T) - 1)) return CDFO_EALIGN;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const double px = (double)N * h * w;
-  CdfoProfScope prof(st, KID_LAYOUT, 2.0 * 27 * C0 * px, (1.0 + 4.0 * C0) * px);
+  CdfoProfScope prof(st, KID_LAYOUT, 2.0 * 27 * C0 * px, (sizeof(T) + 4.0 * C0) * px);
   const int lds = (3 * LP_HALO * LP_HALO + 28 * C0) * (int)sizeof(float);
-  hipLaunchKernelGGL(lpips_stem_kernel, dim3((unsigned)cdiv(w, LP_T), (unsigned)cdiv(h, LP_T), (unsigned)N), dim3(256), lds, st, src, pitch,
-                     fstride, h, w, weight, bias, C0, normalize ? 1 : 0, dst);
+  hipLaunchKernelGGL((lpips_stem_kernel<T, P...>), dim3((unsigned)cdiv(w, LP_T), (unsigned)cdiv(h, LP_T), (unsigned)N), dim3(256), lds, st, src,
+                     pitch, fstride, h, w, weight, bias, C0, normalize ? 1 : 0, dst, peak...);
   CDFO_LAUNCH_CHECK();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int cdfo_lpips_stem_u8(const unsigned char* src, int pitch, long long fstride, int N, int h, int w, const float* weight,
+                                  const float* bias, int C0, int normalize, float* dst, void* stream) {
+  return lpips_stem<unsigned char>(src, pitch, fstride, N, h, w, weight, bias, C0, normalize, dst, stream);
+}
+
+extern "C" int cdfo_lpips_stem_u16(const unsigned short* src, int pitch, long long fstride, int N, int h, int w, const float* weight,
+                                   const float* bias, int C0, int normalize, float* dst, int peak, void* stream) {
+  if (peak < 1 || peak > 65535) return CDFO_EINVAL;
+  return lpips_stem<unsigned short>(src, pitch, fstride, N, h, w, weight, bias, C0, normalize, dst, stream, (float)peak);
 }
 
 extern "C" int cdfo_lpips_pool2(const float* src, int N, int H, int W, int C, float* dst, void* stream) {

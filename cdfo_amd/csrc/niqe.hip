@@ -2,12 +2,14 @@
 // cdfo_amd/metrics.py: niqe_features_u8 makes the seven launches of a chunk and the score from the features on the host).
 //   cdfo_niqe_mscn_u8 / _f64   (x - mu) / (sigma + 1) with the 7 x 7 window, replicate padding at the edge of the region, fp64 out
 //   cdfo_niqe_half             the fixed 8-tap half-size filter on x / 255, rows then columns, the edge sample repeated, * 255
+//   cdfo_niqe_mscn_u16 / cdfo_niqe_half_u16   the two on 16-bit samples of a peak of 1 .. 65535: x = 255 v / peak (metric_sample.h)
 //   cdfo_niqe_block_sums       per (frame, block) the thirty moment sums of the five maps, in a fixed order
 //   cdfo_niqe_features         the table search (one wave each) and the 18 features of one scale
 // Everything is fp64 and written the way the statement is: the taps in the statement's order, and no contraction of a multiply with
 // the add behind it (the pragma below), so the maps differ from numpy's by the library functions' last bits only.  All stores are
 // vector stores.
 #include "common.h"
+#include "metric_sample.h"
 #include "numeric.h"
 
 #pragma clang fp contract(off)
@@ -20,10 +22,11 @@ struct NiqeWindow { double h[49]; };
 
 constexpr int NQ_TW = 64, NQ_TH = 16;                 // the MSCN tile; its apron is 3 samples each way
 
-// grid (tiles across, tiles down, frame).  T: unsigned char (a frame, read in place) or double (the half image).
-template <typename T>
+// grid (tiles across, tiles down, frame).  T: unsigned char or unsigned short (a frame, read in place; the latter with its peak
+// behind dst) or double (the half image).
+template <typename T, typename... P>
 __global__ __launch_bounds__(256) void niqe_mscn_kernel(const T* __restrict__ src, int pitch, long long fstride, int R, int C,
-                                                        NiqeWindow win, double* __restrict__ dst) {
+                                                        NiqeWindow win, double* __restrict__ dst, P... peak) {
   __shared__ double t[NQ_TH + 6][NQ_TW + 6];
   const int n = blockIdx.z, y0 = blockIdx.y * NQ_TH, x0 = blockIdx.x * NQ_TW;
   const T* p = src + (long long)n * fstride;
@@ -32,7 +35,7 @@ __global__ __launch_bounds__(256) void niqe_mscn_kernel(const T* __restrict__ sr
     int y = y0 + r - 3, x = x0 + c - 3;
     y = y < 0 ? 0 : y > R - 1 ? R - 1 : y;               // the edge of the REGION, not of the frame
     x = x < 0 ? 0 : x > C - 1 ? C - 1 : x;
-    t[r][c] = (double)p[y * pitch + x];
+    t[r][c] = metric_sample(p[y * pitch + x], peak...);
   }
   __syncthreads();
   double* out = dst + (long long)n * R * C;
@@ -60,18 +63,19 @@ __device__ __forceinline__ int niqe_mirror(int i, int n) {   // [a,b,c] -> [c,b,
   return i < 0 ? 0 : i > n - 1 ? n - 1 : i;
 }
 
-// grid (tiles across, tiles down, frame) over the R/2 x C/2 outputs
-__global__ __launch_bounds__(256) void niqe_half_kernel(const unsigned char* __restrict__ src, int pitch, long long fstride, int R, int C,
-                                                        double* __restrict__ dst) {
+// grid (tiles across, tiles down, frame) over the R/2 x C/2 outputs.  T, peak: as niqe_mscn_kernel's.
+template <typename T, typename... P>
+__global__ __launch_bounds__(256) void niqe_half_kernel(const T* __restrict__ src, int pitch, long long fstride, int R, int C,
+                                                        double* __restrict__ dst, P... peak) {
   constexpr int IN = 2 * NQ_HT + 6;
   __shared__ double tin[IN][IN], mid[NQ_HT][IN];
   const double w[8] = {-3.0 / 256, -9.0 / 256, 29.0 / 256, 111.0 / 256, 111.0 / 256, 29.0 / 256, -9.0 / 256, -3.0 / 256};
   const int n = blockIdx.z, oy0 = blockIdx.y * NQ_HT, ox0 = blockIdx.x * NQ_HT;
-  const unsigned char* p = src + (long long)n * fstride;
+  const T* p = src + (long long)n * fstride;
   for (int i = threadIdx.x; i < IN * IN; i += 256) {
     const int r = i / IN, c = i - r * IN;
     const int y = niqe_mirror(2 * oy0 - 3 + r, R), x = niqe_mirror(2 * ox0 - 3 + c, C);
-    tin[r][c] = (double)p[y * pitch + x] / 255.0;
+    tin[r][c] = metric_sample(p[y * pitch + x], peak...) / 255.0;
   }
   __syncthreads();
   for (int i = threadIdx.x; i < NQ_HT * IN; i += 256) {   // rows first: output row r of inputs 2r-3 .. 2r+4
@@ -174,8 +178,9 @@ __global__ __launch_bounds__(320) void niqe_features_kernel(const double* __rest
   }
 }
 
-template <typename T>
-int niqe_mscn(const T* src, int pitch, long long fstride, int K, int R, int C, const double* window, double* dst, void* stream) {
+// peak: empty, or the peak of 16-bit samples, checked by the entry point
+template <typename T, typename... P>
+int niqe_mscn(const T* src, int pitch, long long fstride, int K, int R, int C, const double* window, double* dst, void* stream, P... peak) {
   if (!src || !window || !dst || K <= 0 || K > 65535 || R <= 0 || C <= 0 || pitch < C || fstride < 0) return CDFO_EINVAL;
   if (!fits32(R, pitch) || !fits32(R, C) || cdiv(R, NQ_TH) > 65535) return CDFO_EINVAL;        // 32-bit offsets inside a frame
   if ((reinterpret_cast<uintptr_t>(dst) & 7u) || (reinterpret_cast<uintptr_t>(src) & (sizeof(T) - 1))) return CDFO_EALIGN;
@@ -183,8 +188,21 @@ int niqe_mscn(const T* src, int pitch, long long fstride, int K, int R, int C, c
   for (int i = 0; i < 49; ++i) win.h[i] = window[i];
   hipStream_t st = static_cast<hipStream_t>(stream);
   CdfoProfScope prof(st, KID_LAYOUT, 5.0 * 49 * K * (double)R * C, (sizeof(T) + 8.0) * K * (double)R * C);
-  hipLaunchKernelGGL(niqe_mscn_kernel<T>, dim3((unsigned)cdiv(C, NQ_TW), (unsigned)cdiv(R, NQ_TH), (unsigned)K), dim3(256), 0, st, src, pitch,
-                     fstride, R, C, win, dst);
+  hipLaunchKernelGGL((niqe_mscn_kernel<T, P...>), dim3((unsigned)cdiv(C, NQ_TW), (unsigned)cdiv(R, NQ_TH), (unsigned)K), dim3(256), 0, st, src, pitch,
+                     fstride, R, C, win, dst, peak...);
+  CDFO_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T, typename... P>
+int niqe_half(const T* src, int pitch, long long fstride, int K, int R, int C, double* dst, void* stream, P... peak) {
+  if (!src || !dst || K <= 0 || K > 65535 || R < 8 || C < 8 || (R & 1) || (C & 1) || pitch < C || fstride < 0) return CDFO_EINVAL;
+  if (!fits32(R, pitch) || cdiv(R / 2, NQ_HT) > 65535) return CDFO_EINVAL;                     // 32-bit offsets inside a frame
+  if ((reinterpret_cast<uintptr_t>(dst) & 7u) || (reinterpret_cast<uintptr_t>(src) & (sizeof(T) - 1))) return CDFO_EALIGN;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  CdfoProfScope prof(st, KID_LAYOUT, 2.0 * 8 * K * 0.75 * R * C, K * (double)R * C * (2.0 + sizeof(T)));
+  hipLaunchKernelGGL((niqe_half_kernel<T, P...>), dim3((unsigned)cdiv(C / 2, NQ_HT), (unsigned)cdiv(R / 2, NQ_HT), (unsigned)K), dim3(256), 0, st,
+                     src, pitch, fstride, R, C, dst, peak...);
   CDFO_LAUNCH_CHECK();
   return 0;
 }
@@ -201,16 +219,20 @@ extern "C" int cdfo_niqe_mscn_f64(const double* src, int pitch, long long fstrid
   return niqe_mscn<double>(src, pitch, fstride, K, R, C, window, dst, stream);
 }
 
+extern "C" int cdfo_niqe_mscn_u16(const unsigned short* src, int pitch, long long fstride, int K, int R, int C, const double* window,
+                                  double* dst, int peak, void* stream) {
+  if (peak < 1 || peak > 65535) return CDFO_EINVAL;
+  return niqe_mscn<unsigned short>(src, pitch, fstride, K, R, C, window, dst, stream, (double)peak);
+}
+
 extern "C" int cdfo_niqe_half(const unsigned char* src, int pitch, long long fstride, int K, int R, int C, double* dst, void* stream) {
-  if (!src || !dst || K <= 0 || K > 65535 || R < 8 || C < 8 || (R & 1) || (C & 1) || pitch < C || fstride < 0) return CDFO_EINVAL;
-  if (!fits32(R, pitch) || cdiv(R / 2, NQ_HT) > 65535) return CDFO_EINVAL;                     // 32-bit offsets inside a frame
-  if (reinterpret_cast<uintptr_t>(dst) & 7u) return CDFO_EALIGN;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  CdfoProfScope prof(st, KID_LAYOUT, 2.0 * 8 * K * 0.75 * R * C, K * (double)R * C * 3.0);
-  hipLaunchKernelGGL(niqe_half_kernel, dim3((unsigned)cdiv(C / 2, NQ_HT), (unsigned)cdiv(R / 2, NQ_HT), (unsigned)K), dim3(256), 0, st, src,
-                     pitch, fstride, R, C, dst);
-  CDFO_LAUNCH_CHECK();
-  return 0;
+  return niqe_half<unsigned char>(src, pitch, fstride, K, R, C, dst, stream);
+}
+
+extern "C" int cdfo_niqe_half_u16(const unsigned short* src, int pitch, long long fstride, int K, int R, int C, double* dst, int peak,
+                                  void* stream) {
+  if (peak < 1 || peak > 65535) return CDFO_EINVAL;
+  return niqe_half<unsigned short>(src, pitch, fstride, K, R, C, dst, stream, (double)peak);
 }
 
 extern "C" int cdfo_niqe_block_sums(const double* mscn, int K, int R, int C, int B, double* sums, void* stream) {

@@ -1,6 +1,7 @@
 // tOF's dense Farneback flow of 8-bit luma pairs on the device (DESIGN.md has the definition, tests/tof_ref.py its numpy statement;
 // cdfo_amd/metrics.py: farneback_u8 / tof_frames_u8 make the launches of a chunk, stage by stage).  Pairs are the batch dimension:
 //   cdfo_tof_level_u8    u8 frames -> the fp64 level images of every pair (prev, cur): stage smoothing and bilinear resize fused
+//   cdfo_tof_level_u16   the same of 16-bit frames of a peak of 1 .. 65535: x = 255 v / peak (metric_sample.h)
 //   cdfo_tof_polyexp     level images -> the five coefficient planes (b_x, b_y, a_xx, a_yy, a_xy): both 11-tap passes through LDS
 //   cdfo_tof_matrices    both expansions and the flow -> the five planes of the normal equations (the gather, the border factors)
 //   cdfo_tof_blur_solve  15 x 15 box mean through LDS, plane by plane, then the 2 x 2 solve: the new flow
@@ -12,6 +13,7 @@
 // the last place per stage and 2e-15 px in a solved flow (DESIGN.md has the measurements).  Grids depend on the shapes alone, all
 // stores are vector stores and there are no atomics: equal frames give equal bits.
 #include "common.h"
+#include "metric_sample.h"
 
 #pragma clang fp contract(off)
 
@@ -30,15 +32,16 @@ __device__ __forceinline__ int tof_reflect101(int i, int n) {          // dcb|ab
 }
 __device__ __forceinline__ int tof_clamp(int i, int n) { return i < 0 ? 0 : i > n - 1 ? n - 1 : i; }
 
-// the smoothed sample at (yc, xc): down the columns first, then along the row
-__device__ __forceinline__ double tof_smooth(const unsigned char* __restrict__ p, int pitch, int H, int W, int yc, int xc,
-                                             const TofTaps& taps, int n) {
+// the smoothed sample at (yc, xc): down the columns first, then along the row.  T, peak: as tof_level_kernel's.
+template <typename T, typename... P>
+__device__ __forceinline__ double tof_smooth(const T* __restrict__ p, int pitch, int H, int W, int yc, int xc, const TofTaps& taps, int n,
+                                             P... peak) {
   const int r = (n - 1) >> 1;
   double s = 0.0;
   for (int j = 0; j < n; ++j) {
     const int x = tof_reflect101(xc + j - r, W);
     double col = 0.0;
-    for (int i = 0; i < n; ++i) col = col + taps.t[i] * (double)p[tof_reflect101(yc + i - r, H) * pitch + x];
+    for (int i = 0; i < n; ++i) col = col + taps.t[i] * metric_sample(p[tof_reflect101(yc + i - r, H) * pitch + x], peak...);
     s = s + taps.t[j] * col;
   }
   return s;
@@ -56,14 +59,16 @@ __device__ __forceinline__ void tof_resize_at(int i, int N, int n, int& i0, int&
 
 // grid (tiles of 64 across, tiles of 4 down, 2 K): z = 2 pair + slot, slot 0 the pair's previous frame, 1 its current one.
 // dst [K][2][h][w].  A weight of exactly 0 (always at h == H, w == W) drops its second sample: (1 - 0) a + 0 b == a.
-__global__ __launch_bounds__(256) void tof_level_kernel(const unsigned char* __restrict__ prev, int ppitch, long long pstride,
-                                                        const unsigned char* __restrict__ cur, int cpitch, long long cstride,
-                                                        const unsigned char* __restrict__ first, int fpitch, int H, int W, int h,
-                                                        int w, TofTaps taps, int n, double* __restrict__ dst) {
+// T: unsigned char, or unsigned short with the samples' peak behind dst (metric_sample.h).
+template <typename T, typename... P>
+__global__ __launch_bounds__(256) void tof_level_kernel(const T* __restrict__ prev, int ppitch, long long pstride,
+                                                        const T* __restrict__ cur, int cpitch, long long cstride,
+                                                        const T* __restrict__ first, int fpitch, int H, int W, int h,
+                                                        int w, TofTaps taps, int n, double* __restrict__ dst, P... peak) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= w || y >= h) return;
   const int pair = blockIdx.z >> 1, slot = blockIdx.z & 1;
-  const unsigned char* p;
+  const T* p;
   int pitch;
   if (slot) {
     p = cur + (long long)pair * cstride;
@@ -80,13 +85,13 @@ __global__ __launch_bounds__(256) void tof_level_kernel(const unsigned char* __r
   tof_resize_at(y, H, h, y0, y1, wy);
   tof_resize_at(x, W, w, x0, x1, wx);
   const bool one_x = wx == 0.0 || x1 == x0;
-  const double s00 = tof_smooth(p, pitch, H, W, y0, x0, taps, n);
-  const double s01 = one_x ? s00 : tof_smooth(p, pitch, H, W, y0, x1, taps, n);
+  const double s00 = tof_smooth(p, pitch, H, W, y0, x0, taps, n, peak...);
+  const double s01 = one_x ? s00 : tof_smooth(p, pitch, H, W, y0, x1, taps, n, peak...);
   const double top = (1.0 - wx) * s00 + wx * s01;
   double bot = top;
   if (!(wy == 0.0 || y1 == y0)) {
-    const double s10 = tof_smooth(p, pitch, H, W, y1, x0, taps, n);
-    const double s11 = one_x ? s10 : tof_smooth(p, pitch, H, W, y1, x1, taps, n);
+    const double s10 = tof_smooth(p, pitch, H, W, y1, x0, taps, n, peak...);
+    const double s11 = one_x ? s10 : tof_smooth(p, pitch, H, W, y1, x1, taps, n, peak...);
     bot = (1.0 - wx) * s10 + wx * s11;
   }
   dst[(long long)blockIdx.z * h * w + y * w + x] = (1.0 - wy) * top + wy * bot;
@@ -303,24 +308,41 @@ __global__ __launch_bounds__(64) void tof_epe_mean_kernel(const double* __restri
   out[blockIdx.x] = s / count;
 }
 
-}  // namespace
-
-extern "C" int cdfo_tof_level_u8(const unsigned char* prev, int ppitch, long long pstride, const unsigned char* cur, int cpitch,
-                                 long long cstride, const unsigned char* first, int fpitch, int K, int H, int W, int h, int w,
-                                 const double* taps, int ntaps, double* dst, void* stream) {
+// peak: empty, or the peak of 16-bit samples, checked by the entry point
+template <typename T, typename... P>
+int tof_level(const T* prev, int ppitch, long long pstride, const T* cur, int cpitch, long long cstride, const T* first, int fpitch, int K,
+              int H, int W, int h, int w, const double* taps, int ntaps, double* dst, void* stream, P... peak) {
   if (!prev || !cur || !taps || !dst || K <= 0 || 2 * (long long)K > 65535 || H < CDFO_TOF_MIN || W < CDFO_TOF_MIN) return CDFO_EINVAL;
   if (h <= 0 || w <= 0 || h > H || w > W || ppitch < W || cpitch < W || (first && fpitch < W) || pstride < 0 || cstride < 0) return CDFO_EINVAL;
   if (ntaps < 3 || ntaps > CDFO_TOF_MAX_TAPS || !(ntaps & 1) || ntaps / 2 >= (H < W ? H : W)) return CDFO_EINVAL;   // one reflection
   if (!fits32(H, ppitch) || !fits32(H, cpitch) || (first && !fits32(H, fpitch)) || !fits32(h, w) || cdiv(h, 4) > 65535) return CDFO_EINVAL;
   if (misaligned8(dst)) return CDFO_EALIGN;
+  if ((reinterpret_cast<uintptr_t>(prev) | reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(first)) & (sizeof(T) - 1))
+    return CDFO_EALIGN;
   TofTaps t;
   for (int i = 0; i < CDFO_TOF_MAX_TAPS; ++i) t.t[i] = i < ntaps ? taps[i] : 0.0;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  CdfoProfScope prof(st, KID_LAYOUT, 8.0 * ntaps * ntaps * K * (double)h * w, 2.0 * K * ((double)H * W + 8.0 * h * w));
-  hipLaunchKernelGGL(tof_level_kernel, dim3((unsigned)cdiv(w, 64), (unsigned)cdiv(h, 4), (unsigned)(2 * K)), dim3(256), 0, st, prev, ppitch,
-                     pstride, cur, cpitch, cstride, first, fpitch, H, W, h, w, t, ntaps, dst);
+  CdfoProfScope prof(st, KID_LAYOUT, 8.0 * ntaps * ntaps * K * (double)h * w, 2.0 * K * (sizeof(T) * (double)H * W + 8.0 * h * w));
+  hipLaunchKernelGGL((tof_level_kernel<T, P...>), dim3((unsigned)cdiv(w, 64), (unsigned)cdiv(h, 4), (unsigned)(2 * K)), dim3(256), 0, st, prev,
+                     ppitch, pstride, cur, cpitch, cstride, first, fpitch, H, W, h, w, t, ntaps, dst, peak...);
   CDFO_LAUNCH_CHECK();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int cdfo_tof_level_u8(const unsigned char* prev, int ppitch, long long pstride, const unsigned char* cur, int cpitch,
+                                 long long cstride, const unsigned char* first, int fpitch, int K, int H, int W, int h, int w,
+                                 const double* taps, int ntaps, double* dst, void* stream) {
+  return tof_level<unsigned char>(prev, ppitch, pstride, cur, cpitch, cstride, first, fpitch, K, H, W, h, w, taps, ntaps, dst, stream);
+}
+
+extern "C" int cdfo_tof_level_u16(const unsigned short* prev, int ppitch, long long pstride, const unsigned short* cur, int cpitch,
+                                  long long cstride, const unsigned short* first, int fpitch, int K, int H, int W, int h, int w,
+                                  const double* taps, int ntaps, double* dst, int peak, void* stream) {
+  if (peak < 1 || peak > 65535) return CDFO_EINVAL;
+  return tof_level<unsigned short>(prev, ppitch, pstride, cur, cpitch, cstride, first, fpitch, K, H, W, h, w, taps, ntaps, dst, stream,
+                                   (double)peak);
 }
 
 extern "C" int cdfo_tof_polyexp(const double* img, int N, int h, int w, const double* kernels, double* R, void* stream) {

@@ -33,6 +33,9 @@ Farneback flows of the chunk's ground-truth pairs and result pairs go through th
 (`metrics.tof_frames_u8`), the frame in front of the chunk carried on the device.  ``lpips=`` a
 model adds LPIPS, the learned perceptual distance to the ground truth, on 8-bit luma (`metrics.lpips_layers_u8`, DESIGN.md section
 5.0000000000000000): a VGG-shaped trunk in fp32 behind tOF's launches, five layer values per frame kept on the device until the last chunk.
+Above 8 bits those four are a ValueError unless ``evaluate_yuv(..., rescale_metrics=True)``: then the same launches run on the uint16
+luma with the format's peak, a sample v read as 255 v / peak (LPIPS: v / peak), the ``metrics.*_u16`` forms (DESIGN.md section
+5.000000000000000000).
 
 Deliberate deviation: ``cal_psnr_ssim`` sends single-channel frames through ``to_y_channel``, an fp32 ``/255*255`` round
 trip, and takes fp32 means.  The metric semantics here are the project's established ones, ``oracle/metrics_ref.py``: fp64 on the
@@ -160,13 +163,14 @@ def _check_msssim(lr, gt, crop_border: int) -> None:
     M.msssim_region(4 * lr.shape[0], 4 * lr.shape[1], *gt.shape, crop_border)
 
 
-def _check_niqe(lr, niqe):
+def _check_niqe(lr, niqe, rescale_metrics: bool = False):
     """The pristine model of a ``niqe=`` argument (None: the metric is off), before any device work: `metrics.niqe_params`' checks;
-    ValueError above 8 bits (the reference defines the metric on 0 .. 255 integers) and for x4 frames below one 96 x 96 block."""
+    ValueError above 8 bits (the reference defines the metric on 0 .. 255 integers) and for x4 frames below one 96 x 96 block.
+    ``rescale_metrics``: no error above 8 bits, where the loop then runs the metric's 16-bit form (`evaluate_yuv`)."""
     if niqe is None:
         return None
     params = niqe if isinstance(niqe, M.NiqeParams) else M.niqe_params(niqe)
-    if lr.dtype != torch.uint8:
+    if lr.dtype != torch.uint8 and not rescale_metrics:
         raise ValueError(f"niqe: the metric is defined on 8-bit samples, the format's peak is {lr.peak}")
     M.niqe_region(4 * lr.shape[0], 4 * lr.shape[1])
     return params
@@ -177,13 +181,14 @@ def _niqe(features: np.ndarray, params) -> np.ndarray:
     return np.atleast_1d(M.niqe_from_features(features, params)) if len(features) else np.zeros(0, np.float64)
 
 
-def _check_brisque(lr, brisque):
+def _check_brisque(lr, brisque, rescale_metrics: bool = False):
     """The model of a ``brisque=`` argument (None: the metric is off), before any device work: `metrics.brisque_params`' checks;
-    ValueError above 8 bits (the reference defines the metric on 0 .. 255 integers) and for x4 frames below 16 x 16."""
+    ValueError above 8 bits (the reference defines the metric on 0 .. 255 integers) and for x4 frames below 16 x 16.
+    ``rescale_metrics``: as `_check_niqe`'s."""
     if brisque is None:
         return None
     params = brisque if isinstance(brisque, M.BrisqueParams) else M.brisque_params(brisque)
-    if lr.dtype != torch.uint8:
+    if lr.dtype != torch.uint8 and not rescale_metrics:
         raise ValueError(f"brisque: the metric is defined on 8-bit samples, the format's peak is {lr.peak}")
     M.brisque_size(4 * lr.shape[0], 4 * lr.shape[1])
     return params
@@ -194,27 +199,28 @@ def _brisque(features: np.ndarray, params) -> np.ndarray:
     return np.atleast_1d(M.brisque_from_features(features, params)) if len(features) else np.zeros(0, np.float64)
 
 
-def _check_tof(lr, gt, tof) -> bool:
+def _check_tof(lr, gt, tof, rescale_metrics: bool = False) -> bool:
     """Whether tOF runs, before any device work: ValueError without ground truth, above 8 bits (the reference computes the flow of
-    8-bit images) and for a common region below 32 x 32 (`metrics.tof_size`)."""
+    8-bit images) and for a common region below 32 x 32 (`metrics.tof_size`).  ``rescale_metrics``: as `_check_niqe`'s."""
     if not tof:
         return False
     if gt is None:
         raise ValueError("tof: the metric compares the result's flow with the ground truth's, and there is no ground truth")
-    if lr.dtype != torch.uint8:
+    if lr.dtype != torch.uint8 and not rescale_metrics:
         raise ValueError(f"tof: the metric is defined on 8-bit samples, the format's peak is {lr.peak}")
     M.tof_size(min(4 * lr.shape[0], gt.shape[0]), min(4 * lr.shape[1], gt.shape[1]))
     return True
 
 
-def _check_lpips(lr, gt, lpips):
+def _check_lpips(lr, gt, lpips, rescale_metrics: bool = False):
     """The model of an ``lpips=`` argument (None: the metric is off), before any device work: `metrics.lpips_params`' checks;
-    ValueError without ground truth, above 8 bits and for a common region below 16 x 16 (`metrics.lpips_size`)."""
+    ValueError without ground truth, above 8 bits and for a common region below 16 x 16 (`metrics.lpips_size`).
+    ``rescale_metrics``: as `_check_niqe`'s."""
     if lpips is None:
         return None
     if gt is None:
         raise ValueError("lpips: the metric is a distance to the ground truth, and there is no ground truth")
-    if lr.dtype != torch.uint8:
+    if lr.dtype != torch.uint8 and not rescale_metrics:
         raise ValueError(f"lpips: the metric is defined on 8-bit samples, the format's peak is {lr.peak}")
     M.lpips_size(min(4 * lr.shape[0], gt.shape[0]), min(4 * lr.shape[1], gt.shape[1]))
     return M.lpips_params(lpips)
@@ -350,8 +356,9 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
     -> (the `StreamingSR`, sse_y int64 [T], sse_uv int64 [2,T], ssim fp64 [T], MS-SSIM components fp64 [T,5,2], NIQE features fp64
     [T,nb,36], BRISQUE features fp64 [T,36], tOF fp64 [T], LPIPS layer values fp64 [T,5]); the arrays are empty without ground truth
     (sse_uv without chroma, the components without ``msssim``, tOF without ``tof``, the layer values without ``lpips``), the features
-    without ``niqe`` / ``brisque``.  The module's docstring has the
-    order of events."""
+    without ``niqe`` / ``brisque``.  Above 8 bits (``lr.dtype`` uint16, which the callers' checks let through with
+    ``rescale_metrics`` only) those four run their ``_u16`` forms with ``lr.peak`` on the same scratch; tOF's carried frames are
+    uint16 then.  The module's docstring has the order of events."""
     T, kmax, kind, peak = lr.frames, min(chunk, lr.frames), lr.dtype, lr.peak
     has_c = lr.chroma_shape is not None
     out_y, out_c = (shape and (4 * shape[0], 4 * shape[1]) for shape in (lr.shape, lr.chroma_shape))      # None stays None
@@ -431,16 +438,19 @@ def _run_chunks(lr, load, gt, sink, chunk: int, share_compensation: bool, crop: 
                     if ms_scratch is not None:
                         ms.append(M.msssim_components(y8, gy, crop, None if kind == torch.uint8 else peak, ms_scratch))
                 if nq_scratch is not None:
-                    nq.append(M.niqe_features_u8(y8, nq_scratch))
+                    nq.append(M.niqe_features_u8(y8, nq_scratch) if kind == torch.uint8 else M.niqe_features_u16(y8, peak, nq_scratch))
                 if bq_scratch is not None:
-                    bq.append(M.brisque_features_u8(y8, bq_scratch))
+                    bq.append(M.brisque_features_u8(y8, bq_scratch) if kind == torch.uint8 else
+                              M.brisque_features_u16(y8, peak, bq_scratch))
                 if tf_scratch is not None:
-                    tf.append(M.tof_frames_u8(gy, y8, tf_gt, tf_sr, tf_scratch))
+                    tf.append(M.tof_frames_u8(gy, y8, tf_gt, tf_sr, tf_scratch) if kind == torch.uint8 else
+                              M.tof_frames_u16(gy, y8, peak, tf_gt, tf_sr, tf_scratch))
                     tf_gt, tf_sr = tf_carry
                     tf_gt.copy_(gy[k - 1])
                     tf_sr.copy_(y8[k - 1])
                 if lp_scratch is not None:
-                    lp.append(M.lpips_layers_u8(y8, gy, lpips, lp_scratch))
+                    lp.append(M.lpips_layers_u8(y8, gy, lpips, lp_scratch) if kind == torch.uint8 else
+                              M.lpips_layers_u16(y8, gy, peak, lpips, lp_scratch))
                 if sink is not None:
                     ready = torch.cuda.Event()
                     ready.record(main)
@@ -467,7 +477,7 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
                       share_compensation: bool = False, crop_border: int = 4, quantise: str = "trunc", workers: int = 8,
                       png_level: int = 6, gumbel_uniform: Optional[Sequence] = None,
                       frame_noise: Optional[Sequence] = None, msssim: bool = False, niqe=None, brisque=None,
-                      tof: bool = False, lpips=None, coding: str = "LD") -> SequenceResult:
+                      tof: bool = False, lpips=None, coding: str = "LD", rescale_metrics: bool = False) -> SequenceResult:
     """Super-resolve the sequence in ``lr_dir`` / ``side_dir`` (the reference's test layout, see cdfo_amd/priors.py) with ``model`` (on a
     GPU), ``chunk`` centre frames per forward.  ``save_dir``: write every frame as an 8-bit PNG under its LR file name.  ``gt_dir``:
     per-frame PSNR / SSIM of the 8-bit frames against ``<gt_dir>/%05d.png`` over the common size less ``crop_border``.
@@ -487,21 +497,22 @@ def evaluate_sequence(model, lr_dir: str, side_dir: str, gt_dir: Optional[str] =
     the project ships no model, and parity with the ``lpips`` package is unpinned); with ground truth every frame's distance to it is
     then reported as well (`metrics.lpips_u8`: VGG-shaped trunk on the luma over the whole common region, lower is better); the
     region must be at least 16 x 16, and without ground truth it is a ValueError.  ``coding``: `StreamingSR`'s ("LD": the reference's
-    flows from list 1; "RA": the random-access field from both lists, for a model trained on it)."""
+    flows from list 1; "RA": the random-access field from both lists, for a model trained on it).  ``rescale_metrics``:
+    `evaluate_yuv`'s, accepted for symmetry: the frames here are 8-bit, where it changes nothing."""
     workers, chunk = _check_args(workers, quantise, chunk)
     check_coding(coding)
     t_start = time.perf_counter()
     lr = _PngSource(lr_dir)
-    nq_params = _check_niqe(lr, niqe)
-    bq_params = _check_brisque(lr, brisque)
+    nq_params = _check_niqe(lr, niqe, rescale_metrics)
+    bq_params = _check_brisque(lr, brisque, rescale_metrics)
     gt = sink = None
     if gt_dir is not None:
         gt = _PngSource(gt_dir, ["%05d.png" % t for t in range(lr.frames)])
         _check_regions(lr, gt, crop_border, 0)
         if msssim:
             _check_msssim(lr, gt, crop_border)
-    tof = _check_tof(lr, gt, tof)
-    lp_params = _check_lpips(lr, gt, lpips)
+    tof = _check_tof(lr, gt, tof, rescale_metrics)
+    lp_params = _check_lpips(lr, gt, lpips, rescale_metrics)
     if save_dir is not None:
         sink = _PngSink(save_dir, lr.names, png_level)   # the result PNGs take the LR frames' names (test_LD_37.py:180)
 
@@ -569,7 +580,7 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
                  quantise: str = "trunc", workers: int = 8, gumbel_uniform: Optional[Sequence] = None,
                  frame_noise: Optional[Sequence] = None, gt_size: Optional[Tuple[int, int]] = None,
                  pix_fmt: str = "yuv420p", msssim: bool = False, niqe=None, brisque=None, tof: bool = False,
-                 lpips=None, coding: str = "LD") -> YuvResult:
+                 lpips=None, coding: str = "LD", rescale_metrics: bool = False) -> YuvResult:
     """`evaluate_sequence` on raw 8-bit I420 files (cdfo_amd/yuv.py).  ``lr_yuv``: the LR sequence, ``width`` x ``height`` (even);
     the coding priors stay in ``side_dir``.  The luma goes the way it goes there (`StreamingSR.iter_chunked`, ``finish_frames`` with the
     PSNR numerator, ``ssim_u8``).  The chroma never passes through the model: per chunk the U and V planes of its centre frames are
@@ -587,7 +598,11 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     `evaluate_sequence`'s, on the luma of 8-bit formats; above 8 bits it is a ValueError (the reference defines the metric on 0 .. 255
     integers).  ``brisque``: as `evaluate_sequence`'s, with the same restriction to 8-bit formats.  ``tof``: as `evaluate_sequence`'s, on
     the luma of 8-bit formats with ground truth.  ``lpips``: as `evaluate_sequence`'s, on the luma only, of 8-bit formats with ground
-    truth.  ``coding``: as `evaluate_sequence`'s."""
+    truth.  ``coding``: as `evaluate_sequence`'s.  ``rescale_metrics``: True lifts that restriction of ``niqe``, ``brisque``, ``tof``
+    and ``lpips``: above 8 bits they then run their 16-bit forms on the luma (`metrics.niqe_features_u16`, `brisque_features_u16`,
+    `tof_frames_u16`, `lpips_layers_u16`) with the format's peak, a sample v read as 255 v / peak (LPIPS: v / peak) -- the project's
+    own definition, the reference has none above 8 bits; the size limits, the order of the errors, the result's fields and
+    the log are the 8-bit ones.  On an 8-bit format, and with False (the default) on any, nothing changes."""
     fmt = parse_pix_fmt(pix_fmt)
     check_coding(coding)
     workers, chunk = _check_args(workers, quantise, chunk)
@@ -595,8 +610,8 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
     ccrop = chroma_crop(crop_border, fmt.chroma)
     with YuvReader(lr_yuv, width, height, fmt) as head:
         lr = _YuvSource(head)
-    nq_params = _check_niqe(lr, niqe)
-    bq_params = _check_brisque(lr, brisque)
+    nq_params = _check_niqe(lr, niqe, rescale_metrics)
+    bq_params = _check_brisque(lr, brisque, rescale_metrics)
     gt = reader = writer = None
     try:
         if gt_yuv is not None:
@@ -608,8 +623,8 @@ def evaluate_yuv(model, lr_yuv: str, width: int, height: int, side_dir: str, gt_
             _check_regions(lr, gt, crop_border, ccrop)
             if msssim:
                 _check_msssim(lr, gt, crop_border)
-        tof = _check_tof(lr, gt, tof)
-        lp_params = _check_lpips(lr, gt, lpips)
+        tof = _check_tof(lr, gt, tof, rescale_metrics)
+        lp_params = _check_lpips(lr, gt, lpips, rescale_metrics)
         writer = YuvWriter(save_yuv, 4 * width, 4 * height, fmt) if save_yuv is not None else None
 
         def load():

@@ -980,6 +980,13 @@ def _f64_out(out: Optional[torch.Tensor], shape: tuple, like: torch.Tensor, name
     return out
 
 
+def _metric_peak(name: str, peak) -> int:
+    """The peak of the 16-bit form of a metric's sample kernel, 2**depth - 1: an integer in 1 .. 65535 (`streaming.check_peak`'s rule)."""
+    if isinstance(peak, bool) or not isinstance(peak, int) or not 1 <= peak <= 65535:
+        raise ValueError(f"{name}: peak must be an integer in 1 .. 65535, got {peak!r}")
+    return peak
+
+
 def _niqe_region(name: str, H: int, W: int, rows: int, cols: int, N: int):
     rows, cols = int(rows), int(cols)
     if N <= 0 or not 0 < rows <= H or not 0 < cols <= W:
@@ -987,35 +994,47 @@ def _niqe_region(name: str, H: int, W: int, rows: int, cols: int, N: int):
     return rows, cols
 
 
-def niqe_mscn(src: torch.Tensor, rows: int, cols: int, window, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def niqe_mscn(src: torch.Tensor, rows: int, cols: int, window, out: Optional[torch.Tensor] = None,
+              peak: Optional[int] = None) -> torch.Tensor:
     """src: uint8 or fp64 frames [K,H,W] (or [H,W]) on the device with contiguous rows, read in place (pitch and frame stride may
     exceed the frame) -> fp64 [K,rows,cols]: the MSCN map of the top-left ``rows`` x ``cols``, (x - mu) / (sigma + 1) under the 7 x 7
-    ``window`` (49 fp64 values, a host array), the samples beyond the REGION's edge replaced by the edge sample."""
-    if src.dtype not in (torch.uint8, torch.float64):
+    ``window`` (49 fp64 values, a host array), the samples beyond the REGION's edge replaced by the edge sample.  ``peak``: the frames
+    are uint16 samples of that peak, read as x = 255 v / peak (cdfo_niqe_mscn_u16)."""
+    if peak is not None:
+        peak, kind = _metric_peak("niqe_mscn", peak), torch.uint16
+    elif src.dtype not in (torch.uint8, torch.float64):
         raise ValueError(f"niqe_mscn: uint8 or fp64 frames expected, got {src.dtype}")
-    s, N, H, W, sp, ss = _sample_frames(src, "niqe_mscn: src", src.dtype)
+    else:
+        kind = src.dtype
+    s, N, H, W, sp, ss = _sample_frames(src, "niqe_mscn: src", kind)
     rows, cols = _niqe_region("niqe_mscn", H, W, rows, cols, N)
     win = np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
     if win.size != 49:
         raise ValueError(f"niqe_mscn: a window of 7 x 7 values expected, got {win.size}")
     out = _f64_out(out, (N, rows, cols), s, "niqe_mscn")
-    entry = "cdfo_niqe_mscn_u8" if src.dtype == torch.uint8 else "cdfo_niqe_mscn_f64"
+    entry = "cdfo_niqe_mscn_u16" if peak is not None else "cdfo_niqe_mscn_u8" if src.dtype == torch.uint8 else "cdfo_niqe_mscn_f64"
     with on_device(s):
-        check(getattr(_lib.lib(), entry)(_vp(s), sp, C.c_longlong(ss), N, rows, cols, C.c_void_p(win.ctypes.data), _vp(out), _stream()),
-              entry)
+        check(getattr(_lib.lib(), entry)(_vp(s), sp, C.c_longlong(ss), N, rows, cols, C.c_void_p(win.ctypes.data), _vp(out),
+                                         *(() if peak is None else (peak,)), _stream()), entry)
     return out
 
 
-def niqe_half(src: torch.Tensor, rows: int, cols: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def niqe_half(src: torch.Tensor, rows: int, cols: int, out: Optional[torch.Tensor] = None, peak: Optional[int] = None) -> torch.Tensor:
     """src: uint8 frames as `niqe_mscn` takes them -> fp64 [K,rows/2,cols/2]: the top-left ``rows`` x ``cols`` (even) at half size,
-    the fixed 8 taps of include/cdfo_hip.h on x / 255 down the columns, then along the rows, times 255; not rounded."""
-    s, N, H, W, sp, ss = _sample_frames(src, "niqe_half: src", torch.uint8)
+    the fixed 8 taps of include/cdfo_hip.h on x / 255 down the columns, then along the rows, times 255; not rounded.  ``peak``: as
+    `niqe_mscn`'s (cdfo_niqe_half_u16)."""
+    if peak is not None:
+        peak = _metric_peak("niqe_half", peak)
+    s, N, H, W, sp, ss = _sample_frames(src, "niqe_half: src", torch.uint8 if peak is None else torch.uint16)
     rows, cols = _niqe_region("niqe_half", H, W, rows, cols, N)
     if rows % 2 or cols % 2 or min(rows, cols) < 8:
         raise ValueError(f"niqe_half: an even region of at least 8 x 8 expected, got {rows} x {cols}")
     out = _f64_out(out, (N, rows // 2, cols // 2), s, "niqe_half")
     with on_device(s):
-        check(_lib.lib().cdfo_niqe_half(_vp(s), sp, C.c_longlong(ss), N, rows, cols, _vp(out), _stream()), "cdfo_niqe_half")
+        if peak is None:
+            check(_lib.lib().cdfo_niqe_half(_vp(s), sp, C.c_longlong(ss), N, rows, cols, _vp(out), _stream()), "cdfo_niqe_half")
+        else:
+            check(_lib.lib().cdfo_niqe_half_u16(_vp(s), sp, C.c_longlong(ss), N, rows, cols, _vp(out), peak, _stream()), "cdfo_niqe_half_u16")
     return out
 
 
@@ -1058,35 +1077,46 @@ def niqe_features(sums: torch.Tensor, count: int, table: torch.Tensor, scale: in
 BRISQUE_STRIP = 16                                      # CDFO_BRISQUE_STRIP: rows per workgroup of `brisque_sums`
 
 
-def brisque_mscn(src: torch.Tensor, window, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def brisque_mscn(src: torch.Tensor, window, out: Optional[torch.Tensor] = None, peak: Optional[int] = None) -> torch.Tensor:
     """src: uint8 or fp64 frames [K,H,W] (or [H,W]) on the device with contiguous rows, read in place (pitch and frame stride may
     exceed the frame) -> fp64 [K,H,W]: the MSCN map of the whole frame, (x - mu) / (sigma + 1) under the 7 x 7 ``window`` (49 fp64
-    values, a host array) with the reference's epsilon 2^-23 under the root, the samples beyond the FRAME's edge zero."""
-    if src.dtype not in (torch.uint8, torch.float64):
+    values, a host array) with the reference's epsilon 2^-23 under the root, the samples beyond the FRAME's edge zero.  ``peak``: the
+    frames are uint16 samples of that peak, read as x = 255 v / peak (cdfo_brisque_mscn_u16)."""
+    if peak is not None:
+        peak, kind = _metric_peak("brisque_mscn", peak), torch.uint16
+    elif src.dtype not in (torch.uint8, torch.float64):
         raise ValueError(f"brisque_mscn: uint8 or fp64 frames expected, got {src.dtype}")
-    s, N, H, W, sp, ss = _sample_frames(src, "brisque_mscn: src", src.dtype)
+    else:
+        kind = src.dtype
+    s, N, H, W, sp, ss = _sample_frames(src, "brisque_mscn: src", kind)
     if N <= 0 or H <= 0 or W <= 0:
         raise ValueError(f"brisque_mscn: no samples in {N} frames of {H} x {W}")
     win = np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
     if win.size != 49:
         raise ValueError(f"brisque_mscn: a window of 7 x 7 values expected, got {win.size}")
     out = _f64_out(out, (N, H, W), s, "brisque_mscn")
-    entry = "cdfo_brisque_mscn_u8" if src.dtype == torch.uint8 else "cdfo_brisque_mscn_f64"
+    entry = "cdfo_brisque_mscn_u16" if peak is not None else "cdfo_brisque_mscn_u8" if src.dtype == torch.uint8 else "cdfo_brisque_mscn_f64"
     with on_device(s):
-        check(getattr(_lib.lib(), entry)(_vp(s), sp, C.c_longlong(ss), N, H, W, C.c_void_p(win.ctypes.data), _vp(out), _stream()), entry)
+        check(getattr(_lib.lib(), entry)(_vp(s), sp, C.c_longlong(ss), N, H, W, C.c_void_p(win.ctypes.data), _vp(out),
+                                         *(() if peak is None else (peak,)), _stream()), entry)
     return out
 
 
-def brisque_half(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def brisque_half(src: torch.Tensor, out: Optional[torch.Tensor] = None, peak: Optional[int] = None) -> torch.Tensor:
     """src: uint8 frames as `brisque_mscn` takes them, at least 8 x 8 -> fp64 [K,ceil(H/2),ceil(W/2)]: the frame at half size, the fixed
     8 taps of include/cdfo_hip.h on x itself down the columns, then along the rows, the edge sample repeated; odd sizes are legal;
-    not rounded."""
-    s, N, H, W, sp, ss = _sample_frames(src, "brisque_half: src", torch.uint8)
+    not rounded.  ``peak``: as `brisque_mscn`'s (cdfo_brisque_half_u16)."""
+    if peak is not None:
+        peak = _metric_peak("brisque_half", peak)
+    s, N, H, W, sp, ss = _sample_frames(src, "brisque_half: src", torch.uint8 if peak is None else torch.uint16)
     if N <= 0 or min(H, W) < 8:
         raise ValueError(f"brisque_half: frames of at least 8 x 8 expected, got {N} of {H} x {W}")
     out = _f64_out(out, (N, (H + 1) // 2, (W + 1) // 2), s, "brisque_half")
     with on_device(s):
-        check(_lib.lib().cdfo_brisque_half(_vp(s), sp, C.c_longlong(ss), N, H, W, _vp(out), _stream()), "cdfo_brisque_half")
+        if peak is None:
+            check(_lib.lib().cdfo_brisque_half(_vp(s), sp, C.c_longlong(ss), N, H, W, _vp(out), _stream()), "cdfo_brisque_half")
+        else:
+            check(_lib.lib().cdfo_brisque_half_u16(_vp(s), sp, C.c_longlong(ss), N, H, W, _vp(out), peak, _stream()), "cdfo_brisque_half_u16")
     return out
 
 
@@ -1137,16 +1167,20 @@ def _tof_f64(t: torch.Tensor, dims: int, name: str) -> tuple:
 
 
 def tof_level(prev: torch.Tensor, cur: torch.Tensor, h: int, w: int, taps, first: Optional[torch.Tensor] = None,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, peak: Optional[int] = None) -> torch.Tensor:
     """prev, cur: uint8 frames [K,H,W] (or [H,W]) on the device with contiguous rows, read in place -> fp64 [K,2,h,w]: per pair the
     level image of its previous frame and of its current one, smoothed with the odd number of ``taps`` (a host array, at most 19)
     down the columns and along the rows, reflect-101, then resized to h x w bilinearly.  Pair j is (prev[j], cur[j]); with ``first``
-    (uint8 [H,W]) it is (first, cur[0]) for j = 0 and (prev[j - 1], cur[j]) beyond, so ``prev`` may then be ``cur`` itself."""
-    c, N, H, W, cp, cs = _sample_frames(cur, "tof_level: cur", torch.uint8)
-    p, Np, Hp, Wp, pp, ps = _sample_frames(prev, "tof_level: prev", torch.uint8)
+    (uint8 [H,W]) it is (first, cur[0]) for j = 0 and (prev[j - 1], cur[j]) beyond, so ``prev`` may then be ``cur`` itself.  ``peak``:
+    all frames are uint16 samples of that peak, read as x = 255 v / peak (cdfo_tof_level_u16)."""
+    kind = torch.uint8 if peak is None else torch.uint16
+    if peak is not None:
+        peak = _metric_peak("tof_level", peak)
+    c, N, H, W, cp, cs = _sample_frames(cur, "tof_level: cur", kind)
+    p, Np, Hp, Wp, pp, ps = _sample_frames(prev, "tof_level: prev", kind)
     f = fp = None
     if first is not None:
-        f, Nf, Hf, Wf, fp, _ = _sample_frames(first, "tof_level: first", torch.uint8)
+        f, Nf, Hf, Wf, fp, _ = _sample_frames(first, "tof_level: first", kind)
         if (Nf, Hf, Wf) != (1, H, W) or f.device != c.device:
             raise ValueError(f"tof_level: first must be one frame of {H} x {W} on cur's device, got {tuple(f.shape)}")
     if N <= 0 or (Hp, Wp) != (H, W) or Np < (N if first is None else N - 1) or p.device != c.device:
@@ -1158,9 +1192,11 @@ def tof_level(prev: torch.Tensor, cur: torch.Tensor, h: int, w: int, taps, first
     if not 3 <= t.size <= TOF_MAX_TAPS or t.size % 2 == 0 or t.size // 2 >= min(H, W):
         raise ValueError(f"tof_level: an odd number of taps in 3 .. {TOF_MAX_TAPS} expected, got {t.size}")
     out = _f64_out(out, (N, 2, h, w), c, "tof_level")
+    entry = "cdfo_tof_level_u8" if peak is None else "cdfo_tof_level_u16"
     with on_device(c):
-        check(_lib.lib().cdfo_tof_level_u8(_vp(p), pp, C.c_longlong(ps), _vp(c), cp, C.c_longlong(cs), _vp(f), fp or 0, N, H, W, h, w,
-                                           C.c_void_p(t.ctypes.data), int(t.size), _vp(out), _stream()), "cdfo_tof_level_u8")
+        check(getattr(_lib.lib(), entry)(_vp(p), pp, C.c_longlong(ps), _vp(c), cp, C.c_longlong(cs), _vp(f), fp or 0, N, H, W, h, w,
+                                         C.c_void_p(t.ctypes.data), int(t.size), _vp(out), *(() if peak is None else (peak,)), _stream()),
+              entry)
     return out
 
 
@@ -1255,12 +1291,15 @@ def _lpips_out(out: Optional[torch.Tensor], shape: tuple, like: torch.Tensor, na
 
 
 def lpips_stem(frames: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, normalize: bool = True,
-               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               out: Optional[torch.Tensor] = None, peak: Optional[int] = None) -> torch.Tensor:
     """frames: uint8 [N,h,w] (or [h,w]) on the device with contiguous rows, read in place (a view of larger frames is a region);
     weight fp32 [C0,3,3,3] and bias fp32 [C0] on the same device, C0 a multiple of 16, at most 256 -> fp32 [N,h,w,C0]: ReLU of the
     trunk's first convolution on the three scaled channels of the luma (``normalize``: samples to -1 .. 1 first), zeros round the
-    SCALED tensor."""
-    f, N, h, w, fp, fs = _sample_frames(frames, "lpips_stem: frames", torch.uint8)
+    SCALED tensor.  ``peak``: the frames are uint16 samples of that peak, v / peak where the 8-bit form has v / 255
+    (cdfo_lpips_stem_u16)."""
+    if peak is not None:
+        peak = _metric_peak("lpips_stem", peak)
+    f, N, h, w, fp, fs = _sample_frames(frames, "lpips_stem: frames", torch.uint8 if peak is None else torch.uint16)
     if N <= 0 or h <= 0 or w <= 0:
         raise ValueError(f"lpips_stem: no samples in {N} frames of {h} x {w}")
     for name, t in (("weight", weight), ("bias", bias)):
@@ -1271,9 +1310,10 @@ def lpips_stem(frames: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, n
         raise ValueError(f"lpips_stem: weight [C0,3,3,3] and bias [C0] with C0 a multiple of 16 up to {LPIPS_STEM_MAXC} expected, got "
                          f"{tuple(weight.shape)} and {tuple(bias.shape)}")
     out = _lpips_out(out, (N, h, w, C0), f, "lpips_stem")
+    entry = "cdfo_lpips_stem_u8" if peak is None else "cdfo_lpips_stem_u16"
     with on_device(f):
-        check(_lib.lib().cdfo_lpips_stem_u8(_vp(f), fp, C.c_longlong(fs), N, h, w, _vp(weight), _vp(bias), C0, int(bool(normalize)),
-                                            _vp(out), _stream()), "cdfo_lpips_stem_u8")
+        check(getattr(_lib.lib(), entry)(_vp(f), fp, C.c_longlong(fs), N, h, w, _vp(weight), _vp(bias), C0, int(bool(normalize)),
+                                         _vp(out), *(() if peak is None else (peak,)), _stream()), entry)
     return out
 
 

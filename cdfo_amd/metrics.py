@@ -32,6 +32,11 @@ the caller brings (``lpips_params``; the project ships none).  The trunk runs in
 distance behind the features in fp64; the device leaves five layer values per frame (``lpips_layers_u8``), the host adds them
 (``lpips_from_layers``).  The definition is the project's own; parity with the ``lpips`` package is unpinned.  DESIGN.md has the
 definition, tests/lpips_ref.py is its torch statement.
+
+``niqe_u16``, ``brisque_u16``, ``tof_u16``, ``lpips_u16`` (and the ``*_features_u16``, ``farneback_u16``, ``tof_frames_u16``,
+``lpips_layers_u16`` under them): the four on uint16 frames of samples in 0 .. ``peak`` = 2**depth - 1, the project's own definition
+(DESIGN.md): the kernels that read samples form 255 v / peak in fp64 (LPIPS' stem v / peak in fp32), everything behind that is the
+8-bit form's, scratch objects, tables and host steps included.  Frames 257 k at the peak 65535 give the bits of the frames k.
 """
 from __future__ import annotations
 
@@ -47,7 +52,7 @@ import torch
 
 from . import _lib
 from . import kernels as K
-from .kernels import _sample_frames, _stream, _vp, on_device
+from .kernels import _metric_peak, _sample_frames, _stream, _vp, on_device
 
 
 def _partials(a: torch.Tensor, b: torch.Tensor, crop: int, metric: int, from_unit_range: bool, round8: bool):
@@ -426,6 +431,40 @@ def niqe_u8(frames: torch.Tensor, params) -> np.ndarray:
     return np.atleast_1d(niqe_from_features(niqe_features_u8(frames), params))
 
 
+def niqe_features_u16(frames: torch.Tensor, peak: int, scratch: NiqeScratch = None) -> torch.Tensor:
+    """`niqe_features_u8` for uint16 [K,H,W] device frames of samples in 0 .. ``peak`` (2**depth - 1, an integer in 1 .. 65535): the
+    two kernels that read samples form x = 255 v / peak in fp64, an exact product and one correctly rounded division, and every
+    statement behind x is the 8-bit one (the project's definition above 8 bits; samples above the peak are not clamped).
+    The scratch, the table and the launches are `niqe_features_u8`'s; frames 257 k at the peak 65535 give the bits of the frames k."""
+    peak = _metric_peak("niqe_features_u16", peak)
+    a, N, H, W, _, _ = _sample_frames(frames, "frames", torch.uint16)
+    if N == 0:
+        raise ValueError("niqe_features_u16: no frames")
+    R, Cc = niqe_region(H, W)
+    if scratch is None:
+        scratch = NiqeScratch(N, R, Cc, a.device)
+    elif not isinstance(scratch, NiqeScratch) or scratch.device != a.device or scratch.frames < N or (scratch.rows, scratch.cols) != (R, Cc):
+        raise ValueError(f"scratch: a niqe_scratch for at least {N} frames of {R} x {Cc} on {a.device} expected")
+    nb, B = scratch.blocks, NIQE_BLOCK
+    with on_device(a):
+        table, window = _niqe_table_on(a.device), niqe_window()
+        out = torch.empty((N, nb, 36), dtype=torch.float64, device=a.device)
+        m1 = K.niqe_mscn(a, R, Cc, window, scratch.mscn1[:N * R * Cc].view(N, R, Cc), peak=peak)
+        hf = K.niqe_half(a, R, Cc, scratch.half[:N * R * Cc // 4].view(N, R // 2, Cc // 2), peak=peak)
+        m2 = K.niqe_mscn(hf, R // 2, Cc // 2, window, scratch.mscn2[:N * R * Cc // 4].view(N, R // 2, Cc // 2))
+        s = scratch.sums[:2 * N * nb * 30].view(2, N, nb, 5, 6)
+        K.niqe_features(K.niqe_block_sums(m1, B, s[0]), B * B, table, 0, out)
+        K.niqe_features(K.niqe_block_sums(m2, B // 2, s[1]), B * B // 4, table, 1, out)
+    return out
+
+
+def niqe_u16(frames: torch.Tensor, peak: int, params) -> np.ndarray:
+    """`niqe_u8` for uint16 [K,H,W] device frames of samples in 0 .. ``peak``: `niqe_features_u16`, then `niqe_from_features`."""
+    peak = _metric_peak("niqe_u16", peak)
+    params = params if isinstance(params, NiqeParams) else niqe_params(params)
+    return np.atleast_1d(niqe_from_features(niqe_features_u16(frames, peak), params))
+
+
 # ---- BRISQUE: the reference's second no-reference metric on the 8-bit luma (DESIGN.md has the definition; csrc/brisque.hip) ----
 BRISQUE_MIN = 16                                        # the smallest frame, each way; scale 2 is then 8 x 8
 BRISQUE_TABLE = NIQE_TABLE
@@ -580,6 +619,41 @@ def brisque_u8(frames: torch.Tensor, params) -> np.ndarray:
     the project ships none."""
     params = params if isinstance(params, BrisqueParams) else brisque_params(params)
     return np.atleast_1d(brisque_from_features(brisque_features_u8(frames), params))
+
+
+def brisque_features_u16(frames: torch.Tensor, peak: int, scratch: BrisqueScratch = None) -> torch.Tensor:
+    """`brisque_features_u8` for uint16 [K,H,W] device frames of samples in 0 .. ``peak`` (2**depth - 1, an integer in 1 .. 65535):
+    the two kernels that read samples form x = 255 v / peak in fp64 as `niqe_features_u16`'s do, the half image filters x itself, and
+    every statement behind x is the 8-bit one.  The scratch, the table and the launches are `brisque_features_u8`'s."""
+    peak = _metric_peak("brisque_features_u16", peak)
+    a, N, H, W, _, _ = _sample_frames(frames, "frames", torch.uint16)
+    if N == 0:
+        raise ValueError("brisque_features_u16: no frames")
+    H, W = brisque_size(H, W)
+    if scratch is None:
+        scratch = BrisqueScratch(N, H, W, a.device)
+    elif not isinstance(scratch, BrisqueScratch) or scratch.device != a.device or scratch.frames < N or (scratch.h, scratch.w) != (H, W):
+        raise ValueError(f"scratch: a brisque_scratch for at least {N} frames of {H} x {W} on {a.device} expected")
+    Hh, Wh = (H + 1) // 2, (W + 1) // 2
+    g1, g2 = scratch.strips
+    with on_device(a):
+        table, window = _brisque_table_on(a.device), brisque_window()
+        out = torch.empty((N, 36), dtype=torch.float64, device=a.device)
+        m1 = K.brisque_mscn(a, window, scratch.mscn1[:N * H * W].view(N, H, W), peak=peak)
+        hf = K.brisque_half(a, scratch.half[:N * Hh * Wh].view(N, Hh, Wh), peak=peak)
+        m2 = K.brisque_mscn(hf, window, scratch.mscn2[:N * Hh * Wh].view(N, Hh, Wh))
+        s1 = scratch.sums[:N * g1 * 30].view(N, g1, 5, 6)
+        s2 = scratch.sums[N * g1 * 30:N * (g1 + g2) * 30].view(N, g2, 5, 6)
+        K.brisque_features(K.brisque_sums(m1, s1), H * W, table, 0, out)
+        K.brisque_features(K.brisque_sums(m2, s2), Hh * Wh, table, 1, out)
+    return out
+
+
+def brisque_u16(frames: torch.Tensor, peak: int, params) -> np.ndarray:
+    """`brisque_u8` for uint16 [K,H,W] device frames of samples in 0 .. ``peak``: `brisque_features_u16`, then `brisque_from_features`."""
+    peak = _metric_peak("brisque_u16", peak)
+    params = params if isinstance(params, BrisqueParams) else brisque_params(params)
+    return np.atleast_1d(brisque_from_features(brisque_features_u16(frames, peak), params))
 
 
 # ---- tOF: the distance between the Farneback flows of ground truth and result (DESIGN.md has the definition; csrc/tof.hip) ----
@@ -756,6 +830,71 @@ def tof_u8(gt: torch.Tensor, sr: torch.Tensor) -> np.ndarray:
     """Per-frame tOF (lower is better) of two uint8 [T,H,W] device stacks, ground truth and result, fp64 numpy [T] on the host:
     `tof_frames_u8` on the whole sequence, frame 0 against itself."""
     return tof_frames_u8(gt, sr).cpu().numpy()
+
+
+def farneback_u16(prev: torch.Tensor, cur: torch.Tensor, peak: int, scratch: TofScratch = None) -> torch.Tensor:
+    """`farneback_u8` for uint16 [N,H,W] device stacks of samples in 0 .. ``peak`` (2**depth - 1, an integer in 1 .. 65535): the level
+    images are formed from x = 255 v / peak in fp64 (an exact product, one correctly rounded division), so the flow is Farneback's on
+    the 0 .. 255 scale whatever the depth; every launch behind the level images is `farneback_u8`'s."""
+    peak = _metric_peak("farneback_u16", peak)
+    c, N, H, W, _, _ = _sample_frames(cur, "cur", torch.uint16)
+    p, Np, Hp, Wp, _, _ = _sample_frames(prev, "prev", torch.uint16)
+    if N == 0 or (Np, Hp, Wp) != (N, H, W) or p.device != c.device:
+        raise ValueError(f"farneback_u16: two stacks of one shape on one device expected, got {tuple(p.shape)} and {tuple(c.shape)}")
+    tof_size(H, W)
+    with on_device(c):
+        s = _tof_scratch_for(scratch, N, H, W, c.device)
+        out = torch.empty((N, H, W, 2), dtype=torch.float64, device=c.device)
+        for g0 in range(0, N, s.pairs):
+            g1 = min(g0 + s.pairs, N)
+            _farneback(s, g1 - g0, lambda k, h, w, taps, img: K.tof_level(p[g0:g1], c[g0:g1], h, w, taps, out=img, peak=peak), out[g0:g1])
+    return out
+
+
+def tof_frames_u16(gt: torch.Tensor, sr: torch.Tensor, peak: int, gt_prev: torch.Tensor = None, sr_prev: torch.Tensor = None,
+                   scratch: TofScratch = None) -> torch.Tensor:
+    """`tof_frames_u8` for uint16 stacks (and carried frames) of samples in 0 .. ``peak``, read as `farneback_u16` reads them; the
+    grouping, the scratch and every launch behind the level images are `tof_frames_u8`'s."""
+    peak = _metric_peak("tof_frames_u16", peak)
+    g, k, Hg, Wg, _, _ = _sample_frames(gt, "gt", torch.uint16)
+    r, kr, Hr, Wr, _, _ = _sample_frames(sr, "sr", torch.uint16)
+    if k == 0 or kr != k or r.device != g.device:
+        raise ValueError(f"tof_frames_u16: two stacks of one length on one device expected, got {tuple(g.shape)} and {tuple(r.shape)}")
+    H, W = min(Hg, Hr), min(Wg, Wr)
+    tof_size(H, W)
+    firsts = []
+    for name, stack, first in (("gt_prev", g, gt_prev), ("sr_prev", r, sr_prev)):
+        if first is None:
+            first = stack[0]
+        elif not first.is_cuda or first.dtype != torch.uint16 or tuple(first.shape) != tuple(stack.shape[1:]) or first.device != g.device:
+            raise ValueError(f"tof_frames_u16: {name} must be a uint16 frame {tuple(stack.shape[1:])} on the stacks' device")
+        firsts.append(first[:H, :W])
+    g, r = g[:, :H, :W], r[:, :H, :W]
+    with on_device(g):
+        s = _tof_scratch_for(scratch, 2 * k, H, W, g.device)
+        if s.pairs < 2:
+            raise ValueError("tof_frames_u16: the scratch must hold at least two pairs")
+        out, m = torch.empty(k, dtype=torch.float64, device=g.device), s.pairs // 2
+        for f0 in range(0, k, m):
+            f1 = min(f0 + m, k)
+            n = f1 - f0
+
+            def level(kk, h, w, taps, img):
+                for half, (stack, first) in enumerate(((g, firsts[0]), (r, firsts[1]))):
+                    dst = img[half * n:(half + 1) * n]
+                    if f0 == 0:
+                        K.tof_level(stack[:f1], stack[:f1], h, w, taps, first=first, out=dst, peak=peak)
+                    else:
+                        K.tof_level(stack[f0 - 1:f1 - 1], stack[f0:f1], h, w, taps, out=dst, peak=peak)
+
+            flow = _farneback(s, 2 * n, level)
+            K.tof_epe(flow[:n], flow[n:], s.partials[:n * ((H + K.TOF_STRIP - 1) // K.TOF_STRIP)].view(n, -1), out[f0:f1])
+    return out
+
+
+def tof_u16(gt: torch.Tensor, sr: torch.Tensor, peak: int) -> np.ndarray:
+    """`tof_u8` for two uint16 [T,H,W] device stacks of samples in 0 .. ``peak``: `tof_frames_u16` on the whole sequence."""
+    return tof_frames_u16(gt, sr, peak).cpu().numpy()
 
 
 # ---- LPIPS: the learned perceptual distance of result and ground truth, VGG-shaped trunk (DESIGN.md has the definition; csrc/lpips.hip) ----
@@ -995,3 +1134,57 @@ def lpips_u8(sr: torch.Tensor, gt: torch.Tensor, params, normalize: bool = True,
     any device work; the project ships none, and parity with the ``lpips`` package is unpinned."""
     params = lpips_params(params)
     return np.atleast_1d(lpips_from_layers(lpips_layers_u8(sr, gt, params, scratch, normalize)))
+
+
+def lpips_layers_u16(sr: torch.Tensor, gt: torch.Tensor, peak: int, params, scratch: LpipsScratch = None,
+                     normalize: bool = True) -> torch.Tensor:
+    """`lpips_layers_u8` for uint16 stacks of samples in 0 .. ``peak`` (2**depth - 1, an integer in 1 .. 65535): the stem forms
+    (float)v / (float)peak, one correctly rounded fp32 division, where the 8-bit one forms (float)v / 255.f; the trunk, the distance,
+    the scratch and the launches behind the stem are `lpips_layers_u8`'s.  Frames 257 k at the peak 65535 give the bits of the frames
+    k."""
+    peak = _metric_peak("lpips_layers_u16", peak)
+    a, N, Ha, Wa, _, _ = _sample_frames(sr, "sr", torch.uint16)
+    b, Nb, Hb, Wb, _, _ = _sample_frames(gt, "gt", torch.uint16)
+    if N == 0 or Nb != N or a.device != b.device:
+        raise ValueError(f"lpips_layers_u16: two stacks of one length on one device expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    h, w = min(Ha, Hb), min(Wa, Wb)
+    sizes = lpips_size(h, w)
+    params = lpips_params(params)
+    widths = params.widths
+    if scratch is None:
+        scratch = LpipsScratch(1, h, w, widths, N, a.device)
+    elif not isinstance(scratch, LpipsScratch) or scratch.device != a.device or (scratch.h, scratch.w) != (h, w) \
+            or scratch.widths != widths or scratch.frames < N:
+        raise ValueError(f"scratch: an lpips_scratch for at least {N} frames of a {h} x {w} region and widths {widths} on {a.device} expected")
+    a, b = a[:, :h, :w], b[:, :h, :w]
+    strips = scratch.strips
+    with on_device(a):
+        m = _lpips_on(params, a.device)
+        partials = scratch.partials[:N * sum(strips)]
+        first = [N * sum(strips[:k]) for k in range(5)]
+        for g0 in range(0, N, scratch.pairs):
+            g1 = min(g0 + scratch.pairs, N)
+            n = g1 - g0
+            act = lambda buf, k, c: buf[:2 * n * sizes[k][0] * sizes[k][1] * c].view(2 * n, sizes[k][0], sizes[k][1], c)
+            cur, other = scratch.a, scratch.b
+            x = act(cur, 0, widths[0])
+            K.lpips_stem(a[g0:g1], m.w0, m.b0, normalize, out=x[:n], peak=peak)
+            K.lpips_stem(b[g0:g1], m.w0, m.b0, normalize, out=x[n:], peak=peak)
+            i = 0
+            for k, convs in enumerate(LPIPS_STAGES):
+                if k:
+                    x = K.lpips_pool2(x, act(other, k, widths[k - 1]))
+                    cur, other = other, cur
+                for _ in range(convs - (k == 0)):
+                    x = K.conv(x, m.convs[i], pad=1, act=K.ACT_RELU, prec=K.PREC_F32, out=act(other, k, widths[k]))
+                    cur, other = other, cur
+                    i += 1
+                K.lpips_dist(x[:n], x[n:], m.lins[k], partials[first[k]:first[k] + N * strips[k]].view(N, strips[k])[g0:g1])
+        return K.lpips_fold(partials, N, strips, [hk * wk for hk, wk in sizes])
+
+
+def lpips_u16(sr: torch.Tensor, gt: torch.Tensor, peak: int, params, normalize: bool = True, scratch: LpipsScratch = None) -> np.ndarray:
+    """`lpips_u8` for two uint16 [N,H,W] device stacks of samples in 0 .. ``peak``: `lpips_layers_u16`, then `lpips_from_layers`."""
+    peak = _metric_peak("lpips_u16", peak)
+    params = lpips_params(params)
+    return np.atleast_1d(lpips_from_layers(lpips_layers_u16(sr, gt, peak, params, scratch, normalize)))

@@ -793,13 +793,21 @@ int cdfo_msssim_partials_u16(const unsigned short* a, int a_pitch, long long a_f
  *                     inputs give equal bits.
  * cdfo_niqe_features: from those sums of blocks of `count` samples and the device table (gam [CDFO_NIQE_TABLE], then r_gam
  *                     [CDFO_NIQE_TABLE]) the 18 features of each block into features[(n nb + b) 36 + 18 scale ...], scale 0 or 1:
- *                     the index is the first minimum of |r_gam - rn|, 0 when rn is NaN. */
+ *                     the index is the first minimum of |r_gam - rn|, 0 when rn is NaN.
+ * cdfo_niqe_mscn_u16 / cdfo_niqe_half_u16: the two sample readers on 16-bit frames of `peak` = 2^depth - 1 (1 .. 65535, else
+ *                     CDFO_EINVAL; src 2-byte aligned): x = (255.0 v) / peak in fp64, an exact product and ONE correctly rounded
+ *                     division (no reciprocal), v not clamped; every statement behind x is the 8-bit one, the same template.  v = 257 k
+ *                     at peak 65535 gives k exactly, so such frames give the bits of the 8-bit frames k. */
 #define CDFO_NIQE_TABLE 9801
 int cdfo_niqe_mscn_u8(const unsigned char* src, int pitch, long long fstride, int K, int R, int C, const double* window, double* dst,
                       void* stream);
 int cdfo_niqe_mscn_f64(const double* src, int pitch, long long fstride, int K, int R, int C, const double* window, double* dst,
                        void* stream);
 int cdfo_niqe_half(const unsigned char* src, int pitch, long long fstride, int K, int R, int C, double* dst, void* stream);
+int cdfo_niqe_mscn_u16(const unsigned short* src, int pitch, long long fstride, int K, int R, int C, const double* window, double* dst,
+                       int peak, void* stream);
+int cdfo_niqe_half_u16(const unsigned short* src, int pitch, long long fstride, int K, int R, int C, double* dst, int peak,
+                       void* stream);
 int cdfo_niqe_block_sums(const double* mscn, int K, int R, int C, int B, double* sums, void* stream);
 int cdfo_niqe_features(const double* sums, int K, int nb, int count, const double* table, int scale, double* features, void* stream);
 
@@ -819,7 +827,9 @@ int cdfo_niqe_features(const double* sums, int K, int nb, int count, const doubl
  * cdfo_brisque_features: adds the G strips in index order and writes, from those sums over `count` = H W samples and the device table
  *                     (gam, r_gam, r_ggd, CDFO_BRISQUE_TABLE entries each), the 18 features of each frame into
  *                     features[n 36 + 18 scale ...], scale 0 or 1: the map's symmetric fit (first minimum of |r_ggd - rho|), its four
- *                     products' asymmetric fits (|r_gam - rn|); index 0 where the searched value is NaN. */
+ *                     products' asymmetric fits (|r_gam - rn|); index 0 where the searched value is NaN.
+ * cdfo_brisque_mscn_u16 / cdfo_brisque_half_u16: the two sample readers on 16-bit frames of `peak` (1 .. 65535, else CDFO_EINVAL; src
+ *                     2-byte aligned), x = (255.0 v) / peak as cdfo_niqe_mscn_u16 forms it; the half image filters x itself. */
 #define CDFO_BRISQUE_TABLE 9801
 #define CDFO_BRISQUE_STRIP 16
 int cdfo_brisque_mscn_u8(const unsigned char* src, int pitch, long long fstride, int K, int H, int W, const double* window, double* dst,
@@ -827,6 +837,10 @@ int cdfo_brisque_mscn_u8(const unsigned char* src, int pitch, long long fstride,
 int cdfo_brisque_mscn_f64(const double* src, int pitch, long long fstride, int K, int H, int W, const double* window, double* dst,
                           void* stream);
 int cdfo_brisque_half(const unsigned char* src, int pitch, long long fstride, int K, int H, int W, double* dst, void* stream);
+int cdfo_brisque_mscn_u16(const unsigned short* src, int pitch, long long fstride, int K, int H, int W, const double* window, double* dst,
+                          int peak, void* stream);
+int cdfo_brisque_half_u16(const unsigned short* src, int pitch, long long fstride, int K, int H, int W, double* dst, int peak,
+                          void* stream);
 int cdfo_brisque_sums(const double* mscn, int K, int H, int W, double* partials, void* stream);
 int cdfo_brisque_features(const double* partials, int K, int G, int count, const double* table, int scale, double* features,
                           void* stream);
@@ -843,7 +857,9 @@ int cdfo_brisque_features(const double* partials, int K, int G, int count, const
  *                     CDFO_TOF_MIN each way) is smoothed with the `ntaps` (odd, 3 .. CDFO_TOF_MAX_TAPS; doubles in HOST memory)
  *                     down the columns and then along the rows, reflect-101, and resized to h x w (h <= H, w <= W) bilinearly: the
  *                     source coordinate (i + 1/2) (N / n) - 1/2, both taps clamped, the weight from the unclamped floor.
- * cdfo_tof_polyexp:   img [N][h][w] -> R [N][5][h][w] = (b_x, b_y, a_xx, a_yy, a_xy), the edge sample repeated.  `kernels`: 37 doubles
+ * cdfo_tof_level_u16: the same of 16-bit frames of `peak` (1 .. 65535, else CDFO_EINVAL; 2-byte aligned): Farneback runs on
+ *                     x = (255.0 v) / peak as cdfo_niqe_mscn_u16 forms it.
+ * cdfo_tof_polyexp:  img [N][h][w] -> R [N][5][h][w] = (b_x, b_y, a_xx, a_yy, a_xy), the edge sample repeated.  `kernels`: 37 doubles
  *                     in HOST memory: the 11 taps g, x g, x^2 g, then the inverse Gram matrix's entries [1][1], [0][3], [3][3], [5][5].
  * cdfo_tof_matrices:  R [N][2][5][h][w] (a pair's previous, then current expansion) and flow [N][h][w][2] (dx, dy; NULL: zeros) ->
  *                     M [N][5][h][w], the normal equations' planes with the border factors applied.
@@ -858,6 +874,9 @@ int cdfo_brisque_features(const double* partials, int K, int G, int count, const
 int cdfo_tof_level_u8(const unsigned char* prev, int ppitch, long long pstride, const unsigned char* cur, int cpitch, long long cstride,
                       const unsigned char* first, int fpitch, int K, int H, int W, int h, int w, const double* taps, int ntaps,
                       double* dst, void* stream);
+int cdfo_tof_level_u16(const unsigned short* prev, int ppitch, long long pstride, const unsigned short* cur, int cpitch, long long cstride,
+                       const unsigned short* first, int fpitch, int K, int H, int W, int h, int w, const double* taps, int ntaps,
+                       double* dst, int peak, void* stream);
 int cdfo_tof_polyexp(const double* img, int N, int h, int w, const double* kernels, double* R, void* stream);
 int cdfo_tof_matrices(const double* R, const double* flow, int N, int h, int w, double* M, void* stream);
 int cdfo_tof_blur_solve(const double* M, int N, int h, int w, double* flow, void* stream);
@@ -874,7 +893,9 @@ int cdfo_tof_epe(const double* a, const double* b, int K, int h, int w, double* 
  *                     shift_c) / scale_c, shift = (-.030, -.088, -.188), scale = (.458, .448, .450); the SCALED tensor is padded
  *                     with zeros; weight [C0][3][3][3] and bias [C0] fp32 on the device, C0 a multiple of 16, at most
  *                     CDFO_LPIPS_STEM_MAXC.
- * cdfo_lpips_pool2:   src [N][H][W][C] -> dst [N][H/2][W/2][C], the maximum of each 2 x 2 block (odd sizes floor; a NaN wins), C a
+ * cdfo_lpips_stem_u16: the same of 16-bit frames of `peak` (1 .. 65535, else CDFO_EINVAL; src 2-byte aligned): x = (float)v /
+ *                     (float)peak, one correctly rounded fp32 division, where the 8-bit form has (float)v / 255.f; v not clamped.
+ * cdfo_lpips_pool2:  src [N][H][W][C] -> dst [N][H/2][W/2][C], the maximum of each 2 x 2 block (odd sizes floor; a NaN wins), C a
  *                     multiple of 4.  Bit-exact.
  * cdfo_lpips_dist:    fa, fb [N][h][w][C], lin [C] fp64 -> partials [N][G], G = ceil(h / CDFO_LPIPS_STRIP): per strip of rows the
  *                     sum over its pixels of sum_c lin[c] (fa_c / (|fa| + 1e-10) - fb_c / (|fb| + 1e-10))^2, |.| the root of the
@@ -888,6 +909,8 @@ int cdfo_tof_epe(const double* a, const double* b, int K, int h, int w, double* 
 #define CDFO_LPIPS_MAX_LAYERS 8
 int cdfo_lpips_stem_u8(const unsigned char* src, int pitch, long long fstride, int N, int h, int w, const float* weight,
                        const float* bias, int C0, int normalize, float* dst, void* stream);
+int cdfo_lpips_stem_u16(const unsigned short* src, int pitch, long long fstride, int N, int h, int w, const float* weight,
+                        const float* bias, int C0, int normalize, float* dst, int peak, void* stream);
 int cdfo_lpips_pool2(const float* src, int N, int H, int W, int C, float* dst, void* stream);
 int cdfo_lpips_dist(const float* fa, const float* fb, const double* lin, int N, int h, int w, int C, double* partials, void* stream);
 int cdfo_lpips_fold(const double* partials, int N, int layers, const int* strips, const long long* counts, double* out, void* stream);

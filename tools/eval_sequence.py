@@ -2,7 +2,7 @@
 
     python tools/eval_sequence.py --lr LR_DIR --side SIDE_DIR [--gt GT_DIR] [--out SAVE_DIR] [--chunk 8] [--share] [--workers 8]
                                   [--weights FILE.pth] [--name SEQUENCE] [--msssim] [--niqe PARAMS] [--brisque MODEL] [--tof]
-                                  [--lpips MODEL]
+                                  [--lpips MODEL] [--rescale-metrics]
     python tools/eval_sequence.py --synthetic T H W [--out SAVE_DIR] ...
     python tools/eval_sequence.py --lr-yuv FILE --size W H --side SIDE_DIR [--gt-yuv FILE [--gt-size W H]] [--out-yuv FILE] ...
     python tools/eval_sequence.py --synthetic T H W --yuv [--out-yuv FILE] ...
@@ -26,6 +26,9 @@ unpinned); `` tOF: %.5f`` last on the log line.  The common region must be at le
 truth through a VGG-shaped trunk (cdfo_amd.metrics.lpips_u8), with the model in MODEL, an .npz with w0 .. w12, b0 .. b12 and lin0 ..
 lin4 (cdfo_amd.metrics.lpips_params; the project ships no model, tools/make_lpips_model.py writes one from a user's checkpoints;
 parity with the lpips package is unpinned); `` LPIPS: %.5f`` last on the log line.  The common region must be at least 16 x 16.
+--rescale-metrics (with --pix-fmt above 8 bits): --niqe, --brisque, --tof and --lpips are no error there but run their 16-bit forms on
+the luma, a sample v of the format's peak read as 255 v / peak (LPIPS: v / peak); the project's own definition, the
+reference has none above 8 bits.  On 8-bit material it changes nothing.
 
 Prints the reference's log line and frames/s, forward only and end to end.  --synthetic writes a random sequence of T frames of
 H x W with 4H x 4W ground truth into a temporary directory and evaluates that (with --weights absent the model is randomly
@@ -61,6 +64,8 @@ def main():
     ap.add_argument("--brisque", metavar="MODEL", help="score every output frame with BRISQUE with this support-vector model (.npz)")
     ap.add_argument("--tof", action="store_true", help="report the luma's tOF (Farneback flow of result against ground truth) as well")
     ap.add_argument("--lpips", metavar="MODEL", help="report the luma's LPIPS against the ground truth with this model (.npz) as well")
+    ap.add_argument("--rescale-metrics", action="store_true",
+                    help="above 8 bits: run --niqe / --brisque / --tof / --lpips on the luma read as 255 v / peak instead of refusing")
     ap.add_argument("--pix-fmt", default="yuv420p", help="the format of the raw files (cdfo_amd.yuv.parse_pix_fmt); default yuv420p")
     ap.add_argument("--coding", choices=("LD", "RA"), default="LD",
                     help="RA: flows from both motion lists, for a model trained on the random-access field (--synthetic then marks blocks)")
@@ -91,14 +96,14 @@ def main():
             r = evaluate_yuv(model, lr, size[0], size[1], side, gt_yuv=gt, save_yuv=a.out_yuv, chunk=a.chunk,
                              share_compensation=a.share, workers=a.workers, gt_size=tuple(a.gt_size) if a.gt_size else None,
                              pix_fmt=a.pix_fmt, msssim=a.msssim, niqe=a.niqe, brisque=a.brisque, tof=a.tof, lpips=a.lpips,
-                             coding=a.coding)
+                             coding=a.coding, rescale_metrics=a.rescale_metrics)
         else:
             lr, side, gt = a.lr, a.side, a.gt
             if a.synthetic is not None:
                 lr, side, gt = write_synthetic_sequence(tmp, *a.synthetic, markers=a.coding == "RA")
             r = evaluate_sequence(model, lr, side, gt_dir=gt, save_dir=a.out, chunk=a.chunk, share_compensation=a.share,
                                   workers=a.workers, msssim=a.msssim, niqe=a.niqe, brisque=a.brisque, tof=a.tof, lpips=a.lpips,
-                                  coding=a.coding)
+                                  coding=a.coding, rescale_metrics=a.rescale_metrics)
     name = a.name or os.path.basename(os.path.normpath(lr if a.synthetic is None else "synthetic"))
     if gt is not None:
         print(format_log_yuv(r, name) if yuv else format_log(r, name))
