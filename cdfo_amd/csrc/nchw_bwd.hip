@@ -45,12 +45,12 @@ __global__ __launch_bounds__(256) void conv2d_nchw_bwd_input_kernel(const float*
 }
 
 // one wave per weight element (co, c, ky, kx): gw = sum_{b,oy,ox} gout[b][co][oy][ox] * in[b][c][oy*s-p+ky][ox*s-p+kx];
-// waves Co*C*kh*kw .. + Co - 1: the bias gradient of channel co (sum of gout)
+// waves Co*C*kh*kw .. + Co - 1: the bias gradient of channel co (sum of gout).  gw == NULL: the Co bias waves alone (in unused)
 __global__ __launch_bounds__(64) void conv2d_nchw_bwd_weight_kernel(const float* __restrict__ in, const float* __restrict__ gout,
                                                                     int B, int C, int H, int W, int Co, int kh, int kw,
                                                                     int stride, int pad, int Ho, int Wo,
                                                                     float* __restrict__ gw, float* __restrict__ gbias) {
-  const long long nw = (long long)Co * C * kh * kw;
+  const long long nw = gw ? (long long)Co * C * kh * kw : 0;
   const long long e = blockIdx.x;
   const long long npo = (long long)Ho * Wo;
   float s = 0.f;
@@ -253,13 +253,13 @@ extern "C" int cdfo_conv2d_nchw_bwd(const float* in, const float* w, const float
                                     int kh, int kw, int stride, int pad, float* gin, float* gw, float* gbias, void* stream) {
   if (B <= 0 || C <= 0 || Co <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || !gout) return CDFO_EINVAL;
   const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
-  if (Ho <= 0 || Wo <= 0 || (gin && !w) || ((gw || gbias) && !in && gw)) return CDFO_EINVAL;
+  if (H + 2 * pad < kh || W + 2 * pad < kw || (gin && !w) || (gw && !in)) return CDFO_EINVAL;   // gbias needs gout alone
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (gin)
     hipLaunchKernelGGL(conv2d_nchw_bwd_input_kernel, dim3(grid_for((long long)B * C * H * W)), dim3(256), 0, st, gout, w, B, C, H,
                        W, Co, kh, kw, stride, pad, Ho, Wo, gin);
-  if (gw) {
-    const long long waves = (long long)Co * C * kh * kw + (gbias ? Co : 0);
+  if (gw || gbias) {
+    const long long waves = (gw ? (long long)Co * C * kh * kw : 0) + (gbias ? Co : 0);
     if (waves > 0x7fffffffLL) return CDFO_EINVAL;
     hipLaunchKernelGGL(conv2d_nchw_bwd_weight_kernel, dim3((unsigned)waves), dim3(64), 0, st, in, gout, B, C, H, W, Co, kh, kw,
                        stride, pad, Ho, Wo, gw, gbias);
@@ -270,8 +270,8 @@ extern "C" int cdfo_conv2d_nchw_bwd(const float* in, const float* w, const float
 
 extern "C" int cdfo_maxpool_nchw_bwd(const float* in, const float* gout, int BC, int H, int W, int k, int stride, int* idx_scratch,
                                      float* gin, void* stream) {
-  const int Ho = (H - k) / stride + 1, Wo = (W - k) / stride + 1;
-  if (BC <= 0 || k <= 0 || stride <= 0 || Ho <= 0 || Wo <= 0 || !idx_scratch || (long long)H * W >= (1ll << 31)) return CDFO_EINVAL;
+  if (BC <= 0 || k <= 0 || stride <= 0 || H < k || W < k || !idx_scratch || (long long)H * W >= (1ll << 31)) return CDFO_EINVAL;
+  const int Ho = (H - k) / stride + 1, Wo = (W - k) / stride + 1;   // after the check: stride 0 must not reach the division
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(maxpool_nchw_argmax_kernel, dim3(grid_for((long long)BC * Ho * Wo)), dim3(256), 0, st, in, BC, H, W, k, stride,
                      Ho, Wo, idx_scratch);

@@ -49,9 +49,12 @@ __global__ __launch_bounds__(256) void maxpool_nchw_kernel(const float* __restri
     const int oy = (i / Wo) % Ho;
     const long long bc = i / ((long long)Wo * Ho);
     const float* ip = in + bc * H * W;
-    float m = -INFINITY;
+    float m = -INFINITY;   // the arg-max kernel's fold (nchw_bwd.hip), ATen's: a NaN in the window wins, fmaxf would drop it
     for (int ky = 0; ky < k; ++ky)
-      for (int kx = 0; kx < k; ++kx) m = fmaxf(m, ip[(long long)(oy * stride + ky) * W + ox * stride + kx]);
+      for (int kx = 0; kx < k; ++kx) {
+        const float v = ip[(long long)(oy * stride + ky) * W + ox * stride + kx];
+        if (v > m || v != v) m = v;
+      }
     out[i] = m;
   }
 }
@@ -67,6 +70,7 @@ __global__ __launch_bounds__(256) void resize_bilinear_nchw_kernel(const float* 
     const int ox = i % Wo;
     const int oy = (i / Wo) % Ho;
     const long long bc = i / ((long long)Wo * Ho);
+    // contracted to one fma each (-ffp-contract=fast), which is also what ATen's CPU kernel evaluates: tests/nchw_cases.py::resize_taps
     float sy = ((float)oy + 0.5f) * sh - 0.5f, sx = ((float)ox + 0.5f) * sw - 0.5f;
     sy = sy < 0.f ? 0.f : sy;
     sx = sx < 0.f ? 0.f : sx;
@@ -154,8 +158,8 @@ __global__ __launch_bounds__(256) void mv_offset_mask_kernel(const float* __rest
 extern "C" int cdfo_conv2d_nchw(const float* in, const float* w, const float* bias, int B, int C, int H, int W, int Co,
                                 int kh, int kw, int stride, int pad, int act, float* out, void* stream) {
   if (B <= 0 || C <= 0 || Co <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0) return CDFO_EINVAL;
+  if (H + 2 * pad < kh || W + 2 * pad < kw) return CDFO_EINVAL;   // not Ho <= 0: C's division truncates -1 / 2 to 0
   const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
-  if (Ho <= 0 || Wo <= 0) return CDFO_EINVAL;
   hipLaunchKernelGGL(conv2d_nchw_kernel, dim3(grid_for((long long)B * Co * Ho * Wo)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), in, w, bias, B, C, H, W, Co, kh, kw, stride, pad, Ho, Wo, act, out);
   CDFO_LAUNCH_CHECK();
@@ -163,8 +167,8 @@ extern "C" int cdfo_conv2d_nchw(const float* in, const float* w, const float* bi
 }
 
 extern "C" int cdfo_maxpool_nchw(const float* in, int BC, int H, int W, int k, int stride, float* out, void* stream) {
+  if (BC <= 0 || k <= 0 || stride <= 0 || H < k || W < k) return CDFO_EINVAL;   // before the division by stride
   const int Ho = (H - k) / stride + 1, Wo = (W - k) / stride + 1;
-  if (BC <= 0 || k <= 0 || stride <= 0 || Ho <= 0 || Wo <= 0) return CDFO_EINVAL;
   hipLaunchKernelGGL(maxpool_nchw_kernel, dim3(grid_for((long long)BC * Ho * Wo)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), in, BC, H, W, k, stride, Ho, Wo, out);
   CDFO_LAUNCH_CHECK();

@@ -54,11 +54,11 @@ class _Conv2d(Function):
         Co, _, kh, kw = w.shape
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
         gx = torch.empty_like(x) if need_x else None
-        gw = torch.empty_like(w) if (need_w or need_b) else None
+        gw = torch.empty_like(w) if need_w else None
         gb = torch.empty(Co, dtype=torch.float32, device=x.device) if need_b else None
         check(_lib.lib().cdfo_conv2d_nchw_bwd(_vp(x), _vp(w), _vp(g), B, Cc, H, W, Co, kh, kw, stride, pad, _vp(gx), _vp(gw), _vp(gb),
                                               _stream()), "cdfo_conv2d_nchw_bwd")
-        return gx, (gw if need_w else None), gb, None, None, None
+        return gx, gw, gb, None, None, None
 
 
 class _MaxPool(Function):

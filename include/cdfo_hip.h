@@ -570,7 +570,9 @@ int cdfo_lincomb(float* out, const float* a, float ca, const float* b, float cb,
                  void* stream);
 
 /* ---- small NCHW operators of the DCN consumer modules DSTA (ops/attentionlayer.py:86-156) and MVDualAttAlignment
- * (arch/SIDECVSR_our.py:3265-3352); contiguous NCHW fp32, one thread per output (nchw_ops.hip) ------------------ */
+ * (arch/SIDECVSR_our.py:3265-3352); contiguous NCHW fp32, one thread per output (nchw_ops.hip).  A kernel or pooling
+ * window larger than the (padded) input is CDFO_EINVAL, here and in the backward; cdfo_maxpool_nchw propagates a NaN in
+ * the window like torch.max_pool2d (and like the arg-max of its backward) ----------------------------------------- */
 int cdfo_conv2d_nchw(const float* in, const float* w, const float* bias, int B, int C, int H, int W, int Co, int kh,
                      int kw, int stride, int pad, int act, float* out, void* stream);
 int cdfo_maxpool_nchw(const float* in, int BC, int H, int W, int k, int stride, float* out, void* stream);
@@ -596,7 +598,8 @@ int cdfo_conv3x3_c64_n16(const float* x, int ldx, int B, int H, int W, const voi
 
 /* ---- backward of the same operators (nchw_bwd.hip): DSTA and MVDualAttAlignment under autograd, like their reference classes
  * (ops/attentionlayer.py:117-156, arch/SIDECVSR_our.py:3303-3352).  Gather kernels, fixed summation order, no atomics.
- * cdfo_conv2d_nchw_bwd: any of gin [B,C,H,W] (needs w), gw [Co,C,kh,kw] (+ optional gbias [Co]; needs in) may be NULL; all ASSIGNED.
+ * cdfo_conv2d_nchw_bwd: any of gin [B,C,H,W] (needs w), gw [Co,C,kh,kw] (needs in), gbias [Co] (needs gout alone, with or without
+ *   gw) may be NULL; every output given is ASSIGNED.
  * cdfo_maxpool_nchw_bwd: idx_scratch = BC*Ho*Wo ints (the windows' arg-max, first maximum in scan order).
  * cdfo_ew_nchw_bwd modes: 1 g*(y>0) (y = relu output), 2 g*y*(1-y) (y = sigmoid output), 4 g[bc]/P (adjoint of the plane mean),
  *   5 / 6: the DSTA gate out = x*sigmoid(a)*yv[bc] w.r.t. a / w.r.t. x; cdfo_gate_nchw_bwd_y: w.r.t. yv ([BC]).
