@@ -533,6 +533,13 @@ class _SeqAttn(Function):
         return dq, dv, None
 
 
+# The adjoint of flow_warp scatters.  False: with fp32 atomics (cdfo_flow_warp_bwd), whose order the device chooses -- the low bits of
+# every gradient upstream of the warp change from run to run.  True: as fixed-point 64-bit integer sums scaled by the gradient's range
+# (cdfo_flow_warp_bwd_fixed): equal inputs give equal bits, for a range probe, two zero fills and a rounding pass more (about 1 % of a
+# training step).  `train.fit` sets it for the run when it trains with the LPIPS term; everything else leaves the path as it was.
+FLOW_WARP_FIXED = False
+
+
 class _FlowWarp(Function):
     @staticmethod
     def forward(ctx, x, mv, mv_bstride):
@@ -547,7 +554,14 @@ class _FlowWarp(Function):
         (B, H, W, Cc), bs = ctx.meta
         g = _c(g)
         dx = torch.zeros((B, H, W, Cc), dtype=torch.float32, device=g.device)
-        check(_lib.lib().cdfo_flow_warp_bwd(_vp(g), Cc, _vp(mv), C.c_longlong(bs), B, H, W, Cc, _vp(dx), Cc, _stream()), "cdfo_flow_warp_bwd")
+        if not FLOW_WARP_FIXED:
+            check(_lib.lib().cdfo_flow_warp_bwd(_vp(g), Cc, _vp(mv), C.c_longlong(bs), B, H, W, Cc, _vp(dx), Cc, _stream()), "cdfo_flow_warp_bwd")
+            return dx, None, None
+        slots = torch.zeros(2, dtype=torch.int32, device=g.device)
+        K.range_probe(g, slots)
+        acc = torch.zeros(B * H * W * Cc, dtype=torch.int64, device=g.device)
+        check(_lib.lib().cdfo_flow_warp_bwd_fixed(_vp(g), Cc, _vp(mv), C.c_longlong(bs), B, H, W, Cc, _vp(slots), _vp(acc), _vp(dx), Cc,
+                                                  _stream()), "cdfo_flow_warp_bwd_fixed")
         return dx, None, None
 
 

@@ -5,7 +5,8 @@
 // before the 16-bit forms existed.
 //   fp64 metrics: x = (255 v) / peak.  The product is exact, the division is the one rounding: no reciprocal.  v = 257 k at the peak
 //                 65535 gives k exactly.
-//   LPIPS' stem:  x01 = (float)v / (float)peak, one fp32 division, where the 8-bit form has (float)v / 255.f.
+//   LPIPS' stem:  x01 = (float)v / (float)peak, one fp32 division, where the 8-bit form has (float)v / 255.f.  A float sample (the
+//                 training loss, cdfo_lpips_stem_f32) is x01 itself: no division, no clamp, no quantisation.
 #pragma once
 
 __device__ __forceinline__ double metric_sample(unsigned char v) { return (double)v; }
@@ -14,3 +15,4 @@ __device__ __forceinline__ double metric_sample(unsigned short v, double peak) {
 
 __device__ __forceinline__ float unit_sample(unsigned char v) { return (float)v / 255.f; }
 __device__ __forceinline__ float unit_sample(unsigned short v, float peak) { return (float)v / peak; }
+__device__ __forceinline__ float unit_sample(float v) { return v; }

@@ -687,6 +687,82 @@ __global__ __launch_bounds__(256) void flow_warp_bwd_kernel(const float* __restr
   }
 }
 
+// The same adjoint with sums whose order does not matter: a contribution w_corner * g[p] (the fp32 product of the kernel above) is
+// scaled by a power of two, rounded to an integer and added with a 64-bit integer atomic, and integer addition is associative, so
+// equal inputs give equal bits from run to run -- which the fp32 atomics above do not.  The scale comes from the range probe of g
+// (slots[0]: the bits of the largest finite |g|, slots[1]: 1 if g holds a NaN or an infinity; cdfo_range_probe): a destination takes
+// at most one contribution per source pixel, each below 2^(e + 1) with e the probe's exponent, so with nb = ceil(log2(H W)) + 1 the
+// scale 2^(62 - nb - (e + 1)) keeps every sum below 2^62; a unit of the sum is 2^(nb - 61) of the largest |g| (2^-48 at 64 x 64),
+// far below the fp32 rounding of the result.  A non-finite g takes the float atomics into dx, so that NaN and infinity propagate.
+__device__ __forceinline__ double flow_warp_fixed_scale(const unsigned* __restrict__ slots, int H, int W) {
+  int e = (int)((slots[0] >> 23) & 255u) - 127;
+  if (e < -126) e = -126;
+  int nb = 1;
+  while ((1ll << nb) < (long long)H * W) ++nb;
+  return ldexp(1.0, 62 - (nb + 1) - (e + 1));
+}
+
+__global__ __launch_bounds__(256) void flow_warp_bwd_fixed_kernel(const float* __restrict__ g, int ldg, const float* __restrict__ mv,
+                                                                  long long mv_bstride, int B, int H, int W, int C,
+                                                                  const unsigned* __restrict__ slots, unsigned long long* __restrict__ acc,
+                                                                  float* __restrict__ dx, int ldo) {
+  const int cgs = C >> 2;
+  const long long total = (long long)B * H * W * cgs;
+  const float wm = (float)(W - 1 > 1 ? W - 1 : 1), hm = (float)(H - 1 > 1 ? H - 1 : 1);
+  const bool bad = slots[1] != 0;
+  const double scale = flow_warp_fixed_scale(slots, H, W);
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int cg = (int)(i % cgs);
+    const long long p = i / cgs;
+    const int x = (int)(p % W), y = (int)((p / W) % H);
+    const long long b = p / ((long long)W * H);
+    const float* m = mv + b * mv_bstride;
+    const float fx = m[(long long)y * W + x], fy = m[(long long)(H + y) * W + x];
+    const float nx = 2.0f * ((float)x + fx) / wm - 1.0f, ny = 2.0f * ((float)y + fy) / hm - 1.0f;
+    const float sx = ((nx + 1.f) / 2.f) * (float)(W - 1), sy = ((ny + 1.f) / 2.f) * (float)(H - 1);
+    if (!(sx > -1.f && sx < (float)W && sy > -1.f && sy < (float)H)) continue;
+    const float x0f = floorf(sx), y0f = floorf(sy);
+    const int x0 = (int)x0f, y0 = (int)y0f;
+    const float tx = sx - x0f, ty = sy - y0f;
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + p * ldg + cg * 4);
+    const bool xa = x0 >= 0 && x0 < W, xb = x0 + 1 >= 0 && x0 + 1 < W;
+    auto add = [&](int yy, int xx, float w) {
+      const long long px = (b * H + yy) * W + xx;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float v = gv[e] * w;
+        if (bad) atomicAdd(dx + px * ldo + cg * 4 + e, v);
+        else atomicAdd(acc + px * C + cg * 4 + e, (unsigned long long)__double2ll_rn((double)v * scale));
+      }
+    };
+    if (y0 >= 0 && y0 < H) {
+      if (xa) add(y0, x0, (1.f - tx) * (1.f - ty));
+      if (xb) add(y0, x0 + 1, tx * (1.f - ty));
+    }
+    if (y0 + 1 >= 0 && y0 + 1 < H) {
+      if (xa) add(y0 + 1, x0, (1.f - tx) * ty);
+      if (xb) add(y0 + 1, x0 + 1, tx * ty);
+    }
+  }
+}
+
+// dx[p][c] = acc[p][c] / scale, one rounding to fp32; with a non-finite g the float atomics above have filled dx already
+__global__ __launch_bounds__(256) void flow_warp_bwd_fixed_finish_kernel(const long long* __restrict__ acc, const unsigned* __restrict__ slots,
+                                                                         long long rows, int H, int W, int C, float* __restrict__ dx, int ldo) {
+  if (slots[1] != 0) return;
+  const double inv = 1.0 / flow_warp_fixed_scale(slots, H, W);
+  const int cgs = C >> 2;
+  const long long total = rows * cgs;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long p = i / cgs;
+    const int c = (int)(i - p * cgs) * 4;
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (float)((double)acc[p * C + c + e] * inv);
+    *reinterpret_cast<f32x4*>(dx + p * ldo + c) = o;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ resample adjoints
 // adjoint of bilinear x2, align_corners = False (F.interpolate, arch.py:324-333): out[Y] = 0.25 in[clamp(y - 1)] + 0.75 in[y]
 // for Y = 2y, 0.75 in[y] + 0.25 in[clamp(y + 1)] for Y = 2y + 1.  din[y] gathers Y = 2y-1 .. 2y+2 (weights .25 .75 .75 .25;
@@ -891,6 +967,21 @@ extern "C" int cdfo_flow_warp_bwd(const float* g, int ldg, const float* mv, long
   if (!aligned16(g) || !aligned16(dx)) return CDFO_EALIGN;
   hipLaunchKernelGGL(flow_warp_bwd_kernel, dim3(tr_grid((long long)B * H * W * (C / 4))), dim3(256), 0, static_cast<hipStream_t>(stream), g, ldg, mv,
                      mv_bstride, B, H, W, C, dx, ldo);
+  CDFO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cdfo_flow_warp_bwd_fixed(const float* g, int ldg, const float* mv, long long mv_bstride, int B, int H, int W, int C,
+                                        const void* slots2, long long* acc, float* dx, int ldo, void* stream) {
+  if (!g || !mv || !dx || !slots2 || !acc || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4 || ldg % 4 || ldo % 4 || ldg < C || ldo < C)
+    return CDFO_EINVAL;
+  if (!aligned16(g) || !aligned16(dx) || reinterpret_cast<uintptr_t>(acc) & 7u || reinterpret_cast<uintptr_t>(slots2) & 3u) return CDFO_EALIGN;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long rows = (long long)B * H * W;
+  const unsigned* slots = static_cast<const unsigned*>(slots2);
+  hipLaunchKernelGGL(flow_warp_bwd_fixed_kernel, dim3(tr_grid(rows * (C / 4))), dim3(256), 0, st, g, ldg, mv, mv_bstride, B, H, W, C, slots,
+                     reinterpret_cast<unsigned long long*>(acc), dx, ldo);
+  hipLaunchKernelGGL(flow_warp_bwd_fixed_finish_kernel, dim3(tr_grid(rows * (C / 4))), dim3(256), 0, st, acc, slots, rows, H, W, C, dx, ldo);
   CDFO_LAUNCH_CHECK();
   return 0;
 }

@@ -1291,15 +1291,15 @@ def _lpips_out(out: Optional[torch.Tensor], shape: tuple, like: torch.Tensor, na
 
 
 def lpips_stem(frames: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, normalize: bool = True,
-               out: Optional[torch.Tensor] = None, peak: Optional[int] = None) -> torch.Tensor:
+               out: Optional[torch.Tensor] = None, peak: Optional[int] = None, _f32: bool = False) -> torch.Tensor:
     """frames: uint8 [N,h,w] (or [h,w]) on the device with contiguous rows, read in place (a view of larger frames is a region);
     weight fp32 [C0,3,3,3] and bias fp32 [C0] on the same device, C0 a multiple of 16, at most 256 -> fp32 [N,h,w,C0]: ReLU of the
     trunk's first convolution on the three scaled channels of the luma (``normalize``: samples to -1 .. 1 first), zeros round the
     SCALED tensor.  ``peak``: the frames are uint16 samples of that peak, v / peak where the 8-bit form has v / 255
-    (cdfo_lpips_stem_u16)."""
+    (cdfo_lpips_stem_u16).  ``_f32``: fp32 samples used as they are (`lpips_stem_f32`)."""
     if peak is not None:
         peak = _metric_peak("lpips_stem", peak)
-    f, N, h, w, fp, fs = _sample_frames(frames, "lpips_stem: frames", torch.uint8 if peak is None else torch.uint16)
+    f, N, h, w, fp, fs = _sample_frames(frames, "lpips_stem: frames", torch.float32 if _f32 else torch.uint8 if peak is None else torch.uint16)
     if N <= 0 or h <= 0 or w <= 0:
         raise ValueError(f"lpips_stem: no samples in {N} frames of {h} x {w}")
     for name, t in (("weight", weight), ("bias", bias)):
@@ -1310,11 +1310,19 @@ def lpips_stem(frames: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, n
         raise ValueError(f"lpips_stem: weight [C0,3,3,3] and bias [C0] with C0 a multiple of 16 up to {LPIPS_STEM_MAXC} expected, got "
                          f"{tuple(weight.shape)} and {tuple(bias.shape)}")
     out = _lpips_out(out, (N, h, w, C0), f, "lpips_stem")
-    entry = "cdfo_lpips_stem_u8" if peak is None else "cdfo_lpips_stem_u16"
+    entry = "cdfo_lpips_stem_f32" if _f32 else "cdfo_lpips_stem_u8" if peak is None else "cdfo_lpips_stem_u16"
     with on_device(f):
         check(getattr(_lib.lib(), entry)(_vp(f), fp, C.c_longlong(fs), N, h, w, _vp(weight), _vp(bias), C0, int(bool(normalize)),
                                          _vp(out), *(() if peak is None else (peak,)), _stream()), entry)
     return out
+
+
+def lpips_stem_f32(frames: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, normalize: bool = True,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`lpips_stem` of fp32 frames [N,h,w] (or [h,w]) with contiguous rows whose samples are used as they are, nominally in 0 .. 1:
+    no division, no clamp, no quantisation (cdfo_lpips_stem_f32; the training loss).  Samples k / 255 give the bits of the 8-bit
+    form on k."""
+    return lpips_stem(frames, weight, bias, normalize, out, _f32=True)
 
 
 def lpips_pool2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1341,6 +1349,64 @@ def lpips_dist(fa: torch.Tensor, fb: torch.Tensor, lin: torch.Tensor, out: Optio
     out = _f64_out(out, (N, (h + LPIPS_STRIP - 1) // LPIPS_STRIP), fa, "lpips_dist")
     with on_device(fa):
         check(_lib.lib().cdfo_lpips_dist(_vp(fa), _vp(fb), _vp(lin), N, h, w, Cc, _vp(out), _stream()), "cdfo_lpips_dist")
+    return out
+
+
+def lpips_dist_bwd(fa: torch.Tensor, fb: torch.Tensor, lin: torch.Tensor, gscale: torch.Tensor, gin: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fa, fb: dense fp32 [N,h,w,C] on one device, C a multiple of 16; lin: dense fp64 [C]; gscale: dense fp32 [N], the upstream
+    gradient of each frame's layer distance; gin: dense fp32 [N,h,w,C] or None, the gradient that arrives at this tap from the deeper
+    stage -> fp32 [N,h,w,C]: the gradient at the pre-activation of ``fa``, ``fa_c > 0 ? d(gscale_n d_n)/d fa_c + gin_c : +0``, the
+    derivative in fp64 and rounded once (csrc/lpips.hip has the closed form).  The select drops what arrives where ``fa`` is not
+    positive, a NaN included."""
+    N, h, w, Cc = _lpips_act(fa, "lpips_dist_bwd: fa")
+    if _lpips_act(fb, "lpips_dist_bwd: fb") != (N, h, w, Cc) or fb.device != fa.device:
+        raise ValueError(f"lpips_dist_bwd: two stacks of one shape on one device expected, got {tuple(fa.shape)} and {tuple(fb.shape)}")
+    if Cc % 16:
+        raise ValueError(f"lpips_dist_bwd: C must be a multiple of 16, got {Cc}")
+    if not isinstance(lin, torch.Tensor) or lin.dtype != torch.float64 or tuple(lin.shape) != (Cc,) or not lin.is_contiguous() \
+            or lin.device != fa.device:
+        raise ValueError(f"lpips_dist_bwd: lin must be a dense fp64 [{Cc}] tensor on the stacks' device")
+    if not isinstance(gscale, torch.Tensor) or gscale.dtype != torch.float32 or tuple(gscale.shape) != (N,) or not gscale.is_contiguous() \
+            or gscale.device != fa.device:
+        raise ValueError(f"lpips_dist_bwd: gscale must be a dense fp32 [{N}] tensor on the stacks' device")
+    if gin is not None and (_lpips_act(gin, "lpips_dist_bwd: gin") != (N, h, w, Cc) or gin.device != fa.device):
+        raise ValueError(f"lpips_dist_bwd: gin must have the stacks' shape and device, got {tuple(gin.shape)}")
+    out = _lpips_out(out, (N, h, w, Cc), fa, "lpips_dist_bwd")
+    with on_device(fa):
+        check(_lib.lib().cdfo_lpips_dist_bwd(_vp(fa), _vp(fb), _vp(lin), _vp(gscale), _vp(gin), N, h, w, Cc, _vp(out), _stream()),
+              "cdfo_lpips_dist_bwd")
+    return out
+
+
+def lpips_pool2_bwd(x: torch.Tensor, g: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x: dense fp32 [N,H,W,C], the pool's input; g: dense fp32 [N,H//2,W//2,C], the gradient at its output -> fp32 [N,H,W,C]: g at
+    the element `lpips_pool2` took, +0 elsewhere and in the floored row and column; bit-equal to the CPU backward of
+    ``torch.max_pool2d``."""
+    N, H, W, Cc = _lpips_act(x, "lpips_pool2_bwd: x")
+    if H < 2 or W < 2:
+        raise ValueError(f"lpips_pool2_bwd: at least 2 x 2 expected, got {H} x {W}")
+    if _lpips_act(g, "lpips_pool2_bwd: g") != (N, H // 2, W // 2, Cc) or g.device != x.device:
+        raise ValueError(f"lpips_pool2_bwd: g [{N},{H // 2},{W // 2},{Cc}] on x's device expected, got {tuple(g.shape)}")
+    out = _lpips_out(out, (N, H, W, Cc), x, "lpips_pool2_bwd")
+    with on_device(x):
+        check(_lib.lib().cdfo_lpips_pool2_bwd(_vp(x), _vp(g), N, H, W, Cc, _vp(out), _stream()), "cdfo_lpips_pool2_bwd")
+    return out
+
+
+def lpips_stem_bwd(g: torch.Tensor, wf: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """g: dense fp32 [N,h,w,C0], the gradient at the stem's output already masked by it; wf: dense fp32 [C0,3,3] on the same device,
+    the stem's weights folded over the three scaled channels (`cdfo_amd.metrics`: ``k sum_c w[o][c] / scale_c``) -> fp32 [N,h,w]:
+    the gradient at the samples, the adjoint of the scaling and conv1_1 as one 3 x 3 C0 -> 1 convolution with flipped taps."""
+    N, h, w, C0 = _lpips_act(g, "lpips_stem_bwd: g")
+    if C0 % 16 or C0 > LPIPS_STEM_MAXC:
+        raise ValueError(f"lpips_stem_bwd: C0 must be a multiple of 16 up to {LPIPS_STEM_MAXC}, got {C0}")
+    if not isinstance(wf, torch.Tensor) or wf.dtype != torch.float32 or tuple(wf.shape) != (C0, 3, 3) or not wf.is_contiguous() \
+            or wf.device != g.device:
+        raise ValueError(f"lpips_stem_bwd: wf must be a dense fp32 [{C0},3,3] tensor on g's device")
+    out = _lpips_out(out, (N, h, w), g, "lpips_stem_bwd")
+    with on_device(g):
+        check(_lib.lib().cdfo_lpips_stem_bwd(_vp(g), _vp(wf), N, h, w, C0, _vp(out), _stream()), "cdfo_lpips_stem_bwd")
     return out
 
 

@@ -1,11 +1,16 @@
 """The training loss on the device: the reference's Charbonnier loss (opt/loss.py:20-31), ``sum(sqrt((sr - hr)^2 + eps))``, as one HIP
 pass (csrc/train_batch.hip: cdfo_charbonnier) that leaves the fp32 sum on the device and the derivative beside it -- where the script has
-a six-operator torch expression and a ``loss.item()`` per step."""
+a six-operator torch expression and a ``loss.item()`` per step.
+
+`lpips_loss` is the perceptual distance the evaluators score with (`cdfo_amd.metrics.lpips_u8`) as a training loss, the pairing of the
+reference's opt/loss.py with opt/lpips: the metric's launches behind a float stem, and an explicit backward through the frozen trunk
+on the device (csrc/lpips.hip)."""
 from __future__ import annotations
 
 import torch
 
 from . import kernels as K
+from . import metrics as M
 
 
 class _Charbonnier(torch.autograd.Function):
@@ -30,3 +35,70 @@ def charbonnier(sr: torch.Tensor, hr: torch.Tensor, eps: float = 1e-4) -> torch.
     if not sr.is_cuda:
         raise NotImplementedError("charbonnier: the HIP path needs device tensors (there is no CPU fallback)")
     return _Charbonnier.apply(sr, hr, float(eps))
+
+
+class _Lpips(torch.autograd.Function):
+    """The forward is `metrics.lpips_layers_f32`'s launches on all N pairs as one batch, with the result's thirteen activations and
+    the ground truth's five taps copied out of the ping-pong scratch; the backward walks the stages 5 -> 1."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, params, normalize):
+        a, b = sr.detach().view(sr.shape[0], sr.shape[-2], sr.shape[-1]), hr.detach().view(hr.shape[0], hr.shape[-2], hr.shape[-1])
+        N, h, w = a.shape
+        acts, taps = [None] * M.LPIPS_CONVS, []
+        last = [sum(M.LPIPS_STAGES[:k + 1]) - 1 for k in range(5)]
+
+        def keep(i, x, n):
+            acts[i] = x[:n].clone()
+            if i in last:
+                taps.append(x[n:].clone())
+
+        with K.on_device(a):
+            scratch = M.LpipsScratch(N, h, w, params.widths, N, a.device)
+            layers = M._lpips_layers_f32(a, b, params, scratch, normalize, keep)
+            loss = ((((layers[:, 0] + layers[:, 1]) + layers[:, 2]) + layers[:, 3]) + layers[:, 4]).float()
+        ctx.params, ctx.normalize, ctx.shape = params, normalize, sr.shape
+        ctx.save_for_backward(*acts, *taps)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .autograd import act_bwd
+        saved = ctx.saved_tensors
+        acts, taps = saved[:M.LPIPS_CONVS], saved[M.LPIPS_CONVS:]
+        gscale = grad_out.detach().to(torch.float32).contiguous()
+        with K.on_device(gscale):
+            m = M._lpips_adjoint_on(ctx.params, gscale.device)
+            gin, i = None, M.LPIPS_CONVS - 1
+            for k in range(4, -1, -1):
+                g = K.lpips_dist_bwd(acts[i], taps[k], m.lins[k], gscale, gin)       # at conv i's pre-activation
+                for _ in range(M.LPIPS_STAGES[k] - 1):
+                    g = K.conv(g, m.adj[i - 1], pad=1, prec=K.PREC_F32)               # at conv i - 1's output ...
+                    i -= 1
+                    g = act_bwd(g, acts[i], K.ACT_RELU)                               # ... and through its ReLU
+                if k:
+                    g = K.conv(g, m.adj[i - 1], pad=1, prec=K.PREC_F32)               # at the pool's output
+                    i -= 1
+                    gin = K.lpips_pool2_bwd(acts[i], g)                               # at the tap before, in front of its select
+            gx = K.lpips_stem_bwd(g, m.wf[ctx.normalize])
+        return gx.view(ctx.shape), None, None, None
+
+
+def lpips_loss(sr: torch.Tensor, hr: torch.Tensor, model, normalize: bool = True) -> torch.Tensor:
+    """Per-frame LPIPS of ``sr`` to ``hr`` as a loss: fp32 [N] on the device, the fp64 total (((d0 + d1) + d2) + d3) + d4 of
+    `metrics.lpips_layers_f32` rounded once.  ``sr``, ``hr``: dense fp32 device tensors [N,1,H,W] or [N,H,W] of one shape, H, W >= 16,
+    samples nominally in 0 .. 1 and used as they are (no / 255, no clamp, no quantisation); anything else is a ValueError, nothing is
+    made contiguous or cast.  ``model``: what `metrics.lpips_params` takes, checked before any device work; its weights are frozen.
+    Gradient flows to ``sr`` only (``hr`` gets None), through the fp32 trunk by explicit HIP adjoints; a ReLU output <= 0 passes +0
+    whatever arrives (a select), a max-pool routes to the element ATen's CPU kernel picks.  Equal inputs give equal bits, forward and
+    backward; ``sr`` equal to ``hr`` gives exactly 0 and an all-zero gradient.  There is no host synchronisation.
+
+    Kept between forward and backward, in bytes: ``4 N sum_k h_k w_k C_k (convs_k + 1)`` with (h_k, w_k) = (H >> k, W >> k), C_k the
+    stage widths and convs = (2, 2, 3, 3, 3) -- the result's thirteen activations and the ground truth's five taps.  The forward also
+    holds, until it returns, two ping-pong buffers of ``8 N max_k h_k w_k C_k`` bytes each."""
+    params = M.lpips_params(model)
+    a, b = M._lpips_f32_frames(sr, "lpips_loss: sr"), M._lpips_f32_frames(hr, "lpips_loss: hr")
+    if sr.shape != hr.shape or sr.device != hr.device:
+        raise ValueError(f"lpips_loss: two tensors of one shape on one device expected, got {tuple(sr.shape)} and {tuple(hr.shape)}")
+    M.lpips_size(a.shape[1], a.shape[2])
+    return _Lpips.apply(sr, hr, params, bool(normalize))

@@ -31,7 +31,8 @@ DESIGN.md has the definition, tests/tof_ref.py is its numpy statement.
 the caller brings (``lpips_params``; the project ships none).  The trunk runs in fp32 on the matrix cores (``kernels.conv``), the
 distance behind the features in fp64; the device leaves five layer values per frame (``lpips_layers_u8``), the host adds them
 (``lpips_from_layers``).  The definition is the project's own; parity with the ``lpips`` package is unpinned.  DESIGN.md has the
-definition, tests/lpips_ref.py is its torch statement.
+definition, tests/lpips_ref.py is its torch statement.  ``lpips_layers_f32`` is the same behind a float stem (a sample is x itself), the
+forward of the training loss `cdfo_amd.loss.lpips_loss`, whose backward needs `lpips_stem_adjoint` and the adjoint weights packed here.
 
 ``niqe_u16``, ``brisque_u16``, ``tof_u16``, ``lpips_u16`` (and the ``*_features_u16``, ``farneback_u16``, ``tof_frames_u16``,
 ``lpips_layers_u16`` under them): the four on uint16 frames of samples in 0 .. ``peak`` = 2**depth - 1, the project's own definition
@@ -1069,6 +1070,91 @@ def _lpips_on(params: LpipsParams, device):
         params._device[device] = SimpleNamespace(w0=t(params.weights[0], torch.float32), b0=t(params.biases[0], torch.float32),
                                                  convs=convs, lins=[t(l, torch.float64) for l in params.lins])
     return params._device[device]
+
+
+def lpips_stem_adjoint(weight0, normalize: bool = True) -> np.ndarray:
+    """fp32 [C0,3,3]: the stem's weights [C0,3,3,3] folded over the three scaled channels, ``k sum_c w[o][c][ky][kx] / scale_c`` with
+    k = 2 with ``normalize``, else 1, formed in fp64 and rounded once.  The padding of the scaled tensor is constant, so this is all
+    the adjoint of the scaling and conv1_1 needs (`kernels.lpips_stem_bwd`)."""
+    w = np.asarray(weight0, dtype=np.float64)
+    scale = np.array((.458, .448, .450), dtype=np.float64)
+    return ((2.0 if normalize else 1.0) * (w / scale[None, :, None, None]).sum(axis=1)).astype(np.float32)
+
+
+def _lpips_adjoint_on(params: LpipsParams, device):
+    """`_lpips_on` with what the backward of `cdfo_amd.loss.lpips_loss` needs beside it, built once per model and device on first use:
+    ``adj``, the other twelve convolutions' adjoint weights (flipped and transposed, no bias) packed by `kernels.pack_conv`, and
+    ``wf``, the stem's folded weights for both values of ``normalize``."""
+    m = _lpips_on(params, device)
+    if not hasattr(m, "adj"):
+        t = lambda a: torch.from_numpy(np.array(a)).to(device=m.w0.device, dtype=torch.float32)
+        with torch.cuda.device(m.w0.device):
+            m.wf = {flag: t(lpips_stem_adjoint(params.weights[0], flag)).contiguous() for flag in (False, True)}
+            m.adj = [K.pack_conv(t(w).flip(2, 3).transpose(0, 1).contiguous(), None) for w in params.weights[1:]]
+    return m
+
+
+def _lpips_f32_frames(t: torch.Tensor, name: str) -> torch.Tensor:
+    """A dense fp32 device tensor [N,1,H,W] or [N,H,W] as [N,H,W]; anything else is a ValueError (nothing is cast or copied)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() \
+            or not (t.dim() == 3 or (t.dim() == 4 and t.shape[1] == 1)) or t.shape[0] == 0:
+        raise ValueError(f"{name}: a dense fp32 device tensor [N,1,H,W] or [N,H,W] expected, got {getattr(t, 'dtype', type(t))} "
+                         f"{tuple(getattr(t, 'shape', ()))}" + (f" strides {t.stride()}" if isinstance(t, torch.Tensor) else ""))
+    return t.view(t.shape[0], t.shape[-2], t.shape[-1])
+
+
+def _lpips_layers_f32(a: torch.Tensor, b: torch.Tensor, params: LpipsParams, scratch: LpipsScratch, normalize: bool, keep=None):
+    """`lpips_layers_u8`'s launches behind the float stem on fp32 [N,h,w] stacks of one shape.  ``keep(i, x, n)``: called behind
+    convolution ``i`` (0 .. 12) with its output ``x`` [2 n,...], the result's frames first; the buffer is reused two launches on."""
+    N, h, w = a.shape
+    sizes, widths, strips = scratch.sizes, scratch.widths, scratch.strips
+    with on_device(a):
+        m = _lpips_on(params, a.device)
+        partials = scratch.partials[:N * sum(strips)]
+        first = [N * sum(strips[:k]) for k in range(5)]
+        for g0 in range(0, N, scratch.pairs):
+            g1 = min(g0 + scratch.pairs, N)
+            n = g1 - g0
+            act = lambda buf, k, c: buf[:2 * n * sizes[k][0] * sizes[k][1] * c].view(2 * n, sizes[k][0], sizes[k][1], c)
+            cur, other = scratch.a, scratch.b
+            x = act(cur, 0, widths[0])
+            K.lpips_stem_f32(a[g0:g1], m.w0, m.b0, normalize, out=x[:n])
+            K.lpips_stem_f32(b[g0:g1], m.w0, m.b0, normalize, out=x[n:])
+            if keep is not None:
+                keep(0, x, n)
+            i = 0
+            for k, convs in enumerate(LPIPS_STAGES):
+                if k:
+                    x = K.lpips_pool2(x, act(other, k, widths[k - 1]))
+                    cur, other = other, cur
+                for _ in range(convs - (k == 0)):
+                    x = K.conv(x, m.convs[i], pad=1, act=K.ACT_RELU, prec=K.PREC_F32, out=act(other, k, widths[k]))
+                    cur, other = other, cur
+                    i += 1
+                    if keep is not None:
+                        keep(i, x, n)
+                K.lpips_dist(x[:n], x[n:], m.lins[k], partials[first[k]:first[k] + N * strips[k]].view(N, strips[k])[g0:g1])
+        return K.lpips_fold(partials, N, strips, [hk * wk for hk, wk in sizes])
+
+
+def lpips_layers_f32(sr: torch.Tensor, hr: torch.Tensor, params, scratch: LpipsScratch = None, normalize: bool = True) -> torch.Tensor:
+    """`lpips_layers_u8` for float frames, the forward of the training loss (`cdfo_amd.loss.lpips_loss`): fp64 device tensor [N,5].
+    ``sr``, ``hr``: dense fp32 device tensors [N,1,H,W] or [N,H,W] of ONE shape, H, W >= 16; a sample is used as x itself, nominally
+    in 0 .. 1: no / 255, no clamp, no quantisation.  Behind that load every launch is `lpips_layers_u8`'s, so frames fp32(k) / 255
+    give the bits of the uint8 frames k."""
+    a, b = _lpips_f32_frames(sr, "lpips_layers_f32: sr"), _lpips_f32_frames(hr, "lpips_layers_f32: hr")
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError(f"lpips_layers_f32: two stacks of one shape on one device expected, got {tuple(sr.shape)} and {tuple(hr.shape)}")
+    N, h, w = (int(v) for v in a.shape)
+    lpips_size(h, w)
+    params = lpips_params(params)
+    widths = params.widths
+    if scratch is None:
+        scratch = LpipsScratch(1, h, w, widths, N, a.device)
+    elif not isinstance(scratch, LpipsScratch) or scratch.device != a.device or (scratch.h, scratch.w) != (h, w) \
+            or scratch.widths != widths or scratch.frames < N:
+        raise ValueError(f"scratch: an lpips_scratch for at least {N} frames of a {h} x {w} region and widths {widths} on {a.device} expected")
+    return _lpips_layers_f32(a, b, params, scratch, bool(normalize))
 
 
 def lpips_layers_u8(sr: torch.Tensor, gt: torch.Tensor, params, scratch: LpipsScratch = None, normalize: bool = True) -> torch.Tensor:

@@ -1,8 +1,10 @@
 """The training loop of train_LD_37.py:359-402 with nothing but the log on the host: batches come from a resident `ClipSet` (one launch
 each, cdfo_amd/train_data.py), the loss is `cdfo_amd.loss.charbonnier` (one pass, no ``.item()``), forward and backward are the HIP
-autograd path of ``CVSR_V8``.  The losses of an epoch stay on the device and are read once, for the reference's log line."""
+autograd path of ``CVSR_V8``.  The losses of an epoch stay on the device and are read once, for the reference's log line.
+With an LPIPS model the step's loss gains a perceptual term, `cdfo_amd.loss.lpips_loss`, the pairing opt/loss.py has with opt/lpips."""
 from __future__ import annotations
 
+import math
 import os
 from datetime import datetime
 from typing import Callable, List, Optional, Sequence
@@ -10,7 +12,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .loss import charbonnier
+from .loss import charbonnier, lpips_loss
 from .train_data import ClipSet
 
 MILESTONE, GAMMA = 2000, 0.5
@@ -24,15 +26,46 @@ def learning_rate(lr0: float, epoch: int) -> float:
 
 def fit(model, clips: ClipSet, epochs: int, out_dir: str, batch_size: int = 20, crop: int = 64, lr: float = 1e-4,
         weight_decay: float = 1e-5, val_itv: int = 200, val: Optional[Sequence[str]] = None, seed: int = 4, start_epoch: int = 0,
-        log: Callable[[str], None] = print, val_coding: str = "LD") -> List[float]:
+        log: Callable[[str], None] = print, val_coding: str = "LD", lpips=None, lpips_weight: float = 0.0) -> List[float]:
     """Train ``model`` (a ``CVSR_V8`` on the clip set's device) for epochs ``start_epoch .. epochs - 1``; returns the epochs' average
     losses.  Adam with ``lr`` and ``weight_decay``; the rate of each epoch is set directly (`learning_rate`).  Every ``val_itv`` epochs
     ``state_dict()`` goes to ``<out_dir>/ckpt/epoch-N.pth`` and, with ``val = (lr_dir, side_dir, gt_dir)``, that sequence is evaluated
     (`evaluate_sequence`) and its PSNR and SSIM are logged.  ``seed`` seeds the plans' generator.  ``val_coding``: the ``coding`` of that
-    evaluation ("RA": the validation flows are the random-access loader's field, what a ``ClipSet(..., coding="RA")`` trains on)."""
-    from .evaluate import evaluate_sequence
+    evaluation ("RA": the validation flows are the random-access loader's field, what a ``ClipSet(..., coding="RA")`` trains on).
+    ``lpips``: an LPIPS model (what `metrics.lpips_params` takes); the step's loss is then ``charbonnier(sr, hr) + lpips_weight *
+    lpips_loss(sr, hr, lpips).sum()``, the returned averages and the log line's loss are that total, and the line ends with
+    `` | charbonnier: %f | lpips: %f``, the epoch's averages of the two terms (the second unweighted).  A model without a finite
+    positive ``lpips_weight``, a weight without a model and ``crop < 4`` (the HR crop ``4 crop`` is then below LPIPS' 16 x 16) are
+    ValueErrors before the first batch.  With a model two runs from one seed leave equal weights: the loss is bit-reproducible, and
+    for the run `autograd.FLOW_WARP_FIXED` makes the flow warp's adjoint so.  Without a model every result, log line, allocation and
+    launch is what it was."""
     from .streaming import check_coding
     check_coding(val_coding)
+    if lpips is None:
+        if lpips_weight:
+            raise ValueError(f"fit: lpips_weight {lpips_weight!r} needs an LPIPS model (lpips=)")
+    else:
+        from .metrics import lpips_params
+        if isinstance(lpips_weight, bool) or not isinstance(lpips_weight, (int, float)) or not math.isfinite(lpips_weight) or lpips_weight <= 0:
+            raise ValueError(f"fit: an LPIPS model needs a finite positive lpips_weight, got {lpips_weight!r}")
+        if crop < 4:
+            raise ValueError(f"fit: LPIPS needs an HR crop of at least 16 x 16, got crop = {crop} (HR {4 * crop} x {4 * crop})")
+        lpips = lpips_params(lpips)
+    if lpips is not None:                  # two runs from one seed then leave equal weights: the warp's adjoint adds in a fixed-point order
+        from . import autograd
+        was, autograd.FLOW_WARP_FIXED = autograd.FLOW_WARP_FIXED, True
+        try:
+            return _fit(model, clips, epochs, out_dir, batch_size, crop, lr, weight_decay, val_itv, val, seed, start_epoch, log, val_coding,
+                        lpips, lpips_weight)
+        finally:
+            autograd.FLOW_WARP_FIXED = was
+    return _fit(model, clips, epochs, out_dir, batch_size, crop, lr, weight_decay, val_itv, val, seed, start_epoch, log, val_coding, None, 0.0)
+
+
+def _fit(model, clips, epochs, out_dir, batch_size, crop, lr, weight_decay, val_itv, val, seed, start_epoch, log, val_coding, lpips,
+         lpips_weight) -> List[float]:
+    """The loop of `fit` behind its argument checks."""
+    from .evaluate import evaluate_sequence
     os.makedirs(os.path.join(out_dir, "ckpt"), exist_ok=True)
     rng = np.random.default_rng(seed)
     optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
@@ -41,18 +74,25 @@ def fit(model, clips: ClipSet, epochs: int, out_dir: str, batch_size: int = 20, 
     for epoch in range(start_epoch, epochs):
         for group in optimizer.param_groups:
             group["lr"] = learning_rate(lr, epoch)
-        losses = []
+        losses, terms = [], []
         for plan in clips.epoch(batch_size, rng, crop):
             optimizer.zero_grad()
             x, mvs0, mvs1, pms, rms, ufs, hr = clips.batch(plan, crop)
             sr, _ = model(x, mvs0, mvs1, pms, rms, ufs)
             loss = charbonnier(sr, hr)
+            if lpips is not None:
+                pix, perc = loss, lpips_loss(sr, hr, lpips).sum()
+                loss = pix + lpips_weight * perc
+                terms.append(torch.stack((pix.detach(), perc.detach())))
             losses.append(loss.detach())
             loss.backward()
             optimizer.step()
         per_batch = torch.stack(losses).cpu().tolist()                        # the epoch's one read of the device
         averages.append(round(sum(per_batch) / len(per_batch), 5))
-        log('[%s] Epoch: %d/%d | average epoch loss: %f' % (datetime.now().strftime("%d/%m/%Y %H:%M:%S"), epoch + 1, epochs, averages[-1]))
+        line = '[%s] Epoch: %d/%d | average epoch loss: %f' % (datetime.now().strftime("%d/%m/%Y %H:%M:%S"), epoch + 1, epochs, averages[-1])
+        if lpips is not None:
+            line += ' | charbonnier: %f | lpips: %f' % tuple(torch.stack(terms).mean(dim=0).cpu().tolist())
+        log(line)
         if (epoch + 1) % val_itv == 0:
             torch.save(model.state_dict(), os.path.join(out_dir, "ckpt", "epoch-%d.pth" % (epoch + 1)))
             log('Saved model. lr %f' % optimizer.param_groups[0]["lr"])

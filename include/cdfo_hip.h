@@ -510,7 +510,11 @@ int cdfo_dcn_backward_dt(int dtype, const void* in, const void* offset, const vo
  * cdfo_layernorm64_bwd, cdfo_dwconv3x3_wgrad, cdfo_spatial_gate16_bwd, cdfo_chanconv9 (9 taps along the channel axis,
  * flip = adjoint), cdfo_corr9 (weight gradient of a 9-tap convolution along the channel axis (0) or the image rows (1)),
  * cdfo_gumbel_mask (the hard mask of arch.py:2168-2195 as a tensor), cdfo_seq_attn_bwd (adjoint of cdfo_seq_attn, modes
- * 0-2, probabilities recomputed), cdfo_flow_warp_bwd (scatter with fp32 atomics into a zero-filled dx),
+ * 0-2, probabilities recomputed), cdfo_flow_warp_bwd (scatter with fp32 atomics into a zero-filled dx; the order of the sums, and
+ * with it the low bits, change from run to run), cdfo_flow_warp_bwd_fixed (the same scatter as 64-bit fixed-point integer atomics
+ * into a zero-filled `acc` [B][H][W][C], then one rounding into a zero-filled dx: equal inputs give equal bits; `slots2` are the two
+ * words of cdfo_range_probe over a dense g, which set the scale -- a unit is 2^(ceil(log2(H W)) - 60) of the largest |g| -- and send
+ * a g that holds a NaN or an infinity through the fp32 atomics; what the autograd path uses),
  * cdfo_resample2_bwd (adjoints of bilinear x2 / x0.5). */
 long long cdfo_conv_wgrad_slab_floats(int A, int Bc, int ks, int nsplit);
 int cdfo_conv_wgrad(const float* S, int lds_, int A, const float* L, int ldl, int Bc, int N, int Hs, int Ws, int Hl, int Wl,
@@ -540,6 +544,8 @@ int cdfo_seq_attn_bwd(const float* q, int ldq, const float* v, int ldv, const fl
                       float* dq, int lddq, float* dv, int lddv, int B, int H, int W, int mode, void* stream);
 int cdfo_flow_warp_bwd(const float* g, int ldg, const float* mv, long long mv_bstride, int B, int H, int W, int C, float* dx,
                        int ldo, void* stream);
+int cdfo_flow_warp_bwd_fixed(const float* g, int ldg, const float* mv, long long mv_bstride, int B, int H, int W, int C,
+                             const void* slots2, long long* acc, float* dx, int ldo, void* stream);
 int cdfo_resample2_bwd(const float* g, int ldg, int B, int H, int W, int C, int up, float* din, int ldo, void* stream);
 
 /* ---- pixel-local operators of the CVSR_V7 forward (v7_ops.hip) ---------------------------
@@ -905,7 +911,25 @@ int cdfo_tof_epe(const double* a, const double* b, int K, int h, int w, double* 
  *                     pixel's sum of squares over the channels.  C a multiple of 4.
  * cdfo_lpips_fold:    partials: the layers' [N][strips[k]] blocks one behind the other -> out [N][layers], the strips of (frame,
  *                     layer) added in index order and divided by counts[k].  `strips` and `counts` are in HOST memory, at most
- *                     CDFO_LPIPS_MAX_LAYERS of each. */
+ *                     CDFO_LPIPS_MAX_LAYERS of each.
+ * The training loss (cdfo_amd/loss.py: lpips_loss) and its adjoint; the gradient goes to the result's samples only:
+ * cdfo_lpips_stem_f32: cdfo_lpips_stem_u8 of fp32 samples (src 4-byte aligned) used as x themselves: no division, no clamp, no
+ *                     quantisation.  Samples k / 255 (correctly rounded) give the bits of the 8-bit form on k.
+ * cdfo_lpips_dist_bwd: fa, fb [N][h][w][C], lin [C] fp64, gscale [N] fp32 (the upstream gradient of each frame's layer distance),
+ *                     gin [N][h][w][C] or null (the gradient that arrives at this tap from the deeper stage) -> gout [N][h][w][C]:
+ *                     per pixel in fp64, r = 1 / (|fa| + 1e-10), u_c = fa_c / (|fa| + 1e-10) - fb_c / (|fb| + 1e-10) (two quotients
+ *                     as in cdfo_lpips_dist: equal stacks give exactly 0), q = sum_c lin_c u_c fa_c,
+ *                     t_c = gscale_n / (h w) 2 r (lin_c u_c - (r q / |fa|) fa_c), gout_c = fa_c > 0 ? (float)(t_c + gin_c) : +0
+ *                     -- a select: a NaN or an infinity under a ReLU output that is not positive is dropped, the 0 / 0 of a pixel
+ *                     whose tap is zero in every channel included.  C a multiple of 16.
+ * cdfo_lpips_pool2_bwd: x [N][H][W][C] (the pool's input), g [N][H/2][W/2][C] -> gx [N][H][W][C]: g goes to the element
+ *                     cdfo_lpips_pool2 took (the first maximum in the order (0,0), (0,1), (1,0), (1,1); a NaN takes the cell, the
+ *                     last one if there are several), +0 to the other three and to the row and column the floor drops.  Exact.
+ * cdfo_lpips_stem_bwd: g [N][h][w][C0] (already masked by the stem's output), wf [C0][3][3] fp32 on the device -> gx [N][h][w] =
+ *                     sum_o sum_ky sum_kx wf[o][ky][kx] g[y + 1 - ky][x + 1 - kx][o], g zero outside: the adjoint of the scaling
+ *                     and conv1_1 with wf[o][ky][kx] = k sum_c weight[o][c][ky][kx] / scale_c, k = 2 with `normalize`, else 1,
+ *                     formed by the caller.  C0 as for the stem.
+ * Every element of every output is written; nothing is atomic. */
 #define CDFO_LPIPS_MIN 16
 #define CDFO_LPIPS_STRIP 2
 #define CDFO_LPIPS_STEM_MAXC 256
@@ -917,6 +941,12 @@ int cdfo_lpips_stem_u16(const unsigned short* src, int pitch, long long fstride,
 int cdfo_lpips_pool2(const float* src, int N, int H, int W, int C, float* dst, void* stream);
 int cdfo_lpips_dist(const float* fa, const float* fb, const double* lin, int N, int h, int w, int C, double* partials, void* stream);
 int cdfo_lpips_fold(const double* partials, int N, int layers, const int* strips, const long long* counts, double* out, void* stream);
+int cdfo_lpips_stem_f32(const float* src, int pitch, long long fstride, int N, int h, int w, const float* weight,
+                        const float* bias, int C0, int normalize, float* dst, void* stream);
+int cdfo_lpips_dist_bwd(const float* fa, const float* fb, const double* lin, const float* gscale, const float* gin, int N, int h,
+                        int w, int C, float* gout, void* stream);
+int cdfo_lpips_pool2_bwd(const float* x, const float* g, int N, int H, int W, int C, float* gx, void* stream);
+int cdfo_lpips_stem_bwd(const float* g, const float* wf, int N, int h, int w, int C0, float* gx, void* stream);
 
 /* ---- training batches and the training loss (train_batch.hip; cdfo_amd/train_data.py, cdfo_amd/loss.py) ----
  * cdfo_train_batch:   the resident clip set -- lr, pms, hr unsigned and rms signed 8-bit [S][T][H][W] ([S][T][4H][4W] for hr), ufs
