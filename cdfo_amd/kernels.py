@@ -2208,3 +2208,84 @@ def charbonnier(sr: torch.Tensor, hr: torch.Tensor, eps: float):
     check(_lib.lib().cdfo_charbonnier(_vp(sr), _vp(hr), C.c_longlong(n), C.c_float(eps), _vp(g), _vp(partial), CHARBONNIER_MAX_BLOCKS,
                                       _vp(loss), _stream()), "cdfo_charbonnier")
     return loss, g
+
+
+FFL_MIN, FFL_MAX = 16, 512           # CDFO_FFL_MIN, CDFO_FFL_MAX of include/cdfo_hip.h
+_ffl_tables = {}                     # (device, n) -> the twiddle table of length n there: uploaded once per process and device
+
+
+def ffl_size(n) -> bool:
+    """Whether ``n`` is a transform length of the focal frequency loss: a power of two from 16 to 512."""
+    return isinstance(n, int) and FFL_MIN <= n <= FFL_MAX and n & (n - 1) == 0
+
+
+def ffl_twiddles(n: int) -> np.ndarray:
+    """fp32 [n/2, 2]: (cos, sin)(2 pi k / n) for k < n / 2, computed in fp64 and rounded once."""
+    if not ffl_size(n):
+        raise ValueError(f"ffl_twiddles: a power of two from {FFL_MIN} to {FFL_MAX} expected, got {n!r}")
+    a = 2.0 * np.pi * np.arange(n // 2, dtype=np.float64) / n
+    return np.stack((np.cos(a), np.sin(a)), axis=1).astype(np.float32)
+
+
+def _ffl_table_on(device, n: int) -> torch.Tensor:
+    if (device, n) not in _ffl_tables:
+        _ffl_tables[device, n] = torch.from_numpy(ffl_twiddles(n)).to(device)
+    return _ffl_tables[device, n]
+
+
+def _ffl_frames(sr: torch.Tensor, hr: torch.Tensor, who: str):
+    """(N, H, W) of two dense fp32 device tensors [N,1,H,W] or [N,H,W] of one shape on one device; anything else is a ValueError."""
+    for name, t in (("sr", sr), ("hr", hr)):
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() not in (3, 4) or (t.dim() == 4 and t.shape[1] != 1):
+            raise ValueError(f"{who}: {name} must be a dense fp32 device tensor [N,1,H,W] or [N,H,W], got {t.dtype} {tuple(t.shape)} "
+                             f"strides {t.stride()}")
+    if sr.shape != hr.shape or sr.device != hr.device or sr.shape[0] == 0:
+        raise ValueError(f"{who}: sr and hr must have one shape with N >= 1 on one device, got {tuple(sr.shape)} and {tuple(hr.shape)}")
+    N, H, W = int(sr.shape[0]), int(sr.shape[-2]), int(sr.shape[-1])
+    if not ffl_size(H) or not ffl_size(W) or N > 65535:
+        raise ValueError(f"{who}: H and W must be powers of two from {FFL_MIN} to {FFL_MAX} and N at most 65535, got N = {N}, {H} x {W}")
+    return N, H, W
+
+
+def ffl_alpha(alpha, who: str) -> float:
+    """``alpha`` as the float the kernels take, or a ValueError: a finite real number >= 0 (it crosses the C ABI as fp32)."""
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not np.isfinite(alpha) or alpha < 0 or alpha > 3.4e38:
+        raise ValueError(f"{who}: alpha must be a finite number >= 0, got {alpha!r}")
+    return float(alpha)
+
+
+def _ffl_spectrum(sr, hr, N, H, W):
+    """(F fp32 [N,H,W,2], pmax fp64 [N,P]) of cdfo_ffl_spectrum."""
+    dev = sr.device
+    P = W // (8 if H > 256 else 16)                                          # cdfo_ffl_tiles
+    F = torch.empty((N, H, W, 2), dtype=torch.float32, device=dev)
+    pmax = torch.empty((N, P), dtype=torch.float64, device=dev)
+    check(_lib.lib().cdfo_ffl_spectrum(_vp(sr), _vp(hr), N, H, W, _vp(_ffl_table_on(dev, H)), _vp(_ffl_table_on(dev, W)), _vp(F), _vp(pmax),
+                                       N * P, _stream()), "cdfo_ffl_spectrum")
+    return F, pmax
+
+
+def ffl_spectrum(sr: torch.Tensor, hr: torch.Tensor) -> torch.Tensor:
+    """complex64 [N,H,W]: fft2(sr - hr, norm="ortho"), the full spectrum.  A test surface of the loss's transform, not a general FFT."""
+    N, H, W = _ffl_frames(sr, hr, "ffl_spectrum")
+    return torch.view_as_complex(_ffl_spectrum(sr, hr, N, H, W)[0])
+
+
+def ffl_loss(sr: torch.Tensor, hr: torch.Tensor, alpha: float = 1.0, want_grad: bool = True):
+    """(loss fp32 [N], g fp32 like sr or None): the focal frequency loss of each frame and, with ``want_grad``, its derivative by sr
+    (the two inverse passes; skipped otherwise).  Scratch: the spectrum, 8 N H W bytes, and two small fp64 arrays; no host sync."""
+    N, H, W = _ffl_frames(sr, hr, "ffl_loss")
+    alpha = ffl_alpha(alpha, "ffl_loss")
+    dev = sr.device
+    F, pmax = _ffl_spectrum(sr, hr, N, H, W)
+    S = max(1, H * W // 4096)                                                # cdfo_ffl_strips
+    partial = torch.empty((N, S), dtype=torch.float64, device=dev)
+    loss = torch.empty(N, dtype=torch.float32, device=dev)
+    check(_lib.lib().cdfo_ffl_weight(_vp(F), _vp(pmax), pmax.shape[1], N, H, W, C.c_float(alpha), int(bool(want_grad)), _vp(partial), N * S,
+                                     _vp(loss), _stream()), "cdfo_ffl_weight")
+    if not want_grad:
+        return loss, None
+    g = torch.empty_like(sr)
+    check(_lib.lib().cdfo_ffl_inverse(_vp(F), N, H, W, _vp(_ffl_table_on(dev, H)), _vp(_ffl_table_on(dev, W)), _vp(g), _stream()),
+          "cdfo_ffl_inverse")
+    return loss, g

@@ -4,7 +4,11 @@ a six-operator torch expression and a ``loss.item()`` per step.
 
 `lpips_loss` is the perceptual distance the evaluators score with (`cdfo_amd.metrics.lpips_u8`) as a training loss, the pairing of the
 reference's opt/loss.py with opt/lpips: the metric's launches behind a float stem, and an explicit backward through the frozen trunk
-on the device (csrc/lpips.hip)."""
+on the device (csrc/lpips.hip).
+
+`focal_frequency_loss` is the frequency term of the reference's ``Focal_Frequecny_Loss`` / ``Charbonnier_FFL_Loss``
+(opt/deep_learning.py:192-220), by the project's own definition written after the defaults of the package those classes call: a 2-D
+FFT in HIP, the spectrum weighted by its own magnitude, and the inverse FFT for the gradient (csrc/ffl.hip)."""
 from __future__ import annotations
 
 import torch
@@ -102,3 +106,48 @@ def lpips_loss(sr: torch.Tensor, hr: torch.Tensor, model, normalize: bool = True
         raise ValueError(f"lpips_loss: two tensors of one shape on one device expected, got {tuple(sr.shape)} and {tuple(hr.shape)}")
     M.lpips_size(a.shape[1], a.shape[2])
     return _Lpips.apply(sr, hr, params, bool(normalize))
+
+
+class _FocalFrequency(torch.autograd.Function):
+    """As `_Charbonnier`: the forward leaves the derivative beside the loss.  Entered only when ``sr`` needs a gradient."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, alpha):
+        with K.on_device(sr):
+            loss, g = K.ffl_loss(sr.detach(), hr.detach(), alpha, want_grad=True)
+        ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (g,) = ctx.saved_tensors
+        return grad_out.view(-1, *([1] * (g.dim() - 1))) * g, None, None
+
+
+def focal_frequency_loss(sr: torch.Tensor, hr: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
+    """Per-frame focal frequency loss of ``sr`` to ``hr``: fp32 [N] on the device.  The project's own definition, after the defaults
+    of the ``focal_frequency_loss`` package (patch_factor 1, no averaged spectrum, no log or batch matrix); parity with the package is
+    not pinned.  For a frame of H x W samples: ``d = sr - hr`` (one fp32 subtraction; the transform is linear, so the package's
+    difference of two spectra is this in exact arithmetic), ``F = fft2(d, norm="ortho")``, ``D = Re(F)^2 + Im(F)^2``,
+    ``M = sqrt(D) ** alpha`` (0 ** 0 = 1), ``w = M / max(M)`` over the frame's bins, NaN -> 0, clamped to [0, 1] and held constant for
+    the gradient, ``loss = sum(w D) / (H W)``.  ``alpha = 0`` weighs every bin 1: the loss is mean(d^2).
+
+    ``sr``, ``hr``: dense fp32 device tensors [N,1,H,W] or [N,H,W] of one shape on one device, H and W powers of two from 16 to 512
+    (they may differ); ``alpha`` a finite number >= 0 (the kernels take it as fp32).  Anything else is a ValueError before any device
+    work; nothing is made contiguous or cast; CPU tensors raise NotImplementedError.  Gradient flows to ``sr`` only (``hr`` gets
+    None) and is exact, ``2 / (H W) Re(ifft2(w F, norm="ortho"))``, scaled by the upstream gradient of the frame.  The weights, the
+    terms and their sum are fp64 in a fixed order and nothing is atomic: equal inputs give equal bits, forward and backward; ``sr``
+    equal to ``hr`` gives exactly 0 and an all-zero gradient.  A frame with a non-finite sample gets a NaN loss and an unspecified
+    gradient; the other frames are untouched.  There is no host synchronisation.
+
+    Kept between forward and backward: the gradient, ``4 N H W`` bytes (nothing under ``no_grad`` or when ``sr`` needs no gradient:
+    the inverse passes are then not launched).  The forward also holds, until it returns, the spectrum (``8 N H W`` bytes) and two
+    fp64 arrays of ``N W / 16`` (``N W / 8`` at H = 512) and ``N max(1, H W / 4096)`` values."""
+    if not sr.is_cuda or not hr.is_cuda:
+        raise NotImplementedError("focal_frequency_loss: the HIP path needs device tensors (there is no CPU fallback)")
+    K._ffl_frames(sr, hr, "focal_frequency_loss")
+    alpha = K.ffl_alpha(alpha, "focal_frequency_loss")
+    if not (torch.is_grad_enabled() and sr.requires_grad):                  # hr gets no gradient: nothing to record
+        with K.on_device(sr):
+            return K.ffl_loss(sr.detach(), hr.detach(), alpha, want_grad=False)[0]
+    return _FocalFrequency.apply(sr, hr, alpha)

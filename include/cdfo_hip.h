@@ -984,6 +984,38 @@ int cdfo_train_batch_ra(const unsigned char* lr, const unsigned char* pms, const
 int cdfo_charbonnier(const float* sr, const float* hr, long long n, float eps, float* grad, double* partial, int partial_cap,
                      float* loss, void* stream);
 
+/* ---- the focal frequency loss and its 2-D FFT pair (ffl.hip; cdfo_amd/loss.py: focal_frequency_loss) ----
+ * Frames are dense fp32 [N][H][W]; H and W are powers of two from CDFO_FFL_MIN to CDFO_FFL_MAX and may differ, 1 <= N <= 65535.  A
+ * spectrum F is complex fp32 [N][H][W] (re, im interleaved, 8-byte aligned), bin (ky, kx) = sum_yx d[y][x] exp(-2 pi i (ky y / H +
+ * kx x / W)) / sqrt(H W): the full spectrum of numpy's fft2(norm="ortho").  tw_h, tw_w: the twiddle tables of the two lengths on the
+ * device, n / 2 pairs (cos, sin)(2 pi k / n) in fp32 for length n, computed in fp64 and rounded once by the caller, 8-byte aligned
+ * (one pointer serves both when H == W).  Every entry point checks its arguments before any HIP call: a null pointer, N, H or W
+ * outside the above, a scratch capacity that is too small and an alpha that is negative or not finite are CDFO_EINVAL.
+ * cdfo_ffl_tiles:    P(H, W) = W / 16 (W / 8 when H = 512), the column tiles of a frame; cdfo_ffl_strips: S(H, W) = max(1, H W /
+ *                    4096), the strips of the weight pass.  Functions of the shape alone; CDFO_EINVAL for a size outside the set.
+ * cdfo_ffl_spectrum: d = sr - hr (one fp32 subtraction) -> F = fft2(d) / sqrt(H W), the scale applied once in fp64, and pmax [N][P]
+ *                    fp64: per column tile the maximum of D = re^2 + im^2 of the ROUNDED fp32 bins, formed in fp64 (a NaN is
+ *                    skipped).  pmax_cap >= N P doubles.  Two launches.
+ * cdfo_ffl_weight:   F and pmax [N][P] (any P >= 1 values per frame whose maximum is the frame's largest D) -> loss[n] = sum_bins(w D)
+ *                    / (H W), D as above, w = M / max M with M = sqrt(D)^alpha (alpha == 1: no pow; 0^0 = 1), NaN -> 0, clamped to
+ *                    [0, 1]; w, the terms and the sum in fp64, strips of 4096 bins added in index order, one rounding to fp32.  With
+ *                    `apply` F is overwritten by w F (product in fp64, rounded once).  partial: scratch of partial_cap >= N S
+ *                    doubles.  A frame with a non-finite bin gets a NaN loss; other frames are untouched.  Two launches.
+ * cdfo_ffl_inverse:  F -> g [N][H][W] = 2 / (H W) Re(ifft2(F) sqrt(H W)), i.e. the gradient of the loss when F holds w F; the scale
+ *                    is applied once in fp64, the imaginary part is dropped.  F IS OVERWRITTEN (the column pass works in place).
+ *                    Two launches.
+ * Radix-2 transforms in LDS; no atomics, grids are functions of (N, H, W) alone, equal inputs give equal bits.  Every element of
+ * every output is written. */
+#define CDFO_FFL_MIN 16
+#define CDFO_FFL_MAX 512
+int cdfo_ffl_tiles(int H, int W);
+int cdfo_ffl_strips(int H, int W);
+int cdfo_ffl_spectrum(const float* sr, const float* hr, int N, int H, int W, const float* tw_h, const float* tw_w, float* F,
+                      double* pmax, int pmax_cap, void* stream);
+int cdfo_ffl_weight(float* F, const double* pmax, int P, int N, int H, int W, float alpha, int apply, double* partial,
+                    int partial_cap, float* loss, void* stream);
+int cdfo_ffl_inverse(float* F, int N, int H, int W, const float* tw_h, const float* tw_w, float* g, void* stream);
+
 /* ---- optional per-launch HIP-event timing on the launch stream (bench.py's live roofline figures) ----------- */
 int cdfo_prof_begin(int max_records);
 int cdfo_prof_end(int* launches, double* ms, double* flops, double* bytes, int nkid);

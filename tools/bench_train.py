@@ -1,10 +1,12 @@
 """Developer benchmark (GPU box only): one training step of CVSR_V8 at the reference script's batch (train_LD_37.py: 20 crops of
 64x64, Charbonnier loss) -- forward and backward through the HIP autograd path, timed separately.
 
-    python tools/bench_train.py [B H W] [--lpips random]
+    python tools/bench_train.py [B H W] [--lpips random | --ffl]
 
 --lpips random: passes with and without the perceptual term alternate in one process; the term is 0.1 * cdfo_amd.loss.lpips_loss with a
-seeded random trunk of the published widths (metrics.lpips_random_params), its forward counted with the forward."""
+seeded random trunk of the published widths (metrics.lpips_random_params), its forward counted with the forward.
+--ffl: the same alternation with and without the frequency term, 1.0 * cdfo_amd.loss.focal_frequency_loss (its inverse passes run in
+the forward, as Charbonnier's derivative does); B H W then need 4 H and 4 W powers of two up to 512."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -23,26 +25,36 @@ def main():
         from cdfo_amd.loss import lpips_loss
         from cdfo_amd.metrics import lpips_random_params
         lpips = lpips_random_params()
+    ffl = "--ffl" in argv
+    if ffl:
+        argv.remove("--ffl")
+        if lpips is not None:
+            sys.exit("bench_train: --lpips or --ffl, one at a time")
+        from cdfo_amd.loss import focal_frequency_loss
     B, H, W = (int(a) for a in argv[:3]) if len(argv) >= 3 else (20, 64, 64)
     m = CVSR_V8().cuda().train()
     inp = random_inputs(B, H, W, 7)
     d = {k: v.cuda() for k, v in inp.items() if k != "gumbel_u"}
     hr = torch.rand(B, 1, 4 * H, 4 * W, device="cuda")
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    for it in range(4 if lpips is None else 12):
+    extra = lpips is not None or ffl
+    for it in range(12 if extra else 4):
         with_lpips = lpips is not None and it % 2 == 1
+        with_ffl = ffl and it % 2 == 1
         m.zero_grad(set_to_none=True)
         ev[0].record()
         out, _ = m(d["x"], d["mvs0"], d["mvs1"], d["pms"], d["rms"], d["ufs"])
         loss = torch.sum(torch.sqrt((out - hr) ** 2 + 1e-4))
         if with_lpips:
             loss = loss + 0.1 * lpips_loss(out, hr, lpips).sum()
+        if with_ffl:
+            loss = loss + focal_frequency_loss(out, hr).sum()
         ev[1].record()
         loss.backward()
         ev[2].record()
         torch.cuda.synchronize()
-        if it > (0 if lpips is None else 1):
-            print(f"training step {B}x{H}x{W}{' + lpips' if with_lpips else ''}: forward {ev[0].elapsed_time(ev[1]):.1f} ms, backward {ev[1].elapsed_time(ev[2]):.1f} ms", flush=True)
+        if it > (1 if extra else 0):
+            print(f"training step {B}x{H}x{W}{' + lpips' if with_lpips else ' + ffl' if with_ffl else ''}: forward {ev[0].elapsed_time(ev[1]):.1f} ms, backward {ev[1].elapsed_time(ev[2]):.1f} ms", flush=True)
 
 
 if __name__ == "__main__":

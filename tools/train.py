@@ -2,7 +2,7 @@
 
     python tools/train.py --seq LR_DIR SIDE_DIR HR_DIR [--seq ...] --out DIR [--coding LD] [--epochs 30000] [--batch-size 20] [--crop 64]
                           [--lr 1e-4] [--weight-decay 1e-5] [--val-itv 200] [--val LR_DIR SIDE_DIR GT_DIR] [--val-coding LD] [--weights FILE.pth]
-                          [--lpips MODEL|random --lpips-weight W]
+                          [--lpips MODEL|random --lpips-weight W] [--ffl-weight W [--ffl-alpha A]]
     python tools/train.py --synthetic S T H W --out DIR ...
 
 --coding RA trains the random-access configuration: the clip set keeps both motion lists (the mvl1 files beside mvl0) and the flow field
@@ -11,6 +11,9 @@ is built from both (opt/data_RA_bi.py); --batch-size and --val-itv then default 
 --lpips MODEL adds the perceptual term to the step's loss, charbonnier + W * sum of the batch's per-frame LPIPS (cdfo_amd.loss.lpips_loss):
 MODEL is the caller's .npz (tools/make_lpips_model.py; the project ships none), `random` a seeded random trunk of the published widths,
 which says that the loop runs and nothing about quality.  --lpips-weight W is then required, finite and positive.
+
+--ffl-weight W adds the frequency term, W * sum of the batch's per-frame focal frequency loss (cdfo_amd.loss.focal_frequency_loss: the
+spectrum of sr - hr weighted by its own magnitude to the power --ffl-alpha, default 1); --crop must then be a power of two from 4 to 128.
 
 --seq names one training sequence in the layout of cdfo_amd/priors.py (every frame with its own prior files, 00000 included) and a
 directory of 8-bit grey HR frames %05d.png.  --synthetic trains on S random sequences of T frames of H x W instead
@@ -41,6 +44,8 @@ def main():
     ap.add_argument("--seed", type=int, default=4)
     ap.add_argument("--lpips", metavar="MODEL|random", help="an LPIPS model (.npz) or `random`: adds --lpips-weight * LPIPS to the loss")
     ap.add_argument("--lpips-weight", type=float, default=0.0)
+    ap.add_argument("--ffl-weight", type=float, default=0.0, help="adds --ffl-weight * the focal frequency loss to the step's loss")
+    ap.add_argument("--ffl-alpha", type=float, default=1.0, help="the exponent of the spectrum weight (needs --ffl-weight)")
     a = ap.parse_args()
     if (a.seq is None) == (a.synthetic is None):
         ap.error("--seq LR_DIR SIDE_DIR HR_DIR (once per sequence), or --synthetic S T H W")
@@ -68,7 +73,8 @@ def main():
         clips = ClipSet.from_directories(a.seq, coding=a.coding)
     print(f"{clips.coding}: {len(clips)} sequences of {clips.T} frames of {clips.H}x{clips.W} on the device")
     fit(model, clips, a.epochs, a.out, batch_size=a.batch_size, crop=a.crop, lr=a.lr, weight_decay=a.weight_decay, val_itv=a.val_itv,
-        val=a.val, seed=a.seed, val_coding=a.val_coding, lpips=lpips, lpips_weight=a.lpips_weight)
+        val=a.val, seed=a.seed, val_coding=a.val_coding, lpips=lpips, lpips_weight=a.lpips_weight, ffl_weight=a.ffl_weight,
+        ffl_alpha=a.ffl_alpha)
 
 
 if __name__ == "__main__":
