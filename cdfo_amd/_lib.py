@@ -50,7 +50,9 @@ def header_prototypes(path: str = HEADER_PATH):
         ret, name, args = m.group(1), m.group(2), m.group(3).strip()
         at = []
         if args and args != "void":
-            at = [_ctype(" ".join(a.split()), f"prototype of {name}") for a in args.split(",")]
+            decls = [" ".join(a.split()) for a in args.split(",")]
+            # a double by value crosses only as an argument (adam.hip's hyper-parameters); cdfo_conv_args has none, and _ctype refuses it
+            at = [C.c_double if "*" not in d and d.startswith("double") else _ctype(d, f"prototype of {name}") for d in decls]
         protos[name] = (C.c_char_p if ret.startswith("const char") else C.c_longlong if ret == "long long" else C.c_int, at)
     return protos
 

@@ -5,6 +5,8 @@ With an LPIPS model the step's loss gains a perceptual term, `cdfo_amd.loss.lpip
 with an ``ffl_weight`` it gains a frequency term, `cdfo_amd.loss.focal_frequency_loss` (opt/deep_learning.py's Charbonnier_FFL_Loss)."""
 from __future__ import annotations
 
+import contextlib
+import copy
 import math
 import os
 from datetime import datetime
@@ -28,7 +30,8 @@ def learning_rate(lr0: float, epoch: int) -> float:
 def fit(model, clips: ClipSet, epochs: int, out_dir: str, batch_size: int = 20, crop: int = 64, lr: float = 1e-4,
         weight_decay: float = 1e-5, val_itv: int = 200, val: Optional[Sequence[str]] = None, seed: int = 4, start_epoch: int = 0,
         log: Callable[[str], None] = print, val_coding: str = "LD", lpips=None, lpips_weight: float = 0.0, ffl_weight: float = 0.0,
-        ffl_alpha: float = 1.0) -> List[float]:
+        ffl_alpha: float = 1.0, optimizer: str = "torch", max_grad_norm: Optional[float] = None, deterministic: bool = False,
+        save_state: bool = False, resume: Optional[str] = None) -> List[float]:
     """Train ``model`` (a ``CVSR_V8`` on the clip set's device) for epochs ``start_epoch .. epochs - 1``; returns the epochs' average
     losses.  Adam with ``lr`` and ``weight_decay``; the rate of each epoch is set directly (`learning_rate`).  Every ``val_itv`` epochs
     ``state_dict()`` goes to ``<out_dir>/ckpt/epoch-N.pth`` and, with ``val = (lr_dir, side_dir, gt_dir)``, that sequence is evaluated
@@ -46,7 +49,20 @@ def fit(model, clips: ClipSet, epochs: int, out_dir: str, batch_size: int = 20, 
     ``[ | lpips: %f]`` `` | ffl: %f`` (unweighted).  The run is reproducible as the LPIPS run is (`autograd.FLOW_WARP_FIXED`).  A
     negative, non-finite or bool weight, an ``ffl_alpha`` other than 1.0 without a weight (or one that is not a finite number >= 0)
     and a ``crop`` that is not a power of two from 4 to 128 (the HR crop is the transform's size) are ValueErrors before the first
-    batch.  With ``ffl_weight = 0.0`` nothing changes."""
+    batch.  With ``ffl_weight = 0.0`` nothing changes.
+    ``optimizer``: "torch" (``torch.optim.Adam``) or "device" (`cdfo_amd.optim.DeviceAdam` with the same hyper-parameters: three
+    launches a step, a step with a non-finite gradient is skipped instead of ending the run).  With "device" the epoch's line ends with
+    `` | grad norm: %f``, the mean norm before clipping over the epoch's unskipped steps, and `` | skipped: %d`` when the epoch
+    skipped steps; both come with the losses in the epoch's one read.  ``max_grad_norm``: a finite positive number clips the
+    gradient to that norm (``clip_grad_norm_``'s coefficient) and needs ``optimizer="device"``.  ``deterministic``: sets
+    `autograd.FLOW_WARP_FIXED` for the run, as an LPIPS or FFL term does.  ``save_state``: beside every ``epoch-N.pth`` (unchanged)
+    goes ``epoch-N.state.pth``: the optimizer's state dict and kind, the epoch, the averages so far, the states of the plans'
+    generator and of torch's CPU and device generators, and the run-defining arguments (`RUN_ARGUMENTS`); plain tensors and Python
+    values, written after the checkpoint's validation.  ``resume``: such a file; the weights come from its sibling ``epoch-N.pth``,
+    everything above is restored and the run continues at epoch N (``start_epoch`` stays 0), bit for bit when the run is
+    reproducible (``deterministic`` or a loss term that sets it).  A state of either optimizer continues on the other.  A state file
+    whose run-defining arguments differ from the call's (the first difference is named), a missing sibling and ``epochs <= N`` are
+    ValueErrors before the first batch.  Without these keywords nothing changes."""
     from .streaming import check_coding
     check_coding(val_coding)
     if lpips is None:
@@ -68,32 +84,192 @@ def fit(model, clips: ClipSet, epochs: int, out_dir: str, batch_size: int = 20, 
             raise ValueError(f"fit: ffl_weight needs a crop that is a power of two from 4 to 128 (HR 16 .. 512), got crop = {crop!r}")
     elif isinstance(ffl_alpha, bool) or ffl_alpha != 1.0:
         raise ValueError(f"fit: ffl_alpha {ffl_alpha!r} needs an ffl_weight")
-    if lpips is not None or ffl_weight:    # two runs from one seed then leave equal weights: the warp's adjoint adds in a fixed-point order
-        from . import autograd
-        was, autograd.FLOW_WARP_FIXED = autograd.FLOW_WARP_FIXED, True
-        try:
-            return _fit(model, clips, epochs, out_dir, batch_size, crop, lr, weight_decay, val_itv, val, seed, start_epoch, log, val_coding,
-                        lpips, lpips_weight, float(ffl_weight), ffl_alpha)
-        finally:
-            autograd.FLOW_WARP_FIXED = was
-    return _fit(model, clips, epochs, out_dir, batch_size, crop, lr, weight_decay, val_itv, val, seed, start_epoch, log, val_coding, None, 0.0)
+    if optimizer not in ("torch", "device"):
+        raise ValueError(f"fit: optimizer must be 'torch' or 'device', got {optimizer!r}")
+    if max_grad_norm is not None:
+        from .optim import _check_max_norm
+        max_grad_norm = _check_max_norm(max_grad_norm, "fit")
+        if optimizer != "device":
+            raise ValueError("fit: max_grad_norm needs optimizer='device'")
+    if not lpips_weight:
+        lpips_weight = 0.0
+    run = run_arguments(batch_size, crop, lr, weight_decay, seed, clips.coding, lpips_weight, float(ffl_weight), ffl_alpha, max_grad_norm)
+    state = None
+    if resume is not None:
+        if start_epoch != 0:
+            raise ValueError(f"fit: resume continues at the state file's epoch; start_epoch must stay 0, got {start_epoch!r}")
+        state = read_state(resume, run, epochs)
+    # two runs from one seed then leave equal weights: the warp's adjoint adds in a fixed-point order
+    with _flow_warp_fixed(bool(deterministic) or lpips is not None or bool(ffl_weight)):
+        return _fit(model, clips, epochs, out_dir, batch_size, crop, lr, weight_decay, val_itv, val, seed, start_epoch, log, val_coding,
+                    lpips, lpips_weight, float(ffl_weight), ffl_alpha, optimizer, max_grad_norm, bool(save_state), state, run)
+
+
+@contextlib.contextmanager
+def _flow_warp_fixed(on: bool):
+    """`autograd.FLOW_WARP_FIXED` set for the block when ``on``: the one place a run is made reproducible."""
+    if not on:
+        yield
+        return
+    from . import autograd
+    was, autograd.FLOW_WARP_FIXED = autograd.FLOW_WARP_FIXED, True
+    try:
+        yield
+    finally:
+        autograd.FLOW_WARP_FIXED = was
+
+
+# ---- the state file: what a run needs, beside its weights, to continue bit for bit -------------------------------------------------
+
+RUN_ARGUMENTS = ("batch_size", "crop", "lr", "weight_decay", "seed", "coding", "lpips_weight", "ffl_weight", "ffl_alpha", "max_grad_norm")
+
+
+def run_arguments(batch_size, crop, lr, weight_decay, seed, coding, lpips_weight, ffl_weight, ffl_alpha, max_grad_norm) -> dict:
+    """The arguments that define a run, as the state file keeps them (`RUN_ARGUMENTS`' order)."""
+    return dict(zip(RUN_ARGUMENTS, (batch_size, crop, lr, weight_decay, seed, coding, lpips_weight, ffl_weight, ffl_alpha, max_grad_norm)))
+
+
+def check_run_arguments(saved: dict, current: dict, path: str = "the state file") -> None:
+    """ValueError naming the first of `RUN_ARGUMENTS` in which the state file's run differs from the call's."""
+    for name in RUN_ARGUMENTS:
+        if name not in saved:
+            raise ValueError(f"fit: {path} does not record {name}")
+        if saved[name] != current[name] or (saved[name] is None) != (current[name] is None):
+            raise ValueError(f"fit: {path} was written by a run with {name} = {saved[name]!r}, this call has {name} = {current[name]!r}")
+
+
+def _plain(x):
+    """Tensors on the CPU, containers and Python values as they are: what ``torch.load`` reads with its defaults."""
+    if isinstance(x, torch.Tensor):
+        return x.detach().cpu()
+    if isinstance(x, dict):
+        return {k: _plain(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(_plain(v) for v in x)
+    if isinstance(x, np.generic):
+        return x.item()
+    return x
+
+
+def generator_states(rng: np.random.Generator, device=None) -> dict:
+    """The state of the plans' generator, of torch's CPU generator and of torch's generator of ``device`` (the Gumbel keys' source)."""
+    cuda = device is not None and torch.device(device).type == "cuda"
+    return {"numpy": _plain(copy.deepcopy(rng.bit_generator.state)), "torch_cpu": torch.get_rng_state().clone(),
+            "torch_device": torch.cuda.get_rng_state(device).clone() if cuda else None}
+
+
+def set_generator_states(rng: np.random.Generator, states: dict, device=None) -> None:
+    """Put `generator_states` back: the next draws are those that followed the call that took them."""
+    if states["numpy"]["bit_generator"] != rng.bit_generator.state["bit_generator"]:
+        raise ValueError(f"fit: the state file's plan generator is a {states['numpy']['bit_generator']}, this run's a "
+                         f"{rng.bit_generator.state['bit_generator']}")
+    rng.bit_generator.state = states["numpy"]
+    torch.set_rng_state(states["torch_cpu"].cpu())
+    if states.get("torch_device") is not None and device is not None and torch.device(device).type == "cuda":
+        torch.cuda.set_rng_state(states["torch_device"].cpu(), device)
+
+
+def state_path(out_dir: str, epoch: int) -> str:
+    return os.path.join(out_dir, "ckpt", "epoch-%d.state.pth" % epoch)
+
+
+def weights_beside(path: str) -> str:
+    """``.../epoch-N.pth`` for the state file ``.../epoch-N.state.pth``."""
+    if not path.endswith(".state.pth"):
+        raise ValueError(f"fit: resume takes a state file (epoch-N.state.pth), got {path!r}")
+    return path[:-len(".state.pth")] + ".pth"
+
+
+def write_state(path: str, optimizer, kind: str, epoch: int, averages, rng, device, run: dict) -> None:
+    opt = optimizer.state_dict()
+    torch.save({"optimizer": _plain(opt), "optimizer_kind": kind, "epoch": int(epoch), "averages": [float(a) for a in averages],
+                "generators": generator_states(rng, device), "run": _plain(dict(run))}, path)
+
+
+def read_state(path: str, run: dict, epochs: int) -> dict:
+    """The state file at ``path``, checked against the call: its run-defining arguments, its sibling weights, its epoch."""
+    if not os.path.isfile(path):
+        raise ValueError(f"fit: no state file at {path!r}")
+    weights = weights_beside(path)
+    state = torch.load(path, map_location="cpu")
+    for key in ("optimizer", "optimizer_kind", "epoch", "averages", "generators", "run"):
+        if not isinstance(state, dict) or key not in state:
+            raise ValueError(f"fit: {path!r} is not a state file: no {key!r}")
+    check_run_arguments(state["run"], run, repr(path))
+    if not os.path.isfile(weights):
+        raise ValueError(f"fit: the weights of {path!r} are missing: no {weights!r}")
+    if epochs <= state["epoch"]:
+        raise ValueError(f"fit: {path!r} is the state after epoch {state['epoch']}; epochs = {epochs!r} leaves nothing to run")
+    state["weights"] = weights
+    return state
+
+
+def _adam_state_by_name(opt_state: dict, all_names: List[str]):
+    """An optimizer state of either kind as a `DeviceAdam.state_dict()` whose ``names`` say which parameters the moments belong to;
+    None for a torch state that holds no moments yet."""
+    from .optim import adam_moments
+    if "param_groups" not in opt_state:
+        if opt_state.get("names") is None:
+            raise ValueError("fit: the state file's optimizer state does not name its parameters")
+        return opt_state
+    indices = sorted(opt_state["state"])
+    if not indices:
+        return None
+    if len(opt_state["param_groups"]) != 1 or len(opt_state["param_groups"][0]["params"]) != len(all_names):
+        raise ValueError("fit: the state file's optimizer state is not over this model's parameters")
+    step, skipped, m, v, _ = adam_moments(opt_state, len(indices), indices)
+    return {"step": step, "skipped": skipped, "names": [all_names[i] for i in indices], "exp_avg": m, "exp_avg_sq": v}
 
 
 def _fit(model, clips, epochs, out_dir, batch_size, crop, lr, weight_decay, val_itv, val, seed, start_epoch, log, val_coding, lpips,
-         lpips_weight, ffl_weight=0.0, ffl_alpha=1.0) -> List[float]:
+         lpips_weight, ffl_weight=0.0, ffl_alpha=1.0, kind="torch", max_grad_norm=None, save_state=False, state=None, run=None) -> List[float]:
     """The loop of `fit` behind its argument checks."""
     from .evaluate import evaluate_sequence
     os.makedirs(os.path.join(out_dir, "ckpt"), exist_ok=True)
     rng = np.random.default_rng(seed)
-    optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
+    on_device = kind == "device"
+    named = dict(model.named_parameters())
+
+    def device_adam(names):
+        from .optim import DeviceAdam
+        return DeviceAdam([(n, named[n]) for n in names], lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+
+    # DeviceAdam wants a gradient for every parameter it was given; the model has parameters no loss reaches (torch.optim.Adam passes
+    # them by).  So it is made over the parameters that have a gradient after the first backward, or over those the state file names.
+    optimizer = None if on_device else torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
+    if on_device:                                # what the torch path's first zero_grad() does: a stale .grad is not the first step's
+        for p in named.values():
+            p.grad = None
     averages = []
+    device = next(model.parameters()).device
+    seen = (0, 0, 0.0)                           # DeviceAdam's (step, skipped, sum of norms) at the top of the epoch
+    if state is not None:
+        model.load_state_dict(torch.load(state["weights"], map_location=device))
+        saved = _adam_state_by_name(state["optimizer"], list(named))
+        if on_device and saved is not None:
+            optimizer = device_adam(saved["names"])
+            optimizer.load_state_dict(saved)
+            seen = (saved["step"], saved["skipped"], 0.0)
+        elif not on_device and saved is not None:
+            from .optim import load_into_torch_adam
+            if state["optimizer_kind"] == "torch":
+                optimizer.load_state_dict(state["optimizer"])
+            else:
+                load_into_torch_adam(optimizer, saved, [named[n] for n in saved["names"]])
+        averages = list(state["averages"])
+        set_generator_states(rng, state["generators"], device)
+        start_epoch = state["epoch"]
     model.train()
     for epoch in range(start_epoch, epochs):
-        for group in optimizer.param_groups:
-            group["lr"] = learning_rate(lr, epoch)
+        if not on_device:
+            for group in optimizer.param_groups:
+                group["lr"] = learning_rate(lr, epoch)
+        elif optimizer is not None:
+            optimizer.lr = learning_rate(lr, epoch)
         losses, terms = [], []
         for plan in clips.epoch(batch_size, rng, crop):
-            optimizer.zero_grad()
+            if optimizer is not None:
+                optimizer.zero_grad()
             x, mvs0, mvs1, pms, rms, ufs, hr = clips.batch(plan, crop)
             sr, _ = model(x, mvs0, mvs1, pms, rms, ufs)
             loss = charbonnier(sr, hr)
@@ -110,21 +286,37 @@ def _fit(model, clips, epochs, out_dir, batch_size, crop, lr, weight_decay, val_
                 terms.append(torch.stack(parts))
             losses.append(loss.detach())
             loss.backward()
+            if optimizer is None:
+                optimizer = device_adam([n for n, p in named.items() if p.grad is not None])
+                optimizer.lr = learning_rate(lr, epoch)
             optimizer.step()
-        per_batch = torch.stack(losses).cpu().tolist()                        # the epoch's one read of the device
+        if on_device:                                                         # the same read, the optimizer's counters and norms behind the losses
+            per_batch = torch.cat([torch.stack(losses).double(), optimizer.counters.double(), optimizer.norm_sum.reshape(1)]).cpu().tolist()
+            now = (int(per_batch[-3]), int(per_batch[-2]), per_batch[-1])
+            del per_batch[-3:]
+        else:
+            per_batch = torch.stack(losses).cpu().tolist()                    # the epoch's one read of the device
         averages.append(round(sum(per_batch) / len(per_batch), 5))
         line = '[%s] Epoch: %d/%d | average epoch loss: %f' % (datetime.now().strftime("%d/%m/%Y %H:%M:%S"), epoch + 1, epochs, averages[-1])
         if terms:
             names = ['charbonnier'] + ['lpips'] * (lpips is not None) + ['ffl'] * bool(ffl_weight)
             line += ''.join(' | %s: %f' % nv for nv in zip(names, torch.stack(terms).mean(dim=0).cpu().tolist()))
+        if on_device:
+            made = now[0] - seen[0]
+            line += ' | grad norm: %f' % ((now[2] - seen[2]) / made if made else float("nan"))
+            if now[1] != seen[1]:
+                line += ' | skipped: %d' % (now[1] - seen[1])
+            seen = now
         log(line)
         if (epoch + 1) % val_itv == 0:
             torch.save(model.state_dict(), os.path.join(out_dir, "ckpt", "epoch-%d.pth" % (epoch + 1)))
-            log('Saved model. lr %f' % optimizer.param_groups[0]["lr"])
+            log('Saved model. lr %f' % learning_rate(lr, epoch))
             if val is not None:
                 model.eval()
                 with torch.no_grad():
                     r = evaluate_sequence(model, val[0], val[1], gt_dir=val[2], coding=val_coding)
                 model.train()
                 log('PSNR:%f, SSIM: %f' % (r.mean_psnr, r.mean_ssim))
+            if save_state:                # after the validation: whatever that drew from a generator is part of the state
+                write_state(state_path(out_dir, epoch + 1), optimizer, kind, epoch + 1, averages, rng, device, run)
     return averages

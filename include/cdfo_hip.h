@@ -1016,6 +1016,38 @@ int cdfo_ffl_weight(float* F, const double* pmax, int P, int N, int H, int W, fl
                     int partial_cap, float* loss, void* stream);
 int cdfo_ffl_inverse(float* F, int N, int H, int W, const float* tw_h, const float* tw_w, float* g, void* stream);
 
+/* ---- Adam on the device (adam.hip; cdfo_amd/optim.py: DeviceAdam) ----
+ * The moments of all parameters live in one fp32 buffer m and one fp32 buffer v of `total` elements each (16-byte aligned, total a
+ * multiple of 4); parameters and gradients stay the caller's fp32 tensors.
+ * table:      [ntensors][4] 64-bit words (p, g, offset, n) on the device: tensor t has n elements at p, its gradient at g, and
+ *             owns [offset, offset + n) of m and v; offset is a multiple of 4.  table_host is the host copy the caller uploaded: the
+ *             entry points validate IT (a null p or g, n < 0 or above INT_MAX, an offset that is negative, not a multiple of 4 or,
+ *             in cdfo_adam_step, with offset + n > total are CDFO_EINVAL; p or g not 4-byte aligned is CDFO_EALIGN) and never read
+ *             the device table on the host.  p and g need not be 16-byte aligned: such a tensor takes a scalar path.
+ * chunks:     [nchunks][2] ints (tensor, first element) on the device: every run of at most CDFO_ADAM_CHUNK elements of every
+ *             tensor once, first a multiple of CDFO_ADAM_CHUNK (cdfo_amd/optim.py: chunk_table).  A row that lies outside its
+ *             tensor, or outside m and v, touches nothing.
+ * cdfo_grad_norm_partials: partials[c] = sum of g^2 over chunk c, products and sums in fp64, in a fixed order (adam.hip).
+ * cdfo_adam_scalars:       one workgroup adds the partials in a fixed order and writes scalars [6] (fp64): [0] norm = sqrt(sum),
+ *             [1] coef = 1 when max_norm <= 0 or norm <= max_norm, else max_norm / (norm + 1e-6), rounded to fp32, [2] step_size =
+ *             lr / (1 - beta1^step), [3] 1 / sqrt(1 - beta2^step), [4] skip = !isfinite(sum), [5] the sum of norm over the
+ *             unskipped steps so far.  counters [2] (64-bit): unless skipping, step = ++counters[0] before [2] and [3] are formed
+ *             from it; when skipping ++counters[1] and [1..3], [5] keep their values.  lr < 0 or NaN, a beta outside [0, 1) and a
+ *             NaN max_norm are CDFO_EINVAL.
+ * cdfo_adam_step:          returns at once when scalars[4] is set (p, m, v keep their bits); else per element in fp32
+ *             g' = coef g + wd p;  m += (1 - beta1)(g' - m);  v = beta2 v + (1 - beta2) g' g';  p -= step_size (m / (sqrt(v)
+ *             inv_bc2_sqrt + eps)), torch.optim.Adam's single-tensor statement (L2 weight decay, no amsgrad).  g is not written.
+ * Every entry point: a null pointer, ntensors <= 0, nchunks <= 0 are CDFO_EINVAL.  One launch each, no atomics, grids are functions
+ * of the sizes alone, equal inputs give equal bits. */
+#define CDFO_ADAM_CHUNK 4096
+int cdfo_grad_norm_partials(const long long* table_host, const long long* table, int ntensors, const int* chunks, int nchunks,
+                            double* partials, void* stream);
+int cdfo_adam_scalars(const double* partials, int nchunks, double lr, double beta1, double beta2, double max_norm,
+                      long long* counters, double* scalars, void* stream);
+int cdfo_adam_step(const long long* table_host, const long long* table, int ntensors, const int* chunks, int nchunks, float* m,
+                   float* v, long long total, const double* scalars, double beta1, double beta2, double eps, double weight_decay,
+                   void* stream);
+
 /* ---- optional per-launch HIP-event timing on the launch stream (bench.py's live roofline figures) ----------- */
 int cdfo_prof_begin(int max_records);
 int cdfo_prof_end(int* launches, double* ms, double* flops, double* bytes, int nkid);

@@ -3,6 +3,7 @@
     python tools/train.py --seq LR_DIR SIDE_DIR HR_DIR [--seq ...] --out DIR [--coding LD] [--epochs 30000] [--batch-size 20] [--crop 64]
                           [--lr 1e-4] [--weight-decay 1e-5] [--val-itv 200] [--val LR_DIR SIDE_DIR GT_DIR] [--val-coding LD] [--weights FILE.pth]
                           [--lpips MODEL|random --lpips-weight W] [--ffl-weight W [--ffl-alpha A]]
+                          [--optimizer torch|device] [--max-grad-norm X] [--deterministic] [--save-state] [--resume STATE.pth]
     python tools/train.py --synthetic S T H W --out DIR ...
 
 --coding RA trains the random-access configuration: the clip set keeps both motion lists (the mvl1 files beside mvl0) and the flow field
@@ -14,6 +15,13 @@ which says that the loop runs and nothing about quality.  --lpips-weight W is th
 
 --ffl-weight W adds the frequency term, W * sum of the batch's per-frame focal frequency loss (cdfo_amd.loss.focal_frequency_loss: the
 spectrum of sr - hr weighted by its own magnitude to the power --ffl-alpha, default 1); --crop must then be a power of two from 4 to 128.
+
+--optimizer device runs Adam on the device (cdfo_amd.optim.DeviceAdam: three launches a step, the epoch's line gains the mean gradient
+norm, a step with a non-finite gradient is skipped and counted instead of ending the run); --max-grad-norm X then clips the gradient to
+that norm.  --save-state writes ckpt/epoch-N.state.pth beside every epoch-N.pth: the optimizer's state, the generators' states, the
+averages and the run's arguments.  --resume ckpt/epoch-N.state.pth continues that run at epoch N with the weights of its sibling
+epoch-N.pth (--weights is then not used); the run-defining arguments must be those of the run that wrote it.  With --deterministic
+(or an LPIPS or FFL term) the continued run leaves the bits of the uninterrupted one.
 
 --seq names one training sequence in the layout of cdfo_amd/priors.py (every frame with its own prior files, 00000 included) and a
 directory of 8-bit grey HR frames %05d.png.  --synthetic trains on S random sequences of T frames of H x W instead
@@ -46,6 +54,11 @@ def main():
     ap.add_argument("--lpips-weight", type=float, default=0.0)
     ap.add_argument("--ffl-weight", type=float, default=0.0, help="adds --ffl-weight * the focal frequency loss to the step's loss")
     ap.add_argument("--ffl-alpha", type=float, default=1.0, help="the exponent of the spectrum weight (needs --ffl-weight)")
+    ap.add_argument("--optimizer", choices=("torch", "device"), default="torch", help="device: Adam in HIP (cdfo_amd.optim.DeviceAdam)")
+    ap.add_argument("--max-grad-norm", type=float, help="clip the gradient to this norm (needs --optimizer device)")
+    ap.add_argument("--deterministic", action="store_true", help="a reproducible run: the flow warp's adjoint adds in a fixed order")
+    ap.add_argument("--save-state", action="store_true", help="write ckpt/epoch-N.state.pth beside every checkpoint")
+    ap.add_argument("--resume", metavar="STATE.pth", help="continue the run of this state file (ckpt/epoch-N.state.pth)")
     a = ap.parse_args()
     if (a.seq is None) == (a.synthetic is None):
         ap.error("--seq LR_DIR SIDE_DIR HR_DIR (once per sequence), or --synthetic S T H W")
@@ -61,7 +74,7 @@ def main():
     lpips = None if a.lpips is None else metrics.lpips_random_params() if a.lpips == "random" else metrics.lpips_params(a.lpips)
     torch.manual_seed(a.seed)
     model = CVSR_V8(SCGs=8)
-    if a.weights:
+    if a.weights and not a.resume:
         model.load_state_dict(torch.load(a.weights, map_location="cpu"))
     model = model.cuda()
     if a.synthetic:
@@ -74,7 +87,8 @@ def main():
     print(f"{clips.coding}: {len(clips)} sequences of {clips.T} frames of {clips.H}x{clips.W} on the device")
     fit(model, clips, a.epochs, a.out, batch_size=a.batch_size, crop=a.crop, lr=a.lr, weight_decay=a.weight_decay, val_itv=a.val_itv,
         val=a.val, seed=a.seed, val_coding=a.val_coding, lpips=lpips, lpips_weight=a.lpips_weight, ffl_weight=a.ffl_weight,
-        ffl_alpha=a.ffl_alpha)
+        ffl_alpha=a.ffl_alpha, optimizer=a.optimizer, max_grad_norm=a.max_grad_norm, deterministic=a.deterministic, save_state=a.save_state,
+        resume=a.resume)
 
 
 if __name__ == "__main__":
