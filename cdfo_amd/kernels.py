@@ -2289,3 +2289,76 @@ def ffl_loss(sr: torch.Tensor, hr: torch.Tensor, alpha: float = 1.0, want_grad: 
     check(_lib.lib().cdfo_ffl_inverse(_vp(F), N, H, W, _vp(_ffl_table_on(dev, H)), _vp(_ffl_table_on(dev, W)), _vp(g), _stream()),
           "cdfo_ffl_inverse")
     return loss, g
+
+
+SSIM_LOSS_MIN, SSIM_LOSS_MS_MIN, SSIM_LOSS_MAX = 11, 176, 16384      # one window; CDFO_MSSSIM_MIN; the entry points' largest side
+SSIM_LOSS_TILE = (16, 32)                                             # rows x columns of valid positions a workgroup takes
+
+
+def ssim_loss_peak(peak, who: str) -> float:
+    """``peak`` as the double the kernels take, or a ValueError: a finite real number > 0."""
+    if isinstance(peak, bool) or not isinstance(peak, (int, float)) or not np.isfinite(peak) or peak <= 0:
+        raise ValueError(f"{who}: peak must be a finite number > 0, got {peak!r}")
+    return float(peak)
+
+
+def ssim_loss_tiles(H: int, W: int, levels: int) -> int:
+    """cdfo_ssim_loss_tiles: the tiles of all levels of an H x W frame."""
+    th, tw = SSIM_LOSS_TILE
+    return sum(-(-((H >> j) - 10) // th) * -(-((W >> j) - 10) // tw) for j in range(levels))
+
+
+def _ssim_loss_frames(sr: torch.Tensor, hr: torch.Tensor, levels: int, who: str):
+    """(N, H, W) of two dense fp32 device tensors [N,1,H,W] or [N,H,W] of one shape on one device; anything else is a ValueError."""
+    if levels not in (1, 5):
+        raise ValueError(f"{who}: 1 or 5 levels expected, got {levels!r}")
+    for name, t in (("sr", sr), ("hr", hr)):
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() not in (3, 4) or (t.dim() == 4 and t.shape[1] != 1):
+            raise ValueError(f"{who}: {name} must be a dense fp32 device tensor [N,1,H,W] or [N,H,W], got {t.dtype} {tuple(t.shape)} "
+                             f"strides {t.stride()}")
+    if sr.shape != hr.shape or sr.device != hr.device or sr.shape[0] == 0:
+        raise ValueError(f"{who}: sr and hr must have one shape with N >= 1 on one device, got {tuple(sr.shape)} and {tuple(hr.shape)}")
+    N, H, W = int(sr.shape[0]), int(sr.shape[-2]), int(sr.shape[-1])
+    lo = SSIM_LOSS_MS_MIN if levels == 5 else SSIM_LOSS_MIN
+    if min(H, W) < lo or max(H, W) > SSIM_LOSS_MAX or N > 65535:
+        raise ValueError(f"{who}: H and W must be from {lo} to {SSIM_LOSS_MAX} and N at most 65535, got N = {N}, {H} x {W}")
+    return N, H, W
+
+
+def ssim_loss(sr: torch.Tensor, hr: torch.Tensor, peak: float = 1.0, levels: int = 1, want_grad: bool = True):
+    """(loss fp32 [N], g fp32 like sr or None): ``1 - SSIM`` (``levels`` 1) or ``1 - MS-SSIM`` (5) of each frame and, with
+    ``want_grad``, its derivative by sr (the P/Q/R and adjoint passes, coarsest level first; skipped otherwise).  Launches: ``levels``
+    sums, ``levels - 1`` pools, one combine, and ``2 levels`` for the gradient.  Scratch until it returns: the pyramid of both frames
+    (8 N h_j w_j bytes per level j >= 1), the tile sums, means and coefficients, and for the gradient the three fp64 maps of the
+    largest level (24 N (H - 10)(W - 10) bytes) and the fp64 gradients of levels >= 1.  No host synchronisation."""
+    N, H, W = _ssim_loss_frames(sr, hr, levels, "ssim_loss")
+    peak = ssim_loss_peak(peak, "ssim_loss")
+    dev, lib = sr.device, _lib.lib()
+    T = ssim_loss_tiles(H, W, levels)                                        # cdfo_ssim_loss_tiles
+    partial = torch.empty((N, T, 2), dtype=torch.float64, device=dev)
+    xs, ys = [sr], [hr]
+    for j in range(levels):
+        if j:
+            h, w = H >> (j - 1), W >> (j - 1)
+            xs.append(torch.empty((N, h >> 1, w >> 1), dtype=torch.float32, device=dev))
+            ys.append(torch.empty((N, h >> 1, w >> 1), dtype=torch.float32, device=dev))
+            check(lib.cdfo_ssim_loss_pool(_vp(xs[j - 1]), _vp(ys[j - 1]), N, h, w, _vp(xs[j]), _vp(ys[j]), _stream()), "cdfo_ssim_loss_pool")
+        check(lib.cdfo_ssim_loss_level(_vp(xs[j]), _vp(ys[j]), N, H, W, levels, j, peak, _vp(partial), partial.numel(), _stream()),
+              "cdfo_ssim_loss_level")
+    means = torch.empty((N, levels, 2), dtype=torch.float64, device=dev)
+    coef = torch.empty((N, levels, 2), dtype=torch.float64, device=dev)
+    loss = torch.empty(N, dtype=torch.float32, device=dev)
+    check(lib.cdfo_ssim_loss_combine(_vp(partial), partial.numel(), N, H, W, levels, _vp(means), _vp(coef), _vp(loss), _stream()),
+          "cdfo_ssim_loss_combine")
+    if not want_grad:
+        return loss, None
+    pqr = torch.empty(3 * N * (H - 10) * (W - 10), dtype=torch.float64, device=dev)
+    g, coarse = torch.empty_like(sr), None
+    for j in range(levels - 1, -1, -1):
+        check(lib.cdfo_ssim_loss_pqr(_vp(xs[j]), _vp(ys[j]), N, H, W, levels, j, peak, _vp(coef), _vp(pqr), pqr.numel(), _stream()),
+              "cdfo_ssim_loss_pqr")
+        g64 = torch.empty((N, H >> j, W >> j), dtype=torch.float64, device=dev) if j else None
+        check(lib.cdfo_ssim_loss_adjoint(_vp(pqr), _vp(xs[j]), _vp(ys[j]), N, H, W, levels, j, _vp(coarse), _vp(g64), _vp(None if j else g),
+                                         _stream()), "cdfo_ssim_loss_adjoint")
+        coarse = g64
+    return loss, g

@@ -8,7 +8,11 @@ on the device (csrc/lpips.hip).
 
 `focal_frequency_loss` is the frequency term of the reference's ``Focal_Frequecny_Loss`` / ``Charbonnier_FFL_Loss``
 (opt/deep_learning.py:192-220), by the project's own definition written after the defaults of the package those classes call: a 2-D
-FFT in HIP, the spectrum weighted by its own magnitude, and the inverse FFT for the gradient (csrc/ffl.hip)."""
+FFT in HIP, the spectrum weighted by its own magnitude, and the inverse FFT for the gradient (csrc/ffl.hip).
+
+`ssim_loss` and `msssim_loss` are ``1 - SSIM`` and ``1 - MS-SSIM`` by the definitions the evaluators score with
+(`cdfo_amd.metrics.calculate_ssim`, `msssim_u8`) on float frames, with the exact gradient: the window as two separable passes through
+LDS in fp64, forward and adjoint (csrc/ssim_loss.hip, DESIGN.md)."""
 from __future__ import annotations
 
 import torch
@@ -151,3 +155,70 @@ def focal_frequency_loss(sr: torch.Tensor, hr: torch.Tensor, alpha: float = 1.0)
         with K.on_device(sr):
             return K.ffl_loss(sr.detach(), hr.detach(), alpha, want_grad=False)[0]
     return _FocalFrequency.apply(sr, hr, alpha)
+
+
+class _StructuralLoss(torch.autograd.Function):
+    """As `_FocalFrequency`: the forward leaves the derivative beside the loss.  Entered only when ``sr`` needs a gradient."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, peak, levels):
+        with K.on_device(sr):
+            loss, g = K.ssim_loss(sr.detach(), hr.detach(), peak, levels, want_grad=True)
+        ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (g,) = ctx.saved_tensors
+        return grad_out.view(-1, *([1] * (g.dim() - 1))) * g, None, None, None
+
+
+def _structural_loss(sr, hr, peak, levels, who):
+    if not sr.is_cuda or not hr.is_cuda:
+        raise NotImplementedError(f"{who}: the HIP path needs device tensors (there is no CPU fallback)")
+    K._ssim_loss_frames(sr, hr, levels, who)
+    peak = K.ssim_loss_peak(peak, who)
+    if not (torch.is_grad_enabled() and sr.requires_grad):                  # hr gets no gradient: nothing to record
+        with K.on_device(sr):
+            return K.ssim_loss(sr.detach(), hr.detach(), peak, levels, want_grad=False)[0]
+    return _StructuralLoss.apply(sr, hr, peak, levels)
+
+
+def ssim_loss(sr: torch.Tensor, hr: torch.Tensor, peak: float = 1.0) -> torch.Tensor:
+    """Per-frame ``1 - SSIM`` of ``sr`` to ``hr``: fp32 [N] on the device, by the project's own definition (the metric's,
+    `metrics.calculate_ssim` with ``crop_border=0, from_unit_range=False`` at ``peak = 255``).  Samples are used as they are: no scale,
+    no clamp, no quantisation, no crop border.  With the separable 11-tap Gaussian G of sigma 1.5 over valid positions only,
+    ``C1 = (0.01 peak)^2``, ``C2 = (0.03 peak)^2``, and everything behind the fp32 loads in fp64: ``m1 = G*sr``, ``m2 = G*hr``,
+    ``e11 = G*sr^2``, ``e22 = G*hr^2``, ``e12 = G*(sr hr)``, ``cs = (2 (e12 - m1 m2) + C2) / ((e11 - m1^2) + (e22 - m2^2) + C2)``,
+    ``l = (2 m1 m2 + C1) / (m1^2 + m2^2 + C1)``, ``loss = 1 - mean(l cs)`` over the (H - 10)(W - 10) positions.
+
+    ``sr``, ``hr``: dense fp32 device tensors [N,1,H,W] or [N,H,W] of one shape on one device, H, W >= 11; ``peak`` a finite number
+    > 0.  Anything else is a ValueError before any device work; nothing is made contiguous or cast; CPU tensors raise
+    NotImplementedError.  Gradient flows to ``sr`` only (``hr`` gets None) and is exact: ``Gt*P + 2 sr Gt*Q + hr Gt*R`` with P, Q, R
+    the derivatives of the mean by m1, e11, e12 and ``Gt*`` the full correlation, scaled by the upstream gradient of the frame.  Sums
+    run in a fixed order and nothing is atomic: equal inputs give equal bits, forward and backward.  The loss is rounded to fp32 once
+    and so is every gradient element.  There is no host synchronisation.
+
+    Kept between forward and backward: the gradient, ``4 N H W`` bytes (nothing under ``no_grad`` or when ``sr`` needs no gradient:
+    the gradient passes are then not launched).  The forward also holds, until it returns, the tile sums, means and coefficients (fp64,
+    ``N (2 T + 4)`` values for T tiles of 16 x 32 positions) and, for the gradient, three fp64 maps, ``24 N (H - 10)(W - 10)`` bytes."""
+    return _structural_loss(sr, hr, peak, 1, "ssim_loss")
+
+
+def msssim_loss(sr: torch.Tensor, hr: torch.Tensor, peak: float = 1.0) -> torch.Tensor:
+    """Per-frame ``1 - MS-SSIM`` of ``sr`` to ``hr`` over five scales: fp32 [N] on the device, by the project's own definition
+    (`metrics.msssim_u8`'s on float frames).  Level j + 1 is the 2 x 2 non-overlapping mean of level j from the top-left
+    sample, a trailing odd row or column dropped, held in fp32: a sample is ``fp32(((a + b) + c) + d in fp64, times 0.25)``.  With
+    `ssim_loss`'s cs and l per level, ``M_cs[j] = mean(cs)``, ``M_ssim[j] = mean(l cs)`` and `metrics.MSSSIM_WEIGHTS` w:
+    ``loss = 1 - prod_{j<4} max(M_cs[j], 0)^w[j] max(M_ssim[4], 0)^w[4]``.  If any of those five means is <= 0 the loss is exactly 1 and
+    the frame's gradient exactly zero.
+
+    Arguments, errors and reproducibility as `ssim_loss`, with ``min(H, W) >= metrics.msssim_min_size`` (176).  The gradient is exact
+    with the pool's rounding taken as the identity: a coarser level's gradient reaches each of a sample's four parents as a quarter of
+    its value, a dropped row or column gets none; levels above 0 keep theirs in fp64, so an element is rounded once.
+
+    Kept between forward and backward: the gradient, ``4 N H W`` bytes (nothing when none is wanted).  The forward also holds, until it
+    returns, levels 1 .. 4 of both frames (``8 N sum_j h_j w_j`` bytes, about ``2.7 N H W``), the tile sums, means and coefficients,
+    and for the gradient three fp64 maps of level 0's size (``24 N (H - 10)(W - 10)`` bytes) and up to two fp64 level gradients
+    (``8 N h_j w_j`` bytes each, j >= 1)."""
+    return _structural_loss(sr, hr, peak, 5, "msssim_loss")

@@ -2,7 +2,8 @@
 each, cdfo_amd/train_data.py), the loss is `cdfo_amd.loss.charbonnier` (one pass, no ``.item()``), forward and backward are the HIP
 autograd path of ``CVSR_V8``.  The losses of an epoch stay on the device and are read once, for the reference's log line.
 With an LPIPS model the step's loss gains a perceptual term, `cdfo_amd.loss.lpips_loss`, the pairing opt/loss.py has with opt/lpips;
-with an ``ffl_weight`` it gains a frequency term, `cdfo_amd.loss.focal_frequency_loss` (opt/deep_learning.py's Charbonnier_FFL_Loss)."""
+with an ``ffl_weight`` it gains a frequency term, `cdfo_amd.loss.focal_frequency_loss` (opt/deep_learning.py's Charbonnier_FFL_Loss);
+with an ``ssim_weight`` a structural one, `cdfo_amd.loss.ssim_loss` or `msssim_loss`, the figures the evaluators score with."""
 from __future__ import annotations
 
 import contextlib
@@ -15,7 +16,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .loss import charbonnier, focal_frequency_loss, lpips_loss
+from .loss import charbonnier, focal_frequency_loss, lpips_loss, msssim_loss, ssim_loss
 from .train_data import ClipSet
 
 MILESTONE, GAMMA = 2000, 0.5
@@ -31,7 +32,7 @@ def fit(model, clips: ClipSet, epochs: int, out_dir: str, batch_size: int = 20, 
         weight_decay: float = 1e-5, val_itv: int = 200, val: Optional[Sequence[str]] = None, seed: int = 4, start_epoch: int = 0,
         log: Callable[[str], None] = print, val_coding: str = "LD", lpips=None, lpips_weight: float = 0.0, ffl_weight: float = 0.0,
         ffl_alpha: float = 1.0, optimizer: str = "torch", max_grad_norm: Optional[float] = None, deterministic: bool = False,
-        save_state: bool = False, resume: Optional[str] = None) -> List[float]:
+        save_state: bool = False, resume: Optional[str] = None, ssim_weight: float = 0.0, ssim_scales: int = 1) -> List[float]:
     """Train ``model`` (a ``CVSR_V8`` on the clip set's device) for epochs ``start_epoch .. epochs - 1``; returns the epochs' average
     losses.  Adam with ``lr`` and ``weight_decay``; the rate of each epoch is set directly (`learning_rate`).  Every ``val_itv`` epochs
     ``state_dict()`` goes to ``<out_dir>/ckpt/epoch-N.pth`` and, with ``val = (lr_dir, side_dir, gt_dir)``, that sequence is evaluated
@@ -62,7 +63,14 @@ def fit(model, clips: ClipSet, epochs: int, out_dir: str, batch_size: int = 20, 
     everything above is restored and the run continues at epoch N (``start_epoch`` stays 0), bit for bit when the run is
     reproducible (``deterministic`` or a loss term that sets it).  A state of either optimizer continues on the other.  A state file
     whose run-defining arguments differ from the call's (the first difference is named), a missing sibling and ``epochs <= N`` are
-    ValueErrors before the first batch.  Without these keywords nothing changes."""
+    ValueErrors before the first batch.  Without these keywords nothing changes.
+    ``ssim_weight``: a finite positive weight adds ``ssim_weight * ssim_loss(sr, hr).sum()`` (``ssim_scales = 1``) or ``ssim_weight *
+    msssim_loss(sr, hr).sum()`` (``ssim_scales = 5``) to the step's loss, after the FFL term when both are on; averages and the logged
+    loss are the total, and the line gains `` | ssim: %f`` or `` | msssim: %f`` (unweighted) behind the other terms.  The run is
+    reproducible as the LPIPS run is (`autograd.FLOW_WARP_FIXED`).  A negative, non-finite or bool weight, ``ssim_scales`` outside
+    {1, 5}, five scales without a weight, ``crop < 3`` for one scale (the HR crop ``4 crop`` is then below the 11-tap window) and
+    ``crop < 44`` for five (below `metrics.msssim_min_size`) are ValueErrors before the first batch.  A state file written before
+    these keywords existed reads as ``ssim_weight = 0.0, ssim_scales = 1``.  With ``ssim_weight = 0.0`` nothing changes."""
     from .streaming import check_coding
     check_coding(val_coding)
     if lpips is None:
@@ -84,6 +92,18 @@ def fit(model, clips: ClipSet, epochs: int, out_dir: str, batch_size: int = 20, 
             raise ValueError(f"fit: ffl_weight needs a crop that is a power of two from 4 to 128 (HR 16 .. 512), got crop = {crop!r}")
     elif isinstance(ffl_alpha, bool) or ffl_alpha != 1.0:
         raise ValueError(f"fit: ffl_alpha {ffl_alpha!r} needs an ffl_weight")
+    if isinstance(ssim_weight, bool) or not isinstance(ssim_weight, (int, float)) or not math.isfinite(ssim_weight) or ssim_weight < 0:
+        raise ValueError(f"fit: ssim_weight must be a finite number >= 0, got {ssim_weight!r}")
+    if isinstance(ssim_scales, bool) or ssim_scales not in (1, 5):
+        raise ValueError(f"fit: ssim_scales must be 1 or 5, got {ssim_scales!r}")
+    if ssim_weight:
+        need = 3 if ssim_scales == 1 else 44
+        if isinstance(crop, bool) or not isinstance(crop, int) or crop < need:
+            raise ValueError(f"fit: ssim_weight with ssim_scales = {ssim_scales} needs crop >= {need} (an HR crop of at least "
+                             f"{11 if ssim_scales == 1 else 176} samples each way), got crop = {crop!r}")
+    elif ssim_scales != 1:
+        raise ValueError(f"fit: ssim_scales {ssim_scales!r} needs an ssim_weight")
+    ssim_scales = int(ssim_scales)
     if optimizer not in ("torch", "device"):
         raise ValueError(f"fit: optimizer must be 'torch' or 'device', got {optimizer!r}")
     if max_grad_norm is not None:
@@ -93,16 +113,18 @@ def fit(model, clips: ClipSet, epochs: int, out_dir: str, batch_size: int = 20, 
             raise ValueError("fit: max_grad_norm needs optimizer='device'")
     if not lpips_weight:
         lpips_weight = 0.0
-    run = run_arguments(batch_size, crop, lr, weight_decay, seed, clips.coding, lpips_weight, float(ffl_weight), ffl_alpha, max_grad_norm)
+    run = run_arguments(batch_size, crop, lr, weight_decay, seed, clips.coding, lpips_weight, float(ffl_weight), ffl_alpha, max_grad_norm,
+                        ssim_weight=float(ssim_weight), ssim_scales=ssim_scales)
     state = None
     if resume is not None:
         if start_epoch != 0:
             raise ValueError(f"fit: resume continues at the state file's epoch; start_epoch must stay 0, got {start_epoch!r}")
         state = read_state(resume, run, epochs)
     # two runs from one seed then leave equal weights: the warp's adjoint adds in a fixed-point order
-    with _flow_warp_fixed(bool(deterministic) or lpips is not None or bool(ffl_weight)):
+    with _flow_warp_fixed(bool(deterministic) or lpips is not None or bool(ffl_weight) or bool(ssim_weight)):
         return _fit(model, clips, epochs, out_dir, batch_size, crop, lr, weight_decay, val_itv, val, seed, start_epoch, log, val_coding,
-                    lpips, lpips_weight, float(ffl_weight), ffl_alpha, optimizer, max_grad_norm, bool(save_state), state, run)
+                    lpips, lpips_weight, float(ffl_weight), ffl_alpha, optimizer, max_grad_norm, bool(save_state), state, run,
+                    float(ssim_weight), ssim_scales)
 
 
 @contextlib.contextmanager
@@ -121,21 +143,29 @@ def _flow_warp_fixed(on: bool):
 
 # ---- the state file: what a run needs, beside its weights, to continue bit for bit -------------------------------------------------
 
-RUN_ARGUMENTS = ("batch_size", "crop", "lr", "weight_decay", "seed", "coding", "lpips_weight", "ffl_weight", "ffl_alpha", "max_grad_norm")
+RUN_ARGUMENTS = ("batch_size", "crop", "lr", "weight_decay", "seed", "coding", "lpips_weight", "ffl_weight", "ffl_alpha", "max_grad_norm",
+                 "ssim_weight", "ssim_scales")
 
 
-def run_arguments(batch_size, crop, lr, weight_decay, seed, coding, lpips_weight, ffl_weight, ffl_alpha, max_grad_norm) -> dict:
+def run_arguments(batch_size, crop, lr, weight_decay, seed, coding, lpips_weight, ffl_weight, ffl_alpha, max_grad_norm,
+                  ssim_weight=0.0, ssim_scales=1) -> dict:
     """The arguments that define a run, as the state file keeps them (`RUN_ARGUMENTS`' order)."""
-    return dict(zip(RUN_ARGUMENTS, (batch_size, crop, lr, weight_decay, seed, coding, lpips_weight, ffl_weight, ffl_alpha, max_grad_norm)))
+    return dict(zip(RUN_ARGUMENTS, (batch_size, crop, lr, weight_decay, seed, coding, lpips_weight, ffl_weight, ffl_alpha, max_grad_norm,
+                                    ssim_weight, ssim_scales)))
+
+
+_ARGUMENT_DEFAULTS = {"ssim_weight": 0.0, "ssim_scales": 1}       # names a state file written before they existed does not record
 
 
 def check_run_arguments(saved: dict, current: dict, path: str = "the state file") -> None:
-    """ValueError naming the first of `RUN_ARGUMENTS` in which the state file's run differs from the call's."""
+    """ValueError naming the first of `RUN_ARGUMENTS` in which the state file's run differs from the call's.  A file that lacks
+    ``ssim_weight`` / ``ssim_scales`` was written by a run without the term: they read as 0.0 and 1."""
     for name in RUN_ARGUMENTS:
-        if name not in saved:
+        if name not in saved and name not in _ARGUMENT_DEFAULTS:
             raise ValueError(f"fit: {path} does not record {name}")
-        if saved[name] != current[name] or (saved[name] is None) != (current[name] is None):
-            raise ValueError(f"fit: {path} was written by a run with {name} = {saved[name]!r}, this call has {name} = {current[name]!r}")
+        was = saved[name] if name in saved else _ARGUMENT_DEFAULTS[name]
+        if was != current[name] or (was is None) != (current[name] is None):
+            raise ValueError(f"fit: {path} was written by a run with {name} = {was!r}, this call has {name} = {current[name]!r}")
 
 
 def _plain(x):
@@ -181,7 +211,10 @@ def weights_beside(path: str) -> str:
 
 
 def write_state(path: str, optimizer, kind: str, epoch: int, averages, rng, device, run: dict) -> None:
+    """A run without a structural term writes the file it always wrote: a name of `_ARGUMENT_DEFAULTS` at its default is left out
+    (`check_run_arguments` reads its absence as that default)."""
     opt = optimizer.state_dict()
+    run = {k: v for k, v in run.items() if k not in _ARGUMENT_DEFAULTS or v != _ARGUMENT_DEFAULTS[k]}
     torch.save({"optimizer": _plain(opt), "optimizer_kind": kind, "epoch": int(epoch), "averages": [float(a) for a in averages],
                 "generators": generator_states(rng, device), "run": _plain(dict(run))}, path)
 
@@ -222,7 +255,8 @@ def _adam_state_by_name(opt_state: dict, all_names: List[str]):
 
 
 def _fit(model, clips, epochs, out_dir, batch_size, crop, lr, weight_decay, val_itv, val, seed, start_epoch, log, val_coding, lpips,
-         lpips_weight, ffl_weight=0.0, ffl_alpha=1.0, kind="torch", max_grad_norm=None, save_state=False, state=None, run=None) -> List[float]:
+         lpips_weight, ffl_weight=0.0, ffl_alpha=1.0, kind="torch", max_grad_norm=None, save_state=False, state=None, run=None,
+         ssim_weight=0.0, ssim_scales=1) -> List[float]:
     """The loop of `fit` behind its argument checks."""
     from .evaluate import evaluate_sequence
     os.makedirs(os.path.join(out_dir, "ckpt"), exist_ok=True)
@@ -273,7 +307,7 @@ def _fit(model, clips, epochs, out_dir, batch_size, crop, lr, weight_decay, val_
             x, mvs0, mvs1, pms, rms, ufs, hr = clips.batch(plan, crop)
             sr, _ = model(x, mvs0, mvs1, pms, rms, ufs)
             loss = charbonnier(sr, hr)
-            if lpips is not None or ffl_weight:
+            if lpips is not None or ffl_weight or ssim_weight:
                 parts = [loss.detach()]
                 if lpips is not None:
                     perc = lpips_loss(sr, hr, lpips).sum()
@@ -283,6 +317,10 @@ def _fit(model, clips, epochs, out_dir, batch_size, crop, lr, weight_decay, val_
                     freq = focal_frequency_loss(sr, hr, ffl_alpha).sum()
                     loss = loss + ffl_weight * freq
                     parts.append(freq.detach())
+                if ssim_weight:
+                    struct = (ssim_loss if ssim_scales == 1 else msssim_loss)(sr, hr).sum()
+                    loss = loss + ssim_weight * struct
+                    parts.append(struct.detach())
                 terms.append(torch.stack(parts))
             losses.append(loss.detach())
             loss.backward()
@@ -299,7 +337,7 @@ def _fit(model, clips, epochs, out_dir, batch_size, crop, lr, weight_decay, val_
         averages.append(round(sum(per_batch) / len(per_batch), 5))
         line = '[%s] Epoch: %d/%d | average epoch loss: %f' % (datetime.now().strftime("%d/%m/%Y %H:%M:%S"), epoch + 1, epochs, averages[-1])
         if terms:
-            names = ['charbonnier'] + ['lpips'] * (lpips is not None) + ['ffl'] * bool(ffl_weight)
+            names = ['charbonnier'] + ['lpips'] * (lpips is not None) + ['ffl'] * bool(ffl_weight) + ['ssim' if ssim_scales == 1 else 'msssim'] * bool(ssim_weight)
             line += ''.join(' | %s: %f' % nv for nv in zip(names, torch.stack(terms).mean(dim=0).cpu().tolist()))
         if on_device:
             made = now[0] - seen[0]

@@ -1048,6 +1048,42 @@ int cdfo_adam_step(const long long* table_host, const long long* table, int nten
                    float* v, long long total, const double* scalars, double beta1, double beta2, double eps, double weight_decay,
                    void* stream);
 
+/* ---- SSIM and MS-SSIM as training losses (ssim_loss.hip; cdfo_amd/loss.py: ssim_loss, msssim_loss) ----
+ * A frame is dense fp32 [H][W], a stack [N][H][W], 1 <= N <= 65535.  `levels` is 1 (SSIM: H, W >= 11) or 5 (MS-SSIM: H, W >=
+ * CDFO_MSSSIM_MIN); H, W <= 16384 are the sizes of LEVEL 0 in every call; level j is (H >> j) x (W >> j), and x, y of a call with
+ * `level` are that level's stacks.  peak: finite and > 0; C1 = (0.01 peak)^2, C2 = (0.03 peak)^2 in fp64.  Per valid position of a
+ * level, with the 11-tap Gaussian of cdfo_metric_partials, behind the fp32 loads in fp64: m1 = G*x, m2 = G*y, e11 = G*x^2, e22 =
+ * G*y^2, e12 = G*xy, cs = (2 (e12 - m1 m2) + C2) / ((e11 - m1^2) + (e22 - m2^2) + C2), l = (2 m1 m2 + C1) / (m1^2 + m2^2 + C1).
+ * Every entry point checks its arguments before any HIP call: a null pointer, N, H, W, levels, level or peak outside the above and a
+ * capacity that is too small are CDFO_EINVAL, a misaligned pointer (4 bytes for fp32, 8 for fp64) CDFO_EALIGN.
+ * cdfo_ssim_loss_tiles:   T(H, W, levels), the tiles of 16 x 32 valid positions of all levels of a frame; no launch.
+ * cdfo_ssim_loss_level:   partial [N][T][2] fp64 (partial_cap >= 2 N T doubles): the level's tiles, behind those of the levels before
+ *                         it, get (sum cs, sum l cs) over the tile, added in a fixed order.  One launch.
+ * cdfo_ssim_loss_pool:    x, y [N][h][w] (h, w >= 22) -> xn, yn [N][h / 2][w / 2]: fp32(((a + b) + c) + d in fp64, times 0.25) of the
+ *                         2 x 2 block from the top-left sample; a trailing odd row or column is dropped.  One launch.
+ * cdfo_ssim_loss_combine: partial (every level written) -> means [N][levels][2] = (M_cs, M_ssim), the tiles added in index order;
+ *                         loss [N] fp32 = 1 - M_ssim[0] (levels 1) or 1 - prod_{j<4} M_cs[j]^w[j] M_ssim[4]^w[4], rounded once;
+ *                         coef [N][levels][2] = (d loss / d M_cs[j], d loss / d M_ssim[j]).  If any of the five means used is <= 0
+ *                         the loss is exactly 1 and the frame's coefficients are 0.  One launch.
+ * cdfo_ssim_loss_pqr:     pqr [N][3][h - 10][w - 10] fp64 (pqr_cap doubles) of the level: P = d/d m1, Q = d/d e11, R = d/d e12 of
+ *                         (coef[n][level][0] sum cs + coef[n][level][1] sum l cs) / ((h - 10)(w - 10)).  One launch.
+ * cdfo_ssim_loss_adjoint: the level's gradient by x: (Gt*P + 2 x Gt*Q) + y Gt*R, Gt* the full correlation (the adjoint of the valid
+ *                         one), plus, for level < levels - 1, a quarter of coarse [N][h / 2][w / 2] (the next level's gradient,
+ *                         fp64, required) at (row / 2, column / 2) where that exists.  Level 0 writes g32 [N][H][W], rounded once;
+ *                         a level above 0 writes g64 [N][h][w].  The pointer the level does not use is ignored.  One launch.
+ * No atomics, grids are functions of (N, H, W) alone, equal inputs give equal bits.  Every element of every output is written. */
+#define CDFO_MSSSIM_MIN 176
+int cdfo_ssim_loss_tiles(int H, int W, int levels);
+int cdfo_ssim_loss_level(const float* x, const float* y, int N, int H, int W, int levels, int level, double peak, double* partial,
+                         long long partial_cap, void* stream);
+int cdfo_ssim_loss_pool(const float* x, const float* y, int N, int h, int w, float* xn, float* yn, void* stream);
+int cdfo_ssim_loss_combine(const double* partial, long long partial_cap, int N, int H, int W, int levels, double* means, double* coef,
+                           float* loss, void* stream);
+int cdfo_ssim_loss_pqr(const float* x, const float* y, int N, int H, int W, int levels, int level, double peak, const double* coef,
+                       double* pqr, long long pqr_cap, void* stream);
+int cdfo_ssim_loss_adjoint(const double* pqr, const float* x, const float* y, int N, int H, int W, int levels, int level,
+                           const double* coarse, double* g64, float* g32, void* stream);
+
 /* ---- optional per-launch HIP-event timing on the launch stream (bench.py's live roofline figures) ----------- */
 int cdfo_prof_begin(int max_records);
 int cdfo_prof_end(int* launches, double* ms, double* flops, double* bytes, int nkid);

@@ -3,6 +3,7 @@
     python tools/train.py --seq LR_DIR SIDE_DIR HR_DIR [--seq ...] --out DIR [--coding LD] [--epochs 30000] [--batch-size 20] [--crop 64]
                           [--lr 1e-4] [--weight-decay 1e-5] [--val-itv 200] [--val LR_DIR SIDE_DIR GT_DIR] [--val-coding LD] [--weights FILE.pth]
                           [--lpips MODEL|random --lpips-weight W] [--ffl-weight W [--ffl-alpha A]]
+                          [--ssim-weight W [--ssim-scales 1|5]]
                           [--optimizer torch|device] [--max-grad-norm X] [--deterministic] [--save-state] [--resume STATE.pth]
     python tools/train.py --synthetic S T H W --out DIR ...
 
@@ -15,6 +16,9 @@ which says that the loop runs and nothing about quality.  --lpips-weight W is th
 
 --ffl-weight W adds the frequency term, W * sum of the batch's per-frame focal frequency loss (cdfo_amd.loss.focal_frequency_loss: the
 spectrum of sr - hr weighted by its own magnitude to the power --ffl-alpha, default 1); --crop must then be a power of two from 4 to 128.
+
+--ssim-weight W adds the structural term, W * sum of the batch's per-frame 1 - SSIM (cdfo_amd.loss.ssim_loss; --crop >= 3) or, with
+--ssim-scales 5, 1 - MS-SSIM over five scales (cdfo_amd.loss.msssim_loss; --crop >= 44: the HR crop must hold 176 samples each way).
 
 --optimizer device runs Adam on the device (cdfo_amd.optim.DeviceAdam: three launches a step, the epoch's line gains the mean gradient
 norm, a step with a non-finite gradient is skipped and counted instead of ending the run); --max-grad-norm X then clips the gradient to
@@ -54,6 +58,8 @@ def main():
     ap.add_argument("--lpips-weight", type=float, default=0.0)
     ap.add_argument("--ffl-weight", type=float, default=0.0, help="adds --ffl-weight * the focal frequency loss to the step's loss")
     ap.add_argument("--ffl-alpha", type=float, default=1.0, help="the exponent of the spectrum weight (needs --ffl-weight)")
+    ap.add_argument("--ssim-weight", type=float, default=0.0, help="adds --ssim-weight * (1 - SSIM) of every frame to the step's loss")
+    ap.add_argument("--ssim-scales", type=int, choices=(1, 5), default=1, help="5: 1 - MS-SSIM instead (needs --ssim-weight)")
     ap.add_argument("--optimizer", choices=("torch", "device"), default="torch", help="device: Adam in HIP (cdfo_amd.optim.DeviceAdam)")
     ap.add_argument("--max-grad-norm", type=float, help="clip the gradient to this norm (needs --optimizer device)")
     ap.add_argument("--deterministic", action="store_true", help="a reproducible run: the flow warp's adjoint adds in a fixed order")
@@ -88,7 +94,7 @@ def main():
     fit(model, clips, a.epochs, a.out, batch_size=a.batch_size, crop=a.crop, lr=a.lr, weight_decay=a.weight_decay, val_itv=a.val_itv,
         val=a.val, seed=a.seed, val_coding=a.val_coding, lpips=lpips, lpips_weight=a.lpips_weight, ffl_weight=a.ffl_weight,
         ffl_alpha=a.ffl_alpha, optimizer=a.optimizer, max_grad_norm=a.max_grad_norm, deterministic=a.deterministic, save_state=a.save_state,
-        resume=a.resume)
+        resume=a.resume, ssim_weight=a.ssim_weight, ssim_scales=a.ssim_scales)
 
 
 if __name__ == "__main__":
